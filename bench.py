@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the LRBMS offline hot path (project + estimate-offline: K7 + K8 + P1 + P2 of SURVEY.md section 8).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2] [--no-cpu-baseline] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over all subdomains of the synthetic multiscale-diffusion problem
 (BASELINE.json config 3: 32x32 subdomains, local basis dim 40, fp64): Oswald image bases, RT0 flux-reconstruction
@@ -10,6 +10,10 @@ operators, bases) are resident in HBM before the timed region.  For N > 1 the su
 (strong scaling, as BASELINE.json config 4) and every step starts with the halo all-gather of neighbour basis rows.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+
+--dump-outputs DIR writes what the last timed step computed (the arrays `project_and_estimate` hands its caller, named as in
+include/lrbms_hip.h) to DIR/<name>.npy in fp64: two builds run with the same arguments get the same inputs and can be compared
+output for output.  Arrays over DUMP_BYTES in all are cut to one seeded sample of subdomains (dump_outputs).
 """
 import argparse
 import json
@@ -219,6 +223,34 @@ def load_pmc_traffic(config):
     return stale
 
 
+DUMP_BYTES = 60 << 20          # under 64 MB (10^6 bytes too) with the .npy headers
+DUMP_NAMES = {
+    'sys': ('B_sys', 'rhs_red', 'E_red', 'M_red'),
+    8: ('G_nc_self', 'r_fd', 'G_rdd_self', 'G_bb_self', 'G_ab_self', 'G_aa', 'F_side', 'F_nc'),     # factored layout
+    6: ('G_nc', 'r_fd', 'G_rdd', 'G_bb', 'G_ab', 'G_aa'),                                         # dense layout
+}
+DUMP_S_AXIS = {'B_sys': 1, 'G_ab_self': 1, 'G_ab': 1, 'G_aa': 2}     # the subdomain axis, where it is not the first
+
+
+def dump_outputs(dirname, buf, S, seed=0):
+    """Write the outputs of a pass (``buf['sys']`` and ``buf['grams']``, in their C-ABI names) as DIR/<name>.npy, fp64.  When
+    they exceed DUMP_BYTES together (480 MB at config 3), every array keeps the rows of the same subdomains: a sample drawn
+    with a fixed seed, ascending, that only depends on S.  Returns what was written."""
+    import torch
+    arrays = list(zip(DUMP_NAMES['sys'], buf['sys'])) + list(zip(DUMP_NAMES[len(buf['grams'])], buf['grams']))
+    per_subdomain = sum(v.numel() * 8 for _, v in arrays) // S
+    keep = min(S, DUMP_BYTES // per_subdomain)
+    rows = np.sort(np.random.default_rng(seed).choice(S, size=keep, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    written = 0
+    for name, v in arrays:
+        idx = torch.as_tensor(rows, device=v.device)
+        part = v.index_select(DUMP_S_AXIS.get(name, 0), idx).to(torch.float64).cpu().numpy()
+        np.save(os.path.join(dirname, name + '.npy'), part)
+        written += part.nbytes
+    return {'dir': dirname, 'arrays': [n for n, _ in arrays], 'subdomains': int(keep), 'of': int(S), 'bytes': int(written)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -232,7 +264,16 @@ def main():
                     help='launch-policy option of the 2D context (NativeContext.OPTIONS), e.g. --opt streams=0; measurement only')
     ap.add_argument('--opt3', action='append', default=[], metavar='NAME=VALUE',
                     help='the same for the 3D context (Native3DContext.OPTIONS), e.g. --opt3 serial=1')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the outputs of the last timed step as DIR/<name>.npy (fp64, at most 64 MB: a seeded sample of '
+                         'subdomains; rank 0 writes its own rows; 2D configurations)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
+    if args.dump_outputs and args.config.startswith('cfg5'):
+        ap.error('--dump-outputs covers the 2D configurations')
     opts = {k: int(v) for k, v in (o.split('=') for o in args.opt)}
     opts3 = {k: int(v) for k, v in (o.split('=') for o in args.opt3)}
 
@@ -375,6 +416,8 @@ def main():
     if world > 1:
         dist.all_reduce(cs, op=dist.ReduceOp.SUM)
     output_checksum, output_abs_checksum = float(cs[0]), float(cs[1])
+    # before anything below writes into `buf` again
+    dumped = dump_outputs(args.dump_outputs, buf, eng.S) if args.dump_outputs and rank == 0 else None
 
     # the dense (fp64-MFMA) kernels of the pass on their own: phase 4 = k_f1, k_f2, k_f3 (HIP events on the launch stream)
     dense_ms = None
@@ -643,6 +686,8 @@ def main():
                'timed_region': 'W warm-up + exactly K timed passes between barrier + synchronize, at steady device clocks: the untimed '
                                'per-kernel timing leg (>= 30 passes of the same step) runs in front of it -- after an idle period the '
                                'first ~25 passes run up to 10 % slower (tools/ramp_time.py)'}
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
         out['assemble'] = {'metric': 'offline assembly K1-K6, K9 (+ flux coefficients)', 'ms': assemble_ms,
                            'value': eng.S / (1e-3 * assemble_ms), 'unit': 'subdomains/s (this rank)'}
         if online is not None:
