@@ -6,7 +6,11 @@ and ``solve`` loop.  The enrichment step differs in how it is executed, not in w
 solved by ONE kernel launch (one workgroup per marked neighbourhood, ``lrbms_local_correction_solve``) and the bases
 are extended by one masked Gram-Schmidt step, then ``reductor.reduce(touched=marked)`` re-runs the fused project+estimate pass
 over the marked subdomains and their neighbours only (pylrbms_amd/reductor.py: incremental re-projection)."""
+import inspect
+
 import numpy as np
+
+MAX_BASIS_SIZE = 64      # the widest local basis the reduced solvers take (lrbms_reduced_solve: N <= 64)
 
 
 def doerfler_marking(indicators, theta):
@@ -36,6 +40,7 @@ class AdaptiveEnrichment:
         self.target_error = target_error
         self.marking_doerfler_theta = marking_doerfler_theta
         self.marking_max_age = marking_max_age
+        self._incremental = 'touched' in inspect.signature(reductor.reduce).parameters
 
     def _global_indicators(self, indicators):
         """Sharded discretization: the marking is global, so every rank needs the indicators of all subdomains (one
@@ -59,7 +64,11 @@ class AdaptiveEnrichment:
             marked_subdomains.add(ii)
         mine = sorted(ii for ii in marked_subdomains if ii in set(self.discretization.engine.local))   # this rank's share
         if getattr(self, '_reserve', 0) and hasattr(self.reductor, 'reserve'):
-            self.reductor.reserve(self.reductor.basis_size() + self._reserve)      # (every rank: the widths agree in reduce())
+            # room for this loop's vectors behind the widest REAL basis: the slab grows only when its free columns do not suffice
+            # (each rank decides for its own subdomains; reduce() pads every rank to the widest slab)
+            need = max(self.reductor.local_sizes(), default=0) + self._reserve
+            if need > self.reductor.basis_size():
+                self.reductor.reserve(min(need, MAX_BASIS_SIZE))
             self._reserve = 0
         if hasattr(self.reductor, 'enrich_local_batch'):
             self.reductor.enrich_local_batch(mine, U, mu)
@@ -68,9 +77,9 @@ class AdaptiveEnrichment:
                 self.reductor.enrich_local(ii, U, mu)
         # re-projection (online_enrichment.py:52 calls reductor.reduce()): only the marked subdomains' bases changed, so only they
         # and their neighbours are projected again -- into the arrays of self.rd -- unless the basis slab had to grow
-        try:
+        if self._incremental:
             self.rd = self.reductor.reduce(touched=sorted(marked_subdomains))
-        except TypeError:                                     # a reductor without the incremental form
+        else:                                                 # a reductor without the incremental form
             self.rd = self.reductor.reduce()
         for ii in range(self.block_space.num_blocks):
             age_count[ii] = 1 if ii in marked_subdomains else age_count[ii] + 1

@@ -34,6 +34,27 @@ def theta_of(p, mu):
     return np.array([c.evaluate(mu) for c in p['lambda']['coefficients']])
 
 
+def problem_with_q_components(shape, kc, Q, seed=7):
+    """The multiscale problem (grid, template, kappa, f of multiscale_problem) with ``Q`` affine diffusion components:
+    lambda_q = exp(0.5 g_q), g_q seeded per fine element (piecewise constant: no quadrature-point ties at block edges),
+    theta_q(mu) = mu['diffusion'][q], mu_bar = mu_hat = (1, ..., 1), so lambda_bar = lambda_hat = sum_q lambda_q."""
+    from pylrbms_amd import multiscale_problem
+    from pylrbms_amd.functions import ElementwiseFunction, SumFunction
+    from pylrbms_amd.parameters import ProjectionParameterFunctional
+    p = multiscale_problem.init_grid_and_problem({'num_subdomains': list(shape), 'coarse_per_subdomain': kc})
+    Kx, Ky = p['grid'].K
+    rng = np.random.default_rng(seed)
+    funcs = [ElementwiseFunction(np.exp(0.5 * rng.standard_normal((Ky, Kx, 8))), name='lambda_{}'.format(q)) for q in range(Q)]
+    p['lambda'] = {'functions': funcs,
+                   'coefficients': [ProjectionParameterFunctional('diffusion', (Q,), (q,)) for q in range(Q)]}
+    p['parameter_type'] = {'diffusion': (Q,)}
+    p['mu_bar'] = p['mu_hat'] = (1.0,) * Q
+    p['mu_min'], p['mu_max'] = (0.1,) * Q, (1.0,) * Q
+    p['lambda_bar'] = SumFunction(funcs, [1.0] * Q, name='lambda_bar')
+    p['lambda_hat'] = SumFunction(funcs, [1.0] * Q, name='lambda_hat')
+    return p
+
+
 def make_bases(S, n, N, seed=0):
     """Constant + (N-1) seeded random columns per subdomain, NOT orthonormalised."""
     V = np.empty((S, n, N))
@@ -53,6 +74,24 @@ def energy_orthonormalize(V, d_oracle):
         L = np.linalg.cholesky(G)
         out[ii] = np.linalg.solve(L, V[ii].T).T
     return out
+
+
+def ragged_padded_bases(d_oracle, N, seed=0, spread=6):
+    """Ragged local bases in a slab of width N, as ``LRBMSReductor.reserve`` leaves them: subdomain s holds sizes[s] real
+    columns (spread over max(1, N - spread) .. N, the widest always present), energy-orthonormal in the oracle's local product,
+    followed by exact zero columns.  Returns (V [S, n, N], sizes)."""
+    S, n = d_oracle.S, d_oracle.n
+    rng = np.random.default_rng(seed)
+    lo = max(1, N - spread)
+    sizes = [int(x) for x in rng.integers(lo, N + 1, size=S)]
+    sizes[int(rng.integers(S))] = N
+    V = np.zeros((S, n, N))
+    for ii in range(S):
+        X = make_bases(1, n, sizes[ii], seed=seed + 31 * ii)[0]
+        P = d_oracle.block(d_oracle.energy_product, ii, ii).toarray()
+        L = np.linalg.cholesky(X.T @ P @ X)
+        V[ii, :, :sizes[ii]] = np.linalg.solve(L, X.T).T
+    return V, sizes
 
 
 def slots_of(grid, ii):

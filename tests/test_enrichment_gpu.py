@@ -8,7 +8,7 @@ on the ragged bases the enrichment produces are compared at 1e-7."""
 import numpy as np
 import pytest
 
-from common import oracle_from_problem
+from common import energy_orthonormalize, make_bases, oracle_from_problem
 from oracle.lrbms import OracleReductor
 
 pytestmark = pytest.mark.gpu
@@ -256,3 +256,84 @@ def test_corrector_solves_on_a_sharded_discretization_match_the_single_rank_ones
                 assert np.abs(got[i] - ref[g]).max() < 1e-9 * np.abs(ref[g]).max()
                 seen.append(g)
     assert sorted(set(seen)) == list(range(whole.S))
+
+
+def _even(k):
+    return k + (k & 1)
+
+
+def _check_loop_over_many_parameters(p, d, data, reductor, mus, reserve, min_enriching):
+    """AdaptiveEnrichment.solve(mu, enrichment_steps=1) for every mu, as online_adaptive_lrbms.py:166-167 does.  After every call:
+    the slab is no wider than the widest real basis plus this call's reserve (even, at most 64); a call that leaves the width
+    unchanged re-projected incrementally, and then every array of the reduced model equals a whole pass on the same bases, bit
+    for bit.  Returns the loop, the last solution and its estimate."""
+    import torch
+    from pylrbms_amd.online_enrichment import AdaptiveEnrichment
+    eng = d.engine
+    loop = AdaptiveEnrichment(p, d, data['block_space'], reductor, reductor.reduce(), target_error=1e-12,
+                              marking_doerfler_theta=0.8, marking_max_age=2)
+    incremental = enriching = 0
+    for k, mu in enumerate(mus):
+        width, before = reductor.basis_size(), sum(reductor.local_sizes())
+        history = []
+        U, rd, _ = loop.solve(mu, enrichment_steps=1, callback=lambda rd_, U_, mu_, info: history.append(dict(info)))
+        assert len(history) == 2 and history[0]['eta'] > loop.target_error, k
+        enriching += sum(reductor.local_sizes()) > before
+        N = reductor.basis_size()
+        assert N <= min(64, _even(max(reductor.local_sizes()) + reserve)), (k, N, reductor.local_sizes())
+        if N == width:
+            assert reductor.last_reduce_info['incremental'], k
+            incremental += 1
+            fresh = eng.project_and_estimate(d._with_halo(reductor._V), eng.alloc_reduce_buffers(N))
+            for a, b in zip((rd.B_sys, rd.rhs_red, rd.E_red, rd.M_red) + tuple(rd.grams), list(fresh['sys']) + list(fresh['grams'])):
+                assert torch.equal(a, b), k
+    assert enriching >= min_enriching and incremental >= 1, (enriching, incremental)
+    return loop, U, history[-1]['eta']
+
+
+def _check_against_the_oracle(p, reductor, U, eta, mu):
+    o = oracle_from_problem(p)
+    V = [reductor.bases['domain_{}'.format(ii)].tensor[0].cpu().numpy() for ii in range(o.S)]
+    oreductor = OracleReductor(o, V)
+    ored = oreductor.reduce()
+    u_o = ored.solve(mu)
+    eta_o = ored.estimate(u_o, mu)
+    assert abs(eta - eta_o) < 1e-7 * eta_o
+    rec_o = np.stack(oreductor.reconstruct(u_o))
+    assert np.abs(reductor.reconstruct(U).data.reshape(o.S, o.n) - rec_o).max() < 1e-7 * np.abs(rec_o).max()
+
+
+def test_enrichment_loop_over_twenty_parameters():
+    """The reference's online phase (online_adaptive_lrbms.py:112-118, 166-167): OS2015 2 x 2, initial_RB_order 0, extended by the
+    solutions at mu_min and mu_max, then 20 random mu with one enrichment step each.  The slab must grow with the real bases, not
+    by the reserve on every call (which made reduce(touched=) fall back to the whole pass every time and passed N = 64 after about
+    13 parameters from config 3's width)."""
+    from pylrbms_amd.discretize_elliptic_block_swipdg import discretize
+    from pylrbms_amd.reductor import LRBMSReductor
+    p = _problem('OS2015_academic_problem', {'num_subdomains': [2, 2], 'half_num_fine_elements_per_subdomain_and_dim': 4})
+    d, data = discretize(p)
+    reductor = LRBMSReductor(d, order=0)
+    for mu in (p['mu_min'], p['mu_max']):
+        reductor.extend_basis(d.solve(mu))
+    assert reductor.local_sizes() == [3] * 4
+    mus = reductor.reduce().parameter_space.sample_randomly(20, seed=17)
+    loop, U, eta = _check_loop_over_many_parameters(p, d, data, reductor, mus, reserve=1, min_enriching=5)
+    _check_against_the_oracle(p, reductor, U, eta, mus[-1])
+
+
+def test_enrichment_loop_from_config3_width():
+    """Config 3's template and basis size (k_c = 4, N = 40) on 3 x 3 subdomains: 14 enriching parameters stay within N <= 64
+    (the reduced solvers' limit) and the final model matches the oracle on the device-built bases."""
+    from pylrbms_amd import multiscale_problem
+    from pylrbms_amd.discretize_elliptic_block_swipdg import discretize
+    from pylrbms_amd.reductor import LRBMSReductor
+    p = multiscale_problem.init_grid_and_problem({'num_subdomains': [3, 3], 'coarse_per_subdomain': 4})
+    d, data = discretize(p)
+    o = oracle_from_problem(p)
+    V0 = energy_orthonormalize(make_bases(o.S, o.n, 40, seed=23), o)
+    reductor = LRBMSReductor(d, bases={'domain_{}'.format(ii): V0[ii].T for ii in range(o.S)})
+    assert reductor.basis_size() == 40
+    mus = [(m,) for m in np.random.default_rng(29).uniform(0.1, 1.0, 14)]
+    loop, U, eta = _check_loop_over_many_parameters(p, d, data, reductor, mus, reserve=1, min_enriching=10)
+    assert 40 < reductor.basis_size() <= 64
+    _check_against_the_oracle(p, reductor, U, eta, mus[-1])

@@ -44,12 +44,11 @@ def _problems():
         # BASELINE.json config 2 geometry (k_c = 4, N = 20) on a smaller subdomain grid
         'multiscale_4x3_kc4_N20': (lambda: multiscale_problem.init_grid_and_problem(
             {'num_subdomains': [4, 3], 'coarse_per_subdomain': 4}), 20, 0.7),
-        # BASELINE.json config 3's exact kernel shapes (k_c = 4, N = 40, Q = 2: k_f1v<3,2,1,2,4>, k_prep_lds<3> with the G_nc fold,
-        # k_f2<5>, k_thin3<3>) on a 3 x 3 grid (one interior subdomain, every boundary kind) directly against the oracle
+        # BASELINE.json config 3's exact kernel shapes (k_c = 4, N = 40, Q = 2: the rank-2 projection kernel k_f1w, k_prep_lds<3> with
+        # the G_nc fold, k_f2<5>, k_thin3<3>) on a 3 x 3 grid (one interior subdomain, every boundary kind) directly against the oracle
         'multiscale_3x3_kc4_N40': (lambda: multiscale_problem.init_grid_and_problem(
             {'num_subdomains': [3, 3], 'coarse_per_subdomain': 4}), 40, 0.3),
-        # N = 34: the second instantiation of the lean projection kernel for three row tiles (k_f1v<3,2,1,2,3>: six levels of
-        # column tiles), with short packed tails of the symmetric groups (2 columns each)
+        # N = 34: the narrowest width of k_f1w (even N in 34 .. 40), with short packed tails of the symmetric groups (2 columns each)
         'multiscale_3x2_kc4_N34': (lambda: multiscale_problem.init_grid_and_problem(
             {'num_subdomains': [3, 2], 'coarse_per_subdomain': 4}), 34, 0.55),
         # the widest supported basis (N = 64, QN = 128): k_f1 needs two column slices -> its generic (runtime-Q) producer
