@@ -1421,7 +1421,8 @@ void launch_pg(const GA& a, int batch, int nw, hipStream_t st) {
   if (a.ksplit > 1) hipLaunchKernelGGL((k3_pg_combine<KIND>), dim3(batch1), dim3(256), 0, st, a);
 }
 
-// tile shapes: square (rt == ct) for everything but AB, where ct = tiles of Q N >= rt = tiles of N
+// tile shapes: square (rt == ct) for everything but AB, where ct = tiles of Q N >= rt = tiles of N (no AB (3, 4): rt = 3 means
+// N > 32, so Q = 1 and ct = rt).  tests/test_dispatch_coverage3d.py checks that every listed shape is reachable and tested.
 template <int KIND>
 int dispatch_pg(const GA& a, int batch, int rt, int ct, int nw, hipStream_t st) {
 #define PGCASE(R, C)                                 \
@@ -1430,7 +1431,7 @@ int dispatch_pg(const GA& a, int batch, int rt, int ct, int nw, hipStream_t st) 
     return 0;                                        \
   }
   if constexpr (KIND != G_AB) { PGCASE(1, 1) PGCASE(2, 2) PGCASE(3, 3) PGCASE(4, 4) }
-  if constexpr (KIND == G_AB) { PGCASE(1, 1) PGCASE(1, 2) PGCASE(1, 3) PGCASE(1, 4) PGCASE(2, 2) PGCASE(2, 3) PGCASE(2, 4) PGCASE(3, 3) PGCASE(3, 4) PGCASE(4, 4) }
+  if constexpr (KIND == G_AB) { PGCASE(1, 1) PGCASE(1, 2) PGCASE(1, 3) PGCASE(1, 4) PGCASE(2, 2) PGCASE(2, 3) PGCASE(2, 4) PGCASE(3, 3) PGCASE(4, 4) }
 #undef PGCASE
   return -1;
 }
@@ -3394,7 +3395,9 @@ int lrbms3_reduced_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t
     return LRBMS_OK;
   }
   const size_t lds = sizeof(double) * ((size_t)(7 * N + Q * N + t.nbf + t.nb) * EST_MB + 256);
-  if (lds > 64 * 1024) return fail3(ctx, LRBMS_E_INVALID, "reduced_estimate_batch: template too large for the LDS");
+  if (lds > 160 * 1024) return fail3(ctx, LRBMS_E_INVALID, "reduced_estimate_batch: template too large for the LDS");
+  if (lds > 64 * 1024)      // k_c = 4 at Q N = 64: 71 808 B
+    HIP3(ctx, hipFuncSetAttribute((const void*)k3_estimate_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   for (int m0 = 0; m0 < nmu; m0 += EST_MB) {
     TB8 th{};
     for (int m = 0; m < EST_MB && m0 + m < nmu; ++m)

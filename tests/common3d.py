@@ -161,3 +161,27 @@ def oracle_dense_blocks(p, d, rd, ii):
 
 def reduce_with_oracle(p, d, V):
     return Reductor3D(d, [V[ii] for ii in range(d.S)]).reduce()
+
+
+def problem_with_q_components3d(P, kc, Q, seed=7):
+    """A problem on the grid of ``P`` subdomains with ``Q`` smooth, distinct, positive diffusion components
+    lambda_q(x) = 1 + 0.5 sin(a_q . x + b_q) (a_q, b_q seeded per component), theta_0 = 1 and theta_q(mu) = mu^q (q >= 1), and
+    lambda_bar = lambda_hat = sum_q theta_q(mu_bar) lambda_q.  The 3D counterpart of tests/common.py:problem_with_q_components."""
+    from pylrbms_amd.grid3d import make_grid3d
+    rng = np.random.default_rng(seed)
+    A, B = rng.uniform(0.5, 3.0, size=(Q, 3)), rng.uniform(0.0, 2.0 * np.pi, size=Q)
+
+    def lam(q):
+        return lambda x: 1.0 + 0.5 * np.sin(x @ A[q] + B[q])
+
+    lams = [lam(q) for q in range(Q)]
+    thetas = [lambda mu, q=q: mu ** q for q in range(Q)]
+    mu_bar = 0.5
+    wbar = [t(mu_bar) for t in thetas]
+
+    def lbar(x):
+        return sum(w * f(x) for w, f in zip(wbar, lams))
+
+    grid = make_grid3d(num_subdomains=list(P), cubes_per_subdomain_and_dim=kc, kappa=np.eye(3))
+    return dict(name='q{}_{}'.format(Q, 'x'.join(map(str, P))), grid=grid, lambdas=lams, thetas=thetas, kappa=np.eye(3), f=_f,
+                lambda_bar=lbar, lambda_hat=lbar, mu_bar=mu_bar, mu_hat=mu_bar, N=None, mu=0.7, P=list(P), kc=kc)

@@ -286,7 +286,7 @@ def test_phased_pass_is_bit_identical_to_the_whole_pass(case):
 def test_batched_estimate_matches_single_estimates(case):
     p, d, eng, rd, out = case['p'], case['d'], case['eng'], case['rd'], case['out']
     rng = np.random.default_rng(8)
-    nmu = 11                                            # two passes of the kernel: 8 + 3
+    nmu = 11                                            # one partial chunk of k3_estimate_batch16 (16 parameters per launch)
     mus = list(rng.uniform(0.1, 1.3, size=nmu))
     U = rng.standard_normal((d.S, p['N'], nmu))
     thetas = np.stack([c3.theta_of(p, mu) for mu in mus])
