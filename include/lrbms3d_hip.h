@@ -232,6 +232,49 @@ int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const doub
 int lrbms3_fom_apply(lrbms3_ctx* ctx, int32_t Q, int32_t M, const double* theta, const double* A_diag, const double* A_cpl,
                      const double* x, double* y, void* stream);
 
+/* -- parabolic LRBMS ------------------------------------------------------------------------------------------------------ */
+/* M u' + A(mu) u = f with the block L2 product as mass (the 3D counterpart of the 2D parabolic block, include/lrbms_hip.h;
+ * reference discretize_parabolic_block_swipdg.py, estimators.py ParabolicEstimator).  The P2 DG mass matrix is
+ * element-block-diagonal: every block is the mesh table TM of the element's type, M_s^-1 is TM^-1 per element.  Every export
+ * needs S_ext == S (LRBMS_E_INVALID otherwise).
+ *
+ * lrbms3_mass_inverse_norm2   Y [S][n][L] -> out [S][L] = y^T M_s^-1 y (time residual of the estimate).  2D: lrbms_mass_inverse_norm2.
+ * lrbms3_project_mass         V [S_ext][n][N] (the first S slabs are read), 1 <= N <= 64 -> M_red [S][N][N] = V_s^T M_s V_s on the
+ *                             fp64 matrix cores; zero-padded basis columns give exact zero rows and columns. */
+int lrbms3_mass_inverse_norm2(lrbms3_ctx* ctx, int32_t L, const double* Y, double* out, void* stream);
+int lrbms3_project_mass(lrbms3_ctx* ctx, int32_t N, const double* V, double* M_red, void* stream);
+
+/* Implicit Euler (pyMOR's ImplicitEulerTimeStepper(nt)) on the full-order system, all nt steps in one call:
+ *   (M + dt A(mu)) u_{k+1} = M u_k + dt b,  k = 0 .. nt-1.
+ * The step operator (dt theta-combined blocks, TM added to the (e, e) blocks), its element-block inverses and its coarse level
+ * are built once per call; every step is a CG of lrbms3_fom_solve warm-started at u_k.  The coarse inverse that
+ * lrbms3_fom_precond_keep holds for the elliptic solves is neither used nor replaced.
+ *   theta [Q] host; U [nt+1][S][n]: U[0] = initial value (input), U[1..nt] written; work: lrbms3_fom_implicit_euler_work_size
+ *   doubles; info (host, may be NULL): {total CG iterations, worst final residual relative to |M u_k + dt b|}.
+ *   LRBMS_E_INVALID if dt <= 0 or nt < 1; LRBMS_E_NOT_CONVERGED if a step misses rtol within max_iter.
+ * 2D: lrbms_fom_implicit_euler. */
+int64_t lrbms3_fom_implicit_euler_work_size(lrbms3_ctx* ctx);
+int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, double dt, int32_t nt, const double* A_diag,
+                              const double* A_cpl, const double* b, double* work, double* U, double rtol, int32_t max_iter,
+                              double* info, void* stream);
+
+/* The reduced counterpart on the projected operators: (M_red + dt sum_q theta_q B_sys_q) u_{k+1} = M_red u_k + dt rhs_red.
+ *   B_sys [Q][S][7][N][N], rhs_red [S][N] as the pass writes them, M_red [S][N][N] (lrbms3_project_mass); U [nt+1][S][N]
+ *   (U[0] input); work: lrbms3_reduced_implicit_euler_work_size doubles; info as above.  The step operator and its inverse
+ *   diagonal blocks are built once; every step runs the block-Jacobi PCG of lrbms3_reduced_solve warm-started at u_k.
+ *   Padded unknowns (zero basis columns) stay exactly at their U[0] value.  N <= 64, Q <= 8.  2D: lrbms_reduced_implicit_euler. */
+int64_t lrbms3_reduced_implicit_euler_work_size(lrbms3_ctx* ctx, int32_t N);
+int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* theta, double dt, int32_t nt,
+                                  const double* B_sys, const double* M_red, const double* rhs_red, double* work, double* U,
+                                  double rtol, int32_t max_iter, double* info, void* stream);
+
+/* Time-stepping residual of the reduced model: dU [L][S][N] -> out [L][S] = y^T M_red[s]^-1 y, y = (sum_q theta_q B_sys_q dU_l)_s.
+ * On padded columns M_red counts as the identity (they contribute 0).  work: lrbms3_reduced_time_residual_work_size doubles.
+ * 2D: lrbms_reduced_time_residual. */
+int64_t lrbms3_reduced_time_residual_work_size(lrbms3_ctx* ctx, int32_t N);
+int lrbms3_reduced_time_residual(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t L, const double* theta, const double* B_sys,
+                                 const double* M_red, const double* dU, double* work, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,16 @@ SIGNATURES3 = {
     'lrbms3_fom_solve_work_size': (c_i64, [c_vp]),
     'lrbms3_fom_solve': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
     'lrbms3_fom_apply': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'lrbms3_mass_inverse_norm2': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'lrbms3_project_mass': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'lrbms3_fom_implicit_euler_work_size': (c_i64, [c_vp]),
+    'lrbms3_fom_implicit_euler': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32,
+                                                 _P_DBL, c_vp]),
+    'lrbms3_reduced_implicit_euler_work_size': (c_i64, [c_vp, c_i32]),
+    'lrbms3_reduced_implicit_euler': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
+                                                     c_i32, _P_DBL, c_vp]),
+    'lrbms3_reduced_time_residual_work_size': (c_i64, [c_vp, c_i32]),
+    'lrbms3_reduced_time_residual': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _bound = None
@@ -390,3 +400,90 @@ class Native3DContext:
                                        self._ptr(x, (self.S_ext, self.n, M), 'x'), c_vp(y.data_ptr()), self._stream())
         self._check(rc, 'lrbms3_fom_apply')
         return y
+
+    # ------------------------------------------------------------------ parabolic
+    def mass_inverse_norm2(self, Y):
+        """Y [S, n, L] -> [S, L]: y^T M_s^-1 y per subdomain and vector (block L2 product inverted element by element)."""
+        if Y.dim() != 3:
+            raise NativeError('Y: expected [S, n, L]')
+        L = int(Y.shape[2])
+        out = self.empty(self.S, L)
+        rc = self.lib.lrbms3_mass_inverse_norm2(self.handle, L, self._ptr(Y, (self.S, self.n, L), 'Y'), c_vp(out.data_ptr()),
+                                                self._stream())
+        self._check(rc, 'lrbms3_mass_inverse_norm2')
+        return out
+
+    def project_mass(self, V):
+        """V [S_ext, n, N] -> M_red [S, N, N] = V_s^T M_s V_s (N <= 64)."""
+        if V.dim() != 3:
+            raise NativeError('V: expected [S_ext, n, N]')
+        N = int(V.shape[2])
+        M_red = self.empty(self.S, N, N)
+        rc = self.lib.lrbms3_project_mass(self.handle, N, self._ptr(V, (self.S_ext, self.n, N), 'V'), c_vp(M_red.data_ptr()),
+                                          self._stream())
+        self._check(rc, 'lrbms3_project_mass')
+        return M_red
+
+    def fom_implicit_euler(self, Q, theta, dt, nt, A_diag, A_cpl, b, U0=None, rtol=1e-10, max_iter=50000, work=None):
+        """(M + dt A(mu)) u_{k+1} = M u_k + dt b for k < nt in one native call -> U [nt + 1, S, n] (U[0] = U0, default zero),
+        (total CG iterations, worst final relative residual)."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        assert th.shape == (Q,)
+        nt = int(nt)
+        if work is None:
+            size = int(self.lib.lrbms3_fom_implicit_euler_work_size(self.handle))
+            if size < 0:
+                raise NativeError('lrbms3_fom_implicit_euler_work_size: mesh not uploaded')
+            work = self.empty(size)
+        U = self.empty(max(nt, 0) + 1, self.S, self.n)
+        if U0 is None:
+            U[0].zero_()
+        else:
+            U[0].copy_(U0.reshape(self.S, self.n))
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_fom_implicit_euler(self.handle, Q, th.ctypes.data_as(_P_DBL), float(dt), nt,
+                                                self._ptr(A_diag, (Q, self.S, self.n_T, 5, 100), 'A_diag'),
+                                                self._ptr(A_cpl, (Q, self.S, 6, self.ncf, 100), 'A_cpl'),
+                                                self._ptr(b, (self.S, self.n), 'b'), c_vp(work.data_ptr()), c_vp(U.data_ptr()),
+                                                float(rtol), int(max_iter), info, self._stream())
+        self._check(rc, 'lrbms3_fom_implicit_euler')
+        return U, (int(info[0]), float(info[1]))
+
+    def reduced_implicit_euler(self, Q, theta, dt, nt, B_sys, M_red, rhs_red, U0=None, rtol=1e-12, max_iter=20000, work=None):
+        """(M_red + dt sum_q theta_q B_sys_q) u_{k+1} = M_red u_k + dt rhs_red -> U [nt + 1, S, N] (U[0] = U0, default zero),
+        (total CG iterations, worst final relative residual)."""
+        N, S = int(rhs_red.shape[1]), self.S
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        assert th.shape == (Q,)
+        nt = int(nt)
+        if work is None:
+            work = self.empty(int(self.lib.lrbms3_reduced_implicit_euler_work_size(self.handle, N)))
+        U = self.empty(max(nt, 0) + 1, S, N)
+        if U0 is None:
+            U[0].zero_()
+        else:
+            U[0].copy_(U0.reshape(S, N))
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_reduced_implicit_euler(self.handle, Q, N, th.ctypes.data_as(_P_DBL), float(dt), nt,
+                                                    self._ptr(B_sys, (Q, S, 7, N, N), 'B_sys'), self._ptr(M_red, (S, N, N), 'M_red'),
+                                                    self._ptr(rhs_red, (S, N), 'rhs_red'), c_vp(work.data_ptr()),
+                                                    c_vp(U.data_ptr()), float(rtol), int(max_iter), info, self._stream())
+        self._check(rc, 'lrbms3_reduced_implicit_euler')
+        return U, (int(info[0]), float(info[1]))
+
+    def reduced_time_residual(self, Q, theta, B_sys, M_red, dU, work=None):
+        """dU [L, S, N] -> [L, S]: y^T M_red[s]^-1 y with y = (sum_q theta_q B_sys_q dU_l)_s."""
+        if dU.dim() != 3:
+            raise NativeError('dU: expected [L, S, N]')
+        L, S, N = int(dU.shape[0]), self.S, int(dU.shape[2])
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        assert th.shape == (Q,)
+        if work is None:
+            work = self.empty(int(self.lib.lrbms3_reduced_time_residual_work_size(self.handle, N)))
+        out = self.empty(L, S)
+        rc = self.lib.lrbms3_reduced_time_residual(self.handle, Q, N, L, th.ctypes.data_as(_P_DBL),
+                                                   self._ptr(B_sys, (Q, S, 7, N, N), 'B_sys'), self._ptr(M_red, (S, N, N), 'M_red'),
+                                                   self._ptr(dU, (L, S, N), 'dU'), c_vp(work.data_ptr()), c_vp(out.data_ptr()),
+                                                   self._stream())
+        self._check(rc, 'lrbms3_reduced_time_residual')
+        return out

@@ -66,6 +66,8 @@ struct lrbms3_ctx {
                                                     // groups of the batched reduced solve (all three)
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   double* thbar = nullptr;         // [8] device: theta(mu_bar) of lrbms3_assemble_energy_product
+  double* tm_inv = nullptr;        // [6][100] device (owned): inverses of the element mass tables (parabolic path, first use)
+  const double* tm_inv_src = nullptr;   // the TM table they were taken from (a new mesh upload invalidates them)
   double* pg_part = nullptr;       // K-split partial results of the k3_pg kernels (library-owned, grown on demand)
   long pg_part_cap = 0;
   // launch policy (lrbms3_ctx_set_option): the library reads no environment variable
@@ -3414,6 +3416,78 @@ int64_t lrbms3_reduced_solve_work_size(lrbms3_ctx* ctx, int32_t N) {
   return S * 7 * N * N + S * N * N + 6 * S * N + 5 * S + 16;
 }
 
+}  // extern "C"
+
+namespace {
+
+// work layout of the single-parameter reduced PCG (lrbms3_reduced_solve_work_size doubles)
+struct RedWork {
+  double *Amu, *Dinv, *r, *z, *p0, *p1, *Ap, *prz0, *prz1, *ppap, *prr, *scal;
+};
+
+RedWork red_work(long S, int N, double* work) {
+  RedWork w;
+  w.Amu = work;
+  w.Dinv = w.Amu + S * 7 * N * N;
+  w.r = w.Dinv + S * N * N;
+  w.z = w.r + S * N;
+  w.p0 = w.z + S * N;
+  w.p1 = w.p0 + S * N;
+  w.Ap = w.p1 + S * N;
+  w.prz0 = w.Ap + S * N;     // partial sums, ping-pong
+  w.prz1 = w.prz0 + S;
+  w.ppap = w.prz1 + S;
+  w.prr = w.ppap + S;
+  w.scal = w.prr + S;        // [0] rr, [1] bb
+  return w;
+}
+
+// Block-Jacobi PCG on the 7-slot operator w.Amu (inverse diagonal blocks in w.Dinv) from u = 0; the relative residual is taken
+// against |rhs|, or against the device scalar bref (squared norm) when it is given and non-zero (warm starts, as fom_cg).
+int red_cg(lrbms3_ctx* ctx, hipStream_t st, int N, RedWork& w, const double* rhs, double* u, double rtol, int max_iter, double* info,
+           const double* bref, const char* name) {
+  const T3& t = ctx->t;
+  const long S = t.S;
+  hipLaunchKernelGGL(k3_pcg_init, dim3(S), dim3(64), 0, st, N, rhs, w.Dinv, u, w.r, w.z, w.p0, w.prz0, w.prr);
+  hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)S, w.prr, w.scal + 1);
+  LAUNCH3(ctx);
+  double bb = 0.0, bn = 0.0;
+  HIP3(ctx, hipMemcpyAsync(&bb, w.scal + 1, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (bref) HIP3(ctx, hipMemcpyAsync(&bn, bref, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP3(ctx, hipStreamSynchronize(st));
+  if (info) info[0] = 0, info[1] = 0;
+  if (bb == 0.0) return LRBMS_OK;
+  const double den = bn > 0.0 ? bn : bb;
+  const size_t lds = sizeof(double) * (7 * N + 64);
+  double *po = w.p0, *pn = w.p1, *rz_old = w.prz1, *rz_cur = w.prz0;
+  int it = 0;
+  double rel = 1.0;
+  const int check = 8;
+  while (it < max_iter) {
+    for (int k = 0; k < check && it < max_iter; ++k, ++it) {
+      hipLaunchKernelGGL(k3_pcg_matvec, dim3(S), dim3(64), lds, st, t, N, it == 0 ? 1 : 0, w.Amu, w.z, po, pn, w.Ap, rz_cur, rz_old, w.ppap);
+      hipLaunchKernelGGL(k3_pcg_update, dim3(S), dim3(64), 0, st, (int)S, N, w.Dinv, pn, w.Ap, u, w.r, w.z, rz_cur, w.ppap, rz_old, w.prr);
+      std::swap(po, pn);
+      std::swap(rz_old, rz_cur);
+    }
+    hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)S, w.prr, w.scal);
+    LAUNCH3(ctx);
+    double rr = 0.0;
+    HIP3(ctx, hipMemcpyAsync(&rr, w.scal, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP3(ctx, hipStreamSynchronize(st));
+    rel = sqrt(rr / den);
+    if (!(rel == rel)) return fail3(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual");
+    if (rel <= rtol) break;
+  }
+  if (info) info[0] = it, info[1] = rel;
+  if (rel > rtol) return fail3(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": not converged");
+  return LRBMS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int lrbms3_reduced_solve(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* theta, const double* B_sys, const double* rhs_red,
                          double* work, double* u, double rtol, int32_t max_iter, double* info, void* stream) {
   REQUIRE3(ctx);
@@ -3423,52 +3497,10 @@ int lrbms3_reduced_solve(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* th
     return fail3(ctx, LRBMS_E_INVALID, "reduced_solve: bad argument");
   hipStream_t st = (hipStream_t)stream;
   const long S = t.S, per_q = S * 7 * N * N;
-  double* Amu = work;
-  double* Dinv = Amu + per_q;
-  double* r = Dinv + S * N * N;
-  double* z = r + S * N;
-  double* p0 = z + S * N;
-  double* p1 = p0 + S * N;
-  double* Ap = p1 + S * N;
-  double* prz0 = Ap + S * N;     // partial sums, ping-pong
-  double* prz1 = prz0 + S;
-  double* ppap = prz1 + S;
-  double* prr = ppap + S;
-  double* scal = prr + S;        // [0] rr, [1] bb
-  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, make_theta(Q, theta), B_sys, Amu);
-  hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, Amu, Dinv);
-  hipLaunchKernelGGL(k3_pcg_init, dim3(S), dim3(64), 0, st, N, rhs_red, Dinv, u, r, z, p0, prz0, prr);
-  hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)S, prr, scal + 1);
-  LAUNCH3(ctx);
-  double bb = 0.0;
-  HIP3(ctx, hipMemcpyAsync(&bb, scal + 1, sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP3(ctx, hipStreamSynchronize(st));
-  if (info) info[0] = 0, info[1] = 0;
-  if (bb == 0.0) return LRBMS_OK;
-  const size_t lds = sizeof(double) * (7 * N + 64);
-  double *po = p0, *pn = p1, *rz_old = prz1, *rz_cur = prz0;
-  int it = 0;
-  double rel = 1.0;
-  const int check = 8;
-  while (it < max_iter) {
-    for (int k = 0; k < check && it < max_iter; ++k, ++it) {
-      hipLaunchKernelGGL(k3_pcg_matvec, dim3(S), dim3(64), lds, st, t, N, it == 0 ? 1 : 0, Amu, z, po, pn, Ap, rz_cur, rz_old, ppap);
-      hipLaunchKernelGGL(k3_pcg_update, dim3(S), dim3(64), 0, st, (int)S, N, Dinv, pn, Ap, u, r, z, rz_cur, ppap, rz_old, prr);
-      std::swap(po, pn);
-      std::swap(rz_old, rz_cur);
-    }
-    hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)S, prr, scal);
-    LAUNCH3(ctx);
-    double rr = 0.0;
-    HIP3(ctx, hipMemcpyAsync(&rr, scal, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP3(ctx, hipStreamSynchronize(st));
-    rel = sqrt(rr / bb);
-    if (!(rel == rel)) return fail3(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve: NaN residual");
-    if (rel <= rtol) break;
-  }
-  if (info) info[0] = it, info[1] = rel;
-  if (rel > rtol) return fail3(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve: not converged");
-  return LRBMS_OK;
+  RedWork w = red_work(S, N, work);
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, make_theta(Q, theta), B_sys, w.Amu);
+  hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, w.Amu, w.Dinv);
+  return red_cg(ctx, st, N, w, rhs_red, u, rtol, max_iter, info, nullptr, "reduced_solve");
 }
 
 // doubles of work per group of <= 16 parameters of the batched reduced solve
@@ -3729,47 +3761,60 @@ int64_t lrbms3_fom_solve_work_size(lrbms3_ctx* ctx) {
          M + 4 * nblk + 2 * M + (int64_t)t.S * 112 + 2 * M * M + 2;       // coarse level: prc, pr0, r0, y0, blocks, A1, A1inv, info
 }
 
-int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const double* A_diag, const double* A_cpl, const double* b,
-                     double* work, double* x, double rtol, int32_t max_iter, double* info, void* stream) {
-  REQUIRE3(ctx);
-  const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "fom_solve: needs all subdomains on this rank");
-  if (Q < 1 || Q > 8 || !theta || !A_diag || !A_cpl || !b || !work || !x) return fail3(ctx, LRBMS_E_INVALID, "fom_solve: bad argument");
-  hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+
+// work layout of the full-order CG (lrbms3_fom_solve_work_size doubles; lrbms3_fom_implicit_euler appends its own buffers)
+struct FomWork {
+  int nbx;
+  long nblk, Mmax;
+  double *Amu, *Cmu, *Dinv, *r, *z, *p, *y, *prz, *prc, *ppy, *prr, *scal, *pr0, *r0, *y0, *A1b, *A1, *A1inv;
+  rocblas_int* pinfo;
+};
+
+FomWork fom_work(const T3& t, double* work) {
+  FomWork w;
   const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100, total = S * t.n;
-  const int nbx = (t.nT + FOM_EPB - 1) / FOM_EPB;
-  const long nblk = S * nbx, Mmax = std::min<long>(4 * S, FOM_MAX_COARSE);
-  double* Amu = work;
-  double* Cmu = Amu + nd;
-  double* Dinv = Cmu + ncp;
-  double* r = Dinv + S * t.nT * 100;
-  double* z = r + total;
-  double* p = z + total;
-  double* y = p + total;
-  double* prz = y + total;
-  double* prc = prz + nblk;            // coarse contributions to r.z: summed with prz by ONE reduction
-  double* ppy = prc + Mmax;
-  double* prr = ppy + nblk;
-  double* scal = prr + nblk;
-  double* pr0 = scal + 16;
-  double* r0 = pr0 + 4 * nblk;
-  double* y0 = r0 + Mmax;
-  double* A1b = y0 + Mmax;
-  double* A1 = A1b + S * 112;
-  double* A1inv = A1 + Mmax * Mmax;
-  rocblas_int* pinfo = (rocblas_int*)(A1inv + Mmax * Mmax);
-  const QV th = make_theta(Q, theta);
-  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, nd, Q, th, A_diag, Amu);
-  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((ncp + 255) / 256)), dim3(256), 0, st, ncp, Q, th, A_cpl, Cmu);
-  hipLaunchKernelGGL(k3f_block_inverse, dim3((t.nT + 63) / 64, S), dim3(64), 0, st, t, Amu, Dinv);
-  // ---- coarse level (LRBMS3_OPT_FOM_COARSE 0 switches it off)
+  w.nbx = (t.nT + FOM_EPB - 1) / FOM_EPB;
+  w.nblk = S * w.nbx;
+  w.Mmax = std::min<long>(4 * S, FOM_MAX_COARSE);
+  w.Amu = work;
+  w.Cmu = w.Amu + nd;
+  w.Dinv = w.Cmu + ncp;
+  w.r = w.Dinv + S * t.nT * 100;
+  w.z = w.r + total;
+  w.p = w.z + total;
+  w.y = w.p + total;
+  w.prz = w.y + total;
+  w.prc = w.prz + w.nblk;              // coarse contributions to r.z: summed with prz by ONE reduction
+  w.ppy = w.prc + w.Mmax;
+  w.prr = w.ppy + w.nblk;
+  w.scal = w.prr + w.nblk;
+  w.pr0 = w.scal + 16;
+  w.r0 = w.pr0 + 4 * w.nblk;
+  w.y0 = w.r0 + w.Mmax;
+  w.A1b = w.y0 + w.Mmax;
+  w.A1 = w.A1b + S * 112;
+  w.A1inv = w.A1 + w.Mmax * w.Mmax;
+  w.pinfo = (rocblas_int*)(w.A1inv + w.Mmax * w.Mmax);
+  return w;
+}
+
+// Coarse level of the two-level preconditioner on the operator in w.Amu / w.Cmu (LRBMS3_OPT_FOM_COARSE 0 switches it off).
+// shared_pc: the elliptic solves' kept inverse (lrbms3_fom_precond_keep) may be used and is refreshed; false: a private one
+// in the work buffer, the context's is neither read nor replaced.  Out: nc (0 = block-Jacobi alone) and the dense inverse.
+int fom_coarse(lrbms3_ctx* ctx, hipStream_t st, FomWork& w, bool shared_pc, int& nc_out, const double*& A1inv_out) {
+  const T3& t = ctx->t;
+  const long S = t.S;
+  double* A1inv = w.A1inv;
   const bool coarse_env = ctx->opt_fom_coarse != 0;
   int nc = coarse_env ? ctx->fom_nc : 0;
   if (nc > 1 && (long)nc * S > FOM_MAX_COARSE) nc = 1;       // the dense coarse inverse is capped: constants instead of P1, then none
   if ((long)nc * S > FOM_MAX_COARSE) nc = 0;
   const double* Phi = ctx->fom_phi;
   const long M = (long)nc * S;
-  const bool kept = nc > 0 && ctx->fom_keep && ctx->fom_pc && ctx->fom_pc_M == M && ctx->fom_pc_nc == nc;
+  const bool kept = shared_pc && nc > 0 && ctx->fom_keep && ctx->fom_pc && ctx->fom_pc_M == M && ctx->fom_pc_nc == nc;
   if (kept) A1inv = ctx->fom_pc;          // built by an earlier solve (another parameter: any SPD preconditioner is admissible)
   if (nc > 0 && !kept) {
     if (!ctx->blas) {
@@ -3779,22 +3824,22 @@ int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const doub
     }
     rocblas_handle h = (rocblas_handle)ctx->blas;
     if (rocblas_set_stream(h, st) != rocblas_status_success) return fail3(ctx, LRBMS_E_HIP, "rocblas_set_stream failed");
-    hipLaunchKernelGGL(k3f_coarse_blocks, dim3(S), dim3(256), 0, st, t, Phi, Amu, Cmu, A1b);
-    HIP3(ctx, hipMemsetAsync(A1, 0, sizeof(double) * 2 * M * M, st));             // A1 and the identity behind it (A1inv at M * M when nc = 4)
-    double* Id = A1 + M * M;
-    hipLaunchKernelGGL(k3f_coarse_dense, dim3((unsigned)((std::max(M, S * 112) + 255) / 256)), dim3(256), 0, st, t, nc, A1b, A1, Id);
+    hipLaunchKernelGGL(k3f_coarse_blocks, dim3(S), dim3(256), 0, st, t, Phi, w.Amu, w.Cmu, w.A1b);
+    HIP3(ctx, hipMemsetAsync(w.A1, 0, sizeof(double) * 2 * M * M, st));             // A1 and the identity behind it (A1inv at M * M when nc = 4)
+    double* Id = w.A1 + M * M;
+    hipLaunchKernelGGL(k3f_coarse_dense, dim3((unsigned)((std::max(M, S * 112) + 255) / 256)), dim3(256), 0, st, t, nc, w.A1b, w.A1, Id);
     LAUNCH3(ctx);
-    if (rocsolver_dpotrf(h, rocblas_fill_lower, (rocblas_int)M, A1, (rocblas_int)M, pinfo) != rocblas_status_success)
+    if (rocsolver_dpotrf(h, rocblas_fill_lower, (rocblas_int)M, w.A1, (rocblas_int)M, w.pinfo) != rocblas_status_success)
       return fail3(ctx, LRBMS_E_HIP, "rocsolver_dpotrf failed");
     rocblas_int hinfo = 0;
-    HIP3(ctx, hipMemcpyAsync(&hinfo, pinfo, sizeof(rocblas_int), hipMemcpyDeviceToHost, st));
+    HIP3(ctx, hipMemcpyAsync(&hinfo, w.pinfo, sizeof(rocblas_int), hipMemcpyDeviceToHost, st));
     HIP3(ctx, hipStreamSynchronize(st));
     if (hinfo != 0) nc = 0;                                   // not positive definite (dependent functions): block-Jacobi alone
-    else if (rocsolver_dpotrs(h, rocblas_fill_lower, (rocblas_int)M, (rocblas_int)M, A1, (rocblas_int)M, Id, (rocblas_int)M) !=
+    else if (rocsolver_dpotrs(h, rocblas_fill_lower, (rocblas_int)M, (rocblas_int)M, w.A1, (rocblas_int)M, Id, (rocblas_int)M) !=
              rocblas_status_success)
       return fail3(ctx, LRBMS_E_HIP, "rocsolver_dpotrs failed");
     A1inv = Id;
-    if (nc > 0 && ctx->fom_keep) {
+    if (shared_pc && nc > 0 && ctx->fom_keep) {
       if (ctx->fom_pc && ctx->fom_pc_M != M) {
         HIP3(ctx, hipFree(ctx->fom_pc));
         ctx->fom_pc = nullptr;
@@ -3806,6 +3851,22 @@ int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const doub
       ctx->fom_pc_nc = nc;
     }
   }
+  nc_out = nc;
+  A1inv_out = A1inv;
+  return LRBMS_OK;
+}
+
+// Preconditioned CG on the operator in w (element-block inverses in w.Dinv, coarse level nc / A1inv of fom_coarse) from x = 0.
+// The relative residual is taken against |b|, or against the device scalar bref (squared norm) when it is given and non-zero:
+// a warm-started solve hands in the correction's right-hand side b - K x0 and the norm of the full right-hand side.
+int fom_cg(lrbms3_ctx* ctx, hipStream_t st, FomWork& w, int nc, const double* A1inv, const double* b, double* x, double rtol,
+           int max_iter, double* info, const double* bref, const char* name) {
+  const T3& t = ctx->t;
+  const long S = t.S, total = S * t.n, nblk = w.nblk, M = (long)nc * S;
+  const int nbx = w.nbx;
+  const double* Phi = ctx->fom_phi;
+  double *Amu = w.Amu, *Cmu = w.Cmu, *Dinv = w.Dinv, *r = w.r, *z = w.z, *p = w.p, *y = w.y, *prz = w.prz, *prc = w.prc;
+  double *ppy = w.ppy, *prr = w.prr, *scal = w.scal, *pr0 = w.pr0, *r0 = w.r0, *y0 = w.y0;
   const long nrz = nblk + (nc > 0 ? M : 0);
   auto coarse = [&]() {
     if (nc == 0) return;
@@ -3818,11 +3879,13 @@ int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const doub
   hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)nrz, prz, scal + 0);
   hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)nblk, prr, scal + 4);
   LAUNCH3(ctx);
-  double bb = 0.0;
+  double bb = 0.0, bn = 0.0;
   HIP3(ctx, hipMemcpyAsync(&bb, scal + 4, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (bref) HIP3(ctx, hipMemcpyAsync(&bn, bref, sizeof(double), hipMemcpyDeviceToHost, st));
   HIP3(ctx, hipStreamSynchronize(st));
   if (info) info[0] = 0, info[1] = 0;
   if (bb == 0.0) return LRBMS_OK;
+  const double den = bn > 0.0 ? bn : bb;
   int it = 0;
   double rel = 1.0;
   const int check = 16;
@@ -3842,13 +3905,37 @@ int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const doub
     double rr = 0.0;
     HIP3(ctx, hipMemcpyAsync(&rr, scal + 3, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP3(ctx, hipStreamSynchronize(st));
-    rel = sqrt(rr / bb);
-    if (!(rel == rel)) return fail3(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve: NaN residual");
+    rel = sqrt(rr / den);
+    if (!(rel == rel)) return fail3(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual");
     if (rel <= rtol) break;
   }
   if (info) info[0] = it, info[1] = rel;
-  if (rel > rtol) return fail3(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve: not converged");
+  if (rel > rtol) return fail3(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": not converged");
   return LRBMS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const double* A_diag, const double* A_cpl, const double* b,
+                     double* work, double* x, double rtol, int32_t max_iter, double* info, void* stream) {
+  REQUIRE3(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "fom_solve: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || !theta || !A_diag || !A_cpl || !b || !work || !x) return fail3(ctx, LRBMS_E_INVALID, "fom_solve: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100;
+  FomWork w = fom_work(t, work);
+  const QV th = make_theta(Q, theta);
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, nd, Q, th, A_diag, w.Amu);
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((ncp + 255) / 256)), dim3(256), 0, st, ncp, Q, th, A_cpl, w.Cmu);
+  hipLaunchKernelGGL(k3f_block_inverse, dim3((t.nT + 63) / 64, S), dim3(64), 0, st, t, w.Amu, w.Dinv);
+  int nc = 0;
+  const double* A1inv = nullptr;
+  int rc = fom_coarse(ctx, st, w, true, nc, A1inv);
+  if (rc != LRBMS_OK) return rc;
+  return fom_cg(ctx, st, w, nc, A1inv, b, x, rtol, max_iter, info, nullptr, "fom_solve");
 }
 
 int lrbms3_fom_apply(lrbms3_ctx* ctx, int32_t Q, int32_t M, const double* theta, const double* A_diag, const double* A_cpl,
@@ -3857,6 +3944,426 @@ int lrbms3_fom_apply(lrbms3_ctx* ctx, int32_t Q, int32_t M, const double* theta,
   if (Q < 1 || Q > 8 || M < 1 || !theta || !A_diag || !A_cpl || !x || !y) return fail3(ctx, LRBMS_E_INVALID, "fom_apply: bad argument");
   const T3& t = ctx->t;
   hipLaunchKernelGGL(k3_fom_apply, dim3(t.nT, t.S), dim3(256), 0, (hipStream_t)stream, t, Q, M, make_theta(Q, theta), A_diag, A_cpl, x, y);
+  LAUNCH3(ctx);
+  return LRBMS_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------- parabolic path
+// M u' + A(mu) u = f with the block L2 product as mass: implicit Euler on the full-order and on the reduced system, the mass
+// norms of the parabolic estimator, the projected mass.  The P2 DG mass matrix is element-block-diagonal, every block the
+// table TM of the element's type, so M^-1 is TM^-1 per element (inverted once per context).  The step operators reuse the CG
+// machinery of lrbms3_fom_solve / lrbms3_reduced_solve (fom_coarse, fom_cg, red_cg).
+namespace {
+
+// inverses of the six element mass tables: one workgroup per type, Gauss-Jordan in LDS (SPD: no pivoting)
+__global__ __launch_bounds__(64) void k3p_tm_inverse(const double* __restrict__ TM, double* __restrict__ TMinv) {
+  __shared__ double a[10][21];
+  const int ty = blockIdx.x, tid = threadIdx.x;
+  for (int i = tid; i < 200; i += 64) {
+    const int r = i / 20, c = i - r * 20;
+    a[r][c] = c < 10 ? TM[ty * 100 + r * 10 + c] : (c - 10 == r ? 1.0 : 0.0);
+  }
+  __syncthreads();
+  for (int p = 0; p < 10; ++p) {
+    const double ip = 1.0 / a[p][p];
+    __syncthreads();
+    if (tid < 20) a[p][tid] *= ip;
+    __syncthreads();
+    for (int i = tid; i < 200; i += 64) {
+      const int r = i / 20, c = i - r * 20;
+      if (r != p && c != p) a[r][c] -= a[r][p] * a[p][c];
+    }
+    __syncthreads();
+    if (tid < 10 && tid != p) a[tid][p] = 0.0;
+    __syncthreads();
+  }
+  for (int i = tid; i < 100; i += 64) TMinv[ty * 100 + i] = a[i / 10][10 + i % 10];
+}
+
+// out [S][L] = sum_e y_e^T TM_e^-1 y_e, Y [S][n][L]: one workgroup per subdomain streams its slab once.  Threads (g, l) of a
+// chunk of Lc <= 256 vectors: vector l0 + l, elements g, g + G, ... (G = 256 / Lc); the G partial sums are added in a fixed order.
+__global__ __launch_bounds__(256) void k3p_mass_inv_norm2(T3 t, int L, const double* __restrict__ TMinv, const double* __restrict__ Y,
+                                                          double* __restrict__ out) {
+  __shared__ double mi[600], red[256];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  for (int i = tid; i < 600; i += 256) mi[i] = TMinv[i];
+  for (int l0 = 0; l0 < L; l0 += 256) {
+    const int Lc = L - l0 < 256 ? L - l0 : 256, G = 256 / Lc, g = tid / Lc, l = tid - g * Lc;
+    __syncthreads();
+    double acc = 0.0;
+    if (g < G)
+      for (int e = g; e < t.nT; e += G) {
+        const double* Mi = mi + t.elem_type[e] * 100;
+        const double* y = Y + ((long)s * t.n + e * 10) * L + l0 + l;
+        double v[10];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) v[i] = y[(long)i * L];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) {
+          double a = 0.0;
+#pragma unroll
+          for (int j = 0; j < 10; ++j) a += Mi[i * 10 + j] * v[j];
+          acc += v[i] * a;
+        }
+      }
+    red[tid] = acc;
+    __syncthreads();
+    if (tid < Lc) {
+      double sum = 0.0;
+      for (int k = 0; k < G; ++k) sum += red[k * Lc + tid];
+      out[(long)s * L + l0 + tid] = sum;
+    }
+  }
+}
+
+// M_red [S][N][N] = sum_e V_e^T TM_e V_e on the fp64 matrix cores, one workgroup of 8 waves per subdomain, one wave per element
+// at a time.  Z = TM_e V_e (TM as the A operand: lane row l&15, k l>>4; rows of V_e as the B operand), then G += V_e^T Z: the
+// accumulator layout of Z (rows (l>>4) + 4 r, column l&15) is the B operand of k-step r, and the A operand of that step,
+// V_e[(l>>4) + 4 r][16 rt + (l&15)], is the B operand of the first product for k-step r -- every lane loads its 3 T values of
+// V_e once (rows >= 10 and columns >= N as zeros) and both products read them from registers.  T = 16-column tiles per side.
+template <int T>
+__global__ __launch_bounds__(512) void k3p_project_mass(T3 t, int N, const double* __restrict__ V, double* __restrict__ Mred) {
+  __shared__ double red[8][256];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  d4 acc[T][T];
+#pragma unroll
+  for (int rt = 0; rt < T; ++rt)
+#pragma unroll
+    for (int ct = 0; ct < T; ++ct) acc[rt][ct] = d4{0.0, 0.0, 0.0, 0.0};
+  const double* Vs = V + (long)s * t.n * N;
+  for (int e = wave; e < t.nT; e += 8) {
+    const double* tm = t.TM + t.elem_type[e] * 100;
+    const double* Ve = Vs + (long)e * 10 * N;
+    double a[3], v[3][T];
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) {
+      const int r = 4 * ks + lk;
+      a[ks] = (li < 10 && r < 10) ? tm[li * 10 + r] : 0.0;
+#pragma unroll
+      for (int ct = 0; ct < T; ++ct) {
+        const int c = 16 * ct + li;
+        v[ks][ct] = (r < 10 && c < N) ? Ve[r * N + c] : 0.0;
+      }
+    }
+#pragma unroll
+    for (int ct = 0; ct < T; ++ct) {
+      d4 z = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int ks = 0; ks < 3; ++ks) z = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], v[ks][ct], z, 0, 0, 0);
+#pragma unroll
+      for (int rt = 0; rt < T; ++rt)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[r][rt], z[r], acc[rt][ct], 0, 0, 0);
+    }
+  }
+  // the waves' tiles summed in a fixed order through the LDS
+#pragma unroll
+  for (int rt = 0; rt < T; ++rt)
+#pragma unroll
+    for (int ct = 0; ct < T; ++ct) {
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave][r * 64 + lane] = acc[rt][ct][r];
+      __syncthreads();
+      if (tid < 256) {
+        const int r = tid >> 6, l = tid & 63;
+        double sum = 0.0;
+        for (int w = 0; w < 8; ++w) sum += red[w][tid];
+        const int row = 16 * rt + (l >> 4) + 4 * r, col = 16 * ct + (l & 15);
+        if (row < N && col < N) Mred[((long)s * N + row) * N + col] = sum;
+      }
+    }
+}
+
+// Amu [S][n_T][5][100] (slot 0 = the (e, e) block) += TM of the element's type: the mass part of the implicit Euler step operator
+__global__ __launch_bounds__(256) void k3p_fom_add_mass(T3 t, long total, double* __restrict__ Amu) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long se = i / 100;
+  const int c = (int)(i - se * 100), e = (int)(se % t.nT);
+  Amu[se * 500 + c] += t.TM[t.elem_type[e] * 100 + c];
+}
+
+// right-hand side of a warm-started step: f = TM u_k + dt b (per element), rhs = f - Ku (Ku = step operator applied to u_k);
+// partial |f|^2 per workgroup (rows as k3f_update)
+__global__ __launch_bounds__(256) void k3p_fom_rhs(T3 t, double dt, const double* __restrict__ u, const double* __restrict__ b,
+                                                   const double* __restrict__ Ku, double* __restrict__ rhs, double* __restrict__ part) {
+  __shared__ double red[256];
+  const int s = blockIdx.y, tid = threadIdx.x;
+  const int el = tid / 10, i = tid - el * 10, e = blockIdx.x * FOM_EPB + el;
+  const bool on = el < FOM_EPB && e < t.nT;
+  double f = 0.0;
+  if (on) {
+    const long d = (long)s * t.n + e * 10 + i;
+    const double* tm = t.TM + t.elem_type[e] * 100 + i * 10;
+    const double* ue = u + (long)s * t.n + e * 10;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) acc += tm[j] * ue[j];
+    f = acc + dt * b[d];
+    rhs[d] = f - Ku[d];
+  }
+  const double sum = block_sum(f * f, red);
+  if (tid == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(256) void k3p_axpy(long total, const double* __restrict__ x, double* __restrict__ y) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < total) y[i] += x[i];
+}
+
+// Amu [S][7][N][N] slot 3 (self) += M_red [S][N][N]
+__global__ __launch_bounds__(256) void k3p_red_add_mass(long total, int N, const double* __restrict__ Mred, double* __restrict__ Amu) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long NN = (long)N * N, s = i / NN;
+  Amu[(s * 7 + 3) * NN + (i - s * NN)] += Mred[i];
+}
+
+// reduced step right-hand side: f = M_red u_k + dt rhs_red, rhs = f - Ku; partial |f|^2 per subdomain
+__global__ __launch_bounds__(64) void k3p_red_rhs(int N, double dt, const double* __restrict__ Mred, const double* __restrict__ u,
+                                                  const double* __restrict__ rhs_red, const double* __restrict__ Ku,
+                                                  double* __restrict__ rhs, double* __restrict__ part) {
+  __shared__ double us[64], red[64];
+  const int s = blockIdx.x, i = threadIdx.x;
+  us[i] = i < N ? u[(long)s * N + i] : 0.0;
+  __syncthreads();
+  double f = 0.0;
+  if (i < N) {
+    const double* M = Mred + ((long)s * N + i) * N;
+    double acc = 0.0;
+    for (int j = 0; j < N; ++j) acc += M[j] * us[j];
+    f = acc + dt * rhs_red[(long)s * N + i];
+    rhs[(long)s * N + i] = f - Ku[(long)s * N + i];
+  }
+  red[i] = f * f;
+  __syncthreads();
+  for (int w = 32; w > 0; w >>= 1) {
+    if (i < w) red[i] += red[i + w];
+    __syncthreads();
+  }
+  if (i == 0) part[s] = red[0];
+}
+
+// out [L][S] = y^T Minv_s y, y = (Amu dU_l)_s on the 7-slot operator; one workgroup per (subdomain, vector)
+__global__ __launch_bounds__(64) void k3p_time_residual(T3 t, int N, const double* __restrict__ Amu, const double* __restrict__ Minv,
+                                                        const double* __restrict__ dU, double* __restrict__ out) {
+  extern __shared__ double lds[];   // [7][N] | y [N] | 64
+  double* ys = lds + 7 * N;
+  double* red = ys + N;
+  const int s = blockIdx.x, l = blockIdx.y, i = threadIdx.x, S = t.S;
+  const double* x = dU + (long)l * S * N;
+  for (int k = i; k < 7 * N; k += 64) {
+    const int s2 = t.nbr[s * 7 + k / N];
+    lds[k] = s2 >= 0 ? x[(long)s2 * N + k % N] : 0.0;
+  }
+  __syncthreads();
+  double y = 0.0;
+  if (i < N) {
+    for (int slot = 0; slot < 7; ++slot) {
+      if (t.nbr[s * 7 + slot] < 0) continue;
+      const double* row = Amu + (((long)s * 7 + slot) * N + i) * N;
+      const double* ps = lds + slot * N;
+      for (int j = 0; j < N; ++j) y += row[j] * ps[j];
+    }
+    ys[i] = y;
+  }
+  __syncthreads();
+  double w = 0.0;
+  if (i < N) {
+    const double* D = Minv + ((long)s * N + i) * N;
+    for (int j = 0; j < N; ++j) w += D[j] * ys[j];
+  }
+  red[i] = i < N ? y * w : 0.0;
+  __syncthreads();
+  for (int k = 32; k > 0; k >>= 1) {
+    if (i < k) red[i] += red[i + k];
+    __syncthreads();
+  }
+  if (i == 0) out[(long)l * S + s] = red[0];
+}
+
+int ensure_tm_inverse(lrbms3_ctx* ctx, hipStream_t st) {
+  if (ctx->tm_inv && ctx->tm_inv_src == ctx->t.TM) return LRBMS_OK;
+  if (!ctx->tm_inv) {
+    HIP3(ctx, hipMalloc((void**)&ctx->tm_inv, sizeof(double) * 600));
+    ctx->owned.push_back(ctx->tm_inv);
+  }
+  hipLaunchKernelGGL(k3p_tm_inverse, dim3(6), dim3(64), 0, st, ctx->t.TM, ctx->tm_inv);
+  LAUNCH3(ctx);
+  HIP3(ctx, hipStreamSynchronize(st));      // later calls may come on other streams
+  ctx->tm_inv_src = ctx->t.TM;
+  return LRBMS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lrbms3_mass_inverse_norm2(lrbms3_ctx* ctx, int32_t L, const double* Y, double* out, void* stream) {
+  REQUIRE3(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "mass_inverse_norm2: needs all subdomains on this rank");
+  if (L < 1 || !Y || !out) return fail3(ctx, LRBMS_E_INVALID, "mass_inverse_norm2: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = ensure_tm_inverse(ctx, st);
+  if (rc != LRBMS_OK) return rc;
+  hipLaunchKernelGGL(k3p_mass_inv_norm2, dim3(t.S), dim3(256), 0, st, t, L, ctx->tm_inv, Y, out);
+  LAUNCH3(ctx);
+  return LRBMS_OK;
+}
+
+int lrbms3_project_mass(lrbms3_ctx* ctx, int32_t N, const double* V, double* M_red, void* stream) {
+  REQUIRE3(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "project_mass: needs all subdomains on this rank");
+  if (N < 1 || N > 64 || !V || !M_red) return fail3(ctx, LRBMS_E_INVALID, "project_mass: bad argument (1 <= N <= 64)");
+  hipStream_t st = (hipStream_t)stream;
+  const int T = (N + 15) / 16;
+  if (T == 1) hipLaunchKernelGGL(k3p_project_mass<1>, dim3(t.S), dim3(512), 0, st, t, N, V, M_red);
+  else if (T == 2) hipLaunchKernelGGL(k3p_project_mass<2>, dim3(t.S), dim3(512), 0, st, t, N, V, M_red);
+  else if (T == 3) hipLaunchKernelGGL(k3p_project_mass<3>, dim3(t.S), dim3(512), 0, st, t, N, V, M_red);
+  else hipLaunchKernelGGL(k3p_project_mass<4>, dim3(t.S), dim3(512), 0, st, t, N, V, M_red);
+  LAUNCH3(ctx);
+  return LRBMS_OK;
+}
+
+int64_t lrbms3_fom_implicit_euler_work_size(lrbms3_ctx* ctx) {
+  const int64_t base = lrbms3_fom_solve_work_size(ctx);
+  if (base < 0) return -1;
+  const T3& t = ctx->t;
+  const int64_t nblk = (int64_t)t.S * ((t.nT + FOM_EPB - 1) / FOM_EPB);
+  return base + (int64_t)t.S * t.n + nblk + 16;          // + right-hand side of the correction, partial |f|^2, |f|^2
+}
+
+int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, double dt, int32_t nt, const double* A_diag,
+                              const double* A_cpl, const double* b, double* work, double* U, double rtol, int32_t max_iter,
+                              double* info, void* stream) {
+  REQUIRE3(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "fom_implicit_euler: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || !theta || !A_diag || !A_cpl || !b || !work || !U)
+    return fail3(ctx, LRBMS_E_INVALID, "fom_implicit_euler: bad argument");
+  if (!(dt > 0.0) || nt < 1) return fail3(ctx, LRBMS_E_INVALID, "fom_implicit_euler: dt > 0 and nt >= 1 required");
+  hipStream_t st = (hipStream_t)stream;
+  const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100, total = S * t.n;
+  FomWork w = fom_work(t, work);
+  double* rhs = work + lrbms3_fom_solve_work_size(ctx);
+  double* part = rhs + total;
+  double* ff = part + w.nblk;
+  QV th = make_theta(Q, theta);
+  for (int q = 0; q < Q; ++q) th.v[q] *= dt;
+  // step operator M + dt A(mu): element-block inverses and coarse level once per call, on it (never the elliptic solves' kept one)
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, nd, Q, th, A_diag, w.Amu);
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((ncp + 255) / 256)), dim3(256), 0, st, ncp, Q, th, A_cpl, w.Cmu);
+  hipLaunchKernelGGL(k3p_fom_add_mass, dim3((unsigned)((S * t.nT * 100 + 255) / 256)), dim3(256), 0, st, t, S * t.nT * 100, w.Amu);
+  hipLaunchKernelGGL(k3f_block_inverse, dim3((t.nT + 63) / 64, S), dim3(64), 0, st, t, w.Amu, w.Dinv);
+  LAUNCH3(ctx);
+  int nc = 0;
+  const double* A1inv = nullptr;
+  int rc = fom_coarse(ctx, st, w, false, nc, A1inv);
+  if (rc != LRBMS_OK) return rc;
+  double iters = 0.0, worst = 0.0;
+  if (info) info[0] = 0, info[1] = 0;
+  for (int k = 0; k < nt; ++k) {
+    // warm start at u_k: the correction solves K d = (M u_k + dt b) - K u_k, with the residual relative to |M u_k + dt b|
+    const double* uk = U + (long)k * total;
+    double* un = U + (long)(k + 1) * total;
+    hipLaunchKernelGGL(k3f_matvec, dim3(xcd_grid(w.nbx, (int)S)), dim3(256), 0, st, t, w.nbx, w.Amu, w.Cmu, uk, w.y, w.ppy);
+    hipLaunchKernelGGL(k3p_fom_rhs, dim3(w.nbx, S), dim3(256), 0, st, t, dt, uk, b, w.y, rhs, part);
+    hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)w.nblk, part, ff);
+    LAUNCH3(ctx);
+    double inf[2] = {0.0, 0.0};
+    rc = fom_cg(ctx, st, w, nc, A1inv, rhs, un, rtol, max_iter, inf, ff, "fom_implicit_euler");
+    iters += inf[0];
+    worst = std::max(worst, inf[1]);
+    if (info) info[0] = iters, info[1] = worst;
+    if (rc != LRBMS_OK) return rc;
+    hipLaunchKernelGGL(k3p_axpy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, uk, un);
+    LAUNCH3(ctx);
+  }
+  return LRBMS_OK;
+}
+
+int64_t lrbms3_reduced_implicit_euler_work_size(lrbms3_ctx* ctx, int32_t N) {
+  const int64_t base = lrbms3_reduced_solve_work_size(ctx, N);
+  if (base < 0) return -1;
+  return base + (int64_t)ctx->t.S * N + ctx->t.S + 16;    // + right-hand side of the correction, partial |f|^2, |f|^2
+}
+
+int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* theta, double dt, int32_t nt,
+                                  const double* B_sys, const double* M_red, const double* rhs_red, double* work, double* U,
+                                  double rtol, int32_t max_iter, double* info, void* stream) {
+  REQUIRE3(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 64 || !theta || !B_sys || !M_red || !rhs_red || !work || !U)
+    return fail3(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: bad argument");
+  if (!(dt > 0.0) || nt < 1) return fail3(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: dt > 0 and nt >= 1 required");
+  hipStream_t st = (hipStream_t)stream;
+  const long S = t.S, per_q = S * 7 * N * N, total = S * N;
+  RedWork w = red_work(S, N, work);
+  double* rhs = work + lrbms3_reduced_solve_work_size(ctx, N);
+  double* part = rhs + total;
+  double* ff = part + S;
+  QV th = make_theta(Q, theta);
+  for (int q = 0; q < Q; ++q) th.v[q] *= dt;
+  // M_red + dt sum_q theta_q B_sys_q, the mass on the self slot; zero-padded columns keep a zero diagonal there, so the block
+  // inverse puts the identity on them and the padded unknowns stay exactly 0
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, th, B_sys, w.Amu);
+  hipLaunchKernelGGL(k3p_red_add_mass, dim3((unsigned)((S * N * N + 255) / 256)), dim3(256), 0, st, S * N * N, N, M_red, w.Amu);
+  hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, w.Amu, w.Dinv);
+  LAUNCH3(ctx);
+  const size_t lds = sizeof(double) * (7 * N + 64);
+  double iters = 0.0, worst = 0.0;
+  if (info) info[0] = 0, info[1] = 0;
+  for (int k = 0; k < nt; ++k) {
+    const double* uk = U + (long)k * total;
+    double* un = U + (long)(k + 1) * total;
+    // K u_k by the CG's matvec (first iteration: p = z = u_k), into Ap
+    hipLaunchKernelGGL(k3_pcg_matvec, dim3(S), dim3(64), lds, st, t, N, 1, w.Amu, uk, uk, w.p1, w.Ap, w.prz0, w.prz1, w.ppap);
+    hipLaunchKernelGGL(k3p_red_rhs, dim3(S), dim3(64), 0, st, N, dt, M_red, uk, rhs_red, w.Ap, rhs, part);
+    hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)S, part, ff);
+    LAUNCH3(ctx);
+    double inf[2] = {0.0, 0.0};
+    int rc = red_cg(ctx, st, N, w, rhs, un, rtol, max_iter, inf, ff, "reduced_implicit_euler");
+    iters += inf[0];
+    worst = std::max(worst, inf[1]);
+    if (info) info[0] = iters, info[1] = worst;
+    if (rc != LRBMS_OK) return rc;
+    hipLaunchKernelGGL(k3p_axpy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, uk, un);
+    LAUNCH3(ctx);
+  }
+  return LRBMS_OK;
+}
+
+int64_t lrbms3_reduced_time_residual_work_size(lrbms3_ctx* ctx, int32_t N) {
+  if (!ctx || !ctx->has_mesh) return -1;
+  const int64_t S = ctx->t.S;
+  return S * 7 * N * N + S * N * N;
+}
+
+int lrbms3_reduced_time_residual(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t L, const double* theta, const double* B_sys,
+                                 const double* M_red, const double* dU, double* work, double* out, void* stream) {
+  REQUIRE3(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "reduced_time_residual: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 64 || L < 1 || L > 65535 || !theta || !B_sys || !M_red || !dU || !work || !out)
+    return fail3(ctx, LRBMS_E_INVALID, "reduced_time_residual: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const long S = t.S, per_q = S * 7 * N * N, NN = (long)N * N;
+  double* Amu = work;
+  double* Minv = Amu + per_q;
+  // M_red^-1 by the reduced solver's block inverse, which reads the self slot of a 7-slot operator: M_red goes to slot 3 of Amu
+  // first (its zero-diagonal rule: the identity on padded columns), then Amu receives the combined operator
+  HIP3(ctx, hipMemcpy2DAsync(Amu + 3 * NN, sizeof(double) * 7 * NN, M_red, sizeof(double) * NN, sizeof(double) * NN, S,
+                             hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, Amu, Minv);
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, make_theta(Q, theta), B_sys, Amu);
+  hipLaunchKernelGGL(k3p_time_residual, dim3(S, L), dim3(64), sizeof(double) * (8 * N + 64), st, t, N, Amu, Minv, dU, out);
   LAUNCH3(ctx);
   return LRBMS_OK;
 }

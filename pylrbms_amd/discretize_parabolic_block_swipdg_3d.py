@@ -1,0 +1,181 @@
+"""Parabolic block SWIPDG P2 discretization in 3D on the HIP path: the 3D counterpart of
+``pylrbms_amd.discretize_parabolic_block_swipdg`` (reference discretize_parabolic_block_swipdg.py:17-95, estimators.py:139-168).
+
+``M u' + A(mu) u = f`` with the block L2 product as mass, zero initial data and implicit Euler with ``nt`` steps:
+
+    d, data = discretize(grid_and_problem_data, T, nt)     # the elliptic 3D discretize + T, time_stepper, initial_data
+    U = d.solve(mu)                                       # [S, n, nt + 1]: ONE native call (lrbms3_fom_implicit_euler)
+    d.estimate(U, mu)                                     # est, (local_eta_nc, local_eta_r, local_eta_df, time_residual, time_deriv_nc)
+    reductor = ParabolicLRBMSReductor3D(d)
+    reductor.extend_basis(U[:, :, idx]);  rd = reductor.reduce()
+    u = rd.solve(mu);  rd.estimate(u, mu);  reductor.reconstruct(u)
+
+The estimate restates ``OracleParabolic.estimate`` (oracle/parabolic.py): the elliptic terms of every vector of the trajectory,
+scaled by 2 sqrt(dt / 3); ``time_residual_k = sqrt(dt / 3 * sum_s y^T M_s^-1 y)`` with ``y = A(mu) (U_{k+1} - U_k)``;
+``time_deriv_nc = sqrt(max(nc(dU), 0) / dt)``; ``est = |eta| + |time_residual| + |time_deriv_nc|``.
+
+Not built (``NotImplementedError``): the elliptic-reconstruction terms (the reference's branch is ``assert False``,
+estimators.py:64), sharded discretizations (``S_ext != S``) and ``enrich_local``."""
+import numpy as np
+
+from pylrbms_amd.discretize_elliptic_block_swipdg_3d import (BlockDiscretization3D, ExtensionError3D, LRBMSReductor3D,
+                                                             ReducedDiscretization3D)
+from pylrbms_amd.discretize_parabolic_block_swipdg import ImplicitEulerTimeStepper
+from pylrbms_amd.parameters import CubicParameterSpace
+
+
+def _parabolic_estimate(d, mu, dt, eta_loc, time_residual2, time_deriv_nc2):
+    """ParabolicEstimator.estimate (estimators.py:141-168) from the local elliptic terms eta_loc [3, S, L] of the L vectors, the
+    summed time residuals y^T M^-1 y [L - 1] and the nc terms of the differences [S, L - 1] (all squared quantities)."""
+    nc, r, df = (np.asarray(x, dtype=np.float64) for x in eta_loc)
+    a_bar, a_hat, g_bar = d.alpha(mu, d.mu_bar), d.alpha(mu, d.mu_hat), d.gamma(mu, d.mu_bar)
+    eta = (np.sqrt(g_bar) * np.linalg.norm(nc, axis=0) + (1.0 / np.sqrt(a_hat)) * np.linalg.norm(r + df, axis=0)) / np.sqrt(a_bar)
+    time_residual = np.sqrt(np.asarray(time_residual2, dtype=np.float64) * (dt / 3))
+    s = 2 * np.sqrt(dt / 3)
+    eta, nc, r, df = eta * s, nc * s, r * s, df * s
+    time_deriv_nc = np.sqrt(np.maximum(np.asarray(time_deriv_nc2, dtype=np.float64), 0.0) / dt)
+    est = np.linalg.norm(eta) + np.linalg.norm(time_residual) + np.linalg.norm(time_deriv_nc)
+    return est, (nc, r, df, time_residual, time_deriv_nc)
+
+
+class InstationaryDiscretization3D(BlockDiscretization3D):
+    """The 3D block discretization with ``T``, ``time_stepper`` (implicit Euler, ``nt`` steps), zero ``initial_data`` [S, n] and
+    ``parameter_space``; built by ``discretize`` below."""
+
+    @property
+    def dt(self):
+        return self.T / self.time_stepper.nt
+
+    def solve(self, mu, rtol=1e-10, max_iter=50000, return_info=False):
+        """The trajectory as a device slab U [S, n, nt + 1] (U[:, :, 0] = the initial data): all nt implicit Euler steps in one
+        native call, each a warm-started two-level CG on M + dt A(mu).  ``last_solve_info`` = (total CG iterations, worst relative
+        residual)."""
+        eng = self.engine
+        U, info = eng.ctx.fom_implicit_euler(self.Q, self.theta(mu), self.dt, self.time_stepper.nt, eng.ops['A_diag'],
+                                             eng.ops['A_cpl'], eng.ops['b'], U0=self.initial_data, rtol=rtol, max_iter=max_iter)
+        self.last_solve_info = info
+        U = U.permute(1, 2, 0).contiguous()
+        return (U, info) if return_info else U
+
+    def solve_stationary(self, mu, rtol=1e-10, max_iter=50000, return_info=False):
+        """The elliptic solve of the underlying discretization (the limit t -> oo)."""
+        return BlockDiscretization3D.solve(self, mu, rtol=rtol, max_iter=max_iter, return_info=return_info)
+
+    def _elliptic_terms(self, U, mu):
+        """Local nc / r / df [3, S, L] of every column of U [S, n, L]: chunks of <= 64 // Q columns become a basis of the pass
+        (it takes Q N <= 64) and the batched estimate with identity coefficients evaluates each column's forms."""
+        import torch
+        eng = self.engine
+        theta = self.theta(mu)
+        step = max(1, 64 // self.Q)
+        out = []
+        for c0 in range(0, U.shape[2], step):
+            V = U[:, :, c0:c0 + step].contiguous()
+            L = V.shape[2]
+            buf = eng.project_and_estimate(V)
+            u = torch.eye(L, dtype=V.dtype, device=V.device).expand(eng.S_ext, L, L).contiguous()
+            out.append(eng.ctx.reduced_estimate_batch(self.Q, np.tile(theta, (L, 1)), u, buf, eng.ops, eng.hdiam))
+        return torch.cat(out, dim=2).cpu().numpy()
+
+    def estimate(self, U, mu, decompose=False):
+        """est, (local_eta_nc [S, nt+1], local_eta_r, local_eta_df, time_residual [nt], time_deriv_nc [S, nt]) of a trajectory
+        U [S, n, nt + 1] (``decompose`` is accepted for the API shape: the parts are always returned)."""
+        eng = self.engine
+        U = (U if isinstance(U, eng.ctx.torch.Tensor) else eng.ctx.from_numpy(np.asarray(U))).contiguous()
+        dU = (U[:, :, 1:] - U[:, :, :-1]).contiguous()
+        eta_loc = self._elliptic_terms(U, mu)
+        Y = eng.ctx.fom_apply(self.Q, self.theta(mu), eng.ops['A_diag'], eng.ops['A_cpl'], dU)
+        tr2 = eng.ctx.mass_inverse_norm2(Y).sum(dim=0).cpu().numpy()
+        tdnc2 = self._elliptic_terms(dU, mu)[0]
+        return _parabolic_estimate(self, mu, self.dt, eta_loc, tr2, tdnc2)
+
+
+class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
+    """``rd`` of the parabolic path: the reduced elliptic model plus the projected mass ``M_red`` [S, N, N]."""
+
+    def __init__(self, reductor, out, M_red):
+        super().__init__(reductor, out)
+        self.M_red = M_red
+        self.T, self.time_stepper = reductor.d.T, reductor.d.time_stepper
+
+    @property
+    def dt(self):
+        return self.T / self.time_stepper.nt
+
+    def solve(self, mu, rtol=1e-12, max_iter=20000, return_info=False):
+        """Reduced implicit Euler from zero: u [nt + 1, S, N] (one native call)."""
+        d = self.d
+        u, info = d.engine.ctx.reduced_implicit_euler(d.Q, d.theta(mu), self.dt, self.time_stepper.nt, self.out['B_sys'], self.M_red,
+                                                      self.out['rhs_red'], rtol=rtol, max_iter=max_iter)
+        self.last_solve_info = info
+        return (u, info) if return_info else u
+
+    def estimate(self, u, mu, decompose=False):
+        """The five parts of ``InstationaryDiscretization3D.estimate`` for reduced coefficients u [nt + 1, S, N]: the elliptic terms
+        from the batched reduced estimate (one parameter column per time step), the nc row of the same call on the differences, the
+        time residual with M_red^-1."""
+        d = self.d
+        eng, Q, theta = d.engine, d.Q, d.theta(mu)
+        u = u.contiguous()
+        du = (u[1:] - u[:-1]).contiguous()
+        L = u.shape[0]
+        eta_loc = eng.ctx.reduced_estimate_batch(Q, np.tile(theta, (L, 1)), u.permute(1, 2, 0).contiguous(), self.out, eng.ops,
+                                                 eng.hdiam).cpu().numpy()
+        tdnc2 = eng.ctx.reduced_estimate_batch(Q, np.tile(theta, (L - 1, 1)), du.permute(1, 2, 0).contiguous(), self.out, eng.ops,
+                                               eng.hdiam)[0].cpu().numpy()
+        tr2 = eng.ctx.reduced_time_residual(Q, theta, self.out['B_sys'], self.M_red, du).sum(dim=1).cpu().numpy()
+        return _parabolic_estimate(d, mu, self.dt, eta_loc, tr2, tdnc2)
+
+
+class ParabolicLRBMSReductor3D(LRBMSReductor3D):
+    """``ParabolicLRBMSReductor`` (2D: pylrbms_amd.reductor) for the 3D path.  ``extend_basis`` takes a trajectory [S, n, L]: its
+    vectors are Gram-Schmidt-ed into the local bases one after the other, a vector that is numerically in the span of a local basis
+    is skipped for that subdomain, ``ExtensionError3D`` if nothing was added anywhere; ``reduce()`` returns the instationary reduced
+    model; ``reconstruct(u)`` maps u [nt + 1, S, N] to [S, n, nt + 1]."""
+
+    def extend_basis(self, U, max_vectors=None):
+        U = self._as_slab(U)
+        added = 0
+        for k in range(U.shape[2]):
+            if max_vectors is not None and self.basis_size() >= max_vectors:
+                break
+            v, ok = self._orthonormalize(U[:, :, k:k + 1])
+            added += int(self._append(v, ok).sum())
+        if added == 0:
+            raise ExtensionError3D('no snapshot block extends its local basis')
+
+    def enrich_local(self, subdomain, U, mu=None):
+        raise NotImplementedError('online enrichment is not built for the parabolic 3D path')
+
+    def reduce(self):
+        rd = super().reduce()
+        M_red = self.d.engine.ctx.project_mass(self._V.contiguous())
+        return InstationaryReducedDiscretization3D(self, rd.out, M_red)
+
+    def reconstruct(self, u):
+        return self._torch.einsum('snj,ksj->snk', self._V, u).contiguous()
+
+
+def discretize(grid_and_problem_data, T, nt, device_index=0, elliptic_reconstruction=False):
+    """``(d, data)`` of the parabolic 3D path: the elliptic 3D ``discretize`` plus ``T``, implicit Euler with ``nt`` steps, zero
+    initial data and the parameter space."""
+    if elliptic_reconstruction:
+        raise NotImplementedError('elliptic_reconstruction: the reference never evaluates it (estimators.py:64 is assert False); '
+                                  'the 3D parabolic path does not build it')
+    grid = grid_and_problem_data['grid']
+    if getattr(grid, 'world_size', 1) > 1:
+        raise NotImplementedError('the 3D parabolic path needs all subdomains on one rank (sharded discretization: S_ext != S)')
+    d = InstationaryDiscretization3D(grid_and_problem_data, device_index=device_index)
+    eng = d.engine
+    if eng.S_ext != eng.S:
+        raise NotImplementedError('the 3D parabolic path needs all subdomains on one rank (sharded discretization: S_ext != S)')
+    if not (float(T) > 0.0) or int(nt) < 1:
+        raise ValueError('T > 0 and nt >= 1 required')
+    d.T = float(T)
+    d.time_stepper = ImplicitEulerTimeStepper(nt=nt, solver_options='operator')
+    d.initial_data = eng.ctx.zeros(eng.S, eng.t.n)
+    pr = d.parameter_range if d.parameter_range is not None else (0.1, 1.0)
+    d.parameter_space = CubicParameterSpace({'mu': ()}, pr[0], pr[1])
+    d.name = 'parabolic_block_swipdg_3d'
+    data = {'grid': d.grid, 'engine': eng, 'operators': eng.ops}
+    return d, data
