@@ -456,6 +456,41 @@ int64_t lrbms_reduced_time_residual_work_size(lrbms_ctx* ctx, int32_t N);
 int lrbms_reduced_time_residual(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t L, const double* theta, const double* B_sys,
                                 const double* M_red, const double* dU, double* work, double* out, void* stream);
 
+/* -- time-dependent affine sources of the parabolic path: f(t, mu) = sum_j phi_j(t, mu) f_j, K components ----------------
+ * The host evaluates the coefficient table phi [nt+1][K] (row 0: t = 0, row k: the time of step k);
+ * the library never evaluates an expression.  b_K [K][S][n] holds one load vector per component (lrbms_assemble_rhs on each
+ * component's samples).  Single rank (S_ext == S) throughout.
+ *
+ *   lrbms_assemble_source_gram      f_smp_K [K][S][n_T][f_stride] (K sample tables as for lrbms_assemble_rhs) ->
+ *                                   F2 [S][K][K] = (f_j, f_l)_{L2(Omega_s)}, rule `f2`; K = 1: F2 == f2 of lrbms_assemble_rhs
+ *                                   bit for bit.  K <= 64.
+ *   lrbms_fom_implicit_euler_src    lrbms_fom_implicit_euler with the step right-hand side M u_k + dt sum_j phi[k+1][j] b_j;
+ *                                   phi [nt+1][K] device.  Same work size, info and errors.
+ *   lrbms_reduced_implicit_euler_src  lrbms_reduced_implicit_euler with M_red u_k + dt sum_j phi[k+1][j] rhs_red_K[j];
+ *                                   rhs_red_K [K][S][N], phi [nt+1][K] device.  N <= 64.
+ *   lrbms_project_sources           for the basis V [S][n][N] (and D [S][n_T][5 Q N], the per-element divergence of its RT0
+ *                                   reconstruction images: lrbms_flux_reconstruct, then lrbms_div_apply mode 0):
+ *                                   rhs_red_K [K][S][N] = V_s^T b_j,s;  r_fd_K [K][S][5 Q N] = sum_T bsum_j[s,T] D[s,T,.]
+ *                                   with bsum the sum of b_j over the three DoFs of T.  K = 1 with the discretization's b: the
+ *                                   projection pass's rhs_red and r_fd.  One launch, fp64 MFMA.  K <= 64.
+ *   lrbms_reduced_source_terms      out [S][L] = (phi_l^T F2_s phi_l - 2 sum_j phi_lj r_fd_K[j][s]^T w_l(s)) (1/pi^2) / ceps[s] hdiam^2
+ *                                   for L columns u [S][N][L] (column fastest) with their own phi [L][K] (device); w_l(s) is the
+ *                                   theta-weighted neighbour stacking of the r_fd term of lrbms_reduced_estimate.  Added to the
+ *                                   r row of lrbms_reduced_estimate_batch run with f2 = 0 and r_fd = 0 it gives the residual
+ *                                   indicator for f = sum_j phi_lj f_j (the indicator is affine in (f2, r_fd)). */
+int lrbms_assemble_source_gram(lrbms_ctx* ctx, int32_t K, const double* f_smp_K, double* F2, void* stream);
+int lrbms_fom_implicit_euler_src(lrbms_ctx* ctx, int32_t Q, int32_t K, const double* theta, double dt, int32_t nt,
+                                 const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                 double* U, double rtol, int32_t max_iter, double* info, void* stream);
+int lrbms_reduced_implicit_euler_src(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, const double* theta, double dt, int32_t nt,
+                                     const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
+                                     double* work, double* U, double rtol, int32_t max_iter, double* info, void* stream);
+int lrbms_project_sources(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, const double* b_K, const double* V, const double* D,
+                          double* rhs_red_K, double* r_fd_K, void* stream);
+int lrbms_reduced_source_terms(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t L, const double* theta, const double* phi,
+                               const double* F2, const double* r_fd_K, const double* u, const double* ceps, double hdiam,
+                               double* out, void* stream);
+
 /* -- online enrichment (SURVEY.md section 8f "next" #1) ---------------------------------------------------- */
 /* Dirichlet correction blocks of the neighbourhood problems: on every coupling face of subdomain s, the boundary-form
  * diagonal block minus the inner-face block already contained in A_diag

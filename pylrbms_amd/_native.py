@@ -84,6 +84,14 @@ SIGNATURES = {
                                                     c_i32, _P_DBL, c_vp]),
     'lrbms_reduced_time_residual_work_size': (c_i64, [c_vp, c_i32]),
     'lrbms_reduced_time_residual': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'lrbms_assemble_source_gram': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'lrbms_fom_implicit_euler_src': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                    c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms_reduced_implicit_euler_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                        c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms_project_sources': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'lrbms_reduced_source_terms': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
+                                                  c_vp, c_vp]),
     'lrbms_assemble_dirichlet_correction': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms_local_correction_work_size': (c_i64, [c_vp, c_i32]),
     'lrbms_local_correction_solve': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_i32, _P_I32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
@@ -680,6 +688,90 @@ class NativeContext:
                                                   self._ptr(M_red, (S, N, N), 'M_red'), self._ptr(dU, (L, S, N), 'dU'),
                                                   c_vp(work.data_ptr()), c_vp(out.data_ptr()), self._stream())
         self._check(rc, 'lrbms_reduced_time_residual')
+        return out
+
+    # ------------------------------------------------------------------ time-dependent affine sources (parabolic path)
+    def assemble_source_gram(self, f_smp_K):
+        """f_smp_K [K, S, n_T, f_stride] -> F2 [S, K, K] = (f_j, f_l)_{L2(Omega_s)}."""
+        K, qd = f_smp_K.shape[0], self._quad()
+        F2 = self.empty(self.S, K, K)
+        rc = self.lib.lrbms_assemble_source_gram(self.handle, K, self._ptr(f_smp_K, (K, self.S, self.n_T, qd.f_stride), 'f_smp_K'),
+                                                 c_vp(F2.data_ptr()), self._stream())
+        self._check(rc, 'lrbms_assemble_source_gram')
+        return F2
+
+    def _phi(self, phi, rows=None):
+        phi = phi if hasattr(phi, 'data_ptr') else self.from_numpy(np.ascontiguousarray(np.asarray(phi, dtype=np.float64)))
+        assert phi.dim() == 2 and (rows is None or phi.shape[0] == rows), 'phi must be [{}, K]'.format(rows)
+        phi = phi.contiguous()
+        self._ptr(phi, tuple(phi.shape), 'phi')
+        return phi
+
+    def fom_implicit_euler_src(self, theta, dt, nt, A_diag, A_cpl, b_K, phi, U0=None, rtol=1e-12, max_iter=100000):
+        """(M + dt A(mu)) u_{k+1} = M u_k + dt sum_j phi[k+1, j] b_K[j] -> (U [nt + 1, S, n], info); phi [nt + 1, K]."""
+        Q, S, K = A_diag.shape[0], self.S, b_K.shape[0]
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        assert th.shape == (Q,)
+        ph = self._phi(phi, int(nt) + 1)
+        assert ph.shape[1] == K
+        work = self.empty(int(self.lib.lrbms_fom_solve_work_size(self.handle)))
+        U = self.zeros(int(nt) + 1, S, self.n)
+        if U0 is not None:
+            U[0] = U0.reshape(S, self.n)
+        info = np.zeros(2)
+        rc = self.lib.lrbms_fom_implicit_euler_src(self.handle, Q, K, _dblp(th), float(dt), int(nt),
+                                                   self._ptr(A_diag, (Q, S, self.n_T, 4, 9), 'A_diag'),
+                                                   self._ptr(A_cpl, (Q, S, 4, self.ncf, 9), 'A_cpl'),
+                                                   self._ptr(b_K, (K, S, self.n), 'b_K'), c_vp(ph.data_ptr()),
+                                                   c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), _dblp(info),
+                                                   self._stream())
+        self._check(rc, 'lrbms_fom_implicit_euler_src')
+        return U, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
+
+    def reduced_implicit_euler_src(self, theta, dt, nt, B_sys, M_red, rhs_red_K, phi, U0=None, rtol=1e-13, max_iter=20000):
+        """(M_red + dt A_red(mu)) u_{k+1} = M_red u_k + dt sum_j phi[k+1, j] rhs_red_K[j] -> (U [nt + 1, S, N], info)."""
+        Q, S, N, K = B_sys.shape[0], self.S, B_sys.shape[3], rhs_red_K.shape[0]
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        assert th.shape == (Q,)
+        ph = self._phi(phi, int(nt) + 1)
+        assert ph.shape[1] == K
+        work = self.empty(int(self.lib.lrbms_reduced_solve_work_size(self.handle, N)))
+        U = self.zeros(int(nt) + 1, S, N)
+        if U0 is not None:
+            U[0] = U0.reshape(S, N)
+        info = np.zeros(2)
+        rc = self.lib.lrbms_reduced_implicit_euler_src(self.handle, Q, N, K, _dblp(th), float(dt), int(nt),
+                                                       self._ptr(B_sys, (Q, S, 5, N, N), 'B_sys'), self._ptr(M_red, (S, N, N), 'M_red'),
+                                                       self._ptr(rhs_red_K, (K, S, N), 'rhs_red_K'), c_vp(ph.data_ptr()),
+                                                       c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter),
+                                                       _dblp(info), self._stream())
+        self._check(rc, 'lrbms_reduced_implicit_euler_src')
+        return U, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
+
+    def project_sources(self, Q, b_K, V, D, out=None):
+        """b_K [K, S, n], V [S(_ext), n, N], D [S, n_T, 5 Q N] -> (rhs_red_K [K, S, N], r_fd_K [K, S, 5 Q N])."""
+        K, S, N = b_K.shape[0], self.S, V.shape[2]
+        C = 5 * Q * N
+        rhs_K, rfd_K = out if out is not None else (self.empty(K, S, N), self.empty(K, S, C))
+        rc = self.lib.lrbms_project_sources(self.handle, Q, N, K, self._ptr(b_K, (K, S, self.n), 'b_K'),
+                                            self._ptr(V, (V.shape[0], self.n, N), 'V'), self._ptr(D, (S, self.n_T, C), 'D'),
+                                            self._ptr(rhs_K, (K, S, N), 'rhs_red_K'), self._ptr(rfd_K, (K, S, C), 'r_fd_K'),
+                                            self._stream())
+        self._check(rc, 'lrbms_project_sources')
+        return rhs_K, rfd_K
+
+    def reduced_source_terms(self, theta, phi, F2, r_fd_K, u, ceps, hdiam):
+        """u [S, N, L] (column fastest), phi [L, K] -> [S, L]: the source part of the scaled residual indicator."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        Q, S, N, L, K = len(th), self.S, u.shape[1], u.shape[2], F2.shape[1]
+        ph = self._phi(phi, L)
+        assert ph.shape[1] == K
+        out = self.empty(S, L)
+        rc = self.lib.lrbms_reduced_source_terms(self.handle, Q, N, K, L, _dblp(th), c_vp(ph.data_ptr()),
+                                                 self._ptr(F2, (S, K, K), 'F2'), self._ptr(r_fd_K, (K, S, 5 * Q * N), 'r_fd_K'),
+                                                 self._ptr(u, (S, N, L), 'u'), self._ptr(ceps, (S,), 'ceps'), float(hdiam),
+                                                 c_vp(out.data_ptr()), self._stream())
+        self._check(rc, 'lrbms_reduced_source_terms')
         return out
 
     # ------------------------------------------------------------------ online enrichment

@@ -214,6 +214,39 @@ __global__ __launch_bounds__(256) void k_assemble_rhs(Tmpl t, const Quad* __rest
   }
 }
 
+// Gram matrix of K source components per subdomain: F2[s][j][l] = (f_j, f_l)_{L2(Omega_s)} with rule `f2`, from the K sample
+// tables f_smp_K [K][S][n_T][f_stride] (the layout lrbms_assemble_rhs reads).  One workgroup per (s, pair j <= l), both
+// triangles written.  The per-element expression and the reduction are those of k_assemble_rhs, so F2[s][0][0] of K = 1
+// equals its f2[s] bit for bit.
+__global__ __launch_bounds__(256) void k_assemble_source_gram(Tmpl t, const Quad* __restrict__ qd, int S, int K,
+                                                              const double* __restrict__ f_smp_K, double* __restrict__ F2) {
+  __shared__ double red_sum[256];
+  const Quad& Q_ = *qd;
+  const int s = blockIdx.x;
+  int pr = blockIdx.y, j = 0;                  // pair index -> (j, l), j <= l, row by row
+  while (pr >= K - j) { pr -= K - j; ++j; }
+  const int l = j + pr;
+  const long tab = (long)S * t.nT * Q_.f_stride;
+  double acc = 0.0;
+  for (int e = threadIdx.x; e < t.nT; e += blockDim.x) {
+    const double* fa = f_smp_K + j * tab + ((long)s * t.nT + e) * Q_.f_stride;
+    const double* fb = f_smp_K + l * tab + ((long)s * t.nT + e) * Q_.f_stride;
+    double sq = 0.0;
+    for (int k = 0; k < Q_.f2.n; ++k) sq += Q_.f2.w[k] * t.area[e] * fa[Q_.o_ff2 + k] * fb[Q_.o_ff2 + k];
+    acc += sq;
+  }
+  red_sum[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) red_sum[threadIdx.x] += red_sum[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    F2[((long)s * K + j) * K + l] = red_sum[0];
+    F2[((long)s * K + l) * K + j] = red_sum[0];
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // K6 + K9.  One thread per (s, e).
 __global__ __launch_bounds__(256) void k_assemble_products(Tmpl t, const Quad* __restrict__ qd, int S, int S_ext,
@@ -453,6 +486,13 @@ int launch_assemble_swipdg(lrbms_ctx* ctx, int Q, const double* lam, double* A_d
   dim3 grid((unsigned)((total + 255) / 256), Q);
   if (!ctx->qdev) return lrbms_fail(ctx, LRBMS_E_STATE, "quadrature not set (lrbms_set_quadrature)");
   hipLaunchKernelGGL(k_assemble_swipdg, grid, dim3(256), 0, st, t, ctx->qdev, ctx->S, ctx->S_ext, ctx->nbr, lam, A_diag, A_cpl);
+  LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}
+
+int launch_assemble_source_gram(lrbms_ctx* ctx, int K, const double* f_smp_K, double* F2, hipStream_t st) {
+  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_source_gram: K must be in [1, 64]");
+  hipLaunchKernelGGL(k_assemble_source_gram, dim3(ctx->S, K * (K + 1) / 2), dim3(256), 0, st, ctx->t, ctx->qdev, ctx->S, K, f_smp_K, F2);
   LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }

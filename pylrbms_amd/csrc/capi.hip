@@ -37,6 +37,17 @@ int launch_reduced_implicit_euler(lrbms_ctx* ctx, int Q, int N, const double* th
                                   int max_iter, double* info, hipStream_t st);
 int launch_reduced_time_residual(lrbms_ctx* ctx, int Q, int N, int L, const double* theta, const double* B_sys, const double* M_red,
                                  const double* dU, double* work, double* out, hipStream_t st);
+int launch_fom_implicit_euler_src(lrbms_ctx* ctx, int Q, int K, const double* theta, double dt, int nt, const double* A_diag,
+                                  const double* A_cpl, const double* bK, const double* phi, double* work, double* U, double rtol,
+                                  int max_iter, double* info, hipStream_t st);
+int launch_reduced_implicit_euler_src(lrbms_ctx* ctx, int Q, int N, int K, const double* theta, double dt, int nt,
+                                      const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
+                                      double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st);
+int launch_reduced_source_terms(lrbms_ctx* ctx, int Q, int N, int K, int L, const double* theta, const double* phi, const double* F2,
+                                const double* r_fd_K, const double* u, const double* ceps, double hdiam, double* out, hipStream_t st);
+int launch_assemble_source_gram(lrbms_ctx* ctx, int K, const double* f_smp_K, double* F2, hipStream_t st);
+int launch_project_sources(lrbms_ctx* ctx, int N, int C, int K, const double* bK, const double* V, const double* D, double* rhs_K,
+                           double* rfd_K, hipStream_t st);
 void coarse_release(lrbms_ctx* ctx);   // online.hip
 int64_t reduced_precond_size(lrbms_ctx* ctx, int N);
 int launch_reduced_precond_build(lrbms_ctx* ctx, int Q, int N, const double* theta, const double* B_sys, double* work, double* pc,
@@ -673,6 +684,46 @@ int lrbms_reduced_implicit_euler(lrbms_ctx* ctx, int32_t Q, int32_t N, const dou
   CHECK_PTR(ctx, rhs_red); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
   return launch_reduced_implicit_euler(ctx, Q, N, theta, dt, nt, B_sys, M_red, rhs_red, work, U, rtol, max_iter, info,
                                        (hipStream_t)stream);
+}
+
+int lrbms_assemble_source_gram(lrbms_ctx* ctx, int32_t K, const double* f_smp_K, double* F2, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_PTR(ctx, f_smp_K); CHECK_PTR(ctx, F2);
+  if (!ctx->qdev) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_source_gram: lrbms_set_quadrature first");
+  return launch_assemble_source_gram(ctx, K, f_smp_K, F2, (hipStream_t)stream);
+}
+
+int lrbms_fom_implicit_euler_src(lrbms_ctx* ctx, int32_t Q, int32_t K, const double* theta, double dt, int32_t nt,
+                                 const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                 double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, 1); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, A_diag); CHECK_PTR(ctx, A_cpl);
+  CHECK_PTR(ctx, b_K); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
+  return launch_fom_implicit_euler_src(ctx, Q, K, theta, dt, nt, A_diag, A_cpl, b_K, phi, work, U, rtol, max_iter, info,
+                                       (hipStream_t)stream);
+}
+
+int lrbms_reduced_implicit_euler_src(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, const double* theta, double dt, int32_t nt,
+                                     const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
+                                     double* work, double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, B_sys); CHECK_PTR(ctx, M_red);
+  CHECK_PTR(ctx, rhs_red_K); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
+  return launch_reduced_implicit_euler_src(ctx, Q, N, K, theta, dt, nt, B_sys, M_red, rhs_red_K, phi, work, U, rtol, max_iter, info,
+                                           (hipStream_t)stream);
+}
+
+int lrbms_project_sources(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, const double* b_K, const double* V, const double* D,
+                          double* rhs_red_K, double* r_fd_K, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, b_K); CHECK_PTR(ctx, V); CHECK_PTR(ctx, D);
+  CHECK_PTR(ctx, rhs_red_K); CHECK_PTR(ctx, r_fd_K);
+  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources needs all subdomains on one rank");
+  return launch_project_sources(ctx, N, 5 * Q * N, K, b_K, V, D, rhs_red_K, r_fd_K, (hipStream_t)stream);
+}
+
+int lrbms_reduced_source_terms(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t L, const double* theta, const double* phi,
+                               const double* F2, const double* r_fd_K, const double* u, const double* ceps, double hdiam,
+                               double* out, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, F2);
+  CHECK_PTR(ctx, r_fd_K); CHECK_PTR(ctx, u); CHECK_PTR(ctx, ceps); CHECK_PTR(ctx, out);
+  return launch_reduced_source_terms(ctx, Q, N, K, L, theta, phi, F2, r_fd_K, u, ceps, hdiam, out, (hipStream_t)stream);
 }
 
 int64_t lrbms_reduced_time_residual_work_size(lrbms_ctx* ctx, int32_t N) {

@@ -293,6 +293,41 @@ __global__ __launch_bounds__(256) void k_fom_step_residual(Tmpl t, long ne, doub
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
+// the same with a time-dependent affine source:  r = M u_k + dt sum_j phi_j b_j - y,  b_j = bK + j nv (bK [K][S][n]),
+// phi = the coefficient row of the step (device, K entries).  With K = 1 and phi = 1 the expressions are those of
+// k_fom_step_residual (1.0 * b == b), so the two agree bit for bit.
+__global__ __launch_bounds__(256) void k_fom_step_residual_src(Tmpl t, long ne, double dt, const double* __restrict__ uk, int K,
+                                                               const double* __restrict__ phi, const double* __restrict__ bK,
+                                                               const double* __restrict__ y, double* __restrict__ r,
+                                                               double* __restrict__ partial) {
+  __shared__ double red[256];
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long nv = ne * 3;
+  double acc = 0.0;
+  if (idx < ne) {
+    const double m = t.area[idx % t.nT] / 12.0;
+    const double u0 = uk[idx * 3], u1 = uk[idx * 3 + 1], u2 = uk[idx * 3 + 2];
+    const double sum = u0 + u1 + u2;
+    const double uv[3] = {u0, u1, u2};
+    double bk[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < K; ++j) {
+      const double pj = phi[j];
+      const double* bj = bK + (long)j * nv + idx * 3;
+      for (int i = 0; i < 3; ++i) bk[i] += pj * bj[i];
+    }
+    for (int i = 0; i < 3; ++i) {
+      // the contraction k_fom_step_residual compiles to (fma of the mass term onto dt b), spelled out: the compiler would
+      // otherwise fuse dt * bk instead and the two kernels would differ in the last bit
+      const double dtb = dt * bk[i];
+      const double rhs = __fma_rn(m, sum + uv[i], dtb);
+      r[idx * 3 + i] = rhs - y[idx * 3 + i];
+      acc += rhs * rhs;
+    }
+  }
+  const double s = block_sum_256(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
 // Coarse level (see online.hip): the span of the subdomain indicator functions.  A0[s][t] = 1^T A_st 1: the sum of all
 // entries of the combined blocks between subdomains s and t.  One workgroup per subdomain.
 __global__ __launch_bounds__(256) void k_fom_coarse_entries(Tmpl t, int S, const int* __restrict__ nbr, const double* __restrict__ Amu_d,
@@ -532,13 +567,15 @@ int launch_fom_solve(lrbms_ctx* ctx, int Q, const double* theta, const double* A
   return LRBMS_OK;
 }
 
-// Implicit Euler for M u' + A(mu) u = b (pyMOR ImplicitEulerTimeStepper as used at discretize_parabolic_block_swipdg.py:87;
-// InstationaryDuneDiscretization._solve :28-40):  (M + dt A(mu)) u_{k+1} = M u_k + dt b,  nt steps in ONE call: the
-// theta-weighted blocks (+ the mass on the diagonal 3x3 blocks) are combined once, every step is a warm-started CG with
-// the kernels of lrbms_fom_solve.  U [nt+1][S][n]: U[0] is the initial value (input), U[1..nt] are written.
-// info[0] = CG iterations over all steps, info[1] = worst final residual relative to |M u_k + dt b|.
-int launch_fom_implicit_euler(lrbms_ctx* ctx, int Q, const double* theta, double dt, int nt, const double* A_diag, const double* A_cpl,
-                              const double* b, double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st) {
+namespace {
+
+// The time loop shared by lrbms_fom_implicit_euler and lrbms_fom_implicit_euler_src: combine (M + dt A(mu)) once, then per
+// step y = (M + dt A) u_k, the step's right-hand side and residual (`step_rhs(step, uk, c)` launches the kernel that writes
+// c.r and the |rhs|^2 partials into c.ppap), and a warm-started CG.
+template <typename StepRhs>
+int fom_euler_run(lrbms_ctx* ctx, const char* name, int Q, const double* theta, double dt, int nt, const double* A_diag,
+                  const double* A_cpl, double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st,
+                  StepRhs&& step_rhs) {
   if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler needs all subdomains on one rank");
   if (Q < 1 || Q > 8 || max_iter < 1 || !(rtol > 0.0) || nt < 1 || !(dt > 0.0))
     return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: bad Q / max_iter / rtol / nt / dt");
@@ -560,7 +597,7 @@ int launch_fom_implicit_euler(lrbms_ctx* ctx, int Q, const double* theta, double
     // y = (M + dt A) u_k  (the matvec kernel with first = 1 takes its direction from `z`)
     hipLaunchKernelGGL(k_fom_cg_matvec, dim3(c.nmv), dim3(256), 0, st, ctx->t, ctx->S, ctx->nbr, c.Amu_d, c.Amu_c, uk, c.p[1], c.prz[0],
                        c.prz[1], nblk, 1, (const double*)nullptr, c.p[0], c.y, c.ppap);
-    hipLaunchKernelGGL(k_fom_step_residual, dim3(nblk), dim3(256), 0, st, ctx->t, c.ne, dt, uk, b, c.y, c.r, c.ppap);
+    step_rhs(step, uk, c);
     LRBMS_LAUNCH_CHECK(ctx);
     double ref2 = 0.0;
     if (int rc = fom_host_sum(ctx, c.ppap, host, &ref2, st)) return rc;
@@ -572,9 +609,38 @@ int launch_fom_implicit_euler(lrbms_ctx* ctx, int Q, const double* theta, double
     if (rel > worst) worst = rel;
     if (rel > rtol) {
       if (info) { info[0] = (double)total_it; info[1] = worst; }
-      return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_implicit_euler: CG did not reach rtol");
+      return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name);
     }
   }
   if (info) { info[0] = (double)total_it; info[1] = worst; }
   return LRBMS_OK;
+}
+
+}  // namespace
+
+// Implicit Euler for M u' + A(mu) u = b (pyMOR ImplicitEulerTimeStepper as used at discretize_parabolic_block_swipdg.py:87;
+// InstationaryDuneDiscretization._solve :28-40):  (M + dt A(mu)) u_{k+1} = M u_k + dt b,  nt steps in ONE call: the
+// theta-weighted blocks (+ the mass on the diagonal 3x3 blocks) are combined once, every step is a warm-started CG with
+// the kernels of lrbms_fom_solve.  U [nt+1][S][n]: U[0] is the initial value (input), U[1..nt] are written.
+// info[0] = CG iterations over all steps, info[1] = worst final residual relative to |M u_k + dt b|.
+int launch_fom_implicit_euler(lrbms_ctx* ctx, int Q, const double* theta, double dt, int nt, const double* A_diag, const double* A_cpl,
+                              const double* b, double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st) {
+  return fom_euler_run(ctx, "fom_implicit_euler: CG did not reach rtol", Q, theta, dt, nt, A_diag, A_cpl, work, U, rtol, max_iter,
+                       info, st, [&](int, const double* uk, FomCg& c) {
+    hipLaunchKernelGGL(k_fom_step_residual, dim3(c.nblk), dim3(256), 0, st, ctx->t, c.ne, dt, uk, b, c.y, c.r, c.ppap);
+  });
+}
+
+// The same with the time-dependent affine source f(t, mu) = sum_j phi_j(t, mu) f_j:
+//   (M + dt A(mu)) u_{k+1} = M u_k + dt sum_j phi[k+1][j] b_j,   bK [K][S][n], phi [nt+1][K] (device; row k+1 = step k).
+// Only the kernel that forms the step's right-hand side differs from launch_fom_implicit_euler.
+int launch_fom_implicit_euler_src(lrbms_ctx* ctx, int Q, int K, const double* theta, double dt, int nt, const double* A_diag,
+                                  const double* A_cpl, const double* bK, const double* phi, double* work, double* U, double rtol,
+                                  int max_iter, double* info, hipStream_t st) {
+  if (K < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_src: K < 1");
+  return fom_euler_run(ctx, "fom_implicit_euler_src: CG did not reach rtol", Q, theta, dt, nt, A_diag, A_cpl, work, U, rtol,
+                       max_iter, info, st, [&](int step, const double* uk, FomCg& c) {
+    hipLaunchKernelGGL(k_fom_step_residual_src, dim3(c.nblk), dim3(256), 0, st, ctx->t, c.ne, dt, uk, K, phi + (long)(step + 1) * K,
+                       bK, c.y, c.r, c.ppap);
+  });
 }

@@ -497,6 +497,65 @@ __global__ __launch_bounds__(64) void k_red_step_residual(int N, double dt, cons
   if (threadIdx.x == 0) partial[s] = acc;
 }
 
+// the same with a time-dependent affine source: b_s = sum_j phi_j bK[j][s] (bK [K][S][N], phi the step's row, device).
+// K = 1, phi = 1: the expressions of k_red_step_residual (1.0 * b == b), bit for bit.
+__global__ __launch_bounds__(64) void k_red_step_residual_src(int S, int N, double dt, const double* __restrict__ M_red,
+                                                              const double* __restrict__ uk, int K, const double* __restrict__ phi,
+                                                              const double* __restrict__ bK, const double* __restrict__ y,
+                                                              double* __restrict__ r, double* __restrict__ partial) {
+  extern __shared__ double lds[];
+  const int s = blockIdx.x;
+  for (int i = threadIdx.x; i < N; i += 64) lds[i] = uk[(long)s * N + i];
+  __syncthreads();
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < N; i += 64) {
+    const double* row = M_red + ((long)s * N + i) * N;
+    double bk = 0.0;
+    for (int j = 0; j < K; ++j) bk += phi[j] * bK[((long)j * S + s) * N + i];
+    double rhs = dt * bk;
+    for (int c = 0; c < N; ++c) rhs += row[c] * lds[c];
+    r[(long)s * N + i] = rhs - y[(long)s * N + i];
+    acc += rhs * rhs;
+  }
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if (threadIdx.x == 0) partial[s] = acc;
+}
+
+// Source part of the residual indicator for L coefficient columns with their own source coefficients phi_l [L][K]:
+//   out[s][l] = (phi_l^T F2_s phi_l - 2 sum_j phi_lj r_fd_K[j][s]^T w_l(s)) (1/pi^2) / ceps[s] hdiam^2
+// with w_l(s)[(slot, q, i)] = theta_q u[nbr(s, slot)][i][l] (the stacking of the r_fd term of k_reduced_estimate), u [S][N][L]
+// (column fastest), F2 [S][K][K], r_fd_K [K][S][5 Q N].  One workgroup per subdomain, one wave per column (strided).
+__global__ __launch_bounds__(256) void k_reduced_source_terms(int S, const int* __restrict__ nbr, int Q, int N, int K, int L, QVec theta,
+                                                              const double* __restrict__ phi, const double* __restrict__ F2,
+                                                              const double* __restrict__ r_fd_K, const double* __restrict__ u,
+                                                              const double* __restrict__ ceps, double hdiam, double* __restrict__ out) {
+  const int s = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int QN = Q * N, C = 5 * QN;
+  const double pi = 3.14159265358979323846;
+  const double scale = ((1.0 / (pi * pi)) / ceps[s]) * hdiam * hdiam;
+  for (int l = wave; l < L; l += 4) {
+    const double* ph = phi + (long)l * K;
+    double lin = 0.0;
+    for (int c = lane; c < C; c += 64) {
+      const int slot = c / QN, rem = c - slot * QN, q = rem / N, i = rem - q * N;
+      const int s2 = nbr[s * 5 + slot];
+      if (s2 < 0) continue;
+      const double w = theta.v[q] * u[((long)s2 * N + i) * L + l];
+      double g = 0.0;
+      for (int j = 0; j < K; ++j) g += ph[j] * r_fd_K[((long)j * S + s) * C + c];
+      lin += g * w;
+    }
+    for (int off = 32; off > 0; off >>= 1) lin += __shfl_down(lin, off, 64);
+    if (lane == 0) {
+      const double* F = F2 + (long)s * K * K;
+      double quad = 0.0;
+      for (int j = 0; j < K; ++j)
+        for (int m = 0; m < K; ++m) quad += ph[j] * F[j * K + m] * ph[m];
+      out[(long)s * L + l] = (quad - 2.0 * lin) * scale;
+    }
+  }
+}
+
 // out[s] = y_s^T Dinv[s] y_s  (one wave per subdomain)
 __global__ __launch_bounds__(64) void k_red_inv_norm2(int N, const double* __restrict__ Dinv, const double* __restrict__ y,
                                                       double* __restrict__ out) {
@@ -1201,13 +1260,15 @@ int launch_reduced_solve(lrbms_ctx* ctx, int Q, int N, const double* theta, cons
   return LRBMS_OK;
 }
 
-// Reduced implicit Euler (SURVEY.md section 8f #3; the reduced counterpart of InstationaryDuneDiscretization._solve,
-// discretize_parabolic_block_swipdg.py:28-40):  (M_red + dt sum_q theta_q B_q) u_{k+1} = M_red u_k + dt rhs_red.
-// The step operator and its block-Jacobi preconditioner are built once, every step is a warm-started PCG with the
-// kernels of lrbms_reduced_solve.  U [nt+1][S][N]: U[0] initial value (input), U[1..nt] written.
-int launch_reduced_implicit_euler(lrbms_ctx* ctx, int Q, int N, const double* theta, double dt, int nt, const double* B_sys,
-                                  const double* M_red, const double* rhs_red, double* work, double* U, double rtol,
-                                  int max_iter, double* info, hipStream_t st) {
+namespace {
+
+// The time loop shared by lrbms_reduced_implicit_euler and lrbms_reduced_implicit_euler_src: the step operator and its
+// preconditioner are built once; per step y = (M + dt A) u_k, then `step_rhs(step, uk, b)` launches the kernel that forms the
+// step's right-hand side, writes b.r and the |rhs|^2 partials into b.ppap, then a warm-started PCG.
+template <typename StepRhs>
+int red_euler_run(lrbms_ctx* ctx, const char* name, int Q, int N, const double* theta, double dt, int nt, const double* B_sys,
+                  const double* M_red, double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st,
+                  StepRhs&& step_rhs) {
   if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler needs all subdomains on one rank");
   if (N > 64 || N < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: N > 64 not supported by the block inverse");
   if (Q < 1 || Q > 8 || nt < 1 || !(dt > 0.0) || !(rtol > 0.0) || max_iter < 1)
@@ -1239,7 +1300,7 @@ int launch_reduced_implicit_euler(lrbms_ctx* ctx, int Q, int N, const double* th
     else
       hipLaunchKernelGGL(k_cg2_matvec<false>, dim3(S), dim3(256), sizeof(double) * 10 * N, st, ctx->nbr, S, N, b.Amu, uk, b.p[1], b.prz[0],
                          b.prz[1], 1, b.p[0], b.y, b.ppap);
-    hipLaunchKernelGGL(k_red_step_residual, dim3(S), dim3(64), sizeof(double) * N, st, N, dt, M_red, uk, rhs_red, b.y, b.r, b.ppap);
+    step_rhs(step, uk, b);
     LRBMS_LAUNCH_CHECK(ctx);
     double ref2 = 0.0;
     if (int rc = host_sum(ctx, b.ppap, host, &ref2, st)) return rc;
@@ -1251,10 +1312,51 @@ int launch_reduced_implicit_euler(lrbms_ctx* ctx, int Q, int N, const double* th
     if (rel > worst) worst = rel;
     if (rel > rtol) {
       if (info) { info[0] = (double)total_it; info[1] = worst; }
-      return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_implicit_euler: CG did not reach rtol");
+      return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name);
     }
   }
   if (info) { info[0] = (double)total_it; info[1] = worst; }
+  return LRBMS_OK;
+}
+
+}  // namespace
+
+// Reduced implicit Euler (SURVEY.md section 8f #3; the reduced counterpart of InstationaryDuneDiscretization._solve,
+// discretize_parabolic_block_swipdg.py:28-40):  (M_red + dt sum_q theta_q B_q) u_{k+1} = M_red u_k + dt rhs_red.
+// The step operator and its block-Jacobi preconditioner are built once, every step is a warm-started PCG with the
+// kernels of lrbms_reduced_solve.  U [nt+1][S][N]: U[0] initial value (input), U[1..nt] written.
+int launch_reduced_implicit_euler(lrbms_ctx* ctx, int Q, int N, const double* theta, double dt, int nt, const double* B_sys,
+                                  const double* M_red, const double* rhs_red, double* work, double* U, double rtol,
+                                  int max_iter, double* info, hipStream_t st) {
+  return red_euler_run(ctx, "reduced_implicit_euler: CG did not reach rtol", Q, N, theta, dt, nt, B_sys, M_red, work, U, rtol,
+                       max_iter, info, st, [&](int, const double* uk, RedCg& b) {
+    hipLaunchKernelGGL(k_red_step_residual, dim3(ctx->S), dim3(64), sizeof(double) * N, st, N, dt, M_red, uk, rhs_red, b.y, b.r, b.ppap);
+  });
+}
+
+// The same with the time-dependent affine source: rhs_red of step k is sum_j phi[k+1][j] rhs_red_K[j]
+// (rhs_red_K [K][S][N], phi [nt+1][K] device).  Only the step's right-hand side kernel differs.
+int launch_reduced_implicit_euler_src(lrbms_ctx* ctx, int Q, int N, int K, const double* theta, double dt, int nt,
+                                      const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
+                                      double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st) {
+  if (K < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_src: K < 1");
+  return red_euler_run(ctx, "reduced_implicit_euler_src: CG did not reach rtol", Q, N, theta, dt, nt, B_sys, M_red, work, U, rtol,
+                       max_iter, info, st, [&](int step, const double* uk, RedCg& b) {
+    hipLaunchKernelGGL(k_red_step_residual_src, dim3(ctx->S), dim3(64), sizeof(double) * N, st, ctx->S, N, dt, M_red, uk, K,
+                       phi + (long)(step + 1) * K, rhs_red_K, b.y, b.r, b.ppap);
+  });
+}
+
+// Source part of the residual indicator for L columns (k_reduced_source_terms): out [S][L], single rank.
+int launch_reduced_source_terms(lrbms_ctx* ctx, int Q, int N, int K, int L, const double* theta, const double* phi, const double* F2,
+                                const double* r_fd_K, const double* u, const double* ceps, double hdiam, double* out, hipStream_t st) {
+  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms needs all subdomains on one rank");
+  if (N < 1 || L < 1 || K < 1 || Q < 1 || Q > 8) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: bad N / L / K / Q");
+  QVec th;
+  for (int q = 0; q < 8; ++q) th.v[q] = q < Q ? theta[q] : 0.0;
+  hipLaunchKernelGGL(k_reduced_source_terms, dim3(ctx->S), dim3(256), 0, st, ctx->S, ctx->nbr, Q, N, K, L, th, phi, F2, r_fd_K, u, ceps,
+                     hdiam, out);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 

@@ -13,6 +13,15 @@ with ``nt`` steps (:87).  The reference's version does not run at HEAD (SURVEY.m
 operator plus the mass is combined once, every step is a warm-started CG on it.  On a sharded discretization the solves
 run on the gathered operator, and so does the time residual of the parabolic estimate (its elliptic-reconstruction
 variant needs all subdomains on one rank).
+
+Time-dependent affine sources (the reference's artificial-channels problem, python/scripts/parabolic.py):
+``p['f'] = {'functions': [f_0 .. f_{K-1}], 'coefficients': [phi_0 .. phi_{K-1}]}`` with coefficients that may read ``mu`` and
+``'_t'``.  The host evaluates ``phi [nt + 1][K]`` once per ``mu`` (``d.source_coefficients(mu)``: row 0 at t = 0, row k at the time
+of step k accumulated as pyMOR's implicit Euler does, ``t += dt``); the load vectors ``b_K [K][S][n]`` and the Grams
+``F2 [S][K][K]`` are assembled once.  ``solve`` -> ``lrbms_fom_implicit_euler_src``; the estimate evaluates the elliptic part of
+``U_k`` with ``f(t_k, mu)`` (row k): ``lrbms_reduced_estimate_batch`` with f2 = 0, r_fd = 0 plus ``lrbms_project_sources`` /
+``lrbms_reduced_source_terms``.  A single component with coefficient 1 takes the path above unchanged.
+Single rank only; the elliptic reconstruction is not available with such a source.
 """
 import numpy as np
 
@@ -38,6 +47,31 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         opts = inverse_options if isinstance(inverse_options, dict) else {}
         return min(float(opts.get('precision', 1e-12)), 1e-10), max(int(opts.get('max_iter', 20000)), 20000)
 
+    _src = None       # the time-dependent source (``_setup_sources``), None: one component with coefficient 1
+
+    def source_coefficients(self, mu):
+        """``phi [nt + 1][K]`` (fp64, host) of the time-dependent source at ``mu``: row 0 at t = 0, row k at the time of step k,
+        accumulated like pyMOR's ``implicit_euler`` (``t += dt``, then ``mu['_t'] = t``).  A plain number as
+        coefficient is a constant."""
+        if self._src is None:
+            return np.ones((self.time_stepper.nt + 1, 1))
+        from pylrbms_amd.parameters import Parameter
+        mu = self.parse_parameter(mu)
+        nt = self.time_stepper.nt
+        dt = self.T / nt
+        coeffs = self._src['coefficients']
+        phi = np.empty((nt + 1, len(coeffs)))
+        t = 0.0
+        for k in range(nt + 1):
+            if k > 0:
+                t += dt
+            mu_t = Parameter(dict(mu, _t=np.array(t)))
+            phi[k] = [c.evaluate(mu_t) if hasattr(c, 'evaluate') else float(c) for c in coeffs]
+        return phi
+
+    def _phi_device(self, mu):
+        return self.engine.ctx.from_numpy(np.ascontiguousarray(self.source_coefficients(mu)))
+
     def solve(self, mu, inverse_options=None):
         """``_solve`` (:28-40): ``nt + 1`` vectors, the first one the (zero) initial data."""
         import torch
@@ -45,6 +79,11 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         rtol, max_iter = self._solve_options(inverse_options)
         dt = self.T / self.time_stepper.nt
         U0 = self.initial_data.tensor[:, :, 0] if self.initial_data is not None else None
+        if self._src is not None:
+            U, info = eng.ctx.fom_implicit_euler_src(self.theta(mu), dt, self.time_stepper.nt, eng.A_diag, eng.A_cpl,
+                                                     self._src['b_K'], self._phi_device(mu), U0=U0, rtol=rtol, max_iter=max_iter)
+            self.last_solve_info = info
+            return BlockVectorArray(U.permute(1, 2, 0), self.solution_space)
         if eng.S_ext != eng.S:
             # sharded: like the stationary solve, on the gathered block operator (DuneDiscretization._global_fom); the
             # initial data of the reference is zero (:82), a non-zero one would have to be gathered as well
@@ -62,7 +101,45 @@ class InstationaryDuneDiscretization(DuneDiscretization):
 
     def solve_stationary(self, mu, inverse_options=None):
         """The elliptic solve of the underlying discretization (the limit ``t -> oo``)."""
+        if self._src is not None:
+            raise NotImplementedError('solve_stationary: the source depends on time (f = sum_j phi_j(t, mu) f_j)')
         return DuneDiscretization.solve(self, mu, inverse_options=inverse_options)
+
+    def _source_rows(self, mu, L):
+        """The phi rows of the columns of an array of ``L`` vectors: the trajectory's rows if ``L == nt + 1``; otherwise None
+        (no source: the time-derivative term reads only the nonconformity of U_{k+1} - U_k, which does not involve f)."""
+        if self._src is None or L != self.time_stepper.nt + 1:
+            return None
+        return self._phi_device(mu)
+
+    def _local_estimates(self, U, mu):
+        """With a time-dependent source: the indicators of U_k for f(t_k, mu) = sum_j phi[k][j] f_j.  The source-free part is
+        the batched estimate with f2 = 0 and r_fd = 0; the f terms of the residual indicator come from
+        ``lrbms_project_sources`` on the same chunk (identity coefficients) and ``lrbms_reduced_source_terms``."""
+        if self._src is None:
+            return DuneDiscretization._local_estimates(self, U, mu)
+        import torch
+        eng, c = self.engine, self.engine.ctx
+        theta = self.theta(mu)
+        rows = self._source_rows(mu, len(U))
+        zero_f2 = c.zeros(eng.S)
+        out = []
+        for c0 in range(0, len(U), 16):
+            V = U.tensor[:, :, c0:c0 + 16].contiguous()
+            L = V.shape[2]
+            buf = eng.project_and_estimate(V, project_system=False)
+            grams = list(buf['grams'])
+            grams[1] = torch.zeros_like(grams[1])                             # r_fd of the engine's own b: not used
+            u = torch.eye(L, dtype=V.dtype, device=V.device).expand(eng.S, L, L).contiguous()
+            eta = c.reduced_estimate_batch(np.tile(theta, (L, 1)), u, tuple(grams), zero_f2, eng.ceps, eng.hdiam)
+            if rows is not None:
+                D = c.div_apply(c.flux_reconstruct(eng.F, V), mode=0)
+                _, r_fd_K = c.project_sources(eng.Q, self._src['b_K'], V, D)
+                eta[1] += c.reduced_source_terms(theta, rows[c0:c0 + L].contiguous(), self._src['F2'], r_fd_K, u, eng.ceps,
+                                                 eng.hdiam)
+            out.append(eta)
+        eta = torch.cat(out, dim=2)
+        return eta[0], eta[1], eta[2]
 
     def _time_residual_norm2(self, dU, mu):
         """``R = operator.apply(dU, mu); l2_product.apply_inverse(R).pairwise_dot(R)`` (estimators.py:146-148): [len(dU)]."""
@@ -102,9 +179,49 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         return torch.cat(out, dim=1)
 
 
+def _source_components(p):
+    """(functions, coefficients) of a source that is not one component with coefficient 1 (the elliptic path's only form,
+    discretize_elliptic_block_swipdg.discretize), else None."""
+    f = p['f']
+    if not isinstance(f, dict):
+        return None
+    funcs, coeffs = list(f['functions']), list(f['coefficients'])
+    if len(funcs) != len(coeffs) or not funcs:
+        raise ValueError("p['f'] needs as many coefficients as functions (and at least one)")
+    if len(funcs) == 1 and not hasattr(coeffs[0], 'evaluate') and coeffs[0] == 1:
+        return None
+    return funcs, coeffs
+
+
+def _setup_sources(d, funcs, coeffs):
+    """Load vectors b_K [K][S][n] (``lrbms_assemble_rhs`` per component) and Grams F2 [S][K][K] (``lrbms_assemble_source_gram``)
+    of the K source components, sampled at the points of the engine's rules ``rhs`` / ``f2``."""
+    import torch
+    from pylrbms_amd.engine import sample_function, volume_record_points
+    eng = d.engine
+    sp = eng.quadrature
+    xf, cl, kl = volume_record_points(eng.grid, eng.local, (sp.rhs, sp.f2))
+    f_smp_K = eng.ctx.from_numpy(np.ascontiguousarray(np.stack([sample_function(fn, xf, cl, kl) for fn in funcs])))
+    b_K = torch.stack([eng.ctx.assemble_rhs(f_smp_K[j].contiguous(), eng.lhat)[0] for j in range(len(funcs))]).contiguous()
+    F2 = eng.ctx.assemble_source_gram(f_smp_K)
+    d._src = {'functions': funcs, 'coefficients': coeffs, 'K': len(funcs), 'f_smp_K': f_smp_K, 'b_K': b_K, 'F2': F2}
+
+
 def discretize(grid_and_problem_data, T, nt, solver_options=None, mpi_comm=None, device_index=None,
                elliptic_reconstruction=False):
-    """Reference :43-95.  Returns ``(d, d_data)``."""
+    """Reference :43-95.  Returns ``(d, d_data)``.  ``p['f']`` may be ``{'functions': [...], 'coefficients': [...]}`` with any
+    number of components and coefficients of ``mu`` and ``'_t'`` (module docstring)."""
+    src = _source_components(grid_and_problem_data)
+    if src is not None:
+        from pylrbms_amd.functions import SumFunction
+        grid = grid_and_problem_data['grid']
+        if len(grid.subdomains_on_rank) != grid.num_subdomains:
+            raise NotImplementedError('a time-dependent / multi-component source needs all subdomains on one rank')
+        if elliptic_reconstruction:
+            raise NotImplementedError('elliptic_reconstruction with a time-dependent / multi-component source')
+        # the elliptic discretization is built on sum_j f_j (its quadrature orders cover every component); its own b / f2
+        # are not read on this path
+        grid_and_problem_data = dict(grid_and_problem_data, f=SumFunction(src[0], [1.0] * len(src[0]), name='f_sum'))
     d, d_data = discretize_ell(grid_and_problem_data, solver_options, mpi_comm, device_index=device_index)
     assert isinstance(d.parameter_space, CubicParameterSpace)              # :45
     d.__class__ = InstationaryDuneDiscretization
@@ -124,4 +241,6 @@ def discretize(grid_and_problem_data, T, nt, solver_options=None, mpi_comm=None,
     parameter_range = grid_and_problem_data['parameter_range'] if 'parameter_range' in grid_and_problem_data else (0.1, 1.0)
     d.parameter_space = CubicParameterSpace(d.parameter_type, parameter_range[0], parameter_range[1])   # :93
     d.name = 'parabolic_block_swipdg'
+    if src is not None:
+        _setup_sources(d, *src)
     return d, d_data

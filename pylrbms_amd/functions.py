@@ -23,7 +23,18 @@ def _per_element(v, x):
     return np.broadcast_to(v, shape)
 
 
-class ExpressionFunction:
+class _Arithmetic:
+    """``+`` / ``-`` between data functions (dune.xt.functions supports both; the reference's artificial-channels problem
+    builds lambda_bar / lambda_hat with them): the result is a ``SumFunction``."""
+
+    def __add__(self, other):
+        return SumFunction([self, other], [1.0, 1.0], name='({} + {})'.format(self.name, other.name))
+
+    def __sub__(self, other):
+        return SumFunction([self, other], [1.0, -1.0], name='({} - {})'.format(self.name, other.name))
+
+
+class ExpressionFunction(_Arithmetic):
     """``make_expression_function_1x1(grid, 'x', expr, order=, name=)``: numpy-evaluated expression in x[0], x[1]."""
 
     def __init__(self, variable, expression, order=2, name='expression'):
@@ -39,7 +50,7 @@ class ExpressionFunction:
         return np.broadcast_to(np.asarray(out, dtype=np.float64), x.shape[:-1])
 
 
-class ConstantFunction:
+class ConstantFunction(_Arithmetic):
     order = 0
 
     def __init__(self, value, name='constant'):
@@ -49,7 +60,7 @@ class ConstantFunction:
         return np.broadcast_to(self.value, np.asarray(x).shape[:-1])
 
 
-class CheckerboardFunction:
+class CheckerboardFunction(_Arithmetic):
     """``make_checkerboard_function_1x1``: piecewise constant on a Cartesian ``num_elements`` checkerboard,
     ``values[ix + nx * iy]``; the cell is decided by the element centre."""
     order = 0
@@ -71,7 +82,7 @@ class CheckerboardFunction:
         return _per_element(v, x)
 
 
-class ElementwiseFunction:
+class ElementwiseFunction(_Arithmetic):
     """Piecewise constant per fine element: ``table[cy, cx, t]`` indexed by the canonical element key
     (synthetic multiscale coefficient fields)."""
     order = 0
@@ -85,13 +96,33 @@ class ElementwiseFunction:
         return _per_element(v, x)
 
 
-class SumFunction:
+class SumFunction(_Arithmetic):
     def __init__(self, functions, coefficients, name='sum'):
         self.functions, self.coefficients, self.name = list(functions), [float(c) for c in coefficients], name
         self.order = max(getattr(f, 'order', 2) for f in self.functions)
 
     def __call__(self, x, centers, keys):
         return sum(c * f(x, centers, keys) for f, c in zip(self.functions, self.coefficients))
+
+
+class IndicatorFunction(_Arithmetic):
+    """``make_indicator_function_1x1(grid, [[[ll, ur], value], ...], name)``: an element gets the sum of the values of every
+    box that contains its CENTRE, boxes closed on both sides (``ll <= c <= ur``; the dune-xt ``IndicatorFunction``
+    convention).  Piecewise constant per element, declared order 0."""
+    order = 0
+
+    def __init__(self, boxes, name='indicator'):
+        self.boxes = [(np.asarray(ll, dtype=np.float64), np.asarray(ur, dtype=np.float64), float(value))
+                      for (ll, ur), value in boxes]
+        self.name = name
+
+    def __call__(self, x, centers, keys=None):
+        c = np.asarray(centers, dtype=np.float64)
+        v = np.zeros(c.shape[:-1])
+        for ll, ur, value in self.boxes:
+            inside = np.all((c >= ll) & (c <= ur), axis=-1)
+            v = v + np.where(inside, value, 0.0)
+        return _per_element(v, x)
 
 
 def make_expression_function_1x1(grid, variable, expression, order=2, name='expression'):
@@ -104,6 +135,10 @@ def make_constant_function_1x1(grid, value, name='constant'):
 
 def make_constant_function_2x2(grid, value, name='constant'):
     return ConstantFunction(np.asarray(value, dtype=np.float64).reshape(2, 2), name=name)
+
+
+def make_indicator_function_1x1(grid, boxes, name='indicator'):
+    return IndicatorFunction(boxes, name=name)
 
 
 def make_checkerboard_function_1x1(grid_provider, lower_left, upper_right, num_elements, values, name='checkerboard'):

@@ -16,7 +16,9 @@ def parse_parameter(mu, parameter_type):
     if isinstance(mu, Parameter):
         return mu
     if isinstance(mu, dict):
-        return Parameter({k: np.asarray(v, dtype=np.float64).reshape(parameter_type[k]) for k, v in mu.items()})
+        # components outside ``parameter_type`` (e.g. the time '_t' pyMOR's time steppers add) keep their own shape
+        return Parameter({k: np.asarray(v, dtype=np.float64).reshape(parameter_type[k] if k in parameter_type else np.shape(v))
+                          for k, v in mu.items()})
     if not parameter_type:
         return Parameter()
     flat = np.atleast_1d(np.asarray(list(mu) if not np.isscalar(mu) else [mu], dtype=np.float64)).ravel()
@@ -39,15 +41,18 @@ class ParameterFunctional:
 
 
 class ExpressionParameterFunctional(ParameterFunctional):
+    """``parameter_type=None``: a functional of no parameter (the reference passes ``None`` for a constant, e.g. '-1').
+    Comparisons evaluate to 0.0 / 1.0 (pyMOR evaluates the expression with NumPy, ``float`` of a NumPy bool)."""
+
     def __init__(self, expression, parameter_type, name=None):
-        self.expression, self.parameter_type, self.name = expression, dict(parameter_type), name
+        self.expression, self.parameter_type, self.name = expression, dict(parameter_type or {}), name
         self._code = compile(expression, '<functional>', 'eval')
 
     def evaluate(self, mu=None):
-        mu = parse_parameter(mu, self.parameter_type)
+        mu = parse_parameter(mu, self.parameter_type) if mu is not None or self.parameter_type else Parameter()
         env = {k: (v.item() if np.size(v) == 1 else v) for k, v in mu.items()}
         env.update({'sin': np.sin, 'cos': np.cos, 'exp': np.exp, 'sqrt': np.sqrt, 'pi': np.pi})
-        return float(eval(self._code, {'__builtins__': {}}, env))
+        return float(np.asarray(eval(self._code, {'__builtins__': {}}, env), dtype=np.float64))
 
 
 class ProjectionParameterFunctional(ParameterFunctional):

@@ -430,6 +430,8 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
     """The reduced instationary model of the parabolic path: reduced implicit Euler (``lrbms_reduced_implicit_euler``, the
     whole trajectory in one native call) and the same ``ParabolicEstimator`` with the projected operators."""
 
+    rhs_red_K = r_fd_K = None     # the projected source components (time-dependent source: ParabolicLRBMSReductor.reduce)
+
     def __init__(self, reductor, buffers, N):
         super().__init__(reductor, buffers, N)
         self.T, self.time_stepper = self.d.T, self.d.time_stepper
@@ -438,6 +440,11 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
     def solve(self, mu, inverse_options=None):
         eng = self.d.engine
         dt = self.T / self.time_stepper.nt
+        if self.rhs_red_K is not None:                               # time-dependent source: sum_j phi[k+1][j] rhs_red_K[j]
+            U, info = eng.ctx.reduced_implicit_euler_src(self.d.theta(mu), dt, self.time_stepper.nt, self.B_sys, self.M_red,
+                                                         self.rhs_red_K, self.d._phi_device(mu))
+            self.last_solve_info = info
+            return ReducedVectorArray(U.permute(1, 2, 0))
         if eng.S_ext != eng.S:                                       # sharded: on the gathered reduced system, like rd.solve
             from pylrbms_amd.parallel import gather_subdomain_rows
             ctx, B_all, rhs_all = self._global_online()
@@ -448,6 +455,32 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
                                                      self.rhs_red)
         self.last_solve_info = info
         return ReducedVectorArray(U.permute(1, 2, 0))
+
+    def _local_estimates(self, U, mu):
+        """With a time-dependent source: the reduced counterpart of InstationaryDuneDiscretization._local_estimates -- the
+        batched estimate with f2 = 0, r_fd = 0 plus ``lrbms_reduced_source_terms`` on rhs_red_K's companions r_fd_K, F2."""
+        if self.rhs_red_K is None:
+            return ReducedDiscretization._local_estimates(self, U, mu)
+        torch = self._torch
+        eng = self.d.engine
+        theta = self.d.theta(mu)
+        u_all = U.tensor                                                   # [S, N, len(U)]
+        rows = self.d._source_rows(mu, u_all.shape[2])
+        zero_f2 = eng.ctx.zeros(eng.S)
+        grams = list(self.grams)
+        grams[1] = torch.zeros_like(grams[1])
+        grams = tuple(grams)
+        cols = []
+        for c0 in range(0, u_all.shape[2], 16):
+            u = u_all[:, :, c0:c0 + 16].contiguous()
+            L = u.shape[2]
+            eta = eng.ctx.reduced_estimate_batch(np.tile(theta, (L, 1)), u, grams, zero_f2, eng.ceps, eng.hdiam)
+            if rows is not None:
+                eta[1] += eng.ctx.reduced_source_terms(theta, rows[c0:c0 + L].contiguous(), self.d._src['F2'], self.r_fd_K, u,
+                                                       eng.ceps, eng.hdiam)
+            cols.append(eta)
+        eta = torch.cat(cols, dim=2)
+        return eta[0], eta[1], eta[2]
 
     def _gathered_mass(self):
         if getattr(self, '_M_all', None) is None:
@@ -512,5 +545,14 @@ class ParabolicLRBMSReductor(LRBMSReductor):
 
     def _reduce(self, touched=None):
         rd = super()._reduce(touched=touched)
-        return InstationaryReducedDiscretization(self, {'sys': (rd.B_sys, rd.rhs_red, rd.E_red, rd.M_red), 'grams': rd.grams},
-                                                 rd.N)
+        out = InstationaryReducedDiscretization(self, {'sys': (rd.B_sys, rd.rhs_red, rd.E_red, rd.M_red), 'grams': rd.grams},
+                                                rd.N)
+        src = getattr(self.d, '_src', None)
+        if src is not None:
+            # the K source components projected like rhs_red / r_fd: one lrbms_project_sources launch on the basis and the
+            # divergence of its RT0 reconstruction images (lrbms_flux_reconstruct -> lrbms_div_apply mode 0)
+            eng = self.d.engine
+            V = self._V.contiguous()
+            D = eng.ctx.div_apply(eng.ctx.flux_reconstruct(eng.F, V), mode=0)
+            out.rhs_red_K, out.r_fd_K = eng.ctx.project_sources(eng.Q, src['b_K'], V, D)
+        return out

@@ -74,6 +74,9 @@ def load_bases(d, path):
 def save_reduced(rd, path):
     """Write the reduced model ``rd`` (projected system + projected estimator operators) to ``path``."""
     from safetensors.torch import save_file
+    if getattr(rd, 'rhs_red_K', None) is not None:
+        raise NotImplementedError('save_reduced: the model carries a time-dependent source with {} component(s) (rhs_red_K, '
+                                  'r_fd_K), which this format does not store'.format(rd.rhs_red_K.shape[0]))
     meta = _signature(rd.d, rd.N)
     meta['kind'] = 'reduced'
     meta['local_sizes'] = json.dumps(rd.reductor.local_sizes())
