@@ -148,7 +148,10 @@ int lrbms_assemble_rhs(lrbms_ctx* ctx, const double* f_smp, const double* lhat, 
  *   ebar   [S][n_T]                        int_T lambda_bar         (E_ii = ebar * stiffness template)
  *   caa    [Q][Q][S][n_T]                  int_T lambda_q lambda_q' / lambda_hat
  *   Aab    [Q][S][n_T][3][3]               df_ab element blocks [i][f]
- *   Bbb    [S][n_T][3][3]                  df_bb element blocks [f][g] */
+ *   Bbb    [S][n_T][3][3]                  df_bb element blocks [f][g]: symmetric positive definite (the kappa^-1-weighted RT0 mass
+ *                                          of the element).  The fused pass relies on it (LRBMS_OPT_F2_FORM 0 factors each block by
+ *                                          Cholesky from its upper triangle); a subdomain with a block that is not SPD gets a NaN
+ *                                          G_bb[self, self] there, not finite wrong numbers */
 int lrbms_assemble_products(lrbms_ctx* ctx, int32_t Q, const double* theta_bar, const double* lam, const double* lam_df,
                             const double* lbar, const double* lhat, double* P_diag, double* ebar, double* caa, double* Aab,
                             double* Bbb, void* stream);
@@ -267,7 +270,11 @@ void* lrbms_ctx_aux_stream(lrbms_ctx* ctx, int32_t i);
  *                              same kernel; 2: the LDS form without that fold (k_f3 computes G_nc[self, self]); 0: the two streaming
  *                              sweeps.  With more subdomains than CUs k_prep_lds runs one persistent workgroup per CU that takes its
  *                              subdomains one after the other and prefetches the next slab into registers; 3: as 1 with one workgroup
- *                              per subdomain at every count (the same bits; cross-check) */
+ *                              per subdomain at every count (the same bits; cross-check)
+ *   LRBMS_OPT_F2_FORM          0 (default): the flux Grams G_bb, G_rdd [self, self] of the fused pass as symmetric Grams of the
+ *                              Cholesky-scaled flux rows (k_f2g; Bbb must be SPD, see lrbms_assemble_products) wherever its
+ *                              per-element factor table fits in LDS; 1: the R~^T B R~ form k_f2 for every shape (cross-check:
+ *                              G_bb and G_rdd differ at rounding level, every other output is the same bits) */
 #define LRBMS_OPT_STREAMS 3
 #define LRBMS_OPT_F1_KSPLIT 4
 #define LRBMS_OPT_F1_FORM 5
@@ -275,6 +282,7 @@ void* lrbms_ctx_aux_stream(lrbms_ctx* ctx, int32_t i);
 #define LRBMS_OPT_SOLVE_VALU 7
 #define LRBMS_OPT_ESTIMATE_VALU 8
 #define LRBMS_OPT_PREP_LDS 10
+#define LRBMS_OPT_F2_FORM 11
 int lrbms_ctx_set_option(lrbms_ctx* ctx, int32_t option, int32_t value);
 
 /* LRBMS_OPT_OSWALD_VERTEX_PATCH on sharded grids: nbr_diag [S][4] (host) = index into the S_ext slabs of the diagonal neighbour

@@ -1,4 +1,4 @@
-"""Build-time guard for the hand-scheduled prefetch of k_f1 / k_f2 and of the persistent k_prep_lds (csrc/fused.hip).
+"""Build-time guard for the hand-scheduled prefetch of k_f1 / k_f2 / k_f2g and of the persistent k_prep_lds (csrc/fused.hip).
 
 The producer waves of both kernels prefetch with inline-asm ``global_load_dwordx2`` that the compiler does not track
 and complete them with a hand-counted ``s_waitcnt vmcnt(n)``.  That is correct only while (i) the compiler emits no
@@ -210,7 +210,7 @@ def check_fused_isa(asm_path):
     report, problems = [], []
     seen = 0
     for name, lines in fns.items():
-        m = re.search(r'\dk_f(1u|1v|1|2)I((?:Li\d+E)+)E', name) or re.search(r'\dk_f(1w)()E4Tmpl', name)      # (k_f1w is no template)
+        m = re.search(r'\dk_f(1u|1v|1|2g|2)I((?:Li\d+E)+)E', name) or re.search(r'\dk_f(1w)()E4Tmpl', name)      # (k_f1w is no template)
         if not m:
             continue
         kernel = 'k_f{}<{}>'.format(m.group(1), ','.join(re.findall(r'Li(\d+)E', m.group(2))))

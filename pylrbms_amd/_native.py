@@ -532,7 +532,8 @@ class NativeContext:
 
     OPTIONS = {'oswald_zero_on_subdomain_boundary': 1, 'accumulate_coupling_across_q': 2, 'oswald_vertex_patch': 9, 'prep_lds': 10,
                # launch policy (no numerical convention): the library reads no environment variable
-               'streams': 3, 'f1_ksplit': 4, 'f1_form': 5, 'coarse': 6, 'solve_valu': 7, 'estimate_valu': 8}
+               'streams': 3, 'f1_ksplit': 4, 'f1_form': 5, 'coarse': 6, 'solve_valu': 7, 'estimate_valu': 8,
+               'f2_form': 11}
 
     def set_option(self, name, value):
         """Switch one of the conventions the reference tree leaves open, or the launch policy of the library

@@ -193,6 +193,7 @@ int lrbms_ctx_set_option(lrbms_ctx* ctx, int32_t option, int32_t value) {
     case LRBMS_OPT_STREAMS: ctx->opt_streams = value; break;
     case LRBMS_OPT_F1_KSPLIT: ctx->opt_f1_ksplit = value; break;
     case LRBMS_OPT_F1_FORM: ctx->opt_f1_legacy = value; break;
+    case LRBMS_OPT_F2_FORM: ctx->opt_f2_form = value; break;
     case LRBMS_OPT_COARSE: ctx->opt_coarse = value; break;
     case LRBMS_OPT_SOLVE_VALU: ctx->opt_solve_valu = value; break;
     case LRBMS_OPT_ESTIMATE_VALU: ctx->opt_estimate_valu = value; break;

@@ -24,7 +24,8 @@
 //   k_vertex_avg     A(+B)  Oswald vertex averages Avg_self [S][nv][N], Avg_side [S][4][nvs][N]
 //   k_flux_side, k_vertex_side   B   R_side / Avg_side alone (phase 2 of a sharded pass)
 //   k_f1<NTX,7,Q>    A   X = V:  B_sys diag, E_red, M_red, G_aa, G_ab[:, self], rhs_red  (MFMA; grid.z = 2: K-split)
-//   k_f2<NR>         A   X = R~: G_bb[self,self], G_rdd[self,self], r_fd[self]           (MFMA, symmetric tiles)
+//   k_f2g<NR>        A   X = C R~, sqrt|T| d: G_bb[self,self], G_rdd[self,self] as Grams X^T X, r_fd[self]  (MFMA, symmetric tiles;
+//                       k_f2<NR>: the R~^T B R~ form, LRBMS_OPT_F2_FORM 1)
 //   k_f3<NTX>        A   X = W_self: G_nc[self,self]                                     (MFMA, symmetric tiles)
 //   k_thin_nc        B   grid (4 sides, S): block-row `a` and block [self,a] of G_nc     (MFMA + VALU, latency-bound)
 //   k_thin_rt        B   grid (4 sides, S): blocks [a,self], [a,a] of G_bb, G_rdd; G_ab[:, a], r_fd[a]  (write-bound)
@@ -36,6 +37,7 @@
 #include <map>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "lrbms_dev.h"
 
@@ -58,11 +60,15 @@ using W2 = std::integral_constant<int, 2>;
 #if !defined(LRBMS_EXPERIMENT_BUILD) &&                                                                               \
     (defined(F1_NO_STAGE) || defined(F1_NO_APPLY) || defined(F1_NO_VALU_STAGE) || defined(F1_NO_MFMA) ||             \
      defined(F1_LDS_FILL) || defined(F1_PRODUCER_PRIO) || defined(F1_SPLIT_SIMD) || defined(F1_PF) ||                \
-     defined(F2_NO_STAGE) || defined(F2_NO_MFMA) || defined(F1_TRACE) || defined(F1V_NO_STORE) || defined(F1V_NO_MIRROR) || defined(F3_EW_X) || defined(PREP_TRACE) || defined(THIN_TRACE))
+     defined(F2_NO_STAGE) || defined(F2_NO_MFMA) || defined(F2G_WG) || defined(F1_TRACE) || defined(F1V_NO_STORE) || defined(F1V_NO_MIRROR) || defined(F3_EW_X) || defined(PREP_TRACE) || defined(THIN_TRACE))
 #error "experiment switch defined in a product build of fused.hip (use tools/build_variant.sh, which sets LRBMS_EXPERIMENT_BUILD)"
 #endif
 #ifndef F1_SPLIT_SIMD
 #define F1_SPLIT_SIMD 0
+#endif
+#ifndef F2G_WG
+#define F2G_WG 3    // k_f2g<NR <= 5>: workgroups per CU its register budget is cut for (NR = 5 at config 3: 80 VGPRs, 109-110 us;
+                    // 2 workgroups, the compiler's 84 VGPRs: 115-116 us)
 #endif
 #ifndef F1_PF
 #define F1_PF 1     // prefetch distance of the k_f1 producers in chunks (1 or 2; measured at config 3: 550 us vs 566 us)
@@ -3115,6 +3121,248 @@ __global__ __launch_bounds__(64 * (F2_NCW + EC)) void k_f2(Tmpl t, F2Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// F2, Gram form (LRBMS_OPT_F2_FORM 0): the same outputs as k_f2 from half the staging.  B_T is SPD (the kappa^-1-weighted
+// RT0 mass of the element), so with its Cholesky factor B_T = C_T^T C_T (C_T upper triangular)
+//   G_bb[self,self]  = sum_T (C_T R~_T)^T (C_T R~_T),      G_rdd[self,self] = sum_T (sqrt|T| d_T)^T (sqrt|T| d_T):
+// both are Grams X^T X, so a fragment of a k-step is the A operand of its tile row AND the B operand of its tile column
+// (the 16x16x4 f64 A and B layouts coincide).  The producers stage 4 rows per element (X_T = C_T R~_T, x_T = sqrt|T| d_T)
+// into ONE buffer per chunk -- rows 3 e + f (f = 0..2) of the EC elements, then EC rows x_T -- and every consumer wave
+// reads each fragment it needs once per k-step (f2g_plan: the upper-triangular tiles dealt so that a wave's tiles span
+// few fragment rows), then issues its MFMAs: 3 k-steps into G_bb, 1 into G_rdd.
+//
+// C_T and sqrt|T| are computed once per workgroup in the prologue, one thread per element, from Bbb.  A pivot that is not
+// positive (Bbb not SPD, include/lrbms_hip.h) makes that element's factor NaN, so the subdomain's G_bb comes out NaN.
+// r_fd keeps k_f2's expression and summation order exactly (bsum * d, fixed-order sum over the producer waves).
+constexpr int F2G_ROWS = 4 * EC;   // staged rows per chunk: 3 EC of X, EC of x
+constexpr int F2G_EL = 8;          // doubles per element of the factor table: c00 c01 c02 c11 c12 c22 sqrt|T| (pad)
+
+// Deal of the NR (NR + 1) / 2 upper-triangular tiles over the F2_NCW consumer roles: role w takes NTRI / NCW tiles (one
+// more for the first NTRI % NCW roles), greedily the unassigned tile that adds the fewest new fragment rows to the role's
+// set (first in row-major order on a tie).  NR = 5: 4 + 4 + 4 + 3 tiles over 3 + 3 + 3 + 3 fragments (k_f2 reads 2 per tile).
+template <int NR>
+struct F2gPlan {
+  static constexpr int NTRI = NR * (NR + 1) / 2, NCW = F2_NCW, TPW = (NTRI + NCW - 1) / NCW;
+  int nt[NCW] = {}, nf[NCW] = {};
+  int frag[NCW][NR] = {};          // fragment rows (row tile indices) the role reads
+  int ta[NCW][TPW] = {}, tb[NCW][TPW] = {};   // tile k of the role = (frag[ta], frag[tb]), frag[ta] <= frag[tb]
+  constexpr F2gPlan() {
+    bool used[NTRI] = {};
+    for (int w = 0; w < NCW; ++w) {
+      const int want = NTRI / NCW + (w < NTRI % NCW ? 1 : 0);
+      int local[NR] = {};
+      for (int i = 0; i < NR; ++i) local[i] = -1;
+      for (int k = 0; k < want; ++k) {
+        int best = -1, bi = 0, bj = 0, bcost = 3;
+        for (int i = 0, idx = 0; i < NR; ++i)
+          for (int j = i; j < NR; ++j, ++idx) {
+            if (used[idx]) continue;
+            const int cost = (local[i] < 0 ? 1 : 0) + (j != i && local[j] < 0 ? 1 : 0);
+            if (cost < bcost) { bcost = cost; best = idx; bi = i; bj = j; }
+          }
+        used[best] = true;
+        if (local[bi] < 0) { local[bi] = nf[w]; frag[w][nf[w]++] = bi; }
+        if (local[bj] < 0) { local[bj] = nf[w]; frag[w][nf[w]++] = bj; }
+        ta[w][k] = local[bi];
+        tb[w][k] = local[bj];
+        ++nt[w];
+      }
+    }
+  }
+};
+
+template <int... I, class F>
+__device__ inline void static_for(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+
+// Consumer role ROLE of k_f2g: accumulate its tiles over all chunks, then store them (and the mirror images of the
+// off-diagonal ones) into the [self, self] blocks.
+template <int NR, int ROLE>
+__device__ inline void f2g_consume(const double* buf, int nchunks, double* gb, double* gd, int QN, int li, int lk) {
+  constexpr int LD = padded_ld(NR);
+  constexpr F2gPlan<NR> P{};
+  constexpr int NT = P.nt[ROLE], NF = P.nf[ROLE];
+  if constexpr (NT == 0) {
+    for (int c = 0; c <= nchunks; ++c) lds_barrier();   // barriers 0 .. nchunks - 1 and the final one
+  } else {
+    d4 accb[NT], accd[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) accb[k] = accd[k] = (d4){0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < nchunks; ++c) {
+      lds_barrier();                               // barrier c
+      const double* x = buf + (c & 1) * F2G_ROWS * LD + lk * LD + li;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {             // k-steps 0..2: rows of X (G_bb); 3: rows of x (G_rdd)
+        double f[NF];
+        static_for(std::make_integer_sequence<int, NF>{}, [&](auto u) { f[u] = x[4 * ks * LD + P.frag[ROLE][u] * 16]; });
+#ifndef F2_NO_MFMA
+        static_for(std::make_integer_sequence<int, NT>{}, [&](auto k) {
+          constexpr int A = P.ta[ROLE][k], B = P.tb[ROLE][k];
+          if (ks < 3) accb[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[A], f[B], accb[k], 0, 0, 0);
+          else accd[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[A], f[B], accd[k], 0, 0, 0);
+        });
+#else
+        (void)f;
+#endif
+      }
+    }
+    lds_barrier();                                 // final barrier
+    static_for(std::make_integer_sequence<int, NT>{}, [&](auto k) {
+      constexpr int TI = P.frag[ROLE][P.ta[ROLE][k]], TJ = P.frag[ROLE][P.tb[ROLE][k]];
+      const int col = TJ * 16 + li;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = TI * 16 + lk + 4 * r;
+        const double vb = accb[k][r], vd = accd[k][r];
+        if (col < QN && row < QN) {
+          gb[(long)row * QN + col] = vb;
+          gd[(long)row * QN + col] = vd;
+          if (TI != TJ) {                          // mirror of the off-diagonal tiles
+            gb[(long)col * QN + row] = vb;
+            gd[(long)col * QN + row] = vd;
+          }
+        }
+      }
+    });
+  }
+}
+
+// Dynamic LDS of k_f2g: factor table [nT][F2G_EL], coef [nT][3], bsum [nT], rt [nT][3] (int)
+inline size_t f2g_dyn_lds_bytes(const Tmpl& t) { return sizeof(double) * (F2G_EL + 4) * (size_t)t.nT + sizeof(int) * 3 * (size_t)t.nT; }
+template <int NR>
+constexpr size_t f2g_static_lds_bytes() { return sizeof(double) * (2 * F2G_ROWS * padded_ld(NR) + EC * 128); }
+
+template <int NR>
+__global__ __launch_bounds__(64 * (F2_NCW + EC)) __attribute__((amdgpu_waves_per_eu(NR <= 5 ? 2 * F2G_WG : 2))) void k_f2g(Tmpl t, F2Args a) {
+  constexpr int LD = padded_ld(NR);
+  extern __shared__ double dyn[];
+  __shared__ double Xg[2 * F2G_ROWS * LD];
+  __shared__ double red[EC * 128];
+  const int s = subdomain_of(t, blockIdx.x), tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = uniform(tid >> 6);
+  const int nthreads = 64 * (F2_NCW + EC);
+  const int QN = a.Q * a.N, C = 5 * QN;
+  double* fac = dyn;
+  double* coefs = dyn + F2G_EL * t.nT;
+  double* bsums = coefs + 3 * t.nT;
+  int* rts = reinterpret_cast<int*>(bsums + t.nT);
+  const int* nbr_s = a.nbr + s * 5;
+  for (int i = tid; i < 3 * t.nT; i += nthreads) {
+    const int T = i / 3, f = i - 3 * T;
+    coefs[i] = face_sign_at(t, nbr_s, T, f) * t.face_len[i] / t.area[T];
+    rts[i] = t.elem_rt[i];
+  }
+  for (int T = tid; T < t.nT; T += nthreads) {
+    const double* be = a.b + (long)s * t.n + 3 * T;
+    bsums[T] = be[0] + be[1] + be[2];
+    const double* B = a.Bbb + ((long)s * t.nT + T) * 9;    // upper triangle of B_T = C^T C
+    const double p0 = B[0];
+    const double c00 = sqrt(p0), c01 = B[1] / c00, c02 = B[2] / c00;
+    const double p1 = B[4] - c01 * c01;
+    const double c11 = sqrt(p1), c12 = (B[5] - c01 * c02) / c11;
+    const double p2 = B[8] - c02 * c02 - c12 * c12;
+    const double c22 = sqrt(p2);
+    const bool spd = p0 > 0.0 && p1 > 0.0 && p2 > 0.0;     // false also for a NaN pivot
+    const double nan = __builtin_nan("");
+    double* ft = fac + F2G_EL * T;
+    ft[0] = spd ? c00 : nan;
+    ft[1] = spd ? c01 : nan;
+    ft[2] = spd ? c02 : nan;
+    ft[3] = spd ? c11 : nan;
+    ft[4] = spd ? c12 : nan;
+    ft[5] = spd ? c22 : nan;
+    ft[6] = sqrt(t.area[T]);
+    ft[7] = 0.0;
+  }
+  for (int i = tid; i < 2 * F2G_ROWS * LD; i += nthreads) Xg[i] = 0.0;
+  for (int i = tid; i < EC * 128; i += nthreads) red[i] = 0.0;
+  __syncthreads();
+  const int nchunks = t.nT / EC;
+  const double* Rs = a.Rself + (long)s * t.nrt * QN;
+
+  if (wave < EC) {
+    // ================================================= producers
+    // Prefetch set of one element: its 3 face rows of R~ in two column halves (6 asm loads; idle lanes re-read the last
+    // column), completed by an explicit s_waitcnt vmcnt(6) (see gload_f64 and k_f2); the factors come from LDS.
+    double rv[2][3], nrv[2][3];
+    const int cc0 = lane < QN ? lane : QN - 1, cc1 = lane + 64 < QN ? lane + 64 : QN - 1;
+    auto load = [&](int T, double (&r)[2][3]) {
+      const int r0 = rts[3 * T], r1 = rts[3 * T + 1], r2 = rts[3 * T + 2];
+      r[0][0] = gload_f64(Rs + (long)r0 * QN + cc0);
+      r[0][1] = gload_f64(Rs + (long)r1 * QN + cc0);
+      r[0][2] = gload_f64(Rs + (long)r2 * QN + cc0);
+      r[1][0] = gload_f64(Rs + (long)r0 * QN + cc1);
+      r[1][1] = gload_f64(Rs + (long)r1 * QN + cc1);
+      r[1][2] = gload_f64(Rs + (long)r2 * QN + cc1);
+    };
+    auto wait_set = [&](double (&r)[2][3]) {
+      asm volatile("s_waitcnt vmcnt(6)" : "+v"(r[0][0]), "+v"(r[0][1]), "+v"(r[0][2]), "+v"(r[1][0]), "+v"(r[1][1]), "+v"(r[1][2]));
+    };
+    auto wait_set_tie = [&](double (&r)[2][3]) {
+      asm volatile("" : "+v"(r[0][0]), "+v"(r[0][1]), "+v"(r[0][2]), "+v"(r[1][0]), "+v"(r[1][1]), "+v"(r[1][2]));
+    };
+    load(wave, rv);
+    double rfd_part[2] = {0.0, 0.0};   // columns lane and lane + 64 (QN <= 128)
+    auto step = [&](int c, double (&cr)[2][3], double (&nr)[2][3]) {
+      const int T = c * EC + wave, el = wave;
+      load(c + 1 < nchunks ? T + EC : T, nr);      // unconditional: the wait below counts on exactly 6 younger loads
+      wait_set(cr);
+      double* xb = Xg + (c & 1) * F2G_ROWS * LD;
+      const double* ft = fac + F2G_EL * T;
+      const double u00 = ft[0], u01 = ft[1], u02 = ft[2], u11 = ft[3], u12 = ft[4], u22 = ft[5], sqa = ft[6];
+      const double c0f = coefs[3 * T], c1f = coefs[3 * T + 1], c2f = coefs[3 * T + 2];
+      const double bsum = bsums[T];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int cc = lane + 64 * k;
+#ifdef F2_NO_STAGE
+        if (cc < QN && cr[k][0] == 1.2345e300) {
+#else
+        if (cc < QN) {
+#endif
+          const double rv0 = cr[k][0], rv1 = cr[k][1], rv2 = cr[k][2];
+          xb[(3 * el) * LD + cc] = u00 * rv0 + u01 * rv1 + u02 * rv2;
+          xb[(3 * el + 1) * LD + cc] = u11 * rv1 + u12 * rv2;
+          xb[(3 * el + 2) * LD + cc] = u22 * rv2;
+          const double d = c0f * rv0 + c1f * rv1 + c2f * rv2;     // as k_f2: r_fd stays bit-identical
+          xb[(3 * EC + el) * LD + cc] = sqa * d;
+          rfd_part[k] += bsum * d;
+        }
+      }
+      lds_barrier();                               // barrier c: buffer c & 1 complete (loads stay in flight)
+    };
+    for (int c = 0; c < nchunks; c += 2) {         // nT is a multiple of 8, so nchunks is even
+      step(c, rv, nrv);
+      step(c + 1, nrv, rv);
+    }
+    lds_barrier();                                 // final barrier
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last prefetch set is never consumed, but it has to stay
+    wait_set_tie(rv);                                  // live until its loads have landed (see k_f1)
+    wait_set_tie(nrv);
+    red[wave * 128 + lane] = rfd_part[0];
+    red[wave * 128 + 64 + lane] = rfd_part[1];
+  } else {
+    // ================================================= consumers
+    // role of this wave rotated by the subdomain, as in k_f2: the roles with one tile fewer move over the SIMDs
+    double* gb = a.G_bb + (long)s * a.gstride;     // [self, self]: block 0 of the block-compact layout
+    double* gd = a.G_rdd + (long)s * a.gstride;
+    switch ((wave - EC + s) & (F2_NCW - 1)) {
+      case 0: f2g_consume<NR, 0>(Xg, nchunks, gb, gd, QN, li, lk); break;
+      case 1: f2g_consume<NR, 1>(Xg, nchunks, gb, gd, QN, li, lk); break;
+      case 2: f2g_consume<NR, 2>(Xg, nchunks, gb, gd, QN, li, lk); break;
+      default: f2g_consume<NR, 3>(Xg, nchunks, gb, gd, QN, li, lk); break;
+    }
+  }
+  // r_fd self block: fixed-order sum over the EC producer waves
+  __syncthreads();
+  for (int c = tid; c < QN; c += nthreads) {
+    double sum = 0.0;
+    for (int w = 0; w < EC; ++w) sum += red[w * 128 + c];
+    a.r_fd[(long)s * C + 2 * QN + c] = sum;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // F3: X = W_self (Oswald interpolation error of the own basis), Y = E W_self.  4 waves; tiles dealt round-robin.
 struct F3Args {
   const double *V, *ebar, *AvgSelf, *AvgSide;
@@ -4826,9 +5074,38 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
     }
   }
   // ---- F2
-  if (do_a) {
+  // LRBMS_OPT_F2_FORM 0: the Gram form k_f2g (every NR = ceil(QN / 16) the pass accepts); it keeps a factor table of
+  // 64 bytes per element in LDS beside k_f2's tables, so a template whose table does not fit runs k_f2 instead (as does
+  // LRBMS_OPT_F2_FORM 1, the cross-check)
+  const int nr2 = (QN + 15) / 16;
+  static const size_t f2g_static[8] = {f2g_static_lds_bytes<1>(), f2g_static_lds_bytes<2>(), f2g_static_lds_bytes<3>(), f2g_static_lds_bytes<4>(),
+                                       f2g_static_lds_bytes<5>(), f2g_static_lds_bytes<6>(), f2g_static_lds_bytes<7>(), f2g_static_lds_bytes<8>()};
+  const bool f2_gram = ctx->opt_f2_form == 0 && f2g_dyn_lds_bytes(t) + f2g_static[nr2 - 1] <= 160 * 1024;
+  if (do_a && f2_gram) {
     F2Args a{Rself, Bbb, b, ctx->nbr, G_bb, G_rdd, r_fd, Q, N, S, gstride};
-    const int nr = (QN + 15) / 16;
+    const size_t ldsf2 = f2g_dyn_lds_bytes(t);
+#define LRBMS_F2G(NRV)                                                                                                      \
+  do {                                                                                                                       \
+    LRBMS_HIP_CHECK(ctx, raise_max_lds(ctx->device, (const void*)k_f2g<NRV>, (int)ldsf2));                                  \
+    hipLaunchKernelGGL(k_f2g<NRV>, dim3(Sg), dim3(64 * (F2_NCW + EC)), ldsf2, s_f23, t, a);                                   \
+  } while (0)
+    KScope ks(ctx, "k_f2", s_f23);
+    switch (nr2) {
+      case 1: LRBMS_F2G(1); break;
+      case 2: LRBMS_F2G(2); break;
+      case 3: LRBMS_F2G(3); break;
+      case 4: LRBMS_F2G(4); break;
+      case 5: LRBMS_F2G(5); break;
+      case 6: LRBMS_F2G(6); break;
+      case 7: LRBMS_F2G(7); break;
+      default: LRBMS_F2G(8); break;
+    }
+#undef LRBMS_F2G
+    LRBMS_LAUNCH_CHECK(ctx);
+  }
+  if (do_a && !f2_gram) {
+    F2Args a{Rself, Bbb, b, ctx->nbr, G_bb, G_rdd, r_fd, Q, N, S, gstride};
+    const int nr = nr2;
     const size_t ldsf2 = sizeof(double) * 4 * t.nT + sizeof(int) * 3 * t.nT;
 #define LRBMS_F2(NRV)                                                                                                       \
   do {                                                                                                                       \
