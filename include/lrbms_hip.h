@@ -499,6 +499,23 @@ int lrbms_reduced_source_terms(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, 
                                const double* F2, const double* r_fd_K, const double* u, const double* ceps, double hdiam,
                                double* out, void* stream);
 
+/* -- parameter-dependent affine sources of the stationary path: f(mu) = sum_j phi_j(mu) f_j, K components --
+ * The host evaluates phi (the coefficients theta^f_j(mu)); b_K, F2, rhs_red_K and r_fd_K are those of the block above.
+ *
+ *   lrbms_reduced_solve_batch_src   lrbms_reduced_solve_batch where column m of the panel solves against
+ *                                   sum_j phi[m][j] rhs_red_K[j]: theta [nmu][Q] host, phi [nmu][K] host, rhs_red_K [K][S][N],
+ *                                   u [S][N][nmu].  Work size lrbms_reduced_solve_batch_work_size(N, nmu); same limits (N <= 64,
+ *                                   nmu <= 64, groups of 16/32/64), preconditioner handling, info and error codes.  1 <= K <= 64.
+ *                                   K = 1, phi = 1: the bits of lrbms_reduced_solve_batch.  A column whose right-hand side is
+ *                                   exactly zero comes back as zeros.  Single rank.
+ *   lrbms_combine_sources           y [M] = sum_j phi[j] x_K[j] for x_K [K][M] (device), phi [K] host, 1 <= K <= 64; the sum is
+ *                                   spelled out with fma from the first product (the order of lrbms_reduced_solve_batch_src).
+ *                                   Forms b(mu) from b_K (M = S n) and rhs_red(mu) from rhs_red_K (M = S N). */
+int lrbms_reduced_solve_batch_src(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta, const double* phi,
+                                  const double* B_sys, const double* rhs_red_K, double* work, double* u, double rtol, int32_t max_iter,
+                                  double* info, void* stream);
+int lrbms_combine_sources(lrbms_ctx* ctx, int32_t K, int64_t M, const double* phi, const double* x_K, double* y, void* stream);
+
 /* -- online enrichment (SURVEY.md section 8f "next" #1) ---------------------------------------------------- */
 /* Dirichlet correction blocks of the neighbourhood problems: on every coupling face of subdomain s, the boundary-form
  * diagonal block minus the inner-face block already contained in A_diag

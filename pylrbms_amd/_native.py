@@ -92,6 +92,9 @@ SIGNATURES = {
     'lrbms_project_sources': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'lrbms_reduced_source_terms': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
                                                   c_vp, c_vp]),
+    'lrbms_reduced_solve_batch_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_dbl,
+                                                     c_i32, _P_DBL, c_vp]),
+    'lrbms_combine_sources': (ctypes.c_int, [c_vp, c_i32, c_i64, _P_DBL, c_vp, c_vp, c_vp]),
     'lrbms_assemble_dirichlet_correction': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms_local_correction_work_size': (c_i64, [c_vp, c_i32]),
     'lrbms_local_correction_solve': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_i32, _P_I32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
@@ -774,6 +777,57 @@ class NativeContext:
                                                  c_vp(out.data_ptr()), self._stream())
         self._check(rc, 'lrbms_reduced_source_terms')
         return out
+
+    # ------------------------------------------------------------------ parameter-dependent affine sources (stationary path)
+    def combine_sources(self, phi, x_K, out=None):
+        """phi [K] (host), x_K [K, ...] (device) -> y [...] = sum_j phi[j] x_K[j] (``lrbms_combine_sources``)."""
+        ph = np.ascontiguousarray(phi, dtype=np.float64).reshape(-1)
+        K = int(x_K.shape[0])
+        assert ph.shape == (K,), 'phi must have K = {} entries'.format(K)
+        M = int(x_K[0].numel())
+        x = self._ptr(x_K, (K,) + tuple(x_K.shape[1:]), 'x_K')
+        y = out if out is not None else self.empty(*x_K.shape[1:])
+        rc = self.lib.lrbms_combine_sources(self.handle, K, M, _dblp(ph), x, self._ptr(y, tuple(x_K.shape[1:]), 'y'), self._stream())
+        self._check(rc, 'lrbms_combine_sources')
+        return y
+
+    def reduced_solve_batch_src(self, thetas, phis, B_sys, rhs_red_K, rtol=1e-13, max_iter=20000, work=None):
+        """thetas [nmu, Q], phis [nmu, K] (host), rhs_red_K [K, S, N] -> u [S, N, nmu] (mu fastest), info: column m solves
+        against sum_j phis[m, j] rhs_red_K[j]."""
+        Q, S, N, K = B_sys.shape[0], self.S, B_sys.shape[3], rhs_red_K.shape[0]
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        ph = np.ascontiguousarray(phis, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, Q) and ph.shape == (nmu, K)
+        need = int(self.lib.lrbms_reduced_solve_batch_work_size(self.handle, N, nmu))
+        if work is None:
+            work = self.empty(need)
+        if work.numel() < need:
+            raise NativeError('reduced_solve_batch_src: work too small')
+        u = self.empty(S, N, nmu)
+        info = np.zeros(2)
+        rc = self.lib.lrbms_reduced_solve_batch_src(self.handle, Q, N, K, nmu, _dblp(th), _dblp(ph),
+                                                    self._ptr(B_sys, (Q, S, 5, N, N), 'B_sys'),
+                                                    self._ptr(rhs_red_K, (K, S, N), 'rhs_red_K'), c_vp(work.data_ptr()),
+                                                    c_vp(u.data_ptr()), float(rtol), int(max_iter), _dblp(info), self._stream())
+        self._check(rc, 'lrbms_reduced_solve_batch_src')
+        return u, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
+
+    def reduced_solve_batches_src(self, thetas, phis, B_sys, rhs_red_K, per_call=64, rtol=1e-13, max_iter=20000, concat=True):
+        """``reduced_solve_batches`` with a right-hand side of its own per parameter (phis [nmu, K])."""
+        torch = self.torch
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        ph = np.ascontiguousarray(phis, dtype=np.float64)
+        per_call = max(1, min(int(per_call), 64))
+        work = self.empty(int(self.lib.lrbms_reduced_solve_batch_work_size(self.handle, int(B_sys.shape[3]), min(per_call, th.shape[0]))))
+        res = [self.reduced_solve_batch_src(th[b0:b0 + per_call], ph[b0:b0 + per_call], B_sys, rhs_red_K, rtol=rtol,
+                                            max_iter=max_iter, work=work)
+               for b0 in range(0, th.shape[0], per_call)]
+        if concat:
+            u = torch.cat([r[0] for r in res], dim=2) if len(res) > 1 else res[0][0]
+        else:
+            u = [r[0] for r in res]
+        return u, {'iterations': max(r[1]['iterations'] for r in res), 'relative_residual': max(r[1]['relative_residual'] for r in res)}
 
     # ------------------------------------------------------------------ online enrichment
     def assemble_dirichlet_correction(self, lam):

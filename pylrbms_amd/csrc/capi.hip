@@ -48,6 +48,10 @@ int launch_reduced_source_terms(lrbms_ctx* ctx, int Q, int N, int K, int L, cons
 int launch_assemble_source_gram(lrbms_ctx* ctx, int K, const double* f_smp_K, double* F2, hipStream_t st);
 int launch_project_sources(lrbms_ctx* ctx, int N, int C, int K, const double* bK, const double* V, const double* D, double* rhs_K,
                            double* rfd_K, hipStream_t st);
+int launch_reduced_solve_batch_src(lrbms_ctx* ctx, int Q, int N, int K, int nmu, const double* theta, const double* phi,
+                                   const double* B_sys, const double* rhs_red_K, double* work, double* u, double rtol, int max_iter,
+                                   double* info, hipStream_t st);
+int launch_combine_sources(lrbms_ctx* ctx, int K, long M, const double* phi, const double* x_K, double* y, hipStream_t st);
 void coarse_release(lrbms_ctx* ctx);   // online.hip
 int64_t reduced_precond_size(lrbms_ctx* ctx, int N);
 int launch_reduced_precond_build(lrbms_ctx* ctx, int Q, int N, const double* theta, const double* B_sys, double* work, double* pc,
@@ -153,6 +157,7 @@ int lrbms_ctx_destroy(lrbms_ctx* ctx) {
   if (ctx->ksp_ticket) (void)hipFree(ctx->ksp_ticket);
   if (ctx->subset) (void)hipFree(ctx->subset);
   if (ctx->wab) (void)hipFree(ctx->wab);
+  if (ctx->src_phi) (void)hipFree(ctx->src_phi);
   for (int i = 0; i < 3; ++i) {
     if (ctx->aux[i]) lrbms_side_stream_release(ctx->device, i);
     if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]);
@@ -725,6 +730,21 @@ int lrbms_reduced_source_terms(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, 
   LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, F2);
   CHECK_PTR(ctx, r_fd_K); CHECK_PTR(ctx, u); CHECK_PTR(ctx, ceps); CHECK_PTR(ctx, out);
   return launch_reduced_source_terms(ctx, Q, N, K, L, theta, phi, F2, r_fd_K, u, ceps, hdiam, out, (hipStream_t)stream);
+}
+
+int lrbms_reduced_solve_batch_src(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta, const double* phi,
+                                  const double* B_sys, const double* rhs_red_K, double* work, double* u, double rtol, int32_t max_iter,
+                                  double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, B_sys);
+  CHECK_PTR(ctx, rhs_red_K); CHECK_PTR(ctx, work); CHECK_PTR(ctx, u);
+  return launch_reduced_solve_batch_src(ctx, Q, N, K, nmu, theta, phi, B_sys, rhs_red_K, work, u, rtol, max_iter, info,
+                                        (hipStream_t)stream);
+}
+
+int lrbms_combine_sources(lrbms_ctx* ctx, int32_t K, int64_t M, const double* phi, const double* x_K, double* y, void* stream) {
+  if (!ctx) return LRBMS_E_INVALID;
+  CHECK_PTR(ctx, phi); CHECK_PTR(ctx, x_K); CHECK_PTR(ctx, y);
+  return launch_combine_sources(ctx, K, (long)M, phi, x_K, y, (hipStream_t)stream);
 }
 
 int64_t lrbms_reduced_time_residual_work_size(lrbms_ctx* ctx, int32_t N) {

@@ -1997,6 +1997,20 @@ __global__ __launch_bounds__(256) void k_bcg_init(long total, int nmu, const dou
   }
 }
 
+// k_bcg_init with a right-hand side of its own per column (lrbms_reduced_solve_batch_src): r[s][i][m] = sum_j phi[m0 + m][j]
+// rhs_K[j][s][i], the contraction spelled out with __fma_rn from the first product (K = 1, phi = 1: the bits of k_bcg_init)
+__global__ __launch_bounds__(256) void k_bcg_init_src(long total, int nmu, int m0, int K, long SN, const double* __restrict__ phi,
+                                                      const double* __restrict__ rhs_K, double* __restrict__ x, double* __restrict__ r) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / nmu;
+    const double* ph = phi + (long)(m0 + (int)(i - row * nmu)) * K;
+    double acc = ph[0] * rhs_K[row];
+    for (int j = 1; j < K; ++j) acc = __fma_rn(ph[j], rhs_K[j * SN + row], acc);
+    x[i] = 0.0;
+    r[i] = acc;
+  }
+}
+
 }  // namespace
 
 // doubles of work per group of <= 16 parameters of the batched reduced solve: u (groups of a multi-group call solve into their
@@ -2030,12 +2044,14 @@ __global__ __launch_bounds__(256) void k_bcg_scatter(long rows, int nm, int nmu,
 // are S latency-bound workgroups, so the groups share the chip at little cost to each other (config 3: 6 100 mu-solves/s with
 // one group at a time, 8 700 with three in flight).  One preconditioner per call, read-only while the groups run: the prebuilt
 // one (lrbms_reduced_precond_use) or the inverse diagonal blocks + coarse level at the mean theta of the call.
-int launch_reduced_solve_batch(lrbms_ctx* ctx, int Q, int N, int nmu, const double* theta, const double* B_sys,
-                               const double* rhs_red, double* work, double* u, double rtol, int max_iter, double* info,
-                               hipStream_t st) {
-  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch needs all subdomains on one rank");
-  if (N > 64 || nmu < 1 || nmu > 64)
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: need N <= 64, nmu <= 64");
+//
+// The group / iteration driver is shared with lrbms_reduced_solve_batch_src: K == 0 broadcasts rhs [S][N] to every column
+// (k_bcg_init); K >= 1 gives column m the right-hand side sum_j phi_dev[m][j] rhs[j] of rhs [K][S][N] (k_bcg_init_src).  The
+// start kernel is the only difference.  A column whose right-hand side is zero has r = z = p = 0, so rz, pAp and with them
+// alpha and beta stay 0 (k_bcg_reduce) and its relative residual counts as 0: it comes back as zeros beside the others.
+static int reduced_solve_batch_drive(lrbms_ctx* ctx, int Q, int N, int nmu, const double* theta, const double* B_sys,
+                                     const double* rhs_red, int K, const double* phi_dev, double* work, double* u, double rtol,
+                                     int max_iter, double* info, hipStream_t st) {
   const int S = ctx->S;
   const int GW = reduced_batch_group_width(ctx, nmu);
   const int ng = (nmu + GW - 1) / GW;
@@ -2185,8 +2201,12 @@ int launch_reduced_solve_batch(lrbms_ctx* ctx, int Q, int N, int nmu, const doub
     Group& G = g[k];
     const long vec = (long)S * N * G.nm;
     if (GW > 16) LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(G.theta_dev, G.thd, sizeof(double) * 8 * BMAX, hipMemcpyHostToDevice, G.st));
-    hipLaunchKernelGGL(k_bcg_init, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, G.st, vec, G.nm,
-                       rhs_red, G.ug, G.r);
+    if (K == 0)
+      hipLaunchKernelGGL(k_bcg_init, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, G.st, vec, G.nm,
+                         rhs_red, G.ug, G.r);
+    else
+      hipLaunchKernelGGL(k_bcg_init_src, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, G.st, vec,
+                         G.nm, G.m0, K, (long)S * N, phi_dev, rhs_red, G.ug, G.r);
     update(G, 1);
     LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host[k], G.scal, sizeof(double) * 4 * BMAX, hipMemcpyDeviceToHost, G.st));
   }
@@ -2281,6 +2301,88 @@ int launch_reduced_solve_batch(lrbms_ctx* ctx, int Q, int N, int nmu, const doub
   if (info) { info[0] = it; info[1] = rel; }
   if (rc != LRBMS_OK) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: NaN residual (system not SPD?)");
   if (rel > rtol) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: CG did not reach rtol");
+  return LRBMS_OK;
+}
+
+int launch_reduced_solve_batch(lrbms_ctx* ctx, int Q, int N, int nmu, const double* theta, const double* B_sys,
+                               const double* rhs_red, double* work, double* u, double rtol, int max_iter, double* info,
+                               hipStream_t st) {
+  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch needs all subdomains on one rank");
+  if (N > 64 || nmu < 1 || nmu > 64)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: need N <= 64, nmu <= 64");
+  return reduced_solve_batch_drive(ctx, Q, N, nmu, theta, B_sys, rhs_red, 0, nullptr, work, u, rtol, max_iter, info, st);
+}
+
+// lrbms_reduced_solve_batch with column m solving against sum_j phi[m][j] rhs_red_K[j].  phi [nmu][K] arrives on the host and
+// goes to a ctx-owned device table (64 x 64 doubles, allocated on first use) on the caller's stream ahead of the fork, so the
+// work size is that of lrbms_reduced_solve_batch.  Only k_bcg_init_src reads the table, and every group has synchronised behind
+// it before the call returns: the next call may overwrite it.
+int launch_reduced_solve_batch_src(lrbms_ctx* ctx, int Q, int N, int K, int nmu, const double* theta, const double* phi,
+                                   const double* B_sys, const double* rhs_red_K, double* work, double* u, double rtol, int max_iter,
+                                   double* info, hipStream_t st) {
+  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch_src needs all subdomains on one rank");
+  if (N > 64 || nmu < 1 || nmu > 64)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch_src: need N <= 64, nmu <= 64");
+  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch_src: need 1 <= K <= 64");
+  if (!ctx->src_phi) LRBMS_HIP_CHECK(ctx, hipMalloc((void**)&ctx->src_phi, sizeof(double) * 64 * 64));
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->src_phi, phi, sizeof(double) * nmu * K, hipMemcpyHostToDevice, st));
+  return reduced_solve_batch_drive(ctx, Q, N, nmu, theta, B_sys, rhs_red_K, K, ctx->src_phi, work, u, rtol, max_iter, info, st);
+}
+
+// y [M] = sum_j phi[j] x_K[j] [M] in the fma order of k_bcg_init_src: a streaming grid-stride loop, two doubles (one 16-byte load
+// per operand) per thread and step where every row is 16-byte aligned, a scalar loop otherwise
+namespace {
+struct SrcPhi { double v[64]; };
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_combine_sources(int K, long M, SrcPhi phi, const double* __restrict__ x, double* __restrict__ y) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  if (WIDE) {
+    const long M2 = M >> 1;
+    const double2* x2 = reinterpret_cast<const double2*>(x);
+    double2* y2 = reinterpret_cast<double2*>(y);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < M2; i += stride) {
+      double2 v = x2[i];
+      double2 acc = make_double2(phi.v[0] * v.x, phi.v[0] * v.y);
+#pragma unroll 4
+      for (int j = 1; j < K; ++j) {
+        v = x2[j * M2 + i];
+        acc.x = __fma_rn(phi.v[j], v.x, acc.x);
+        acc.y = __fma_rn(phi.v[j], v.y, acc.y);
+      }
+      y2[i] = acc;
+    }
+  } else {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
+      double acc = phi.v[0] * x[i];
+#pragma unroll 4
+      for (int j = 1; j < K; ++j) acc = __fma_rn(phi.v[j], x[j * M + i], acc);
+      y[i] = acc;
+    }
+  }
+}
+}  // namespace
+
+int launch_combine_sources(lrbms_ctx* ctx, int K, long M, const double* phi, const double* x_K, double* y, hipStream_t st) {
+  if (K < 1 || K > 64 || M < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "combine_sources: need 1 <= K <= 64, M >= 1");
+  if (ctx->num_cus == 0) {
+    int ncu = 0;
+    LRBMS_HIP_CHECK(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    ctx->num_cus = ncu > 0 ? ncu : 256;
+  }
+  SrcPhi ph;
+  for (int j = 0; j < 64; ++j) ph.v[j] = j < K ? phi[j] : 0.0;
+  const bool wide = (M & 1) == 0 && ((uintptr_t)x_K & 15) == 0 && ((uintptr_t)y & 15) == 0;
+  const long items = wide ? M / 2 : M;
+  // four workgroups of 256 per CU cover the chip; fewer when the vector is short
+  long blocks = (items + 255) / 256;
+  const long cap = 4L * ctx->num_cus;
+  blocks = blocks < cap ? blocks : cap;
+  if (wide)
+    hipLaunchKernelGGL(k_combine_sources<true>, dim3((unsigned)blocks), dim3(256), 0, st, K, M, ph, x_K, y);
+  else
+    hipLaunchKernelGGL(k_combine_sources<false>, dim3((unsigned)blocks), dim3(256), 0, st, K, M, ph, x_K, y);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 

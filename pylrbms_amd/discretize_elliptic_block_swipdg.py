@@ -7,6 +7,13 @@ the hot path: ``solve``, ``estimate``, ``operators[...]``, ``products['l2']``, `
 ``flux_reconstruction`` / ``oswald_interpolation_error``.  All arithmetic is done by the HIP kernels through
 ``pylrbms_amd.engine.Engine``; nothing here computes on the CPU besides coefficient sampling and index bookkeeping.
 
+Parameter-dependent affine sources (reference :589-598): ``p['f'] = {'functions': [f_j], 'coefficients': [theta^f_j]}`` with any
+number of components and coefficients that are parameter functionals of ``mu``.  The engine is built on ``sum_j f_j``; the load
+vectors ``b_K``, samples and Grams ``F2`` of the components are set up once (``pylrbms_amd.sources``, kept as ``d._affine_f``).
+``solve`` and the correctors combine ``b(mu) = sum_j theta^f_j(mu) b_j`` on the device (``lrbms_combine_sources``); the estimate is
+the batched estimate with f2 = 0, r_fd = 0 plus ``lrbms_reduced_source_terms``.  Single rank only.  One
+component with the literal coefficient 1 takes the plain path.
+
 """
 import numpy as np
 
@@ -14,6 +21,7 @@ from pylrbms_amd.engine import Engine, blockell_to_dense
 from pylrbms_amd.estimators import EllipticEstimator
 from pylrbms_amd.parallel import Communicator, HaloExchange, HaloPlan
 from pylrbms_amd.parameters import CubicParameterSpace, parse_parameter
+from pylrbms_amd.sources import check_coefficients, evaluate_coefficients, local_estimates, setup_sources, source_components
 from pylrbms_amd.vectorarrays import BlockVectorArray, BlockVectorSpace, SubSpace
 
 
@@ -120,6 +128,8 @@ class LocalDivergenceOperator:
 class DuneDiscretization:
     """Block-SWIPDG discretization living on one GPU (one rank's tile of subdomains)."""
 
+    _affine_f = None   # the parameter-dependent affine source (pylrbms_amd.sources.setup_sources); None: the plain source
+
     def __init__(self, engine, grid_and_problem_data, solver_options, mpi_comm):
         self.engine = engine
         self.grid = grid_and_problem_data['grid']
@@ -164,6 +174,16 @@ class DuneDiscretization:
         mu = self.parse_parameter(mu)
         return np.array([c.evaluate(mu) for c in self.lambda_coeffs])
 
+    def f_coefficients(self, mu):
+        """theta^f(mu) [K] (fp64, host): the coefficients of the affine source at ``mu`` (``[1.]`` for the plain source)."""
+        if self._affine_f is None:
+            return np.ones(1)
+        return evaluate_coefficients(self._affine_f['coefficients'], self.parse_parameter(mu))
+
+    def _load_vector(self, mu):
+        """b(mu) = sum_j theta^f_j(mu) b_j [S, n] on the device (``lrbms_combine_sources``)."""
+        return self.engine.ctx.combine_sources(self.f_coefficients(mu), self._affine_f['b_K'])
+
     def with_(self, **kwargs):
         for k, v in kwargs.items():
             setattr(self, k, v)
@@ -201,6 +221,10 @@ class DuneDiscretization:
         max_iter = int(opts.get('max_iter', 20000)) if isinstance(opts, dict) else 20000
         max_iter = max(max_iter, 20000)
         sharded = eng.S_ext != eng.S
+        if self._affine_f is not None:                                    # single rank (discretize refuses a sharded grid)
+            x, info = eng.ctx.fom_solve(theta, eng.A_diag, eng.A_cpl, self._load_vector(mu), rtol=rtol, max_iter=max_iter)
+            self.last_solve_info = info
+            return BlockVectorArray(x.reshape(eng.S, eng.t.n, 1), self.solution_space)
         if not sharded:
             x, info = eng.ctx.fom_solve(theta, eng.A_diag, eng.A_cpl, eng.b, rtol=rtol, max_iter=max_iter)
             self.last_solve_info = info
@@ -249,6 +273,8 @@ class DuneDiscretization:
         """Per-subdomain nc / r / df for every vector of a full-order array: the vectors become a basis of ``len(U)``
         columns (in chunks of 16) pushed through K7 / K8 / P2, and the k-th unit coefficient vector selects the k-th
         pairwise form -- one batched estimate launch per chunk."""
+        if self._affine_f is not None:
+            return self._local_estimates_affine(U, mu)
         import torch
         eng = self.engine
         theta = self.theta(mu)
@@ -267,13 +293,19 @@ class DuneDiscretization:
         eta = torch.cat(out, dim=2)                                        # [3, S, len(U)]
         return eta[0], eta[1], eta[2]
 
+    def _local_estimates_affine(self, U, mu):
+        """With the affine source: the parabolic full-order route (``pylrbms_amd.sources.local_estimates``) with the row
+        theta^f(mu) for every column."""
+        return local_estimates(self.engine, U.tensor, self.theta(mu), self._affine_f, np.tile(self.f_coefficients(mu), (len(U), 1)))
+
     def estimate(self, U, mu=None, decompose=False):
         return self.estimator.estimate(U, self.parse_parameter(mu), self, decompose=decompose)
 
     def solve_for_local_correction(self, subdomain, Us, mu=None, inverse_options=None):
         """block_swipdg.py:227-316.  ``Us`` (the current solution on the neighbourhood) is accepted and unused, as in
         the reference, whose Dirichlet-lift functional is commented out (:250-261): the corrector is the solution of the
-        neighbourhood problem with homogeneous Dirichlet values on the outer boundary and right-hand side f."""
+        neighbourhood problem with homogeneous Dirichlet values on the outer boundary and right-hand side f (with an affine
+        source: f frozen at ``mu``)."""
         return self.solve_for_local_corrections([subdomain], mu, inverse_options=inverse_options)[0]
 
     def solve_for_local_corrections(self, subdomains, mu=None, inverse_options=None):
@@ -283,7 +315,9 @@ class DuneDiscretization:
         opts = inverse_options if isinstance(inverse_options, dict) else {}
         rtol = min(float(opts.get('precision', 1e-12)), 1e-10)
         marked = [eng.local.index(int(ii)) for ii in subdomains]
-        corr, info = eng.local_corrections(self.theta(self.parse_parameter(mu)), marked, rtol=rtol)
+        # affine source: the load of the corrector problems is the L2 functional of f(mu), b(mu) = sum_j theta^f_j(mu) b_j
+        b = self._load_vector(mu) if self._affine_f is not None else None
+        corr, info = eng.local_corrections(self.theta(self.parse_parameter(mu)), marked, rtol=rtol, b=b)
         self.last_local_correction_info = info
         out = []
         for k, i in enumerate(marked):
@@ -304,9 +338,16 @@ def discretize(grid_and_problem_data, solver_options=None, mpi_comm=None, device
         lambda_funcs, lambda_coeffs = [lambda_], [ConstantParameterFunctional(1.)]
         p = dict(p, **{'lambda': {'functions': lambda_funcs, 'coefficients': lambda_coeffs}})
     f = p['f']
-    if isinstance(f, dict):                                               # block_swipdg.py:589-595,:739-748,:780-785
-        if len(f['functions']) != 1 or f['coefficients'][0] != 1:
-            raise NotImplementedError('the residual operators exist only for one f component with coefficient 1')
+    src = source_components(p)                                            # block_swipdg.py:589-595,:739-748,:780-785
+    if src is not None:
+        # f(mu) = sum_j theta^f_j(mu) f_j: the engine is built on sum_j f_j (its quadrature orders cover every component); its own
+        # b / f2 are not read on this path
+        from pylrbms_amd.functions import SumFunction
+        check_coefficients(src[1], p.get('parameter_type', {}))
+        if len(grid.subdomains_on_rank) != grid.num_subdomains:
+            raise NotImplementedError('a parameter-dependent / multi-component source needs all subdomains on one rank')
+        f = SumFunction(src[0], [1.0] * len(src[0]), name='f_sum')
+    elif isinstance(f, dict):
         f = f['functions'][0]
     mu_bar, mu_hat = p['mu_bar'], p['mu_hat']
     theta_bar = np.array([c.evaluate(mu_bar) for c in lambda_coeffs])
@@ -320,6 +361,8 @@ def discretize(grid_and_problem_data, solver_options=None, mpi_comm=None, device
     engine.assemble()
 
     d = DuneDiscretization(engine, p, solver_options, mpi_comm)
+    if src is not None:
+        d._affine_f = setup_sources(engine, *src)
     operators = {}
     for ii in engine.local:
         for kind in ('nc', 'r_fd', 'r_dd', 'df_aa', 'df_bb', 'df_ab', 'local_energy_dg_product'):
@@ -329,8 +372,8 @@ def discretize(grid_and_problem_data, solver_options=None, mpi_comm=None, device
     d.products = {'l2': [OperatorHandle('l2_{}'.format(ii), 'l2', ii, d) for ii in engine.local]}
     oi_op, fr_op = LinearImageOperator(d, 'oswald'), LinearImageOperator(d, 'flux')
     ones = np.ones(engine.S)
-    d.estimator = EllipticEstimator(grid, engine.ceps, engine.hdiam * ones, engine.f2, lambda_coeffs, mu_bar, mu_hat,
-                                    fr_op, oswald_interpolation_error=oi_op, mpi_comm=d.mpi_comm)
+    d.estimator = EllipticEstimator(grid, engine.ceps, engine.hdiam * ones, engine.f2 if src is None else None, lambda_coeffs,
+                                    mu_bar, mu_hat, fr_op, oswald_interpolation_error=oi_op, mpi_comm=d.mpi_comm)
     parameter_range = p['parameter_range'] if 'parameter_range' in p else (0.1, 1.0)
     d.parameter_space = CubicParameterSpace(d.parameter_type, parameter_range[0], parameter_range[1])
 

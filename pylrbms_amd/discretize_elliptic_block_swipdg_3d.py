@@ -21,9 +21,16 @@ class BlockDiscretization3D:
     def __init__(self, p, device_index=0):
         self.grid = p['grid']
         lam = p['lambda']
+        f = p['f']
+        if isinstance(f, dict):
+            from pylrbms_amd.sources import source_components
+            if source_components(p) is not None:          # refused before any device work (the 2D path takes them)
+                raise NotImplementedError('the 3D path takes one source function; a multi-component / parameter-dependent source '
+                                          'exists on the 2D path only')
+            f = f['functions'][0]
         self.coefficients = list(lam['coefficients'])
         self.mu_bar, self.mu_hat = p['mu_bar'], p['mu_hat']
-        self.engine = Engine3D(self.grid, lam['functions'], p['f'], p['lambda_bar'], p['lambda_hat'],
+        self.engine = Engine3D(self.grid, lam['functions'], f, p['lambda_bar'], p['lambda_hat'],
                                data_degree=p.get('data_degree', 2), device_index=device_index,
                                theta_bar=[float(c(self.mu_bar)) for c in self.coefficients]).assemble()
         self.Q = self.engine.Q

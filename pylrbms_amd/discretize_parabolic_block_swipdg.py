@@ -29,6 +29,7 @@ from pylrbms_amd.discretize_elliptic_block_swipdg import DuneDiscretization, Ope
 from pylrbms_amd.discretize_elliptic_block_swipdg import discretize as discretize_ell
 from pylrbms_amd.estimators import ParabolicEstimator
 from pylrbms_amd.parameters import CubicParameterSpace
+from pylrbms_amd.sources import local_estimates, setup_sources, source_components
 from pylrbms_amd.vectorarrays import BlockVectorArray
 
 
@@ -118,28 +119,7 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         ``lrbms_project_sources`` on the same chunk (identity coefficients) and ``lrbms_reduced_source_terms``."""
         if self._src is None:
             return DuneDiscretization._local_estimates(self, U, mu)
-        import torch
-        eng, c = self.engine, self.engine.ctx
-        theta = self.theta(mu)
-        rows = self._source_rows(mu, len(U))
-        zero_f2 = c.zeros(eng.S)
-        out = []
-        for c0 in range(0, len(U), 16):
-            V = U.tensor[:, :, c0:c0 + 16].contiguous()
-            L = V.shape[2]
-            buf = eng.project_and_estimate(V, project_system=False)
-            grams = list(buf['grams'])
-            grams[1] = torch.zeros_like(grams[1])                             # r_fd of the engine's own b: not used
-            u = torch.eye(L, dtype=V.dtype, device=V.device).expand(eng.S, L, L).contiguous()
-            eta = c.reduced_estimate_batch(np.tile(theta, (L, 1)), u, tuple(grams), zero_f2, eng.ceps, eng.hdiam)
-            if rows is not None:
-                D = c.div_apply(c.flux_reconstruct(eng.F, V), mode=0)
-                _, r_fd_K = c.project_sources(eng.Q, self._src['b_K'], V, D)
-                eta[1] += c.reduced_source_terms(theta, rows[c0:c0 + L].contiguous(), self._src['F2'], r_fd_K, u, eng.ceps,
-                                                 eng.hdiam)
-            out.append(eta)
-        eta = torch.cat(out, dim=2)
-        return eta[0], eta[1], eta[2]
+        return local_estimates(self.engine, U.tensor, self.theta(mu), self._src, self._source_rows(mu, len(U)))
 
     def _time_residual_norm2(self, dU, mu):
         """``R = operator.apply(dU, mu); l2_product.apply_inverse(R).pairwise_dot(R)`` (estimators.py:146-148): [len(dU)]."""
@@ -180,31 +160,14 @@ class InstationaryDuneDiscretization(DuneDiscretization):
 
 
 def _source_components(p):
-    """(functions, coefficients) of a source that is not one component with coefficient 1 (the elliptic path's only form,
-    discretize_elliptic_block_swipdg.discretize), else None."""
-    f = p['f']
-    if not isinstance(f, dict):
-        return None
-    funcs, coeffs = list(f['functions']), list(f['coefficients'])
-    if len(funcs) != len(coeffs) or not funcs:
-        raise ValueError("p['f'] needs as many coefficients as functions (and at least one)")
-    if len(funcs) == 1 and not hasattr(coeffs[0], 'evaluate') and coeffs[0] == 1:
-        return None
-    return funcs, coeffs
+    """(functions, coefficients) of a source that is not one component with coefficient 1, else None
+    (``pylrbms_amd.sources.source_components``)."""
+    return source_components(p)
 
 
 def _setup_sources(d, funcs, coeffs):
-    """Load vectors b_K [K][S][n] (``lrbms_assemble_rhs`` per component) and Grams F2 [S][K][K] (``lrbms_assemble_source_gram``)
-    of the K source components, sampled at the points of the engine's rules ``rhs`` / ``f2``."""
-    import torch
-    from pylrbms_amd.engine import sample_function, volume_record_points
-    eng = d.engine
-    sp = eng.quadrature
-    xf, cl, kl = volume_record_points(eng.grid, eng.local, (sp.rhs, sp.f2))
-    f_smp_K = eng.ctx.from_numpy(np.ascontiguousarray(np.stack([sample_function(fn, xf, cl, kl) for fn in funcs])))
-    b_K = torch.stack([eng.ctx.assemble_rhs(f_smp_K[j].contiguous(), eng.lhat)[0] for j in range(len(funcs))]).contiguous()
-    F2 = eng.ctx.assemble_source_gram(f_smp_K)
-    d._src = {'functions': funcs, 'coefficients': coeffs, 'K': len(funcs), 'f_smp_K': f_smp_K, 'b_K': b_K, 'F2': F2}
+    """b_K, f_smp_K and F2 of the K source components (``pylrbms_amd.sources.setup_sources``), kept as ``d._src``."""
+    d._src = setup_sources(d.engine, funcs, coeffs)
 
 
 def discretize(grid_and_problem_data, T, nt, solver_options=None, mpi_comm=None, device_index=None,

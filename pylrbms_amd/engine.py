@@ -312,8 +312,9 @@ class Engine:
         return self.ctx.reduced_solve(theta, B_sys, rhs_red, rtol=rtol, max_iter=max_iter)
 
     # ------------------------------------------------------------------ online enrichment (section 8f "next" #1)
-    def local_corrections(self, theta, marked, rtol=1e-12, max_iter=20000):
-        """Neighbourhood corrector solves for the subdomains ``marked`` (local indices): [len(marked), n] + info."""
+    def local_corrections(self, theta, marked, rtol=1e-12, max_iter=20000, b=None):
+        """Neighbourhood corrector solves for the subdomains ``marked`` (local indices): [len(marked), n] + info.  ``b``: the
+        load vector [S, n] (default: the engine's own; an affine source hands in b(mu), single rank)."""
         if not self.assembled:
             raise NativeError('assemble() must run before local_corrections()')
         if self.S_ext != self.S and not getattr(self, '_is_hood', False):
@@ -321,6 +322,8 @@ class Engine:
             # not hold.  The corrector problems run on a second engine whose LOCAL set is this rank's local + halo
             # subdomains (same leading order, so local indices agree); its coefficients are sampled and its blocks assembled
             # here, without communication (assembly needs coefficient samples only).
+            if b is not None:
+                raise NotImplementedError('a load vector of its own on a sharded discretization')
             if getattr(self, '_hood_engine', None) is None:
                 import copy
                 g2 = copy.copy(self.grid)
@@ -331,8 +334,8 @@ class Engine:
             return corr, info
         if getattr(self, 'D_corr', None) is None:
             self.D_corr = self.ctx.assemble_dirichlet_correction(self.lam)
-        return self.ctx.local_correction_solve(theta, marked, self.A_diag, self.A_cpl, self.D_corr, self.b, rtol=rtol,
-                                               max_iter=max_iter)
+        return self.ctx.local_correction_solve(theta, marked, self.A_diag, self.A_cpl, self.D_corr, self.b if b is None else b,
+                                               rtol=rtol, max_iter=max_iter)
 
 
 # ---------------------------------------------------------------------- layout converters (host, for API / tests)

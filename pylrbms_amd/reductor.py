@@ -32,7 +32,13 @@ class ExtensionError(Exception):
 
 
 class ReducedDiscretization:
-    """``rd``: block-sparse reduced system + projected estimator operators, resident in HBM."""
+    """``rd``: block-sparse reduced system + projected estimator operators, resident in HBM.
+
+    With a parameter-dependent affine source (``d._affine_f``) ``rhs_red_K [K, S, N]`` and ``r_fd_K [K, S, 5 Q N]`` hold the
+    projected components (``LRBMSReductor.reduce``); what the pass projected from ``sum_j f_j`` belongs to no parameter, so such a
+    model exposes ``rhs_red = None`` and ``operators['r_fd'] = None``."""
+
+    rhs_red_K = r_fd_K = None
 
     def __init__(self, reductor, buffers, N):
         import torch
@@ -59,8 +65,8 @@ class ReducedDiscretization:
         if self._operators is None:
             from pylrbms_amd.engine import expand_factored_grams
             g = expand_factored_grams(self.grams)
-            self._operators = {'nc': g[0], 'r_fd': g[1], 'r_dd': g[2], 'df_bb': g[3], 'df_ab': g[4], 'df_aa': g[5],
-                               'local_energy_dg_product': self.E_red}
+            self._operators = {'nc': g[0], 'r_fd': None if self._affine() else g[1], 'r_dd': g[2], 'df_bb': g[3], 'df_ab': g[4],
+                               'df_aa': g[5], 'local_energy_dg_product': self.E_red}
         return self._operators
 
     def parse_parameter(self, mu):
@@ -85,12 +91,22 @@ class ReducedDiscretization:
         finally:
             ctx.reduced_precond_use(None)
 
+    def _affine(self):
+        """The stationary path's affine source is projected into this model (parabolic models keep their own reading)."""
+        return self.rhs_red_K is not None and getattr(self.d, '_affine_f', None) is not None
+
     def solve(self, mu, inverse_options=None):
         """``rd.solve(mu)`` (online_adaptive_lrbms.py:141): (sum_q theta_q A_q^red) u = b^red.  The reference does a
         dense LU of the unblocked matrix; here PCG on the block-sparse system (``lrbms_reduced_solve``) with the inverse
-        diagonal blocks plus a coarse level on the first local basis vectors as preconditioner."""
+        diagonal blocks plus a coarse level on the first local basis vectors as preconditioner.  With an affine source
+        b^red(mu) = sum_j theta^f_j(mu) rhs_red_K[j] (``lrbms_combine_sources``)."""
         eng = self.d.engine
         theta = self.d.theta(mu)
+        if self._affine():
+            rhs = eng.ctx.combine_sources(self.d.f_coefficients(mu), self.rhs_red_K)
+            u, info = self._solve_with_preconditioner(eng.ctx, self.B_sys, lambda: eng.reduced_solve(theta, self.B_sys, rhs))
+            self.last_solve_info = info
+            return ReducedVectorArray(u.reshape(eng.S, self.N, 1))
         if eng.S_ext != eng.S:
             ctx, B_all, rhs_all = self._global_online()
             u, info = self._solve_with_preconditioner(ctx, B_all, lambda: ctx.reduced_solve(theta, B_all, rhs_all))
@@ -106,6 +122,11 @@ class ReducedDiscretization:
         groups of 16 on its own streams); returns one ``ReducedVectorArray`` with ``len(mus)`` vectors."""
         eng = self.d.engine
         thetas = np.array([self.d.theta(mu) for mu in mus])
+        if self._affine():                                   # a right-hand side of its own per parameter (single rank)
+            phis = np.array([self.d.f_coefficients(mu) for mu in mus])
+            u = self._solve_with_preconditioner(
+                eng.ctx, self.B_sys, lambda: eng.ctx.reduced_solve_batches_src(thetas, phis, self.B_sys, self.rhs_red_K)[0])
+            return ReducedVectorArray(u)
         # sharded: on the gathered reduced system, like solve(); every rank keeps the rows of its own subdomains
         ctx, B_sys, rhs = self._global_online() if eng.S_ext != eng.S else (eng.ctx, self.B_sys, self.rhs_red)
 
@@ -139,6 +160,8 @@ class ReducedDiscretization:
         return self._online
 
     def _local_estimates(self, U, mu):
+        if self._affine():
+            return self._local_estimates_affine(U, mu)
         torch = self._torch
         eng = self.d.engine
         theta = self.d.theta(mu)
@@ -159,6 +182,29 @@ class ReducedDiscretization:
                 cols.append(eng.reduced_estimate(theta, u[:, :, 0].contiguous(), self.grams)[:, :, None])
             else:
                 cols.append(eng.ctx.reduced_estimate_batch(np.tile(theta, (L, 1)), u, self.grams, eng.f2, eng.ceps, eng.hdiam))
+        eta = torch.cat(cols, dim=2)
+        return eta[0], eta[1], eta[2]
+
+    def _local_estimates_affine(self, U, mu):
+        """With an affine source: the batched estimate with f2 = 0 and r_fd = 0 plus ``lrbms_reduced_source_terms`` on r_fd_K and
+        F2 with the row theta^f(mu) for every column (the reduced counterpart of DuneDiscretization._local_estimates_affine)."""
+        torch = self._torch
+        eng = self.d.engine
+        theta = self.d.theta(mu)
+        phi = self.d.f_coefficients(mu)
+        u_all = U.tensor                                                   # [S, N, len(U)]
+        zero_f2 = eng.ctx.zeros(eng.S)
+        grams = list(self.grams)
+        grams[1] = torch.zeros_like(grams[1])
+        grams = tuple(grams)
+        cols = []
+        for c0 in range(0, u_all.shape[2], 16):
+            u = u_all[:, :, c0:c0 + 16].contiguous()
+            L = u.shape[2]
+            eta = eng.ctx.reduced_estimate_batch(np.tile(theta, (L, 1)), u, grams, zero_f2, eng.ceps, eng.hdiam)
+            eta[1] += eng.ctx.reduced_source_terms(theta, np.tile(phi, (L, 1)), self.d._affine_f['F2'], self.r_fd_K, u, eng.ceps,
+                                                   eng.hdiam)
+            cols.append(eta)
         eta = torch.cat(cols, dim=2)
         return eta[0], eta[1], eta[2]
 
@@ -364,7 +410,7 @@ class LRBMSReductor:
             subset = eng.touched_targets(set(int(g) for g in touched) | dirty)
             eng.project_and_estimate(V, last, subset=subset)
             self.last_reduce_info = {'incremental': True, 'subdomains': len(subset)}
-            return ReducedDiscretization(self, last, N)
+            return self._with_affine_source(ReducedDiscretization(self, last, N), V, last)
         if getattr(self, '_buffers', None) is None or self._buffers['N'] != N:
             self._buffers = eng.alloc_reduce_buffers(N)                   # scratch (and image bases if unfused): reused
         buf = dict(self._buffers)
@@ -375,7 +421,26 @@ class LRBMSReductor:
             self._image_bases = {'OI': buf['Wt'], 'RT': buf['Rt']}      # target-major image bases (device tensors)
         self._last_reduce = buf
         self.last_reduce_info = {'incremental': False, 'subdomains': eng.S}
-        return ReducedDiscretization(self, buf, N)
+        return self._with_affine_source(ReducedDiscretization(self, buf, N), V, buf)
+
+    def _with_affine_source(self, rd, V, buf):
+        """The K components of the stationary path's affine source projected like rhs_red / r_fd (``lrbms_project_sources`` on
+        the basis and the divergence of its RT0 reconstruction images), into ``rd.rhs_red_K`` / ``rd.r_fd_K``.  On every
+        subdomain, also after an incremental re-projection: the arrays are those of a whole ``reduce()``.  They live in the
+        reduce buffers ``buf`` like the rest of the model, so an incremental reduce writes them in place and a previous model
+        sharing those buffers stays consistent (as its B_sys and Grams do)."""
+        src = getattr(self.d, '_affine_f', None)
+        if src is not None:
+            eng = self.d.engine
+            V = V.contiguous()
+            D = eng.ctx.div_apply(eng.ctx.flux_reconstruct(eng.F, V), mode=0)
+            K, N = int(src['K']), int(V.shape[2])
+            out = buf.get('src')
+            if out is None or tuple(out[0].shape) != (K, eng.S, N):
+                out = (eng.ctx.empty(K, eng.S, N), eng.ctx.empty(K, eng.S, 5 * eng.Q * N))
+            rd.rhs_red_K, rd.r_fd_K = buf['src'] = eng.ctx.project_sources(eng.Q, src['b_K'], V, D, out=out)
+            rd.rhs_red = None                                             # the projection of sum_j f_j: no parameter's
+        return rd
 
     def image_bases(self):
         """The image bases the reference keeps as ``bases['OI_i']`` / ``bases['RT_i']`` (reductor.py:40-60), target-major:

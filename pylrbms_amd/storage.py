@@ -10,7 +10,8 @@ shape, subdomain template, affine components, basis width) and is checked on loa
            ``G_aa`` [Q, Q, S, N, N] and either the factored layout ``G_nc`` [S, N, N], ``G_rdd`` / ``G_bb`` [S, QN, QN],
            ``G_ab`` [Q, S, N, QN], ``F_side`` [S, 4, ncf, 4QN + 4], ``F_nc`` [S, 4, nvs, 2N + 4nvs] (default of the fused
            pass) or the dense one ``G_nc`` [S, 5N, 5N], ``G_rdd`` / ``G_bb`` [S, 9, QN, QN] (block-compact), ``G_ab``
-           [Q, S, N, 5QN] (include/lrbms_hip.h)
+           [Q, S, N, 5QN] (include/lrbms_hip.h); with a parameter-dependent affine source (stationary path) also
+           ``rhs_red_K`` [K, S, N] and ``r_fd_K`` [K, S, 5QN], and ``source_K`` in the header (checked on load)
 """
 import json
 
@@ -74,14 +75,18 @@ def load_bases(d, path):
 def save_reduced(rd, path):
     """Write the reduced model ``rd`` (projected system + projected estimator operators) to ``path``."""
     from safetensors.torch import save_file
-    if getattr(rd, 'rhs_red_K', None) is not None:
+    affine = getattr(rd, 'rhs_red_K', None) is not None and getattr(rd.d, '_affine_f', None) is not None
+    if getattr(rd, 'rhs_red_K', None) is not None and not affine:
         raise NotImplementedError('save_reduced: the model carries a time-dependent source with {} component(s) (rhs_red_K, '
                                   'r_fd_K), which this format does not store'.format(rd.rhs_red_K.shape[0]))
     meta = _signature(rd.d, rd.N)
     meta['kind'] = 'reduced'
     meta['local_sizes'] = json.dumps(rd.reductor.local_sizes())
-    tensors = dict(zip(_SYS, (rd.B_sys, rd.rhs_red, rd.E_red, rd.M_red)))
+    tensors = {k: v for k, v in zip(_SYS, (rd.B_sys, rd.rhs_red, rd.E_red, rd.M_red)) if v is not None}   # affine: no rhs_red
     tensors.update(dict(zip(_GRAMS + ('F_side', 'F_nc'), rd.grams)))       # zip stops after 6 tensors for the dense layout
+    if affine:
+        meta['source_K'] = str(int(rd.rhs_red_K.shape[0]))
+        tensors.update(rhs_red_K=rd.rhs_red_K, r_fd_K=rd.r_fd_K)
     save_file({k: v.contiguous() for k, v in tensors.items()}, path, metadata=meta)
     return path
 
@@ -93,8 +98,8 @@ def load_reduced(reductor, path, cls=None):
     d = reductor.d
     with safe_open(path, framework='pt', device=str(d.engine.ctx.device)) as f:
         meta = f.metadata()
-        tensors = {k: f.get_tensor(k) for k in _SYS + _GRAMS}
-        for k in ('F_side', 'F_nc'):
+        tensors = {k: f.get_tensor(k) for k in _SYS + _GRAMS if k != 'rhs_red'}
+        for k in ('rhs_red', 'F_side', 'F_nc', 'rhs_red_K', 'r_fd_K'):
             if k in f.keys():
                 tensors[k] = f.get_tensor(k)
     N = int(meta['N'])
@@ -103,6 +108,14 @@ def load_reduced(reductor, path, cls=None):
     _check(meta, want, path)
     if json.loads(meta['local_sizes']) != reductor.local_sizes():
         raise ValueError('{}: stored local basis sizes do not match the reductor'.format(path))
-    buffers = {'sys': tuple(tensors[k] for k in _SYS),
+    src = getattr(d, '_affine_f', None)
+    want_K = None if src is None else str(int(src['K']))
+    if meta.get('source_K') != want_K:
+        raise ValueError('{}: stored source components {} do not match this discretization ({})'.format(
+            path, meta.get('source_K', 'none'), want_K or 'none'))
+    buffers = {'sys': tuple(tensors.get(k) for k in _SYS),
                'grams': [tensors[k] for k in _GRAMS] + ([tensors['F_side'], tensors['F_nc']] if 'F_side' in tensors else [])}
-    return (cls or ReducedDiscretization)(reductor, buffers, N)
+    rd = (cls or ReducedDiscretization)(reductor, buffers, N)
+    if src is not None:
+        rd.rhs_red_K, rd.r_fd_K = tensors['rhs_red_K'], tensors['r_fd_K']
+    return rd
