@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Benchmark of the LRBMS offline hot path (project + estimate-offline: K7 + K8 + P1 + P2 of SURVEY.md section 8).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-online] [--no-config5]]
 
 One "step" = one pass of the hot path over all subdomains of the synthetic multiscale-diffusion problem
 (BASELINE.json config 3: 32x32 subdomains, local basis dim 40, fp64): Oswald image bases, RT0 flux-reconstruction
@@ -9,7 +10,12 @@ image bases, Galerkin projection of the block SWIPDG system and of every estimat
 operators, bases) are resident in HBM before the timed region.  For N > 1 the subdomains are tiled over the ranks
 (strong scaling, as BASELINE.json config 4) and every step starts with the halo all-gather of neighbour basis rows.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what its headline figure needs: set-up,
+the untimed passes that bring the device to its steady clocks, W warm-up + K timed passes, the outputs' checks and checksums.
+--full adds everything else the benchmark measures, each in runs of its own: the CPU baselines (`cpu_baseline`), the per-kernel
+table and the rooflines (`roofline`), the dense layout, the assembly time (`assemble`), the online solve, enrichment and parabolic
+legs and, at config 3 on one rank, the config-5 leg (`config5`); --no-cpu-baseline, --no-online and --no-config5 leave legs of a
+full run out.  The timed region and the headline figure are the same with and without --full.
 
 --dump-outputs DIR writes what the last timed step computed (the arrays `project_and_estimate` hands its caller, named as in
 include/lrbms_hip.h) to DIR/<name>.npy in fp64: two builds run with the same arguments get the same inputs and can be compared
@@ -257,9 +263,12 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', default='cfg3', choices=sorted(CONFIGS) + ['cfg5', 'cfg5_tile8'])
-    ap.add_argument('--no-config5', action='store_true', help='skip the config-5 (3D, P2) leg of the default run')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-online', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline figure: CPU baselines, per-kernel and roofline figures, the '
+                         'dense layout, assembly, the online, enrichment and parabolic legs, the config-5 leg of config 3')
+    ap.add_argument('--no-config5', action='store_true', help='skip the config-5 (3D, P2) leg of a --full run')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU baselines of a --full run')
+    ap.add_argument('--no-online', action='store_true', help='skip the online, enrichment and parabolic legs of a --full run')
     ap.add_argument('--opt', action='append', default=[], metavar='NAME=VALUE',
                     help='launch-policy option of the 2D context (NativeContext.OPTIONS), e.g. --opt streams=0; measurement only')
     ap.add_argument('--opt3', action='append', default=[], metavar='NAME=VALUE',
@@ -284,8 +293,8 @@ def main():
         # BASELINE.json config 5 (3D diffusion, SWIPDG p = 2): its own line (bench3d.py); one rank holds all subdomains
         import bench3d
         line = bench3d.run(args.config, args.steps, args.warmup, device_index=int(os.environ.get('LRBMS_BENCH_DEVICE', local_rank)),
-                           cpu=not args.no_cpu_baseline, online=not args.no_online, world=world, rank=rank,
-                           backend=os.environ.get('LRBMS_BENCH_BACKEND', 'nccl'), options=opts3)
+                           cpu=args.full and not args.no_cpu_baseline, online=args.full and not args.no_online, world=world, rank=rank,
+                           backend=os.environ.get('LRBMS_BENCH_BACKEND', 'nccl'), options=opts3, full=args.full)
         if line is not None:
             print(json.dumps(line), flush=True)
         return
@@ -294,10 +303,10 @@ def main():
 
     # the CPU baseline runs first: its worker pool is fork()ed from a process that has not initialised the GPU
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg['num_subdomains'], N, cfg['coarse_per_subdomain'])
     cpu5 = None
-    do_cfg5 = world == 1 and rank == 0 and args.config == 'cfg3' and not args.no_config5
+    do_cfg5 = args.full and world == 1 and rank == 0 and args.config == 'cfg3' and not args.no_config5
     if do_cfg5 and not args.no_cpu_baseline:
         try:
             import bench3d
@@ -338,12 +347,14 @@ def main():
         eng.ctx.set_option(name, value)
     eng.assemble()
     torch.cuda.synchronize()
-    ta0, ta1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ta0.record()
-    eng.assemble()                                   # K1-K6, K8 coefficients, K9 (reported separately)
-    ta1.record()
-    torch.cuda.synchronize()
-    assemble_ms = ta0.elapsed_time(ta1)
+    assemble_ms = None
+    if args.full:
+        ta0, ta1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ta0.record()
+        eng.assemble()                               # K1-K6, K8 coefficients, K9 (reported separately)
+        ta1.record()
+        torch.cuda.synchronize()
+        assemble_ms = ta0.elapsed_time(ta1)
     t = grid.template
     S_total = grid.num_subdomains
 
@@ -368,24 +379,27 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Every kernel of the pass on its own: HIP event pairs on the stream each kernel is launched on (lrbms_kernel_timing), in a
-    # separate untimed loop of the same steps -- and it runs FIRST: after an idle period (the host builds the bases above) the
-    # device needs ~25 passes (18 ms) to reach its steady clocks, the first ones run up to 10 % slower (tools/ramp_time.py), and W
-    # warm-up passes of 0.7 ms do not cover that.  The timed region below is W warm-up + exactly K timed passes, at steady clocks.
+    # An untimed loop of the same steps runs FIRST: after an idle period (the host builds the bases above) the device needs ~25
+    # passes (18 ms) to reach its steady clocks, the first ones run up to 10 % slower (tools/ramp_time.py), and W warm-up passes of
+    # 0.7 ms do not cover that.  The timed region below is W warm-up + exactly K timed passes, at steady clocks.  With --full the
+    # last K of these passes time every kernel of the pass on its own: HIP event pairs on the stream each kernel is launched on
+    # (lrbms_kernel_timing).
     kernel_ms = None
     if eng.ctx.fused_supported(eng.Q, N, factored=True):
         for _ in range(max(0, 30 - args.steps)):
             step()
-        eng.ctx.kernel_timing(True)
+        if args.full:
+            eng.ctx.kernel_timing(True)
         for _ in range(args.steps):
             step()
-        rows = eng.ctx.kernel_timing_read()
-        eng.ctx.kernel_timing(False)
-        if world == 1:
-            kernel_ms = {}
-            for name, ms in rows:
-                kernel_ms.setdefault({'k_f1w': 'k_f1', 'k_f1v': 'k_f1', 'k_f1u': 'k_f1'}.get(name, name), []).append(ms)   # the forms of one step
-            kernel_ms = {k: float(np.mean(v)) for k, v in kernel_ms.items()}
+        if args.full:
+            rows = eng.ctx.kernel_timing_read()
+            eng.ctx.kernel_timing(False)
+            if world == 1:
+                kernel_ms = {}
+                for name, ms in rows:
+                    kernel_ms.setdefault({'k_f1w': 'k_f1', 'k_f1v': 'k_f1', 'k_f1u': 'k_f1'}.get(name, name), []).append(ms)   # the forms of one step
+                kernel_ms = {k: float(np.mean(v)) for k, v in kernel_ms.items()}
     fence()
 
     for _ in range(args.warmup):
@@ -421,7 +435,7 @@ def main():
 
     # the dense (fp64-MFMA) kernels of the pass on their own: phase 4 = k_f1, k_f2, k_f3 (HIP events on the launch stream)
     dense_ms = None
-    if world == 1 and eng.ctx.fused_supported(eng.Q, N, factored=True):
+    if args.full and world == 1 and eng.ctx.fused_supported(eng.Q, N, factored=True):
         pargs = (V, eng.F, eng.A_diag, eng.A_cpl, eng.P_diag, eng.b, eng.ebar, eng.caa, eng.Aab, eng.Bbb, buf['work'],
                  buf['sys'], buf['grams'])
         eng.ctx.project_estimate_fused(*pargs, phase=4)
@@ -438,7 +452,7 @@ def main():
     # the same pass writing the DENSE block-compact layout (G_rdd / G_bb [S][9][QN][QN], G_nc [S][5N][5N]: what rd.operators hands a
     # caller of the reference's API; the timed region above writes the factored layout the reduced estimate consumes)
     dense_layout_ms = None
-    if world == 1 and eng.ctx.fused_supported(eng.Q, N, factored=False):
+    if args.full and world == 1 and eng.ctx.fused_supported(eng.Q, N, factored=False):
         bufd = eng.alloc_reduce_buffers(N, factored=False)
         eng.__dict__.pop('_bound_pass', None)
         eng.project_and_estimate(V, bufd)
@@ -455,7 +469,7 @@ def main():
         torch.cuda.empty_cache()
 
     online = None
-    if world == 1 and not args.no_online:
+    if args.full and world == 1 and not args.no_online:
         # online phase (O1) on the same problem: energy-orthonormalise the local bases (B1) with the projected energy
         # product of the last pass, re-project, then solve 256 parameters in batches of 16
         Lh = np.linalg.cholesky(buf['sys'][2].cpu().numpy())                 # [S, N, N], small: done on the host
@@ -518,7 +532,7 @@ def main():
                             'estimates: lrbms_reduced_estimate_batch (local nc / r / df terms of every subdomain)'}
 
     enrichment = None
-    if world == 1 and not args.no_online:
+    if args.full and world == 1 and not args.no_online:
         # online enrichment: the neighbourhood corrector problems of ALL subdomains in one launch
         # (5 * 384 = 1920 unknowns each at config 3), block-Jacobi PCG to rtol 1e-12 inside one workgroup per problem
         th = np.array([c.evaluate(0.3) for c in lam['coefficients']])
@@ -550,7 +564,7 @@ def main():
         enrichment['incremental_reprojection'] = reproj
 
     parabolic = None
-    if world == 1 and not args.no_online:
+    if args.full and world == 1 and not args.no_online:
         # parabolic LRBMS: implicit Euler trajectories, full order and reduced, each ONE native call
         # (T = 0.05, 10 steps, mu = 0.5, zero initial data; the reduced model is the online one built above)
         th = np.array([c.evaluate(0.5) for c in lam['coefficients']])
@@ -587,91 +601,93 @@ def main():
 
     if rank == 0:
         Q = eng.Q
-        flops = algorithmic_flops_per_subdomain(t.n, t.n_rt, t.n_T, N, Q)
-        byts = algorithmic_bytes_per_subdomain(t.n, t.n_rt, t.n_T, N, Q)
-        # device time of one pass on this rank's stream (HIP events on the launch stream)
-        dev_s_per_step = 1e-3 * dev_ms / args.steps
-        s_rank = eng.S
-        model = kernel_model(t, N, Q, s_rank)
-        f1_flops = eng.ctx.fused_mfma_per_subdomain(Q, N) * 2048 * s_rank     # what the launcher's form of k_f1 executes (k_f1v: dead
-        model['k_f1'] = (model['k_f1'][0], model['k_f1'][1], f1_flops)        # tiles of the symmetric groups skipped, two applies)
-        # COMPULSORY bytes of the pass: every input once (basis slabs + the neighbour rows a subdomain reads, assembled
-        # operators) and every output once, in the layouts the pass actually writes (G_rdd / G_bb block-compact).  This is
-        # what the HBM roofline is priced against; the SURVEY 8(d) "algorithmic" count also charges the intermediates W, R,
-        # D and the dense form of the two big Gram operators, which the fused pass never moves -- reported separately below,
-        # it is NOT a utilisation figure (it exceeds what HBM can stream).
-        inputs = 8 * (t.n * N + 4 * 3 * t.ntouch * N + t.n_T * (36 * Q + 36 + 1 + Q * Q + 9 * Q + 9) + Q * 4 * t.ncf * 9 +
-                      Q * t.n_rt * 6 + t.n) * s_rank
-        outputs = sum(w for k, (r, w, f) in model.items() if k not in ('k_flux_compact', 'k_vertex_avg', 'k_thin3', 'k_prep_lds'))
-        compulsory = inputs + outputs
-        ach_gbs = compulsory / dev_s_per_step / 1e9
-        pmc = load_pmc_traffic(args.config) if world == 1 else None
-        pmc_note = None
-        if pmc and pmc['stale']:
-            pmc_note = '{} (withheld: the kernel sources changed since that profile was taken)'.format(pmc['file'])
-            pmc = None
-        traffic = pmc['per_pass_bytes'] if pmc else None
-        # The pass is bound by the fp64 matrix pipe, not by HBM: its dominant kernel (k_f1, ~45 % of the pass) and the dense
-        # kernels together run at > 0.5 of the MFMA peak while the compulsory bytes need 0.12 of the HBM peak.  Top level = the
-        # time-weighted bound: executed fp64-MFMA flops of the dense kernels (k_f1 + k_f2 + k_f3, padding included, as the
-        # library counts them) over their measured time; the HBM view of the whole pass stays beside it under `hbm`.
-        hbm = {'bound': 'hbm', 'achieved': ach_gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': ach_gbs / PEAK_HBM_GBS,
-               'basis': 'compulsory bytes per pass (inputs once + outputs once, compact layouts) / device time of the pass',
-               'compulsory_bytes': compulsory, 'compulsory_input_bytes': inputs, 'compulsory_output_bytes': outputs,
-               'traffic': traffic, 'traffic_over_compulsory': (traffic / compulsory) if traffic else None,
-               'traffic_frac_of_peak': (traffic / dev_s_per_step / 1e9 / PEAK_HBM_GBS) if traffic else None,
-               'traffic_source': pmc['file'] if pmc else pmc_note}
-        roofline = {'bound': 'mfma', 'achieved': None, 'peak': PEAK_FP64_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': None,
-                    'traffic': traffic, 'traffic_source': pmc['file'] if pmc else pmc_note, 'hbm': hbm,
-                    'basis': 'executed fp64-MFMA flops (padding included) of the dense kernels k_f1 + k_f2 (+ k_f3 when it runs) / their '
-                             'measured time (phase 4 of the pass, HIP events on the launch stream); the dominant kernel alone: dominant_kernel',
-                    'kernel': 'fused project+estimate pass: k_prep_lds (flux image, vertex averages and G_nc[self,self] from one copy of '
-                              'the basis slab in LDS; without LRBMS_OPT_PREP_LDS: k_flux_compact, k_vertex_avg, k_f3), k_f1, k_f2, k_thin3 '
-                              '(= k_coupling, k_thin_rt, k_thin_ncf in one launch)',
-                    'device_ms_per_step': 1e3 * dev_s_per_step,
-                    'dense_layout_ms_per_step': dense_layout_ms,
-                    'survey_8d_algorithmic': {'bytes_per_subdomain': byts, 'flops_per_subdomain': flops,
-                                              'note': 'canonical counts of SURVEY 8(d); ~90 % of the flops are structural zeros the pass '
-                                                      'skips and the bytes include intermediates it keeps on chip: not executed, not moved',
-                                              'GBps': byts * s_rank / dev_s_per_step / 1e9,
-                                              'TFLOPs': flops * s_rank / dev_s_per_step / 1e12}}
-        if kernel_ms:
-            table = []
-            for name, ms in sorted(kernel_ms.items(), key=lambda kv: -kv[1]):
-                r, w, f = model.get(name, (None, None, None))
-                row = {'name': name, 'us': 1e3 * ms, 'bytes_read': r, 'bytes_written': w, 'mfma_flops': f}
-                if r is not None:
-                    row['hbm_GBps'] = (r + w) / (1e-3 * ms) / 1e9
-                    row['hbm_frac'] = row['hbm_GBps'] / PEAK_HBM_GBS
-                if f:
-                    row['mfma_TFLOPs'] = f / (1e-3 * ms) / 1e12
-                    row['mfma_frac'] = row['mfma_TFLOPs'] / PEAK_FP64_MFMA_TFLOPS
-                if pmc and name in pmc.get('per_kernel', {}):
-                    row['pmc_bytes'] = pmc['per_kernel'][name]['bytes']
-                table.append(row)
-            roofline['kernels'] = table
-            roofline['kernels_sum_us'] = sum(r['us'] for r in table)
-            dom = table[0]
-            roofline['dominant_kernel'] = dict(dom, bound='mfma' if dom.get('mfma_frac', 0) >= dom.get('hbm_frac', 0) else 'hbm',
-                                               frac=max(dom.get('mfma_frac', 0), dom.get('hbm_frac', 0)))
-        if dense_ms is not None:
-            # (with LRBMS_OPT_PREP_LDS, the default, G_nc[self, self] is produced by k_prep_lds and k_f3 is not launched)
-            dense_names = [k for k in ('k_f1', 'k_f2', 'k_f3') if kernel_ms is None or k in kernel_ms]
-            mf = sum(model[k][2] for k in dense_names)
-            roofline['dense_kernels'] = {'bound': 'mfma', 'achieved': mf / (1e-3 * dense_ms) / 1e12, 'peak': PEAK_FP64_MFMA_TFLOPS,
-                                         'unit': 'TFLOP/s', 'frac': mf / (1e-3 * dense_ms) / 1e12 / PEAK_FP64_MFMA_TFLOPS,
-                                         'ms': dense_ms, 'executed_mfma_flops': mf,
-                                         'kernel': ' + '.join(dense_names) + ' (phase 4 of the pass; executed fp64 MFMA flops, padding '
-                                                   'included, over their measured time)'}
-            roofline['achieved'], roofline['frac'] = roofline['dense_kernels']['achieved'], roofline['dense_kernels']['frac']
-        elif kernel_ms and roofline.get('dominant_kernel', {}).get('mfma_TFLOPs'):
-            roofline['achieved'] = roofline['dominant_kernel']['mfma_TFLOPs']
-            roofline['frac'] = roofline['dominant_kernel']['mfma_frac']
-        # the pass as a whole against the matrix peak: every executed fp64-MFMA flop (the dense kernels, the G_nc fold of the
-        # preparation kernel; padding included, as the library counts them) over the time of the whole pass
-        pass_flops = sum(f for k, (r, w, f) in model.items() if f and (kernel_ms is None or k in kernel_ms))
-        roofline['pass_executed_mfma_flops'] = pass_flops
-        roofline['pass_mfma_frac'] = pass_flops / dev_s_per_step / 1e12 / PEAK_FP64_MFMA_TFLOPS
+        roofline = None
+        if args.full:
+            flops = algorithmic_flops_per_subdomain(t.n, t.n_rt, t.n_T, N, Q)
+            byts = algorithmic_bytes_per_subdomain(t.n, t.n_rt, t.n_T, N, Q)
+            # device time of one pass on this rank's stream (HIP events on the launch stream)
+            dev_s_per_step = 1e-3 * dev_ms / args.steps
+            s_rank = eng.S
+            model = kernel_model(t, N, Q, s_rank)
+            f1_flops = eng.ctx.fused_mfma_per_subdomain(Q, N) * 2048 * s_rank     # what the launcher's form of k_f1 executes (k_f1v: dead
+            model['k_f1'] = (model['k_f1'][0], model['k_f1'][1], f1_flops)        # tiles of the symmetric groups skipped, two applies)
+            # COMPULSORY bytes of the pass: every input once (basis slabs + the neighbour rows a subdomain reads, assembled
+            # operators) and every output once, in the layouts the pass actually writes (G_rdd / G_bb block-compact).  This is
+            # what the HBM roofline is priced against; the SURVEY 8(d) "algorithmic" count also charges the intermediates W, R,
+            # D and the dense form of the two big Gram operators, which the fused pass never moves -- reported separately below,
+            # it is NOT a utilisation figure (it exceeds what HBM can stream).
+            inputs = 8 * (t.n * N + 4 * 3 * t.ntouch * N + t.n_T * (36 * Q + 36 + 1 + Q * Q + 9 * Q + 9) + Q * 4 * t.ncf * 9 +
+                          Q * t.n_rt * 6 + t.n) * s_rank
+            outputs = sum(w for k, (r, w, f) in model.items() if k not in ('k_flux_compact', 'k_vertex_avg', 'k_thin3', 'k_prep_lds'))
+            compulsory = inputs + outputs
+            ach_gbs = compulsory / dev_s_per_step / 1e9
+            pmc = load_pmc_traffic(args.config) if world == 1 else None
+            pmc_note = None
+            if pmc and pmc['stale']:
+                pmc_note = '{} (withheld: the kernel sources changed since that profile was taken)'.format(pmc['file'])
+                pmc = None
+            traffic = pmc['per_pass_bytes'] if pmc else None
+            # The pass is bound by the fp64 matrix pipe, not by HBM: its dominant kernel (k_f1, ~45 % of the pass) and the dense
+            # kernels together run at > 0.5 of the MFMA peak while the compulsory bytes need 0.12 of the HBM peak.  Top level = the
+            # time-weighted bound: executed fp64-MFMA flops of the dense kernels (k_f1 + k_f2 + k_f3, padding included, as the
+            # library counts them) over their measured time; the HBM view of the whole pass stays beside it under `hbm`.
+            hbm = {'bound': 'hbm', 'achieved': ach_gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': ach_gbs / PEAK_HBM_GBS,
+                   'basis': 'compulsory bytes per pass (inputs once + outputs once, compact layouts) / device time of the pass',
+                   'compulsory_bytes': compulsory, 'compulsory_input_bytes': inputs, 'compulsory_output_bytes': outputs,
+                   'traffic': traffic, 'traffic_over_compulsory': (traffic / compulsory) if traffic else None,
+                   'traffic_frac_of_peak': (traffic / dev_s_per_step / 1e9 / PEAK_HBM_GBS) if traffic else None,
+                   'traffic_source': pmc['file'] if pmc else pmc_note}
+            roofline = {'bound': 'mfma', 'achieved': None, 'peak': PEAK_FP64_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': None,
+                        'traffic': traffic, 'traffic_source': pmc['file'] if pmc else pmc_note, 'hbm': hbm,
+                        'basis': 'executed fp64-MFMA flops (padding included) of the dense kernels k_f1 + k_f2 (+ k_f3 when it runs) / their '
+                                 'measured time (phase 4 of the pass, HIP events on the launch stream); the dominant kernel alone: dominant_kernel',
+                        'kernel': 'fused project+estimate pass: k_prep_lds (flux image, vertex averages and G_nc[self,self] from one copy of '
+                                  'the basis slab in LDS; without LRBMS_OPT_PREP_LDS: k_flux_compact, k_vertex_avg, k_f3), k_f1, k_f2, k_thin3 '
+                                  '(= k_coupling, k_thin_rt, k_thin_ncf in one launch)',
+                        'device_ms_per_step': 1e3 * dev_s_per_step,
+                        'dense_layout_ms_per_step': dense_layout_ms,
+                        'survey_8d_algorithmic': {'bytes_per_subdomain': byts, 'flops_per_subdomain': flops,
+                                                  'note': 'canonical counts of SURVEY 8(d); ~90 % of the flops are structural zeros the pass '
+                                                          'skips and the bytes include intermediates it keeps on chip: not executed, not moved',
+                                                  'GBps': byts * s_rank / dev_s_per_step / 1e9,
+                                                  'TFLOPs': flops * s_rank / dev_s_per_step / 1e12}}
+            if kernel_ms:
+                table = []
+                for name, ms in sorted(kernel_ms.items(), key=lambda kv: -kv[1]):
+                    r, w, f = model.get(name, (None, None, None))
+                    row = {'name': name, 'us': 1e3 * ms, 'bytes_read': r, 'bytes_written': w, 'mfma_flops': f}
+                    if r is not None:
+                        row['hbm_GBps'] = (r + w) / (1e-3 * ms) / 1e9
+                        row['hbm_frac'] = row['hbm_GBps'] / PEAK_HBM_GBS
+                    if f:
+                        row['mfma_TFLOPs'] = f / (1e-3 * ms) / 1e12
+                        row['mfma_frac'] = row['mfma_TFLOPs'] / PEAK_FP64_MFMA_TFLOPS
+                    if pmc and name in pmc.get('per_kernel', {}):
+                        row['pmc_bytes'] = pmc['per_kernel'][name]['bytes']
+                    table.append(row)
+                roofline['kernels'] = table
+                roofline['kernels_sum_us'] = sum(r['us'] for r in table)
+                dom = table[0]
+                roofline['dominant_kernel'] = dict(dom, bound='mfma' if dom.get('mfma_frac', 0) >= dom.get('hbm_frac', 0) else 'hbm',
+                                                   frac=max(dom.get('mfma_frac', 0), dom.get('hbm_frac', 0)))
+            if dense_ms is not None:
+                # (with LRBMS_OPT_PREP_LDS, the default, G_nc[self, self] is produced by k_prep_lds and k_f3 is not launched)
+                dense_names = [k for k in ('k_f1', 'k_f2', 'k_f3') if kernel_ms is None or k in kernel_ms]
+                mf = sum(model[k][2] for k in dense_names)
+                roofline['dense_kernels'] = {'bound': 'mfma', 'achieved': mf / (1e-3 * dense_ms) / 1e12, 'peak': PEAK_FP64_MFMA_TFLOPS,
+                                             'unit': 'TFLOP/s', 'frac': mf / (1e-3 * dense_ms) / 1e12 / PEAK_FP64_MFMA_TFLOPS,
+                                             'ms': dense_ms, 'executed_mfma_flops': mf,
+                                             'kernel': ' + '.join(dense_names) + ' (phase 4 of the pass; executed fp64 MFMA flops, padding '
+                                                       'included, over their measured time)'}
+                roofline['achieved'], roofline['frac'] = roofline['dense_kernels']['achieved'], roofline['dense_kernels']['frac']
+            elif kernel_ms and roofline.get('dominant_kernel', {}).get('mfma_TFLOPs'):
+                roofline['achieved'] = roofline['dominant_kernel']['mfma_TFLOPs']
+                roofline['frac'] = roofline['dominant_kernel']['mfma_frac']
+            # the pass as a whole against the matrix peak: every executed fp64-MFMA flop (the dense kernels, the G_nc fold of the
+            # preparation kernel; padding included, as the library counts them) over the time of the whole pass
+            pass_flops = sum(f for k, (r, w, f) in model.items() if f and (kernel_ms is None or k in kernel_ms))
+            roofline['pass_executed_mfma_flops'] = pass_flops
+            roofline['pass_mfma_frac'] = pass_flops / dev_s_per_step / 1e12 / PEAK_FP64_MFMA_TFLOPS
         out = {'metric': 'offline project+estimate throughput', 'value': value, 'unit': 'subdomains/s',
                'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
                'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
@@ -682,14 +698,17 @@ def main():
                                               cfg['num_subdomains'][0], cfg['num_subdomains'][1],
                                               cfg['coarse_per_subdomain'], t.n, t.n_rt, Q, N),
                           'subdomains': S_total, 'N': N, 'Q': Q, 'parallelism': 'subdomain tiles x{}'.format(world)},
-               'roofline': roofline, 'distributed': dist_info, 'output_checksum': output_checksum, 'output_abs_checksum': output_abs_checksum,
-               'timed_region': 'W warm-up + exactly K timed passes between barrier + synchronize, at steady device clocks: the untimed '
-                               'per-kernel timing leg (>= 30 passes of the same step) runs in front of it -- after an idle period the '
-                               'first ~25 passes run up to 10 % slower (tools/ramp_time.py)'}
+               'distributed': dist_info, 'output_checksum': output_checksum, 'output_abs_checksum': output_abs_checksum,
+               'timed_region': 'W warm-up + exactly K timed passes between barrier + synchronize, at steady device clocks: untimed '
+                               'passes of the same step (>= 30; with --full the per-kernel timing leg) run in front of it -- after an '
+                               'idle period the first ~25 passes run up to 10 % slower (tools/ramp_time.py)'}
+        if roofline is not None:
+            out['roofline'] = roofline
         if dumped is not None:
             out['dumped_outputs'] = dumped
-        out['assemble'] = {'metric': 'offline assembly K1-K6, K9 (+ flux coefficients)', 'ms': assemble_ms,
-                           'value': eng.S / (1e-3 * assemble_ms), 'unit': 'subdomains/s (this rank)'}
+        if assemble_ms is not None:
+            out['assemble'] = {'metric': 'offline assembly K1-K6, K9 (+ flux coefficients)', 'ms': assemble_ms,
+                               'value': eng.S / (1e-3 * assemble_ms), 'unit': 'subdomains/s (this rank)'}
         if online is not None:
             out['online'] = online
         if enrichment is not None:
@@ -705,7 +724,7 @@ def main():
             torch.cuda.empty_cache()
             try:
                 out['config5'] = bench3d.run('cfg5', steps=args.steps, warmup=args.warmup, device_index=local_rank, cpu=False,
-                                             online=not args.no_online, options=opts3)
+                                             online=not args.no_online, options=opts3, full=True)
                 if cpu5 is not None:
                     out['config5']['cpu_baseline'] = cpu5
             except Exception as exc:           # the config-3 line must not depend on the second leg: report, do not fail

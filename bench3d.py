@@ -1,9 +1,12 @@
 """Bench leg of BASELINE.json config 5 (3D diffusion, 8 x 8 x 8 subdomains, SWIPDG p = 2, local basis dim 30) -- used by
-bench.py (`--config cfg5` prints its line; the default config-3 run carries it as the `config5` object).
+bench.py (`--config cfg5` prints its line; a `--full` run of config 3 carries it as the `config5` object).
 
 A step is one pass of the 3D project+estimate path (lrbms3_project_estimate) over all subdomains of this rank on synthetic
 data (pylrbms_amd/multiscale_problem3d.py, constant + seeded random basis columns resident in HBM).  One GPU holds the whole
 8 x 8 x 8 configuration (0.47 GB of bases, 2.6 GB of assembled element blocks).
+
+`run(full=False)` (a plain bench run) does only what the headline figure needs; `full=True` adds the per-kernel table, the
+roofline and the assembly time (the CPU baseline and the online legs have switches of their own).
 
 Roofline of the dominant kernel: executed fp64-MFMA flops (padding included, counted from the kernel's own tile shapes) over
 its HIP-event duration against 78.6 TFLOP/s; compulsory HBM bytes of the pass (inputs once + outputs once) beside it."""
@@ -64,7 +67,7 @@ def cpu_baseline3d(N):
     """The 3D oracle's Reductor3D.reduce() (NumPy / SciPy) on a 2 x 2 x 2 sample of the same problem (k_c = 4, N as config 5),
     timed before the process touches the GPU: one process, and the target subdomains farmed over a fork()ed pool on the host cores
     the process may use (as bench.py does for config 3).  Why not 4 x 4 x 4: the oracle ASSEMBLES its global sparse operators in
-    Python (21 s for 2 x 2 x 2, 76 s for 3 x 3 x 3, ~3 min for 4 x 4 x 4: untimed, but inside the default bench run), and its
+    Python (21 s for 2 x 2 x 2, 76 s for 3 x 3 x 3, ~3 min for 4 x 4 x 4: untimed, but inside a --full bench run), and its
     rate per target subdomain barely depends on the sample (1.4 / s at 2 x 2 x 2, 1.0 / s at 3 x 3 x 3 on one core here)."""
     import multiprocessing as mp
     from threadpoolctl import threadpool_limits
@@ -100,12 +103,13 @@ def cpu_baseline3d(N):
             'sample': 'oracle.lrbms3d.Reductor3D.reduce() (NumPy/SciPy fp64) on 2x2x2 subdomains of the same synthetic 3D problem '
                       '(k_c = 4, n = 3840, N = {}): value = the 8 target subdomains farmed over a {}-process pool (1 BLAS thread '
                       'each), value_1core = one process; timed before the GPU is touched.  A 4x4x4 sample would add ~3 min of '
-                      'untimed oracle assembly (Python) to the default bench run; the per-subdomain rate barely depends on the '
+                      'untimed oracle assembly (Python) to a --full bench run; the per-subdomain rate barely depends on the '
                       'sample size'.format(N, workers),
             'os_cpu_count': hc['os_cpu_count'], 'affinity': hc['affinity'], 'cgroup_quota': hc['cgroup_quota']}
 
 
-def run(config='cfg5', steps=10, warmup=2, device_index=0, cpu=True, online=True, world=1, rank=0, backend='nccl', options=None):
+def run(config='cfg5', steps=10, warmup=2, device_index=0, cpu=True, online=True, world=1, rank=0, backend='nccl', options=None,
+        full=True):
     """One rank of the config-5 bench.  world > 1 (launched by torch.distributed.run): the 8 x 8 x 8 subdomains are cut into
     one 3D tile per rank (strong scaling, as BASELINE.json config 5 asks for 8 GPUs), every step = one halo exchange of the
     neighbour rows (all_to_all_single over RCCL, point to point) + one pass; rank 0 returns the line, the others None."""
@@ -135,12 +139,13 @@ def run(config='cfg5', steps=10, warmup=2, device_index=0, cpu=True, online=True
         eng.ctx.set_option(name, value)
     eng.assemble()
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    eng.assemble()
-    e1.record()
-    torch.cuda.synchronize()
-    assemble_ms = e0.elapsed_time(e1)
+    if full:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        eng.assemble()
+        e1.record()
+        torch.cuda.synchronize()
+        assemble_ms = e0.elapsed_time(e1)
     t, S, Q = eng.t, eng.S, eng.Q
     S_total = p['grid'].num_subdomains
     g = torch.Generator(device='cuda').manual_seed(rank)
@@ -162,15 +167,18 @@ def run(config='cfg5', steps=10, warmup=2, device_index=0, cpu=True, online=True
             dist.barrier()
         torch.cuda.synchronize()
 
-    # the per-kernel timing leg (an untimed loop of the same passes) runs FIRST: after the host-side setup above the device needs
-    # ~18 ms of work to reach its steady clocks (tools/ramp_time.py); the timed region is W warm-up + exactly K passes behind it
+    # an untimed loop of the same passes runs FIRST (with `full`, its last K passes are the per-kernel timing leg): after the
+    # host-side setup above the device needs ~18 ms of work to reach its steady clocks (tools/ramp_time.py); the timed region is
+    # W warm-up + exactly K passes behind it
     for _ in range(max(0, 10 - steps)):
         eng.project_and_estimate(V, out, work, halo=halo)
-    eng.ctx.kernel_timing(True)
+    if full:
+        eng.ctx.kernel_timing(True)
     for _ in range(steps):
         eng.project_and_estimate(V, out, work)
-    rows = eng.ctx.kernel_timing_read()
-    eng.ctx.kernel_timing(False)
+    if full:
+        rows = eng.ctx.kernel_timing_read()
+        eng.ctx.kernel_timing(False)
     fence()
     for _ in range(warmup):
         eng.project_and_estimate(V, out, work, halo=halo)
@@ -194,60 +202,62 @@ def run(config='cfg5', steps=10, warmup=2, device_index=0, cpu=True, online=True
         raise RuntimeError('config-5 pass produced non-finite values in {}'.format(bad))
     checksum = {k: float(v.sum()) for k, v in out.items()}
     checksum['all'] = float(sum(checksum.values()))
-    agg = {}
-    for name, v in rows:
-        agg.setdefault(name, []).append(v)
-    counts = mfma_counts(t, N, Q)
-    table = []
-    for name, v in sorted(agg.items(), key=lambda kv: -np.mean(kv[1])):
-        us = 1e3 * float(np.mean(v))
-        row = {'name': name, 'us': us}
-        if name in counts:
-            fl = counts[name] * S * MFMA_FLOPS
-            row.update(mfma_flops=fl, mfma_TFLOPs=fl / (us * 1e-6) / 1e12, mfma_frac=fl / (us * 1e-6) / 1e12 / PEAK_FP64_MFMA_TFLOPS)
-        table.append(row)
-    inputs, outputs = compulsory_bytes(t, S, N, Q)
-    dense_us = sum(r['us'] for r in table if 'mfma_flops' in r)
-    dense_fl = sum(r['mfma_flops'] for r in table if 'mfma_flops' in r)
-    dom = table[0]
-    roofline = {'bound': 'mfma' if 'mfma_frac' in dom else 'hbm', 'unit': 'TFLOP/s' if 'mfma_frac' in dom else 'GB/s',
-                'achieved': dom.get('mfma_TFLOPs'), 'peak': PEAK_FP64_MFMA_TFLOPS, 'frac': dom.get('mfma_frac'), 'traffic': None,
-                'kernel': dom['name'], 'kernel_us': dom['us'],
-                'basis': 'executed fp64-MFMA flops of the dominant kernel (padding included) / its HIP-event duration',
-                'dense_kernels': {'us': dense_us, 'mfma_flops': dense_fl, 'TFLOPs': dense_fl / (dense_us * 1e-6) / 1e12,
-                                  'frac': dense_fl / (dense_us * 1e-6) / 1e12 / PEAK_FP64_MFMA_TFLOPS},
-                'compulsory_bytes': inputs + outputs, 'compulsory_input_bytes': inputs, 'compulsory_output_bytes': outputs,
-                'compulsory_GBps': (inputs + outputs) / (dev_ms * 1e-3) / 1e9,
-                'compulsory_frac_of_hbm_peak': (inputs + outputs) / (dev_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                'device_ms_per_step': dev_ms, 'kernels': table, 'kernels_sum_us': sum(r['us'] for r in table)}
-    # measured HBM traffic per launch from the committed rocprofv3 PMC passes of this configuration (FETCH_SIZE x 2 + WRITE_SIZE as the
-    # guide prescribes for gfx950; separate --pmc runs, tools/cfg5_pmc.sh): profiles/rNN_cfg5_pmc_traffic.json
-    if world == 1:
-        import glob
-        import json as _json
-        for path in sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles', 'r*_pmc_traffic.json')), reverse=True):
-            try:
-                doc = _json.load(open(path))
-            except (OSError, ValueError):
-                continue
-            if doc.get('config') != config:
-                continue
-            from pylrbms_amd._build import source_sha
-            if doc.get('csrc_sha') != source_sha():       # a profile speaks for the kernels it was taken from: look for this build's
-                roofline.setdefault('traffic_source', '{} (withheld: the kernel sources changed since that profile was taken)'.format(
-                    os.path.join('profiles', os.path.basename(path))))
-                continue
-            for r in table:
-                if r['name'] in doc['per_kernel']:
-                    r['pmc_bytes'] = doc['per_kernel'][r['name']]['bytes']
-            if dom['name'] in doc['per_kernel']:
-                roofline['traffic'] = doc['per_kernel'][dom['name']]['bytes']
-                roofline['traffic_GBps'] = roofline['traffic'] / (dom['us'] * 1e-6) / 1e9
-                roofline['traffic_frac_of_hbm_peak'] = roofline['traffic_GBps'] / PEAK_HBM_GBS
-            roofline['traffic_per_pass'] = doc['per_pass_bytes']
-            roofline['traffic_over_compulsory'] = doc['per_pass_bytes'] / (inputs + outputs)
-            roofline['traffic_source'] = os.path.join('profiles', os.path.basename(path))
-            break
+    roofline = None
+    if full:
+        agg = {}
+        for name, v in rows:
+            agg.setdefault(name, []).append(v)
+        counts = mfma_counts(t, N, Q)
+        table = []
+        for name, v in sorted(agg.items(), key=lambda kv: -np.mean(kv[1])):
+            us = 1e3 * float(np.mean(v))
+            row = {'name': name, 'us': us}
+            if name in counts:
+                fl = counts[name] * S * MFMA_FLOPS
+                row.update(mfma_flops=fl, mfma_TFLOPs=fl / (us * 1e-6) / 1e12, mfma_frac=fl / (us * 1e-6) / 1e12 / PEAK_FP64_MFMA_TFLOPS)
+            table.append(row)
+        inputs, outputs = compulsory_bytes(t, S, N, Q)
+        dense_us = sum(r['us'] for r in table if 'mfma_flops' in r)
+        dense_fl = sum(r['mfma_flops'] for r in table if 'mfma_flops' in r)
+        dom = table[0]
+        roofline = {'bound': 'mfma' if 'mfma_frac' in dom else 'hbm', 'unit': 'TFLOP/s' if 'mfma_frac' in dom else 'GB/s',
+                    'achieved': dom.get('mfma_TFLOPs'), 'peak': PEAK_FP64_MFMA_TFLOPS, 'frac': dom.get('mfma_frac'), 'traffic': None,
+                    'kernel': dom['name'], 'kernel_us': dom['us'],
+                    'basis': 'executed fp64-MFMA flops of the dominant kernel (padding included) / its HIP-event duration',
+                    'dense_kernels': {'us': dense_us, 'mfma_flops': dense_fl, 'TFLOPs': dense_fl / (dense_us * 1e-6) / 1e12,
+                                      'frac': dense_fl / (dense_us * 1e-6) / 1e12 / PEAK_FP64_MFMA_TFLOPS},
+                    'compulsory_bytes': inputs + outputs, 'compulsory_input_bytes': inputs, 'compulsory_output_bytes': outputs,
+                    'compulsory_GBps': (inputs + outputs) / (dev_ms * 1e-3) / 1e9,
+                    'compulsory_frac_of_hbm_peak': (inputs + outputs) / (dev_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                    'device_ms_per_step': dev_ms, 'kernels': table, 'kernels_sum_us': sum(r['us'] for r in table)}
+        # measured HBM traffic per launch from the committed rocprofv3 PMC passes of this configuration (FETCH_SIZE x 2 + WRITE_SIZE as the
+        # guide prescribes for gfx950; separate --pmc runs, tools/cfg5_pmc.sh): profiles/rNN_cfg5_pmc_traffic.json
+        if world == 1:
+            import glob
+            import json as _json
+            for path in sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles', 'r*_pmc_traffic.json')), reverse=True):
+                try:
+                    doc = _json.load(open(path))
+                except (OSError, ValueError):
+                    continue
+                if doc.get('config') != config:
+                    continue
+                from pylrbms_amd._build import source_sha
+                if doc.get('csrc_sha') != source_sha():       # a profile speaks for the kernels it was taken from: look for this build's
+                    roofline.setdefault('traffic_source', '{} (withheld: the kernel sources changed since that profile was taken)'.format(
+                        os.path.join('profiles', os.path.basename(path))))
+                    continue
+                for r in table:
+                    if r['name'] in doc['per_kernel']:
+                        r['pmc_bytes'] = doc['per_kernel'][r['name']]['bytes']
+                if dom['name'] in doc['per_kernel']:
+                    roofline['traffic'] = doc['per_kernel'][dom['name']]['bytes']
+                    roofline['traffic_GBps'] = roofline['traffic'] / (dom['us'] * 1e-6) / 1e9
+                    roofline['traffic_frac_of_hbm_peak'] = roofline['traffic_GBps'] / PEAK_HBM_GBS
+                roofline['traffic_per_pass'] = doc['per_pass_bytes']
+                roofline['traffic_over_compulsory'] = doc['per_pass_bytes'] / (inputs + outputs)
+                roofline['traffic_source'] = os.path.join('profiles', os.path.basename(path))
+                break
     mine = [float(S), float(len(eng.halo)), float(halo.send_bytes if halo is not None else 0), float(halo.recv_bytes if halo is not None else 0)]
     if world > 1:
         gathered = [torch.zeros(4, dtype=torch.float64, device=V.device) for _ in range(world)]
@@ -271,9 +281,10 @@ def run(config='cfg5', steps=10, warmup=2, device_index=0, cpu=True, online=True
                                       cfg['cubes_per_subdomain'], t.n, t.n_rt, Q, N),
                       'subdomains': S_total, 'N': N, 'Q': Q,
                       'parallelism': 'one rank holds every subdomain' if world == 1 else '3D subdomain tiles x{}'.format(world)},
-           'roofline': roofline, 'distributed': dist_info, 'output_checksum': checksum,
-           'assemble': {'ms': assemble_ms, 'value': S / (1e-3 * assemble_ms), 'unit': 'subdomains/s',
-                        'host_sampling_and_upload_s': setup_s}}
+           'distributed': dist_info, 'output_checksum': checksum}
+    if full:
+        res['roofline'] = roofline
+        res['assemble'] = {'ms': assemble_ms, 'value': S / (1e-3 * assemble_ms), 'unit': 'subdomains/s', 'host_sampling_and_upload_s': setup_s}
     if online:
         # online phase on the same reduced model: 256 parameters in batches of 16, then their estimates one by one
         mus = np.random.default_rng(7).uniform(0.1, 1.0, size=256)
@@ -365,6 +376,7 @@ if __name__ == '__main__':
     ap.add_argument('--config', default='cfg5', choices=sorted(CONFIGS3D))
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also the CPU baseline, the per-kernel table, the roofline, assembly and the online legs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU baseline of a --full run')
     a = ap.parse_args()
-    print(json.dumps(run(a.config, a.steps, a.warmup, cpu=not a.no_cpu_baseline)), flush=True)
+    print(json.dumps(run(a.config, a.steps, a.warmup, cpu=a.full and not a.no_cpu_baseline, online=a.full, full=a.full)), flush=True)

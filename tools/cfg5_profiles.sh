@@ -7,5 +7,5 @@ O=gpurun_out/cfg5; rm -rf $O; mkdir -p $O
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --config cfg5 --opt3 serial=1 --steps 5 --warmup 1 --no-cpu-baseline --no-online > $O/stats.log 2>&1
 cp $O/stats/*/*kernel_stats.csv $O/kernel_stats.csv
 echo stats done
-python3 bench.py --config cfg5 > $O/bench.json 2> $O/bench.err
+python3 bench.py --config cfg5 --full > $O/bench.json 2> $O/bench.err
 tail -c 600 $O/bench.json

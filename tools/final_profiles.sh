@@ -11,5 +11,5 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -- pyt
 echo write done
 python3 tools/pmc_traffic.py 3 $O/fetch $O/write > $O/pmc_traffic.txt 2>&1
 cat $O/pmc_traffic.txt
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 1500 $O/bench.json

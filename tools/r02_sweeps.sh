@@ -4,10 +4,10 @@
 TAG=${1:-r02sw}
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; rm -rf $O; mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err
-echo "bench.py --no-cpu-baseline --no-online --config <c> on one MI355X (per-kernel us from HIP events on the launch streams)" > $O/config_sweep.txt
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
+echo "bench.py --full --no-cpu-baseline --no-online --config <c> on one MI355X (per-kernel us from HIP events on the launch streams)" > $O/config_sweep.txt
 for c in cfg2 cfg3_tile8 cfg3_tile4 cfg3_tile2 cfg3_kc8 cfg3_kc16; do
-  python3 bench.py --no-cpu-baseline --no-online --config $c 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --full --no-cpu-baseline --no-online --config $c 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 ks = ' '.join('{} {:.0f}'.format(k['name'], k['us']) for k in d['roofline'].get('kernels', []))

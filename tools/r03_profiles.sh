@@ -27,6 +27,6 @@ for v in ptrace:prep_trace ttrace:thin_trace; do
   so=pylrbms_amd/_variants/${v%%:*}.so
   if [ -f $so ]; then LRBMS_HIP_LIB=$GRAFT_REPO_ROOT/$so python3 tools/${v##*:}.py 2> /dev/null > $O/${v##*:}.txt; fi
 done
-python3 bench.py > $O/bench.json 2> $O/bench.err
-python3 bench.py --config cfg5 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
+python3 bench.py --config cfg5 --full --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
 tail -n 12 $O/cfg3_pmc_traffic.txt; tail -c 300 $O/bench.json

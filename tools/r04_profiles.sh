@@ -26,6 +26,6 @@ for c in cfg3 cfg3_tile2 cfg3_tile4 cfg3_tile8; do echo "== $c"; python3 tools/p
 for c in cfg2 cfg3 cfg3_tile8 cfg3_tile4 cfg3_tile2 cfg3_kc8 cfg3_kc16; do python3 tools/kernel_times.py $c 2> /dev/null; done > $O/config_sweep.txt
 python3 tools/online_time.py 16 32 64 > $O/online_time.txt 2> /dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/online_stats -- python3 tools/online_time.py 64 > $O/online_stats.log 2>&1 && cp $O/online_stats/*/*kernel_stats.csv $O/online_kernel_stats.csv; rm -rf $O/online_stats
-python3 bench.py > $O/bench.json 2> $O/bench.err
-python3 bench.py --config cfg5 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
+python3 bench.py --config cfg5 --full --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
 tail -n 12 $O/cfg3_pmc_traffic.txt; tail -c 300 $O/bench.json
