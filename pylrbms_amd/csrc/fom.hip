@@ -454,7 +454,7 @@ struct FomCg {
     ppap = prr + nblk;   // [nmv]
     r0 = ppap + nmv;
     c0 = r0 + S;
-    r0w = c0 + 3 * S;             // [nmv] residual sums per wave of the update kernel
+    r0w = c0 + S;                 // [nmv] residual sums per wave of the update kernel (ends at fom_solve_work_size - 16)
     wps = t.nT % 64 == 0 ? t.nT / 64 : 0;
   }
 };

@@ -2649,7 +2649,7 @@ __global__ __launch_bounds__(64) void k3f_block_inverse(T3 t, const double* __re
 }
 
 // scal: [0], [1] r.z of the last two updates (alternating)  [2] pAp  [3] rr  [4] bb
-// p = z + beta p  (beta = rz_new / rz_old, 0 in the first iteration)
+// p = z + beta p  (beta = rz_new / rz_old; p = z in the first iteration)
 //   with the coarse level: z + R0^T y0 in the place of z (y0 [S][nc], Phi [n][4])
 __global__ __launch_bounds__(256) void k3f_dir(long total, int first, int cur, const double* __restrict__ scal,
                                                const double* __restrict__ z, double* __restrict__ p, int n, int nc,
@@ -2663,7 +2663,7 @@ __global__ __launch_bounds__(256) void k3f_dir(long total, int first, int cur, c
     const int dof = (int)(i - s * n);
     for (int k = 0; k < nc; ++k) zi += Phi[dof * 4 + k] * y0[s * nc + k];
   }
-  p[i] = zi + beta * p[i];
+  p[i] = first ? zi : zi + beta * p[i];              // the first direction does not read p: work is uninitialised there
 }
 
 // y = Amu p on the block-ELL + coupling data; partial p.y per workgroup.
