@@ -45,7 +45,7 @@ def fused_assembly(force=False):
     objdir = os.path.join(CSRC, '_obj')
     os.makedirs(objdir, exist_ok=True)
     out = os.path.join(objdir, 'fused.s')
-    deps = [os.path.join(CSRC, 'fused.hip'), os.path.join(CSRC, 'lrbms_dev.h'), os.path.join(HERE, '..', 'include', 'lrbms_hip.h')]
+    deps = [os.path.join(CSRC, f) for f in ('fused.hip', 'lrbms_dev.h', 'lrbms_ctx_base.h')] + [os.path.join(HERE, '..', 'include', 'lrbms_hip.h')]
     if force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         cmd = [_hipcc()] + [f for f in FLAGS if f != '-fPIC'] + ['-S', '--cuda-device-only', os.path.join(CSRC, 'fused.hip'), '-o', out]
         r = subprocess.run(cmd, capture_output=True, text=True)

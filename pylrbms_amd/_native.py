@@ -140,32 +140,38 @@ def _dblp(a):
     return a.ctypes.data_as(_P_DBL)
 
 
-class NativeContext:
-    """One lrbms_ctx per (process, device).  Tensor arguments must be contiguous float64 CUDA tensors on that device;
-    shapes are checked here, on the host, before any kernel may dereference them."""
+class ContextBase:
+    """What the 2D and the 3D contexts share: the C context behind ``handle``, its error reporting, tensor checks, options and
+    kernel timing.  A subclass names its symbol prefix (``PREFIX``: ``lrbms_`` / ``lrbms3_``), its option table and its loader."""
+
+    PREFIX = None                       # 'lrbms_' / 'lrbms3_'
+    OPTIONS = {}                        # name -> LRBMS_OPT_* / LRBMS3_OPT_* of the C header
+    TIMING_CAP = None                   # kernel_timing_read: timed kernels returned per read
+    _load = None                        # staticmethod: the loader that binds the C symbols of the subclass
 
     def __init__(self, device_index=0):
         import torch
         self.torch = torch
         if not torch.cuda.is_available():
             raise NativeError('no HIP device visible: the LRBMS hot path has no CPU fallback')
-        self.lib = load_library()
+        self.lib = self._load()
         self.device = torch.device('cuda', device_index)
         handle = c_vp()
-        rc = self.lib.lrbms_ctx_create(device_index, ctypes.byref(handle))
+        rc = self._fn('ctx_create')(device_index, ctypes.byref(handle))
         if rc != 0:
-            raise NativeError('lrbms_ctx_create failed with code {}'.format(rc))
+            raise NativeError('{}ctx_create failed with code {}'.format(self.PREFIX, rc))
         self.handle = handle
         self._pid = os.getpid()
-        self._keep = None
-        self.S = self.S_ext = None
+
+    def _fn(self, name):
+        return getattr(self.lib, self.PREFIX + name)
 
     def close(self):
         if getattr(self, 'handle', None):
             # a fork()ed child (e.g. a multiprocessing manager started after the GPU was initialised) inherits this
             # object but not the device context behind it: freeing the parent's allocations from there aborts the process
             if getattr(self, '_pid', None) == os.getpid():
-                self.lib.lrbms_ctx_destroy(self.handle)
+                self._fn('ctx_destroy')(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -177,7 +183,7 @@ class NativeContext:
     # ------------------------------------------------------------------ helpers
     def _check(self, rc, what):
         if rc != 0:
-            msg = self.lib.lrbms_last_error(self.handle)
+            msg = self._fn('last_error')(self.handle)
             raise NativeError('{} failed ({}): {}'.format(what, rc, msg.decode() if msg else ''))
 
     def _stream(self):
@@ -201,6 +207,43 @@ class NativeContext:
 
     def from_numpy(self, a):
         return self.torch.from_numpy(np.array(a, dtype=np.float64, order='C', copy=True)).to(self.device)
+
+    def set_option(self, name, value):
+        """Set one entry of ``OPTIONS``: a convention the reference tree leaves open or the launch policy of the library
+        (LRBMS_OPT_* / LRBMS3_OPT_* of the C headers); the library reads no environment variable."""
+        if name not in self.OPTIONS:
+            raise NativeError('unknown option {!r}; known: {}'.format(name, sorted(self.OPTIONS)))
+        self._check(self._fn('ctx_set_option')(self.handle, self.OPTIONS[name], int(value)), self.PREFIX + 'ctx_set_option')
+
+    def kernel_timing(self, enable):
+        """Bracket every kernel of the pass by HIP events on its own stream (measurement only)."""
+        self._check(self._fn('kernel_timing')(self.handle, 1 if enable else 0), self.PREFIX + 'kernel_timing')
+
+    def kernel_timing_read(self, cap=None):
+        """[(kernel name, milliseconds)] of the passes since the last read, at most ``cap`` of them (synchronises the device)."""
+        cap = self.TIMING_CAP if cap is None else int(cap)
+        names = ctypes.create_string_buffer(64 * cap)
+        ms = (c_dbl * cap)()
+        count = c_i32(0)
+        self._check(self._fn('kernel_timing_read')(self.handle, names, 64 * cap, ms, cap, ctypes.byref(count)),
+                    self.PREFIX + 'kernel_timing_read')
+        nm = names.value.decode().split('\n') if count.value else []
+        return [(nm[i], ms[i]) for i in range(count.value)]
+
+
+class NativeContext(ContextBase):
+    """One lrbms_ctx per (process, device).  Tensor arguments must be contiguous float64 CUDA tensors on that device;
+    shapes are checked here, on the host, before any kernel may dereference them."""
+
+    PREFIX = 'lrbms_'
+    TIMING_CAP = 256
+    _load = staticmethod(load_library)
+    OPTIONS = {'oswald_zero_on_subdomain_boundary': 1, 'accumulate_coupling_across_q': 2, 'oswald_vertex_patch': 9, 'prep_lds': 10,
+               # launch policy (no numerical convention): the library reads no environment variable
+               'streams': 3, 'f1_ksplit': 4, 'f1_form': 5, 'coarse': 6, 'solve_valu': 7, 'estimate_valu': 8,
+               'f2_form': 11}
+    S = S_ext = None
+    _keep = None
 
     # ------------------------------------------------------------------ mesh
     def mesh_upload(self, template, kappa, nbr, S, S_ext):
@@ -533,18 +576,6 @@ class NativeContext:
                                                 c_vp(pc.data_ptr()) if pc is not None else None)
         self._check(rc, 'lrbms_reduced_precond_use')
 
-    OPTIONS = {'oswald_zero_on_subdomain_boundary': 1, 'accumulate_coupling_across_q': 2, 'oswald_vertex_patch': 9, 'prep_lds': 10,
-               # launch policy (no numerical convention): the library reads no environment variable
-               'streams': 3, 'f1_ksplit': 4, 'f1_form': 5, 'coarse': 6, 'solve_valu': 7, 'estimate_valu': 8,
-               'f2_form': 11}
-
-    def set_option(self, name, value):
-        """Switch one of the conventions the reference tree leaves open, or the launch policy of the library
-        (include/lrbms_hip.h, LRBMS_OPT_*)."""
-        if name not in self.OPTIONS:
-            raise NativeError('unknown option {!r}; known: {}'.format(name, sorted(self.OPTIONS)))
-        self._check(self.lib.lrbms_ctx_set_option(self.handle, self.OPTIONS[name], int(value)), 'lrbms_ctx_set_option')
-
     def set_diagonal_neighbours(self, nbr_diag):
         """[S, 4] int32: index into the S_ext slabs of the diagonal neighbour at corner SW, SE, NW, NE of every local subdomain
         (or -1) -- read by the Oswald vertex patch (include/lrbms_hip.h: lrbms_set_diagonal_neighbours)."""
@@ -563,20 +594,6 @@ class NativeContext:
     def fused_mfma_per_subdomain(self, Q, N):
         """fp64 MFMA instructions the dense projection kernel executes per subdomain (bench.py's roofline)."""
         return int(self.lib.lrbms_fused_mfma_per_subdomain(self.handle, int(Q), int(N)))
-
-    def kernel_timing(self, enable):
-        """Bracket every kernel of the fused pass by HIP events on its own stream (measurement only)."""
-        self._check(self.lib.lrbms_kernel_timing(self.handle, 1 if enable else 0), 'lrbms_kernel_timing')
-
-    def kernel_timing_read(self):
-        """[(kernel name, milliseconds)] of the fused passes since the last read (synchronises the device)."""
-        cap = 256
-        names = ctypes.create_string_buffer(8192)
-        ms = (ctypes.c_double * cap)()
-        count = c_i32(0)
-        self._check(self.lib.lrbms_kernel_timing_read(self.handle, names, 8192, ms, cap, ctypes.byref(count)), 'lrbms_kernel_timing_read')
-        nm = names.value.decode().split('\n') if count.value else []
-        return [(nm[i], ms[i]) for i in range(count.value)]
 
     def aux_stream(self, i=0):
         """The i-th library-owned stream as a ``torch.cuda.ExternalStream`` (cached)."""

@@ -78,69 +78,13 @@ def load_library(path=None):
     return lib
 
 
-class Native3DContext:
+class Native3DContext(_native.ContextBase):
     """One lrbms3_ctx per (process, device); tensors are contiguous float64 CUDA tensors, shapes checked on the host."""
 
-    def __init__(self, device_index=0):
-        import os
-        import torch
-        self.torch = torch
-        if not torch.cuda.is_available():
-            raise NativeError('no HIP device visible: the LRBMS hot path has no CPU fallback')
-        self.lib = load_library()
-        self.device = torch.device('cuda', device_index)
-        handle = c_vp()
-        if self.lib.lrbms3_ctx_create(device_index, ctypes.byref(handle)) != 0:
-            raise NativeError('lrbms3_ctx_create failed')
-        self.handle, self._pid = handle, os.getpid()
-
-    def close(self):
-        import os
-        if getattr(self, 'handle', None):
-            if self._pid == os.getpid():
-                self.lib.lrbms3_ctx_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            msg = self.lib.lrbms3_last_error(self.handle)
-            raise NativeError('{} failed ({}): {}'.format(what, rc, msg.decode() if msg else ''))
-
-    def _stream(self):
-        return c_vp(self.torch.cuda.current_stream(self.device).cuda_stream)
-
+    PREFIX = 'lrbms3_'
+    TIMING_CAP = 4096
+    _load = staticmethod(load_library)
     OPTIONS = {'ksplit': 1, 'serial': 2, 'waves': 3, 'estimate_valu': 4, 'solve_valu': 5, 'fom_coarse': 6}
-
-    def set_option(self, name, value):
-        """Launch policy of the library (include/lrbms3d_hip.h, LRBMS3_OPT_*); the library reads no environment variable."""
-        if name not in self.OPTIONS:
-            raise NativeError('unknown option {!r} (known: {})'.format(name, sorted(self.OPTIONS)))
-        self._check(self.lib.lrbms3_ctx_set_option(self.handle, self.OPTIONS[name], int(value)), 'lrbms3_ctx_set_option')
-
-    def _ptr(self, t, shape, name):
-        torch = self.torch
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self.device:
-            raise NativeError('{}: expected a float64 tensor on {}'.format(name, self.device))
-        if tuple(t.shape) != tuple(shape):
-            raise NativeError('{}: expected shape {}, got {}'.format(name, tuple(shape), tuple(t.shape)))
-        if not t.is_contiguous():
-            raise NativeError('{}: tensor must be contiguous'.format(name))
-        return c_vp(t.data_ptr())
-
-    def empty(self, *shape):
-        return self.torch.empty(*shape, dtype=self.torch.float64, device=self.device)
-
-    def zeros(self, *shape):
-        return self.torch.zeros(*shape, dtype=self.torch.float64, device=self.device)
-
-    def from_numpy(self, a):
-        return self.torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.device)
 
     # ------------------------------------------------------------------ mesh
     def mesh_upload(self, template, spec, tables, nbr, phys, S, S_ext):
@@ -277,18 +221,6 @@ class Native3DContext:
         rc = self.lib.lrbms3_project_estimate_phase(self.handle, int(phase), Q, N, *args, self._stream())
         self._check(rc, 'lrbms3_project_estimate_phase')
         return out
-
-    def kernel_timing(self, enable):
-        self._check(self.lib.lrbms3_kernel_timing(self.handle, int(bool(enable))), 'lrbms3_kernel_timing')
-
-    def kernel_timing_read(self, cap=4096):
-        names = ctypes.create_string_buffer(64 * cap)
-        ms = (c_dbl * cap)()
-        count = c_i32(0)
-        self._check(self.lib.lrbms3_kernel_timing_read(self.handle, names, 64 * cap, ms, cap, ctypes.byref(count)),
-                    'lrbms3_kernel_timing_read')
-        nm = names.value.decode().split('\n')[:count.value]
-        return list(zip(nm, [ms[i] for i in range(count.value)]))
 
     # ------------------------------------------------------------------ online
     def reduced_estimate(self, Q, theta, u, out, ops, hdiam):

@@ -68,17 +68,6 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
 
 namespace {
 
-template <typename T>
-int upload(lrbms_ctx* ctx, const T* host, size_t count, const T** dev) {
-  if (!host) return lrbms_fail(ctx, LRBMS_E_INVALID, "mesh_upload: null template array");
-  void* p = nullptr;
-  LRBMS_HIP_CHECK(ctx, hipMalloc(&p, sizeof(T) * (count ? count : 1)));
-  ctx->owned.push_back(p);
-  LRBMS_HIP_CHECK(ctx, hipMemcpy(p, host, sizeof(T) * count, hipMemcpyHostToDevice));
-  *dev = static_cast<const T*>(p);
-  return LRBMS_OK;
-}
-
 void free_owned(lrbms_ctx* ctx) {
   for (void* p : ctx->owned) (void)hipFree(p);
   ctx->owned.clear();
@@ -89,7 +78,7 @@ void free_owned(lrbms_ctx* ctx) {
 
 }  // namespace
 
-// ---- the process-wide side streams (lrbms_dev.h)
+// ---- the process-wide side streams and the rest of lrbms_ctx_base.h
 namespace {
 struct SideStream { hipStream_t s = nullptr; int users = 0; };
 std::mutex side_mutex;
@@ -125,6 +114,57 @@ void lrbms_side_stream_release(int device, int i) {
   }
 }
 
+int lrbms_ctx_base_init(lrbms_ctx_base* ctx, int device) {
+  ctx->device = device;
+  bool ok = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) == hipSuccess;
+  for (int i = 0; i < 3 && ok; ++i)
+    ok = (ctx->aux[i] = lrbms_side_stream_acquire(device, i)) != nullptr &&
+         hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming) == hipSuccess;
+  return ok ? LRBMS_OK : LRBMS_E_HIP;
+}
+
+void lrbms_ctx_base_release(lrbms_ctx_base* ctx) {
+  for (int i = 0; i < 3; ++i) {
+    if (ctx->aux[i]) lrbms_side_stream_release(ctx->device, i);
+    if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]);
+  }
+  if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
+  for (auto& k : ctx->ktimers) {
+    if (k.e0) (void)hipEventDestroy(k.e0);
+    if (k.e1) (void)hipEventDestroy(k.e1);
+  }
+}
+
+int lrbms_ctx_kernel_timing(lrbms_ctx_base* ctx, int32_t enable) {
+  if (!ctx) return LRBMS_E_INVALID;
+  ctx->ktime = enable != 0;
+  ctx->ktime_n = 0;
+  for (auto& k : ctx->ktimers) k.used = false;
+  return LRBMS_OK;
+}
+
+int lrbms_ctx_kernel_timing_read(lrbms_ctx_base* ctx, char* names, int64_t names_cap, double* ms, int32_t cap, int32_t* count) {
+  if (!ctx || !names || !ms || !count || names_cap <= 0) return LRBMS_E_INVALID;
+  LRBMS_HIP_CHECK(ctx, hipDeviceSynchronize());
+  int n = 0;
+  std::string joined;
+  for (int i = 0; i < ctx->ktime_n && n < cap; ++i) {
+    const auto& k = ctx->ktimers[i];
+    if (!k.used) continue;
+    float t = 0.f;
+    LRBMS_HIP_CHECK(ctx, hipEventElapsedTime(&t, k.e0, k.e1));
+    ms[n++] = (double)t;
+    if (!joined.empty()) joined += '\n';
+    joined += k.name;
+  }
+  if ((int64_t)joined.size() + 1 > names_cap) return lrbms_fail(ctx, LRBMS_E_INVALID, "kernel_timing_read: names buffer too small");
+  memcpy(names, joined.c_str(), joined.size() + 1);
+  *count = n;
+  ctx->ktime_n = 0;          // the next pass records afresh
+  for (auto& k : ctx->ktimers) k.used = false;
+  return LRBMS_OK;
+}
+
 extern "C" {
 
 const char* lrbms_version(void) { return "lrbms_hip 0.1.0 (gfx950)"; }
@@ -137,13 +177,8 @@ int lrbms_ctx_create(int device, lrbms_ctx** out) {
   if (hipSetDevice(device) != hipSuccess) return LRBMS_E_HIP;
   lrbms_ctx* ctx = new (std::nothrow) lrbms_ctx();
   if (!ctx) return LRBMS_E_INVALID;
-  ctx->device = device;
-  bool ok = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming) == hipSuccess;
-  for (int i = 0; i < 3 && ok; ++i)
-    ok = (ctx->aux[i] = lrbms_side_stream_acquire(device, i)) != nullptr &&
-         hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming) == hipSuccess;
-  if (!ok) return lrbms_ctx_destroy(ctx), LRBMS_E_HIP;     // gives back what was acquired
+  if (lrbms_ctx_base_init(ctx, device) != LRBMS_OK || hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming) != hipSuccess)
+    return lrbms_ctx_destroy(ctx), LRBMS_E_HIP;     // gives back what was acquired
   *out = ctx;
   return LRBMS_OK;
 }
@@ -158,16 +193,8 @@ int lrbms_ctx_destroy(lrbms_ctx* ctx) {
   if (ctx->subset) (void)hipFree(ctx->subset);
   if (ctx->wab) (void)hipFree(ctx->wab);
   if (ctx->src_phi) (void)hipFree(ctx->src_phi);
-  for (int i = 0; i < 3; ++i) {
-    if (ctx->aux[i]) lrbms_side_stream_release(ctx->device, i);
-    if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]);
-  }
-  if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
+  lrbms_ctx_base_release(ctx);
   if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
-  for (auto& k : ctx->ktimers) {
-    if (k.e0) (void)hipEventDestroy(k.e0);
-    if (k.e1) (void)hipEventDestroy(k.e1);
-  }
   delete ctx;
   return LRBMS_OK;
 }
@@ -243,34 +270,10 @@ int lrbms_fused_set_subset(lrbms_ctx* ctx, const int32_t* subset, int32_t count)
   return LRBMS_OK;
 }
 
-int lrbms_kernel_timing(lrbms_ctx* ctx, int32_t enable) {
-  if (!ctx) return LRBMS_E_INVALID;
-  ctx->ktime = enable != 0;
-  ctx->ktime_n = 0;
-  for (auto& k : ctx->ktimers) k.used = false;
-  return LRBMS_OK;
-}
+int lrbms_kernel_timing(lrbms_ctx* ctx, int32_t enable) { return lrbms_ctx_kernel_timing(ctx, enable); }
 
 int lrbms_kernel_timing_read(lrbms_ctx* ctx, char* names, int64_t names_cap, double* ms, int32_t cap, int32_t* count) {
-  if (!ctx || !names || !ms || !count || names_cap <= 0) return LRBMS_E_INVALID;
-  LRBMS_HIP_CHECK(ctx, hipDeviceSynchronize());
-  int n = 0;
-  std::string joined;
-  for (int i = 0; i < ctx->ktime_n && n < cap; ++i) {
-    const auto& k = ctx->ktimers[i];
-    if (!k.used) continue;
-    float t = 0.f;
-    LRBMS_HIP_CHECK(ctx, hipEventElapsedTime(&t, k.e0, k.e1));
-    ms[n++] = (double)t;
-    if (!joined.empty()) joined += '\n';
-    joined += k.name;
-  }
-  if ((int64_t)joined.size() + 1 > names_cap) return lrbms_fail(ctx, LRBMS_E_INVALID, "kernel_timing_read: names buffer too small");
-  memcpy(names, joined.c_str(), joined.size() + 1);
-  *count = n;
-  ctx->ktime_n = 0;          // the next pass records afresh
-  for (auto& k : ctx->ktimers) k.used = false;
-  return LRBMS_OK;
+  return lrbms_ctx_kernel_timing_read(ctx, names, names_cap, ms, cap, count);
 }
 
 int lrbms_mesh_upload(lrbms_ctx* ctx, const lrbms_mesh_desc* d, int32_t S, int32_t S_ext, const int32_t* nbr) {
@@ -326,7 +329,11 @@ int lrbms_mesh_upload(lrbms_ctx* ctx, const lrbms_mesh_desc* d, int32_t S, int32
   const double a = t.kappa[0], b = 0.5 * (t.kappa[1] + t.kappa[2]), c = t.kappa[3];
   t.kmin = 0.5 * (a + c) - std::sqrt(0.25 * (a - c) * (a - c) + b * b);
   int rc;
-#define UP(field, count) if ((rc = upload(ctx, d->field, (size_t)(count), &t.field))) return rc
+#define UP(field, count)                                                                            \
+  do {                                                                                              \
+    if (!d->field) return lrbms_fail(ctx, LRBMS_E_INVALID, "mesh_upload: null template array");     \
+    if ((rc = upload(ctx, d->field, (long)(count), &t.field))) return rc;                           \
+  } while (0)
   UP(nb_elem, 3 * nT); UP(nb_face, 3 * nT); UP(nb_elem_out, 3 * nT); UP(nb_face_out, 3 * nT); UP(elem_side_pos, 3 * nT);
   UP(elem_rt, 3 * nT); UP(face_sign, 3 * nT); UP(dof_vertex, n); UP(vdof_ptr, d->n_vertices + 1); UP(vdof_idx, n);
   UP(rt_e0, d->n_rt); UP(rt_f0, d->n_rt); UP(rt_e1, d->n_rt); UP(rt_f1, d->n_rt); UP(rt_side, d->n_rt);
@@ -343,7 +350,7 @@ int lrbms_mesh_upload(lrbms_ctx* ctx, const lrbms_mesh_desc* d, int32_t S, int32
   UP(grad, 6 * nT); UP(area, nT); UP(normal, 6 * nT); UP(face_len, 3 * nT); UP(points, 6 * nT);
 #undef UP
   const int* nbr_dev = nullptr;
-  if ((rc = upload(ctx, nbr, (size_t)S * 5, &nbr_dev))) return rc;
+  if ((rc = upload(ctx, nbr, (long)S * 5, &nbr_dev))) return rc;
   ctx->nbr = const_cast<int*>(nbr_dev);
   ctx->nbr_host.assign(nbr, nbr + (size_t)S * 5);
   {
@@ -355,7 +362,7 @@ int lrbms_mesh_upload(lrbms_ctx* ctx, const lrbms_mesh_desc* d, int32_t S, int32
         if (sa >= 0 && sa < S) dg[(size_t)i * 4 + c] = nbr[sa * 5 + ((c & 1) ? 3 : 1)];
       }
     const int* dg_dev = nullptr;
-    if ((rc = upload(ctx, dg.data(), dg.size(), &dg_dev))) return rc;
+    if ((rc = upload(ctx, dg.data(), (long)dg.size(), &dg_dev))) return rc;
     t.nbr_diag = dg_dev;
     ctx->diag_explicit = false;
   }

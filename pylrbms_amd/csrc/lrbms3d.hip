@@ -20,10 +20,7 @@
 #include <rocsolver/rocsolver.h>
 
 #include "../../include/lrbms3d_hip.h"
-
-// the process-wide side streams (capi.hip; see lrbms_dev.h): shared with the 2D contexts so that all of them fit the hardware queues
-hipStream_t lrbms_side_stream_acquire(int device, int i);
-void lrbms_side_stream_release(int device, int i);
+#include "lrbms_ctx_base.h"
 
 namespace {
 
@@ -46,11 +43,8 @@ struct T3 {
 
 }  // namespace
 
-struct lrbms3_ctx {
-  int device = 0;
-  bool has_mesh = false;
+struct lrbms3_ctx : lrbms_ctx_base {
   T3 t{};
-  std::vector<void*> owned;
   std::vector<int32_t> nbr_host;
   // coarse space of the full-order solver (lrbms3_fom_coarse_space): nc functions per subdomain, values at the local DoFs
   int fom_nc = 0;
@@ -62,9 +56,6 @@ struct lrbms3_ctx {
   void* blas = nullptr;           // rocBLAS handle (dense coarse inverses), created on first use
   const double* user_pc = nullptr;   // coarse inverse the batched reduced solve uses (lrbms3_reduced_precond_use), caller-owned
   int user_pc_N = 0;
-  hipStream_t aux[3] = {nullptr, nullptr, nullptr}; // library-owned streams: the flux chain and the Oswald chain of the pass; the
-                                                    // groups of the batched reduced solve (all three)
-  hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   double* thbar = nullptr;         // [8] device: theta(mu_bar) of lrbms3_assemble_energy_product
   double* tm_inv = nullptr;        // [6][100] device (owned): inverses of the element mass tables (parabolic path, first use)
   const double* tm_inv_src = nullptr;   // the TM table they were taken from (a new mesh upload invalidates them)
@@ -73,51 +64,9 @@ struct lrbms3_ctx {
   // launch policy (lrbms3_ctx_set_option): the library reads no environment variable
   int opt_ksplit = 0, opt_serial = 0, opt_waves = 0, opt_estimate_valu = 0, opt_solve_valu = 0, opt_fom_coarse = 1;
   bool side_padding = false;       // some side has fewer faces than ncf (unequal cubes per direction): padded factor rows exist
-  bool ktime = false;
-  struct KTimer { const char* name; hipEvent_t e0, e1; };
-  std::vector<KTimer> ktimers;
-  int ktime_n = 0;
-  std::string err;
 };
 
 namespace {
-
-int fail3(lrbms3_ctx* ctx, int code, const std::string& msg) {
-  if (ctx) ctx->err = msg;
-  return code;
-}
-
-#define HIP3(ctx, expr)                                                                        \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) return fail3(ctx, LRBMS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-#define REQUIRE3(ctx)                                                                \
-  do {                                                                               \
-    if (!(ctx)) return LRBMS_E_INVALID;                                              \
-    if (!(ctx)->has_mesh) return fail3(ctx, LRBMS_E_STATE, "mesh not uploaded");     \
-  } while (0)
-#define LAUNCH3(ctx) HIP3(ctx, hipGetLastError())
-
-struct KScope3 {
-  lrbms3_ctx* ctx;
-  hipStream_t st;
-  int idx;
-  KScope3(lrbms3_ctx* c, const char* name, hipStream_t s) : ctx(c), st(s), idx(-1) {
-    if (!c->ktime) return;
-    if (c->ktime_n == (int)c->ktimers.size()) {
-      lrbms3_ctx::KTimer k{name, nullptr, nullptr};
-      if (hipEventCreate(&k.e0) != hipSuccess || hipEventCreate(&k.e1) != hipSuccess) return;
-      c->ktimers.push_back(k);
-    }
-    idx = c->ktime_n++;
-    c->ktimers[idx].name = name;
-    (void)hipEventRecord(c->ktimers[idx].e0, st);
-  }
-  ~KScope3() {
-    if (idx >= 0) (void)hipEventRecord(ctx->ktimers[idx].e1, st);
-  }
-};
 
 __device__ inline int side_slot(int side) { return side < 3 ? side : side + 1; }
 
@@ -2920,17 +2869,6 @@ __global__ __launch_bounds__(256) void k3f_coarse_apply(int M, const double* __r
 }
 
 
-template <typename T>
-int upload(lrbms3_ctx* ctx, const T* host, long count, const T** dev) {
-  void* p = nullptr;
-  if (count <= 0) count = 1;
-  HIP3(ctx, hipMalloc(&p, sizeof(T) * count));
-  ctx->owned.push_back(p);
-  if (host) HIP3(ctx, hipMemcpy(p, host, sizeof(T) * count, hipMemcpyHostToDevice));
-  *dev = (const T*)p;
-  return LRBMS_OK;
-}
-
 QV make_theta(int Q, const double* theta) {
   QV th{};
   for (int q = 0; q < Q && q < 8; ++q) th.v[q] = theta[q];
@@ -2947,12 +2885,7 @@ int lrbms3_ctx_create(int device, lrbms3_ctx** out) {
   if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return LRBMS_E_HIP;
   if (hipSetDevice(device) != hipSuccess) return LRBMS_E_HIP;
   lrbms3_ctx* c = new lrbms3_ctx();
-  c->device = device;
-  for (int i = 0; i < 3; ++i)
-    if ((c->aux[i] = lrbms_side_stream_acquire(device, i)) == nullptr ||
-        hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming) != hipSuccess)
-      return lrbms3_ctx_destroy(c), LRBMS_E_HIP;
-  if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess) return lrbms3_ctx_destroy(c), LRBMS_E_HIP;
+  if (lrbms_ctx_base_init(c, device) != LRBMS_OK) return lrbms3_ctx_destroy(c), LRBMS_E_HIP;
   *out = c;
   return LRBMS_OK;
 }
@@ -2964,15 +2897,7 @@ int lrbms3_ctx_destroy(lrbms3_ctx* ctx) {
   if (ctx->pg_part) (void)hipFree(ctx->pg_part);
   if (ctx->blas) (void)rocblas_destroy_handle((rocblas_handle)ctx->blas);
   if (ctx->fom_pc) (void)hipFree(ctx->fom_pc);
-  for (int i = 0; i < 3; ++i) {
-    if (ctx->aux[i]) lrbms_side_stream_release(ctx->device, i);
-    if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]);
-  }
-  if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-  for (auto& k : ctx->ktimers) {
-    (void)hipEventDestroy(k.e0);
-    (void)hipEventDestroy(k.e1);
-  }
+  lrbms_ctx_base_release(ctx);
   delete ctx;
   return LRBMS_OK;
 }
@@ -2984,7 +2909,7 @@ int lrbms3_ctx_set_option(lrbms3_ctx* ctx, int32_t option, int32_t value) {
   int hi = 1;
   if (option == LRBMS3_OPT_KSPLIT) hi = 8;
   if (option == LRBMS3_OPT_WAVES) hi = 16;
-  if (value < 0 || value > hi) return fail3(ctx, LRBMS_E_INVALID, "set_option: value out of range for this option");
+  if (value < 0 || value > hi) return lrbms_fail(ctx, LRBMS_E_INVALID, "set_option: value out of range for this option");
   switch (option) {
     case LRBMS3_OPT_KSPLIT: ctx->opt_ksplit = value; break;
     case LRBMS3_OPT_SERIAL: ctx->opt_serial = value; break;
@@ -2992,7 +2917,7 @@ int lrbms3_ctx_set_option(lrbms3_ctx* ctx, int32_t option, int32_t value) {
     case LRBMS3_OPT_ESTIMATE_VALU: ctx->opt_estimate_valu = value; break;
     case LRBMS3_OPT_SOLVE_VALU: ctx->opt_solve_valu = value; break;
     case LRBMS3_OPT_FOM_COARSE: ctx->opt_fom_coarse = value; break;
-    default: return fail3(ctx, LRBMS_E_INVALID, "set_option: unknown option");
+    default: return lrbms_fail(ctx, LRBMS_E_INVALID, "set_option: unknown option");
   }
   return LRBMS_OK;
 }
@@ -3000,14 +2925,14 @@ int lrbms3_ctx_set_option(lrbms3_ctx* ctx, int32_t option, int32_t value) {
 int lrbms3_mesh_upload(lrbms3_ctx* ctx, const lrbms3_mesh_desc* d, int32_t S, int32_t S_ext, const int32_t* nbr,
                        const int32_t* phys) {
   if (!ctx || !d || !nbr || !phys) return LRBMS_E_INVALID;
-  if (ctx->has_mesh) return fail3(ctx, LRBMS_E_STATE, "mesh already uploaded (one template per context)");
-  if (S <= 0 || S_ext < S || d->n_T <= 0 || d->ncf <= 0) return fail3(ctx, LRBMS_E_INVALID, "bad sizes");
+  if (ctx->has_mesh) return lrbms_fail(ctx, LRBMS_E_STATE, "mesh already uploaded (one template per context)");
+  if (S <= 0 || S_ext < S || d->n_T <= 0 || d->ncf <= 0) return lrbms_fail(ctx, LRBMS_E_INVALID, "bad sizes");
   for (int s = 0; s < S; ++s) {
-    if (nbr[s * 7 + 3] != s) return fail3(ctx, LRBMS_E_INVALID, "nbr[s][3] must be s");
+    if (nbr[s * 7 + 3] != s) return lrbms_fail(ctx, LRBMS_E_INVALID, "nbr[s][3] must be s");
     for (int k = 0; k < 7; ++k)
-      if (nbr[s * 7 + k] < -1 || nbr[s * 7 + k] >= S_ext) return fail3(ctx, LRBMS_E_INVALID, "nbr entry out of range");
+      if (nbr[s * 7 + k] < -1 || nbr[s * 7 + k] >= S_ext) return lrbms_fail(ctx, LRBMS_E_INVALID, "nbr entry out of range");
   }
-  HIP3(ctx, hipSetDevice(ctx->device));
+  LRBMS_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   T3& t = ctx->t;
   t.S = S; t.S_ext = S_ext;
   t.nT = d->n_T; t.n = 10 * d->n_T; t.nrt = d->n_rt; t.ncf = d->ncf; t.nbf = 6 * d->ncf; t.nvs = d->nvs;
@@ -3069,13 +2994,13 @@ int lrbms3_mesh_upload(lrbms3_ctx* ctx, const lrbms3_mesh_desc* d, int32_t S, in
 }
 
 int lrbms3_assemble_system(lrbms3_ctx* ctx, int32_t Q, const double* lam, double* A_diag, double* A_cpl, void* stream) {
-  REQUIRE3(ctx);
-  if (Q < 1 || Q > 8 || !lam || !A_diag || !A_cpl) return fail3(ctx, LRBMS_E_INVALID, "assemble_system: bad argument");
+  LRBMS_REQUIRE_MESH(ctx);
+  if (Q < 1 || Q > 8 || !lam || !A_diag || !A_cpl) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_system: bad argument");
   const T3& t = ctx->t;
-  if (t.nT % 6) return fail3(ctx, LRBMS_E_INVALID, "assemble_system: template is not made of whole cubes");
+  if (t.nT % 6) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_system: template is not made of whole cubes");
   const dim3 grid(6 * ((t.nT / 6 + 63) / 64), t.S);
   // sides with fewer faces than the padded row length (unequal cubes per direction) leave positions no kernel writes: zero
-  HIP3(ctx, hipMemsetAsync(A_cpl, 0, sizeof(double) * (size_t)Q * t.S * 6 * t.ncf * 100, (hipStream_t)stream));
+  LRBMS_HIP_CHECK(ctx, hipMemsetAsync(A_cpl, 0, sizeof(double) * (size_t)Q * t.S * 6 * t.ncf * 100, (hipStream_t)stream));
   for (int q = 0; q < Q; ++q) {
     hipLaunchKernelGGL((k3_asm<6, 7>), grid, dim3(256), 0, (hipStream_t)stream, t, Q, q, 0, lam, (const double*)nullptr,
                        (const double*)nullptr, A_diag, (double*)nullptr);
@@ -3083,31 +3008,31 @@ int lrbms3_assemble_system(lrbms3_ctx* ctx, int32_t Q, const double* lam, double
       hipLaunchKernelGGL((k3_asm<7, 7>), grid, dim3(256), 0, (hipStream_t)stream, t, Q, q, f, lam, (const double*)nullptr,
                          (const double*)nullptr, A_diag, A_cpl);
   }
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
 int lrbms3_assemble_rhs(lrbms3_ctx* ctx, const double* f_smp, const double* lhat, double* b, double* f2, double* ceps,
                         double* bdiv, void* stream) {
-  REQUIRE3(ctx);
-  if (!f_smp || !lhat || !b || !f2 || !ceps || !bdiv) return fail3(ctx, LRBMS_E_INVALID, "assemble_rhs: null argument");
+  LRBMS_REQUIRE_MESH(ctx);
+  if (!f_smp || !lhat || !b || !f2 || !ceps || !bdiv) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_rhs: null argument");
   const T3& t = ctx->t;
-  if (t.nT % 6) return fail3(ctx, LRBMS_E_INVALID, "assemble_rhs: template is not made of whole cubes");
+  if (t.nT % 6) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_rhs: template is not made of whole cubes");
   const dim3 grid(6 * ((t.nT / 6 + 63) / 64), t.S);
   hipLaunchKernelGGL((k3_asm<4, 1>), grid, dim3(256), 0, (hipStream_t)stream, t, 1, 0, 0, f_smp, f_smp, lhat, b, (double*)nullptr);
   hipLaunchKernelGGL((k3_asm<5, 1>), grid, dim3(256), 0, (hipStream_t)stream, t, 1, 0, 0, f_smp, f_smp, lhat, bdiv, (double*)nullptr);
   hipLaunchKernelGGL(k3_scalars, dim3(t.S), dim3(256), 0, (hipStream_t)stream, t, f_smp, lhat, f2, ceps);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
 int lrbms3_assemble_products(lrbms3_ctx* ctx, int32_t Q, const double* lam, const double* lbar, const double* lhat, double* ebar,
                              double* Aaa, double* Aab, double* Bbb, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   if (Q < 1 || Q > 8 || !lam || !lbar || !lhat || !ebar || !Aaa || !Aab || !Bbb)
-    return fail3(ctx, LRBMS_E_INVALID, "assemble_products: bad argument");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_products: bad argument");
   const T3& t = ctx->t;
-  if (t.nT % 6) return fail3(ctx, LRBMS_E_INVALID, "assemble_products: template is not made of whole cubes");
+  if (t.nT % 6) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_products: template is not made of whole cubes");
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(6 * ((t.nT / 6 + 63) / 64), t.S);
   hipLaunchKernelGGL((k3_asm<0, 7>), grid, dim3(256), 0, st, t, Q, 0, 0, lam, lbar, lhat, ebar, (double*)nullptr);
@@ -3120,51 +3045,51 @@ int lrbms3_assemble_products(lrbms3_ctx* ctx, int32_t Q, const double* lam, cons
     hipLaunchKernelGGL((k3_asm<2, 3>), grid, dim3(256), 0, st, t, Q, q, q, lam, lbar, lhat, Aab + (long)q * t.S * t.nT * 40,
                        (double*)nullptr);
   hipLaunchKernelGGL((k3_asm<3, 1>), grid, dim3(256), 0, st, t, Q, 0, 0, lam, lbar, lhat, Bbb, (double*)nullptr);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
 int lrbms3_assemble_energy_product(lrbms3_ctx* ctx, int32_t Q, const double* theta_bar, const double* lam, double* P_diag,
                                    void* stream) {
-  REQUIRE3(ctx);
-  if (Q < 1 || Q > 8 || !theta_bar || !lam || !P_diag) return fail3(ctx, LRBMS_E_INVALID, "assemble_energy_product: bad argument");
+  LRBMS_REQUIRE_MESH(ctx);
+  if (Q < 1 || Q > 8 || !theta_bar || !lam || !P_diag) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_energy_product: bad argument");
   const T3& t = ctx->t;
-  if (t.nT % 6) return fail3(ctx, LRBMS_E_INVALID, "assemble_energy_product: template is not made of whole cubes");
+  if (t.nT % 6) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_energy_product: template is not made of whole cubes");
   hipStream_t st = (hipStream_t)stream;
   if (!ctx->thbar) {
-    HIP3(ctx, hipMalloc((void**)&ctx->thbar, sizeof(double) * 8));
+    LRBMS_HIP_CHECK(ctx, hipMalloc((void**)&ctx->thbar, sizeof(double) * 8));
     ctx->owned.push_back(ctx->thbar);
   }
   double* thb = ctx->thbar;
-  HIP3(ctx, hipMemcpyAsync(thb, theta_bar, sizeof(double) * Q, hipMemcpyHostToDevice, st));
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(thb, theta_bar, sizeof(double) * Q, hipMemcpyHostToDevice, st));
   const dim3 grid(6 * ((t.nT / 6 + 63) / 64), t.S);
   hipLaunchKernelGGL((k3_asm<8, 7>), grid, dim3(256), 0, st, t, Q, 0, 0, lam, (const double*)nullptr, (const double*)thb, P_diag,
                      (double*)nullptr);
   for (int f = 0; f < 4; ++f)
     hipLaunchKernelGGL((k3_asm<9, 7>), grid, dim3(256), 0, st, t, Q, 0, f, lam, (const double*)nullptr, (const double*)thb, P_diag,
                        (double*)nullptr);
-  LAUNCH3(ctx);
-  HIP3(ctx, hipStreamSynchronize(st));          // theta_bar is a host buffer of the caller
+  LRBMS_LAUNCH_CHECK(ctx);
+  LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));          // theta_bar is a host buffer of the caller
   return LRBMS_OK;
 }
 
 int lrbms3_energy_product_apply(lrbms3_ctx* ctx, int32_t M, const double* P_diag, const double* X, double* Y, void* stream) {
-  REQUIRE3(ctx);
-  if (M < 1 || !P_diag || !X || !Y) return fail3(ctx, LRBMS_E_INVALID, "energy_product_apply: bad argument");
+  LRBMS_REQUIRE_MESH(ctx);
+  if (M < 1 || !P_diag || !X || !Y) return lrbms_fail(ctx, LRBMS_E_INVALID, "energy_product_apply: bad argument");
   const T3& t = ctx->t;
   const double one = 1.0;
   hipLaunchKernelGGL(k3_fom_apply, dim3(t.nT, t.S), dim3(256), 0, (hipStream_t)stream, t, 1, M, make_theta(1, &one), P_diag,
                      (const double*)nullptr, X, Y);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
 int lrbms3_assemble_flux(lrbms3_ctx* ctx, int32_t Q, const double* lam, double* Cf, void* stream) {
-  REQUIRE3(ctx);
-  if (Q < 1 || Q > 8 || !lam || !Cf) return fail3(ctx, LRBMS_E_INVALID, "assemble_flux: bad argument");
+  LRBMS_REQUIRE_MESH(ctx);
+  if (Q < 1 || Q > 8 || !lam || !Cf) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_flux: bad argument");
   const T3& t = ctx->t;
   hipLaunchKernelGGL(k3_assemble_flux, dim3(t.nT, t.S_ext, Q), dim3(64), 0, (hipStream_t)stream, t, lam, Cf);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
@@ -3188,14 +3113,14 @@ int lrbms3_project_estimate_phase(lrbms3_ctx* ctx, int32_t phase, int32_t Q, int
                                   const double* Bbb, const double* bdiv, const double* Cf, double* work, double* B_sys,
                                   double* rhs_red, double* G_nc, double* G_bb, double* G_rdd, double* G_ab, double* G_aa,
                                   double* r_fd, double* Rb, double* Yb, double* Dp, double* Xab, double* As, double* Cn, void* stream) {
-  REQUIRE3(ctx);
-  if (phase < 0 || phase > 2) return fail3(ctx, LRBMS_E_INVALID, "project_estimate: phase must be 0, 1 or 2");
+  LRBMS_REQUIRE_MESH(ctx);
+  if (phase < 0 || phase > 2) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_estimate: phase must be 0, 1 or 2");
   const bool own = phase != 2, side = phase != 1;        // 1: everything that reads rank-local slabs only; 2: the rest
   if (Q < 1 || Q > 8 || N < 1 || N > 64 || Q * N > 64)
-    return fail3(ctx, LRBMS_E_INVALID, "project_estimate: needs N <= 64 and Q N <= 64");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "project_estimate: needs N <= 64 and Q N <= 64");
   if (!V || !A_diag || !A_cpl || !b || !ebar || !Aaa || !Aab || !Bbb || !bdiv || !Cf || !work || !B_sys || !rhs_red || !G_nc ||
       !G_bb || !G_rdd || !G_ab || !G_aa || !r_fd || !Rb || !Yb || !Dp || !Xab || !As || !Cn)
-    return fail3(ctx, LRBMS_E_INVALID, "project_estimate: null argument");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "project_estimate: null argument");
   const T3& t = ctx->t;
   hipStream_t st = (hipStream_t)stream;
   ctx->ktime_n = ctx->ktime ? ctx->ktime_n : 0;
@@ -3210,14 +3135,14 @@ int lrbms3_project_estimate_phase(lrbms3_ctx* ctx, int32_t phase, int32_t Q, int
   // event intervals)
   const bool serial = ctx->ktime || ctx->opt_serial != 0;      // LRBMS3_OPT_SERIAL: rocprofv3 kernel statistics of a serial pass
   hipStream_t sf = serial ? st : ctx->aux[0], sn = serial ? st : ctx->aux[1];
-  HIP3(ctx, hipEventRecord(ctx->ev_fork, st));
-  HIP3(ctx, hipStreamWaitEvent(sf, ctx->ev_fork, 0));
-  HIP3(ctx, hipStreamWaitEvent(sn, ctx->ev_fork, 0));
+  LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
+  LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(sf, ctx->ev_fork, 0));
+  LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(sn, ctx->ev_fork, 0));
   GA a{t, Q, N, V, A_diag, A_cpl, ebar, Aaa, Aab, Bbb, Rs, Avg, nullptr, Zb, G_rdd, r_fd, bdiv, b, rhs_red, Yb, Dp, Xab, 1, nullptr};
   if (own && ctx->side_padding) {      // padded side-face rows are written by no kernel: define them (the estimate multiplies them by 0)
-    HIP3(ctx, hipMemsetAsync(Yb, 0, sizeof(double) * (size_t)t.S * t.nbf * Q * N, sf));
-    HIP3(ctx, hipMemsetAsync(Dp, 0, sizeof(double) * (size_t)t.S * t.nbf * Q * N, sf));
-    HIP3(ctx, hipMemsetAsync(Xab, 0, sizeof(double) * (size_t)Q * t.S * t.nbf * N, sf));
+    LRBMS_HIP_CHECK(ctx, hipMemsetAsync(Yb, 0, sizeof(double) * (size_t)t.S * t.nbf * Q * N, sf));
+    LRBMS_HIP_CHECK(ctx, hipMemsetAsync(Dp, 0, sizeof(double) * (size_t)t.S * t.nbf * Q * N, sf));
+    LRBMS_HIP_CHECK(ctx, hipMemsetAsync(Xab, 0, sizeof(double) * (size_t)Q * t.S * t.nbf * N, sf));
   }
   const int tn = (N + 15) / 16, tq = (Q * N + 15) / 16;
   const int nw_env = ctx->opt_waves;      // LRBMS3_OPT_WAVES
@@ -3226,12 +3151,12 @@ int lrbms3_project_estimate_phase(lrbms3_ctx* ctx, int32_t phase, int32_t Q, int
   int bad = 0;
   {
     const int r0 = own ? 0 : t.nrt, r1 = side ? t.nrt + t.nbf : t.nrt;      // own faces | side faces (the neighbours' share: halo)
-    KScope3 k(ctx, own ? "k3_flux" : "k3_flux<side>", sf);
+    KScope k(ctx, own ? "k3_flux" : "k3_flux<side>", sf);
     hipLaunchKernelGGL(k3_flux, dim3(xcd_grid((r1 - r0 + 4 * FLUX_R * FLUX_LOOP - 1) / (4 * FLUX_R * FLUX_LOOP), t.S)), dim3(256), 0, sf, t, Q, N, r0, r1, V, Cf, Rs, Rb);
   }
   {
     const int r0 = own ? 0 : t.nnodes, r1 = side ? t.nnodes + 6 * t.nvs : t.nnodes;
-    KScope3 k(ctx, own ? "k3_node_avg" : "k3_node_avg<side>", sn);
+    KScope k(ctx, own ? "k3_node_avg" : "k3_node_avg<side>", sn);
     hipLaunchKernelGGL(k3_node_avg, dim3(xcd_grid((r1 - r0 + 4 * NODE_LOOP - 1) / (4 * NODE_LOOP), t.S)), dim3(256), 0, sn, t, N, r0, r1, V, Avg, As);
   }
   const int npair = Q * (Q + 1) / 2;       // A_aa: pairs q <= q', the transposed blocks are written from the same accumulators
@@ -3259,11 +3184,11 @@ int lrbms3_project_estimate_phase(lrbms3_ctx* ctx, int32_t phase, int32_t Q, int
              need_cpl = ks_cpl > 1 ? (long)Q * t.S * 6 * ks_cpl * pg_part_size<G_CPL>(N, QNl) : 0;
   const long need = need_sys + need_aaa + need_nc + need_ab + need_bb + need_cpl;
   if (need > ctx->pg_part_cap) {
-    HIP3(ctx, hipDeviceSynchronize());
+    LRBMS_HIP_CHECK(ctx, hipDeviceSynchronize());
     if (ctx->pg_part) (void)hipFree(ctx->pg_part);
     ctx->pg_part = nullptr;
     ctx->pg_part_cap = 0;
-    HIP3(ctx, hipMalloc((void**)&ctx->pg_part, sizeof(double) * need));
+    LRBMS_HIP_CHECK(ctx, hipMalloc((void**)&ctx->pg_part, sizeof(double) * need));
     ctx->pg_part_cap = need;
   }
   double* part_sys = ctx->pg_part;
@@ -3275,84 +3200,64 @@ int lrbms3_project_estimate_phase(lrbms3_ctx* ctx, int32_t phase, int32_t Q, int
   // (launch order measured: the MFMA-bound G_aa kernel first on the caller's stream, beside the latency-bound preparation
   // kernels of the other two chains, the HBM-bound system kernel after it: 2.39 -> 2.29 ms; a fourth stream for G_aa: slower)
   if (own) {
-    KScope3 k(ctx, "k3_pg<AAA>", st);
+    KScope k(ctx, "k3_pg<AAA>", st);
     a.ksplit = ks_aaa;
     a.part = part_aaa;
     a.out = G_aa;
     bad |= dispatch_pg<G_AAA>(a, npair * t.S, tn, tn, nw, st);
   }
   if (own) {
-    KScope3 k(ctx, "k3_pg<SYS>", st);
+    KScope k(ctx, "k3_pg<SYS>", st);
     a.ksplit = ks_sys;
     a.part = part_sys;
     a.out = B_sys;
     bad |= dispatch_pg<G_SYS>(a, Q * t.S, tn, tn, nw, st);
   }
   if (own) {
-    KScope3 k(ctx, "k3_pg<AB>", sf);
+    KScope k(ctx, "k3_pg<AB>", sf);
     a.ksplit = ks_ab;
     a.part = part_ab;
     a.out = G_ab;
     bad |= dispatch_pg<G_AB>(a, Q * t.S, tn, tq, nw, sf);
   }
   if (own) {
-    KScope3 k(ctx, "k3_pg<NC>", sn);
+    KScope k(ctx, "k3_pg<NC>", sn);
     a.ksplit = ks_nc;
     a.part = part_nc;
     a.out = G_nc;
     bad |= dispatch_pg<G_NC>(a, t.S, tn, tn, nw_s, sn);
   }
   if (own) {
-    KScope3 k(ctx, "k3_pg<BB>", sf);
+    KScope k(ctx, "k3_pg<BB>", sf);
     a.ksplit = ks_bb;
     a.part = part_bb;
     a.out = G_bb;
     bad |= dispatch_pg<G_BB>(a, t.S, tq, tq, nw, sf);          // 4 waves: 291 us, 8 waves: 307 us (tools/nw_sweep.sh)
   }
   if (own) {
-    KScope3 k(ctx, "k3_side_nc", sn);
+    KScope k(ctx, "k3_side_nc", sn);
     hipLaunchKernelGGL(k3_side_nc, dim3((t.nb + 3) / 4, t.S), dim3(256), 0, sn, t, N, Zb, Cn);
   }
   if (side) {
-    KScope3 k(ctx, "k3_pg<CPL>", st);
+    KScope k(ctx, "k3_pg<CPL>", st);
     a.ksplit = ks_cpl;
     a.part = part_cpl;
     a.out = B_sys;
     bad |= dispatch_pg<G_CPL>(a, Q * t.S * 6, tn, tn, nw, st);
   }
-  if (bad) return fail3(ctx, LRBMS_E_INVALID, "project_estimate: unsupported tile shape");
-  HIP3(ctx, hipEventRecord(ctx->ev_join[0], sf));
-  HIP3(ctx, hipEventRecord(ctx->ev_join[1], sn));
-  HIP3(ctx, hipStreamWaitEvent(st, ctx->ev_join[0], 0));
-  HIP3(ctx, hipStreamWaitEvent(st, ctx->ev_join[1], 0));
-  LAUNCH3(ctx);
+  if (bad) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_estimate: unsupported tile shape");
+  LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[0], sf));
+  LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[1], sn));
+  LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[0], 0));
+  LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[1], 0));
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
-int lrbms3_kernel_timing(lrbms3_ctx* ctx, int32_t enable) {
-  if (!ctx) return LRBMS_E_INVALID;
-  ctx->ktime = enable != 0;
-  ctx->ktime_n = 0;
-  return LRBMS_OK;
-}
+int lrbms3_kernel_timing(lrbms3_ctx* ctx, int32_t enable) { return lrbms_ctx_kernel_timing(ctx, enable); }
 
 int lrbms3_kernel_timing_read(lrbms3_ctx* ctx, char* names, int64_t names_cap, double* ms, int32_t cap, int32_t* count) {
-  if (!ctx || !names || !ms || !count) return LRBMS_E_INVALID;
-  HIP3(ctx, hipDeviceSynchronize());
-  std::string all;
-  int n = 0;
-  for (int i = 0; i < ctx->ktime_n && n < cap; ++i) {
-    float f = 0.f;
-    if (hipEventElapsedTime(&f, ctx->ktimers[i].e0, ctx->ktimers[i].e1) != hipSuccess) continue;
-    ms[n++] = f;
-    all += ctx->ktimers[i].name;
-    all += "\n";
-  }
-  if ((int64_t)all.size() + 1 > names_cap) return fail3(ctx, LRBMS_E_INVALID, "kernel_timing_read: names buffer too small");
-  memcpy(names, all.c_str(), all.size() + 1);
-  *count = n;
-  ctx->ktime_n = 0;
-  return LRBMS_OK;
+  return lrbms_ctx_kernel_timing_read(ctx, names, names_cap, ms, cap, count);
 }
 
 int lrbms3_reduced_estimate(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* theta, const double* u, const double* G_nc,
@@ -3360,15 +3265,15 @@ int lrbms3_reduced_estimate(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double*
                             const double* Rb, const double* Yb, const double* Dp, const double* Xab, const double* As,
                             const double* Cn, const double* ebar, const double* Bbb, const double* bdiv, const double* f2,
                             const double* ceps, double hdiam, double* eta_loc, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   if (Q < 1 || Q > 8 || N < 1 || Q * N > 64 || !theta || !u || !eta_loc)
-    return fail3(ctx, LRBMS_E_INVALID, "reduced_estimate: bad argument");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_estimate: bad argument");
   const T3& t = ctx->t;
   EA a{u, G_nc, G_bb, G_rdd, G_ab, G_aa, r_fd, Rb, Yb, Dp, Xab, As, Cn, ebar, Bbb, bdiv, f2, ceps, hdiam, eta_loc};
   const size_t lds = sizeof(double) * (7 * N + Q * N + t.nbf + t.nb + 256);
-  if (lds > 64 * 1024) return fail3(ctx, LRBMS_E_INVALID, "reduced_estimate: template too large for the LDS");
+  if (lds > 64 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_estimate: template too large for the LDS");
   hipLaunchKernelGGL(k3_estimate, dim3(t.S), dim3(256), lds, (hipStream_t)stream, t, Q, N, make_theta(Q, theta), a);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
@@ -3377,36 +3282,36 @@ int lrbms3_reduced_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t
                                   const double* r_fd, const double* Rb, const double* Yb, const double* Dp, const double* Xab,
                                   const double* As, const double* Cn, const double* ebar, const double* Bbb, const double* bdiv,
                                   const double* f2, const double* ceps, double hdiam, double* eta_loc, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   if (Q < 1 || Q > 8 || N < 1 || Q * N > 64 || nmu < 1 || !theta || !u || !eta_loc)
-    return fail3(ctx, LRBMS_E_INVALID, "reduced_estimate_batch: bad argument");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_estimate_batch: bad argument");
   const T3& t = ctx->t;
   EA a{u, G_nc, G_bb, G_rdd, G_ab, G_aa, r_fd, Rb, Yb, Dp, Xab, As, Cn, ebar, Bbb, bdiv, f2, ceps, hdiam, eta_loc};
   const bool est16_env = ctx->opt_estimate_valu == 0;      // LRBMS3_OPT_ESTIMATE_VALU
   const size_t lds16 = sizeof(double) * ((size_t)(7 * N + Q * N + t.nbf + t.nb) * EST16 + EST_NW * 6 * 16 + 4 * EST_NW * 16 + 3 * t.nvs + 1);
   if (est16_env && lds16 <= 160 * 1024 - 2048) {
     if (lds16 > 64 * 1024)
-      HIP3(ctx, hipFuncSetAttribute((const void*)k3_estimate_batch16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k3_estimate_batch16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
     for (int m0 = 0; m0 < nmu; m0 += EST16) {
       TB16 th{};
       for (int m = 0; m < EST16 && m0 + m < nmu; ++m)
         for (int q = 0; q < Q; ++q) th.v[m][q] = theta[(m0 + m) * Q + q];
       hipLaunchKernelGGL(k3_estimate_batch16, dim3(t.S), dim3(64 * EST_NW), lds16, (hipStream_t)stream, t, Q, N, nmu, m0, th, a);
     }
-    LAUNCH3(ctx);
+    LRBMS_LAUNCH_CHECK(ctx);
     return LRBMS_OK;
   }
   const size_t lds = sizeof(double) * ((size_t)(7 * N + Q * N + t.nbf + t.nb) * EST_MB + 256);
-  if (lds > 160 * 1024) return fail3(ctx, LRBMS_E_INVALID, "reduced_estimate_batch: template too large for the LDS");
+  if (lds > 160 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_estimate_batch: template too large for the LDS");
   if (lds > 64 * 1024)      // k_c = 4 at Q N = 64: 71 808 B
-    HIP3(ctx, hipFuncSetAttribute((const void*)k3_estimate_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k3_estimate_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   for (int m0 = 0; m0 < nmu; m0 += EST_MB) {
     TB8 th{};
     for (int m = 0; m < EST_MB && m0 + m < nmu; ++m)
       for (int q = 0; q < Q; ++q) th.v[m][q] = theta[(m0 + m) * Q + q];
     hipLaunchKernelGGL(k3_estimate_batch, dim3(t.S), dim3(256), lds, (hipStream_t)stream, t, Q, N, nmu, m0, th, a);
   }
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
@@ -3450,11 +3355,11 @@ int red_cg(lrbms3_ctx* ctx, hipStream_t st, int N, RedWork& w, const double* rhs
   const long S = t.S;
   hipLaunchKernelGGL(k3_pcg_init, dim3(S), dim3(64), 0, st, N, rhs, w.Dinv, u, w.r, w.z, w.p0, w.prz0, w.prr);
   hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)S, w.prr, w.scal + 1);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   double bb = 0.0, bn = 0.0;
-  HIP3(ctx, hipMemcpyAsync(&bb, w.scal + 1, sizeof(double), hipMemcpyDeviceToHost, st));
-  if (bref) HIP3(ctx, hipMemcpyAsync(&bn, bref, sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP3(ctx, hipStreamSynchronize(st));
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(&bb, w.scal + 1, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (bref) LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(&bn, bref, sizeof(double), hipMemcpyDeviceToHost, st));
+  LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
   if (info) info[0] = 0, info[1] = 0;
   if (bb == 0.0) return LRBMS_OK;
   const double den = bn > 0.0 ? bn : bb;
@@ -3471,16 +3376,16 @@ int red_cg(lrbms3_ctx* ctx, hipStream_t st, int N, RedWork& w, const double* rhs
       std::swap(rz_old, rz_cur);
     }
     hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)S, w.prr, w.scal);
-    LAUNCH3(ctx);
+    LRBMS_LAUNCH_CHECK(ctx);
     double rr = 0.0;
-    HIP3(ctx, hipMemcpyAsync(&rr, w.scal, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP3(ctx, hipStreamSynchronize(st));
+    LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(&rr, w.scal, sizeof(double), hipMemcpyDeviceToHost, st));
+    LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
     rel = sqrt(rr / den);
-    if (!(rel == rel)) return fail3(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual");
+    if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual");
     if (rel <= rtol) break;
   }
   if (info) info[0] = it, info[1] = rel;
-  if (rel > rtol) return fail3(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": not converged");
+  if (rel > rtol) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": not converged");
   return LRBMS_OK;
 }
 
@@ -3490,11 +3395,11 @@ extern "C" {
 
 int lrbms3_reduced_solve(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* theta, const double* B_sys, const double* rhs_red,
                          double* work, double* u, double rtol, int32_t max_iter, double* info, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "reduced_solve: needs all subdomains on this rank");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve: needs all subdomains on this rank");
   if (Q < 1 || Q > 8 || N < 1 || N > 64 || !theta || !B_sys || !rhs_red || !work || !u)
-    return fail3(ctx, LRBMS_E_INVALID, "reduced_solve: bad argument");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve: bad argument");
   hipStream_t st = (hipStream_t)stream;
   const long S = t.S, per_q = S * 7 * N * N;
   RedWork w = red_work(S, N, work);
@@ -3516,11 +3421,11 @@ int64_t lrbms3_reduced_solve_batch_work_size(lrbms3_ctx* ctx, int32_t N, int32_t
 int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nmu, const double* theta, const double* B_sys,
                                const double* rhs_red, double* work, double* u, double rtol, int32_t max_iter, double* info,
                                void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "reduced_solve_batch: needs all subdomains on this rank");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: needs all subdomains on this rank");
   if (Q < 1 || Q > 8 || N < 1 || N > 32 || nmu < 1 || nmu > 64 || !theta || !B_sys || !rhs_red || !work || !u)
-    return fail3(ctx, LRBMS_E_INVALID, "reduced_solve_batch: needs N <= 32 and nmu <= 64");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: needs N <= 32 and nmu <= 64");
   hipStream_t st = (hipStream_t)stream;
   const long S = t.S, per_q = S * 7 * N * N;
   // Up to four groups of <= 16 parameters, each an independent CG on its own stream (the caller's and the library's three side
@@ -3564,8 +3469,8 @@ int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nm
     G.th = TB{};
   }
   if (ng > 1) {
-    HIP3(ctx, hipEventRecord(ctx->ev_fork, st));
-    for (int k = 1; k < ng; ++k) HIP3(ctx, hipStreamWaitEvent(g[k].st, ctx->ev_fork, 0));
+    LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
+    for (int k = 1; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(g[k].st, ctx->ev_fork, 0));
   }
   for (int k = 0; k < ng; ++k) {
     Group& G = g[k];
@@ -3581,14 +3486,14 @@ int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nm
       hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, G.st, per_q, Q, mean, B_sys, G.Amu);
       hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), G.st, N, G.Amu, G.Dinv);
     }
-    HIP3(ctx, hipMemsetAsync(G.scal, 0, sizeof(double) * 80, G.st));
+    LRBMS_HIP_CHECK(ctx, hipMemsetAsync(G.scal, 0, sizeof(double) * 80, G.st));
     hipLaunchKernelGGL(k3b_init, dim3(S), dim3(512), sizeof(double) * (N + 32 * 16), G.st, N, G.nm, nmu, rhs_red, G.Dinv, u + G.m0, G.r,
                        G.z, G.po, G.prz, G.prr);
     if (A0inv)
       hipLaunchKernelGGL(k3b_coarse_apply, dim3((unsigned)((S + 15) / 16)), dim3(1024), 0, G.st, (int)S, N, G.nm, A0inv, G.r, G.y0, G.prc);
     hipLaunchKernelGGL(k3b_reduce, dim3(1), dim3(256), 0, G.st, (int)S, G.nm, G.prr, G.scal + 64);
   }
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   if (info) info[0] = 0, info[1] = 0;
   const int check = A0inv ? 12 : 8;    // iterations between two looks at the residuals (a host synchronisation each)
   const size_t lds_mv = sizeof(double) * (7 * N * 16 + 32 * 16), lds_up = sizeof(double) * (N * 16 + 32 * 16);
@@ -3629,14 +3534,14 @@ int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nm
       Group& G = g[k];
       if (G.done) continue;
       hipLaunchKernelGGL(k3b_reduce, dim3(1), dim3(256), 0, G.st, (int)S, G.nm, G.prr, G.scal + 48);
-      HIP3(ctx, hipMemcpyAsync(rr[k], G.scal + 48, sizeof(double) * 32, hipMemcpyDeviceToHost, G.st));   // [3] residuals, [4] |b|^2
+      LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(rr[k], G.scal + 48, sizeof(double) * 32, hipMemcpyDeviceToHost, G.st));   // [3] residuals, [4] |b|^2
     }
-    LAUNCH3(ctx);
+    LRBMS_LAUNCH_CHECK(ctx);
     all_done = true;
     for (int k = 0; k < ng; ++k) {
       Group& G = g[k];
       if (G.done) continue;
-      HIP3(ctx, hipStreamSynchronize(G.st));
+      LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(G.st));
       G.rel = 0.0;
       for (int m = 0; m < G.nm; ++m) {
         const double bbm = rr[k][16 + m], rm = bbm > 0.0 ? sqrt(rr[k][m] / bbm) : 0.0;
@@ -3649,8 +3554,8 @@ int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nm
   }
   if (ng > 1)
     for (int k = 1; k < ng; ++k) {
-      HIP3(ctx, hipEventRecord(ctx->ev_join[k - 1], g[k].st));
-      HIP3(ctx, hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0));
+      LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[k - 1], g[k].st));
+      LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0));
     }
   int it = 0;
   double rel = 0.0;
@@ -3659,8 +3564,8 @@ int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nm
     rel = g[k].rel > rel ? g[k].rel : rel;
   }
   if (info) info[0] = it, info[1] = rel;
-  if (rc != LRBMS_OK) return fail3(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: NaN residual");
-  if (rel > rtol) return fail3(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: not converged");
+  if (rc != LRBMS_OK) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: NaN residual");
+  if (rel > rtol) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: not converged");
   return LRBMS_OK;
 }
 
@@ -3677,11 +3582,11 @@ int64_t lrbms3_reduced_precond_work_size(lrbms3_ctx* ctx, int32_t N) {
 
 int lrbms3_reduced_precond_build(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* theta, const double* B_sys, double* work,
                                  double* pc, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "reduced_precond_build: needs all subdomains on this rank");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_precond_build: needs all subdomains on this rank");
   if (Q < 1 || Q > 8 || N < 1 || N > 32 || !theta || !B_sys || !work || !pc)
-    return fail3(ctx, LRBMS_E_INVALID, "reduced_precond_build: bad argument (the batched solve it serves takes N <= 32)");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_precond_build: bad argument (the batched solve it serves takes N <= 32)");
   hipStream_t st = (hipStream_t)stream;
   const long S = t.S;
   double* A0 = work;
@@ -3689,43 +3594,43 @@ int lrbms3_reduced_precond_build(lrbms3_ctx* ctx, int32_t Q, int32_t N, const do
   rocblas_int* pinfo = (rocblas_int*)(Id + S * S);
   if (!ctx->blas) {
     rocblas_handle h = nullptr;
-    if (rocblas_create_handle(&h) != rocblas_status_success) return fail3(ctx, LRBMS_E_HIP, "rocblas_create_handle failed");
+    if (rocblas_create_handle(&h) != rocblas_status_success) return lrbms_fail(ctx, LRBMS_E_HIP, "rocblas_create_handle failed");
     ctx->blas = h;
   }
   rocblas_handle h = (rocblas_handle)ctx->blas;
-  if (rocblas_set_stream(h, st) != rocblas_status_success) return fail3(ctx, LRBMS_E_HIP, "rocblas_set_stream failed");
-  HIP3(ctx, hipMemsetAsync(A0, 0, sizeof(double) * 2 * S * S, st));
+  if (rocblas_set_stream(h, st) != rocblas_status_success) return lrbms_fail(ctx, LRBMS_E_HIP, "rocblas_set_stream failed");
+  LRBMS_HIP_CHECK(ctx, hipMemsetAsync(A0, 0, sizeof(double) * 2 * S * S, st));
   hipLaunchKernelGGL(k3r_coarse_fill, dim3((unsigned)((S * 7 + 255) / 256)), dim3(256), 0, st, t, Q, N, make_theta(Q, theta), B_sys, A0, Id);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   if (rocsolver_dpotrf(h, rocblas_fill_lower, (rocblas_int)S, A0, (rocblas_int)S, pinfo) != rocblas_status_success)
-    return fail3(ctx, LRBMS_E_HIP, "rocsolver_dpotrf failed");
+    return lrbms_fail(ctx, LRBMS_E_HIP, "rocsolver_dpotrf failed");
   rocblas_int hinfo = 0;
-  HIP3(ctx, hipMemcpyAsync(&hinfo, pinfo, sizeof(rocblas_int), hipMemcpyDeviceToHost, st));
-  HIP3(ctx, hipStreamSynchronize(st));
-  if (hinfo != 0) return fail3(ctx, LRBMS_E_INVALID, "reduced_precond_build: the coarse matrix is not positive definite (first basis vectors)");
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(&hinfo, pinfo, sizeof(rocblas_int), hipMemcpyDeviceToHost, st));
+  LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  if (hinfo != 0) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_precond_build: the coarse matrix is not positive definite (first basis vectors)");
   if (rocsolver_dpotrs(h, rocblas_fill_lower, (rocblas_int)S, (rocblas_int)S, A0, (rocblas_int)S, Id, (rocblas_int)S) !=
       rocblas_status_success)
-    return fail3(ctx, LRBMS_E_HIP, "rocsolver_dpotrs failed");
-  HIP3(ctx, hipMemcpyAsync(pc, Id, sizeof(double) * S * S, hipMemcpyDeviceToDevice, st));
+    return lrbms_fail(ctx, LRBMS_E_HIP, "rocsolver_dpotrs failed");
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(pc, Id, sizeof(double) * S * S, hipMemcpyDeviceToDevice, st));
   // the inverse diagonal blocks at the same reference parameter (the dense work is done: its space holds the combined blocks)
   const long per_q = S * 7 * N * N;
   hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, make_theta(Q, theta), B_sys, work);
   hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, work, pc + S * S);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
 int lrbms3_reduced_precond_use(lrbms3_ctx* ctx, int32_t N, const double* pc) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   ctx->user_pc = pc;
   ctx->user_pc_N = pc ? N : 0;
   return LRBMS_OK;
 }
 
 int lrbms3_fom_coarse_space(lrbms3_ctx* ctx, int32_t nc, const double* Phi) {
-  REQUIRE3(ctx);
-  if (nc < 0 || nc > 4 || (nc > 0 && !Phi)) return fail3(ctx, LRBMS_E_INVALID, "fom_coarse_space: 0 <= nc <= 4 functions, Phi [n][nc]");
-  if (!ctx->has_mesh) return fail3(ctx, LRBMS_E_STATE, "fom_coarse_space: upload the mesh first");
+  LRBMS_REQUIRE_MESH(ctx);
+  if (nc < 0 || nc > 4 || (nc > 0 && !Phi)) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_coarse_space: 0 <= nc <= 4 functions, Phi [n][nc]");
+  if (!ctx->has_mesh) return lrbms_fail(ctx, LRBMS_E_STATE, "fom_coarse_space: upload the mesh first");
   const T3& t = ctx->t;
   ctx->fom_nc = 0;
   ctx->fom_pc_M = 0;                     // a kept coarse inverse belongs to the old space
@@ -3734,16 +3639,16 @@ int lrbms3_fom_coarse_space(lrbms3_ctx* ctx, int32_t nc, const double* Phi) {
   for (long d = 0; d < t.n; ++d)
     for (int k = 0; k < nc; ++k) padded[d * 4 + k] = Phi[d * nc + k];
   if (!ctx->fom_phi) {
-    HIP3(ctx, hipMalloc((void**)&ctx->fom_phi, sizeof(double) * (size_t)t.n * 4));
+    LRBMS_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fom_phi, sizeof(double) * (size_t)t.n * 4));
     ctx->owned.push_back(ctx->fom_phi);
   }
-  HIP3(ctx, hipMemcpy(ctx->fom_phi, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice));
+  LRBMS_HIP_CHECK(ctx, hipMemcpy(ctx->fom_phi, padded.data(), sizeof(double) * padded.size(), hipMemcpyHostToDevice));
   ctx->fom_nc = nc;
   return LRBMS_OK;
 }
 
 int lrbms3_fom_precond_keep(lrbms3_ctx* ctx, int32_t keep) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   ctx->fom_keep = keep != 0;
   if (!keep) {
     if (ctx->fom_pc) (void)hipFree(ctx->fom_pc);
@@ -3819,34 +3724,34 @@ int fom_coarse(lrbms3_ctx* ctx, hipStream_t st, FomWork& w, bool shared_pc, int&
   if (nc > 0 && !kept) {
     if (!ctx->blas) {
       rocblas_handle h = nullptr;
-      if (rocblas_create_handle(&h) != rocblas_status_success) return fail3(ctx, LRBMS_E_HIP, "rocblas_create_handle failed");
+      if (rocblas_create_handle(&h) != rocblas_status_success) return lrbms_fail(ctx, LRBMS_E_HIP, "rocblas_create_handle failed");
       ctx->blas = h;
     }
     rocblas_handle h = (rocblas_handle)ctx->blas;
-    if (rocblas_set_stream(h, st) != rocblas_status_success) return fail3(ctx, LRBMS_E_HIP, "rocblas_set_stream failed");
+    if (rocblas_set_stream(h, st) != rocblas_status_success) return lrbms_fail(ctx, LRBMS_E_HIP, "rocblas_set_stream failed");
     hipLaunchKernelGGL(k3f_coarse_blocks, dim3(S), dim3(256), 0, st, t, Phi, w.Amu, w.Cmu, w.A1b);
-    HIP3(ctx, hipMemsetAsync(w.A1, 0, sizeof(double) * 2 * M * M, st));             // A1 and the identity behind it (A1inv at M * M when nc = 4)
+    LRBMS_HIP_CHECK(ctx, hipMemsetAsync(w.A1, 0, sizeof(double) * 2 * M * M, st));             // A1 and the identity behind it (A1inv at M * M when nc = 4)
     double* Id = w.A1 + M * M;
     hipLaunchKernelGGL(k3f_coarse_dense, dim3((unsigned)((std::max(M, S * 112) + 255) / 256)), dim3(256), 0, st, t, nc, w.A1b, w.A1, Id);
-    LAUNCH3(ctx);
+    LRBMS_LAUNCH_CHECK(ctx);
     if (rocsolver_dpotrf(h, rocblas_fill_lower, (rocblas_int)M, w.A1, (rocblas_int)M, w.pinfo) != rocblas_status_success)
-      return fail3(ctx, LRBMS_E_HIP, "rocsolver_dpotrf failed");
+      return lrbms_fail(ctx, LRBMS_E_HIP, "rocsolver_dpotrf failed");
     rocblas_int hinfo = 0;
-    HIP3(ctx, hipMemcpyAsync(&hinfo, w.pinfo, sizeof(rocblas_int), hipMemcpyDeviceToHost, st));
-    HIP3(ctx, hipStreamSynchronize(st));
+    LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(&hinfo, w.pinfo, sizeof(rocblas_int), hipMemcpyDeviceToHost, st));
+    LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
     if (hinfo != 0) nc = 0;                                   // not positive definite (dependent functions): block-Jacobi alone
     else if (rocsolver_dpotrs(h, rocblas_fill_lower, (rocblas_int)M, (rocblas_int)M, w.A1, (rocblas_int)M, Id, (rocblas_int)M) !=
              rocblas_status_success)
-      return fail3(ctx, LRBMS_E_HIP, "rocsolver_dpotrs failed");
+      return lrbms_fail(ctx, LRBMS_E_HIP, "rocsolver_dpotrs failed");
     A1inv = Id;
     if (shared_pc && nc > 0 && ctx->fom_keep) {
       if (ctx->fom_pc && ctx->fom_pc_M != M) {
-        HIP3(ctx, hipFree(ctx->fom_pc));
+        LRBMS_HIP_CHECK(ctx, hipFree(ctx->fom_pc));
         ctx->fom_pc = nullptr;
       }
       ctx->fom_pc_M = 0;
-      if (!ctx->fom_pc) HIP3(ctx, hipMalloc((void**)&ctx->fom_pc, sizeof(double) * M * M));
-      HIP3(ctx, hipMemcpyAsync(ctx->fom_pc, Id, sizeof(double) * M * M, hipMemcpyDeviceToDevice, st));
+      if (!ctx->fom_pc) LRBMS_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fom_pc, sizeof(double) * M * M));
+      LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->fom_pc, Id, sizeof(double) * M * M, hipMemcpyDeviceToDevice, st));
       ctx->fom_pc_M = M;
       ctx->fom_pc_nc = nc;
     }
@@ -3878,11 +3783,11 @@ int fom_cg(lrbms3_ctx* ctx, hipStream_t st, FomWork& w, int nc, const double* A1
   coarse();
   hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)nrz, prz, scal + 0);
   hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)nblk, prr, scal + 4);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   double bb = 0.0, bn = 0.0;
-  HIP3(ctx, hipMemcpyAsync(&bb, scal + 4, sizeof(double), hipMemcpyDeviceToHost, st));
-  if (bref) HIP3(ctx, hipMemcpyAsync(&bn, bref, sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP3(ctx, hipStreamSynchronize(st));
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(&bb, scal + 4, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (bref) LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(&bn, bref, sizeof(double), hipMemcpyDeviceToHost, st));
+  LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
   if (info) info[0] = 0, info[1] = 0;
   if (bb == 0.0) return LRBMS_OK;
   const double den = bn > 0.0 ? bn : bb;
@@ -3901,16 +3806,16 @@ int fom_cg(lrbms3_ctx* ctx, hipStream_t st, FomWork& w, int nc, const double* A1
       hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)nrz, prz, scal + (cur ^ 1));
     }
     hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)nblk, prr, scal + 3);
-    LAUNCH3(ctx);
+    LRBMS_LAUNCH_CHECK(ctx);
     double rr = 0.0;
-    HIP3(ctx, hipMemcpyAsync(&rr, scal + 3, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP3(ctx, hipStreamSynchronize(st));
+    LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(&rr, scal + 3, sizeof(double), hipMemcpyDeviceToHost, st));
+    LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
     rel = sqrt(rr / den);
-    if (!(rel == rel)) return fail3(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual");
+    if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual");
     if (rel <= rtol) break;
   }
   if (info) info[0] = it, info[1] = rel;
-  if (rel > rtol) return fail3(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": not converged");
+  if (rel > rtol) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": not converged");
   return LRBMS_OK;
 }
 
@@ -3920,10 +3825,10 @@ extern "C" {
 
 int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const double* A_diag, const double* A_cpl, const double* b,
                      double* work, double* x, double rtol, int32_t max_iter, double* info, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "fom_solve: needs all subdomains on this rank");
-  if (Q < 1 || Q > 8 || !theta || !A_diag || !A_cpl || !b || !work || !x) return fail3(ctx, LRBMS_E_INVALID, "fom_solve: bad argument");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_solve: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || !theta || !A_diag || !A_cpl || !b || !work || !x) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_solve: bad argument");
   hipStream_t st = (hipStream_t)stream;
   const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100;
   FomWork w = fom_work(t, work);
@@ -3940,11 +3845,11 @@ int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const doub
 
 int lrbms3_fom_apply(lrbms3_ctx* ctx, int32_t Q, int32_t M, const double* theta, const double* A_diag, const double* A_cpl,
                      const double* x, double* y, void* stream) {
-  REQUIRE3(ctx);
-  if (Q < 1 || Q > 8 || M < 1 || !theta || !A_diag || !A_cpl || !x || !y) return fail3(ctx, LRBMS_E_INVALID, "fom_apply: bad argument");
+  LRBMS_REQUIRE_MESH(ctx);
+  if (Q < 1 || Q > 8 || M < 1 || !theta || !A_diag || !A_cpl || !x || !y) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_apply: bad argument");
   const T3& t = ctx->t;
   hipLaunchKernelGGL(k3_fom_apply, dim3(t.nT, t.S), dim3(256), 0, (hipStream_t)stream, t, Q, M, make_theta(Q, theta), A_diag, A_cpl, x, y);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
@@ -4189,12 +4094,12 @@ __global__ __launch_bounds__(64) void k3p_time_residual(T3 t, int N, const doubl
 int ensure_tm_inverse(lrbms3_ctx* ctx, hipStream_t st) {
   if (ctx->tm_inv && ctx->tm_inv_src == ctx->t.TM) return LRBMS_OK;
   if (!ctx->tm_inv) {
-    HIP3(ctx, hipMalloc((void**)&ctx->tm_inv, sizeof(double) * 600));
+    LRBMS_HIP_CHECK(ctx, hipMalloc((void**)&ctx->tm_inv, sizeof(double) * 600));
     ctx->owned.push_back(ctx->tm_inv);
   }
   hipLaunchKernelGGL(k3p_tm_inverse, dim3(6), dim3(64), 0, st, ctx->t.TM, ctx->tm_inv);
-  LAUNCH3(ctx);
-  HIP3(ctx, hipStreamSynchronize(st));      // later calls may come on other streams
+  LRBMS_LAUNCH_CHECK(ctx);
+  LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));      // later calls may come on other streams
   ctx->tm_inv_src = ctx->t.TM;
   return LRBMS_OK;
 }
@@ -4204,30 +4109,30 @@ int ensure_tm_inverse(lrbms3_ctx* ctx, hipStream_t st) {
 extern "C" {
 
 int lrbms3_mass_inverse_norm2(lrbms3_ctx* ctx, int32_t L, const double* Y, double* out, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "mass_inverse_norm2: needs all subdomains on this rank");
-  if (L < 1 || !Y || !out) return fail3(ctx, LRBMS_E_INVALID, "mass_inverse_norm2: bad argument");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "mass_inverse_norm2: needs all subdomains on this rank");
+  if (L < 1 || !Y || !out) return lrbms_fail(ctx, LRBMS_E_INVALID, "mass_inverse_norm2: bad argument");
   hipStream_t st = (hipStream_t)stream;
   int rc = ensure_tm_inverse(ctx, st);
   if (rc != LRBMS_OK) return rc;
   hipLaunchKernelGGL(k3p_mass_inv_norm2, dim3(t.S), dim3(256), 0, st, t, L, ctx->tm_inv, Y, out);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
 int lrbms3_project_mass(lrbms3_ctx* ctx, int32_t N, const double* V, double* M_red, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "project_mass: needs all subdomains on this rank");
-  if (N < 1 || N > 64 || !V || !M_red) return fail3(ctx, LRBMS_E_INVALID, "project_mass: bad argument (1 <= N <= 64)");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_mass: needs all subdomains on this rank");
+  if (N < 1 || N > 64 || !V || !M_red) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_mass: bad argument (1 <= N <= 64)");
   hipStream_t st = (hipStream_t)stream;
   const int T = (N + 15) / 16;
   if (T == 1) hipLaunchKernelGGL(k3p_project_mass<1>, dim3(t.S), dim3(512), 0, st, t, N, V, M_red);
   else if (T == 2) hipLaunchKernelGGL(k3p_project_mass<2>, dim3(t.S), dim3(512), 0, st, t, N, V, M_red);
   else if (T == 3) hipLaunchKernelGGL(k3p_project_mass<3>, dim3(t.S), dim3(512), 0, st, t, N, V, M_red);
   else hipLaunchKernelGGL(k3p_project_mass<4>, dim3(t.S), dim3(512), 0, st, t, N, V, M_red);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
@@ -4242,12 +4147,12 @@ int64_t lrbms3_fom_implicit_euler_work_size(lrbms3_ctx* ctx) {
 int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, double dt, int32_t nt, const double* A_diag,
                               const double* A_cpl, const double* b, double* work, double* U, double rtol, int32_t max_iter,
                               double* info, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "fom_implicit_euler: needs all subdomains on this rank");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: needs all subdomains on this rank");
   if (Q < 1 || Q > 8 || !theta || !A_diag || !A_cpl || !b || !work || !U)
-    return fail3(ctx, LRBMS_E_INVALID, "fom_implicit_euler: bad argument");
-  if (!(dt > 0.0) || nt < 1) return fail3(ctx, LRBMS_E_INVALID, "fom_implicit_euler: dt > 0 and nt >= 1 required");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: bad argument");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: dt > 0 and nt >= 1 required");
   hipStream_t st = (hipStream_t)stream;
   const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100, total = S * t.n;
   FomWork w = fom_work(t, work);
@@ -4261,7 +4166,7 @@ int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, d
   hipLaunchKernelGGL(k3_combine, dim3((unsigned)((ncp + 255) / 256)), dim3(256), 0, st, ncp, Q, th, A_cpl, w.Cmu);
   hipLaunchKernelGGL(k3p_fom_add_mass, dim3((unsigned)((S * t.nT * 100 + 255) / 256)), dim3(256), 0, st, t, S * t.nT * 100, w.Amu);
   hipLaunchKernelGGL(k3f_block_inverse, dim3((t.nT + 63) / 64, S), dim3(64), 0, st, t, w.Amu, w.Dinv);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   int nc = 0;
   const double* A1inv = nullptr;
   int rc = fom_coarse(ctx, st, w, false, nc, A1inv);
@@ -4275,7 +4180,7 @@ int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, d
     hipLaunchKernelGGL(k3f_matvec, dim3(xcd_grid(w.nbx, (int)S)), dim3(256), 0, st, t, w.nbx, w.Amu, w.Cmu, uk, w.y, w.ppy);
     hipLaunchKernelGGL(k3p_fom_rhs, dim3(w.nbx, S), dim3(256), 0, st, t, dt, uk, b, w.y, rhs, part);
     hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)w.nblk, part, ff);
-    LAUNCH3(ctx);
+    LRBMS_LAUNCH_CHECK(ctx);
     double inf[2] = {0.0, 0.0};
     rc = fom_cg(ctx, st, w, nc, A1inv, rhs, un, rtol, max_iter, inf, ff, "fom_implicit_euler");
     iters += inf[0];
@@ -4283,7 +4188,7 @@ int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, d
     if (info) info[0] = iters, info[1] = worst;
     if (rc != LRBMS_OK) return rc;
     hipLaunchKernelGGL(k3p_axpy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, uk, un);
-    LAUNCH3(ctx);
+    LRBMS_LAUNCH_CHECK(ctx);
   }
   return LRBMS_OK;
 }
@@ -4297,12 +4202,12 @@ int64_t lrbms3_reduced_implicit_euler_work_size(lrbms3_ctx* ctx, int32_t N) {
 int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* theta, double dt, int32_t nt,
                                   const double* B_sys, const double* M_red, const double* rhs_red, double* work, double* U,
                                   double rtol, int32_t max_iter, double* info, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: needs all subdomains on this rank");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: needs all subdomains on this rank");
   if (Q < 1 || Q > 8 || N < 1 || N > 64 || !theta || !B_sys || !M_red || !rhs_red || !work || !U)
-    return fail3(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: bad argument");
-  if (!(dt > 0.0) || nt < 1) return fail3(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: dt > 0 and nt >= 1 required");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: bad argument");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: dt > 0 and nt >= 1 required");
   hipStream_t st = (hipStream_t)stream;
   const long S = t.S, per_q = S * 7 * N * N, total = S * N;
   RedWork w = red_work(S, N, work);
@@ -4316,7 +4221,7 @@ int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const d
   hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, th, B_sys, w.Amu);
   hipLaunchKernelGGL(k3p_red_add_mass, dim3((unsigned)((S * N * N + 255) / 256)), dim3(256), 0, st, S * N * N, N, M_red, w.Amu);
   hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, w.Amu, w.Dinv);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   const size_t lds = sizeof(double) * (7 * N + 64);
   double iters = 0.0, worst = 0.0;
   if (info) info[0] = 0, info[1] = 0;
@@ -4327,7 +4232,7 @@ int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const d
     hipLaunchKernelGGL(k3_pcg_matvec, dim3(S), dim3(64), lds, st, t, N, 1, w.Amu, uk, uk, w.p1, w.Ap, w.prz0, w.prz1, w.ppap);
     hipLaunchKernelGGL(k3p_red_rhs, dim3(S), dim3(64), 0, st, N, dt, M_red, uk, rhs_red, w.Ap, rhs, part);
     hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)S, part, ff);
-    LAUNCH3(ctx);
+    LRBMS_LAUNCH_CHECK(ctx);
     double inf[2] = {0.0, 0.0};
     int rc = red_cg(ctx, st, N, w, rhs, un, rtol, max_iter, inf, ff, "reduced_implicit_euler");
     iters += inf[0];
@@ -4335,7 +4240,7 @@ int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const d
     if (info) info[0] = iters, info[1] = worst;
     if (rc != LRBMS_OK) return rc;
     hipLaunchKernelGGL(k3p_axpy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, uk, un);
-    LAUNCH3(ctx);
+    LRBMS_LAUNCH_CHECK(ctx);
   }
   return LRBMS_OK;
 }
@@ -4348,23 +4253,23 @@ int64_t lrbms3_reduced_time_residual_work_size(lrbms3_ctx* ctx, int32_t N) {
 
 int lrbms3_reduced_time_residual(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t L, const double* theta, const double* B_sys,
                                  const double* M_red, const double* dU, double* work, double* out, void* stream) {
-  REQUIRE3(ctx);
+  LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return fail3(ctx, LRBMS_E_INVALID, "reduced_time_residual: needs all subdomains on this rank");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_time_residual: needs all subdomains on this rank");
   if (Q < 1 || Q > 8 || N < 1 || N > 64 || L < 1 || L > 65535 || !theta || !B_sys || !M_red || !dU || !work || !out)
-    return fail3(ctx, LRBMS_E_INVALID, "reduced_time_residual: bad argument");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_time_residual: bad argument");
   hipStream_t st = (hipStream_t)stream;
   const long S = t.S, per_q = S * 7 * N * N, NN = (long)N * N;
   double* Amu = work;
   double* Minv = Amu + per_q;
   // M_red^-1 by the reduced solver's block inverse, which reads the self slot of a 7-slot operator: M_red goes to slot 3 of Amu
   // first (its zero-diagonal rule: the identity on padded columns), then Amu receives the combined operator
-  HIP3(ctx, hipMemcpy2DAsync(Amu + 3 * NN, sizeof(double) * 7 * NN, M_red, sizeof(double) * NN, sizeof(double) * NN, S,
+  LRBMS_HIP_CHECK(ctx, hipMemcpy2DAsync(Amu + 3 * NN, sizeof(double) * 7 * NN, M_red, sizeof(double) * NN, sizeof(double) * NN, S,
                              hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, Amu, Minv);
   hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, make_theta(Q, theta), B_sys, Amu);
   hipLaunchKernelGGL(k3p_time_residual, dim3(S, L), dim3(64), sizeof(double) * (8 * N + 64), st, t, N, Amu, Minv, dU, out);
-  LAUNCH3(ctx);
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 

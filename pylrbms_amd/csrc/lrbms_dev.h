@@ -5,7 +5,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lrbms_hip.h"
+#include "lrbms_ctx_base.h"
 
 // Device view of the subdomain template (all pointers into one ctx-owned device allocation).
 struct Tmpl {
@@ -55,36 +55,18 @@ struct Tmpl {
 // the subdomain workgroup-index b of a fused-pass kernel works on
 __device__ inline int subdomain_of(const Tmpl& t, int b) { return t.sub_list ? t.sub_list[b] : b; }
 
-// Library-owned side streams, one set per device, shared by every context of the process (2D and 3D alike).  HIP maps streams
-// round-robin onto a few hardware queues (4 by default); a second context with side streams of its own lands on queues the
-// first one (or the caller's stream) already uses and its "concurrent" chains then run one after another -- measured: the
-// config-5 pass 2.49 ms instead of 2.20 ms when a 2D context with three streams of its own was alive in the process.
-// Reference-counted; the stream is destroyed with its last user.  Thread-safe.
-hipStream_t lrbms_side_stream_acquire(int device, int i);   // i in [0, 3); nullptr on failure
-void lrbms_side_stream_release(int device, int i);
-
-struct lrbms_ctx {
-  int device = 0;
+struct lrbms_ctx : lrbms_ctx_base {
   int num_cus = 0;                // compute units of the device (queried on first use)
-  bool has_mesh = false;
   Tmpl t{};
   int S = 0, S_ext = 0;
   int* nbr = nullptr;             // [S][5] device
   std::vector<int32_t> nbr_host;  // the same on the host (argument checks)
-  std::vector<void*> owned;       // device allocations to free
-  hipStream_t aux[3] = {nullptr, nullptr, nullptr};   // library-owned streams: independent small kernels run concurrently
-  hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_prep = nullptr;   // fused pass, phases 1 / 3: recorded behind the preparation of the own basis; phase 2 waits for it
   hipEvent_t prep_done = nullptr; // ... or for the fork event of that call, recorded at the same point (whichever the last call used)
   // coarse level of the reduced solvers' preconditioner (online.hip): rocBLAS handle and S x S scratch, created on first use
   void* blas = nullptr;
   double* coarse = nullptr;       // [2][S][S] + info
   long coarse_cap = 0;
-  // per-kernel device timing of the fused pass (lrbms_kernel_timing): HIP event pairs on the stream each kernel runs on
-  bool ktime = false;
-  struct KTimer { const char* name; hipEvent_t e0, e1; bool used; };
-  std::vector<KTimer> ktimers;
-  int ktime_n = 0;
   // K-split of k_f1u (fused.hip): per-workgroup partial tiles and one arrival counter per subdomain, allocated on first use
   double* ksp_part = nullptr;
   long ksp_part_cap = 0;
@@ -106,7 +88,6 @@ struct lrbms_ctx {
   double* src_phi = nullptr;         // [64][64] source coefficients of lrbms_reduced_solve_batch_src, allocated on first use
   const double* user_pc = nullptr;   // prebuilt preconditioner the reduced solves use (lrbms_reduced_precond_use), caller-owned
   int user_pc_N = 0;
-  std::string err;
 };
 
 // SWIPDG constants (dune-gdt elliptic-ipdg.hh: inner_sigma / boundary_sigma for polorder <= 1), beta = 1/(d-1) = 1
@@ -115,49 +96,6 @@ struct lrbms_ctx {
 
 __host__ __device__ inline int side_to_slot(int side) { return side < 2 ? side : side + 1; }
 __host__ __device__ inline int slot_to_side(int slot) { return slot < 2 ? slot : slot - 1; }  // slot != 2
-
-static inline int lrbms_fail(lrbms_ctx* ctx, int code, const std::string& msg) {
-  if (ctx) ctx->err = msg;
-  return code;
-}
-
-#define LRBMS_HIP_CHECK(ctx, expr)                                                                  \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return lrbms_fail(ctx, LRBMS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
-  } while (0)
-
-#define LRBMS_REQUIRE_MESH(ctx)                                                      \
-  do {                                                                               \
-    if (!(ctx)) return LRBMS_E_INVALID;                                              \
-    if (!(ctx)->has_mesh) return lrbms_fail(ctx, LRBMS_E_STATE, "mesh not uploaded"); \
-  } while (0)
-
-#define LRBMS_LAUNCH_CHECK(ctx) LRBMS_HIP_CHECK(ctx, hipGetLastError())
-
-// RAII scope around one kernel launch: when timing is enabled (lrbms_kernel_timing) records an event pair on the
-// kernel's own stream; otherwise costs one branch.
-struct KScope {
-  lrbms_ctx* ctx;
-  hipStream_t st;
-  int idx;
-  KScope(lrbms_ctx* c, const char* name, hipStream_t s) : ctx(c), st(s), idx(-1) {
-    if (!c->ktime) return;
-    if (c->ktime_n == (int)c->ktimers.size()) {
-      lrbms_ctx::KTimer k{name, nullptr, nullptr, false};
-      if (hipEventCreate(&k.e0) != hipSuccess || hipEventCreate(&k.e1) != hipSuccess) return;
-      c->ktimers.push_back(k);
-    }
-    idx = c->ktime_n++;
-    c->ktimers[idx].name = name;
-    c->ktimers[idx].used = true;
-    (void)hipEventRecord(c->ktimers[idx].e0, st);
-  }
-  ~KScope() {
-    if (idx >= 0) (void)hipEventRecord(ctx->ktimers[idx].e1, st);
-  }
-};
 
 int build_template_tables(lrbms_ctx* ctx);
 int launch_wab(lrbms_ctx* ctx, int Q, const double* Aab, double* Wab, hipStream_t st);   // fused.hip: W' = hab A_ab

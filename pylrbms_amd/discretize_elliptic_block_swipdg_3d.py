@@ -15,6 +15,7 @@ import numpy as np
 
 from pylrbms_amd._native import NativeError
 from pylrbms_amd.engine3d import Engine3D
+from pylrbms_amd.reductor import ExtensionError, LocalBasisSlab
 
 
 class BlockDiscretization3D:
@@ -203,11 +204,10 @@ class ReducedDiscretization3D:
         return self.d.combine(eta_loc.cpu().numpy(), mu, decompose)
 
 
-class ExtensionError3D(Exception):
-    """A vector handed to ``extend_basis`` is (numerically) in the span of a local basis (pyMOR's ExtensionError)."""
+ExtensionError3D = ExtensionError      # a vector handed to ``extend_basis`` is (numerically) in the span of a local basis
 
 
-class LRBMSReductor3D:
+class LRBMSReductor3D(LocalBasisSlab):
     """``LRBMSReductor`` (reference reductor.py:17-78) for the 3D path: the same constructor and methods, local bases as ONE
     device slab [S, n, N_max] (ragged bases: zero columns behind the ``local_sizes()[s]`` vectors of a subdomain).
 
@@ -235,7 +235,6 @@ class LRBMSReductor3D:
         self.d, self._torch = d, torch
         eng = d.engine
         self.euclidean = products == 'euclidean'
-        self._V, self._nloc = None, None
         if order is None and bases is None:
             order = 0                                                    # reductor.py:23-24
         if bases is not None:
@@ -261,12 +260,6 @@ class LRBMSReductor3D:
         """The basis slab [S (or S_ext), n, N_max] (device); columns >= local_sizes()[s] of subdomain s are zero."""
         return self._V
 
-    def basis_size(self):
-        return 0 if self._V is None else int(self._V.shape[2])
-
-    def local_sizes(self):
-        return [] if self._nloc is None else [int(v) for v in self._nloc[:self.d.engine.S]]
-
     def _product_apply(self, X):
         eng = self.d.engine
         if self.euclidean:
@@ -279,50 +272,10 @@ class LRBMSReductor3D:
         V = self._V[:self.d.engine.S].contiguous()
         return self._torch.einsum('snk,snl->skl', V, self._product_apply(V))
 
-    def _orthonormalize(self, v, atol=1e-13, rtol=1e-10):
-        """Gram-Schmidt with one re-orthogonalisation of the single-column slab ``v`` [S, n, 1] against the local bases; returns the
-        normalised slab and the mask of subdomains whose block was NOT (numerically) in the span of their basis."""
-        torch = self._torch
-        S = self.d.engine.S
-        V = self._V[:S] if self._V is not None and self._V.shape[2] > 0 else None
-        v = v.clone()
-        norm0 = torch.sqrt(torch.clamp((v * self._product_apply(v)).sum(dim=(1, 2)), min=0.0))
-        for _ in range(2):
-            if V is not None:
-                coef = torch.einsum('snk,snl->skl', V, self._product_apply(v))
-                v = v - torch.einsum('snk,skl->snl', V, coef)
-        norm = torch.sqrt(torch.clamp((v * self._product_apply(v)).sum(dim=(1, 2)), min=0.0))
-        ok = (norm > atol) & (norm > rtol * norm0)
-        v = torch.where(ok[:, None, None], v / torch.where(ok, norm, torch.ones_like(norm))[:, None, None], torch.zeros_like(v))
-        return v, ok
-
-    def _append(self, v, ok):
-        torch = self._torch
-        eng = self.d.engine
-        ok_host = ok.cpu().numpy().astype(bool)
-        if self._V is None:
-            self._V = eng.ctx.zeros(eng.S, eng.t.n, 0)
-            self._nloc = np.zeros(eng.S, dtype=np.int64)
-        if self._V.shape[0] != eng.S:
+    def _append_columns(self, v, ok):
+        if self._V is not None and self._V.shape[0] != self.d.engine.S:
             raise NotImplementedError('extending bases that carry their halo: extend the local slab and exchange afterwards')
-        idx = np.where(ok_host)[0]
-        if len(idx) == 0:
-            return ok_host
-        if int(self._nloc[idx].max()) + 1 > self._V.shape[2]:
-            self._V = torch.cat([self._V, eng.ctx.zeros(eng.S, eng.t.n, 1)], dim=2).contiguous()
-        rows = torch.as_tensor(idx, device=self._V.device)
-        cols = torch.as_tensor(self._nloc[idx], device=self._V.device)
-        self._V[rows, :, cols] = v[rows, :, 0]
-        self._nloc[idx] += 1
-        return ok_host
-
-    def _gram_schmidt_extend(self, U):
-        """Extend EVERY local basis by the columns of U [S, n, L], one after the other (all-or-nothing per column)."""
-        for k in range(U.shape[2]):
-            v, ok = self._orthonormalize(U[:, :, k:k + 1])
-            if not bool(ok.all()):
-                raise ExtensionError3D('snapshot block is (numerically) in the span of its local basis')
-            self._append(v, ok)
+        return super()._append_columns(v, ok)
 
     def _as_slab(self, U):
         eng = self.d.engine
@@ -331,11 +284,6 @@ class LRBMSReductor3D:
             U = U[:, :, None]
         assert tuple(U.shape[:2]) == (eng.S, eng.t.n), 'a block DG function [S, n] or [S, n, L]'
         return U.contiguous()
-
-    def extend_basis(self, U):
-        """Restrict the block DG function(s) ``U`` [S, n] / [S, n, L] (e.g. ``d.solve(mu)``) to every subdomain and extend all
-        local bases (the fork's ``extend_basis``; online_adaptive_lrbms.py:117-121)."""
-        self._gram_schmidt_extend(self._as_slab(U))
 
     def extend_basis_local(self, subdomain, U):
         """Extend the basis of ONE subdomain by the vector(s) ``U`` [n] / [n, L] (reductor.py:31,78)."""
@@ -350,8 +298,8 @@ class LRBMSReductor3D:
             full[i, :, 0] = U[:, k]
             v, ok = self._orthonormalize(full)
             if not bool(ok[i]):
-                raise ExtensionError3D('local vector is (numerically) in the span of the local basis')
-            self._append(v, ok & mask)
+                raise ExtensionError('local vector is (numerically) in the span of the local basis')
+            self._append_columns(v, ok & mask)
 
     def enrich_local(self, subdomain, U, mu=None):
         raise NotImplementedError('online enrichment (reductor.py:75-78: neighbourhood corrector solves) is built for the 2D path only')

@@ -18,10 +18,10 @@ Not built (``NotImplementedError``): the elliptic-reconstruction terms (the refe
 estimators.py:64), sharded discretizations (``S_ext != S``) and ``enrich_local``."""
 import numpy as np
 
-from pylrbms_amd.discretize_elliptic_block_swipdg_3d import (BlockDiscretization3D, ExtensionError3D, LRBMSReductor3D,
-                                                             ReducedDiscretization3D)
+from pylrbms_amd.discretize_elliptic_block_swipdg_3d import BlockDiscretization3D, LRBMSReductor3D, ReducedDiscretization3D
 from pylrbms_amd.discretize_parabolic_block_swipdg import ImplicitEulerTimeStepper
 from pylrbms_amd.parameters import CubicParameterSpace
+from pylrbms_amd.reductor import LocalBasisSlab
 
 
 def _parabolic_estimate(d, mu, dt, eta_loc, time_residual2, time_deriv_nc2):
@@ -130,19 +130,10 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
 class ParabolicLRBMSReductor3D(LRBMSReductor3D):
     """``ParabolicLRBMSReductor`` (2D: pylrbms_amd.reductor) for the 3D path.  ``extend_basis`` takes a trajectory [S, n, L]: its
     vectors are Gram-Schmidt-ed into the local bases one after the other, a vector that is numerically in the span of a local basis
-    is skipped for that subdomain, ``ExtensionError3D`` if nothing was added anywhere; ``reduce()`` returns the instationary reduced
+    is skipped for that subdomain, ``ExtensionError`` if nothing was added anywhere; ``reduce()`` returns the instationary reduced
     model; ``reconstruct(u)`` maps u [nt + 1, S, N] to [S, n, nt + 1]."""
 
-    def extend_basis(self, U, max_vectors=None):
-        U = self._as_slab(U)
-        added = 0
-        for k in range(U.shape[2]):
-            if max_vectors is not None and self.basis_size() >= max_vectors:
-                break
-            v, ok = self._orthonormalize(U[:, :, k:k + 1])
-            added += int(self._append(v, ok).sum())
-        if added == 0:
-            raise ExtensionError3D('no snapshot block extends its local basis')
+    extend_basis = LocalBasisSlab._extend_basis_trajectory
 
     def enrich_local(self, subdomain, U, mu=None):
         raise NotImplementedError('online enrichment is not built for the parabolic 3D path')

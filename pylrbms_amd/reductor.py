@@ -31,6 +31,95 @@ class ExtensionError(Exception):
     """pymor.core.exceptions.ExtensionError (caught at online_adaptive_lrbms.py:116-119)."""
 
 
+class LocalBasisSlab:
+    """The local bases of a reductor as ONE device slab ``_V`` [S, n, N_max] with ``_nloc[s]`` vectors in subdomain s (zero
+    columns behind them), extended by Gram-Schmidt in a local product.  Shared by the 2D and the 3D reductors; a subclass supplies
+    the product (``_product_apply``) and the conversion of a snapshot to a slab [S, n, L] (``_as_slab``).  Rows past S of a
+    ready-made slab are a halo: they take no part in the Gram-Schmidt."""
+
+    _V = None                           # [S, n, N_max] device tensor
+    _nloc = None                        # [S] host int array: number of basis vectors per local subdomain
+
+    def _product_apply(self, X):
+        raise NotImplementedError
+
+    def _as_slab(self, U):
+        raise NotImplementedError
+
+    def basis_size(self):
+        """N_max: the width of the basis slab (== every local basis size while the bases are uniform)."""
+        return 0 if self._V is None else int(self._V.shape[2])
+
+    def local_sizes(self):
+        """``[len(rb) for rb in reductor.bases]`` of online_enrichment.py:80."""
+        return [] if self._nloc is None else [int(v) for v in self._nloc[:self.d.engine.S]]
+
+    def _orthonormalize(self, v, atol=1e-13, rtol=1e-10):
+        """Gram-Schmidt (one re-orthogonalisation) of the single-column slab ``v`` [S, n, 1] against the local bases in
+        the product.  Returns the normalised slab and the per-subdomain mask of blocks that were NOT
+        (numerically) in the span of their basis."""
+        import torch
+        V = self._V[:self.d.engine.S] if self._V is not None and self._V.shape[2] > 0 else None
+        v = v.clone()
+        norm0 = torch.sqrt(torch.clamp((v * self._product_apply(v)).sum(dim=(1, 2)), min=0.0))
+        for _ in range(2):
+            if V is not None:
+                coef = torch.einsum('snk,snl->skl', V, self._product_apply(v))     # zero-padded columns give 0
+                v = v - torch.einsum('snk,skl->snl', V, coef)
+        norm = torch.sqrt(torch.clamp((v * self._product_apply(v)).sum(dim=(1, 2)), min=0.0))
+        ok = (norm > atol) & (norm > rtol * norm0)
+        v = torch.where(ok[:, None, None], v / torch.where(ok, norm, torch.ones_like(norm))[:, None, None],
+                        torch.zeros_like(v))
+        return v, ok
+
+    def _append_columns(self, v, ok):
+        """Write block s of ``v`` behind the ``nloc[s]`` vectors of subdomain s for every s with ``ok[s]``; returns ``ok`` on
+        the host."""
+        import torch
+        eng = self.d.engine
+        ok_host = ok.cpu().numpy().astype(bool)
+        if self._V is None:
+            self._V = eng.ctx.zeros(eng.S, eng.t.n, 0)
+            self._nloc = np.zeros(eng.S, dtype=np.int64)
+        idx = np.where(ok_host)[0]
+        if len(idx) == 0:
+            return ok_host
+        if int(self._nloc[idx].max()) + 1 > self._V.shape[2]:
+            self._V = torch.cat([self._V, eng.ctx.zeros(eng.S, eng.t.n, 1)], dim=2).contiguous()
+        rows = torch.as_tensor(idx, device=self._V.device)
+        cols = torch.as_tensor(self._nloc[idx], device=self._V.device)
+        self._V[rows, :, cols] = v[rows, :, 0]
+        self._nloc[idx] += 1
+        return ok_host
+
+    def _gram_schmidt_extend(self, U):
+        """Extend EVERY local basis by the columns of U [S, n, L], one after the other (all-or-nothing per column)."""
+        for k in range(U.shape[2]):
+            v, ok = self._orthonormalize(U[:, :, k:k + 1])
+            if not bool(ok.all()):
+                raise ExtensionError('snapshot block is (numerically) in the span of its local basis')
+            self._append_columns(v, ok)
+
+    def extend_basis(self, U):
+        """Restrict a global snapshot to every subdomain and extend all local bases (the fork's ``extend_basis``;
+        online_adaptive_lrbms.py:117-121); all-or-nothing: ``ExtensionError`` if a block is in the span of its basis."""
+        self._gram_schmidt_extend(self._as_slab(U))
+
+    def _extend_basis_trajectory(self, U, max_vectors=None):
+        """``extend_basis`` of the parabolic reductors: the vectors of a trajectory are Gram-Schmidt-ed into the local bases one
+        after the other, a vector that is numerically in the span of a local basis is skipped for that subdomain (pyMOR
+        ``gram_schmidt`` semantics), at most until the slab is ``max_vectors`` wide; ``ExtensionError`` if nothing was added."""
+        U = self._as_slab(U)
+        added = 0
+        for k in range(U.shape[2]):
+            if max_vectors is not None and self.basis_size() >= max_vectors:
+                break
+            v, ok = self._orthonormalize(U[:, :, k:k + 1])
+            added += int(self._append_columns(v, ok).sum())
+        if added == 0:
+            raise ExtensionError('no snapshot block extends its local basis')
+
+
 class ReducedDiscretization:
     """``rd``: block-sparse reduced system + projected estimator operators, resident in HBM.
 
@@ -214,7 +303,7 @@ class ReducedDiscretization:
         return self.estimator.estimate(U, self.parse_parameter(mu), self, decompose=decompose)
 
 
-class LRBMSReductor:
+class LRBMSReductor(LocalBasisSlab):
 
     def __init__(self, d, bases=None, products=None, order=None, num_cpus=1, solver_options=None):
         assert order is None or 0 <= order <= 1
@@ -223,8 +312,6 @@ class LRBMSReductor:
         self.products = products            # the local energy products; applied through the engine's P_diag
         self.num_cpus = num_cpus            # accepted and ignored, as in the reference (reductor.py:19)
         eng = d.engine
-        self._V = None                      # [S, n, N_max] device tensor
-        self._nloc = None                   # [S] host int array: number of basis vectors per local subdomain
         if bases is not None:
             self._V = self._bases_to_tensor(bases)
             self._nloc = self._nloc_in
@@ -261,35 +348,12 @@ class LRBMSReductor:
         out.update(getattr(self, '_image_bases', {}))
         return out
 
-    def basis_size(self):
-        """N_max: the width of the basis slab (== every local basis size while the bases are uniform)."""
-        return 0 if self._V is None else int(self._V.shape[2])
-
-    def local_sizes(self):
-        """``[len(rb) for rb in reductor.bases]`` of online_enrichment.py:80."""
-        return [] if self._nloc is None else [int(v) for v in self._nloc]
-
     def _product_apply(self, X):
         """P X with P the local energy product (block-ELL) -- the product handed in at online_adaptive_lrbms.py:107."""
         return self.d.engine.ctx.blockell_apply(self.d.engine.P_diag, X.contiguous())
 
-    def _orthonormalize_against_basis(self, v, atol=1e-13, rtol=1e-10):
-        """Gram-Schmidt (one re-orthogonalisation) of the single-column slab ``v`` [S, n, 1] against the local bases in
-        the energy product.  Returns the normalised slab and the per-subdomain mask of blocks that were NOT
-        (numerically) in the span of their basis."""
-        import torch
-        V = self._V
-        v = v.clone()
-        norm0 = torch.sqrt(torch.clamp((v * self._product_apply(v)).sum(dim=(1, 2)), min=0.0))
-        for _ in range(2):
-            if V is not None:
-                coef = torch.einsum('snk,snl->skl', V, self._product_apply(v))     # zero-padded columns give 0
-                v = v - torch.einsum('snk,skl->snl', V, coef)
-        norm = torch.sqrt(torch.clamp((v * self._product_apply(v)).sum(dim=(1, 2)), min=0.0))
-        ok = (norm > atol) & (norm > rtol * norm0)
-        v = torch.where(ok[:, None, None], v / torch.where(ok, norm, torch.ones_like(norm))[:, None, None],
-                        torch.zeros_like(v))
-        return v, ok
+    def _as_slab(self, U):
+        return U.tensor
 
     def reserve(self, width):
         """Room for local bases of up to ``width`` vectors: pads the slab with zero columns (to an even width: the lean kernels
@@ -302,40 +366,10 @@ class LRBMSReductor:
         return self.basis_size()
 
     def _append_columns(self, v, ok):
-        """Write block s of ``v`` behind the ``nloc[s]`` vectors of subdomain s for every s with ``ok[s]``."""
-        import torch
-        eng = self.d.engine
-        ok_host = ok.cpu().numpy().astype(bool)
-        if self._V is None:
-            self._V = eng.ctx.zeros(eng.S, eng.t.n, 1)
-            self._nloc = np.zeros(eng.S, dtype=np.int64)
-        idx = np.where(ok_host)[0]
-        if len(idx) == 0:
-            return ok_host
-        if int(self._nloc[idx].max()) + 1 > self._V.shape[2]:
-            self._V = torch.cat([self._V, eng.ctx.zeros(eng.S, eng.t.n, 1)], dim=2).contiguous()
-        rows = torch.as_tensor(idx, device=self._V.device)
-        cols = torch.as_tensor(self._nloc[idx], device=self._V.device)
-        self._V[rows, :, cols] = v[rows, :, 0]
-        self._nloc[idx] += 1
-        self._dirty = getattr(self, '_dirty', set()) | {int(eng.local[i]) for i in idx}      # bases changed since the last reduce()
+        ok_host = super()._append_columns(v, ok)
+        local = self.d.engine.local          # _dirty: global ids of the subdomains whose basis changed since the last reduce()
+        self._dirty = getattr(self, '_dirty', set()) | {int(local[i]) for i in np.where(ok_host)[0]}
         return ok_host
-
-    def _gram_schmidt_extend(self, U):
-        """Extend EVERY local basis by the columns of U [S, n, L], one after the other (all-or-nothing per column)."""
-        eng = self.d.engine
-        for k in range(U.shape[2]):
-            if self._V is None:
-                self._V = eng.ctx.zeros(eng.S, eng.t.n, 0)
-                self._nloc = np.zeros(eng.S, dtype=np.int64)
-            v, ok = self._orthonormalize_against_basis(U[:, :, k:k + 1])
-            if not bool(ok.all()):
-                raise ExtensionError('snapshot block is (numerically) in the span of its local basis')
-            self._append_columns(v, ok)
-
-    def extend_basis(self, U):
-        """Restrict a global snapshot to every subdomain and extend all local bases (fork ``extend_basis``)."""
-        self._gram_schmidt_extend(U.tensor)
 
     def extend_basis_local(self, U, _defer=False):
         """Reference reductor.py:31,78: extend the basis of the ONE subdomain the single-block array ``U`` lives on.
@@ -358,7 +392,7 @@ class LRBMSReductor:
         full = eng.ctx.zeros(eng.S, eng.t.n, 1)
         rows = torch.as_tensor(np.asarray(marked, dtype=np.int64), device=full.device)
         full[rows] = vecs
-        v, ok = self._orthonormalize_against_basis(full)
+        v, ok = self._orthonormalize(full)
         mask = torch.zeros(eng.S, dtype=torch.bool, device=full.device)
         mask[rows] = True
         ok_host = self._append_columns(v, ok & mask)
@@ -593,20 +627,7 @@ class ParabolicLRBMSReductor(LRBMSReductor):
     of a local basis are skipped for that subdomain (pyMOR ``gram_schmidt`` semantics), ``ExtensionError`` if nothing
     was added anywhere; ``reduce()`` returns the instationary reduced model."""
 
-    def extend_basis(self, U, max_vectors=None):
-        eng = self.d.engine
-        t = U.tensor
-        added = 0
-        for k in range(t.shape[2]):
-            if max_vectors is not None and self.basis_size() >= max_vectors:
-                break
-            if self._V is None:
-                self._V = eng.ctx.zeros(eng.S, eng.t.n, 0)
-                self._nloc = np.zeros(eng.S, dtype=np.int64)
-            v, ok = self._orthonormalize_against_basis(t[:, :, k:k + 1])
-            added += int(self._append_columns(v, ok).sum())
-        if added == 0:
-            raise ExtensionError('no snapshot block extends its local basis')
+    extend_basis = LocalBasisSlab._extend_basis_trajectory
 
     def _reduce(self, touched=None):
         rd = super()._reduce(touched=touched)
