@@ -2640,15 +2640,31 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
       }
     };
     auto bop = [&](const Set& x, int ks, int ct) { return ct < 2 * NPAIR ? x.Bp[ks][ct >> 1][ct & 1] : x.Bs[ks]; };
-    auto stage = [&](int c, Set& cur, const Sc& sc_cur, Sc& sc_nxt) {
+    auto touch_sc = [](const Sc& x) {
+#pragma unroll
+      for (int f = 0; f < 3; ++f) asm volatile("" ::"s"(x.nb[f]) : "memory");
+#pragma unroll
+      for (int pr = 0; pr < NP; ++pr) asm volatile("" ::"s"(x.cc[pr]) : "memory");
+    };
+    // stage c: `sc_cur` holds the scalars of chunk c, `sc_nxt` those of chunk c + 1 (requested in stage c - 1); `sc_cur` then
+    // receives those of chunk c + 2.  The scalars are requested a whole chunk ahead and touched first thing after the barrier,
+    // where lgkmcnt is already 0: hipcc does not see the wait inside lds_barrier(), and its own wait at the first use otherwise
+    // fell behind this stage's LDS stores and scalar requests (one scalar round trip and a store drain per stage).
+    auto stage = [&](int c, Set& cur, Sc& sc_cur, const Sc& sc_nxt) {
       const int T = T0 + c * EC + e;
       const bool more = c + 1 < nchunks;
       double* Xb = Xs + (c & 1) * 3 * EC * LDX;
       double* Zb = Zs + (c & 1) * 2 * EC * LDX;
       double* Yb = Ys + (c & 1) * 3 * EC * LDY;
-      load_sc(more ? T + EC : T, sc_nxt);
+      if (e == 0) F1_STAMP(0, c, 0);
+      touch_sc(sc_nxt);
+      double cc[NP];
+#pragma unroll
+      for (int pr = 0; pr < NP; ++pr) cc[pr] = sc_cur.cc[pr];
+      load_sc(c + 2 < nchunks ? T + 2 * EC : T, sc_cur);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       tie_set(cur);
+      if (e == 0) F1_STAMP(0, c, 1);
       d4 D[NTX];
 #pragma unroll
       for (int ct = 0; ct < NTX; ++ct) D[ct] = (d4){0.0, 0.0, 0.0, 0.0};
@@ -2670,24 +2686,29 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
 #pragma unroll
         for (int pr = 0; pr < NP; ++pr)
 #pragma unroll
-          for (int ct = 0; ct < NTX; ++ct) Yb[koff[pr][ct]] = sc_cur.cc[pr] * D[ct][RRZ];
+          for (int ct = 0; ct < NTX; ++ct) Yb[koff[pr][ct]] = cc[pr] * D[ct][RRZ];
       }
 #pragma unroll
       for (int ct = 0; ct < NTX; ++ct) rhs_part[ct] += D[ct][RRZ];      // meaningful on the lanes kq == KQB
+      if (e == 0) F1_STAMP(0, c, 2);
       if (more) {
 #pragma unroll
         for (int ks = 0; ks < 3; ++ks) ap[ks] = (const double*)((const char*)ap[ks] + ainc);
         load_set(T + EC, sc_nxt, cur);
       }
+      if (e == 0) F1_STAMP(0, c, 3);
     };
     Set s0;
     Sc c0, c1;
     load_sc(T0 + e, c0);
+    load_sc(nchunks > 1 ? T0 + EC + e : T0 + e, c1);
     load_set(T0 + e, c0, s0);
-    auto round = [&](int c, Sc& x0, Sc& x1) {
+    auto round = [&](int c, Sc& x0, const Sc& x1) {
       stage(c, s0, x0, x1);
       lds_barrier();
+      if (e == 0) F1_STAMP(0, c, 4);
       mfma_phase(c, F1wV<0>{});                  // (role A's tiles are the same for every SIMD)
+      if (e == 0) F1_STAMP(0, c, 5);
     };
     for (int c = 0; c < nchunks; c += 2) {
       round(c, c0, c1);
@@ -2754,13 +2775,19 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
       }
     };
     auto bop = [&](const Set& x, int q2, int ct) { return ct < 2 * NPAIR ? x.Bp[q2][ct >> 1][ct & 1] : x.Bs[q2]; };
-    auto stage = [&](int c, Set& cur, Sc& sc_nxt) {
+    // stage c: `sc_nxt` holds the scalars of chunk c + 1 (requested in stage c - 1), `sc_far` receives those of chunk c + 2
+    // (touched first, as in role A)
+    auto stage = [&](int c, Set& cur, const Sc& sc_nxt, Sc& sc_far) {
       const int T = T0 + c * EC + e;
       const bool more = c + 1 < nchunks;
       double* Yb = Ys + (c & 1) * 3 * EC * LDY;
-      load_sc(more ? T + EC : T, sc_nxt);
+      if (e == 0) F1_STAMP(1, c, 0);
+#pragma unroll
+      for (int f = 0; f < 3; ++f) asm volatile("" ::"s"(sc_nxt.rt[f]) : "memory");
+      load_sc(c + 2 < nchunks ? T + 2 * EC : T, sc_far);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       tie_set(cur);
+      if (e == 0) F1_STAMP(1, c, 1);
 #pragma unroll
       for (int q2 = 0; q2 < QP; ++q2) {
         d4 D[NTX];
@@ -2770,10 +2797,12 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
 #pragma unroll
         for (int ct = 0; ct < NTX; ++ct) Yb[yo[q2][ct]] = D[ct][0];
       }
+      if (e == 0) F1_STAMP(1, c, 2);
       if (more) {
         ap += 6 * EC;
         load_set(sc_nxt, cur);
       }
+      if (e == 0) F1_STAMP(1, c, 3);
     };
     // One staging loop per tile plan (SIMDs 0, 1 / 2, 3), each with its OWN prologue behind the wave-uniform branch: with the
     // prologue's asm-managed loads live across the branch, hipcc moved the set's registers on the out-of-line side before the first
@@ -2781,13 +2810,20 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
     // contributions to G_ab were missing; the ISA guard walks the loops, not the prologue).  (Both plans in ONE loop: 101 spilled VGPRs.)
     auto run = [&](auto vtag) {
       Set s0;
-      Sc c0;
+      Sc c0, c1;
       load_sc(T0 + e, c0);
       load_set(c0, s0);
-      for (int c = 0; c < nchunks; ++c) {
-        stage(c, s0, c0);
+      load_sc(nchunks > 1 ? T0 + EC + e : T0 + e, c0);       // scalars of chunk 1 (used by stage 0), then alternating
+      auto round = [&](int c, const Sc& x0, Sc& x1) {
+        stage(c, s0, x0, x1);
         lds_barrier();
+        if (e == 0) F1_STAMP(1, c, 4);
         mfma_phase(c, vtag);
+        if (e == 0) F1_STAMP(1, c, 5);
+      };
+      for (int c = 0; c < nchunks; c += 2) {                 // nT is a multiple of 8, so nchunks is even
+        round(c, c0, c1);
+        round(c + 1, c1, c0);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       tie_set(s0);

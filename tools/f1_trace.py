@@ -1,4 +1,4 @@
-"""Cycle stamps of k_f1 (experiment build -DF1_TRACE: tools/build_variant.sh trace -DF1_TRACE): where a chunk's time goes
+"""Cycle stamps of k_f1 / k_f1u / k_f1v / k_f1w, whichever the config runs (experiment build -DF1_TRACE: tools/build_variant.sh trace -DF1_TRACE): where a chunk's time goes
 in producer wave 0 and consumer wave 4 of workgroup 0.  usage (GPU box): LRBMS_HIP_LIB=.../_variants/trace.so python tools/f1_trace.py"""
 import ctypes
 import os
