@@ -203,8 +203,9 @@ int lrbms_fused_supported(lrbms_ctx* ctx, int32_t Q, int32_t N);
 /* Row length (doubles) of F_nc [S][4][nvs][.]: 2 N + 4 nvs, plus N with LRBMS_OPT_OSWALD_VERTEX_PATCH (the diagonal subdomain's
  * share of the vertex average at the two corner vertices a side carries: A_a | C_a | M_a0 .. M_a3 | A_diag). */
 int32_t lrbms_fused_fnc_ld(lrbms_ctx* ctx, int32_t N);
-/* v_mfma_f64_16x16x4_f64 instructions (2 048 flops each, padding included) the dense projection kernel of the fused pass
- * executes per subdomain for this shape under the context's launch options (measurement only: roofline of bench.py). */
+/* MFMA work in units of 2 048 flop (one v_mfma_f64_16x16x4_f64, padding included; a v_mfma_f64_4x4x4_4b_f64 counts a quarter)
+ * the dense projection kernel of the fused pass executes per subdomain for this shape under the context's launch options
+ * (measurement only: roofline of bench.py). */
 int64_t lrbms_fused_mfma_per_subdomain(lrbms_ctx* ctx, int32_t Q, int32_t N);
 int lrbms_fused_factored_supported(lrbms_ctx* ctx, int32_t Q, int32_t N);
 int64_t lrbms_fused_work_size(lrbms_ctx* ctx, int32_t Q, int32_t N);

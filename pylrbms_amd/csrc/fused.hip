@@ -2442,7 +2442,7 @@ __global__ __launch_bounds__(512, 2) void k_f1v(Tmpl t, F1Args a, GrpTable gt) {
 //     the matrix pipe with the system rows, is stored once as the second X operand (Zs) and, times c^{qq'}, as the Y rows of the
 //     three G_aa groups;
 //   * role B multiplies W'^q_T (2 x 3 per component; k_prep_lds forms it from A_ab with the template table t.hab) with the three
-//     flux rows: four A-operand rows, one accumulator register;
+//     flux rows: four output rows, on the 4x4x4 MFMA (five instructions cover the 2 N columns of an element's flux rows);
 //   * the column tiles come in two kinds (3 or 2 K rows per element) and three classes (row tiles needed); which SIMD owns which
 //     is a compile-time plan (F1wPlan) that balances the MFMA count: 38 / 38 / 37 / 37 per chunk and SIMD.
 struct F1wPlan {
@@ -2725,26 +2725,45 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
     }
   } else {
     // ------------------------------------------------------------- role B: Y^{q,q2} = W'^q_T R_T^{q2}, two rows per element
+    // The product is 4 rows (q, d) x 3 flux rows x 2 N columns: it runs on v_mfma_f64_4x4x4_4b_f64 (four independent 4 x 4 x 4 blocks,
+    // one double per lane for each of A, B and D; 16 cycles against the 64 of a 16x16x4, tools/ubench/mfma64_shapes.hip).  Lane map
+    // (measured with unit patterns, profiles/r09_ubench_mfma64_shapes.txt); lane = 16 lk + li, li = 4 block + (i or j):
+    //   A[block][i][k]: lane 16 k + 4 block + i     B[block][k][j]: lane 16 k + 4 block + j     D[block][i][j]: lane 16 i + 4 block + j
+    // With A replicated over the blocks (lane (lk, li) holds W'[(q, d) = li & 3][k = lk]) one instruction is a 4 x 3 times 3 x 16 product:
+    // lane (lk, li) feeds one column of flux row rt[lk] (the lk = 3 lanes meet the zeros of A) and receives Y row (q, d) = lk of the same
+    // column -- the lane that held it in accumulator register 0 of the 16x16x4 form.  The 2 N <= 80 columns of a flux row are one
+    // contiguous range (a row of R_self is [q2][N]): five instructions per element instead of 2 x 3, q2 = column / N is a lane constant.
+    // Instructions 2 pp, 2 pp + 1 take columns 32 pp + 2 li, + 1 (one 16-byte load), instruction 4 column 64 + li.
+    constexpr int NCI = 5, NPB = NCI / 2;
     struct Set {
       double A;
-      d2 Bp[QP][NPAIR];
-      double Bs[QP];
+      d2 Bp[NPB];
+      double Bs;
     };
     const double* Rs = (const double*)(((unsigned long long)__builtin_amdgcn_readfirstlane((int)((unsigned long long)(a.Rself + (long)s * t.nrt * QN) >> 32)) << 32) |
                                        (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long long)(a.Rself + (long)s * t.nrt * QN)));
-    const int r16 = li, kq = lk;
+    const int kq = lk;
     const double* ap = t.zero64;                        // lanes without an entry walk through the zero table with the same stride
-    if (r16 < 2 * QP && kq < 3) ap = Wab + ((long)(r16 >> 1) * S + s) * t.nT * 6 + (r16 & 1) * 3 + kq;
+    if (kq < 3) ap = Wab + ((long)((li & 3) >> 1) * S + s) * t.nT * 6 + (li & 1) * 3 + kq;
     ap += (long)(T0 + e) * 6;
-    unsigned lcp[QP][NPAIR], lcs[QP];
-    int yo[QP][NTX];                                   // LDS offsets of accumulator register 0: row kq = (q, d) = (kq >> 1, kq & 1)
+    unsigned lcp[NPB], lcs;
+    int yo[NCI];                                       // LDS offsets of the instructions' outputs: row kq = (q, d) = (kq >> 1, kq & 1)
+    {
+      // lanes past the last column hold a duplicate of a valid one: same value to the same address
+      int col[NCI];
 #pragma unroll
-    for (int q2 = 0; q2 < QP; ++q2) {
+      for (int pp = 0; pp < NPB; ++pp) {
+        col[2 * pp] = 32 * pp + 2 * li + 1 < QN ? 32 * pp + 2 * li : QN - 2;
+        col[2 * pp + 1] = col[2 * pp] + 1;
+        lcp[pp] = 8u * (unsigned)col[2 * pp];
+      }
+      col[NCI - 1] = 32 * NPB + li < QN ? 32 * NPB + li : QN - 1;
+      lcs = 8u * (unsigned)col[NCI - 1];
 #pragma unroll
-      for (int pp = 0; pp < NPAIR; ++pp) lcp[q2][pp] = 8u * (unsigned)(q2 * N + (32 * pp + 2 * li + 1 < N ? 32 * pp + 2 * li : N - 2));
-      lcs[q2] = 8u * (unsigned)(q2 * N + (16 * (NTX - 1) + li < N ? 16 * (NTX - 1) + li : N - 1));
-#pragma unroll
-      for (int ct = 0; ct < NTX; ++ct) yo[q2][ct] = (2 * e + (kq & 1)) * LDY + pos(QP + 2 + NP + (kq >> 1) * QP + q2, colc(ct));
+      for (int m = 0; m < NCI; ++m) {
+        const int q2 = col[m] >= N ? 1 : 0;
+        yo[m] = (2 * e + (kq & 1)) * LDY + pos(QP + 2 + NP + (kq >> 1) * QP + q2, col[m] - q2 * N);
+      }
     }
     const unsigned rsr = 8u * (unsigned)QN;
     const cint_p rtc = (cint_p)t.elem_rt;
@@ -2759,22 +2778,16 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
       const unsigned ro = (unsigned)(kq == 1 ? sc.rt[1] : kq == 2 ? sc.rt[2] : sc.rt[0]) * rsr;
       x.A = gload_f64(ap);
 #pragma unroll
-      for (int q2 = 0; q2 < QP; ++q2) {
-#pragma unroll
-        for (int pp = 0; pp < NPAIR; ++pp) x.Bp[q2][pp] = gload_s128(Rs, ro + lcp[q2][pp]);
-        if (NSING) x.Bs[q2] = gload_s64(Rs, ro + lcs[q2]);
-      }
+      for (int pp = 0; pp < NPB; ++pp) x.Bp[pp] = gload_s128(Rs, ro + lcp[pp]);
+      x.Bs = gload_s64(Rs, ro + lcs);
     };
     auto tie_set = [&](Set& x) {
       tie(x.A);
 #pragma unroll
-      for (int q2 = 0; q2 < QP; ++q2) {
-#pragma unroll
-        for (int pp = 0; pp < NPAIR; ++pp) tie2(x.Bp[q2][pp]);
-        if (NSING) tie(x.Bs[q2]);
-      }
+      for (int pp = 0; pp < NPB; ++pp) tie2(x.Bp[pp]);
+      tie(x.Bs);
     };
-    auto bop = [&](const Set& x, int q2, int ct) { return ct < 2 * NPAIR ? x.Bp[q2][ct >> 1][ct & 1] : x.Bs[q2]; };
+    auto bop = [&](const Set& x, int m) { return m < 2 * NPB ? x.Bp[m >> 1][m & 1] : x.Bs; };
     // stage c: `sc_nxt` holds the scalars of chunk c + 1 (requested in stage c - 1), `sc_far` receives those of chunk c + 2
     // (touched first, as in role A)
     auto stage = [&](int c, Set& cur, const Sc& sc_nxt, Sc& sc_far) {
@@ -2788,15 +2801,11 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       tie_set(cur);
       if (e == 0) F1_STAMP(1, c, 1);
+      double D[NCI];
 #pragma unroll
-      for (int q2 = 0; q2 < QP; ++q2) {
-        d4 D[NTX];
+      for (int m = 0; m < NCI; ++m) D[m] = __builtin_amdgcn_mfma_f64_4x4x4f64(cur.A, bop(cur, m), 0.0, 0, 0, 0);
 #pragma unroll
-        for (int ct = 0; ct < NTX; ++ct)
-          D[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur.A, bop(cur, q2, ct), (d4){0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-#pragma unroll
-        for (int ct = 0; ct < NTX; ++ct) Yb[yo[q2][ct]] = D[ct][0];
-      }
+      for (int m = 0; m < NCI; ++m) Yb[yo[m]] = D[m];
       if (e == 0) F1_STAMP(1, c, 2);
       if (more) {
         ap += 6 * EC;
@@ -4603,8 +4612,9 @@ static bool f1w_layout(std::vector<Grp>& groups, int N, int Q) {
   return s3 == 4 && s2 == 2 && ui == 5 && 16 * 15 + 5 * N <= 16 * 28;
 }
 
-// v_mfma_f64_16x16x4_f64 instructions the dense projection kernel (k_f1v / k_f1u / k_f1, whichever the launcher takes for this
-// shape and these options) executes per subdomain; 0 if the fused pass does not support the shape.  For the roofline of bench.py.
+// MFMA work, in units of 2 048 flop (one v_mfma_f64_16x16x4_f64; a v_mfma_f64_4x4x4_4b_f64 is a quarter), the dense projection kernel
+// (k_f1w / k_f1v / k_f1u / k_f1, whichever the launcher takes for this shape and these options) executes per subdomain; 0 if the fused
+// pass does not support the shape.  For the roofline of bench.py.
 long f1_mfma_per_subdomain(lrbms_ctx* ctx, int Q, int N) {
   const Tmpl& t = ctx->t;
   if (N < 1 || N > 64 || Q < 1 || Q > 4) return 0;
@@ -4621,7 +4631,8 @@ long f1_mfma_per_subdomain(lrbms_ctx* ctx, int Q, int N) {
   const bool unified = (Q == 1 || Q == 2) && one_slice && ntx <= 3 && ctx->opt_f1_legacy != 1;
   int lv[3] = {0, 0, 0};
   if (unified && ctx->opt_f1_legacy == 0 && f1w_usable(ctx, Q, N) && f1w_layout(groups, N, Q))
-    return (long)nch * 150 + (long)t.nT * (3 * ntx + Q * ntx);      // k_f1w: 18 tile rows x 3 + 48 x 2 k-steps per chunk; the two applies
+    return (long)nch * 150 + (long)t.nT * 3 * ntx + (long)t.nT * 5 / 4;      // k_f1w: 18 tile rows x 3 + 48 x 2 k-steps per chunk; role A's apply;
+                                                                              // role B's: five 4x4x4_4b (512 flop: a quarter unit) per element
   if (unified && ctx->opt_f1_legacy != 2 && N % 2 == 0 && N >= 2 && f1v_layout(groups, N, ntx, lv) && f1v_instantiated(ntx, Q, lv))
     return (long)nch * 3 * 4 * (lv[0] + 2 * lv[1] + 3 * lv[2]) + (long)t.nT * (3 * ntx + Q * ntx);      // projection + the two applies
   const int tiles = (ng * N + 15) / 16;                         // k_f1u skips the column tiles beyond the last column
