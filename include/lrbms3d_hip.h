@@ -275,6 +275,61 @@ int64_t lrbms3_reduced_time_residual_work_size(lrbms3_ctx* ctx, int32_t N);
 int lrbms3_reduced_time_residual(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t L, const double* theta, const double* B_sys,
                                  const double* M_red, const double* dU, double* work, double* out, void* stream);
 
+/* -- affine sources: f(mu) = sum_j phi_j(mu) f_j on the stationary path, f(t, mu) = sum_j phi_j(t, mu) f_j on the parabolic one ------
+ * The 3D counterparts of the two source blocks of include/lrbms_hip.h, K components, 1 <= K <= 64.  The host
+ * evaluates the coefficients phi; the library never evaluates an expression.  Per component j, lrbms3_assemble_rhs on its samples
+ * gives the load vector and the element integrals: b_K [K][S][n], bdiv_K [K][S][n_T] (its f2 and ceps outputs are not needed).
+ * Every export that reads the mesh needs S_ext == S (LRBMS_E_INVALID otherwise); lrbms3_combine_sources is a plain vector
+ * operation and needs no mesh.  LRBMS_E_INVALID also for K outside [1, 64] and for a null argument.
+ *
+ *   lrbms3_assemble_source_gram     f_smp_K [K][S][n_T][f_stride] (K sample tables as for lrbms3_assemble_rhs) ->
+ *                                   F2 [S][K][K] = (f_j, f_l)_{L2(Omega_s)}: per element the expression, and per subdomain the
+ *                                   reduction order, of the f2 of lrbms3_assemble_rhs; K = 1: that f2 bit for bit.
+ *   lrbms3_project_sources          for the basis V [S][n][N] (N <= 64, Q N <= 64) and R_self [S][n_rt][QN], the RT0 flux image of
+ *                                   the SAME V: the first S n_rt Q N doubles of the work buffer of a finished
+ *                                   lrbms3_project_estimate pass on V (offset 0; the pass leaves it there, read only here):
+ *                                     rhs_red_K [K][S][N]  = V_s^T b_K[j][s]
+ *                                     r_fd_K    [K][S][QN] = sum_e bdiv_K[j][s][e] div(R_self)_e
+ *                                   K = 1 with the discretization's b / bdiv: the pass's rhs_red and r_fd (other summation order).
+ *                                   One launch on the fp64 matrix cores; V and R_self are read once, whatever K.
+ *   lrbms3_reduced_source_terms     L >= 1 columns u [S][N][L] (column fastest), each with its own theta [L][Q] and phi [L][K]
+ *                                   (both DEVICE arrays: one launch serves any number of parameters or time steps):
+ *                                     out [S][L] = (phi_l^T F2_s phi_l - 2 sum_j phi_lj (r_fd_K[j][s]^T ur_l + sum_e bdiv_K[j][s][e] div zf_{l,e}))
+ *                                                  (1/pi^2) / ceps[s] hdiam^2
+ *                                   with ur, zf = Rb ur_a and the side elements of lrbms3_reduced_estimate (Rb [S][nbf][QN] of the
+ *                                   pass).  Added to the r row of lrbms3_reduced_estimate_batch run with f2 = 0, r_fd = 0 and
+ *                                   bdiv = 0 it gives the residual indicator of f = sum_j phi_lj f_j (the indicator is affine in
+ *                                   (f2, r_fd, bdiv)).  N <= 64, Q <= 8.
+ *   lrbms3_reduced_solve_batch_src  lrbms3_reduced_solve_batch where column m solves against sum_j phi[m][j] rhs_red_K[j]:
+ *                                   theta [nmu][Q] host, phi [nmu][K] host, rhs_red_K [K][S][N], u [S][N][nmu].  Work size
+ *                                   lrbms3_reduced_solve_batch_work_size(N, nmu); same limits (N <= 32, nmu <= 64, groups of 16),
+ *                                   preconditioner handling (lrbms3_reduced_precond_use), info and error codes; only the start
+ *                                   kernel differs.  K = 1, phi = 1: the bits of lrbms3_reduced_solve_batch.  A column whose
+ *                                   right-hand side is exactly zero comes back as zeros.
+ *   lrbms3_combine_sources          y [M] = sum_j phi[j] x_K[j] for x_K [K][M] (device), phi [K] host; the sum is spelled out with
+ *                                   fma from the first product (the order of lrbms3_reduced_solve_batch_src; the kernel of
+ *                                   lrbms_combine_sources).  Forms b(mu) (M = S n), rhs_red(mu) (M = S N), bdiv(mu) (M = S n_T).
+ *   lrbms3_fom_implicit_euler_src   lrbms3_fom_implicit_euler with the step right-hand side M u_k + dt sum_j phi[k+1][j] b_K[j];
+ *                                   phi [nt+1][K] device (row k: the time of step k).  Same work size, info and errors.
+ *   lrbms3_reduced_implicit_euler_src  lrbms3_reduced_implicit_euler with M_red u_k + dt sum_j phi[k+1][j] rhs_red_K[j].  N <= 64.
+ *                                   Both: K = 1, phi = 1 gives the bits of the export without _src. */
+int lrbms3_assemble_source_gram(lrbms3_ctx* ctx, int32_t K, const double* f_smp_K, double* F2, void* stream);
+int lrbms3_project_sources(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, const double* b_K, const double* bdiv_K, const double* V,
+                           const double* R_self, double* rhs_red_K, double* r_fd_K, void* stream);
+int lrbms3_reduced_source_terms(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t L, const double* theta, const double* phi,
+                                const double* F2, const double* r_fd_K, const double* bdiv_K, const double* Rb, const double* u,
+                                const double* ceps, double hdiam, double* out, void* stream);
+int lrbms3_reduced_solve_batch_src(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta,
+                                   const double* phi, const double* B_sys, const double* rhs_red_K, double* work, double* u,
+                                   double rtol, int32_t max_iter, double* info, void* stream);
+int lrbms3_combine_sources(lrbms3_ctx* ctx, int32_t K, int64_t M, const double* phi, const double* x_K, double* y, void* stream);
+int lrbms3_fom_implicit_euler_src(lrbms3_ctx* ctx, int32_t Q, int32_t K, const double* theta, double dt, int32_t nt,
+                                  const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                  double* U, double rtol, int32_t max_iter, double* info, void* stream);
+int lrbms3_reduced_implicit_euler_src(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, const double* theta, double dt, int32_t nt,
+                                      const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
+                                      double* work, double* U, double rtol, int32_t max_iter, double* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,17 @@ SIGNATURES3 = {
                                                      c_i32, _P_DBL, c_vp]),
     'lrbms3_reduced_time_residual_work_size': (c_i64, [c_vp, c_i32]),
     'lrbms3_reduced_time_residual': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # affine sources
+    'lrbms3_assemble_source_gram': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'lrbms3_project_sources': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 7),
+    'lrbms3_reduced_source_terms': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_vp] * 8 + [c_dbl, c_vp, c_vp]),
+    'lrbms3_reduced_solve_batch_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32,
+                                                      _P_DBL, c_vp]),
+    'lrbms3_combine_sources': (ctypes.c_int, [c_vp, c_i32, c_i64, _P_DBL, c_vp, c_vp, c_vp]),
+    'lrbms3_fom_implicit_euler_src': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
+                                                     c_i32, _P_DBL, c_vp]),
+    'lrbms3_reduced_implicit_euler_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                         c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
 }
 
 _bound = None
@@ -419,3 +430,126 @@ class Native3DContext(_native.ContextBase):
                                                    self._stream())
         self._check(rc, 'lrbms3_reduced_time_residual')
         return out
+
+    # ------------------------------------------------------------------ affine sources
+    def _dev2(self, a, shape, name):
+        """A host or device table as a contiguous device tensor of the given shape."""
+        a = a if isinstance(a, self.torch.Tensor) else self.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+        a = a.contiguous()
+        self._ptr(a, shape, name)
+        return a
+
+    def assemble_source_gram(self, f_smp_K):
+        """f_smp_K [K, S, n_T, f_stride] -> F2 [S, K, K] = (f_j, f_l)_{L2(Omega_s)}."""
+        K = int(f_smp_K.shape[0])
+        F2 = self.empty(self.S, K, K)
+        rc = self.lib.lrbms3_assemble_source_gram(self.handle, K, self._ptr(f_smp_K, (K, self.S, self.n_T, self.spec.f_stride), 'f_smp_K'),
+                                                  c_vp(F2.data_ptr()), self._stream())
+        self._check(rc, 'lrbms3_assemble_source_gram')
+        return F2
+
+    def project_sources(self, Q, b_K, bdiv_K, V, work):
+        """rhs_red_K [K, S, N] = V_s^T b_K[j, s] and r_fd_K [K, S, QN] = sum_e bdiv_K[j, s, e] div(R_self)_e; ``work`` is the work
+        buffer of a finished ``project_estimate`` pass on the same ``V`` (its flux image R_self lies at offset 0)."""
+        K, N, S = int(b_K.shape[0]), int(V.shape[2]), self.S
+        if work.numel() < S * self.n_rt * Q * N:
+            raise NativeError('work: not the work buffer of a pass with this Q and N')
+        rhs_K, rfd_K = self.empty(K, S, N), self.empty(K, S, Q * N)
+        rc = self.lib.lrbms3_project_sources(self.handle, Q, N, K, self._ptr(b_K, (K, S, self.n), 'b_K'),
+                                             self._ptr(bdiv_K, (K, S, self.n_T), 'bdiv_K'), self._ptr(V, (self.S_ext, self.n, N), 'V'),
+                                             c_vp(work.data_ptr()), c_vp(rhs_K.data_ptr()), c_vp(rfd_K.data_ptr()), self._stream())
+        self._check(rc, 'lrbms3_project_sources')
+        return rhs_K, rfd_K
+
+    def reduced_source_terms(self, Q, thetas, phi, F2, r_fd_K, bdiv_K, Rb, u, ceps, hdiam):
+        """The f terms of the residual indicator for the L columns u [S, N, L] with their own thetas [L, Q] and phi [L, K] (host
+        or device): [S, L], to be added to the r row of ``reduced_estimate_batch`` run with f2 = 0, r_fd = 0 and bdiv = 0."""
+        S, N, L, K = self.S, int(u.shape[1]), int(u.shape[2]), int(F2.shape[1])
+        th, ph = self._dev2(thetas, (L, Q), 'theta'), self._dev2(phi, (L, K), 'phi')
+        out = self.empty(S, L)
+        rc = self.lib.lrbms3_reduced_source_terms(self.handle, Q, N, K, L, c_vp(th.data_ptr()), c_vp(ph.data_ptr()),
+                                                  self._ptr(F2, (S, K, K), 'F2'), self._ptr(r_fd_K, (K, S, Q * N), 'r_fd_K'),
+                                                  self._ptr(bdiv_K, (K, S, self.n_T), 'bdiv_K'), self._ptr(Rb, (S, self.nbf, Q * N), 'Rb'),
+                                                  self._ptr(u, (S, N, L), 'u'), self._ptr(ceps, (S,), 'ceps'), float(hdiam),
+                                                  c_vp(out.data_ptr()), self._stream())
+        self._check(rc, 'lrbms3_reduced_source_terms')
+        return out
+
+    def reduced_solve_batch_src(self, Q, thetas, phi, B_sys, rhs_red_K, rtol=1e-13, max_iter=5000, work=None):
+        """``reduced_solve_batch`` where column m solves against sum_j phi[m, j] rhs_red_K[j]: thetas [nmu, Q], phi [nmu, K] (host)
+        -> u [S, N, nmu], (iterations, worst relative residual)."""
+        K, N, S = int(rhs_red_K.shape[0]), int(rhs_red_K.shape[2]), self.S
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu = th.shape[0]
+        ph = np.ascontiguousarray(phi, dtype=np.float64)
+        assert th.shape == (nmu, Q) and ph.shape == (nmu, K)
+        if work is None:
+            work = self.empty(int(self.lib.lrbms3_reduced_solve_batch_work_size(self.handle, N, nmu)))
+        u = self.empty(S, N, nmu)
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_reduced_solve_batch_src(self.handle, Q, N, K, nmu, th.ctypes.data_as(_P_DBL), ph.ctypes.data_as(_P_DBL),
+                                                     self._ptr(B_sys, (Q, S, 7, N, N), 'B_sys'),
+                                                     self._ptr(rhs_red_K, (K, S, N), 'rhs_red_K'), c_vp(work.data_ptr()),
+                                                     c_vp(u.data_ptr()), float(rtol), int(max_iter), info, self._stream())
+        self._check(rc, 'lrbms3_reduced_solve_batch_src')
+        return u, (int(info[0]), float(info[1]))
+
+    def combine_sources(self, phi, x_K):
+        """sum_j phi[j] x_K[j] for x_K [K, ...] (device), phi [K] (host): a tensor of shape x_K.shape[1:]."""
+        K = int(x_K.shape[0])
+        ph = np.ascontiguousarray(phi, dtype=np.float64)
+        assert ph.shape == (K,)
+        self._ptr(x_K, tuple(x_K.shape), 'x_K')
+        y = self.empty(*x_K.shape[1:])
+        rc = self.lib.lrbms3_combine_sources(self.handle, K, int(y.numel()), ph.ctypes.data_as(_P_DBL), c_vp(x_K.data_ptr()),
+                                             c_vp(y.data_ptr()), self._stream())
+        self._check(rc, 'lrbms3_combine_sources')
+        return y
+
+    def fom_implicit_euler_src(self, Q, theta, dt, nt, A_diag, A_cpl, b_K, phi, U0=None, rtol=1e-10, max_iter=50000, work=None):
+        """``fom_implicit_euler`` with the step right-hand side M u_k + dt sum_j phi[k + 1, j] b_K[j]; phi [nt + 1, K] (host or
+        device) -> U [nt + 1, S, n], (total CG iterations, worst final relative residual)."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        assert th.shape == (Q,)
+        nt, K = int(nt), int(b_K.shape[0])
+        ph = self._dev2(phi, (max(nt, 0) + 1, K), 'phi')
+        if work is None:
+            work = self.empty(int(self.lib.lrbms3_fom_implicit_euler_work_size(self.handle)))
+        U = self.empty(max(nt, 0) + 1, self.S, self.n)
+        if U0 is None:
+            U[0].zero_()
+        else:
+            U[0].copy_(U0.reshape(self.S, self.n))
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_fom_implicit_euler_src(self.handle, Q, K, th.ctypes.data_as(_P_DBL), float(dt), nt,
+                                                    self._ptr(A_diag, (Q, self.S, self.n_T, 5, 100), 'A_diag'),
+                                                    self._ptr(A_cpl, (Q, self.S, 6, self.ncf, 100), 'A_cpl'),
+                                                    self._ptr(b_K, (K, self.S, self.n), 'b_K'), c_vp(ph.data_ptr()),
+                                                    c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), info,
+                                                    self._stream())
+        self._check(rc, 'lrbms3_fom_implicit_euler_src')
+        return U, (int(info[0]), float(info[1]))
+
+    def reduced_implicit_euler_src(self, Q, theta, dt, nt, B_sys, M_red, rhs_red_K, phi, U0=None, rtol=1e-12, max_iter=20000, work=None):
+        """``reduced_implicit_euler`` with M_red u_k + dt sum_j phi[k + 1, j] rhs_red_K[j]; phi [nt + 1, K] (host or device)
+        -> U [nt + 1, S, N], (total CG iterations, worst final relative residual)."""
+        K, N, S = int(rhs_red_K.shape[0]), int(rhs_red_K.shape[2]), self.S
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        assert th.shape == (Q,)
+        nt = int(nt)
+        ph = self._dev2(phi, (max(nt, 0) + 1, K), 'phi')
+        if work is None:
+            work = self.empty(int(self.lib.lrbms3_reduced_implicit_euler_work_size(self.handle, N)))
+        U = self.empty(max(nt, 0) + 1, S, N)
+        if U0 is None:
+            U[0].zero_()
+        else:
+            U[0].copy_(U0.reshape(S, N))
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_reduced_implicit_euler_src(self.handle, Q, N, K, th.ctypes.data_as(_P_DBL), float(dt), nt,
+                                                        self._ptr(B_sys, (Q, S, 7, N, N), 'B_sys'), self._ptr(M_red, (S, N, N), 'M_red'),
+                                                        self._ptr(rhs_red_K, (K, S, N), 'rhs_red_K'), c_vp(ph.data_ptr()),
+                                                        c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), info,
+                                                        self._stream())
+        self._check(rc, 'lrbms3_reduced_implicit_euler_src')
+        return U, (int(info[0]), float(info[1]))

@@ -63,6 +63,8 @@ struct lrbms3_ctx : lrbms_ctx_base {
   long pg_part_cap = 0;
   // launch policy (lrbms3_ctx_set_option): the library reads no environment variable
   int opt_ksplit = 0, opt_serial = 0, opt_waves = 0, opt_estimate_valu = 0, opt_solve_valu = 0, opt_fom_coarse = 1;
+  double* src_phi = nullptr;       // [64][64] device (owned): source coefficients of lrbms3_reduced_solve_batch_src, first use
+  int num_cus = 0;                 // compute units of the device (lrbms3_combine_sources sizes its grid by them), first use
   bool side_padding = false;       // some side has fewer faces than ncf (unequal cubes per direction): padded factor rows exist
 };
 
@@ -2233,6 +2235,50 @@ __global__ __launch_bounds__(512) void k3b_init(int N, int nmu, int ldx, const d
   }
 }
 
+// k3b_init with a right-hand side of its own per column (lrbms3_reduced_solve_batch_src): column m starts from
+// sum_j phi[m][j] rhs_K[j][s], spelled out with fma from the first product; phi = this group's rows [nmu][K] of the device table,
+// rhs_K [K][S][N] (SN = S N).  K = 1 with phi = 1 gives the bits of k3b_init: 1 * x is exact and the rest is its arithmetic.
+__global__ __launch_bounds__(512) void k3b_init_src(int N, int nmu, int ldx, int K, long SN, const double* __restrict__ phi,
+                                                    const double* __restrict__ rhs_K, const double* __restrict__ Dinv,
+                                                    double* __restrict__ x, double* __restrict__ r, double* __restrict__ z,
+                                                    double* __restrict__ p, double* __restrict__ prz, double* __restrict__ prr) {
+  extern __shared__ double lds[];      // [N][16] rhs per column + [32][16] products
+  const int s = blockIdx.x, tid = threadIdx.x, i = tid >> 4, m = tid & 15;
+  for (int k = tid; k < N * 16; k += 512) {
+    const int kk = k >> 4, mm = k & 15;
+    double acc = 0.0;
+    if (mm < nmu) {
+      const double* ph = phi + (long)mm * K;
+      const double* src = rhs_K + (long)s * N + kk;
+      acc = ph[0] * src[0];
+      for (int j = 1; j < K; ++j) acc = __fma_rn(ph[j], src[(long)j * SN], acc);
+    }
+    lds[k] = acc;
+  }
+  __syncthreads();
+  double ri = 0.0, zi = 0.0;
+  const bool on = i < N && m < nmu;
+  if (on) {
+    ri = lds[i * 16 + m];
+    const double* D = Dinv + ((long)s * N + i) * N;
+    for (int j = 0; j < N; ++j) zi += D[j] * lds[j * 16 + m];
+    const long d = ((long)s * N + i) * nmu + m;
+    x[((long)s * N + i) * ldx + m] = 0.0;
+    r[d] = ri; z[d] = zi; p[d] = 0.0;
+  }
+  double* pr = lds + N * 16;
+  for (int pass = 0; pass < 2; ++pass) {
+    __syncthreads();
+    if (i < 32) pr[i * 16 + m] = on ? (pass ? ri * ri : ri * zi) : 0.0;
+    __syncthreads();
+    if (tid < 16) {
+      double a = 0.0;
+      for (int k = 0; k < N; ++k) a += pr[k * 16 + tid];
+      (pass ? prr : prz)[(long)s * 16 + tid] = a;
+    }
+  }
+}
+
 // Coarse level of the batched reduced solve (nullptr members: block-Jacobi alone): y0 [S][16] = A0^-1 r0 of the last residual,
 // prc_* [S][16] its contributions r0 . y0 to r.z -- summed with the fine partials wherever r.z is needed.
 struct CoarseB {
@@ -3418,15 +3464,17 @@ int64_t lrbms3_reduced_solve_batch_work_size(lrbms3_ctx* ctx, int32_t N, int32_t
   return (int64_t)((nmu + 15) / 16) * reduced_batch_group_size(ctx->t.S, N);
 }
 
-int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nmu, const double* theta, const double* B_sys,
-                               const double* rhs_red, double* work, double* u, double rtol, int32_t max_iter, double* info,
-                               void* stream) {
-  LRBMS_REQUIRE_MESH(ctx);
+}  // extern "C"
+
+namespace {
+
+// The group / iteration driver shared by lrbms3_reduced_solve_batch and lrbms3_reduced_solve_batch_src: K == 0 broadcasts
+// rhs_red [S][N] to every column (k3b_init); K >= 1 gives column m the right-hand side sum_j phi[m][j] rhs_red[j] of
+// rhs_red [K][S][N] (k3b_init_src, phi [nmu][K] on the device).  Everything behind the start kernel is the same launch sequence.
+int red_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nmu, const double* theta, const double* B_sys,
+                  const double* rhs_red, int K, const double* phi, double* work, double* u, double rtol, int max_iter, double* info,
+                  hipStream_t st) {
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: needs all subdomains on this rank");
-  if (Q < 1 || Q > 8 || N < 1 || N > 32 || nmu < 1 || nmu > 64 || !theta || !B_sys || !rhs_red || !work || !u)
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: needs N <= 32 and nmu <= 64");
-  hipStream_t st = (hipStream_t)stream;
   const long S = t.S, per_q = S * 7 * N * N;
   // Up to four groups of <= 16 parameters, each an independent CG on its own stream (the caller's and the library's three side
   // streams): a group's kernels are 512 small workgroups that wait on memory most of the time, so two or three groups share the
@@ -3487,8 +3535,12 @@ int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nm
       hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), G.st, N, G.Amu, G.Dinv);
     }
     LRBMS_HIP_CHECK(ctx, hipMemsetAsync(G.scal, 0, sizeof(double) * 80, G.st));
-    hipLaunchKernelGGL(k3b_init, dim3(S), dim3(512), sizeof(double) * (N + 32 * 16), G.st, N, G.nm, nmu, rhs_red, G.Dinv, u + G.m0, G.r,
-                       G.z, G.po, G.prz, G.prr);
+    if (K == 0)
+      hipLaunchKernelGGL(k3b_init, dim3(S), dim3(512), sizeof(double) * (N + 32 * 16), G.st, N, G.nm, nmu, rhs_red, G.Dinv, u + G.m0, G.r,
+                         G.z, G.po, G.prz, G.prr);
+    else
+      hipLaunchKernelGGL(k3b_init_src, dim3(S), dim3(512), sizeof(double) * (N * 16 + 32 * 16), G.st, N, G.nm, nmu, K, S * N,
+                         phi + (long)G.m0 * K, rhs_red, G.Dinv, u + G.m0, G.r, G.z, G.po, G.prz, G.prr);
     if (A0inv)
       hipLaunchKernelGGL(k3b_coarse_apply, dim3((unsigned)((S + 15) / 16)), dim3(1024), 0, G.st, (int)S, N, G.nm, A0inv, G.r, G.y0, G.prc);
     hipLaunchKernelGGL(k3b_reduce, dim3(1), dim3(256), 0, G.st, (int)S, G.nm, G.prr, G.scal + 64);
@@ -3564,9 +3616,47 @@ int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nm
     rel = g[k].rel > rel ? g[k].rel : rel;
   }
   if (info) info[0] = it, info[1] = rel;
-  if (rc != LRBMS_OK) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: NaN residual");
-  if (rel > rtol) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: not converged");
+  if (rc != LRBMS_OK) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": NaN residual");
+  if (rel > rtol) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": not converged");
   return LRBMS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lrbms3_reduced_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nmu, const double* theta, const double* B_sys,
+                               const double* rhs_red, double* work, double* u, double rtol, int32_t max_iter, double* info,
+                               void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (ctx->t.S_ext != ctx->t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 32 || nmu < 1 || nmu > 64 || !theta || !B_sys || !rhs_red || !work || !u)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: needs N <= 32 and nmu <= 64");
+  return red_batch_run(ctx, "reduced_solve_batch", Q, N, nmu, theta, B_sys, rhs_red, 0, nullptr, work, u, rtol, max_iter, info,
+                       (hipStream_t)stream);
+}
+
+// phi [nmu][K] arrives on the host and goes to a ctx-owned device table (64 x 64 doubles, allocated on first use) on the caller's
+// stream ahead of the fork, so the work size is that of lrbms3_reduced_solve_batch.  Only k3b_init_src reads the table, and every
+// group has synchronised behind it before the call returns: the next call may overwrite it.
+int lrbms3_reduced_solve_batch_src(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta,
+                                   const double* phi, const double* B_sys, const double* rhs_red_K, double* work, double* u,
+                                   double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (ctx->t.S_ext != ctx->t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch_src: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 32 || nmu < 1 || nmu > 64 || !theta || !phi || !B_sys || !rhs_red_K || !work || !u)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch_src: needs N <= 32 and nmu <= 64");
+  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch_src: need 1 <= K <= 64");
+  hipStream_t st = (hipStream_t)stream;
+  if (!ctx->src_phi) {
+    void* p = nullptr;
+    LRBMS_HIP_CHECK(ctx, hipMalloc(&p, sizeof(double) * 64 * 64));
+    ctx->owned.push_back(p);
+    ctx->src_phi = static_cast<double*>(p);
+  }
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(ctx->src_phi, phi, sizeof(double) * nmu * K, hipMemcpyHostToDevice, st));
+  return red_batch_run(ctx, "reduced_solve_batch_src", Q, N, nmu, theta, B_sys, rhs_red_K, K, ctx->src_phi, work, u, rtol, max_iter,
+                       info, st);
 }
 
 int64_t lrbms3_reduced_precond_size(lrbms3_ctx* ctx, int32_t N) {
@@ -4015,6 +4105,32 @@ __global__ __launch_bounds__(256) void k3p_fom_rhs(T3 t, double dt, const double
   if (tid == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = sum;
 }
 
+// k3p_fom_rhs with the load sum_j phi[j] b_K[j] (phi: the coefficient row of the step's new time, device; b_K [K][S][n], SN = S n),
+// the sum spelled out with fma from the first product.  K = 1, phi = 1: the bits of k3p_fom_rhs.
+__global__ __launch_bounds__(256) void k3p_fom_rhs_src(T3 t, double dt, const double* __restrict__ u, int K, long SN,
+                                                       const double* __restrict__ phi, const double* __restrict__ b_K,
+                                                       const double* __restrict__ Ku, double* __restrict__ rhs, double* __restrict__ part) {
+  __shared__ double red[256];
+  const int s = blockIdx.y, tid = threadIdx.x;
+  const int el = tid / 10, i = tid - el * 10, e = blockIdx.x * FOM_EPB + el;
+  const bool on = el < FOM_EPB && e < t.nT;
+  double f = 0.0;
+  if (on) {
+    const long d = (long)s * t.n + e * 10 + i;
+    const double* tm = t.TM + t.elem_type[e] * 100 + i * 10;
+    const double* ue = u + (long)s * t.n + e * 10;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) acc += tm[j] * ue[j];
+    double bs = phi[0] * b_K[d];
+    for (int j = 1; j < K; ++j) bs = __fma_rn(phi[j], b_K[(long)j * SN + d], bs);
+    f = acc + dt * bs;
+    rhs[d] = f - Ku[d];
+  }
+  const double sum = block_sum(f * f, red);
+  if (tid == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = sum;
+}
+
 __global__ __launch_bounds__(256) void k3p_axpy(long total, const double* __restrict__ x, double* __restrict__ y) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < total) y[i] += x[i];
@@ -4042,6 +4158,34 @@ __global__ __launch_bounds__(64) void k3p_red_rhs(int N, double dt, const double
     double acc = 0.0;
     for (int j = 0; j < N; ++j) acc += M[j] * us[j];
     f = acc + dt * rhs_red[(long)s * N + i];
+    rhs[(long)s * N + i] = f - Ku[(long)s * N + i];
+  }
+  red[i] = f * f;
+  __syncthreads();
+  for (int w = 32; w > 0; w >>= 1) {
+    if (i < w) red[i] += red[i + w];
+    __syncthreads();
+  }
+  if (i == 0) part[s] = red[0];
+}
+
+// k3p_red_rhs with the load sum_j phi[j] rhs_red_K[j] (rhs_red_K [K][S][N], SN = S N).  K = 1, phi = 1: the bits of k3p_red_rhs.
+__global__ __launch_bounds__(64) void k3p_red_rhs_src(int N, double dt, const double* __restrict__ Mred, const double* __restrict__ u,
+                                                      int K, long SN, const double* __restrict__ phi,
+                                                      const double* __restrict__ rhs_red_K, const double* __restrict__ Ku,
+                                                      double* __restrict__ rhs, double* __restrict__ part) {
+  __shared__ double us[64], red[64];
+  const int s = blockIdx.x, i = threadIdx.x;
+  us[i] = i < N ? u[(long)s * N + i] : 0.0;
+  __syncthreads();
+  double f = 0.0;
+  if (i < N) {
+    const double* M = Mred + ((long)s * N + i) * N;
+    double acc = 0.0;
+    for (int j = 0; j < N; ++j) acc += M[j] * us[j];
+    double bs = phi[0] * rhs_red_K[(long)s * N + i];
+    for (int j = 1; j < K; ++j) bs = __fma_rn(phi[j], rhs_red_K[(long)j * SN + (long)s * N + i], bs);
+    f = acc + dt * bs;
     rhs[(long)s * N + i] = f - Ku[(long)s * N + i];
   }
   red[i] = f * f;
@@ -4144,16 +4288,17 @@ int64_t lrbms3_fom_implicit_euler_work_size(lrbms3_ctx* ctx) {
   return base + (int64_t)t.S * t.n + nblk + 16;          // + right-hand side of the correction, partial |f|^2, |f|^2
 }
 
-int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, double dt, int32_t nt, const double* A_diag,
-                              const double* A_cpl, const double* b, double* work, double* U, double rtol, int32_t max_iter,
-                              double* info, void* stream) {
-  LRBMS_REQUIRE_MESH(ctx);
+}  // extern "C"
+
+namespace {
+
+// The time loop shared by lrbms3_fom_implicit_euler and lrbms3_fom_implicit_euler_src: the step operator M + dt A(mu), its
+// element-block inverses and its coarse level once, then per step K u_k, the right-hand side of the correction (rhs_launch(step, u_k,
+// K u_k, rhs, part): the one kernel in which the two exports differ), the warm-started CG and u_{k+1} = u_k + d.
+template <class F>
+int fom_euler_run(lrbms3_ctx* ctx, const char* name, int Q, const double* theta, double dt, int nt, const double* A_diag,
+                  const double* A_cpl, double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st, F rhs_launch) {
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: needs all subdomains on this rank");
-  if (Q < 1 || Q > 8 || !theta || !A_diag || !A_cpl || !b || !work || !U)
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: bad argument");
-  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: dt > 0 and nt >= 1 required");
-  hipStream_t st = (hipStream_t)stream;
   const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100, total = S * t.n;
   FomWork w = fom_work(t, work);
   double* rhs = work + lrbms3_fom_solve_work_size(ctx);
@@ -4178,11 +4323,11 @@ int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, d
     const double* uk = U + (long)k * total;
     double* un = U + (long)(k + 1) * total;
     hipLaunchKernelGGL(k3f_matvec, dim3(xcd_grid(w.nbx, (int)S)), dim3(256), 0, st, t, w.nbx, w.Amu, w.Cmu, uk, w.y, w.ppy);
-    hipLaunchKernelGGL(k3p_fom_rhs, dim3(w.nbx, S), dim3(256), 0, st, t, dt, uk, b, w.y, rhs, part);
+    rhs_launch(k, uk, w.y, rhs, part, w.nbx);
     hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)w.nblk, part, ff);
     LRBMS_LAUNCH_CHECK(ctx);
     double inf[2] = {0.0, 0.0};
-    rc = fom_cg(ctx, st, w, nc, A1inv, rhs, un, rtol, max_iter, inf, ff, "fom_implicit_euler");
+    rc = fom_cg(ctx, st, w, nc, A1inv, rhs, un, rtol, max_iter, inf, ff, name);
     iters += inf[0];
     worst = std::max(worst, inf[1]);
     if (info) info[0] = iters, info[1] = worst;
@@ -4193,22 +4338,11 @@ int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, d
   return LRBMS_OK;
 }
 
-int64_t lrbms3_reduced_implicit_euler_work_size(lrbms3_ctx* ctx, int32_t N) {
-  const int64_t base = lrbms3_reduced_solve_work_size(ctx, N);
-  if (base < 0) return -1;
-  return base + (int64_t)ctx->t.S * N + ctx->t.S + 16;    // + right-hand side of the correction, partial |f|^2, |f|^2
-}
-
-int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* theta, double dt, int32_t nt,
-                                  const double* B_sys, const double* M_red, const double* rhs_red, double* work, double* U,
-                                  double rtol, int32_t max_iter, double* info, void* stream) {
-  LRBMS_REQUIRE_MESH(ctx);
+// The reduced counterpart, shared by lrbms3_reduced_implicit_euler and lrbms3_reduced_implicit_euler_src.
+template <class F>
+int red_euler_run(lrbms3_ctx* ctx, const char* name, int Q, int N, const double* theta, double dt, int nt, const double* B_sys,
+                  const double* M_red, double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st, F rhs_launch) {
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: needs all subdomains on this rank");
-  if (Q < 1 || Q > 8 || N < 1 || N > 64 || !theta || !B_sys || !M_red || !rhs_red || !work || !U)
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: bad argument");
-  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: dt > 0 and nt >= 1 required");
-  hipStream_t st = (hipStream_t)stream;
   const long S = t.S, per_q = S * 7 * N * N, total = S * N;
   RedWork w = red_work(S, N, work);
   double* rhs = work + lrbms3_reduced_solve_work_size(ctx, N);
@@ -4230,11 +4364,11 @@ int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const d
     double* un = U + (long)(k + 1) * total;
     // K u_k by the CG's matvec (first iteration: p = z = u_k), into Ap
     hipLaunchKernelGGL(k3_pcg_matvec, dim3(S), dim3(64), lds, st, t, N, 1, w.Amu, uk, uk, w.p1, w.Ap, w.prz0, w.prz1, w.ppap);
-    hipLaunchKernelGGL(k3p_red_rhs, dim3(S), dim3(64), 0, st, N, dt, M_red, uk, rhs_red, w.Ap, rhs, part);
+    rhs_launch(k, uk, w.Ap, rhs, part);
     hipLaunchKernelGGL(k3_reduce1, dim3(1), dim3(256), 0, st, (int)S, part, ff);
     LRBMS_LAUNCH_CHECK(ctx);
     double inf[2] = {0.0, 0.0};
-    int rc = red_cg(ctx, st, N, w, rhs, un, rtol, max_iter, inf, ff, "reduced_implicit_euler");
+    int rc = red_cg(ctx, st, N, w, rhs, un, rtol, max_iter, inf, ff, name);
     iters += inf[0];
     worst = std::max(worst, inf[1]);
     if (info) info[0] = iters, info[1] = worst;
@@ -4243,6 +4377,84 @@ int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const d
     LRBMS_LAUNCH_CHECK(ctx);
   }
   return LRBMS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, double dt, int32_t nt, const double* A_diag,
+                              const double* A_cpl, const double* b, double* work, double* U, double rtol, int32_t max_iter,
+                              double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || !theta || !A_diag || !A_cpl || !b || !work || !U)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: bad argument");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler: dt > 0 and nt >= 1 required");
+  hipStream_t st = (hipStream_t)stream;
+  return fom_euler_run(ctx, "fom_implicit_euler", Q, theta, dt, nt, A_diag, A_cpl, work, U, rtol, max_iter, info, st,
+                       [&](int, const double* uk, const double* Ku, double* rhs, double* part, int nbx) {
+                         hipLaunchKernelGGL(k3p_fom_rhs, dim3(nbx, t.S), dim3(256), 0, st, t, dt, uk, b, Ku, rhs, part);
+                       });
+}
+
+int lrbms3_fom_implicit_euler_src(lrbms3_ctx* ctx, int32_t Q, int32_t K, const double* theta, double dt, int32_t nt,
+                                  const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                  double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_src: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || !theta || !A_diag || !A_cpl || !b_K || !phi || !work || !U)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_src: bad argument");
+  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_src: need 1 <= K <= 64");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_src: dt > 0 and nt >= 1 required");
+  hipStream_t st = (hipStream_t)stream;
+  return fom_euler_run(ctx, "fom_implicit_euler_src", Q, theta, dt, nt, A_diag, A_cpl, work, U, rtol, max_iter, info, st,
+                       [&](int step, const double* uk, const double* Ku, double* rhs, double* part, int nbx) {
+                         hipLaunchKernelGGL(k3p_fom_rhs_src, dim3(nbx, t.S), dim3(256), 0, st, t, dt, uk, K, (long)t.S * t.n,
+                                            phi + (long)(step + 1) * K, b_K, Ku, rhs, part);
+                       });
+}
+
+int64_t lrbms3_reduced_implicit_euler_work_size(lrbms3_ctx* ctx, int32_t N) {
+  const int64_t base = lrbms3_reduced_solve_work_size(ctx, N);
+  if (base < 0) return -1;
+  return base + (int64_t)ctx->t.S * N + ctx->t.S + 16;    // + right-hand side of the correction, partial |f|^2, |f|^2
+}
+
+int lrbms3_reduced_implicit_euler(lrbms3_ctx* ctx, int32_t Q, int32_t N, const double* theta, double dt, int32_t nt,
+                                  const double* B_sys, const double* M_red, const double* rhs_red, double* work, double* U,
+                                  double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 64 || !theta || !B_sys || !M_red || !rhs_red || !work || !U)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: bad argument");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler: dt > 0 and nt >= 1 required");
+  hipStream_t st = (hipStream_t)stream;
+  return red_euler_run(ctx, "reduced_implicit_euler", Q, N, theta, dt, nt, B_sys, M_red, work, U, rtol, max_iter, info, st,
+                       [&](int, const double* uk, const double* Ku, double* rhs, double* part) {
+                         hipLaunchKernelGGL(k3p_red_rhs, dim3(t.S), dim3(64), 0, st, N, dt, M_red, uk, rhs_red, Ku, rhs, part);
+                       });
+}
+
+int lrbms3_reduced_implicit_euler_src(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, const double* theta, double dt, int32_t nt,
+                                      const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
+                                      double* work, double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_src: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 64 || !theta || !B_sys || !M_red || !rhs_red_K || !phi || !work || !U)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_src: bad argument");
+  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_src: need 1 <= K <= 64");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_src: dt > 0 and nt >= 1 required");
+  hipStream_t st = (hipStream_t)stream;
+  return red_euler_run(ctx, "reduced_implicit_euler_src", Q, N, theta, dt, nt, B_sys, M_red, work, U, rtol, max_iter, info, st,
+                       [&](int step, const double* uk, const double* Ku, double* rhs, double* part) {
+                         hipLaunchKernelGGL(k3p_red_rhs_src, dim3(t.S), dim3(64), 0, st, N, dt, M_red, uk, K, (long)t.S * N,
+                                            phi + (long)(step + 1) * K, rhs_red_K, Ku, rhs, part);
+                       });
 }
 
 int64_t lrbms3_reduced_time_residual_work_size(lrbms3_ctx* ctx, int32_t N) {
@@ -4271,6 +4483,278 @@ int lrbms3_reduced_time_residual(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t 
   hipLaunchKernelGGL(k3p_time_residual, dim3(S, L), dim3(64), sizeof(double) * (8 * N + 64), st, t, N, Amu, Minv, dU, out);
   LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================= affine sources
+// f(mu) or f(t, mu) = sum_j phi_j f_j with K components: the Grams of the components, the projections of their
+// load vectors and element integrals, and the f terms of the residual indicator for columns with coefficients of their own.
+int launch_combine_sources_base(lrbms_ctx_base* ctx, int* num_cus, int K, long M, const double* phi, const double* x_K, double* y,
+                                hipStream_t st);      // online.hip: the 2D export's kernel, shape-agnostic
+
+namespace {
+
+// F2 [S][K][K]: one workgroup per (subdomain, pair j <= l), the expression and the fixed-order tree of k3_scalars' f2 with one factor
+// from each component -- K = 1 gives that f2 bit for bit.  comp = S n_T f_stride, the stride between two components' samples.
+__global__ __launch_bounds__(256) void k3_source_gram(T3 t, int K, long comp, const double* __restrict__ f_smp_K, double* __restrict__ F2) {
+  __shared__ double sa[256];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  int j = 0, l = blockIdx.y;                 // pair index -> (j, l), row-wise over the upper triangle
+  while (l >= K - j) {
+    l -= K - j;
+    ++j;
+  }
+  l += j;
+  const double* fj = f_smp_K + (long)j * comp;
+  const double* fl = f_smp_K + (long)l * comp;
+  double acc = 0.0;
+  for (int e = tid; e < t.nT; e += 256) {
+    const double* rj = fj + ((long)s * t.nT + e) * t.f_stride;
+    const double* rl = fl + ((long)s * t.nT + e) * t.f_stride;
+    for (int k = 0; k < t.nB; ++k) acc += t.WB[k] * rj[k] * rl[k];
+  }
+  sa[tid] = acc;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) sa[tid] += sa[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    F2[((long)s * K + j) * K + l] = sa[0];
+    F2[((long)s * K + l) * K + j] = sa[0];
+  }
+}
+
+// Both projections of lrbms3_project_sources in one launch on the fp64 matrix cores, one workgroup of 8 waves per (subdomain, role):
+//   role 0   rhs_red_K [K][S][N]  = b_K[j][s]^T V_s                       rows = the n DoFs, row operand = the rows of V_s
+//   role 1   r_fd_K    [K][S][QN] = sum_e bdiv_K[j][s][e] div(R_self)_e    rows = the n_T elements, row operand = the divergence of the
+//            element's four RT0 rows of the flux image R_self [S][n_rt][QN], formed in the lane (orientation and |f| / |T| as k3_estimate)
+// A wave takes four rows per step: the A operand holds the K components' weights of these rows (lane: component l & 15, row l >> 4),
+// the B operand the row operand (lane: column l & 15, row l >> 4); V and R_self are read once, whatever K.  KT = 16-component tiles;
+// up to four 16-column tiles.  The waves' tiles are summed in a fixed order through the LDS.
+template <int KT>
+__global__ __launch_bounds__(512) void k3_project_sources(T3 t, int N, int QN, int K, const double* __restrict__ b_K,
+                                                          const double* __restrict__ bdiv_K, const double* __restrict__ V,
+                                                          const double* __restrict__ Rs, double* __restrict__ rhs_K,
+                                                          double* __restrict__ rfd_K) {
+  __shared__ double red[8][256];
+  const int s = blockIdx.x, mode = blockIdx.y, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int cols = mode ? QN : N, rows = mode ? t.nT : t.n, nct = (cols + 15) / 16;
+  const long xs = (long)t.S * rows;
+  const double* X = (mode ? bdiv_K : b_K) + (long)s * rows;
+  d4 acc[KT][4];
+#pragma unroll
+  for (int rt = 0; rt < KT; ++rt)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int r0 = wave * 4; r0 < rows; r0 += 32) {
+    const int r = r0 + lk;
+    const bool rin = r < rows;
+    double a[KT], v[4];
+#pragma unroll
+    for (int rt = 0; rt < KT; ++rt) {
+      const int j = 16 * rt + li;
+      a[rt] = (rin && j < K) ? X[(long)j * xs + r] : 0.0;
+    }
+    if (mode == 0) {
+      const double* row = V + ((long)s * t.n + (rin ? r : 0)) * N;
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const int c = 16 * ct + li;
+        v[ct] = (rin && c < cols) ? row[c] : 0.0;
+      }
+    } else {
+      const int e = rin ? r : 0, ty = t.elem_type[e];
+      double dd[4];
+      const double* rr[4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        dd[f] = rin ? sgn3(t, s, e, f) * t.divc[ty * 4 + f] : 0.0;
+        rr[f] = Rs + ((long)s * t.nrt + t.elem_rt[e * 4 + f]) * QN;
+      }
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const int c = 16 * ct + li;
+        double dv = 0.0;
+        if (c < cols) {
+#pragma unroll
+          for (int f = 0; f < 4; ++f) dv += dd[f] * rr[f][c];
+        }
+        v[ct] = dv;
+      }
+    }
+#pragma unroll
+    for (int rt = 0; rt < KT; ++rt)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct)
+        if (ct < nct) acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rt], v[ct], acc[rt][ct], 0, 0, 0);
+  }
+  double* out = mode ? rfd_K : rhs_K;
+#pragma unroll
+  for (int rt = 0; rt < KT; ++rt)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      if (ct >= nct) continue;               // (uniform over the workgroup)
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave][r * 64 + lane] = acc[rt][ct][r];
+      __syncthreads();
+      if (tid < 256) {
+        const int r = tid >> 6, l = tid & 63;
+        double sum = 0.0;
+        for (int w = 0; w < 8; ++w) sum += red[w][tid];
+        const int j = 16 * rt + (l >> 4) + 4 * r, c = 16 * ct + (l & 15);
+        if (j < K && c < cols) out[((long)j * t.S + s) * cols + c] = sum;
+      }
+    }
+}
+
+// Sum over the workers (tid >> 3) of the values of column tid & 7, fixed order; red [256].  The result is valid in every thread.
+__device__ inline double column_sum8(double v, double* red) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int w = 128; w >= 8; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  return red[tid & 7];
+}
+
+// The f terms of the residual indicator (lrbms3_reduced_source_terms) for eight columns per workgroup: threads = (worker tid >> 3,
+// column tid & 7) as in k3_estimate_batch, so the eight columns share every factor row.  ur, zf = Rb ur_a and the divergence of zf on
+// the side elements are those of k3_estimate; theta [L][Q] and phi [L][K] are per column.  out [S][L].
+__global__ __launch_bounds__(256) void k3_source_terms(T3 t, int Q, int N, int K, int L, const double* __restrict__ theta,
+                                                       const double* __restrict__ phi, const double* __restrict__ F2,
+                                                       const double* __restrict__ r_fd_K, const double* __restrict__ bdiv_K,
+                                                       const double* __restrict__ Rb, const double* __restrict__ u,
+                                                       const double* __restrict__ ceps, double hdiam, double* __restrict__ out) {
+  extern __shared__ double lds[];
+  const int s = blockIdx.x, tid = threadIdx.x, w = tid >> 3, m = tid & 7, QN = Q * N;
+  double* us = lds;                    // [7][N][8] coefficients on the neighbourhood (0 where no neighbour)
+  double* zf = us + 7 * N * 8;         // [nbf][8]  flux of the neighbours on the side faces
+  double* ths = zf + t.nbf * 8;        // [8][8]    theta_q of the columns
+  double* red = ths + 64;              // [256]
+  const int l0 = blockIdx.y * 8;
+  const int l = l0 + m < L ? l0 + m : L - 1;          // columns behind L repeat the last one and are not stored
+  for (int k = tid; k < 7 * N * 8; k += 256) {
+    const int slot = k / (N * 8), j = (k >> 3) % N, mm = k & 7;
+    const int ll = l0 + mm < L ? l0 + mm : L - 1;
+    const int s2 = t.nbr[s * 7 + slot];
+    us[k] = s2 >= 0 ? u[((long)s2 * N + j) * L + ll] : 0.0;
+  }
+  if (tid < 64) {
+    const int q = tid >> 3, ll = l0 + (tid & 7) < L ? l0 + (tid & 7) : L - 1;
+    ths[tid] = q < Q ? theta[(long)ll * Q + q] : 0.0;
+  }
+  __syncthreads();
+  for (int sf = w; sf < t.nbf; sf += 32) {
+    const double* ua = us + side_slot(sf / t.ncf) * N * 8 + m;
+    const double* r = Rb + ((long)s * t.nbf + sf) * QN;
+    double acc = 0.0;
+    for (int q = 0; q < Q; ++q) {
+      double aq = 0.0;
+      for (int j = 0; j < N; ++j) aq += r[q * N + j] * ua[j * 8];
+      acc += ths[q * 8 + m] * aq;
+    }
+    zf[sf * 8 + m] = acc;
+  }
+  __syncthreads();
+  const double* ph = phi + (long)l * K;
+  const double* u0 = us + 3 * N * 8 + m;
+  double p_fd = 0.0, p_ff = 0.0;
+  for (int r = w; r < QN; r += 32) {
+    double rp = 0.0;
+    for (int j = 0; j < K; ++j) rp += ph[j] * r_fd_K[((long)j * t.S + s) * QN + r];
+    p_fd += rp * (ths[(r / N) * 8 + m] * u0[(r % N) * 8]);
+  }
+  for (int k = w; k < t.nsel; k += 32) {
+    const int e = t.sel_elem[k], ty = t.elem_type[e];
+    double dv = 0.0;
+    for (int f = 0; f < 4; ++f) {
+      const int sf = t.sel_sf[k * 4 + f];
+      const double ze = sf >= 0 ? zf[sf * 8 + m] : 0.0;
+      dv += sgn3(t, s, e, f) * t.divc[ty * 4 + f] * ze;
+    }
+    double bp = 0.0;
+    for (int j = 0; j < K; ++j) bp += ph[j] * bdiv_K[((long)j * t.S + s) * t.nT + e];
+    p_fd += bp * dv;
+  }
+  for (int k = w; k < K * K; k += 32) p_ff += ph[k / K] * F2[(long)s * K * K + k] * ph[k % K];
+  const double fd = column_sum8(p_fd, red);
+  const double ff = column_sum8(p_ff, red);
+  if (w == 0 && l0 + m < L) {
+    const double pi = 3.14159265358979323846;
+    out[(long)s * L + l] = (ff - 2.0 * fd) * (1.0 / (pi * pi)) / ceps[s] * hdiam * hdiam;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int lrbms3_assemble_source_gram(lrbms3_ctx* ctx, int32_t K, const double* f_smp_K, double* F2, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_source_gram: needs all subdomains on this rank");
+  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_source_gram: K must be in [1, 64]");
+  if (!f_smp_K || !F2) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_source_gram: null argument");
+  hipLaunchKernelGGL(k3_source_gram, dim3(t.S, K * (K + 1) / 2), dim3(256), 0, (hipStream_t)stream, t, K, (long)t.S * t.nT * t.f_stride,
+                     f_smp_K, F2);
+  LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}
+
+int lrbms3_project_sources(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, const double* b_K, const double* bdiv_K, const double* V,
+                           const double* R_self, double* rhs_red_K, double* r_fd_K, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: needs all subdomains on this rank");
+  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: K must be in [1, 64]");
+  if (Q < 1 || Q > 8 || N < 1 || N > 64 || Q * N > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: needs N <= 64 and Q N <= 64");
+  if (!b_K || !bdiv_K || !V || !R_self || !rhs_red_K || !r_fd_K) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(t.S, 2);
+#define PSCASE(T)                                                                                                                  \
+  case T:                                                                                                                          \
+    hipLaunchKernelGGL(k3_project_sources<T>, grid, dim3(512), 0, st, t, N, Q * N, K, b_K, bdiv_K, V, R_self, rhs_red_K, r_fd_K); \
+    break
+  switch ((K + 15) / 16) {
+    PSCASE(1);
+    PSCASE(2);
+    PSCASE(3);
+    PSCASE(4);
+  }
+#undef PSCASE
+  LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}
+
+int lrbms3_reduced_source_terms(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t L, const double* theta, const double* phi,
+                                const double* F2, const double* r_fd_K, const double* bdiv_K, const double* Rb, const double* u,
+                                const double* ceps, double hdiam, double* out, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 64 || K < 1 || K > 64 || L < 1 || (L + 7) / 8 > 65535)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: bad N / L / K / Q");
+  if (!theta || !phi || !F2 || !r_fd_K || !bdiv_K || !Rb || !u || !ceps || !out)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: null argument");
+  const size_t lds = sizeof(double) * (7 * (size_t)N * 8 + (size_t)t.nbf * 8 + 64 + 256);
+  if (lds > 64 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: the side faces of this template do not fit the LDS");
+  hipLaunchKernelGGL(k3_source_terms, dim3(t.S, (L + 7) / 8), dim3(256), lds, (hipStream_t)stream, t, Q, N, K, L, theta, phi, F2, r_fd_K,
+                     bdiv_K, Rb, u, ceps, hdiam, out);
+  LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}
+
+int lrbms3_combine_sources(lrbms3_ctx* ctx, int32_t K, int64_t M, const double* phi, const double* x_K, double* y, void* stream) {
+  if (!ctx) return LRBMS_E_INVALID;
+  if (!phi || !x_K || !y) return lrbms_fail(ctx, LRBMS_E_INVALID, "combine_sources: null argument");
+  return launch_combine_sources_base(ctx, &ctx->num_cus, K, (long)M, phi, x_K, y, (hipStream_t)stream);
 }
 
 }  // extern "C"

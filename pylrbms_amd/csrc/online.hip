@@ -2363,12 +2363,15 @@ __global__ __launch_bounds__(256) void k_combine_sources(int K, long M, SrcPhi p
 }
 }  // namespace
 
-int launch_combine_sources(lrbms_ctx* ctx, int K, long M, const double* phi, const double* x_K, double* y, hipStream_t st) {
+// The kernel is shape-agnostic: lrbms_combine_sources and lrbms3_combine_sources (lrbms3d.hip) both launch it through this entry,
+// each with its own context's error string and cached compute-unit count.
+int launch_combine_sources_base(lrbms_ctx_base* ctx, int* num_cus, int K, long M, const double* phi, const double* x_K, double* y,
+                                hipStream_t st) {
   if (K < 1 || K > 64 || M < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "combine_sources: need 1 <= K <= 64, M >= 1");
-  if (ctx->num_cus == 0) {
+  if (*num_cus == 0) {
     int ncu = 0;
     LRBMS_HIP_CHECK(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    ctx->num_cus = ncu > 0 ? ncu : 256;
+    *num_cus = ncu > 0 ? ncu : 256;
   }
   SrcPhi ph;
   for (int j = 0; j < 64; ++j) ph.v[j] = j < K ? phi[j] : 0.0;
@@ -2376,7 +2379,7 @@ int launch_combine_sources(lrbms_ctx* ctx, int K, long M, const double* phi, con
   const long items = wide ? M / 2 : M;
   // four workgroups of 256 per CU cover the chip; fewer when the vector is short
   long blocks = (items + 255) / 256;
-  const long cap = 4L * ctx->num_cus;
+  const long cap = 4L * *num_cus;
   blocks = blocks < cap ? blocks : cap;
   if (wide)
     hipLaunchKernelGGL(k_combine_sources<true>, dim3((unsigned)blocks), dim3(256), 0, st, K, M, ph, x_K, y);
@@ -2384,6 +2387,10 @@ int launch_combine_sources(lrbms_ctx* ctx, int K, long M, const double* phi, con
     hipLaunchKernelGGL(k_combine_sources<false>, dim3((unsigned)blocks), dim3(256), 0, st, K, M, ph, x_K, y);
   LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
+}
+
+int launch_combine_sources(lrbms_ctx* ctx, int K, long M, const double* phi, const double* x_K, double* y, hipStream_t st) {
+  return launch_combine_sources_base(ctx, &ctx->num_cus, K, M, phi, x_K, y, st);
 }
 
 // =========================================================================================================

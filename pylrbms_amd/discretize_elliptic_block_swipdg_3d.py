@@ -19,16 +19,25 @@ from pylrbms_amd.reductor import ExtensionError, LocalBasisSlab
 
 
 class BlockDiscretization3D:
+    _src = None                        # the affine source record (``sources3d.setup_sources3d``); None: one component, coefficient 1
+    _time_dependent_source = False     # the parabolic subclass takes coefficients c(mu, t)
+
     def __init__(self, p, device_index=0):
         self.grid = p['grid']
         lam = p['lambda']
         f = p['f']
+        comp = None
         if isinstance(f, dict):
+            from pylrbms_amd import sources3d
             from pylrbms_amd.sources import source_components
-            if source_components(p) is not None:          # refused before any device work (the 2D path takes them)
-                raise NotImplementedError('the 3D path takes one source function; a multi-component / parameter-dependent source '
-                                          'exists on the 2D path only')
-            f = f['functions'][0]
+            comp = source_components(p)
+            if comp is None:
+                f = f['functions'][0]
+            else:                                          # f = sum_j c_j f_j; the refusals come before any device work
+                arity = sources3d.check_sources3d(self.grid, comp[1])
+                if 2 in arity and not self._time_dependent_source:
+                    raise NotImplementedError('a source coefficient c(mu, t) depends on time: this needs the parabolic discretize')
+                f = sources3d.sum_function(comp[0])          # the engine is built on sum_j f_j, as in 2D
         self.coefficients = list(lam['coefficients'])
         self.mu_bar, self.mu_hat = p['mu_bar'], p['mu_hat']
         self.engine = Engine3D(self.grid, lam['functions'], f, p['lambda_bar'], p['lambda_hat'],
@@ -36,6 +45,22 @@ class BlockDiscretization3D:
                                theta_bar=[float(c(self.mu_bar)) for c in self.coefficients]).assemble()
         self.Q = self.engine.Q
         self.parameter_range = p.get('parameter_range')
+        if comp is not None:
+            self._src = sources3d.setup_sources3d(self.engine, comp[0], comp[1], arity)
+
+    def source_coefficients(self, mu):
+        """[K]: the coefficients c_j(mu) of the source f(mu) = sum_j c_j(mu) f_j ([1.] without an affine source)."""
+        if self._src is None:
+            return np.ones(1)
+        from pylrbms_amd.sources3d import evaluate_stationary
+        return evaluate_stationary(self._src, mu)
+
+    def _load_vector(self, mu):
+        """b(mu) [S, n]: ``lrbms3_combine_sources`` of the components' load vectors."""
+        if self._src is None:
+            return self.engine.ops['b']
+        from pylrbms_amd.sources3d import evaluate_stationary
+        return self.engine.ctx.combine_sources(evaluate_stationary(self._src, mu), self._src['b_K'])
 
     def theta(self, mu):
         return np.array([float(c(mu)) for c in self.coefficients], dtype=np.float64)
@@ -92,7 +117,7 @@ class BlockDiscretization3D:
             if not getattr(self, '_fom_kept', False):       # one dense coarse factorisation for all snapshots of this discretization
                 eng.ctx.fom_precond_keep(True)
                 self._fom_kept = True
-            U, info = eng.ctx.fom_solve(self.Q, self.theta(mu), eng.ops['A_diag'], eng.ops['A_cpl'], eng.ops['b'], rtol=rtol,
+            U, info = eng.ctx.fom_solve(self.Q, self.theta(mu), eng.ops['A_diag'], eng.ops['A_cpl'], self._load_vector(mu), rtol=rtol,
                                         max_iter=max_iter)
             return (U, info) if return_info else U
         import torch
@@ -129,23 +154,50 @@ class BlockDiscretization3D:
         """Full-order estimate of the block DG vector U [S, n] (:205-217): the pass with U as a one-column basis, u = 1."""
         eng = self.engine
         V = (U if isinstance(U, eng.ctx.torch.Tensor) else eng.ctx.from_numpy(np.asarray(U))).reshape(eng.S_ext, eng.t.n, 1).contiguous()
-        out = eng.project_and_estimate(V)
         ones = eng.ctx.zeros(eng.S_ext, 1) + 1.0
-        return self.combine(eng.reduced_estimate(self.theta(mu), ones, out).cpu().numpy(), mu, decompose)
+        if self._src is None:
+            out = eng.project_and_estimate(V)
+            return self.combine(eng.reduced_estimate(self.theta(mu), ones, out).cpu().numpy(), mu, decompose)
+        # affine source: the estimate without its f terms, plus the f terms at c(mu) (the residual indicator is affine in them)
+        from pylrbms_amd import sources3d
+        theta, phi = self.theta(mu), self.source_coefficients(mu)
+        work = eng.alloc_work(1)
+        out = eng.project_and_estimate(V, work=work)
+        out0, ops0 = sources3d.zeroed(eng, out)
+        eta = eng.ctx.reduced_estimate(self.Q, theta, ones, out0, ops0, eng.hdiam)
+        _, r_fd_K = eng.ctx.project_sources(self.Q, self._src['b_K'], self._src['bdiv_K'], V, work)
+        eta[1] += sources3d.source_terms(eng, self.Q, self._src, theta[None], phi[None], r_fd_K, out, ones[:, :, None].contiguous())[:, 0]
+        return self.combine(eta.cpu().numpy(), mu, decompose)
 
 
 class ReducedDiscretization3D:
     """``rd``: the 7-slot block-sparse reduced system and the projected estimator operators (factored layout), in HBM."""
 
-    def __init__(self, reductor, out):
+    def __init__(self, reductor, out, rhs_red_K=None, r_fd_K=None):
+        """``rhs_red_K`` [K, S, N], ``r_fd_K`` [K, S, QN]: the projections of an affine source's components
+        (``lrbms3_project_sources``); ``out['rhs_red']`` and ``out['r_fd']`` -- those of sum_j f_j -- are then None."""
         self.reductor, self.d, self.out = reductor, reductor.d, out
-        self.N = out['rhs_red'].shape[1]
+        self.rhs_red_K, self.r_fd_K = rhs_red_K, r_fd_K
+        self.N = out['B_sys'].shape[-1]
 
     @property
     def operators(self):
         """Dense blocks of the projected estimator operators (reference: ``rd.operators``), built on request from the factors."""
         from pylrbms_amd.engine3d import expand_factored
+        if self.rhs_red_K is not None:
+            raise NotImplementedError('dense operators of a reduced model with an affine source (rhs_red and r_fd are per component)')
         return expand_factored(self.d.engine, self.out, self.d.Q, self.N)
+
+    def _phi(self, mu):
+        """[K]: the stationary source coefficients c(mu) (NotImplementedError if one of them depends on time)."""
+        from pylrbms_amd.sources3d import evaluate_stationary
+        return evaluate_stationary(self.d._src, mu)
+
+    def _zeroed(self):
+        if getattr(self, '_zero', None) is None:
+            from pylrbms_amd.sources3d import zeroed
+            self._zero = zeroed(self.d.engine, self.out)
+        return self._zero
 
     def solve(self, mu, rtol=1e-12, max_iter=20000, return_info=False):
         """``rd.solve(mu)`` (online_adaptive_lrbms.py:141).  N <= 32: the batched solver with one parameter -- it has the
@@ -154,7 +206,12 @@ class ReducedDiscretization3D:
         if self.N <= 32:
             U, info = self.solve_batch([mu], rtol=rtol, max_iter=max_iter, return_info=True)
             return (U[0], info) if return_info else U[0]
-        u, info = self.d.engine.reduced_solve(self.d.theta(mu), self.out, rtol=rtol, max_iter=max_iter)
+        eng = self.d.engine
+        if self.rhs_red_K is None:
+            u, info = eng.reduced_solve(self.d.theta(mu), self.out, rtol=rtol, max_iter=max_iter)
+        else:                                  # rhs_red(mu) by lrbms3_combine_sources, then the single-parameter solve
+            rhs = eng.ctx.combine_sources(self._phi(mu), self.rhs_red_K)
+            u, info = eng.ctx.reduced_solve(self.d.Q, self.d.theta(mu), self.out['B_sys'], rhs, rtol=rtol, max_iter=max_iter)
         return (u, info) if return_info else u
 
     def solve_batch(self, mus, rtol=1e-12, max_iter=20000, return_info=False):
@@ -184,7 +241,12 @@ class ReducedDiscretization3D:
         try:
             for b0 in range(0, len(mus), 64):          # 64 per native call: four groups of 16 on four streams
                 th = np.stack([self.d.theta(mu) for mu in mus[b0:b0 + 64]])
-                ub, inf = eng.ctx.reduced_solve_batch(self.d.Q, th, self.out['B_sys'], self.out['rhs_red'], rtol=rtol, max_iter=max_iter)
+                if self.rhs_red_K is None:
+                    ub, inf = eng.ctx.reduced_solve_batch(self.d.Q, th, self.out['B_sys'], self.out['rhs_red'], rtol=rtol, max_iter=max_iter)
+                else:
+                    ph = np.stack([self._phi(mu) for mu in mus[b0:b0 + 64]])
+                    ub, inf = eng.ctx.reduced_solve_batch_src(self.d.Q, th, ph, self.out['B_sys'], self.rhs_red_K, rtol=rtol,
+                                                              max_iter=max_iter)
                 out.append(ub.permute(2, 0, 1))
                 info = (max(info[0], inf[0]), max(info[1], inf[1]))
         finally:
@@ -192,15 +254,34 @@ class ReducedDiscretization3D:
         U = torch.cat(out, dim=0).contiguous()
         return (U, info) if return_info else U
 
-    def estimate_batch(self, U, mus):
-        """Estimates of the reduced solutions U [len(mus), S, N] (as ``solve_batch`` returns them): list of eta."""
+    def estimate_batch(self, U, mus, decompose=False):
+        """Estimates of the reduced solutions U [len(mus), S, N] (as ``solve_batch`` returns them): list of eta; with ``decompose``
+        list of (eta, (nc, r, df), local indicators) as ``estimate`` returns them."""
         eng = self.d.engine
         th = np.stack([self.d.theta(mu) for mu in mus])
-        eta = eng.ctx.reduced_estimate_batch(self.d.Q, th, U.permute(1, 2, 0).contiguous(), self.out, eng.ops, eng.hdiam).cpu().numpy()
-        return [self.d.combine(eta[:, :, m], mu) for m, mu in enumerate(mus)]
+        u = U.permute(1, 2, 0).contiguous()
+        if self.rhs_red_K is None:
+            eta = eng.ctx.reduced_estimate_batch(self.d.Q, th, u, self.out, eng.ops, eng.hdiam)
+        else:                                  # the f terms of all columns in one launch, each with its own theta and c(mu)
+            from pylrbms_amd.sources3d import source_terms
+            out0, ops0 = self._zeroed()
+            eta = eng.ctx.reduced_estimate_batch(self.d.Q, th, u, out0, ops0, eng.hdiam)
+            ph = np.stack([self._phi(mu) for mu in mus])
+            eta[1] += source_terms(eng, self.d.Q, self.d._src, th, ph, self.r_fd_K, self.out, u)
+        eta = eta.cpu().numpy()
+        return [self.d.combine(eta[:, :, m], mu, decompose) for m, mu in enumerate(mus)]
 
     def estimate(self, u, mu, decompose=False):
-        eta_loc = self.d.engine.reduced_estimate(self.d.theta(mu), u.contiguous(), self.out)
+        eng = self.d.engine
+        if self.rhs_red_K is None:
+            eta_loc = eng.reduced_estimate(self.d.theta(mu), u.contiguous(), self.out)
+        else:
+            from pylrbms_amd.sources3d import source_terms
+            out0, ops0 = self._zeroed()
+            theta = self.d.theta(mu)
+            eta_loc = eng.ctx.reduced_estimate(self.d.Q, theta, u.contiguous(), out0, ops0, eng.hdiam)
+            eta_loc[1] += source_terms(eng, self.d.Q, self.d._src, theta[None], self._phi(mu)[None], self.r_fd_K,
+                                       self.out, u[:, :, None].contiguous())[:, 0]
         return self.d.combine(eta_loc.cpu().numpy(), mu, decompose)
 
 
@@ -312,7 +393,19 @@ class LRBMSReductor3D(LocalBasisSlab):
         V = self._V
         if V.shape[0] != eng.S_ext:
             raise NotImplementedError('sharded discretization: hand in bases [S_ext, n, N] with the halo filled (HaloExchange)')
-        return ReducedDiscretization3D(self, eng.project_and_estimate(V.contiguous()))
+        return ReducedDiscretization3D(self, *self._project(V.contiguous()))
+
+    def _project(self, V):
+        """(out, rhs_red_K, r_fd_K) of one pass; with an affine source also ``lrbms3_project_sources`` on the pass's flux image, and
+        the projections of sum_j f_j (``rhs_red``, ``r_fd``) are dropped: nothing may use them on such a model."""
+        eng, src = self.d.engine, self.d._src
+        if src is None:
+            return eng.project_and_estimate(V), None, None
+        work = eng.alloc_work(V.shape[2])
+        out = eng.project_and_estimate(V, work=work)
+        rhs_red_K, r_fd_K = eng.ctx.project_sources(self.d.Q, src['b_K'], src['bdiv_K'], V, work)
+        out['rhs_red'] = out['r_fd'] = None
+        return out, rhs_red_K, r_fd_K
 
     def reconstruct(self, u):
         return self._torch.einsum('snj,sj->sn', self._V, u)

@@ -42,39 +42,73 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
     """The 3D block discretization with ``T``, ``time_stepper`` (implicit Euler, ``nt`` steps), zero ``initial_data`` [S, n] and
     ``parameter_space``; built by ``discretize`` below."""
 
+    _time_dependent_source = True
+
     @property
     def dt(self):
         return self.T / self.time_stepper.nt
+
+    def source_coefficients(self, mu):
+        """The host table phi [nt + 1, K] of the source f(t, mu) = sum_j c_j(mu, t) f_j: row k at t_k = k dt.  Step k -> k + 1 uses
+        row k + 1; the elliptic part of U_k in the estimate uses row k.  Ones [nt + 1, 1] without an affine source."""
+        nt = self.time_stepper.nt
+        if self._src is None:
+            return np.ones((nt + 1, 1))
+        from pylrbms_amd.sources3d import evaluate_table
+        return evaluate_table(self._src, mu, self.dt, nt)
 
     def solve(self, mu, rtol=1e-10, max_iter=50000, return_info=False):
         """The trajectory as a device slab U [S, n, nt + 1] (U[:, :, 0] = the initial data): all nt implicit Euler steps in one
         native call, each a warm-started two-level CG on M + dt A(mu).  ``last_solve_info`` = (total CG iterations, worst relative
         residual)."""
         eng = self.engine
-        U, info = eng.ctx.fom_implicit_euler(self.Q, self.theta(mu), self.dt, self.time_stepper.nt, eng.ops['A_diag'],
-                                             eng.ops['A_cpl'], eng.ops['b'], U0=self.initial_data, rtol=rtol, max_iter=max_iter)
+        if self._src is None:
+            U, info = eng.ctx.fom_implicit_euler(self.Q, self.theta(mu), self.dt, self.time_stepper.nt, eng.ops['A_diag'],
+                                                 eng.ops['A_cpl'], eng.ops['b'], U0=self.initial_data, rtol=rtol, max_iter=max_iter)
+        else:
+            U, info = eng.ctx.fom_implicit_euler_src(self.Q, self.theta(mu), self.dt, self.time_stepper.nt, eng.ops['A_diag'],
+                                                     eng.ops['A_cpl'], self._src['b_K'], self.source_coefficients(mu),
+                                                     U0=self.initial_data, rtol=rtol, max_iter=max_iter)
         self.last_solve_info = info
         U = U.permute(1, 2, 0).contiguous()
         return (U, info) if return_info else U
 
     def solve_stationary(self, mu, rtol=1e-10, max_iter=50000, return_info=False):
-        """The elliptic solve of the underlying discretization (the limit t -> oo)."""
+        """The elliptic solve of the underlying discretization (the limit t -> oo).  NotImplementedError if a source coefficient
+        depends on time (before the engine is read)."""
+        if self._src is not None:
+            from pylrbms_amd.sources3d import evaluate_stationary
+            evaluate_stationary(self._src, mu)
         return BlockDiscretization3D.solve(self, mu, rtol=rtol, max_iter=max_iter, return_info=return_info)
 
-    def _elliptic_terms(self, U, mu):
+    def _elliptic_terms(self, U, mu, rows=None):
         """Local nc / r / df [3, S, L] of every column of U [S, n, L]: chunks of <= 64 // Q columns become a basis of the pass
-        (it takes Q N <= 64) and the batched estimate with identity coefficients evaluates each column's forms."""
+        (it takes Q N <= 64) and the batched estimate with identity coefficients evaluates each column's forms.  With an affine
+        source the estimate runs without its f terms and ``rows`` [L, K] (the source coefficients of every column; None: no f terms,
+        the caller reads the nc row only) adds them through ``lrbms3_project_sources`` / ``lrbms3_reduced_source_terms``."""
         import torch
-        eng = self.engine
+        from pylrbms_amd import sources3d
+        eng, src = self.engine, self._src
         theta = self.theta(mu)
         step = max(1, 64 // self.Q)
         out = []
         for c0 in range(0, U.shape[2], step):
             V = U[:, :, c0:c0 + step].contiguous()
             L = V.shape[2]
-            buf = eng.project_and_estimate(V)
             u = torch.eye(L, dtype=V.dtype, device=V.device).expand(eng.S_ext, L, L).contiguous()
-            out.append(eng.ctx.reduced_estimate_batch(self.Q, np.tile(theta, (L, 1)), u, buf, eng.ops, eng.hdiam))
+            th = np.tile(theta, (L, 1))
+            if src is None:
+                buf = eng.project_and_estimate(V)
+                out.append(eng.ctx.reduced_estimate_batch(self.Q, th, u, buf, eng.ops, eng.hdiam))
+                continue
+            work = eng.alloc_work(L)
+            buf = eng.project_and_estimate(V, work=work)
+            buf0, ops0 = sources3d.zeroed(eng, buf)
+            eta = eng.ctx.reduced_estimate_batch(self.Q, th, u, buf0, ops0, eng.hdiam)
+            if rows is not None:
+                _, r_fd_K = eng.ctx.project_sources(self.Q, src['b_K'], src['bdiv_K'], V, work)
+                eta[1] += sources3d.source_terms(eng, self.Q, src, th, np.ascontiguousarray(rows[c0:c0 + L]), r_fd_K, buf, u)
+            out.append(eta)
         return torch.cat(out, dim=2).cpu().numpy()
 
     def estimate(self, U, mu, decompose=False):
@@ -83,7 +117,9 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
         eng = self.engine
         U = (U if isinstance(U, eng.ctx.torch.Tensor) else eng.ctx.from_numpy(np.asarray(U))).contiguous()
         dU = (U[:, :, 1:] - U[:, :, :-1]).contiguous()
-        eta_loc = self._elliptic_terms(U, mu)
+        if self._src is not None and U.shape[2] != self.time_stepper.nt + 1:
+            raise ValueError('with a time-dependent source the estimate takes the whole trajectory [S, n, nt + 1]')
+        eta_loc = self._elliptic_terms(U, mu, rows=self.source_coefficients(mu) if self._src is not None else None)
         Y = eng.ctx.fom_apply(self.Q, self.theta(mu), eng.ops['A_diag'], eng.ops['A_cpl'], dU)
         tr2 = eng.ctx.mass_inverse_norm2(Y).sum(dim=0).cpu().numpy()
         tdnc2 = self._elliptic_terms(dU, mu)[0]
@@ -93,8 +129,8 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
 class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
     """``rd`` of the parabolic path: the reduced elliptic model plus the projected mass ``M_red`` [S, N, N]."""
 
-    def __init__(self, reductor, out, M_red):
-        super().__init__(reductor, out)
+    def __init__(self, reductor, out, M_red, rhs_red_K=None, r_fd_K=None):
+        super().__init__(reductor, out, rhs_red_K, r_fd_K)
         self.M_red = M_red
         self.T, self.time_stepper = reductor.d.T, reductor.d.time_stepper
 
@@ -105,8 +141,13 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
     def solve(self, mu, rtol=1e-12, max_iter=20000, return_info=False):
         """Reduced implicit Euler from zero: u [nt + 1, S, N] (one native call)."""
         d = self.d
-        u, info = d.engine.ctx.reduced_implicit_euler(d.Q, d.theta(mu), self.dt, self.time_stepper.nt, self.out['B_sys'], self.M_red,
-                                                      self.out['rhs_red'], rtol=rtol, max_iter=max_iter)
+        if self.rhs_red_K is None:
+            u, info = d.engine.ctx.reduced_implicit_euler(d.Q, d.theta(mu), self.dt, self.time_stepper.nt, self.out['B_sys'], self.M_red,
+                                                          self.out['rhs_red'], rtol=rtol, max_iter=max_iter)
+        else:
+            u, info = d.engine.ctx.reduced_implicit_euler_src(d.Q, d.theta(mu), self.dt, self.time_stepper.nt, self.out['B_sys'],
+                                                              self.M_red, self.rhs_red_K, d.source_coefficients(mu), rtol=rtol,
+                                                              max_iter=max_iter)
         self.last_solve_info = info
         return (u, info) if return_info else u
 
@@ -119,9 +160,16 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
         u = u.contiguous()
         du = (u[1:] - u[:-1]).contiguous()
         L = u.shape[0]
-        eta_loc = eng.ctx.reduced_estimate_batch(Q, np.tile(theta, (L, 1)), u.permute(1, 2, 0).contiguous(), self.out, eng.ops,
-                                                 eng.hdiam).cpu().numpy()
-        tdnc2 = eng.ctx.reduced_estimate_batch(Q, np.tile(theta, (L - 1, 1)), du.permute(1, 2, 0).contiguous(), self.out, eng.ops,
+        out, ops = (self.out, eng.ops) if self.rhs_red_K is None else self._zeroed()
+        th, uc = np.tile(theta, (L, 1)), u.permute(1, 2, 0).contiguous()
+        eta_loc = eng.ctx.reduced_estimate_batch(Q, th, uc, out, ops, eng.hdiam)
+        if self.rhs_red_K is not None:        # the f terms of all nt + 1 columns in one launch, column k with row k of the table
+            from pylrbms_amd.sources3d import source_terms
+            if L != self.time_stepper.nt + 1:
+                raise ValueError('with a time-dependent source the estimate takes the whole trajectory [nt + 1, S, N]')
+            eta_loc[1] += source_terms(eng, Q, d._src, th, d.source_coefficients(mu), self.r_fd_K, self.out, uc)
+        eta_loc = eta_loc.cpu().numpy()
+        tdnc2 = eng.ctx.reduced_estimate_batch(Q, np.tile(theta, (L - 1, 1)), du.permute(1, 2, 0).contiguous(), out, ops,
                                                eng.hdiam)[0].cpu().numpy()
         tr2 = eng.ctx.reduced_time_residual(Q, theta, self.out['B_sys'], self.M_red, du).sum(dim=1).cpu().numpy()
         return _parabolic_estimate(d, mu, self.dt, eta_loc, tr2, tdnc2)
@@ -141,7 +189,7 @@ class ParabolicLRBMSReductor3D(LRBMSReductor3D):
     def reduce(self):
         rd = super().reduce()
         M_red = self.d.engine.ctx.project_mass(self._V.contiguous())
-        return InstationaryReducedDiscretization3D(self, rd.out, M_red)
+        return InstationaryReducedDiscretization3D(self, rd.out, M_red, rd.rhs_red_K, rd.r_fd_K)
 
     def reconstruct(self, u):
         return self._torch.einsum('snj,ksj->snk', self._V, u).contiguous()

@@ -75,6 +75,9 @@ def load_bases(d, path):
 def save_reduced(rd, path):
     """Write the reduced model ``rd`` (projected system + projected estimator operators) to ``path``."""
     from safetensors.torch import save_file
+    if getattr(rd, 'rhs_red_K', None) is not None and type(getattr(rd.d, 'engine', None)).__name__ == 'Engine3D':
+        raise NotImplementedError('save_reduced: a 3D reduced model with an affine source ({} components: rhs_red_K, r_fd_K) is not '
+                                  'stored by this format'.format(rd.rhs_red_K.shape[0]))
     affine = getattr(rd, 'rhs_red_K', None) is not None and getattr(rd.d, '_affine_f', None) is not None
     if getattr(rd, 'rhs_red_K', None) is not None and not affine:
         raise NotImplementedError('save_reduced: the model carries a time-dependent source with {} component(s) (rhs_red_K, '
