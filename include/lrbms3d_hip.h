@@ -330,6 +330,30 @@ int lrbms3_reduced_implicit_euler_src(lrbms3_ctx* ctx, int32_t Q, int32_t N, int
                                       const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
                                       double* work, double* U, double rtol, int32_t max_iter, double* info, void* stream);
 
+/* -- online enrichment ------------------------------------------------------------------------------------------------------ */
+/* Dirichlet correction blocks of the neighbourhood problems: on every coupling face of subdomain s, for the own side element,
+ * the Dirichlet-face block (inside coefficient) minus the inner-face own / own block already contained in A_diag (mesh tables
+ * TFb and TFo contracted with the lambda_q samples at the system face rule, as the diagonal block of lrbms3_assemble_system).
+ *   D_corr [Q][S][6][ncf][100], zero on physical sides and on padded positions.  Once per discretization, not hot.
+ * 2D: lrbms_assemble_dirichlet_correction. */
+int lrbms3_assemble_dirichlet_correction(lrbms3_ctx* ctx, int32_t Q, const double* lam, double* D_corr, void* stream);
+
+/* The corrector problems (reference block_swipdg.py:227-316) of nmark marked subdomains at once: SWIPDG on N(m) = m + face
+ * neighbours (<= 7 subdomains, the slots of nbr[m]) with Dirichlet outer boundary, rhs = L2 functional of f, restricted to m.
+ *   theta [Q] host, marked [nmark] host (in [0, S), no duplicates: LRBMS_E_INVALID otherwise), b [S][n], corr [nmark][n] out;
+ *   work: lrbms3_local_correction_work_size(nmark) doubles -- everything lives there (no allocation in the call), its content on
+ *   entry does not matter;  info (host, may be NULL) [nmark][2] = iterations, final relative residual.
+ * A batched multi-kernel PCG (vectors [nmark][7][n], block-Jacobi from the uncorrected element blocks, scalars per problem on
+ * the device, polled every 16 iterations); the matvec reads every combined block once per iteration for all problems that
+ * contain its subdomain.  A problem is frozen at the first iteration at which its own residual meets rtol or p.Ap <= 0: its result
+ * and its info row do not depend on what else is in the batch.  LRBMS_E_NOT_CONVERGED (message naming the subdomain) if a
+ * problem is above rtol after max_iter or hit p.Ap <= 0 (cells of high aspect ratio can make a neighbourhood operator
+ * indefinite).  Needs S_ext == S (LRBMS_E_INVALID).  2D: lrbms_local_correction_work_size / lrbms_local_correction_solve. */
+int64_t lrbms3_local_correction_work_size(lrbms3_ctx* ctx, int32_t nmark);
+int lrbms3_local_correction_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, int32_t nmark, const int32_t* marked,
+                                  const double* A_diag, const double* A_cpl, const double* D_corr, const double* b, double* work,
+                                  double* corr, double rtol, int32_t max_iter, double* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

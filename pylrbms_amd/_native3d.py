@@ -72,6 +72,11 @@ SIGNATURES3 = {
                                                      c_i32, _P_DBL, c_vp]),
     'lrbms3_reduced_implicit_euler_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                          c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    # online enrichment
+    'lrbms3_assemble_dirichlet_correction': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'lrbms3_local_correction_work_size': (c_i64, [c_vp, c_i32]),
+    'lrbms3_local_correction_solve': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_i32, _P_I32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32,
+                                                     _P_DBL, c_vp]),
 }
 
 _bound = None
@@ -553,3 +558,38 @@ class Native3DContext(_native.ContextBase):
                                                         self._stream())
         self._check(rc, 'lrbms3_reduced_implicit_euler_src')
         return U, (int(info[0]), float(info[1]))
+
+    # ------------------------------------------------------------------ online enrichment
+    def assemble_dirichlet_correction(self, lam):
+        """D_corr [Q, S, 6, ncf, 100]: per coupling face, Dirichlet-face block minus the inner-face own / own block in A_diag."""
+        Q, sp = lam.shape[0], self.spec
+        D_corr = self.empty(Q, self.S, 6, self.ncf, 100)
+        rc = self.lib.lrbms3_assemble_dirichlet_correction(self.handle, Q, self._ptr(lam, (Q, self.S_ext, self.n_T, sp.lam_stride), 'lam'),
+                                                           c_vp(D_corr.data_ptr()), self._stream())
+        self._check(rc, 'lrbms3_assemble_dirichlet_correction')
+        return D_corr
+
+    def local_correction_work_size(self, nmark):
+        return int(self.lib.lrbms3_local_correction_work_size(self.handle, int(nmark)))
+
+    def local_correction_solve(self, Q, theta, marked, A_diag, A_cpl, D_corr, b, rtol=1e-10, max_iter=20000, work=None):
+        """The corrector problems of the subdomains ``marked`` in one native call -> corr [nmark, n], info [nmark, 2] (host:
+        iterations, final relative residual)."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        mk = np.ascontiguousarray(marked, dtype=np.int32).reshape(-1)
+        nmark = int(mk.size)
+        assert th.shape == (Q,) and nmark >= 1
+        if work is None:
+            work = self.empty(self.local_correction_work_size(nmark))
+        elif work.numel() < self.local_correction_work_size(nmark):
+            raise NativeError('work buffer too small')
+        corr = self.empty(nmark, self.n)
+        info = np.zeros((nmark, 2))
+        rc = self.lib.lrbms3_local_correction_solve(self.handle, Q, th.ctypes.data_as(_P_DBL), nmark, mk.ctypes.data_as(_P_I32),
+                                                    self._ptr(A_diag, (Q, self.S, self.n_T, 5, 100), 'A_diag'),
+                                                    self._ptr(A_cpl, (Q, self.S, 6, self.ncf, 100), 'A_cpl'),
+                                                    self._ptr(D_corr, (Q, self.S, 6, self.ncf, 100), 'D_corr'),
+                                                    self._ptr(b, (self.S, self.n), 'b'), c_vp(work.data_ptr()), c_vp(corr.data_ptr()),
+                                                    float(rtol), int(max_iter), info.ctypes.data_as(_P_DBL), self._stream())
+        self._check(rc, 'lrbms3_local_correction_solve')
+        return corr, info

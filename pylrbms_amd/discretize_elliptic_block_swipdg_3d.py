@@ -10,7 +10,11 @@ only (:22-23); this module gives the 3D / P2 path the same surface for the calls
     u = rd.solve(mu);  rd.estimate(u, mu)                 # online (estimators.py:45-130)
 
 ``grid_and_problem_data``: the dict of ``pylrbms_amd.multiscale_problem3d.init_grid_and_problem`` (grid, lambda functions and
-coefficient functionals, lambda_bar / lambda_hat, f, mu_bar / mu_hat).  ``d.solve(mu)`` generates snapshots (block-Jacobi CG)."""
+coefficient functionals, lambda_bar / lambda_hat, f, mu_bar / mu_hat).  ``d.solve(mu)`` generates snapshots (block-Jacobi CG).
+
+Online enrichment (reductor.py:75-78, online_enrichment.py) is opt-in: ``discretize(..., online_enrichment=True)`` also assembles
+the Dirichlet correction blocks of the neighbourhood corrector problems; ``d.solve_for_local_correction(s)``,
+``reductor.enrich_local`` / ``enrich_local_batch`` and ``AdaptiveEnrichment`` then run on the 3D objects."""
 import numpy as np
 
 from pylrbms_amd._native import NativeError
@@ -18,12 +22,25 @@ from pylrbms_amd.engine3d import Engine3D
 from pylrbms_amd.reductor import ExtensionError, LocalBasisSlab
 
 
+class BlockSpace3D:
+    """What ``AdaptiveEnrichment`` and its callbacks read of a (block) vector space: ``num_blocks`` and ``dim``."""
+
+    def __init__(self, num_blocks, dim):
+        self.num_blocks, self.dim = int(num_blocks), int(dim)
+
+
+_NEEDS_KEYWORD = 'online enrichment in 3D needs the corrector data: discretize(..., online_enrichment=True)'
+
+
 class BlockDiscretization3D:
     _src = None                        # the affine source record (``sources3d.setup_sources3d``); None: one component, coefficient 1
     _time_dependent_source = False     # the parabolic subclass takes coefficients c(mu, t)
 
-    def __init__(self, p, device_index=0):
+    def __init__(self, p, device_index=0, online_enrichment=False):
         self.grid = p['grid']
+        self.online_enrichment = bool(online_enrichment)
+        if self.online_enrichment and getattr(self.grid, 'world_size', 1) > 1:
+            raise NotImplementedError('online_enrichment=True on a sharded 3D grid: the corrector solves need all subdomains on one rank')
         lam = p['lambda']
         f = p['f']
         comp = None
@@ -42,8 +59,9 @@ class BlockDiscretization3D:
         self.mu_bar, self.mu_hat = p['mu_bar'], p['mu_hat']
         self.engine = Engine3D(self.grid, lam['functions'], f, p['lambda_bar'], p['lambda_hat'],
                                data_degree=p.get('data_degree', 2), device_index=device_index,
-                               theta_bar=[float(c(self.mu_bar)) for c in self.coefficients]).assemble()
+                               theta_bar=[float(c(self.mu_bar)) for c in self.coefficients]).assemble(self.online_enrichment)
         self.Q = self.engine.Q
+        self.solution_space = BlockSpace3D(self.engine.S, self.engine.S * self.engine.t.n)
         self.parameter_range = p.get('parameter_range')
         if comp is not None:
             self._src = sources3d.setup_sources3d(self.engine, comp[0], comp[1], arity)
@@ -64,6 +82,26 @@ class BlockDiscretization3D:
 
     def theta(self, mu):
         return np.array([float(c(mu)) for c in self.coefficients], dtype=np.float64)
+
+    def parse_parameter(self, mu):
+        """``d.parse_parameter(mu)`` (online_enrichment.py:69): the 3D coefficient functionals take ``mu`` as it is."""
+        return mu
+
+    def solve_for_local_corrections(self, subdomains, mu, rtol=1e-12, max_iter=20000, return_info=False):
+        """The correctors of ``subdomains`` at ``mu`` in one batched native solve: [len(subdomains), n] (device).  Each is the
+        SWIPDG problem on the subdomain and its face neighbours with Dirichlet data on the outer boundary and the load b(mu),
+        restricted to the subdomain (block_swipdg.py:227-316).  ``info`` [len, 2]: iterations, final relative residual."""
+        if not self.online_enrichment:
+            raise NotImplementedError(_NEEDS_KEYWORD)
+        eng = self.engine
+        marked = [eng.local.index(int(ii)) for ii in subdomains]
+        corr, info = eng.local_corrections(self.theta(mu), marked, rtol=rtol, max_iter=max_iter, b=self._load_vector(mu))
+        return (corr, info) if return_info else corr
+
+    def solve_for_local_correction(self, subdomain, Us, mu, rtol=1e-12, max_iter=20000):
+        """``d.solve_for_local_correction(subdomain, Us, mu)`` (block_swipdg.py:227-316) -> [n] (device).  ``Us`` feeds only the
+        Dirichlet lift the reference has commented out: accepted and unused."""
+        return self.solve_for_local_corrections([subdomain], mu, rtol=rtol, max_iter=max_iter)[0]
 
     def shape_functions(self, subdomain, order=0):
         """``d.shape_functions(subdomain, order)`` (discretize_elliptic_block_swipdg.py:190-203 in 2D): the constant (order 0)
@@ -179,6 +217,7 @@ class ReducedDiscretization3D:
         self.reductor, self.d, self.out = reductor, reductor.d, out
         self.rhs_red_K, self.r_fd_K = rhs_red_K, r_fd_K
         self.N = out['B_sys'].shape[-1]
+        self.solution_space = BlockSpace3D(self.d.engine.S, sum(reductor.local_sizes()))
 
     @property
     def operators(self):
@@ -308,8 +347,11 @@ class LRBMSReductor3D(LocalBasisSlab):
         reduce()                   one pass of the hot path (reductor.py:33-73)
         reconstruct(u), reconstruct_local(u, ii)
 
-    Gram-Schmidt runs on the device: the product is applied by ``lrbms3_energy_product_apply``, the rest are batched products.
-    ``enrich_local`` (reductor.py:75-78) needs the neighbourhood corrector solves, which exist in 2D only."""
+        enrich_local(ii, U, mu), enrich_local_batch(subdomains, U, mu)
+                                   corrector solve(s) on the neighbourhood(s), then extend the basis / bases (reductor.py:75-78);
+                                   need ``discretize(..., online_enrichment=True)``
+
+    Gram-Schmidt runs on the device: the product is applied by ``lrbms3_energy_product_apply``, the rest are batched products."""
 
     def __init__(self, d, bases=None, products=None, order=None):
         import torch
@@ -383,7 +425,22 @@ class LRBMSReductor3D(LocalBasisSlab):
             self._append_columns(v, ok & mask)
 
     def enrich_local(self, subdomain, U, mu=None):
-        raise NotImplementedError('online enrichment (reductor.py:75-78: neighbourhood corrector solves) is built for the 2D path only')
+        """Reference reductor.py:75-78: corrector solve on the neighbourhood of ``subdomain`` at ``mu``, then extend its basis;
+        ``ExtensionError3D`` if the corrector is (numerically) in the span of the basis.  ``U`` feeds only the commented-out
+        Dirichlet lift (reductor.py:76)."""
+        self.extend_basis_local(subdomain, self.d.solve_for_local_correction(subdomain, None, mu))
+
+    def enrich_local_batch(self, subdomains, U, mu=None):
+        """The loop of online_enrichment.py:49-50 as ONE batched corrector solve and one masked Gram-Schmidt step.  Returns the
+        subdomains whose basis grew (a corrector already in the span of its basis is skipped)."""
+        subdomains = [int(ii) for ii in subdomains]
+        if not subdomains:
+            if not self.d.online_enrichment:
+                raise NotImplementedError(_NEEDS_KEYWORD)
+            return []
+        corr = self.d.solve_for_local_corrections(subdomains, mu)
+        ok = self._extend_marked([self.d.engine.local.index(ii) for ii in subdomains], corr[:, :, None])
+        return [ii for ii, flag in zip(subdomains, ok) if flag]
 
     # ------------------------------------------------------------------ reduce / reconstruct
     def reduce(self):
@@ -416,8 +473,11 @@ class LRBMSReductor3D(LocalBasisSlab):
         return self._V[i] @ u[i]
 
 
-def discretize(grid_and_problem_data, device_index=0):
-    d = BlockDiscretization3D(grid_and_problem_data, device_index=device_index)
+def discretize(grid_and_problem_data, device_index=0, online_enrichment=False):
+    """``online_enrichment=True`` also assembles the corrector data (``D_corr``: as large as the coupling blocks, 157 MB at config 5)
+    that ``solve_for_local_correction(s)``, ``enrich_local`` and ``enrich_local_batch`` need; without it they raise
+    ``NotImplementedError``.  Not available on a sharded grid."""
+    d = BlockDiscretization3D(grid_and_problem_data, device_index=device_index, online_enrichment=online_enrichment)
     eng = d.engine
     data = {'grid': d.grid, 'engine': eng, 'operators': eng.ops}
     return d, data

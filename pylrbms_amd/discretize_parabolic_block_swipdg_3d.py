@@ -186,6 +186,9 @@ class ParabolicLRBMSReductor3D(LRBMSReductor3D):
     def enrich_local(self, subdomain, U, mu=None):
         raise NotImplementedError('online enrichment is not built for the parabolic 3D path')
 
+    def enrich_local_batch(self, subdomains, U, mu=None):
+        raise NotImplementedError('online enrichment is not built for the parabolic 3D path')
+
     def reduce(self):
         rd = super().reduce()
         M_red = self.d.engine.ctx.project_mass(self._V.contiguous())

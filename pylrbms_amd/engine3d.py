@@ -7,6 +7,7 @@ Data layout in HBM (fp64, C-contiguous; S local subdomains, S_ext = S + halo):
     A_diag [Q][S][n_T][5][100]    SWIPDG blocks, block-ELL over the element adjacency template (10 x 10 blocks, P2)
     P_diag [S][n_T][5][100]       local energy product at mu_bar (the same pattern; local to every subdomain)
     A_cpl  [Q][S][6][ncf][100]    coupling blocks per side face
+    D_corr [Q][S][6][ncf][100]    Dirichlet correction of the neighbourhood corrector problems (``assemble(online_enrichment=True)``)
     V      [S_ext][n][N]          local reduced bases, DoF-major
     outputs of a pass: Native3DContext.out_shapes (factored layout, include/lrbms3d_hip.h)
 """
@@ -56,7 +57,9 @@ class Engine3D:
         self.lbar = c.from_numpy(np.stack([sample(lambda_bar, xb + o) for o in org]))
         self.ops = None
 
-    def assemble(self):
+    def assemble(self, online_enrichment=False):
+        """``online_enrichment``: also assemble ``D_corr`` (a third coupling-sized array, 157 MB at config 5), the data of
+        ``local_corrections``."""
         c = self.ctx
         A_diag, A_cpl = c.assemble_system(self.lam)
         b, f2, ceps, bdiv = c.assemble_rhs(self.f_smp, self.lhat)
@@ -65,6 +68,8 @@ class Engine3D:
         P_diag = c.assemble_energy_product(self.theta_bar, self.lam)          # K6: local energy product at mu_bar
         self.ops = dict(A_diag=A_diag, A_cpl=A_cpl, b=b, f2=f2, ceps=ceps, bdiv=bdiv, ebar=ebar, Aaa=Aaa, Aab=Aab, Bbb=Bbb, Cf=Cf,
                         P_diag=P_diag)
+        if online_enrichment:
+            self.ops['D_corr'] = c.assemble_dirichlet_correction(self.lam)
         return self
 
     def alloc_outputs(self, N):
@@ -97,6 +102,15 @@ class Engine3D:
 
     def reduced_solve(self, theta, out, rtol=1e-13, max_iter=5000):
         return self.ctx.reduced_solve(self.Q, theta, out['B_sys'], out['rhs_red'], rtol=rtol, max_iter=max_iter)
+
+    def local_corrections(self, theta, marked, rtol=1e-12, max_iter=20000, b=None):
+        """The neighbourhood corrector problems of the local subdomains ``marked`` at ``theta`` in one native call
+        (``lrbms3_local_correction_solve``): (corr [nmark, n], info [nmark, 2] = iterations, final relative residual).
+        ``b`` [S, n]: the load vector (default: the assembled one)."""
+        if self.ops is None or 'D_corr' not in self.ops:
+            raise NativeError('assemble(online_enrichment=True) must run before local_corrections()')
+        return self.ctx.local_correction_solve(self.Q, theta, marked, self.ops['A_diag'], self.ops['A_cpl'], self.ops['D_corr'],
+                                               self.ops['b'] if b is None else b, rtol=rtol, max_iter=max_iter)
 
     def interpolate(self, fn):
         """P2 nodal interpolant as a block DG vector [S, n] (host)."""

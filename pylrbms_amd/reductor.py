@@ -92,6 +92,20 @@ class LocalBasisSlab:
         self._nloc[idx] += 1
         return ok_host
 
+    def _extend_marked(self, marked, vecs):
+        """Extend the bases of the local subdomains ``marked`` by the blocks ``vecs`` [len(marked), n, 1]; returns the
+        per-entry success flags (a block in the span of its basis is skipped)."""
+        import torch
+        eng = self.d.engine
+        full = eng.ctx.zeros(eng.S, eng.t.n, 1)
+        rows = torch.as_tensor(np.asarray(marked, dtype=np.int64), device=full.device)
+        full[rows] = vecs
+        v, ok = self._orthonormalize(full)
+        mask = torch.zeros(eng.S, dtype=torch.bool, device=full.device)
+        mask[rows] = True
+        ok_host = self._append_columns(v, ok & mask)
+        return [bool(ok_host[i]) for i in marked]
+
     def _gram_schmidt_extend(self, U):
         """Extend EVERY local basis by the columns of U [S, n, L], one after the other (all-or-nothing per column)."""
         for k in range(U.shape[2]):
@@ -383,20 +397,6 @@ class LRBMSReductor(LocalBasisSlab):
         ok = self._extend_marked([eng.local.index(ii)], U.tensor[:, :, :1])
         if not ok[0]:
             raise ExtensionError('local correction is (numerically) in the span of the local basis')
-
-    def _extend_marked(self, marked, vecs):
-        """Extend the bases of the local subdomains ``marked`` by the blocks ``vecs`` [len(marked), n, 1]; returns the
-        per-entry success flags (a block in the span of its basis is skipped)."""
-        import torch
-        eng = self.d.engine
-        full = eng.ctx.zeros(eng.S, eng.t.n, 1)
-        rows = torch.as_tensor(np.asarray(marked, dtype=np.int64), device=full.device)
-        full[rows] = vecs
-        v, ok = self._orthonormalize(full)
-        mask = torch.zeros(eng.S, dtype=torch.bool, device=full.device)
-        mask[rows] = True
-        ok_host = self._append_columns(v, ok & mask)
-        return [bool(ok_host[i]) for i in marked]
 
     def _flush_local(self):
         import torch
