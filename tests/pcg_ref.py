@@ -218,3 +218,159 @@ def spd_check(M):
     sym = 0.5 * (M + M.T)
     return float(np.linalg.eigvalsh(sym).min()), float(np.abs(M - M.T).max() / np.abs(M).max())
 
+
+
+# ------------------------------------------------------------------------------------------- neighbourhood correctors
+SIDE_TO_SLOT_2D = (0, 1, 3, 4)            # csrc/lrbms_dev.h side_to_slot
+
+
+def diagonal_blocks(A, bs):
+    """The bs x bs diagonal blocks [n / bs, bs, bs] of a sparse matrix."""
+    A = sp.csr_matrix(A)
+    first = bs * np.arange(A.shape[0] // bs)
+    blocks = np.empty((first.size, bs, bs))
+    for i in range(bs):
+        for j in range(bs):
+            blocks[:, i, j] = np.asarray(A[first + i, first + j]).ravel()
+    return blocks
+
+
+def block_jacobi(Minv):
+    """z = M^-1 r for the inverse diagonal blocks Minv [nb, bs, bs]; takes r [n] or [n, m]."""
+    bs = Minv.shape[1]
+    return _as2d(lambda r: np.einsum('eij,ejm->eim', Minv, r.reshape(-1, bs, r.shape[1])).reshape(-1, r.shape[1]))
+
+
+def hood_operator_2d(A_diag, A_cpl, D_corr, theta, template, nbr, ii):
+    """The operator of the corrector problem of subdomain ii (enrich.hip ``hood_block``, restated block by block) from the
+    assembled arrays A_diag [Q, S, n_T, 4, 9], A_cpl / D_corr [Q, S, 4, ncf, 9] -> (A csr on the present members of N(ii) in slot
+    order, dofs: the index of every row in the [S, n] numbering -- ``dofs // n == ii`` picks the own part).
+
+    Member in slot s (subdomain kk = nbr[ii, s]), element e: block 0 is the diagonal block, block 1 + f the one of the element
+    across face f inside kk.  Across a side face: the centre (s == 2) couples through A_cpl with every member it has (a physical
+    side has none: its boundary term is in A_diag already), another member couples with the centre only (side slot == 4 - s).
+    Every other side face of a non-centre member that has a subdomain behind it (nbr[kk, side slot] >= 0) lies on the outer
+    boundary of N(ii): D_corr is added to the element's diagonal block; nothing is added on physical sides."""
+    t = template
+    nT, n = t.n_T, t.n
+    th = np.asarray(theta, dtype=np.float64)
+    nbr = np.asarray(nbr)
+    Ad = np.einsum('q,qsebk->sebk', th, np.asarray(A_diag, dtype=np.float64)).reshape(-1, nT, 4, 3, 3)
+    Ac = np.einsum('q,qsfpk->sfpk', th, np.asarray(A_cpl, dtype=np.float64)).reshape(-1, 4, t.ncf, 3, 3)
+    Dc = np.einsum('q,qsfpk->sfpk', th, np.asarray(D_corr, dtype=np.float64)).reshape(-1, 4, t.ncf, 3, 3)
+    slots = [s for s in range(5) if nbr[ii, s] >= 0]
+    where = {s: k for k, s in enumerate(slots)}
+    nb_elem, pos, out = np.asarray(t.nb_elem), np.asarray(t.elem_side_pos), np.asarray(t.nb_elem_out)
+    ii3, jj3 = np.meshgrid(np.arange(3), np.arange(3), indexing='ij')
+    e = np.arange(nT)
+    rows, cols, data = [], [], []
+
+    def put(member, er, col_member, ec, blocks):
+        rows.append((where[member] * n + 3 * er[:, None, None] + ii3).ravel())
+        cols.append((where[col_member] * n + 3 * ec[:, None, None] + jj3).ravel())
+        data.append(blocks.ravel())
+
+    for s in slots:
+        kk = int(nbr[ii, s])
+        put(s, e, s, e, Ad[kk, :, 0])
+        for f in range(3):
+            inner = nb_elem[:, f] >= 0
+            put(s, e[inner], s, nb_elem[inner, f], Ad[kk, inner, 1 + f])
+            for side in range(4):
+                on = nb_elem[:, f] == -(1 + side)
+                if not on.any():
+                    continue
+                s2 = SIDE_TO_SLOT_2D[side]
+                if s == 2 and nbr[ii, s2] >= 0:
+                    put(s, e[on], s2, out[on, f], Ac[kk, side, pos[on, f]])
+                elif s != 2 and s2 == 4 - s:
+                    put(s, e[on], 2, out[on, f], Ac[kk, side, pos[on, f]])
+                elif s != 2 and nbr[kk, s2] >= 0:
+                    put(s, e[on], s, e[on], Dc[kk, side, pos[on, f]])
+    m = len(slots) * n
+    A = sp.csr_matrix((np.concatenate(data), (np.concatenate(rows), np.concatenate(cols))), shape=(m, m))
+    dofs = np.concatenate([int(nbr[ii, s]) * n + np.arange(n) for s in slots])
+    return A, dofs
+
+
+def hood_block_jacobi_2d(A_hood):
+    """Minv [5 n_T', 3, 3] of k_hood_pcg: the inverse (``inv3``) of every 3 x 3 diagonal block of the corrected neighbourhood
+    operator -- D_corr on the non-centre members included."""
+    return np.linalg.inv(diagonal_blocks(A_hood, 3))
+
+
+def hood_block_jacobi_3d(A_sys, dofs):
+    """Minv [n_el, 10, 10] of lrbms3_local_correction_solve: the inverse of every 10 x 10 element diagonal block of the
+    UNCORRECTED system matrix (k3f_block_inverse on the combined A_diag; one inverse per element for all problems) on the rows
+    ``dofs`` of a neighbourhood (whole elements)."""
+    first = np.asarray(dofs).reshape(-1, 10)[:, 0]
+    A = sp.csr_matrix(A_sys)
+    blocks = np.empty((first.size, 10, 10))
+    for i in range(10):
+        for j in range(10):
+            blocks[:, i, j] = np.asarray(A[first + i, first + j]).ravel()
+    return np.linalg.inv(blocks)
+
+
+def pcg_history(apply_A, apply_Minv, b, kmax):
+    """The iterates x_1 .. x_kmax of ``pcg_iterate`` for one right-hand side b [n] in one sweep -> (X [kmax, n], ratios
+    [kmax]); row k - 1 is x_k, by the recurrences of ``pcg_iterate``."""
+    b = np.asarray(b, dtype=np.float64)
+    x, r = np.zeros_like(b), b.copy()
+    z = apply_Minv(r)
+    p, rz, n0 = z.copy(), float(r @ z), float(np.linalg.norm(b))
+    X, ratios = np.empty((kmax, b.size)), np.empty(kmax)
+    for k in range(kmax):
+        Ap = apply_A(p)
+        pAp = float(p @ Ap)
+        alpha = rz / pAp if pAp != 0.0 else 0.0
+        x = x + alpha * p
+        r = r - alpha * Ap
+        z = apply_Minv(r)
+        rz_new = float(r @ z)
+        beta = rz_new / rz if rz != 0.0 else 0.0
+        p = z + beta * p
+        rz = rz_new
+        X[k], ratios[k] = x, (np.linalg.norm(r) / n0 if n0 > 0.0 else 0.0)
+    return X, ratios
+
+
+class CorrectorRef:
+    """One corrector problem for the iterate tests: operator A (sparse) and load b on the neighbourhood, ``own`` (the rows of
+    the marked subdomain: what the solver exports return) and the inverse diagonal blocks Minv of its preconditioner."""
+
+    def __init__(self, A, b, own, Minv):
+        self.A, self.b, self.own, self.Minv = sp.csr_matrix(A), np.asarray(b, dtype=np.float64), own, Minv
+        self._hist = {}
+
+    def history(self, kmax, Minv=None):
+        """(x_k restricted to ``own`` [kmax, n], ratios [kmax]) with the cell's preconditioner, or with another one (Minv: inverse
+        diagonal blocks, or None inside a 1-tuple for the identity)."""
+        if Minv is None:
+            if self._hist.get('kmax', 0) < kmax:
+                X, ratios = pcg_history(lambda v: self.A @ v, block_jacobi(self.Minv), self.b, kmax)
+                self._hist = {'kmax': kmax, 'X': X[:, self.own], 'ratios': ratios}
+            return self._hist['X'][:kmax], self._hist['ratios'][:kmax]
+        apply = (lambda r: r) if Minv[0] is None else block_jacobi(Minv)
+        X, ratios = pcg_history(lambda v: self.A @ v, apply, self.b, kmax)
+        return X[:, self.own], ratios
+
+    def iterate(self, k):
+        """The ``reference(k)`` of ``check_iterates``: (x_k on ``own`` [n, 1], ratio [1])."""
+        X, ratios = self.history(k)
+        return X[k - 1][:, None], ratios[k - 1:k]
+
+    def stop(self, rtol, cap=2000):
+        """(j, ratios [j]): the first iteration j with |r_j| / |b| <= rtol, as every solver export stops."""
+        kmax = 16
+        while True:
+            _, ratios = self.history(kmax)
+            hit = np.nonzero(ratios <= rtol)[0]
+            if hit.size:
+                return int(hit[0]) + 1, ratios[:hit[0] + 1]
+            assert kmax < cap, 'no iterate below rtol within {} iterations'.format(cap)
+            kmax *= 2
+
+    def solve(self):
+        from scipy.sparse.linalg import spsolve
+        return spsolve(self.A.tocsc(), self.b)[self.own]

@@ -29,6 +29,11 @@ def _problem(name, config):
     ('multiscale_problem', {'num_subdomains': [3, 3], 'coarse_per_subdomain': 6}, 1.0),           # n_T = 288: 2 elements / thread
     ('multiscale_problem', {'num_subdomains': [2, 2], 'coarse_per_subdomain': 3}, 0.6),           # odd k, corner hoods only
     ('OS2015_academic_problem', {'num_subdomains': [1, 3], 'half_num_fine_elements_per_subdomain_and_dim': 6}, 0.5),  # kx != ky, strip
+    # the launch forms of k_hood_pcg the grids above do not reach (n_T = 8 k^2 on k x k squares per subdomain; the dispatch mirror is
+    # tests/test_corrector_iterates_host.py): <1,1024> at k = 5, <4,1024> at k = 8, <8,1024> at k = 11 (104 KB of dynamic LDS)
+    ('OS2015_academic_problem', {'num_subdomains': [3, 3], 'half_num_fine_elements_per_subdomain_and_dim': 15}, 0.1),
+    ('OS2015_academic_problem', {'num_subdomains': [3, 3], 'half_num_fine_elements_per_subdomain_and_dim': 24}, 0.1),
+    ('OS2015_academic_problem', {'num_subdomains': [3, 3], 'half_num_fine_elements_per_subdomain_and_dim': 33}, 0.1),
 ])
 def test_local_corrections_match_the_oracle(name, config, mu):
     from pylrbms_amd.discretize_elliptic_block_swipdg import discretize
