@@ -153,6 +153,26 @@ int lrbms3_project_estimate_phase(lrbms3_ctx* ctx, int32_t phase, int32_t Q, int
                                   double* rhs_red, double* G_nc, double* G_bb, double* G_rdd, double* G_ab, double* G_aa,
                                   double* r_fd, double* Rb, double* Yb, double* Dp, double* Xab, double* As, double* Cn, void* stream);
 
+/* Incremental re-projection: restrict every following lrbms3_project_estimate, lrbms3_project_estimate_phase and
+ * lrbms3_project_sources of this context to the subdomains whose basis changed.  changed [count] is a HOST array of strictly
+ * ascending indices in the S_ext ordering, in [0, S_ext) (a changed halo slab re-projects the side arrays of its local neighbours).
+ * Everything phase 1 writes depends on the subdomain's own slab only, everything phase 2 writes on the slabs of the subdomain and
+ * of its face neighbours (nbr; no diagonal dependence), so the library derives two lists from `changed` and the neighbour table:
+ *   own list    the changed indices < S;
+ *   side list   the local subdomains that are changed or have a changed face neighbour (ascending).
+ * Under the restriction a pass writes
+ *   the own arrays of exactly the own list: G_aa, G_ab, G_nc, G_bb, G_rdd, r_fd, rhs_red, the diagonal slot of B_sys, Yb, Dp, Xab,
+ *   Cn and the three parts of `work` (with padded side tables the listed rows of Yb, Dp, Xab are cleared first, not the arrays);
+ *   the side arrays of exactly the side list: Rb, As and the six coupling slots of B_sys;
+ * every other row of every output and of `work` keeps its bits; strides stay those of all S subdomains.  Phase 1 covers the own
+ * list and phase 2 the side list; 1 followed by 2 stays bit-identical to 0.  lrbms3_project_sources writes the rows of the own list.
+ * Launch sizes, the automatic K-split included, follow the list lengths; an empty list launches nothing.
+ * The lists are copied before the call returns (after a device synchronisation: a pass in flight keeps the lists it started with).
+ * count == 0 lifts the restriction (changed may be NULL), and so does lrbms3_mesh_upload.  LRBMS_E_INVALID with a message, and
+ * nothing changed, for count < 0, an index out of range, a list that is not strictly ascending, and a context without a mesh.
+ * 2D: lrbms_fused_set_subset. */
+int lrbms3_pass_set_subset(lrbms3_ctx* ctx, const int32_t* changed, int32_t count);
+
 /* Per-kernel device timing of the pass, as lrbms_kernel_timing / lrbms_kernel_timing_read. */
 int lrbms3_kernel_timing(lrbms3_ctx* ctx, int32_t enable);
 int lrbms3_kernel_timing_read(lrbms3_ctx* ctx, char* names, int64_t names_cap, double* ms, int32_t cap, int32_t* count);

@@ -34,6 +34,7 @@ SIGNATURES3 = {
     'lrbms3_work_size': (c_i64, [c_vp, c_i32, c_i32]),
     'lrbms3_project_estimate': (ctypes.c_int, [c_vp, c_i32, c_i32] + [c_vp] * 26),
     'lrbms3_project_estimate_phase': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 26),
+    'lrbms3_pass_set_subset': (ctypes.c_int, [c_vp, _P_I32, c_i32]),
     'lrbms3_kernel_timing': (ctypes.c_int, [c_vp, c_i32]),
     'lrbms3_kernel_timing_read': (ctypes.c_int, [c_vp, ctypes.c_char_p, c_i64, _P_DBL, c_i32, _P_I32]),
     'lrbms3_reduced_estimate': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL] + [c_vp] * 18 + [c_dbl, c_vp, c_vp]),
@@ -237,6 +238,16 @@ class Native3DContext(_native.ContextBase):
         rc = self.lib.lrbms3_project_estimate_phase(self.handle, int(phase), Q, N, *args, self._stream())
         self._check(rc, 'lrbms3_project_estimate_phase')
         return out
+
+    def pass_set_subset(self, changed):
+        """Restrict the following ``project_estimate`` / ``project_sources`` calls to the subdomains ``changed`` (strictly ascending
+        indices in the S_ext ordering) and the face neighbours their side arrays reach; ``None`` or empty: all -- incremental
+        re-projection after online enrichment (include/lrbms3d_hip.h: lrbms3_pass_set_subset)."""
+        if changed is None or len(changed) == 0:
+            self._check(self.lib.lrbms3_pass_set_subset(self.handle, None, 0), 'lrbms3_pass_set_subset')
+            return
+        arr = np.ascontiguousarray(changed, dtype=np.int32).reshape(-1)
+        self._check(self.lib.lrbms3_pass_set_subset(self.handle, arr.ctypes.data_as(_P_I32), int(arr.size)), 'lrbms3_pass_set_subset')
 
     # ------------------------------------------------------------------ online
     def reduced_estimate(self, Q, theta, u, out, ops, hdiam):
@@ -453,13 +464,15 @@ class Native3DContext(_native.ContextBase):
         self._check(rc, 'lrbms3_assemble_source_gram')
         return F2
 
-    def project_sources(self, Q, b_K, bdiv_K, V, work):
+    def project_sources(self, Q, b_K, bdiv_K, V, work, out=None):
         """rhs_red_K [K, S, N] = V_s^T b_K[j, s] and r_fd_K [K, S, QN] = sum_e bdiv_K[j, s, e] div(R_self)_e; ``work`` is the work
-        buffer of a finished ``project_estimate`` pass on the same ``V`` (its flux image R_self lies at offset 0)."""
+        buffer of a finished ``project_estimate`` pass on the same ``V`` (its flux image R_self lies at offset 0).  ``out``: the
+        two arrays to write into (a restricted pass, ``pass_set_subset``, writes the rows of its own list only)."""
         K, N, S = int(b_K.shape[0]), int(V.shape[2]), self.S
         if work.numel() < S * self.n_rt * Q * N:
             raise NativeError('work: not the work buffer of a pass with this Q and N')
-        rhs_K, rfd_K = self.empty(K, S, N), self.empty(K, S, Q * N)
+        rhs_K, rfd_K = out if out is not None else (self.empty(K, S, N), self.empty(K, S, Q * N))
+        self._ptr(rhs_K, (K, S, N), 'rhs_red_K'), self._ptr(rfd_K, (K, S, Q * N), 'r_fd_K')
         rc = self.lib.lrbms3_project_sources(self.handle, Q, N, K, self._ptr(b_K, (K, S, self.n), 'b_K'),
                                              self._ptr(bdiv_K, (K, S, self.n_T), 'bdiv_K'), self._ptr(V, (self.S_ext, self.n, N), 'V'),
                                              c_vp(work.data_ptr()), c_vp(rhs_K.data_ptr()), c_vp(rfd_K.data_ptr()), self._stream())

@@ -66,6 +66,11 @@ struct lrbms3_ctx : lrbms_ctx_base {
   double* src_phi = nullptr;       // [64][64] device (owned): source coefficients of lrbms3_reduced_solve_batch_src, first use
   int num_cus = 0;                 // compute units of the device (lrbms3_combine_sources sizes its grid by them), first use
   bool side_padding = false;       // some side has fewer faces than ncf (unequal cubes per direction): padded factor rows exist
+  // restricted pass (lrbms3_pass_set_subset): device lists [S] each (one ctx-owned allocation, made at the first restriction)
+  bool sub_active = false;
+  int* sub_own = nullptr;          // changed local subdomains, ascending: phase 1 runs over them
+  int* sub_side = nullptr;         // local subdomains that are changed or have a changed face neighbour, ascending: phase 2
+  int sub_own_n = 0, sub_side_n = 0;
 };
 
 namespace {
@@ -299,11 +304,21 @@ __device__ inline bool xcd_block(int nblk, int S, int& xblk, int& s) {
 }
 inline unsigned xcd_grid(int nblk, int S) { return (unsigned)((S + 7) / 8 * 8 * nblk); }
 
-__global__ __launch_bounds__(256) void k3_flux(T3 t, int Q, int N, int rbeg, int rend, const double* __restrict__ V,
-                                               const double* __restrict__ Cf, double* __restrict__ Rs, double* __restrict__ Rb) {
+// The same decode for a pass restricted to a list of subdomains (lrbms3_pass_set_subset): the chunks of 8 are formed over the cnt
+// POSITIONS of the list and the subdomain is list[position]; every stride and every neighbour lookup keeps using the subdomain.
+// list == nullptr (a kernel argument: the branch is wave-uniform): no restriction, position == subdomain, cnt == t.S.
+__device__ inline bool xcd_block_list(int nblk, int cnt, const int* __restrict__ list, int& xblk, int& s) {
+  if (!xcd_block(nblk, cnt, xblk, s)) return false;
+  if (list) s = list[s];
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k3_flux(T3 t, int Q, int N, int rbeg, int rend, const int* __restrict__ list, int cnt,
+                                               const double* __restrict__ V, const double* __restrict__ Cf, double* __restrict__ Rs,
+                                               double* __restrict__ Rb) {
   const int QN = Q * N, nrows = rend;          // rows [rbeg, rend) of [own faces | side faces]
   int s, xblk;
-  if (!xcd_block((rend - rbeg + 4 * FLUX_R * FLUX_LOOP - 1) / (4 * FLUX_R * FLUX_LOOP), t.S, xblk, s)) return;
+  if (!xcd_block_list((rend - rbeg + 4 * FLUX_R * FLUX_LOOP - 1) / (4 * FLUX_R * FLUX_LOOP), cnt, list, xblk, s)) return;
   const int lane = threadIdx.x & 63, half = lane >> 5, jl = lane & 31;
   for (int rep = 0; rep < FLUX_LOOP; ++rep) {      // a wave lives for FLUX_LOOP rows: these sweeps are bound by the wave launch rate
   const int row0 = __builtin_amdgcn_readfirstlane(rbeg + ((xblk * FLUX_LOOP + rep) * 4 + (threadIdx.x >> 6)) * FLUX_R);
@@ -380,10 +395,10 @@ __global__ __launch_bounds__(256) void k3_flux(T3 t, int Q, int N, int rbeg, int
 // the 25 us.)
 // Avg [S][n_nodes][N]: own share of the Oswald node average (0 on the physical boundary: the interpolant vanishes there);
 // As [S][6][nvs][N]: the neighbours' shares at the side nodes.  One wave per node, DoF lists through the scalar cache.
-__global__ __launch_bounds__(256) void k3_node_avg(T3 t, int N, int rbeg, int rend, const double* __restrict__ V,
-                                                   double* __restrict__ Avg, double* __restrict__ As) {
+__global__ __launch_bounds__(256) void k3_node_avg(T3 t, int N, int rbeg, int rend, const int* __restrict__ list, int cnt,
+                                                   const double* __restrict__ V, double* __restrict__ Avg, double* __restrict__ As) {
   int s, xblk;
-  if (!xcd_block((rend - rbeg + 4 * NODE_LOOP - 1) / (4 * NODE_LOOP), t.S, xblk, s)) return;          // rows [rbeg, rend) of [own nodes | side nodes]
+  if (!xcd_block_list((rend - rbeg + 4 * NODE_LOOP - 1) / (4 * NODE_LOOP), cnt, list, xblk, s)) return;          // rows [rbeg, rend) of [own nodes | side nodes]
   const int j = threadIdx.x & 63;
   const int jc = j < N ? j : N - 1;
   const int phys = t.phys[s];
@@ -439,6 +454,8 @@ struct GA {
   double *Yb, *Dp, *Xab;  // BB: rows of B R_self and |T| div div R_self at the side faces; AB: A_ab^T V at the side faces
   int ksplit;             // > 1: the items of a (subdomain, operator) are dealt to ksplit workgroups, partial results go to `part`
   double* part;           //      [batch][ksplit][pg_part_size] and k3_pg_combine sums them in a fixed order
+  const int* list;        // restricted pass (lrbms3_pass_set_subset): the nlist subdomains the launch covers; nullptr: all, nlist = t.S
+  int nlist;
 };
 
 // ------------------------------------------------------------------------------------------------- pass: MFMA pipeline
@@ -473,7 +490,7 @@ constexpr int pg_max_threads(int tiles) { return tiles <= 4 ? 1024 : (tiles <= 8
 // of 8 subdomains: same XCD, launched together.
 template <int KIND>
 struct PGBlock {
-  int b, s, q, q2, Mx, My, t2, side, part;
+  int b, pb, s, q, q2, Mx, My, t2, side, part;      // pb: b with the POSITION in the list for the subdomain (partial tiles)
   double* out;
   __device__ bool decode(const GA& a, int x) {
     const T3& t = a.t;
@@ -482,8 +499,10 @@ struct PGBlock {
     const int chunk = x / (8 * nops * ks), within = x - chunk * 8 * nops * ks;
     const int op = (within >> 3) / ks, sx = chunk * 8 + (within & 7);
     part = (within >> 3) - op * ks;
-    if (sx >= t.S) return false;
-    b = KIND == G_CPL ? ((op / 6) * t.S + sx) * 6 + op % 6 : op * t.S + sx;
+    if (sx >= a.nlist) return false;
+    pb = KIND == G_CPL ? ((op / 6) * a.nlist + sx) * 6 + op % 6 : op * a.nlist + sx;
+    const int sr = a.list ? a.list[sx] : sx;          // (wave-uniform: a kernel argument)
+    b = KIND == G_CPL ? ((op / 6) * t.S + sr) * 6 + op % 6 : op * t.S + sr;
     q = q2 = t2 = side = 0;
     if (KIND == G_SYS) {
       q = b / t.S; s = b - q * t.S; Mx = My = N;
@@ -552,7 +571,7 @@ __global__ __launch_bounds__(pg_max_threads(KIND == G_BB ? (RT > 2 ? 8 : 4) : RT
   const int NW = blockDim.x >> 6;
   PGBlock<KIND> B;
   if (!B.decode(a, blockIdx.x)) return;
-  const int b = B.b, s = B.s, q = B.q, q2 = B.q2, Mx = B.Mx, My = B.My, t2 = B.t2, side = B.side, part = B.part;
+  const int pb = B.pb, s = B.s, q = B.q, q2 = B.q2, Mx = B.Mx, My = B.My, t2 = B.t2, side = B.side, part = B.part;
   double* out = B.out;
   int nitems = KIND == G_CPL ? t.ncf : t.nT;
   if (KIND == G_CPL && t2 < 0) {        // no neighbour on that side: the block is zero (the combine kernel skips it too)
@@ -740,7 +759,7 @@ __global__ __launch_bounds__(pg_max_threads(KIND == G_BB ? (RT > 2 ? 8 : 4) : RT
   // the items of this part: a contiguous range of the traversal
   const int plen = (nitems + a.ksplit - 1) / a.ksplit, pbeg = part * plen;
   const int pend = pbeg + plen < nitems ? pbeg + plen : nitems;
-  double* P = a.ksplit > 1 ? a.part + ((long)b * a.ksplit + part) * pg_part_size<KIND>(N, QN) : nullptr;
+  double* P = a.ksplit > 1 ? a.part + ((long)pb * a.ksplit + part) * pg_part_size<KIND>(N, QN) : nullptr;
   Idx ix1, ix2;
   load_idx(pbeg + wave, ix1);
   for (int item0 = pbeg + wave; item0 < pend; item0 += NW) {
@@ -1322,7 +1341,7 @@ __global__ __launch_bounds__(256) void k3_pg_combine(GA a) {
   const int N = a.N, Q = a.Q, QN = Q * N, ks = a.ksplit;
   if (KIND == G_CPL && B.t2 < 0) return;
   const long psz = pg_part_size<KIND>(N, QN);
-  const double* P = a.part + (long)B.b * ks * psz;
+  const double* P = a.part + (long)B.pb * ks * psz;
   const int Mx = B.Mx, My = B.My, nent = Mx * My;
   for (int i = threadIdx.x; i < nent; i += 256) {
     double v = 0.0;
@@ -1361,7 +1380,8 @@ __global__ __launch_bounds__(256) void k3_pg_combine(GA a) {
 
 template <int KIND, int RT, int CT>
 void launch_pg(const GA& a, int batch, int nw, hipStream_t st) {
-  const int batch1 = batch / a.t.S * ((a.t.S + 7) / 8 * 8);     // whole chunks of 8 subdomains (PGBlock: XCD-aware block ids)
+  if (a.nlist <= 0) return;                                    // an empty list of a restricted pass: nothing to launch
+  const int batch1 = batch / a.nlist * ((a.nlist + 7) / 8 * 8);     // whole chunks of 8 subdomains (PGBlock: XCD-aware block ids)
   batch = batch1 * a.ksplit;
   constexpr int maxt = pg_max_threads(KIND == G_BB ? (RT > 2 ? 8 : 4) : RT * CT * (KIND == G_NC || KIND == G_SYS ? 2 : 1));   // NC also holds the node averages of its operands; BB: two upper tile triangles
   if (nw * 64 > maxt) nw = maxt / 64;
@@ -1391,8 +1411,9 @@ int dispatch_pg(const GA& a, int batch, int rt, int ct, int nw, hipStream_t st) 
 
 // Cn [S][nb][N] = -(P^T E W_self) at the boundary nodes: sum of the rows k3_pg<NC> left in Zb over the DoFs of the node.
 // One wave per node, its slot list through the scalar cache.
-__global__ __launch_bounds__(256) void k3_side_nc(T3 t, int N, const double* __restrict__ Zb, double* __restrict__ Cn) {
-  const int s = blockIdx.y, c = threadIdx.x & 63;
+__global__ __launch_bounds__(256) void k3_side_nc(T3 t, int N, const int* __restrict__ list, const double* __restrict__ Zb,
+                                                  double* __restrict__ Cn) {
+  const int s = list ? list[blockIdx.y] : blockIdx.y, c = threadIdx.x & 63;
   const int bn = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (bn >= t.nb) return;
   const int cc = c < N ? c : N - 1;
@@ -1406,6 +1427,20 @@ __global__ __launch_bounds__(256) void k3_side_nc(T3 t, int N, const double* __r
   }
   if (p < p1) a0 += z[(long)t.bn_slots[p] * N];
   if (c < N) Cn[((long)s * t.nb + bn) * N + c] = -(a0 + a1);
+}
+
+// Restricted pass with padded side tables: the rows of Yb, Dp [S][nbf][QN] and Xab [Q][S][nbf][N] of the listed subdomains set to
+// zero (the whole pass clears the three arrays by memset; the padded rows are written by no kernel).  One workgroup per subdomain.
+__global__ __launch_bounds__(256) void k3_zero_side_rows(T3 t, int Q, int N, const int* __restrict__ list, double* __restrict__ Yb,
+                                                         double* __restrict__ Dp, double* __restrict__ Xab) {
+  const int s = list[blockIdx.x];
+  const long nq = (long)t.nbf * Q * N, nx = (long)t.nbf * N;
+  for (long i = threadIdx.x; i < nq; i += 256) {
+    Yb[s * nq + i] = 0.0;
+    Dp[s * nq + i] = 0.0;
+  }
+  for (int q = 0; q < Q; ++q)
+    for (long i = threadIdx.x; i < nx; i += 256) Xab[((long)q * t.S + s) * nx + i] = 0.0;
 }
 
 // ------------------------------------------------------------------------------------------------- online: estimate
@@ -3033,6 +3068,7 @@ int lrbms3_mesh_upload(lrbms3_ctx* ctx, const lrbms3_mesh_desc* d, int32_t S, in
     if ((rc = upload(ctx, tsd.data(), (long)tsd.size(), &t.TSP)) != LRBMS_OK) return rc;
   }
   ctx->nbr_host.assign(nbr, nbr + (long)S * 7);
+  ctx->sub_active = false;      // a restriction of the pass belongs to a mesh
   ctx->side_padding = false;
   for (int i = 0; i < t.nbf; ++i) ctx->side_padding = ctx->side_padding || d->side_elem[i] < 0;
   ctx->has_mesh = true;
@@ -3184,50 +3220,72 @@ int lrbms3_project_estimate_phase(lrbms3_ctx* ctx, int32_t phase, int32_t Q, int
   LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
   LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(sf, ctx->ev_fork, 0));
   LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(sn, ctx->ev_fork, 0));
-  GA a{t, Q, N, V, A_diag, A_cpl, ebar, Aaa, Aab, Bbb, Rs, Avg, nullptr, Zb, G_rdd, r_fd, bdiv, b, rhs_red, Yb, Dp, Xab, 1, nullptr};
-  if (own && ctx->side_padding) {      // padded side-face rows are written by no kernel: define them (the estimate multiplies them by 0)
+  // Restricted pass (lrbms3_pass_set_subset): everything phase 1 launches runs over the own list, everything phase 2 launches over
+  // the side list; a null list is the whole pass, launched exactly as without the feature.
+  const bool sub = ctx->sub_active;
+  const int* l_own = sub ? ctx->sub_own : nullptr;
+  const int* l_side = sub ? ctx->sub_side : nullptr;
+  const int n_own = sub ? ctx->sub_own_n : t.S, n_side = sub ? ctx->sub_side_n : t.S;
+  GA a{t, Q, N, V, A_diag, A_cpl, ebar, Aaa, Aab, Bbb, Rs, Avg, nullptr, Zb, G_rdd, r_fd, bdiv, b, rhs_red, Yb, Dp, Xab, 1, nullptr, l_own, n_own};
+  if (own && ctx->side_padding && !sub) {      // padded side-face rows are written by no kernel: define them (the estimate multiplies them by 0)
     LRBMS_HIP_CHECK(ctx, hipMemsetAsync(Yb, 0, sizeof(double) * (size_t)t.S * t.nbf * Q * N, sf));
     LRBMS_HIP_CHECK(ctx, hipMemsetAsync(Dp, 0, sizeof(double) * (size_t)t.S * t.nbf * Q * N, sf));
     LRBMS_HIP_CHECK(ctx, hipMemsetAsync(Xab, 0, sizeof(double) * (size_t)Q * t.S * t.nbf * N, sf));
   }
+  if (own && ctx->side_padding && sub && n_own > 0)      // ... of the listed subdomains only: every other row keeps its bits
+    hipLaunchKernelGGL(k3_zero_side_rows, dim3(n_own), dim3(256), 0, sf, t, Q, N, l_own, Yb, Dp, Xab);
   const int tn = (N + 15) / 16, tq = (Q * N + 15) / 16;
   const int nw_env = ctx->opt_waves;      // LRBMS3_OPT_WAVES
   const int nw = nw_env > 0 ? nw_env : 4;
   const int nw_s = nw_env > 0 ? nw_env : 8;      // kernels with one workgroup per subdomain only: more waves each
   int bad = 0;
-  {
-    const int r0 = own ? 0 : t.nrt, r1 = side ? t.nrt + t.nbf : t.nrt;      // own faces | side faces (the neighbours' share: halo)
-    KScope k(ctx, own ? "k3_flux" : "k3_flux<side>", sf);
-    hipLaunchKernelGGL(k3_flux, dim3(xcd_grid((r1 - r0 + 4 * FLUX_R * FLUX_LOOP - 1) / (4 * FLUX_R * FLUX_LOOP), t.S)), dim3(256), 0, sf, t, Q, N, r0, r1, V, Cf, Rs, Rb);
-  }
-  {
-    const int r0 = own ? 0 : t.nnodes, r1 = side ? t.nnodes + 6 * t.nvs : t.nnodes;
-    KScope k(ctx, own ? "k3_node_avg" : "k3_node_avg<side>", sn);
-    hipLaunchKernelGGL(k3_node_avg, dim3(xcd_grid((r1 - r0 + 4 * NODE_LOOP - 1) / (4 * NODE_LOOP), t.S)), dim3(256), 0, sn, t, N, r0, r1, V, Avg, As);
+  // own faces | side faces (the neighbours' share: halo), own nodes | side nodes: one launch over both row ranges for the whole
+  // pass, one launch per range and list for a restricted one (unless both lists are the same: all subdomains changed ran 3.5 %
+  // behind the whole pass with the split launches)
+  auto flux = [&](int r0, int r1, const int* list, int cnt, const char* name) {
+    if (cnt <= 0) return;
+    KScope k(ctx, name, sf);
+    hipLaunchKernelGGL(k3_flux, dim3(xcd_grid((r1 - r0 + 4 * FLUX_R * FLUX_LOOP - 1) / (4 * FLUX_R * FLUX_LOOP), cnt)), dim3(256), 0, sf, t, Q, N, r0, r1, list, cnt, V, Cf, Rs, Rb);
+  };
+  auto node_avg = [&](int r0, int r1, const int* list, int cnt, const char* name) {
+    if (cnt <= 0) return;
+    KScope k(ctx, name, sn);
+    hipLaunchKernelGGL(k3_node_avg, dim3(xcd_grid((r1 - r0 + 4 * NODE_LOOP - 1) / (4 * NODE_LOOP), cnt)), dim3(256), 0, sn, t, N, r0, r1, list, cnt, V, Avg, As);
+  };
+  if (!sub || (own && side && n_own == n_side)) {      // (own list within the side list: equal lengths mean equal lists)
+    flux(own ? 0 : t.nrt, side ? t.nrt + t.nbf : t.nrt, l_own, n_own, own ? "k3_flux" : "k3_flux<side>");
+    node_avg(own ? 0 : t.nnodes, side ? t.nnodes + 6 * t.nvs : t.nnodes, l_own, n_own, own ? "k3_node_avg" : "k3_node_avg<side>");
+  } else {
+    if (own) flux(0, t.nrt, l_own, n_own, "k3_flux");
+    if (side) flux(t.nrt, t.nrt + t.nbf, l_side, n_side, "k3_flux<side>");
+    if (own) node_avg(0, t.nnodes, l_own, n_own, "k3_node_avg");
+    if (side) node_avg(t.nnodes, t.nnodes + 6 * t.nvs, l_side, n_side, "k3_node_avg<side>");
   }
   const int npair = Q * (Q + 1) / 2;       // A_aa: pairs q <= q', the transposed blocks are written from the same accumulators
   // K-split for small per-rank subdomain counts (the 4 x 4 x 4 tile of an 8-GPU run has 64): one workgroup per (subdomain,
   // operator) would leave most of the 256 CUs idle, so the element range is dealt to ksplit workgroups and k3_pg_combine sums
-  // their partial results in a fixed order.  Off (ksplit = 1, no extra launch) from ~400 workgroups per kernel on.
+  // their partial results in a fixed order.  Off (ksplit = 1, no extra launch) from ~400 workgroups per kernel on.  A restricted
+  // pass counts the LISTED subdomains: 16 of 512 still fill the chip through the partial tiles, which are indexed by position.
   const int ks_env = ctx->opt_ksplit;      // LRBMS3_OPT_KSPLIT
   // target workgroups per launch, measured on the 4 x 4 x 4 tile of an 8-GPU run (64 subdomains; LRBMS3_OPT_KSPLIT 2 / 4 / 6 / auto):
   // the kernels with ONE workgroup per subdomain and ~240 VGPRs (BB: 4 waves, NC: 8 waves) want one workgroup per CU (k3_pg<BB>
   // 104 us at 256 workgroups, 124 at 512; <NC> 44 vs 51), G_aa three per CU (70 us at 768, 85 at 576), the others two
   auto ksplit_of = [&](int nblocks, int target) {
+    if (nblocks <= 0) return 1;      // an empty list: nothing is launched
     if (ks_env > 0) return ks_env < 8 ? ks_env : 8;
     if (nblocks >= 384) return 1;
     const int k = (target + nblocks - 1) / nblocks;
     return k < 1 ? 1 : (k < 8 ? k : 8);
   };
   const int QNl = Q * N;
-  const int ks_sys = ksplit_of(Q * t.S, 512), ks_aaa = ksplit_of(npair * t.S, 768), ks_nc = ksplit_of(t.S, 256), ks_ab = ksplit_of(Q * t.S, 512),
-            ks_bb = ksplit_of(t.S, 256), ks_cpl = ksplit_of(Q * t.S * 6, 512);
-  const long need_sys = ks_sys > 1 ? (long)Q * t.S * ks_sys * pg_part_size<G_SYS>(N, QNl) : 0,
-             need_aaa = ks_aaa > 1 ? (long)npair * t.S * ks_aaa * pg_part_size<G_AAA>(N, QNl) : 0,
-             need_nc = ks_nc > 1 ? (long)t.S * ks_nc * pg_part_size<G_NC>(N, QNl) : 0,
-             need_ab = ks_ab > 1 ? (long)Q * t.S * ks_ab * pg_part_size<G_AB>(N, QNl) : 0,
-             need_bb = ks_bb > 1 ? (long)t.S * ks_bb * pg_part_size<G_BB>(N, QNl) : 0,
-             need_cpl = ks_cpl > 1 ? (long)Q * t.S * 6 * ks_cpl * pg_part_size<G_CPL>(N, QNl) : 0;
+  const int ks_sys = ksplit_of(Q * n_own, 512), ks_aaa = ksplit_of(npair * n_own, 768), ks_nc = ksplit_of(n_own, 256), ks_ab = ksplit_of(Q * n_own, 512),
+            ks_bb = ksplit_of(n_own, 256), ks_cpl = ksplit_of(Q * n_side * 6, 512);
+  const long need_sys = ks_sys > 1 ? (long)Q * n_own * ks_sys * pg_part_size<G_SYS>(N, QNl) : 0,
+             need_aaa = ks_aaa > 1 ? (long)npair * n_own * ks_aaa * pg_part_size<G_AAA>(N, QNl) : 0,
+             need_nc = ks_nc > 1 ? (long)n_own * ks_nc * pg_part_size<G_NC>(N, QNl) : 0,
+             need_ab = ks_ab > 1 ? (long)Q * n_own * ks_ab * pg_part_size<G_AB>(N, QNl) : 0,
+             need_bb = ks_bb > 1 ? (long)n_own * ks_bb * pg_part_size<G_BB>(N, QNl) : 0,
+             need_cpl = ks_cpl > 1 ? (long)Q * n_side * 6 * ks_cpl * pg_part_size<G_CPL>(N, QNl) : 0;
   const long need = need_sys + need_aaa + need_nc + need_ab + need_bb + need_cpl;
   if (need > ctx->pg_part_cap) {
     LRBMS_HIP_CHECK(ctx, hipDeviceSynchronize());
@@ -3245,51 +3303,53 @@ int lrbms3_project_estimate_phase(lrbms3_ctx* ctx, int32_t phase, int32_t Q, int
   double* part_cpl = part_bb + need_bb;
   // (launch order measured: the MFMA-bound G_aa kernel first on the caller's stream, beside the latency-bound preparation
   // kernels of the other two chains, the HBM-bound system kernel after it: 2.39 -> 2.29 ms; a fourth stream for G_aa: slower)
-  if (own) {
+  if (own && n_own > 0) {
     KScope k(ctx, "k3_pg<AAA>", st);
     a.ksplit = ks_aaa;
     a.part = part_aaa;
     a.out = G_aa;
-    bad |= dispatch_pg<G_AAA>(a, npair * t.S, tn, tn, nw, st);
+    bad |= dispatch_pg<G_AAA>(a, npair * n_own, tn, tn, nw, st);
   }
-  if (own) {
+  if (own && n_own > 0) {
     KScope k(ctx, "k3_pg<SYS>", st);
     a.ksplit = ks_sys;
     a.part = part_sys;
     a.out = B_sys;
-    bad |= dispatch_pg<G_SYS>(a, Q * t.S, tn, tn, nw, st);
+    bad |= dispatch_pg<G_SYS>(a, Q * n_own, tn, tn, nw, st);
   }
-  if (own) {
+  if (own && n_own > 0) {
     KScope k(ctx, "k3_pg<AB>", sf);
     a.ksplit = ks_ab;
     a.part = part_ab;
     a.out = G_ab;
-    bad |= dispatch_pg<G_AB>(a, Q * t.S, tn, tq, nw, sf);
+    bad |= dispatch_pg<G_AB>(a, Q * n_own, tn, tq, nw, sf);
   }
-  if (own) {
+  if (own && n_own > 0) {
     KScope k(ctx, "k3_pg<NC>", sn);
     a.ksplit = ks_nc;
     a.part = part_nc;
     a.out = G_nc;
-    bad |= dispatch_pg<G_NC>(a, t.S, tn, tn, nw_s, sn);
+    bad |= dispatch_pg<G_NC>(a, n_own, tn, tn, nw_s, sn);
   }
-  if (own) {
+  if (own && n_own > 0) {
     KScope k(ctx, "k3_pg<BB>", sf);
     a.ksplit = ks_bb;
     a.part = part_bb;
     a.out = G_bb;
-    bad |= dispatch_pg<G_BB>(a, t.S, tq, tq, nw, sf);          // 4 waves: 291 us, 8 waves: 307 us (tools/nw_sweep.sh)
+    bad |= dispatch_pg<G_BB>(a, n_own, tq, tq, nw, sf);          // 4 waves: 291 us, 8 waves: 307 us (tools/nw_sweep.sh)
   }
-  if (own) {
+  if (own && n_own > 0) {
     KScope k(ctx, "k3_side_nc", sn);
-    hipLaunchKernelGGL(k3_side_nc, dim3((t.nb + 3) / 4, t.S), dim3(256), 0, sn, t, N, Zb, Cn);
+    hipLaunchKernelGGL(k3_side_nc, dim3((t.nb + 3) / 4, n_own), dim3(256), 0, sn, t, N, l_own, Zb, Cn);
   }
-  if (side) {
+  if (side && n_side > 0) {
     KScope k(ctx, "k3_pg<CPL>", st);
     a.ksplit = ks_cpl;
     a.part = part_cpl;
     a.out = B_sys;
-    bad |= dispatch_pg<G_CPL>(a, Q * t.S * 6, tn, tn, nw, st);
+    a.list = l_side;
+    a.nlist = n_side;
+    bad |= dispatch_pg<G_CPL>(a, Q * n_side * 6, tn, tn, nw, st);
   }
   if (bad) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_estimate: unsupported tile shape");
   LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[0], sf));
@@ -3297,6 +3357,53 @@ int lrbms3_project_estimate_phase(lrbms3_ctx* ctx, int32_t phase, int32_t Q, int
   LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[0], 0));
   LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[1], 0));
   LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}
+
+int lrbms3_pass_set_subset(lrbms3_ctx* ctx, const int32_t* changed, int32_t count) {
+  if (!ctx) return LRBMS_E_INVALID;
+  if (!ctx->has_mesh) return lrbms_fail(ctx, LRBMS_E_INVALID, "pass_set_subset: mesh not uploaded");
+  const T3& t = ctx->t;
+  if (count < 0) return lrbms_fail(ctx, LRBMS_E_INVALID, "pass_set_subset: count must not be negative");
+  if (count == 0) {
+    ctx->sub_active = false;
+    return LRBMS_OK;
+  }
+  if (!changed) return lrbms_fail(ctx, LRBMS_E_INVALID, "pass_set_subset: null list with count > 0");
+  for (int i = 0; i < count; ++i) {
+    if (changed[i] < 0 || changed[i] >= t.S_ext)
+      return lrbms_fail(ctx, LRBMS_E_INVALID, "pass_set_subset: index " + std::to_string(changed[i]) + " out of range [0, S_ext)");
+    if (i > 0 && changed[i] <= changed[i - 1])
+      return lrbms_fail(ctx, LRBMS_E_INVALID, "pass_set_subset: the list must be strictly ascending");
+  }
+  // own list: the changed local subdomains; side list: the local subdomains that are changed or see a changed slab (local or
+  // halo) through a face -- from the host copy of the neighbour table
+  std::vector<char> hit((size_t)t.S_ext, 0);
+  for (int i = 0; i < count; ++i) hit[changed[i]] = 1;
+  std::vector<int32_t> lown, lside;
+  for (int s = 0; s < t.S; ++s) {
+    if (hit[s]) lown.push_back(s);
+    bool touched = false;
+    for (int k = 0; k < 7; ++k) {
+      const int s2 = ctx->nbr_host[(size_t)s * 7 + k];
+      touched = touched || (s2 >= 0 && hit[s2]);
+    }
+    if (touched) lside.push_back(s);
+  }
+  if (!ctx->sub_own) {
+    void* p = nullptr;
+    LRBMS_HIP_CHECK(ctx, hipMalloc(&p, sizeof(int) * 2 * (size_t)t.S));
+    ctx->owned.push_back(p);
+    ctx->sub_own = static_cast<int*>(p);
+    ctx->sub_side = ctx->sub_own + t.S;
+  }
+  // synchronous copies: the lists a pass still in flight reads must not change under it, and `changed` may go away after return
+  LRBMS_HIP_CHECK(ctx, hipDeviceSynchronize());
+  if (!lown.empty()) LRBMS_HIP_CHECK(ctx, hipMemcpy(ctx->sub_own, lown.data(), sizeof(int) * lown.size(), hipMemcpyHostToDevice));
+  if (!lside.empty()) LRBMS_HIP_CHECK(ctx, hipMemcpy(ctx->sub_side, lside.data(), sizeof(int) * lside.size(), hipMemcpyHostToDevice));
+  ctx->sub_own_n = (int)lown.size();
+  ctx->sub_side_n = (int)lside.size();
+  ctx->sub_active = true;
   return LRBMS_OK;
 }
 
@@ -4534,12 +4641,13 @@ __global__ __launch_bounds__(256) void k3_source_gram(T3 t, int K, long comp, co
 // the B operand the row operand (lane: column l & 15, row l >> 4); V and R_self are read once, whatever K.  KT = 16-component tiles;
 // up to four 16-column tiles.  The waves' tiles are summed in a fixed order through the LDS.
 template <int KT>
-__global__ __launch_bounds__(512) void k3_project_sources(T3 t, int N, int QN, int K, const double* __restrict__ b_K,
-                                                          const double* __restrict__ bdiv_K, const double* __restrict__ V,
+__global__ __launch_bounds__(512) void k3_project_sources(T3 t, int N, int QN, int K, const int* __restrict__ list,
+                                                          const double* __restrict__ b_K, const double* __restrict__ bdiv_K,
+                                                          const double* __restrict__ V,
                                                           const double* __restrict__ Rs, double* __restrict__ rhs_K,
                                                           double* __restrict__ rfd_K) {
   __shared__ double red[8][256];
-  const int s = blockIdx.x, mode = blockIdx.y, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int s = list ? list[blockIdx.x] : blockIdx.x, mode = blockIdx.y, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cols = mode ? QN : N, rows = mode ? t.nT : t.n, nct = (cols + 15) / 16;
   const long xs = (long)t.S * rows;
@@ -4717,10 +4825,13 @@ int lrbms3_project_sources(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, con
   if (Q < 1 || Q > 8 || N < 1 || N > 64 || Q * N > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: needs N <= 64 and Q N <= 64");
   if (!b_K || !bdiv_K || !V || !R_self || !rhs_red_K || !r_fd_K) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: null argument");
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(t.S, 2);
+  const int* list = ctx->sub_active ? ctx->sub_own : nullptr;      // lrbms3_pass_set_subset: the rows of the own list only
+  const int cnt = ctx->sub_active ? ctx->sub_own_n : t.S;
+  if (cnt <= 0) return LRBMS_OK;
+  const dim3 grid(cnt, 2);
 #define PSCASE(T)                                                                                                                  \
   case T:                                                                                                                          \
-    hipLaunchKernelGGL(k3_project_sources<T>, grid, dim3(512), 0, st, t, N, Q * N, K, b_K, bdiv_K, V, R_self, rhs_red_K, r_fd_K); \
+    hipLaunchKernelGGL(k3_project_sources<T>, grid, dim3(512), 0, st, t, N, Q * N, K, list, b_K, bdiv_K, V, R_self, rhs_red_K, r_fd_K); \
     break
   switch ((K + 15) / 16) {
     PSCASE(1);

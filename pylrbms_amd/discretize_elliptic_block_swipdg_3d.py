@@ -398,7 +398,20 @@ class LRBMSReductor3D(LocalBasisSlab):
     def _append_columns(self, v, ok):
         if self._V is not None and self._V.shape[0] != self.d.engine.S:
             raise NotImplementedError('extending bases that carry their halo: extend the local slab and exchange afterwards')
-        return super()._append_columns(v, ok)
+        ok_host = super()._append_columns(v, ok)
+        # _dirty: local indices of the subdomains whose basis changed since the last reduce()
+        self._dirty = getattr(self, '_dirty', set()) | {int(i) for i in np.where(ok_host)[0]}
+        return ok_host
+
+    def reserve(self, width):
+        """Room for local bases of up to ``width`` vectors: pads the slab with zero columns, to an even width (the wide-load form
+        of the pass takes even N) and at most 64 // Q, the limit of the pass.  Zero columns are the ragged-basis convention of this
+        path and change no result (``local_sizes()`` keeps counting real vectors); later extensions then fill existing columns,
+        the slab keeps its width and ``reduce(touched=...)`` can update the previous model in place."""
+        width = min(int(width) + (int(width) & 1), 64 // self.d.Q)
+        if self._V is not None and width > self._V.shape[2]:
+            self._V = self._torch.nn.functional.pad(self._V, (0, width - self._V.shape[2])).contiguous()
+        return self.basis_size()
 
     def _as_slab(self, U):
         eng = self.d.engine
@@ -443,26 +456,45 @@ class LRBMSReductor3D(LocalBasisSlab):
         return [ii for ii, flag in zip(subdomains, ok) if flag]
 
     # ------------------------------------------------------------------ reduce / reconstruct
-    def reduce(self):
+    def reduce(self, touched=None):
+        """``reductor.reduce()`` (reductor.py:33-73): one pass of the hot path.  ``touched``: global ids of the subdomains whose local
+        bases changed since the previous ``reduce()`` (the marking of online_enrichment.py:38-47): only their own arrays and the
+        side arrays of them and of their face neighbours are projected again (``lrbms3_pass_set_subset``), into the
+        arrays of the previous reduced model, which the returned model shares (the previous one is superseded, as in the
+        reference's loop, online_enrichment.py:52).  The whole pass runs when ``touched`` is None, when there is no previous model
+        of the same width, and on a sharded grid.  ``last_reduce_info``: {'incremental', 'own', 'side'}."""
         eng = self.d.engine
         if self._V is None or self._V.shape[2] == 0:
             raise RuntimeError('no basis')
         V = self._V
         if V.shape[0] != eng.S_ext:
             raise NotImplementedError('sharded discretization: hand in bases [S_ext, n, N] with the halo filled (HaloExchange)')
-        return ReducedDiscretization3D(self, *self._project(V.contiguous()))
+        V = V.contiguous()
+        N = int(V.shape[2])
+        dirty = getattr(self, '_dirty', set())
+        self._dirty = set()
+        last = getattr(self, '_last_reduce', None)
+        subset = None
+        if touched is not None and last is not None and last['N'] == N and eng.S_ext == eng.S:
+            from pylrbms_amd.grid3d import side_targets
+            subset = sorted({eng.ext_pos[int(g)] for g in touched} | dirty)
+            self.last_reduce_info = {'incremental': True, 'own': len(subset), 'side': len(side_targets(eng.nbr, subset))}
+        else:
+            last = self._last_reduce = {'N': N, 'out': eng.alloc_outputs(N), 'work': eng.alloc_work(N), 'src': None}
+            self.last_reduce_info = {'incremental': False, 'own': eng.S, 'side': eng.S}
+        return ReducedDiscretization3D(self, *self._project(V, last, subset))
 
-    def _project(self, V):
-        """(out, rhs_red_K, r_fd_K) of one pass; with an affine source also ``lrbms3_project_sources`` on the pass's flux image, and
-        the projections of sum_j f_j (``rhs_red``, ``r_fd``) are dropped: nothing may use them on such a model."""
+    def _project(self, V, buf, subset=None):
+        """(out, rhs_red_K, r_fd_K) of one pass into the kept buffers ``buf`` (restricted to ``subset`` if given); with an affine
+        source also ``lrbms3_project_sources`` on the pass's flux image, and the model's view of the outputs drops the projections
+        of sum_j f_j (``rhs_red``, ``r_fd``): nothing may use them on such a model."""
         eng, src = self.d.engine, self.d._src
+        out = dict(eng.project_and_estimate(V, buf['out'], buf['work'], subset=subset))
         if src is None:
-            return eng.project_and_estimate(V), None, None
-        work = eng.alloc_work(V.shape[2])
-        out = eng.project_and_estimate(V, work=work)
-        rhs_red_K, r_fd_K = eng.ctx.project_sources(self.d.Q, src['b_K'], src['bdiv_K'], V, work)
+            return out, None, None
+        buf['src'] = eng.project_sources(src['b_K'], src['bdiv_K'], V, buf['work'], out=buf['src'], subset=subset)
         out['rhs_red'] = out['r_fd'] = None
-        return out, rhs_red_K, r_fd_K
+        return out, buf['src'][0], buf['src'][1]
 
     def reconstruct(self, u):
         return self._torch.einsum('snj,sj->sn', self._V, u)

@@ -79,23 +79,53 @@ class Engine3D:
     def alloc_work(self, N):
         return self.ctx.empty(self.ctx.work_size(self.Q, N))
 
-    def project_and_estimate(self, V, out=None, work=None, halo=None):
+    def project_and_estimate(self, V, out=None, work=None, halo=None, subset=None):
         """One pass of the hot path over all local subdomains; V [S_ext, n, N] with the halo filled -- or ``halo`` (a
         ``pylrbms_amd.parallel.HaloExchange`` on this rank's 3D tile) fills it: one exchange step per pass (the rows of the
-        cube layer next to every foreign side), started first and waited for only by the kernels that read neighbour rows."""
+        cube layer next to every foreign side), started first and waited for only by the kernels that read neighbour rows.
+
+        ``subset``: incremental re-projection -- the ascending indices (S_ext ordering) of the subdomains whose basis changed since
+        the pass that filled ``out`` and ``work``: only their own arrays and the side arrays of ``grid3d.side_targets`` of them are
+        written (``lrbms3_pass_set_subset``); every other row keeps its bits.  An empty list runs nothing."""
         if self.ops is None:
             raise NativeError('assemble() must run before project_and_estimate()')
         N = V.shape[2]
+        if subset is not None:
+            if out is None or work is None:
+                raise NativeError('subset= updates the out and work buffers of a previous pass: hand them in')
+            if len(subset) == 0:
+                return out
         out = out if out is not None else self.alloc_outputs(N)
         work = work if work is not None else self.alloc_work(N)
-        if halo is None:
-            return self.ctx.project_estimate(self.Q, V, self.ops, work, out)
-        # sharded: the collective runs while everything that reads rank-local slabs only is computed (all but the neighbours'
-        # shares of the flux image and of the node averages and the coupling blocks: ~95 % of the pass)
-        finish = halo.start(V)
-        self.ctx.project_estimate(self.Q, V, self.ops, work, out, phase=1)
-        finish()
-        return self.ctx.project_estimate(self.Q, V, self.ops, work, out, phase=2)
+        if subset is not None:
+            self.ctx.pass_set_subset(subset)
+        try:
+            if halo is None:
+                return self.ctx.project_estimate(self.Q, V, self.ops, work, out)
+            # sharded: the collective runs while everything that reads rank-local slabs only is computed (all but the neighbours'
+            # shares of the flux image and of the node averages and the coupling blocks: ~95 % of the pass)
+            finish = halo.start(V)
+            self.ctx.project_estimate(self.Q, V, self.ops, work, out, phase=1)
+            finish()
+            return self.ctx.project_estimate(self.Q, V, self.ops, work, out, phase=2)
+        finally:
+            if subset is not None:
+                self.ctx.pass_set_subset(None)
+
+    def project_sources(self, b_K, bdiv_K, V, work, out=None, subset=None):
+        """``lrbms3_project_sources`` on the flux image a finished pass on ``V`` left in ``work``: (rhs_red_K, r_fd_K).  With
+        ``subset`` (as in ``project_and_estimate``) only the rows of the changed local subdomains of ``out`` are written."""
+        if subset is not None:
+            if out is None:
+                raise NativeError('subset= updates the arrays of a previous projection: hand them in as out')
+            if len(subset) == 0:
+                return out
+            self.ctx.pass_set_subset(subset)
+        try:
+            return self.ctx.project_sources(self.Q, b_K, bdiv_K, V, work, out=out)
+        finally:
+            if subset is not None:
+                self.ctx.pass_set_subset(None)
 
     def reduced_estimate(self, theta, u, out):
         return self.ctx.reduced_estimate(self.Q, theta, u, out, self.ops, self.hdiam)

@@ -514,6 +514,20 @@ def tile_grid3d(world_size, P):
     return best[1]
 
 
+def side_targets(neighbor_slots, changed):
+    """The side list of an incremental re-projection (include/lrbms3d_hip.h: lrbms3_pass_set_subset): the rows s of the table
+    ``neighbor_slots`` [S, 7] (index per slot, -1 = none, slot 3 = s itself) that are in ``changed`` or see a member of ``changed``
+    through a face, ascending.  The coupling blocks and the neighbours' shares of the flux image and of the node averages of a
+    subdomain read the bases of its face neighbours only -- no diagonal dependence, unlike the vertex patches of the 2D path."""
+    slots = np.asarray(neighbor_slots).reshape(-1, 7)
+    marks = np.asarray(sorted(int(c) for c in changed), dtype=np.int64)
+    if marks.size == 0:
+        return []
+    hit = np.isin(slots, marks) & (slots >= 0)
+    hit[:, SELF_SLOT] |= np.isin(np.arange(len(slots)), marks)
+    return [int(s) for s in np.where(hit.any(axis=1))[0]]
+
+
 class DDSubdomainsGrid3D:
     """``K`` cubes per direction cut into ``P`` subdomains per direction (the queries of reference grid.py:8-69)."""
 
