@@ -517,6 +517,35 @@ int lrbms_reduced_solve_batch_src(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t 
                                   double* info, void* stream);
 int lrbms_combine_sources(lrbms_ctx* ctx, int32_t K, int64_t M, const double* phi, const double* x_K, double* y, void* stream);
 
+/* -- batched reduced trajectories: nmu <= 64 parameters of the parabolic reduced model in one call --------
+ *   lrbms_reduced_implicit_euler_batch      column m of U [nt+1][S][N][nmu] (parameter fastest; U[0] input) is the trajectory
+ *                                   lrbms_reduced_implicit_euler computes at theta[m] (theta [nmu][Q] host):
+ *                                   (M_red + dt A_m) u_{k+1} = M_red u_k + dt rhs_red, warm-started from u_k.  Every step is ONE
+ *                                   panel PCG for all columns, iterated until every column has |r| / |M_red u_k + dt b_m| <= rtol;
+ *                                   a converged column stays put (alpha = beta = 0), a column with a zero right-hand side keeps
+ *                                   u_{k+1} = u_k.  The panel matvec reads M_red[s] as one more block of the self slot.
+ *                                   One preconditioner per call, built on `stream`: inverse diagonal blocks and coarse level of
+ *                                   M_red + dt sum_q mean(theta)_q B_q.  A preconditioner installed with
+ *                                   lrbms_reduced_precond_use belongs to A, not to the step operator: it is ignored here, as in
+ *                                   lrbms_reduced_implicit_euler.
+ *                                   Limits: 1 <= nmu <= 64, N <= 64, Q <= 8, Q <= 4 for more than 16 parameters, S_ext == S.
+ *                                   max_iter caps the iterations of ONE step; when it is hit the call returns
+ *                                   LRBMS_E_NOT_CONVERGED with the iterate of that step in U[step+1] and info = (iterations so
+ *                                   far, worst ratio).  Otherwise info[0] = sum over the steps of the iterations of the slowest
+ *                                   group, info[1] = worst final ratio.
+ *                                   work: lrbms_reduced_implicit_euler_batch_work_size(N, nmu) doubles.
+ *   lrbms_reduced_implicit_euler_batch_src  the same with b_m of step k = sum_j phi[m][k+1][j] rhs_red_K[j]: rhs_red_K [K][S][N],
+ *                                   phi [nmu][nt+1][K] device (the time convention of lrbms_reduced_implicit_euler_src per
+ *                                   column), 1 <= K <= 64.  K = 1, phi = 1: the bits of lrbms_reduced_implicit_euler_batch. */
+int64_t lrbms_reduced_implicit_euler_batch_work_size(lrbms_ctx* ctx, int32_t N, int32_t nmu);
+int lrbms_reduced_implicit_euler_batch(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t nmu, const double* theta, double dt, int32_t nt,
+                                       const double* B_sys, const double* M_red, const double* rhs_red, double* work, double* U,
+                                       double rtol, int32_t max_iter, double* info, void* stream);
+int lrbms_reduced_implicit_euler_batch_src(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta, double dt,
+                                           int32_t nt, const double* B_sys, const double* M_red, const double* rhs_red_K,
+                                           const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
+                                           void* stream);
+
 /* -- online enrichment (SURVEY.md section 8f "next" #1) ---------------------------------------------------- */
 /* Dirichlet correction blocks of the neighbourhood problems: on every coupling face of subdomain s, the boundary-form
  * diagonal block minus the inner-face block already contained in A_diag

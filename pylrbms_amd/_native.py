@@ -94,6 +94,11 @@ SIGNATURES = {
                                                   c_vp, c_vp]),
     'lrbms_reduced_solve_batch_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_dbl,
                                                      c_i32, _P_DBL, c_vp]),
+    'lrbms_reduced_implicit_euler_batch_work_size': (c_i64, [c_vp, c_i32, c_i32]),
+    'lrbms_reduced_implicit_euler_batch': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                          c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms_reduced_implicit_euler_batch_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp,
+                                                              c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
     'lrbms_combine_sources': (ctypes.c_int, [c_vp, c_i32, c_i64, _P_DBL, c_vp, c_vp, c_vp]),
     'lrbms_assemble_dirichlet_correction': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms_local_correction_work_size': (c_i64, [c_vp, c_i32]),
@@ -767,6 +772,59 @@ class NativeContext(ContextBase):
                                                        c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter),
                                                        _dblp(info), self._stream())
         self._check(rc, 'lrbms_reduced_implicit_euler_src')
+        return U, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
+
+    def _batch_trajectory_buffers(self, name, N, nmu, nt, U0, work):
+        """work and U [nt + 1, S, N, nmu] (U[0] = U0: [S, N] for every column, or [S, N, nmu]; default zero) of the batched
+        reduced implicit Euler exports."""
+        need = int(self.lib.lrbms_reduced_implicit_euler_batch_work_size(self.handle, N, nmu))
+        if need < 0:
+            raise NativeError('{}: bad N / nmu'.format(name))
+        if work is None:
+            work = self.empty(need)
+        if work.numel() < need:
+            raise NativeError('{}: work too small'.format(name))
+        U = self.zeros(max(int(nt), 0) + 1, self.S, N, nmu)
+        if U0 is not None:
+            U[0] = U0.reshape(self.S, N, -1)          # [S, N, 1] broadcasts over the columns
+        return work, U
+
+    def reduced_implicit_euler_batch(self, thetas, dt, nt, B_sys, M_red, rhs_red, U0=None, rtol=1e-13, max_iter=20000, work=None):
+        """nmu <= 64 reduced trajectories in one call: thetas [nmu, Q] -> (U [nt + 1, S, N, nmu] (parameter fastest), info);
+        column m is what ``reduced_implicit_euler`` returns at thetas[m].  ``max_iter`` caps the iterations of one step."""
+        Q, S, N = B_sys.shape[0], self.S, B_sys.shape[3]
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, Q)
+        work, U = self._batch_trajectory_buffers('reduced_implicit_euler_batch', N, nmu, nt, U0, work)
+        info = np.zeros(2)
+        rc = self.lib.lrbms_reduced_implicit_euler_batch(self.handle, Q, N, nmu, _dblp(th), float(dt), int(nt),
+                                                         self._ptr(B_sys, (Q, S, 5, N, N), 'B_sys'), self._ptr(M_red, (S, N, N), 'M_red'),
+                                                         self._ptr(rhs_red, (S, N), 'rhs_red'), c_vp(work.data_ptr()),
+                                                         c_vp(U.data_ptr()), float(rtol), int(max_iter), _dblp(info), self._stream())
+        self._check(rc, 'lrbms_reduced_implicit_euler_batch')
+        return U, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
+
+    def reduced_implicit_euler_batch_src(self, thetas, dt, nt, B_sys, M_red, rhs_red_K, phi, U0=None, rtol=1e-13, max_iter=20000,
+                                         work=None):
+        """``reduced_implicit_euler_batch`` with the step right-hand side M_red u_k + dt sum_j phi[m, k+1, j] rhs_red_K[j] in
+        column m; phi [nmu, nt + 1, K] (host or device)."""
+        Q, S, N, K = B_sys.shape[0], self.S, B_sys.shape[3], rhs_red_K.shape[0]
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, Q)
+        ph = phi if hasattr(phi, 'data_ptr') else self.from_numpy(np.ascontiguousarray(np.asarray(phi, dtype=np.float64)))
+        assert tuple(ph.shape) == (nmu, max(int(nt), 0) + 1, K), 'phi must be [nmu, nt + 1, K]'
+        ph = ph.contiguous()
+        work, U = self._batch_trajectory_buffers('reduced_implicit_euler_batch_src', N, nmu, nt, U0, work)
+        info = np.zeros(2)
+        rc = self.lib.lrbms_reduced_implicit_euler_batch_src(self.handle, Q, N, K, nmu, _dblp(th), float(dt), int(nt),
+                                                             self._ptr(B_sys, (Q, S, 5, N, N), 'B_sys'),
+                                                             self._ptr(M_red, (S, N, N), 'M_red'),
+                                                             self._ptr(rhs_red_K, (K, S, N), 'rhs_red_K'),
+                                                             self._ptr(ph, tuple(ph.shape), 'phi'), c_vp(work.data_ptr()),
+                                                             c_vp(U.data_ptr()), float(rtol), int(max_iter), _dblp(info), self._stream())
+        self._check(rc, 'lrbms_reduced_implicit_euler_batch_src')
         return U, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
 
     def project_sources(self, Q, b_K, V, D, out=None):

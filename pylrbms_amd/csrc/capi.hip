@@ -48,6 +48,13 @@ int launch_reduced_source_terms(lrbms_ctx* ctx, int Q, int N, int K, int L, cons
 int launch_assemble_source_gram(lrbms_ctx* ctx, int K, const double* f_smp_K, double* F2, hipStream_t st);
 int launch_project_sources(lrbms_ctx* ctx, int N, int C, int K, const double* bK, const double* V, const double* D, double* rhs_K,
                            double* rfd_K, hipStream_t st);
+int64_t reduced_implicit_euler_batch_work_size(lrbms_ctx* ctx, int N, int nmu);
+int launch_reduced_implicit_euler_batch(lrbms_ctx* ctx, int Q, int N, int nmu, const double* theta, double dt, int nt, const double* B_sys,
+                                        const double* M_red, const double* rhs_red, double* work, double* U, double rtol, int max_iter,
+                                        double* info, hipStream_t st);
+int launch_reduced_implicit_euler_batch_src(lrbms_ctx* ctx, int Q, int N, int K, int nmu, const double* theta, double dt, int nt,
+                                            const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
+                                            double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st);
 int launch_reduced_solve_batch_src(lrbms_ctx* ctx, int Q, int N, int K, int nmu, const double* theta, const double* phi,
                                    const double* B_sys, const double* rhs_red_K, double* work, double* u, double rtol, int max_iter,
                                    double* info, hipStream_t st);
@@ -746,6 +753,30 @@ int lrbms_reduced_solve_batch_src(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t 
   CHECK_PTR(ctx, rhs_red_K); CHECK_PTR(ctx, work); CHECK_PTR(ctx, u);
   return launch_reduced_solve_batch_src(ctx, Q, N, K, nmu, theta, phi, B_sys, rhs_red_K, work, u, rtol, max_iter, info,
                                         (hipStream_t)stream);
+}
+
+int64_t lrbms_reduced_implicit_euler_batch_work_size(lrbms_ctx* ctx, int32_t N, int32_t nmu) {
+  if (!ctx || !ctx->has_mesh || N < 1 || nmu < 1) return -1;
+  return reduced_implicit_euler_batch_work_size(ctx, N, nmu);
+}
+
+int lrbms_reduced_implicit_euler_batch(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t nmu, const double* theta, double dt, int32_t nt,
+                                       const double* B_sys, const double* M_red, const double* rhs_red, double* work, double* U,
+                                       double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, B_sys); CHECK_PTR(ctx, M_red);
+  CHECK_PTR(ctx, rhs_red); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
+  return launch_reduced_implicit_euler_batch(ctx, Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red, work, U, rtol, max_iter, info,
+                                             (hipStream_t)stream);
+}
+
+int lrbms_reduced_implicit_euler_batch_src(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta, double dt,
+                                           int32_t nt, const double* B_sys, const double* M_red, const double* rhs_red_K,
+                                           const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
+                                           void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, B_sys); CHECK_PTR(ctx, M_red);
+  CHECK_PTR(ctx, rhs_red_K); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
+  return launch_reduced_implicit_euler_batch_src(ctx, Q, N, K, nmu, theta, dt, nt, B_sys, M_red, rhs_red_K, phi, work, U, rtol,
+                                                 max_iter, info, (hipStream_t)stream);
 }
 
 int lrbms_combine_sources(lrbms_ctx* ctx, int32_t K, int64_t M, const double* phi, const double* x_K, double* y, void* stream) {

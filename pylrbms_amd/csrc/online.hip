@@ -1474,14 +1474,22 @@ constexpr int BCG_KMAX = 5;   // outputs per thread of the batched matvec: N * n
 
 struct ThetaBatch { double v[TBMAX * 8]; };   // theta[m][q], q < 8
 
+// The step operator of the batched reduced implicit Euler (lrbms_reduced_implicit_euler_batch) in the three panel matvecs below:
+// MASS = true adds M_red[s] p_self, ONE more block (coefficient 1) in the block list of the self slot; the theta table of such a
+// launch holds dt theta.  The trailing argument is empty for MASS = false: those instantiations are the code they were.
+template <bool MASS> struct MassOp {};
+template <> struct MassOp<true> { const double* M; };   // M_red [S][N][N]
+template <bool MASS> __device__ inline const double* mass_block(const MassOp<MASS>&, long) { return nullptr; }
+template <> __device__ inline const double* mass_block<true>(const MassOp<true>& mo, long off) { return mo.M + off; }
+
 // direction + matvec:  p_new = z + beta p_old (own + neighbour rows, into LDS; own rows written to p_out),
 // y_s = sum_slot sum_q theta_q B_q[s][slot] p_new[nbr(s, slot)],  partial[s][m] = p_new_s . y_s
-template <int BCG_K>
+template <int BCG_K, bool MASS = false>
 __global__ __launch_bounds__(256) void k_bcg_matvec(int S, const int* __restrict__ nbr, int Q, int N, int nmu, ThetaBatch th,
                                                     const double* __restrict__ B_sys, const double* __restrict__ z,
                                                     const double* __restrict__ p_old, const double* __restrict__ beta, int first,
                                                     double* __restrict__ p_out, double* __restrict__ y,
-                                                    double* __restrict__ partial) {
+                                                    double* __restrict__ partial, MassOp<MASS> mass = MassOp<MASS>()) {
   extern __shared__ double lds[];
   const int s = blockIdx.x, tid = threadIdx.x;
   const int NM = N * nmu;
@@ -1504,9 +1512,11 @@ __global__ __launch_bounds__(256) void k_bcg_matvec(int S, const int* __restrict
   for (int k = 0; k < BCG_K; ++k) acc[k] = 0.0;
   for (int slot = 0; slot < 5; ++slot) {
     if (nbr[s * 5 + slot] < 0) continue;
-    for (int q = 0; q < Q; ++q) {
+    const int nq = (MASS && slot == 2) ? Q + 1 : Q;     // the mass block closes the self slot's list
+    for (int q = 0; q < nq; ++q) {
       __syncthreads();
-      const double* B = B_sys + ((((long)q * S + s) * 5 + slot) * N) * N;
+      const bool mb = MASS && q == Q;
+      const double* B = mb ? mass_block(mass, (long)s * N * N) : B_sys + ((((long)q * S + s) * 5 + slot) * N) * N;
       for (int i = tid; i < N * N; i += 256) Bs[i] = B[i];
       __syncthreads();
 #pragma unroll
@@ -1517,7 +1527,7 @@ __global__ __launch_bounds__(256) void k_bcg_matvec(int S, const int* __restrict
           const double* pc = Pt + slot * NM + m;
           double sum = 0.0;
           for (int c = 0; c < N; ++c) sum += Bs[r * N + c] * pc[c * nmu];
-          acc[k] += th.v[m * 8 + q] * sum;
+          acc[k] += mb ? sum : th.v[m * 8 + q] * sum;
         }
       }
     }
@@ -1563,12 +1573,12 @@ typedef double d4m __attribute__((ext_vector_type(4)));
 // Workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt(0), i.e. it waits for the block loads just
 // requested for the NEXT step -- the prefetch would overlap with nothing (the same idiom as lds_barrier in fused.hip).
 __device__ inline void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int NC>
+template <int NC, bool MASS = false>
 __global__ __launch_bounds__(16 * NC) void k_bcg_matvec_mfma(int S, const int* __restrict__ nbr, int Q, int N, int nmu, ThetaBatch th,
                                                          const double* __restrict__ B_sys, const double* __restrict__ z,
                                                          const double* __restrict__ p_old, const double* __restrict__ beta,
                                                          int first, double* __restrict__ p_out, double* __restrict__ y,
-                                                         double* __restrict__ partial) {
+                                                         double* __restrict__ partial, MassOp<MASS> mass = MassOp<MASS>()) {
   extern __shared__ double lds[];
   constexpr int NTH = 16 * NC;                         // threads: 256 / 512
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
@@ -1600,8 +1610,8 @@ __global__ __launch_bounds__(16 * NC) void k_bcg_matvec_mfma(int S, const int* _
   // block list of this subdomain: (slot, q) for every existing neighbour slot; register prefetch of the next block
   constexpr int PF = 4096 / NTH;                       // N * N <= 4096 = NTH threads x PF
   double pf[PF];
-  auto load_block = [&](int slot, int q) {
-    const double* B = B_sys + ((((long)q * S + s) * 5 + slot) * N) * N;
+  auto load_block = [&](int slot, int q) {               // q == Q (MASS): the mass block of the self slot
+    const double* B = (MASS && q == Q) ? mass_block(mass, (long)s * N * N) : B_sys + ((((long)q * S + s) * 5 + slot) * N) * N;
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
       const int i = tid + NTH * k;
@@ -1611,19 +1621,21 @@ __global__ __launch_bounds__(16 * NC) void k_bcg_matvec_mfma(int S, const int* _
   int slots[5], ns = 0;
   for (int slot = 0; slot < 5; ++slot)
     if (nbr[s * 5 + slot] >= 0) slots[ns++] = slot;
-  const int nblk = ns * Q;
+  const int nblk = ns * Q + (MASS ? 1 : 0);              // MASS: the list ends with (self slot, q = Q), all five panels are in LDS
   d4m acc = (d4m){0.0, 0.0, 0.0, 0.0};
   const bool active = rt * 16 < N;                     // this wave's row tile exists
   if (nblk > 0) load_block(slots[0], 0);
   for (int b = 0; b < nblk; ++b) {
-    const int slot = slots[b / Q], q = b - (b / Q) * Q;
+    const bool mb = MASS && b == ns * Q;
+    const int slot = mb ? 2 : slots[b / Q], q = mb ? Q : b - (b / Q) * Q;
     __syncthreads();                                   // previous block's MFMAs are done reading Bs (and Pt is complete)
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
       const int i = tid + NTH * k;
       if (i < N * N) Bs[(i / N) * LDB + i % N] = pf[k];
     }
-    if (b + 1 < nblk) load_block(slots[(b + 1) / Q], (b + 1) - ((b + 1) / Q) * Q);
+    if (MASS && b + 1 == ns * Q) load_block(2, Q);
+    else if (b + 1 < nblk) load_block(slots[(b + 1) / Q], (b + 1) - ((b + 1) / Q) * Q);
     __syncthreads();
     if (active) {
       const double* pslot = Pt + slot * KP * NC;
@@ -1631,6 +1643,7 @@ __global__ __launch_bounds__(16 * NC) void k_bcg_matvec_mfma(int S, const int* _
 #pragma unroll
       for (int qq = 1; qq < 8; ++qq)
         if (q == qq) thv = thq[qq];
+      if (mb) thv = 1.0;
       const int ra = rt * 16 + li < N ? rt * 16 + li : N;
       for (int kk = 0; kk < KP; kk += 4) {
         const double a = Bs[ra * LDB + kk + lk];
@@ -1671,7 +1684,7 @@ __global__ __launch_bounds__(16 * NC) void k_bcg_matvec_mfma(int S, const int* _
 // CT column tiles per wave.  Measured at 64 columns: CT = 2 (512 threads, the A operand of a k-step read from LDS once for two
 // MFMAs, two workgroups of 8 waves per CU instead of one of 16) needs 150 VGPRs, spills under the 128 that two workgroups allow,
 // and takes 131 us against 102 us for CT = 1: every instantiation the launcher takes has CT = 1.
-template <int NC, int KSC, int CT>      // KSC: k-steps compiled in (4, 8, 10, 12, 16 for N <= 16, 32, 40, 48, 64)
+template <int NC, int KSC, int CT, bool MASS = false>      // KSC: k-steps compiled in (4, 8, 10, 12, 16 for N <= 16, 32, 40, 48, 64)
 // (Forcing two workgroups per CU -- 80 VGPRs at 12 waves per workgroup, 52 bytes of scratch -- was measured: 115 us against 102 us.
 // The launch moves ~380 MB -- 131 MB of blocks, 210 MB of direction rows (z and p_old of five slots), 42 MB of results -- in 102 us,
 // 3.7 TB/s: as fast as any streaming kernel of this library gets from the Infinity Cache / HBM.)
@@ -1680,7 +1693,7 @@ __global__ __launch_bounds__(64 * (NC / 16 / CT) * ((KSC + 3) / 4)) void k_bcg_m
                                                               const double* __restrict__ B_sys, const double* __restrict__ z,
                                                               const double* __restrict__ p_old, const double* __restrict__ beta,
                                                               int first, double* __restrict__ p_out, double* __restrict__ y,
-                                                              double* __restrict__ partial) {
+                                                              double* __restrict__ partial, MassOp<MASS> mass = MassOp<MASS>()) {
   extern __shared__ double lds[];
   // one wave per (row tile that exists for this KSC, group of CT column tiles); the column group is the FAST index, so that the
   // waves of a row tile -- and with them the idle lanes of a partial last tile -- spread over the four SIMDs (wave w runs on SIMD
@@ -1696,12 +1709,14 @@ __global__ __launch_bounds__(64 * (NC / 16 / CT) * ((KSC + 3) / 4)) void k_bcg_m
   double* Ps = Bs + 2 * BSZ;                           // [2][4 KSC][NC]
   double* bl = Ps + 2 * PSZ;                           // [NC] beta | [4][NC] theta_q (Q <= 4 with the wide panels: checked by the launcher)
   double* tl = bl + NC;                                // | one dump slot (entries beyond the block / the panel)
-  const int DUMP = 2 * BSZ + 2 * PSZ + 5 * NC;
+  // MASS: a fifth theta row -- the host's table holds 1.0 at [m][Q] (Q <= 4), the coefficient of the mass block
+  constexpr int TQ = MASS ? 5 : 4;
+  const int DUMP = 2 * BSZ + 2 * PSZ + (TQ + 1) * NC;
   for (int i = tid; i < 2 * BSZ + 2 * PSZ; i += NTH) lds[i] = 0.0;
   if (tid < NC) bl[tid] = (tid < nmu && !first) ? beta[tid] : 0.0;
   // (theta through LDS, not registers loaded in front of the loop: hipcc's wait-count state at the loop header keeps a load that was
   // never waited for on the entry path "pending" in every iteration, i.e. a vmcnt(0) in front of its first use -- behind the prefetch)
-  for (int i = tid; i < 4 * NC; i += NTH) tl[i] = (i % NC < nmu) ? theta[(i % NC) * 8 + i / NC] : 0.0;
+  for (int i = tid; i < TQ * NC; i += NTH) tl[i] = (i % NC < nmu) ? theta[(i % NC) * 8 + i / NC] : 0.0;
   constexpr int PF = (16 * KSC * KSC + NTH - 1) / NTH; // N * N <= (4 KSC)^2 <= NTH threads x PF
   constexpr int PP = (4 * KSC * NC + NTH - 1) / NTH;   // N nmu <= 4 KSC NC <= NTH threads x PP
   double pf[PF];                                       // (two sets, blocks b + 1 and b + 2 in flight, were measured: no faster -- the loads are not what a step waits for)
@@ -1715,7 +1730,7 @@ __global__ __launch_bounds__(64 * (NC / 16 / CT) * ((KSC + 3) / 4)) void k_bcg_m
     boff[k] = i < N * N ? (i / N) * LDB + i % N : -1;
   }
   auto load_block = [&](int slot, int q) {             // unconditional loads (clamped index): a conditional one compiles to a branch with a wait
-    const double* B = B_sys + ((((long)q * S + s) * 5 + slot) * N) * N;
+    const double* B = (MASS && q == Q) ? mass_block(mass, (long)s * N * N) : B_sys + ((((long)q * S + s) * 5 + slot) * N) * N;
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
       const int i = tid + NTH * k;
@@ -1757,7 +1772,7 @@ __global__ __launch_bounds__(64 * (NC / 16 / CT) * ((KSC + 3) / 4)) void k_bcg_m
       (poff[k] >= 0 ? dst + poff[k] : lds + DUMP)[0] = v;
     }
   };
-  const int nblk = ns * Q;
+  const int nblk = ns * Q + (MASS ? 1 : 0);            // MASS: the self slot's list has Q + 1 entries, the last is M_red[s]
   d4m acc[CT];
   double pv[CT][KSC];
 #pragma unroll
@@ -1775,7 +1790,8 @@ __global__ __launch_bounds__(64 * (NC / 16 / CT) * ((KSC + 3) / 4)) void k_bcg_m
 #pragma unroll
     for (int k = 0; k < PF; ++k) lds[boff[k] >= 0 ? (b & 1) * BSZ + boff[k] : DUMP] = pf[k];
     const double* Bc = Bs + (b & 1) * BSZ;
-    const int qn = q + 1 < Q ? q + 1 : 0, sin = q + 1 < Q ? si : si + 1;
+    const int qs = (MASS && slot == 2) ? Q + 1 : Q;    // entries of the current slot
+    const int qn = q + 1 < qs ? q + 1 : 0, sin = q + 1 < qs ? si : si + 1;
     const int slotn = sin < ns ? slot_at(sin) : slot;
     const bool newslot = q == 0, stage = newslot && si + 1 < ns;
     const int slot_next = stage ? slot_at(si + 1) : slot;
@@ -2233,6 +2249,7 @@ static int reduced_solve_batch_drive(lrbms_ctx* ctx, int Q, int N, int nmu, cons
         const int first = G.it == 0 ? 1 : 0;
         const long NM = (long)N * G.nm;
         if (use_mfma && GW > 16) {
+          KScope ks(ctx, "k_bcg_matvec_panel", G.st);      // (lrbms_kernel_timing: per-launch time, beside the <mass> form below)
 #define LRBMS_PANEL(NCV, KSV, CTV)                                                                                                  \
   hipLaunchKernelGGL((k_bcg_matvec_panel<NCV, KSV, CTV>), dim3(S), dim3(64 * (NCV / 16 / CTV) * ((KSV + 3) / 4)), lds_mfma, G.st, S, ctx->nbr, Q, N, G.nm,   \
                      G.theta_dev, B_sys, G.z, G.pin, G.scal + 2 * BMAX, first, G.pout, G.y, G.partial)
@@ -2331,6 +2348,363 @@ int launch_reduced_solve_batch_src(lrbms_ctx* ctx, int Q, int N, int K, int nmu,
 
 // y [M] = sum_j phi[j] x_K[j] [M] in the fma order of k_bcg_init_src: a streaming grid-stride loop, two doubles (one 16-byte load
 // per operand) per thread and step where every row is 16-byte aligned, a scalar loop otherwise
+// =========================================================================================================
+// Batched reduced implicit Euler: nmu <= 64 trajectories of (M_red + dt A(mu_m)) u_{k+1} = M_red u_k + dt b_m as ONE panel.
+// The groups, streams, fork / join and exit guard are those of reduced_solve_batch_drive; a loop over the time steps goes
+// around the iteration loop.  Per step and group: k_pbe_gather (x = u_k in the group's layout: the warm start), the MASS form
+// of the group's panel matvec with first = 1 and u_k as direction (y = (M + dt A_m) u_k), k_pbe_step_rhs (r = M u_k + dt b_m - y
+// and the partials of |M u_k + dt b_m|^2, the reference of the step's stopping rule), then the PCG of the stationary driver with
+// the MASS matvec.  The matvec reads Q (present slots) + 1 blocks per subdomain and iteration: M_red[s] is one more entry of the
+// self slot's list, dt sits in the theta table.  One preconditioner per call: inverse diagonal blocks and coarse level of
+// M_red + dt sum_q mean(theta)_q B_q.  A preconditioner installed with lrbms_reduced_precond_use belongs to A and is not used.
+namespace {
+
+// x[row][m] = uk[row][m0 + m]  (uk [rows][nmu] the caller's U[k], x [rows][nm] the group's iterate; one group: a plain copy)
+__global__ __launch_bounds__(256) void k_pbe_gather(long rows, int nm, int nmu, const double* __restrict__ uk, double* __restrict__ x) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < rows * nm; i += (long)gridDim.x * blockDim.x)
+    x[i] = uk[(i / nm) * nmu + i % nm];
+}
+
+// Step start of a group, one workgroup per subdomain:  rhs[i][m] = sum_c M_red[s][i][c] u[c][m] + dt b_m[s][i]  in the operation
+// order of k_red_step_residual(_src) (b_m = phi_0 b_0, then fma over j; dt b_m, then fma over c),  r = rhs - y,
+// partial[m][s] = sum_i rhs[i][m]^2.  K == 0: b_m = b [S][N] for every column; K >= 1: b [K][S][N], phi [nmu][nt1][K] (row `row`).
+// A column with rhs = 0 has u_k = 0 (M_red is SPD), hence y = 0 and r = 0: the PCG leaves it alone (alpha = beta = 0).
+__global__ __launch_bounds__(256) void k_pbe_step_rhs(int S, int N, int nm, int m0, double dt, const double* __restrict__ M_red,
+                                                      const double* __restrict__ u, int K, const double* __restrict__ phi, long phi_ld,
+                                                      const double* __restrict__ b, const double* __restrict__ y,
+                                                      double* __restrict__ r, double* __restrict__ partial) {
+  extern __shared__ double lds[];
+  const int s = blockIdx.x, tid = threadIdx.x, NM = N * nm;
+  double* us = lds;           // [N][nm]
+  double* sq = us + NM;       // [N][nm]
+  const long base = (long)s * NM;
+  for (int i = tid; i < NM; i += 256) us[i] = u[base + i];
+  __syncthreads();
+  for (int i = tid; i < NM; i += 256) {
+    const int row = i / nm, m = i - row * nm;
+    double bm;
+    if (K == 0) {
+      bm = b[(long)s * N + row];
+    } else {
+      const double* ph = phi + (long)(m0 + m) * phi_ld;
+      bm = ph[0] * b[(long)s * N + row];
+      for (int j = 1; j < K; ++j) bm = __fma_rn(ph[j], b[((long)j * S + s) * N + row], bm);
+    }
+    const double* Mr = M_red + ((long)s * N + row) * N;
+    double rhs = dt * bm;
+    for (int c = 0; c < N; ++c) rhs = __fma_rn(Mr[c], us[c * nm + m], rhs);
+    r[base + i] = rhs - y[base + i];
+    sq[i] = rhs * rhs;
+  }
+  __syncthreads();
+  if (tid < nm) {
+    double a = 0.0;
+    for (int row = 0; row < N; ++row) a += sq[row * nm + tid];
+    partial[(long)tid * gridDim.x + s] = a;               // [m][S], the layout k_bcg_reduce sums
+  }
+}
+
+}  // namespace
+
+// the group of reduced_batch_group_size and one more scalar array: |M u_k + dt b_m|^2 of the step
+static long pbe_group_size(long S, int N, int W) { return reduced_batch_group_size(S, N, W) + BMAX; }
+
+int64_t reduced_implicit_euler_batch_work_size(lrbms_ctx* ctx, int N, int nmu) {
+  const long S = ctx->S;
+  const int W = nmu <= 16 ? 16 : nmu <= 32 ? 32 : 64;
+  const long a = (long)((nmu + 15) / 16) * pbe_group_size(S, N, 16), b = (long)((nmu + W - 1) / W) * pbe_group_size(S, N, W);
+  return S * 5 * N * N + S * N * N + (a > b ? a : b) + 16;
+}
+
+// K == 0: rhs [S][N] for every column and step; K >= 1: rhs [K][S][N], phi_dev [nmu][nt+1][K] (device), step k takes row k + 1
+static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, int N, int nmu, const double* theta, double dt, int nt,
+                                     const double* B_sys, const double* M_red, const double* rhs, int K, const double* phi_dev,
+                                     double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st) {
+  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + " needs all subdomains on one rank");
+  if (N < 1 || N > 64 || nmu < 1 || nmu > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": need N <= 64, 1 <= nmu <= 64");
+  if (Q < 1 || Q > 8 || nt < 1 || !(dt > 0.0) || !(rtol > 0.0) || max_iter < 1)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": bad Q / nt / dt / rtol / max_iter");
+  if (nmu > 16 && Q > 4) return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": more than 16 parameters per call need Q <= 4");
+  const int S = ctx->S;
+  const int GW = reduced_batch_group_width(ctx, nmu);
+  const int ng = (nmu + GW - 1) / GW;
+  const long per_q = (long)S * 5 * N * N;
+  const long rows = (long)S * N;
+  QVec mean;                                             // dt * mean theta: the step operator the preconditioner is built for
+  for (int q = 0; q < 8; ++q) mean.v[q] = 0.0;
+  for (int m = 0; m < nmu; ++m)
+    for (int q = 0; q < Q; ++q) mean.v[q] += theta[m * Q + q] / nmu;
+  for (int q = 0; q < 8; ++q) mean.v[q] *= dt;
+  double* Amu = work;
+  double* Dinv = Amu + per_q;
+  double* gwork = Dinv + (long)S * N * N;
+  const long gsize = pbe_group_size(S, N, GW);
+  struct Group {
+    int nm, m0, it, last_it;
+    long total;
+    ThetaBatch th;                                      // dt theta [m][q] (panels of 16)
+    double thd[BMAX * 8];                               // dt theta [m][q] and 1.0 at [m][Q]: the table of the wide panels
+    double *ug, *r, *z, *pin, *pout, *y, *partial, *partial2, *scal, *theta_dev, *ref2;
+    hipStream_t st;
+    bool done;
+    double rel;
+  } g[4];
+  for (int k = 0; k < ng; ++k) {
+    Group& G = g[k];
+    G.m0 = GW * k;
+    G.nm = nmu - G.m0 < GW ? nmu - G.m0 : GW;
+    G.st = k == 0 ? st : ctx->aux[k - 1];
+    G.it = G.last_it = 0;
+    G.total = 0;
+    G.done = false;
+    G.rel = 0.0;
+    const long vec = rows * G.nm;
+    double* w = gwork + k * gsize;
+    G.ug = w;                                           // (one group: set per step, it iterates in place in U[k + 1])
+    G.r = w + rows * GW;
+    G.z = G.r + vec;
+    G.pin = G.z + vec;
+    G.pout = G.pin + vec;
+    G.y = G.pout + vec;
+    G.partial = w + 6L * rows * GW;
+    G.partial2 = G.partial + (long)S * GW;
+    G.scal = G.partial2 + (long)S * GW;                 // rz, alpha, beta, rr (BMAX each)
+    G.theta_dev = G.scal + 4 * BMAX;                    // [BMAX][8]
+    G.ref2 = G.theta_dev + 8 * BMAX;                    // [BMAX]
+    for (int m = 0; m < TBMAX; ++m)
+      for (int q = 0; q < 8; ++q) G.th.v[m * 8 + q] = (m < G.nm && q < Q) ? dt * theta[(G.m0 + m) * Q + q] : 0.0;
+    for (int m = 0; m < BMAX; ++m)
+      for (int q = 0; q < 8; ++q) G.thd[m * 8 + q] = (m < G.nm && q < Q) ? dt * theta[(G.m0 + m) * Q + q] : (m < G.nm && q == Q) ? 1.0 : 0.0;
+  }
+  // ---- the preconditioner of the call, on the caller's stream, before the groups fork
+  const double* A0inv = nullptr;
+  hipLaunchKernelGGL(k_assemble_mu_mass, dim3((unsigned)((per_q + 255) / 256 > 8192 ? 8192 : (per_q + 255) / 256)), dim3(256), 0, st,
+                     per_q, Q, N, mean, B_sys, M_red, Amu);
+  LRBMS_LAUNCH_CHECK(ctx);
+  if (int rc = launch_block_inverse(ctx, (int)S, N, Amu, Dinv, 5, 2, st)) return rc;
+  LRBMS_LAUNCH_CHECK(ctx);
+  if (int rc = coarse_setup(ctx, N, Amu, &A0inv, st)) return rc;
+  const int kp = (N + 3) & ~3, ldb = N + ((4 - N % 8) + 8) % 8;
+  const size_t bs_lds = (size_t)(N + 1) * ldb > (size_t)N * 16 ? (size_t)(N + 1) * ldb : (size_t)N * 16;
+  const int ksn = N <= 16 ? 4 : N <= 32 ? 8 : N <= 40 ? 10 : N <= 48 ? 12 : 16;        // the ksc_n ladder of reduced_solve_batch_drive
+  const size_t lds_panel = sizeof(double) * (2 * ((size_t)(N + 1) * ldb + 16) + 2 * (size_t)4 * ksn * GW + 6 * GW + 1);   // one theta row more
+  const size_t lds_mfma = GW == 16 ? sizeof(double) * ((size_t)5 * kp * 16 + bs_lds) : lds_panel;
+  const bool use_mfma = ctx->opt_solve_valu == 0;
+  if (use_mfma && lds_mfma > 160 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": panels exceed the LDS");
+#define LRBMS_PBE_DISPATCH(X)                                                                                      \
+  do {                                                                                                             \
+    if (GW == 64) {                                                                                                \
+      if (ksn == 4) X(64, 4); else if (ksn == 8) X(64, 8); else if (ksn == 10) X(64, 10); else if (ksn == 12) X(64, 12); else X(64, 16); \
+    } else {                                                                                                       \
+      if (ksn == 4) X(32, 4); else if (ksn == 8) X(32, 8); else if (ksn == 10) X(32, 10); else if (ksn == 12) X(32, 12); else X(32, 16); \
+    }                                                                                                              \
+  } while (0)
+  if (use_mfma && lds_mfma > 64 * 1024) {
+    if (GW == 16) {
+      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec_mfma<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mfma));
+    } else {
+#define LRBMS_PBE_ATTR(NCV, KSV) \
+  LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec_panel<NCV, KSV, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mfma))
+      LRBMS_PBE_DISPATCH(LRBMS_PBE_ATTR);
+#undef LRBMS_PBE_ATTR
+    }
+  }
+  const size_t lds_mv = sizeof(double) * (5 * (size_t)N * 16 + (size_t)N * N + 256);
+  if (!use_mfma && lds_mv > 64 * 1024) {
+    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec<BCG_KMAX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mv));
+    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mv));
+  }
+  const size_t lds_upd_mfma = sizeof(double) * ((size_t)kp * GW + (size_t)2 * N * GW);
+  if (use_mfma && lds_upd_mfma > 64 * 1024) {
+    if (GW == 64)
+      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_update_mfma<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_upd_mfma));
+    else
+      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_update_mfma<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_upd_mfma));
+  }
+  if (ng > 1) {
+    LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
+    for (int k = 1; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(g[k].st, ctx->ev_fork, 0));
+  }
+  auto join = [&]() -> int {                             // the side streams joined into the caller's
+    for (int k = 1; k < ng; ++k) {
+      LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[k - 1], g[k].st));
+      LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0));
+    }
+    return LRBMS_OK;
+  };
+  // every early return between the fork and the join leaves through this guard (see reduced_solve_batch_drive)
+  struct ExitGuard {
+    lrbms_ctx* ctx;
+    hipStream_t st;
+    hipStream_t gs[4];
+    int ng;
+    bool armed;
+    ~ExitGuard() {
+      if (!armed) return;
+      for (int k = 0; k < ng; ++k) (void)hipStreamSynchronize(gs[k]);
+      for (int k = 1; k < ng; ++k) {
+        (void)hipEventRecord(ctx->ev_join[k - 1], gs[k]);
+        (void)hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0);
+      }
+    }
+  } guard{ctx, st, {g[0].st, ng > 1 ? g[1].st : st, ng > 2 ? g[2].st : st, ng > 3 ? g[3].st : st}, ng, true};
+  // the step operator applied to the direction z (+ beta p_old): the MASS form of the matvec reduced_solve_batch_drive would take
+  auto matvec = [&](Group& G, const double* zdir, int first) {
+    const long NM = (long)N * G.nm;
+    const MassOp<true> mo{M_red};
+    if (use_mfma && GW > 16) {
+      KScope ks(ctx, "k_bcg_matvec_panel<mass>", G.st);
+#define LRBMS_PBE_PANEL(NCV, KSV)                                                                                                    \
+  hipLaunchKernelGGL((k_bcg_matvec_panel<NCV, KSV, 1, true>), dim3(S), dim3(64 * (NCV / 16) * ((KSV + 3) / 4)), lds_mfma, G.st, S, ctx->nbr, Q, N, G.nm, \
+                     G.theta_dev, B_sys, zdir, G.pin, G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo)
+      LRBMS_PBE_DISPATCH(LRBMS_PBE_PANEL);
+#undef LRBMS_PBE_PANEL
+    } else if (use_mfma) {
+      hipLaunchKernelGGL((k_bcg_matvec_mfma<16, true>), dim3(S), dim3(256), lds_mfma, G.st, S, ctx->nbr, Q, N, G.nm, G.th, B_sys, zdir, G.pin,
+                         G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo);
+    } else if (NM <= 768) {
+      hipLaunchKernelGGL((k_bcg_matvec<3, true>), dim3(S), dim3(256), lds_mv, G.st, S, ctx->nbr, Q, N, G.nm, G.th, B_sys, zdir, G.pin,
+                         G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo);
+    } else {
+      hipLaunchKernelGGL((k_bcg_matvec<BCG_KMAX, true>), dim3(S), dim3(256), lds_mv, G.st, S, ctx->nbr, Q, N, G.nm, G.th, B_sys, zdir, G.pin,
+                         G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo);
+    }
+  };
+  auto update = [&](Group& G, int first) {
+    const size_t lds_upd = sizeof(double) * 3 * (size_t)N * G.nm;
+    if (use_mfma && GW == 64)
+      hipLaunchKernelGGL(k_bcg_update_mfma<64>, dim3(S), dim3(1024), lds_upd_mfma, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
+                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
+    else if (use_mfma && GW == 32)
+      hipLaunchKernelGGL(k_bcg_update_mfma<32>, dim3(S), dim3(512), lds_upd_mfma, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
+                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
+    else if (use_mfma)
+      hipLaunchKernelGGL(k_bcg_update_mfma<16>, dim3(S), dim3(256), lds_upd_mfma, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
+                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
+    else
+      hipLaunchKernelGGL(k_bcg_update, dim3(S), dim3(256), lds_upd, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
+                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
+    if (A0inv) hipLaunchKernelGGL(k_coarse_apply, dim3((S + 15) / 16, (G.nm + 15) / 16), dim3(1024), 0, G.st, S, N, G.nm, A0inv, G.r, G.z, G.partial);
+    hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, S, G.nm, G.partial, G.partial2, G.scal, first ? 0 : 2);
+  };
+  const size_t lds_rhs = sizeof(double) * 2 * (size_t)N * GW;
+  double host[4][5 * BMAX];                              // rz, alpha, beta, rr | ref2: scal, theta_dev and ref2 are NOT adjacent, two copies
+  int rc = LRBMS_OK;
+  double worst = 0.0;
+  bool capped = false;
+  for (int step = 0; step < nt && rc == LRBMS_OK && !capped; ++step) {
+    const double* uk = U + (long)step * rows * nmu;
+    double* un = U + (long)(step + 1) * rows * nmu;
+    // ---- step start: every group, no look at the host
+    for (int k = 0; k < ng; ++k) {
+      Group& G = g[k];
+      const long vec = rows * G.nm;
+      const unsigned nb = (unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256);
+      if (ng == 1) G.ug = un;
+      if (step == 0 && GW > 16)
+        LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(G.theta_dev, G.thd, sizeof(double) * 8 * BMAX, hipMemcpyHostToDevice, G.st));
+      hipLaunchKernelGGL(k_pbe_gather, dim3(nb), dim3(256), 0, G.st, rows, G.nm, nmu, uk + G.m0, G.ug);
+      matvec(G, G.ug, 1);
+      hipLaunchKernelGGL(k_pbe_step_rhs, dim3(S), dim3(256), lds_rhs, G.st, S, N, G.nm, G.m0, dt, M_red, G.ug, K,
+                         K ? phi_dev + (long)(step + 1) * K : nullptr, (long)(nt + 1) * K, rhs, G.y, G.r, G.partial);
+      hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, S, G.nm, G.partial, (const double*)nullptr, G.ref2, 0);
+      update(G, 1);
+      G.it = 0;
+      G.done = false;
+    }
+    LRBMS_LAUNCH_CHECK(ctx);
+    // the first block goes out without a look at the residuals: a little short of what the previous step took
+    int block = 10;
+    for (int k = 0; k < ng; ++k) {
+      const int guess = (int)(0.8 * g[k].last_it);
+      if (step > 0 && guess > block) block = guess;
+    }
+    if (step > 0 && block > 40) block = 40;
+    bool all_done = false;
+    while (!all_done) {
+      for (int c = 0; c < block; ++c)
+        for (int k = 0; k < ng; ++k) {
+          Group& G = g[k];
+          if (G.done || G.it >= max_iter) continue;
+          matvec(G, G.z, G.it == 0 ? 1 : 0);
+          hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, S, G.nm, G.partial, (const double*)nullptr, G.scal, 1);
+          update(G, 0);
+          double* tmp = G.pin; G.pin = G.pout; G.pout = tmp;
+          ++G.it;
+        }
+      LRBMS_LAUNCH_CHECK(ctx);
+      for (int k = 0; k < ng; ++k)
+        if (!g[k].done) {
+          LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host[k], g[k].scal, sizeof(double) * 4 * BMAX, hipMemcpyDeviceToHost, g[k].st));
+          LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host[k] + 4 * BMAX, g[k].ref2, sizeof(double) * BMAX, hipMemcpyDeviceToHost, g[k].st));
+        }
+      all_done = true;
+      double need_max = 0.0;
+      for (int k = 0; k < ng; ++k) {
+        Group& G = g[k];
+        if (G.done) continue;
+        LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(G.st));
+        G.rel = 0.0;
+        for (int m = 0; m < G.nm; ++m) {
+          const double ref2 = host[k][4 * BMAX + m];
+          const double rm = ref2 > 0.0 ? sqrt(host[k][3 * BMAX + m] / ref2) : 0.0;     // zero right-hand side: u_{k+1} = u_k
+          if (!(rm == rm) || !(ref2 == ref2)) rc = LRBMS_E_NOT_CONVERGED;
+          G.rel = rm > G.rel ? rm : G.rel;
+        }
+        if (G.rel <= rtol || G.it >= max_iter || rc != LRBMS_OK) {
+          G.done = true;
+          continue;
+        }
+        all_done = false;
+        double need = 10.0;
+        if (G.it > 0) {
+          const double rate = log(G.rel) / G.it;          // (relative to |rhs|, as in red_cg_run: aim a little short)
+          if (rate < 0.0) need = 0.8 * (log(rtol) - log(G.rel)) / rate;
+        }
+        need_max = need > need_max ? need : need_max;
+      }
+      block = need_max < 2.0 ? 2 : need_max > 40.0 ? 40 : (int)need_max;
+    }
+    int it = 0;
+    for (int k = 0; k < ng; ++k) {
+      Group& G = g[k];
+      G.last_it = G.it;
+      it = G.it > it ? G.it : it;
+      worst = G.rel > worst ? G.rel : worst;
+      if (G.rel > rtol) capped = true;
+      if (ng > 1) {
+        const long vec = rows * G.nm;
+        hipLaunchKernelGGL(k_bcg_scatter, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, G.st, rows,
+                           G.nm, nmu, G.ug, un + G.m0);
+      }
+    }
+    g[0].total += it;                                    // the iterations of the slowest group, summed over the steps
+    LRBMS_LAUNCH_CHECK(ctx);
+  }
+  if (int jrc = join()) return jrc;
+  guard.armed = false;
+  if (info) { info[0] = (double)g[0].total; info[1] = worst; }
+  if (rc != LRBMS_OK) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual (system not SPD?)");
+  if (capped) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": CG did not reach rtol");
+  return LRBMS_OK;
+}
+
+int launch_reduced_implicit_euler_batch(lrbms_ctx* ctx, int Q, int N, int nmu, const double* theta, double dt, int nt, const double* B_sys,
+                                        const double* M_red, const double* rhs_red, double* work, double* U, double rtol, int max_iter,
+                                        double* info, hipStream_t st) {
+  return reduced_euler_batch_drive(ctx, "reduced_implicit_euler_batch", Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red, 0, nullptr, work,
+                                   U, rtol, max_iter, info, st);
+}
+
+int launch_reduced_implicit_euler_batch_src(lrbms_ctx* ctx, int Q, int N, int K, int nmu, const double* theta, double dt, int nt,
+                                            const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
+                                            double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st) {
+  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_src: need 1 <= K <= 64");
+  return reduced_euler_batch_drive(ctx, "reduced_implicit_euler_batch_src", Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red_K, K, phi,
+                                   work, U, rtol, max_iter, info, st);
+}
+
+
 namespace {
 struct SrcPhi { double v[64]; };
 

@@ -555,6 +555,31 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
         self.last_solve_info = info
         return ReducedVectorArray(U.permute(1, 2, 0))
 
+    def solve_batch(self, mus):
+        """Parameter sweep over the parabolic reduced model: one ``lrbms_reduced_implicit_euler_batch(_src)`` call per 64
+        parameters (every time step is one panel PCG for all of them); returns a list with, per parameter, the
+        ``ReducedVectorArray`` that ``solve(mu)`` returns, so ``estimate(U_m, mu_m)`` takes an entry as it is."""
+        eng = self.d.engine
+        if eng.S_ext != eng.S:
+            raise NotImplementedError('solve_batch of the parabolic reduced model needs all subdomains on one rank '
+                                      '(lrbms_reduced_implicit_euler_batch: S_ext == S); solve(mu) works on a sharded discretization')
+        mus = list(mus)
+        nt = self.time_stepper.nt
+        dt = self.T / nt
+        out, its, rel = [], 0, 0.0
+        for b0 in range(0, len(mus), 64):
+            chunk = mus[b0:b0 + 64]
+            thetas = np.array([self.d.theta(mu) for mu in chunk])
+            if self.rhs_red_K is not None:                           # time-dependent source: a coefficient table per parameter
+                phi = self._torch.stack([self.d._phi_device(mu) for mu in chunk]).contiguous()
+                U, info = eng.ctx.reduced_implicit_euler_batch_src(thetas, dt, nt, self.B_sys, self.M_red, self.rhs_red_K, phi)
+            else:
+                U, info = eng.ctx.reduced_implicit_euler_batch(thetas, dt, nt, self.B_sys, self.M_red, self.rhs_red)
+            its, rel = its + info['iterations'], max(rel, info['relative_residual'])
+            out += [ReducedVectorArray(U[..., m].permute(1, 2, 0)) for m in range(len(chunk))]
+        self.last_solve_info = {'iterations': its, 'relative_residual': rel}
+        return out
+
     def _local_estimates(self, U, mu):
         """With a time-dependent source: the reduced counterpart of InstationaryDuneDiscretization._local_estimates -- the
         batched estimate with f2 = 0, r_fd = 0 plus ``lrbms_reduced_source_terms`` on rhs_red_K's companions r_fd_K, F2."""
