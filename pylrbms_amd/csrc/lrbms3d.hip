@@ -674,7 +674,9 @@ __global__ __launch_bounds__(pg_max_threads(KIND == G_BB ? (RT > 2 ? 8 : 4) : RT
     if (KIND == G_CPL) {
       const int sp = side * t.ncf + item;
       ix.e = t.side_elem[sp];
-      ix.eo = t.side_elem_out[sp];
+      // a padded position (a side with fewer faces than ncf) has zero blocks, but its operand rows are loaded all the same: take them
+      // from the neighbour's element at position 0 of the side -- inside the cube layer, the only rows a halo slab is known to hold
+      ix.eo = t.side_elem_out[ix.e >= 0 ? sp : side * t.ncf];
     }
     if (KIND == G_SYS) {
       const int4 v = *reinterpret_cast<const int4*>(t.nb_elem + item * 4);
@@ -1005,7 +1007,7 @@ __global__ __launch_bounds__(pg_max_threads(KIND == G_BB ? (RT > 2 ? 8 : 4) : RT
     if (FACEK) {
       eb[0] = (unsigned)ix1.aux[0] * ((unsigned)QN * 8u);
     } else if (KIND == G_CPL) {
-      eb[0] = (unsigned)(on ? ix1.eo : 0) * erow;
+      eb[0] = (unsigned)ix1.eo * erow;
     } else {
       eb[0] = (unsigned)e * erow;
       if (KIND == G_SYS) {

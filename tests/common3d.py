@@ -43,16 +43,24 @@ PROBLEMS = {
 }
 
 
-def make_problem(name):
-    P, kc, lams, thetas, kappa, N, mu = PROBLEMS[name]
+UNIT_DOMAIN = ([0.0, 0.0, 0.0], [1.0, 1.0, 1.0])
+
+
+def make_problem(name, domain=None, spec=None):
+    """The problem ``name`` of ``PROBLEMS`` -- or, with ``spec``, a tuple of the same layout under a name of the caller's -- on the
+    box ``domain`` = (lower_left, upper_right); default: the unit cube."""
+    P, kc, lams, thetas, kappa, N, mu = PROBLEMS[name] if spec is None else spec
+    domain = UNIT_DOMAIN if domain is None else (list(domain[0]), list(domain[1]))
     from pylrbms_amd.grid3d import make_grid3d
-    grid = make_grid3d(num_subdomains=P, cubes_per_subdomain_and_dim=kc, kappa=kappa)
+    grid = make_grid3d(domain=domain, num_subdomains=P, cubes_per_subdomain_and_dim=kc, kappa=kappa)
     return dict(name=name, grid=grid, lambdas=lams, thetas=thetas, kappa=kappa, f=_f, lambda_bar=_lbar, lambda_hat=_lbar,
-                mu_bar=0.5, mu_hat=0.5, N=N, mu=mu, P=P, kc=kc)
+                mu_bar=0.5, mu_hat=0.5, N=N, mu=mu, P=P, kc=kc, domain=domain)
 
 
-def oracle_of(p):
-    mesh = KuhnMesh3D(np.asarray(p['P']) * np.asarray(p['kc']), p['P'])
+def oracle_of(p, domain=None):
+    """The CPU oracle of a problem of ``make_problem``, on the problem's box unless ``domain`` names another."""
+    lo, hi = p.get('domain', UNIT_DOMAIN) if domain is None else domain
+    mesh = KuhnMesh3D(np.asarray(p['P']) * np.asarray(p['kc']), p['P'], lower_left=lo, upper_right=hi)
     return Discretization3D(mesh, p['lambdas'], p['thetas'], p['kappa'], p['f'], p['lambda_bar'], p['lambda_hat'], p['mu_bar'],
                             p['mu_hat'])
 
