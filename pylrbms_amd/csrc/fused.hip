@@ -2444,7 +2444,9 @@ __global__ __launch_bounds__(512, 2) void k_f1v(Tmpl t, F1Args a, GrpTable gt) {
 //   * role B multiplies W'^q_T (2 x 3 per component; k_prep_lds forms it from A_ab with the template table t.hab) with the three
 //     flux rows: four output rows, on the 4x4x4 MFMA (five instructions cover the 2 N columns of an element's flux rows);
 //   * the column tiles come in two kinds (3 or 2 K rows per element) and three classes (row tiles needed); which SIMD owns which
-//     is a compile-time plan (F1wPlan) that balances the MFMA count: 38 / 38 / 37 / 37 per chunk and SIMD.
+//     is a compile-time plan (F1wPlan) that balances the MFMA count: 38 / 38 / 37 / 37 per chunk and SIMD;
+//   * of those, the third row tile of a class-3 column tile (rows 32 .. N - 1: at most 8 of 16 live) takes two 4x4x4 per k-step in
+//     place of one 16x16x4 (row_tile in f1w_body): 9 / 9 / 8 / 8 k-steps per chunk and SIMD, all in role B.
 struct F1wPlan {
   static constexpr int NL = 7, LA = 2;                 // levels (four column tiles each: tile 4 l + e on SIMD e); role A takes the first LA
   // v = e >> 1 (SIMDs 0, 1 / 2, 3).  level 0: block 0 of the four K3 symmetric groups; 1: their block 1; 2: v0 their packed tails,
@@ -2460,7 +2462,15 @@ struct F1wPlan {
   }
   static constexpr int slots(int role, int v) { return slots_before(role, v, count(role)); }
   static constexpr int max_slots(int role) { return slots(role, 0) > slots(role, 1) ? slots(role, 0) : slots(role, 1); }
+  // The third row tile (rows 32 .. 47, at most N - 32 <= 8 of them live) runs on the 4x4x4 shape: its slot keeps components [0]
+  // and [1] of the d4 only (rows 32 + lk, 36 + lk).  True for the third slot of a class-3 tile -- all of them are role B's.
+  static constexpr bool tail_slot(int role, int v, int i) {
+    for (int jt = 0; jt < count(role); ++jt)
+      if (cls(first(role) + jt, v) == 3 && i == slots_before(role, v, jt) + 2) return true;
+    return false;
+  }
 };
+static_assert(F1wPlan::cls(0, 0) < 3 && F1wPlan::cls(0, 1) < 3 && F1wPlan::cls(1, 0) < 3 && F1wPlan::cls(1, 1) < 3, "class-3 tiles are role B's");
 template <int V> struct F1wV { static constexpr int value = V; };
 
 template <int ROLE>
@@ -2493,6 +2503,20 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
 #pragma unroll
   for (int i = 0; i < NS; ++i) acc[i] = (d4){0.0, 0.0, 0.0, 0.0};
 
+  // One k-step of row tile i of a column tile.  Row tiles 0 and 1 are full: one 16x16x4.  Row tile 2 holds rows 32 .. N - 1 <= 39:
+  // two 4x4x4 (lane map at role B's apply below) in place of a 16x16x4 with eight or more dead rows -- 2 x 16 cycles for 64.  The B
+  // operand is the same fragment (lane (lk, li): Y[kk + lk][column li], block = li >> 2); A, replicated over the four blocks, is
+  // at[h] = X[kk + lk][32 + 4 h + (li & 3)]; the lane receives row 32 + 4 h + lk of column li, which is where components [0] and [1]
+  // of the 16x16x4 accumulator live.  Columns of Xs / Zs at or beyond N stay zero (role A never writes them): their products land
+  // in rows >= N only, which the epilogue drops.  Both instructions are issued at every N (no branch around an MFMA).
+  auto row_tile = [](d4& c, int i, double a16, const double (&at)[2], double bv) {
+    if (i < 2) {
+      c = __builtin_amdgcn_mfma_f64_16x16x4f64(a16, bv, c, 0, 0, 0);
+    } else {
+      c[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(at[0], bv, c[0], 0, 0, 0);
+      c[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(at[1], bv, c[1], 0, 0, 0);
+    }
+  };
   // the projection of one chunk: 3 k-steps over the V rows for the tiles of kind 3, 2 k-steps over the Z rows for the tiles of kind 2
   auto mfma_phase = [&](int c, auto vtag) {
     constexpr int V = decltype(vtag)::value;
@@ -2503,16 +2527,17 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
     if constexpr (any3) {
 #pragma unroll
       for (int kk = 0; kk < 3 * EC; kk += 4) {
-        double av[NTX];
+        double av[NTX], at[2];
 #pragma unroll
         for (int i = 0; i < NTX; ++i) av[i] = Xb[(kk + lk) * LDX + i * 16 + li];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) at[h] = Xb[(kk + lk) * LDX + 32 + 4 * h + (li & 3)];
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt) {
           if (LV::kr(LV0 + jt, V) == 3) {      // (compile time once the loop is unrolled)
             const double bv = Yb[(kk + lk) * LDY + (4 * (LV0 + jt) + e) * 16 + li];
 #pragma unroll
-            for (int i = 0; i < LV::cls(LV0 + jt, V); ++i)
-              acc[LV::slots_before(ROLE, V, jt) + i] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bv, acc[LV::slots_before(ROLE, V, jt) + i], 0, 0, 0);
+            for (int i = 0; i < LV::cls(LV0 + jt, V); ++i) row_tile(acc[LV::slots_before(ROLE, V, jt) + i], i, av[i], at, bv);
           }
         }
       }
@@ -2520,16 +2545,17 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
     if constexpr (ROLE == 1) {
 #pragma unroll
       for (int kk = 0; kk < 2 * EC; kk += 4) {
-        double av[NTX];
+        double av[NTX], at[2];
 #pragma unroll
         for (int i = 0; i < NTX; ++i) av[i] = Zb[(kk + lk) * LDX + i * 16 + li];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) at[h] = Zb[(kk + lk) * LDX + 32 + 4 * h + (li & 3)];
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt) {
           if (LV::kr(LV0 + jt, V) == 2) {
             const double bv = Yb[(kk + lk) * LDY + (4 * (LV0 + jt) + e) * 16 + li];
 #pragma unroll
-            for (int i = 0; i < LV::cls(LV0 + jt, V); ++i)
-              acc[LV::slots_before(ROLE, V, jt) + i] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bv, acc[LV::slots_before(ROLE, V, jt) + i], 0, 0, 0);
+            for (int i = 0; i < LV::cls(LV0 + jt, V); ++i) row_tile(acc[LV::slots_before(ROLE, V, jt) + i], i, av[i], at, bv);
           }
         }
       }
@@ -2846,10 +2872,16 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
     const long wg = 8L * PW + 64;
     double* mine = a.part + ((long)s * ksplit + blockIdx.z) * wg;
     double* pw = mine + (long)wave * PW + 2 * lane;
+    // (a tail slot carries its two doubles in the h = 0 half; its h = 1 half is neither written nor read)
+    auto put = [&](auto vtag) {
+      constexpr int V = decltype(vtag)::value;
 #pragma unroll
-    for (int i = 0; i < NS; ++i)
+      for (int i = 0; i < NS; ++i)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) store_sc1_b128(pw + (i * 2 + h) * 128, acc[i][2 * h], acc[i][2 * h + 1]);
+        for (int h = 0; h < (LV::tail_slot(ROLE, V, i) ? 1 : 2); ++h) store_sc1_b128(pw + (i * 2 + h) * 128, acc[i][2 * h], acc[i][2 * h + 1]);
+    };
+    if (ROLE == 0 || e < 2) put(F1wV<0>{});
+    else put(F1wV<1>{});
     __syncthreads();
     if (a.rhs_red != nullptr && tid < N) {
       double sum = 0.0;
@@ -2865,13 +2897,18 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
     const double* all = a.part + (long)s * ksplit * wg;
 #pragma unroll
     for (int i = 0; i < NS; ++i) acc[i] = (d4){0.0, 0.0, 0.0, 0.0};
-    for (int z = 0; z < ksplit; ++z) {
-      const double* pz = all + z * wg + (long)wave * PW + 2 * lane;
+    auto gather = [&](auto vtag) {
+      constexpr int V = decltype(vtag)::value;
+      for (int z = 0; z < ksplit; ++z) {
+        const double* pz = all + z * wg + (long)wave * PW + 2 * lane;
 #pragma unroll
-      for (int i = 0; i < NS; ++i)
+        for (int i = 0; i < NS; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][r] += load_sc1_b64(pz + (i * 2 + r / 2) * 128 + r % 2);
-    }
+          for (int r = 0; r < (LV::tail_slot(ROLE, V, i) ? 2 : 4); ++r) acc[i][r] += load_sc1_b64(pz + (i * 2 + r / 2) * 128 + r % 2);
+      }
+    };
+    if (ROLE == 0 || e < 2) gather(F1wV<0>{});
+    else gather(F1wV<1>{});
     if (a.rhs_red != nullptr && tid < N) {
       double sum = 0.0;
       for (int z = 0; z < ksplit; ++z) sum += load_sc1_b64(all + z * wg + 8L * PW + tid);
@@ -2893,7 +2930,7 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
 #pragma unroll
       for (int i = 0; i < LV::cls(LV0 + jt, V); ++i) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
+        for (int r = 0; r < (i < 2 ? 4 : 2); ++r) {      // (the third row tile holds rows 32 + lk, 36 + lk only: see row_tile)
           const int row = i * 16 + lk + 4 * r;
           const double val = acc[LV::slots_before(ROLE, V, jt) + i][r];
           if (live && row < N && (!sym || row <= jj)) {
@@ -4631,8 +4668,9 @@ long f1_mfma_per_subdomain(lrbms_ctx* ctx, int Q, int N) {
   const bool unified = (Q == 1 || Q == 2) && one_slice && ntx <= 3 && ctx->opt_f1_legacy != 1;
   int lv[3] = {0, 0, 0};
   if (unified && ctx->opt_f1_legacy == 0 && f1w_usable(ctx, Q, N) && f1w_layout(groups, N, Q))
-    return (long)nch * 150 + (long)t.nT * 3 * ntx + (long)t.nT * 5 / 4;      // k_f1w: 18 tile rows x 3 + 48 x 2 k-steps per chunk; role A's apply;
-                                                                              // role B's: five 4x4x4_4b (512 flop: a quarter unit) per element
+    return (long)nch * (150 - 34 + 34 * 2 / 4) + (long)t.nT * 3 * ntx + (long)t.nT * 5 / 4;      // k_f1w: 18 tile rows x 3 + 48 x 2 k-steps per chunk; role A's apply;
+                                                                              // role B's: five 4x4x4_4b (512 flop: a quarter unit) per element;
+                                                                              // 34 of the 150 k-steps (third row tile, class 3) are two 4x4x4_4b each
   if (unified && ctx->opt_f1_legacy != 2 && N % 2 == 0 && N >= 2 && f1v_layout(groups, N, ntx, lv) && f1v_instantiated(ntx, Q, lv))
     return (long)nch * 3 * 4 * (lv[0] + 2 * lv[1] + 3 * lv[2]) + (long)t.nT * (3 * ntx + Q * ntx);      // projection + the two applies
   const int tiles = (ng * N + 15) / 16;                         // k_f1u skips the column tiles beyond the last column

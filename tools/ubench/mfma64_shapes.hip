@@ -5,11 +5,16 @@
 //   part 2: cycles per instruction of a stream of independent / dependent MFMAs of either shape and of a "4" placed between two "16",
 //           with one wave per SIMD (waves 4-7 of a 512-thread workgroup, one workgroup per CU) and with two (waves 0-3 stream
 //           another shape beside them: serial means both ~ sum, overlap means both ~ max).
-// build: hipcc --offload-arch=gfx950 -O3 -o mfma64_shapes mfma64_shapes.hip        run: mfma64_shapes [blocks = 256]
+//   part 3: an ACCUMULATING chain (non-zero running C, 128 k-steps) of the half-empty third row tile of k_f1w: rows 0-7 of one "16"
+//           (output registers 0 and 1) against two chains of "4" (rows 0-3 and 4-7, A replicated over the four blocks), same random
+//           operands, compared bit for bit; 256 independent trials.
+// build: hipcc --offload-arch=gfx950 -O3 -o mfma64_shapes mfma64_shapes.hip        run: mfma64_shapes [blocks = 256] [accumulate]
+//   (a second argument runs part 3 alone)
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(64) void k_layout(unsigned long long* out) {
@@ -26,6 +31,73 @@ __global__ __launch_bounds__(64) void k_layout(unsigned long long* out) {
 __global__ __launch_bounds__(64) void k_value(double* out, const double* A, const double* B) {
   const int lane = threadIdx.x;
   out[lane] = __builtin_amdgcn_mfma_f64_4x4x4f64(A[lane], B[lane], 0.0, 0, 0, 0);
+}
+
+// part 3.  X[k][16] (columns 8-15 zero: the rows of the tile beyond N), Y[k][16], C[16][16]; lane = 16 lk + li.  The "16" takes
+// A = X[kk + lk][li], B = Y[kk + lk][li] and returns row lk + 4 r of column li in register r; the "4" takes A = X[kk + lk][4 h + (li & 3)]
+// (h = 0, 1), the same B, and returns row 4 h + lk of column li.
+constexpr int ACC_KSTEPS = 128;
+__global__ __launch_bounds__(64) void k_accumulate(double* out16, double* out4, const double* X, const double* Y, const double* C) {
+  const int lane = threadIdx.x, li = lane & 15, lk = lane >> 4;
+  X += (size_t)blockIdx.x * ACC_KSTEPS * 64, Y += (size_t)blockIdx.x * ACC_KSTEPS * 64, C += (size_t)blockIdx.x * 256;
+  d4 acc;
+  for (int r = 0; r < 4; ++r) acc[r] = C[(lk + 4 * r) * 16 + li];
+  double t0 = acc[0], t1 = acc[1];
+  for (int kk = 0; kk < 4 * ACC_KSTEPS; kk += 4) {
+    const double bv = Y[(kk + lk) * 16 + li];
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(X[(kk + lk) * 16 + li], bv, acc, 0, 0, 0);
+    t0 = __builtin_amdgcn_mfma_f64_4x4x4f64(X[(kk + lk) * 16 + (li & 3)], bv, t0, 0, 0, 0);
+    t1 = __builtin_amdgcn_mfma_f64_4x4x4f64(X[(kk + lk) * 16 + 4 + (li & 3)], bv, t1, 0, 0, 0);
+  }
+  out16[blockIdx.x * 128 + 2 * lane] = acc[0], out16[blockIdx.x * 128 + 2 * lane + 1] = acc[1];
+  out4[blockIdx.x * 128 + 2 * lane] = t0, out4[blockIdx.x * 128 + 2 * lane + 1] = t1;
+}
+
+static int accumulate_case() {
+  const int trials = 256, nk = 4 * ACC_KSTEPS;
+  const size_t nx = (size_t)trials * nk * 16, nc = (size_t)trials * 256, no = (size_t)trials * 128;
+  double *X = (double*)malloc(8 * nx), *Y = (double*)malloc(8 * nx), *C = (double*)malloc(8 * nc);
+  double *h16 = (double*)malloc(8 * no), *h4 = (double*)malloc(8 * no);
+  unsigned long long st = 0x9E3779B97F4A7C15ull;
+  auto rnd = [&]() {      // signed, magnitudes over eight binades: sums cancel and every rounding position occurs
+    st = st * 6364136223846793005ull + 1442695040888963407ull;
+    const double m = 1.0 + (double)((st >> 11) & ((1ull << 52) - 1)) / 4503599627370496.0;
+    return ((st >> 63) ? -m : m) * ldexp(1.0, (int)((st >> 8) & 7) - 4);
+  };
+  for (size_t i = 0; i < nx; ++i) X[i] = i % 16 < 8 ? rnd() : 0.0, Y[i] = rnd();
+  for (size_t i = 0; i < nc; ++i) C[i] = 16.0 * rnd();
+  double *dX, *dY, *dC, *d16, *d4o;
+  hipMalloc(&dX, 8 * nx), hipMalloc(&dY, 8 * nx), hipMalloc(&dC, 8 * nc), hipMalloc(&d16, 8 * no), hipMalloc(&d4o, 8 * no);
+  hipMemcpy(dX, X, 8 * nx, hipMemcpyHostToDevice), hipMemcpy(dY, Y, 8 * nx, hipMemcpyHostToDevice), hipMemcpy(dC, C, 8 * nc, hipMemcpyHostToDevice);
+  hipMemset(d16, 0xff, 8 * no), hipMemset(d4o, 0xff, 8 * no);
+  hipLaunchKernelGGL(k_accumulate, dim3(trials), dim3(64), 0, 0, d16, d4o, dX, dY, dC);
+  if (hipDeviceSynchronize() != hipSuccess) return printf("part 3: kernel failed\n"), 1;
+  hipMemcpy(h16, d16, 8 * no, hipMemcpyDeviceToHost), hipMemcpy(h4, d4o, 8 * no, hipMemcpyDeviceToHost);
+  size_t differ = 0;
+  double worst16 = 0.0, worst4 = 0.0, worst_pair = 0.0;
+  for (int t = 0; t < trials; ++t)
+    for (int lane = 0; lane < 64; ++lane)
+      for (int r = 0; r < 2; ++r) {
+        const int row = (lane >> 4) + 4 * r, col = lane & 15;
+        long double ref = C[(size_t)t * 256 + row * 16 + col], mag = fabsl(ref);
+        for (int k = 0; k < nk; ++k) {
+          const long double pr = (long double)X[((size_t)t * nk + k) * 16 + row] * Y[((size_t)t * nk + k) * 16 + col];
+          ref += pr, mag += fabsl(pr);
+        }
+        const size_t o = (size_t)t * 128 + 2 * lane + r;
+        unsigned long long b16, b4;
+        memcpy(&b16, h16 + o, 8), memcpy(&b4, h4 + o, 8);
+        differ += b16 != b4;
+        worst16 = fmax(worst16, (double)(fabsl(h16[o] - ref) / mag)), worst4 = fmax(worst4, (double)(fabsl(h4[o] - ref) / mag));
+        worst_pair = fmax(worst_pair, (double)(fabsl((long double)h16[o] - h4[o]) / mag));
+      }
+  printf("part 3: accumulating chains, %d trials x 128 outputs (rows 0-7 x 16 columns), %d k-steps each, running C non-zero from the start\n", trials,
+         ACC_KSTEPS);
+  printf("  16x16x4 registers 0, 1 against two 4x4x4_4b chains: %zu of %zu outputs differ bitwise -> %s\n", differ, no,
+         differ == 0 ? "BIT-IDENTICAL" : "NOT bit-identical");
+  printf("  largest |difference| / sum of |terms|: 16x16x4 against long double %.2e, 4x4x4 against long double %.2e, the two shapes %.2e\n", worst16,
+         worst4, worst_pair);
+  return 0;
 }
 
 enum { NONE = 0, IND16 = 1, DEP16 = 2, IND4 = 3, DEP4 = 4, MIX = 5 };
@@ -135,6 +207,7 @@ Res report(int blocks, double* out, long long* ticks, int iters) {
 int main(int argc, char** argv) {
   const int blocks = argc > 1 ? atoi(argv[1]) : 256;
   const int iters = 400;
+  if (argc > 2) return accumulate_case();
   double *out, *dA, *dB;
   long long* ticks;
   unsigned long long* map;
@@ -208,5 +281,5 @@ int main(int argc, char** argv) {
          d16.tick_m / n, t4, t4d, t4mix);
   printf("gate (>= 140 ticks per chunk): 6 (t16 - t4) = %.0f, 6 t16 - 5 t4 = %.0f with t4 independent; %.0f and %.0f with t4 between two 16\n",
          6 * (t16 - t4), 6 * t16 - 5 * t4, 6 * (t16 - t4mix), 6 * t16 - 5 * t4mix);
-  return 0;
+  return accumulate_case();
 }
