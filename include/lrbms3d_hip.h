@@ -350,6 +350,36 @@ int lrbms3_reduced_implicit_euler_src(lrbms3_ctx* ctx, int32_t Q, int32_t N, int
                                       const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
                                       double* work, double* U, double rtol, int32_t max_iter, double* info, void* stream);
 
+/* -- batched reduced trajectories: nmu <= 64 parameters of the parabolic reduced model in one call ----------------
+ *   lrbms3_reduced_implicit_euler_batch      column m of U [nt+1][S][N][nmu] (parameter fastest; U[0] input, [S][N][nmu]) is the
+ *                                   trajectory of lrbms3_reduced_implicit_euler at theta[m]: per step and per group of <= 16 columns
+ *                                   the PCG of lrbms3_reduced_solve_batch on the step operator M_red + dt sum_q theta_qm B_sys_q
+ *                                   (the mass is one more block of the panel matvec's self slot; no combined copy per column is
+ *                                   written), started at u_k and iterating in place in U[k+1]; up to four groups on four streams.
+ *                                   theta [nmu][Q] host; B_sys, M_red, rhs_red [S][N] as for the single export.  One preconditioner
+ *                                   per call, built at the call-mean theta: inverse diagonal blocks (identity on zero-padded basis
+ *                                   columns, which stay exactly 0) and a coarse level on the first local basis vectors; if that
+ *                                   coarse matrix is not positive definite the call runs block-Jacobi alone.  A preconditioner
+ *                                   installed with lrbms3_reduced_precond_use belongs to A: it is neither read nor replaced.
+ *                                   max_iter caps ONE step: on a miss LRBMS_E_NOT_CONVERGED, the iterate in U[step+1], later slabs
+ *                                   untouched.  info (host, may be NULL): {sum over the steps of the slowest group's iterations,
+ *                                   worst final residual relative to |M_red u_k + dt b_m|}.  A column with zero data stays exactly 0.
+ *                                   Limits: N <= 32, nmu <= 64, Q <= 8, dt > 0, nt >= 1, S_ext == S; every violation and every null
+ *                                   pointer is LRBMS_E_INVALID before any launch.
+ *                                   work: lrbms3_reduced_implicit_euler_batch_work_size(N, nmu) doubles.
+ *   lrbms3_reduced_implicit_euler_batch_src  the same with b_m of step k = sum_j phi[m][k+1][j] rhs_red_K[j]: rhs_red_K [K][S][N],
+ *                                   phi [nmu][nt+1][K] on the DEVICE (row k: the time of step k), 1 <= K <= 64.  K = 1, phi = 1: the
+ *                                   bits of lrbms3_reduced_implicit_euler_batch.
+ * 2D: lrbms_reduced_implicit_euler_batch(_src). */
+int64_t lrbms3_reduced_implicit_euler_batch_work_size(lrbms3_ctx* ctx, int32_t N, int32_t nmu);
+int lrbms3_reduced_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nmu, const double* theta, double dt, int32_t nt,
+                                        const double* B_sys, const double* M_red, const double* rhs_red, double* work, double* U,
+                                        double rtol, int32_t max_iter, double* info, void* stream);
+int lrbms3_reduced_implicit_euler_batch_src(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta, double dt,
+                                            int32_t nt, const double* B_sys, const double* M_red, const double* rhs_red_K,
+                                            const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
+                                            void* stream);
+
 /* -- online enrichment ------------------------------------------------------------------------------------------------------ */
 /* Dirichlet correction blocks of the neighbourhood problems: on every coupling face of subdomain s, for the own side element,
  * the Dirichlet-face block (inside coefficient) minus the inner-face own / own block already contained in A_diag (mesh tables

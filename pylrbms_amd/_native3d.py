@@ -73,6 +73,12 @@ SIGNATURES3 = {
                                                      c_i32, _P_DBL, c_vp]),
     'lrbms3_reduced_implicit_euler_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                          c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    # batched reduced trajectories
+    'lrbms3_reduced_implicit_euler_batch_work_size': (c_i64, [c_vp, c_i32, c_i32]),
+    'lrbms3_reduced_implicit_euler_batch': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                           c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms3_reduced_implicit_euler_batch_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp,
+                                                               c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
     # online enrichment
     'lrbms3_assemble_dirichlet_correction': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms3_local_correction_work_size': (c_i64, [c_vp, c_i32]),
@@ -570,6 +576,59 @@ class Native3DContext(_native.ContextBase):
                                                         c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), info,
                                                         self._stream())
         self._check(rc, 'lrbms3_reduced_implicit_euler_src')
+        return U, (int(info[0]), float(info[1]))
+
+    # ------------------------------------------------------------------ batched reduced trajectories
+    def _batch_trajectory_buffers(self, name, N, nmu, nt, U0, work):
+        """work and U [nt + 1, S, N, nmu] (U[0] = U0: [S, N] for every column, or [S, N, nmu]; default zero) of the batched
+        reduced implicit Euler exports."""
+        need = int(self.lib.lrbms3_reduced_implicit_euler_batch_work_size(self.handle, N, nmu))
+        if need < 0:
+            raise NativeError('{}: bad N / nmu'.format(name))
+        if work is None:
+            work = self.empty(need)
+        if work.numel() < need:
+            raise NativeError('{}: work too small'.format(name))
+        U = self.zeros(max(int(nt), 0) + 1, self.S, N, nmu)
+        if U0 is not None:
+            U[0] = U0.reshape(self.S, N, -1)          # [S, N, 1] broadcasts over the columns
+        return work, U
+
+    def reduced_implicit_euler_batch(self, Q, thetas, dt, nt, B_sys, M_red, rhs_red, U0=None, rtol=1e-12, max_iter=20000, work=None):
+        """nmu <= 64 reduced trajectories in one call: thetas [nmu, Q] -> U [nt + 1, S, N, nmu] (parameter fastest), (iterations
+        of the slowest group summed over the steps, worst final relative residual); column m is what ``reduced_implicit_euler``
+        returns at thetas[m].  ``max_iter`` caps the iterations of one step."""
+        N, S = int(rhs_red.shape[1]), self.S
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, Q)
+        work, U = self._batch_trajectory_buffers('reduced_implicit_euler_batch', N, nmu, nt, U0, work)
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_reduced_implicit_euler_batch(self.handle, Q, N, nmu, th.ctypes.data_as(_P_DBL), float(dt), int(nt),
+                                                          self._ptr(B_sys, (Q, S, 7, N, N), 'B_sys'), self._ptr(M_red, (S, N, N), 'M_red'),
+                                                          self._ptr(rhs_red, (S, N), 'rhs_red'), c_vp(work.data_ptr()),
+                                                          c_vp(U.data_ptr()), float(rtol), int(max_iter), info, self._stream())
+        self._check(rc, 'lrbms3_reduced_implicit_euler_batch')
+        return U, (int(info[0]), float(info[1]))
+
+    def reduced_implicit_euler_batch_src(self, Q, thetas, dt, nt, B_sys, M_red, rhs_red_K, phi, U0=None, rtol=1e-12, max_iter=20000,
+                                         work=None):
+        """``reduced_implicit_euler_batch`` with the step right-hand side M_red u_k + dt sum_j phi[m, k + 1, j] rhs_red_K[j] in
+        column m; phi [nmu, nt + 1, K] (host or device)."""
+        K, N, S = int(rhs_red_K.shape[0]), int(rhs_red_K.shape[2]), self.S
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, Q)
+        ph = self._dev2(phi, (nmu, max(int(nt), 0) + 1, K), 'phi')
+        work, U = self._batch_trajectory_buffers('reduced_implicit_euler_batch_src', N, nmu, nt, U0, work)
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_reduced_implicit_euler_batch_src(self.handle, Q, N, K, nmu, th.ctypes.data_as(_P_DBL), float(dt), int(nt),
+                                                              self._ptr(B_sys, (Q, S, 7, N, N), 'B_sys'),
+                                                              self._ptr(M_red, (S, N, N), 'M_red'),
+                                                              self._ptr(rhs_red_K, (K, S, N), 'rhs_red_K'), c_vp(ph.data_ptr()),
+                                                              c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), info,
+                                                              self._stream())
+        self._check(rc, 'lrbms3_reduced_implicit_euler_batch_src')
         return U, (int(info[0]), float(info[1]))
 
     # ------------------------------------------------------------------ online enrichment (DESIGN.md 9.11)

@@ -2316,6 +2316,71 @@ __global__ __launch_bounds__(512) void k3b_init_src(int N, int nmu, int ldx, int
   }
 }
 
+// dst [rows][nm] = this group's columns src[row ldx + m] of a panel with leading dimension ldx
+__global__ __launch_bounds__(256) void k3b_gather(long rows, int nm, int ldx, const double* __restrict__ src, double* __restrict__ dst) {
+  const long total = rows * nm;
+  for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < total; k += (long)gridDim.x * 256) dst[k] = src[(k / nm) * ldx + k % nm];
+}
+
+// Step start of the batched reduced implicit Euler (lrbms3_reduced_implicit_euler_batch(_src)) for one group: given
+// y = (M + dt A_m) u_k from the MASS matvec, f_m = M_red u_k + dt b_m in the operation order of k3p_red_rhs(_src) -- the mass row
+// sum first, then + dt * b, b_m = rhs_K[s][i] (K == 0) or sum_j phi[m][j] rhs_K[j][s][i] spelled out with fma from the first
+// product (phi: this group's rows of step k + 1, row stride ldphi) -- and the CG start of k3b_init from x = u_k: r = f - y,
+// z = Dinv r, p = 0, x written into the group's columns of U[k+1]; partials of r.z, r.r and |f_m|^2.
+__global__ __launch_bounds__(512) void k3b_step_init(int N, int nmu, int ldx, double dt, const double* __restrict__ Mred,
+                                                     const double* __restrict__ uk, int K, long SN, long ldphi,
+                                                     const double* __restrict__ phi, const double* __restrict__ rhs_K,
+                                                     const double* __restrict__ y, const double* __restrict__ Dinv,
+                                                     double* __restrict__ x, double* __restrict__ r, double* __restrict__ z,
+                                                     double* __restrict__ p, double* __restrict__ prz, double* __restrict__ prr,
+                                                     double* __restrict__ pff) {
+  extern __shared__ double lds[];      // [N][16] u_k + [N][16] residual + [32][16] products
+  const int s = blockIdx.x, tid = threadIdx.x, i = tid >> 4, m = tid & 15;
+  double* us = lds;
+  double* rs = lds + N * 16;
+  for (int k = tid; k < N * 16; k += 512) {
+    const int kk = k >> 4, mm = k & 15;
+    us[k] = mm < nmu ? uk[((long)s * N + kk) * ldx + mm] : 0.0;
+  }
+  __syncthreads();
+  double fi = 0.0, ri = 0.0, zi = 0.0;
+  const bool on = i < N && m < nmu;
+  const long d = ((long)s * N + i) * nmu + m;
+  if (on) {
+    const double* M = Mred + ((long)s * N + i) * N;
+    double acc = 0.0;
+    for (int j = 0; j < N; ++j) acc += M[j] * us[j * 16 + m];
+    const double* src = rhs_K + (long)s * N + i;
+    double bs = src[0];
+    if (K > 0) {
+      const double* ph = phi + (long)m * ldphi;
+      bs = ph[0] * src[0];
+      for (int j = 1; j < K; ++j) bs = __fma_rn(ph[j], src[(long)j * SN], bs);
+    }
+    fi = acc + dt * bs;
+    ri = fi - y[d];
+  }
+  if (i < N) rs[i * 16 + m] = ri;
+  __syncthreads();
+  if (on) {
+    const double* D = Dinv + ((long)s * N + i) * N;
+    for (int j = 0; j < N; ++j) zi += D[j] * rs[j * 16 + m];
+    x[((long)s * N + i) * ldx + m] = us[i * 16 + m];
+    r[d] = ri; z[d] = zi; p[d] = 0.0;
+  }
+  double* pr = lds + 2 * N * 16;
+  for (int pass = 0; pass < 3; ++pass) {
+    __syncthreads();
+    if (i < 32) pr[i * 16 + m] = on ? (pass == 0 ? ri * zi : pass == 1 ? ri * ri : fi * fi) : 0.0;
+    __syncthreads();
+    if (tid < 16) {
+      double a = 0.0;
+      for (int k = 0; k < N; ++k) a += pr[k * 16 + tid];
+      (pass == 0 ? prz : pass == 1 ? prr : pff)[(long)s * 16 + tid] = a;
+    }
+  }
+}
+
 // Coarse level of the batched reduced solve (nullptr members: block-Jacobi alone): y0 [S][16] = A0^-1 r0 of the last residual,
 // prc_* [S][16] its contributions r0 . y0 to r.z -- summed with the fine partials wherever r.z is needed.
 struct CoarseB {
@@ -2354,12 +2419,16 @@ __device__ inline double sum_partials16(const double* __restrict__ part, int S, 
 // + 1 of the wave's 8-column band: one 16-byte load for two k-steps), the B operand the direction of the slot from the LDS with the
 // parameter weight theta_qm folded in (a lane owns ONE parameter, l & 15).  Four waves, wave w owns the column band [8 w, 8 w + 8) of
 // every block, so the A_mu strips are read exactly once; the waves' tiles meet in the LDS in a fixed order.
-template <int RT>
+// MASS (lrbms3_reduced_implicit_euler_batch): the step operator M_red + dt A_m -- M_red [S][N][N] is one more A-operand block on
+// the self slot with coefficient 1, dt is folded into th by the host; no augmented copy of B is written anywhere.
+template <bool MASS> struct MassOp3 {};
+template <> struct MassOp3<true> { const double* M; };
+template <int RT, bool MASS = false>
 __global__ __launch_bounds__(256) void k3b_matvec_mfma(T3 t, int Q, int N, int nmu, int first, TB th, const double* __restrict__ B,
                                                        const double* __restrict__ z, const double* __restrict__ p_old,
                                                        double* __restrict__ p_new, double* __restrict__ Ap,
                                                        const double* __restrict__ prz_new, const double* __restrict__ prz_old,
-                                                       double* __restrict__ ppap, CoarseB cl) {
+                                                       double* __restrict__ ppap, CoarseB cl, MassOp3<MASS> mass = MassOp3<MASS>()) {
   extern __shared__ double lds[];      // [7][32][16] direction (rows >= N zero) + [4][RT][256] partial tiles + [32][16] sums
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4, S = t.S;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2423,6 +2492,23 @@ __global__ __launch_bounds__(256) void k3b_matvec_mfma(T3 t, int Q, int N, int n
         }
       }
     }
+    if constexpr (MASS) {                            // + M_red[s] p_self: the same strip loads and MFMA chain, coefficient 1
+      const double b0 = dir[(3 * 32 + c0) * 16 + li], b1 = dir[(3 * 32 + c0 + 1) * 16 + li];
+      const double* blk = mass.M + (long)s * N * N;
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        const int row = rt * 16 + li < N ? rt * 16 + li : N - 1;
+        double a0, a1;
+        if (even) {
+          const double2 v = *reinterpret_cast<const double2*>(blk + row * N + cpair);
+          a0 = v.x; a1 = v.y;
+        } else {
+          a0 = blk[row * N + ca]; a1 = blk[row * N + cb];
+        }
+        acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[rt], 0, 0, 0);
+        acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[rt], 0, 0, 0);
+      }
+    }
   }
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt)
@@ -2455,10 +2541,12 @@ __global__ __launch_bounds__(256) void k3b_matvec_mfma(T3 t, int Q, int N, int n
 
 // direction + matvec: p_new = z + beta_m p_old on the neighbourhood (own part stored), Ap = sum_q theta_qm sum_slot B_q p_new;
 // beta_m = r.z (prz_new) / previous r.z (prz_old)
+template <bool MASS = false>
 __global__ __launch_bounds__(512) void k3b_matvec(T3 t, int Q, int N, int nmu, int first, TB th, const double* __restrict__ B,
                                                   const double* __restrict__ z, const double* __restrict__ p_old,
                                                   double* __restrict__ p_new, double* __restrict__ Ap, const double* __restrict__ prz_new,
-                                                  const double* __restrict__ prz_old, double* __restrict__ ppap, CoarseB cl) {
+                                                  const double* __restrict__ prz_old, double* __restrict__ ppap, CoarseB cl,
+                                                  MassOp3<MASS> mass = MassOp3<MASS>()) {
   extern __shared__ double lds[];      // [7][N][16] direction + [32][16] products
   const int s = blockIdx.x, tid = threadIdx.x, i = tid >> 4, m = tid & 15, S = t.S;
   double bm = 0.0;                     // (512 % 16 == 0: a thread fills entries of its own parameter only)
@@ -2497,6 +2585,13 @@ __global__ __launch_bounds__(512) void k3b_matvec(T3 t, int Q, int N, int nmu, i
         for (int j = 0; j < N; ++j) aq += row[j] * ps[j * 16];
       }
       acc += th.v[m][q] * aq;
+    }
+    if constexpr (MASS) {
+      const double* row = mass.M + ((long)s * N + i) * N;
+      const double* ps = lds + 3 * N * 16 + m;
+      double am = 0.0;
+      for (int j = 0; j < N; ++j) am += row[j] * ps[j * 16];
+      acc += am;
     }
     Ap[((long)s * N + i) * nmu + m] = acc;
   }
@@ -3577,7 +3672,128 @@ int64_t lrbms3_reduced_solve_batch_work_size(lrbms3_ctx* ctx, int32_t N, int32_t
 
 namespace {
 
-// The group / iteration driver shared by lrbms3_reduced_solve_batch and lrbms3_reduced_solve_batch_src: K == 0 broadcasts
+// One group of <= 16 columns of the batched reduced solvers: its slice of the work array, its theta table, its stream and state.
+struct RbGroup {
+  int nm, m0;
+  TB th;
+  double *Amu, *Dinv, *r, *z, *po, *pn, *Ap, *prz, *ppap, *prr, *scal, *y0, *prc;
+  hipStream_t st;
+  bool done;
+  double rel;
+  int it, last_it;
+};
+
+// the vectors, partials and scalars of a group from w on (5 S N 16 + 4 S 16 + 96 + 3 S 16 doubles)
+void rb_group_vectors(RbGroup& G, double* w, long S, int N) {
+  const long nv = S * N * 16;
+  G.r = w;
+  G.z = G.r + nv;
+  G.po = G.z + nv;
+  G.pn = G.po + nv;
+  G.Ap = G.pn + nv;
+  G.prz = G.Ap + nv;                // [2][S][16]: r.z partials of the last two updates (beta needs both)
+  G.ppap = G.prz + 2 * S * 16;
+  G.prr = G.ppap + S * 16;
+  G.scal = G.prr + S * 16;          // [5][16]: only the residual norms ([3], [4]) are reduced by a kernel of their own
+  G.y0 = G.scal + 5 * 16 + 16;      // coarse level: correction and its r.z contributions [2][S][16]
+  G.prc = G.y0 + S * 16;
+}
+
+// What the iteration loop applies: sum_q th_qm B_q on the 7 slots, plus M_red on the self slot when it is given (the step operator
+// of the implicit Euler, dt folded into th); A0inv: the coarse inverse [S][S] or nullptr; u: the panel the solve iterates in, ldx = nmu.
+struct RbOp {
+  int Q, N, nmu;
+  const double *B_sys, *M_red, *A0inv;
+  double* u;
+};
+
+// The iteration loop of the batched reduced solvers from the state the start kernels left (G.it = 0, G.done = false): matvec /
+// update / coarse apply per group, launches interleaved iteration by iteration over the groups' streams, a look at the residuals
+// after first_block and then after every check iterations.  A group leaves at rel <= rtol, at max_iter (honoured exactly) or on a
+// NaN (nan set).  The residual norms sit in scal [3], their references in scal [4].
+int red_batch_iterate(lrbms3_ctx* ctx, const RbOp& op, RbGroup* g, int ng, int first_block, int check, double rtol, int max_iter,
+                      bool& nan) {
+  const T3& t = ctx->t;
+  const long S = t.S;
+  const int Q = op.Q, N = op.N, nmu = op.nmu;
+  const double *B_sys = op.B_sys, *A0inv = op.A0inv;
+  double* u = op.u;
+  const size_t lds_mv = sizeof(double) * (7 * N * 16 + 32 * 16), lds_up = sizeof(double) * (N * 16 + 32 * 16);
+  const size_t lds_mm = sizeof(double) * (7 * 32 * 16 + 4 * (N <= 16 ? 1 : 2) * 256 + 32 * 16);
+  const bool mfma_mv = ctx->opt_solve_valu == 0;      // LRBMS3_OPT_SOLVE_VALU: the VALU panel matvec
+  const MassOp3<true> mo{op.M_red};
+  bool all_done = false;
+  int block = first_block;
+  while (!all_done) {
+    for (int c = 0; c < block; ++c)
+      for (int k = 0; k < ng; ++k) {
+        RbGroup& G = g[k];
+        if (G.done || G.it >= max_iter) continue;
+        const int it = G.it;
+        double* rz_cur = G.prz + (it & 1) * S * 16;          // written by the previous update (or the start kernel)
+        double* rz_nxt = G.prz + ((it + 1) & 1) * S * 16;    // holds the r.z of the update before that until this update overwrites it
+        double* rc_cur = G.prc + (it & 1) * S * 16;
+        double* rc_nxt = G.prc + ((it + 1) & 1) * S * 16;
+        const CoarseB cb{A0inv ? G.y0 : nullptr, rc_cur, rc_nxt};
+        if (op.M_red) {
+          KScope ks(ctx, mfma_mv ? "k3b_matvec_mfma<mass>" : "k3b_matvec<mass>", G.st);
+          if (mfma_mv && N <= 16)
+            hipLaunchKernelGGL((k3b_matvec_mfma<1, true>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys,
+                               G.z, G.po, G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb, mo);
+          else if (mfma_mv)
+            hipLaunchKernelGGL((k3b_matvec_mfma<2, true>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys,
+                               G.z, G.po, G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb, mo);
+          else
+            hipLaunchKernelGGL(k3b_matvec<true>, dim3(S), dim3(512), lds_mv, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
+                               G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb, mo);
+        } else {
+          KScope ks(ctx, mfma_mv ? "k3b_matvec_mfma" : "k3b_matvec", G.st);
+          if (mfma_mv && N <= 16)
+            hipLaunchKernelGGL(k3b_matvec_mfma<1>, dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
+                               G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb);
+          else if (mfma_mv)
+            hipLaunchKernelGGL(k3b_matvec_mfma<2>, dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
+                               G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb);
+          else
+            hipLaunchKernelGGL(k3b_matvec<false>, dim3(S), dim3(512), lds_mv, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
+                               G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb);
+        }
+        hipLaunchKernelGGL(k3b_update, dim3(S), dim3(512), lds_up, G.st, N, G.nm, nmu, G.Dinv, G.pn, G.Ap, u + G.m0, G.r, G.z, (int)S,
+                           rz_cur, A0inv ? rc_cur : nullptr, G.ppap, rz_nxt, G.prr);
+        if (A0inv)    // the coarse correction of the new residual: read by the next matvec (direction) and by the next update (r.z)
+          hipLaunchKernelGGL(k3b_coarse_apply, dim3((unsigned)((S + 15) / 16)), dim3(1024), 0, G.st, (int)S, N, G.nm, A0inv, G.r, G.y0,
+                             rc_nxt);
+        std::swap(G.po, G.pn);
+        ++G.it;
+      }
+    block = check;
+    double rr[4][32];
+    for (int k = 0; k < ng; ++k) {
+      RbGroup& G = g[k];
+      if (G.done) continue;
+      hipLaunchKernelGGL(k3b_reduce, dim3(1), dim3(256), 0, G.st, (int)S, G.nm, G.prr, G.scal + 48);
+      LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(rr[k], G.scal + 48, sizeof(double) * 32, hipMemcpyDeviceToHost, G.st));   // [3] residuals, [4] |b|^2
+    }
+    LRBMS_LAUNCH_CHECK(ctx);
+    all_done = true;
+    for (int k = 0; k < ng; ++k) {
+      RbGroup& G = g[k];
+      if (G.done) continue;
+      LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(G.st));
+      G.rel = 0.0;
+      for (int m = 0; m < G.nm; ++m) {
+        const double bbm = rr[k][16 + m], rm = bbm > 0.0 ? sqrt(rr[k][m] / bbm) : 0.0;
+        if (!(rm == rm)) nan = true;
+        G.rel = rm > G.rel ? rm : G.rel;
+      }
+      if (G.rel <= rtol || G.it >= max_iter || nan) G.done = true;
+      if (!G.done) all_done = false;
+    }
+  }
+  return LRBMS_OK;
+}
+
+// The group driver shared by lrbms3_reduced_solve_batch and lrbms3_reduced_solve_batch_src: K == 0 broadcasts
 // rhs_red [S][N] to every column (k3b_init); K >= 1 gives column m the right-hand side sum_j phi[m][j] rhs_red[j] of
 // rhs_red [K][S][N] (k3b_init_src, phi [nmu][K] on the device).  Everything behind the start kernel is the same launch sequence.
 int red_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nmu, const double* theta, const double* B_sys,
@@ -3590,39 +3806,20 @@ int red_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nm
   // chip at little cost to each other.  Launches are interleaved iteration by iteration; residuals are looked at together.
   const int ng = (nmu + 15) / 16;
   const long gsize = reduced_batch_group_size(S, N);
-  struct Group {
-    int nm, m0;
-    TB th;
-    double *Amu, *Dinv, *r, *z, *po, *pn, *Ap, *prz, *ppap, *prr, *scal, *y0, *prc;
-    hipStream_t st;
-    bool done;
-    double rel;
-    int it;
-  } g[4];
+  RbGroup g[4];
   const double* A0inv = ctx->user_pc_N == N ? ctx->user_pc : nullptr;
   for (int k = 0; k < ng; ++k) {
-    Group& G = g[k];
+    RbGroup& G = g[k];
     G.m0 = 16 * k;
     G.nm = nmu - G.m0 < 16 ? nmu - G.m0 : 16;
     G.st = k == 0 ? st : ctx->aux[k - 1];
     G.done = false;
     G.rel = 0.0;
-    G.it = 0;
-    const long nv = S * N * 16;
+    G.it = G.last_it = 0;
     double* w = work + k * gsize;
     G.Amu = w;                        // blocks at the group-mean theta: only its diagonal blocks are used (preconditioner)
     G.Dinv = G.Amu + per_q;
-    G.r = G.Dinv + S * N * N;
-    G.z = G.r + nv;
-    G.po = G.z + nv;
-    G.pn = G.po + nv;
-    G.Ap = G.pn + nv;
-    G.prz = G.Ap + nv;                // [2][S][16]: r.z partials of the last two updates (beta needs both)
-    G.ppap = G.prz + 2 * S * 16;
-    G.prr = G.ppap + S * 16;
-    G.scal = G.prr + S * 16;          // [5][16]: only the residual norms ([3], [4]) are reduced by a kernel of their own
-    G.y0 = G.scal + 5 * 16 + 16;      // coarse level (lrbms3_reduced_precond_use): correction and its r.z contributions [2][S][16]
-    G.prc = G.y0 + S * 16;
+    rb_group_vectors(G, G.Dinv + S * N * N, S, N);
     G.th = TB{};
   }
   if (ng > 1) {
@@ -3630,7 +3827,7 @@ int red_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nm
     for (int k = 1; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(g[k].st, ctx->ev_fork, 0));
   }
   for (int k = 0; k < ng; ++k) {
-    Group& G = g[k];
+    RbGroup& G = g[k];
     QV mean{};
     for (int m = 0; m < G.nm; ++m)
       for (int q = 0; q < Q; ++q) {
@@ -3657,62 +3854,9 @@ int red_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nm
   LRBMS_LAUNCH_CHECK(ctx);
   if (info) info[0] = 0, info[1] = 0;
   const int check = A0inv ? 12 : 8;    // iterations between two looks at the residuals (a host synchronisation each)
-  const size_t lds_mv = sizeof(double) * (7 * N * 16 + 32 * 16), lds_up = sizeof(double) * (N * 16 + 32 * 16);
-  const size_t lds_mm = sizeof(double) * (7 * 32 * 16 + 4 * (N <= 16 ? 1 : 2) * 256 + 32 * 16);
-  const bool mfma_mv = ctx->opt_solve_valu == 0;      // LRBMS3_OPT_SOLVE_VALU: the VALU panel matvec
-  int rc = LRBMS_OK;
-  bool all_done = false;
-  while (!all_done) {
-    for (int c = 0; c < check; ++c)
-      for (int k = 0; k < ng; ++k) {
-        Group& G = g[k];
-        if (G.done || G.it >= max_iter) continue;
-        const int it = G.it;
-        double* rz_cur = G.prz + (it & 1) * S * 16;          // written by the previous update (or k3b_init)
-        double* rz_nxt = G.prz + ((it + 1) & 1) * S * 16;    // holds the r.z of the update before that until this update overwrites it
-        double* rc_cur = G.prc + (it & 1) * S * 16;
-        double* rc_nxt = G.prc + ((it + 1) & 1) * S * 16;
-        const CoarseB cb{A0inv ? G.y0 : nullptr, rc_cur, rc_nxt};
-        if (mfma_mv && N <= 16)
-          hipLaunchKernelGGL(k3b_matvec_mfma<1>, dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
-                             G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb);
-        else if (mfma_mv)
-          hipLaunchKernelGGL(k3b_matvec_mfma<2>, dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
-                             G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb);
-        else
-          hipLaunchKernelGGL(k3b_matvec, dim3(S), dim3(512), lds_mv, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po, G.pn,
-                             G.Ap, rz_cur, rz_nxt, G.ppap, cb);
-        hipLaunchKernelGGL(k3b_update, dim3(S), dim3(512), lds_up, G.st, N, G.nm, nmu, G.Dinv, G.pn, G.Ap, u + G.m0, G.r, G.z, (int)S,
-                           rz_cur, A0inv ? rc_cur : nullptr, G.ppap, rz_nxt, G.prr);
-        if (A0inv)    // the coarse correction of the new residual: read by the next matvec (direction) and by the next update (r.z)
-          hipLaunchKernelGGL(k3b_coarse_apply, dim3((unsigned)((S + 15) / 16)), dim3(1024), 0, G.st, (int)S, N, G.nm, A0inv, G.r, G.y0,
-                             rc_nxt);
-        std::swap(G.po, G.pn);
-        ++G.it;
-      }
-    double rr[4][32];
-    for (int k = 0; k < ng; ++k) {
-      Group& G = g[k];
-      if (G.done) continue;
-      hipLaunchKernelGGL(k3b_reduce, dim3(1), dim3(256), 0, G.st, (int)S, G.nm, G.prr, G.scal + 48);
-      LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(rr[k], G.scal + 48, sizeof(double) * 32, hipMemcpyDeviceToHost, G.st));   // [3] residuals, [4] |b|^2
-    }
-    LRBMS_LAUNCH_CHECK(ctx);
-    all_done = true;
-    for (int k = 0; k < ng; ++k) {
-      Group& G = g[k];
-      if (G.done) continue;
-      LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(G.st));
-      G.rel = 0.0;
-      for (int m = 0; m < G.nm; ++m) {
-        const double bbm = rr[k][16 + m], rm = bbm > 0.0 ? sqrt(rr[k][m] / bbm) : 0.0;
-        if (!(rm == rm)) rc = LRBMS_E_NOT_CONVERGED;
-        G.rel = rm > G.rel ? rm : G.rel;
-      }
-      if (G.rel <= rtol || G.it >= max_iter || rc != LRBMS_OK) G.done = true;
-      if (!G.done) all_done = false;
-    }
-  }
+  bool nan = false;
+  const RbOp op{Q, N, nmu, B_sys, nullptr, A0inv, u};
+  if (int irc = red_batch_iterate(ctx, op, g, ng, check, check, rtol, max_iter, nan)) return irc;
   if (ng > 1)
     for (int k = 1; k < ng; ++k) {
       LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[k - 1], g[k].st));
@@ -3725,7 +3869,7 @@ int red_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nm
     rel = g[k].rel > rel ? g[k].rel : rel;
   }
   if (info) info[0] = it, info[1] = rel;
-  if (rc != LRBMS_OK) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": NaN residual");
+  if (nan) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": NaN residual");
   if (rel > rtol) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": not converged");
   return LRBMS_OK;
 }
@@ -4564,6 +4708,196 @@ int lrbms3_reduced_implicit_euler_src(lrbms3_ctx* ctx, int32_t Q, int32_t N, int
                          hipLaunchKernelGGL(k3p_red_rhs_src, dim3(t.S), dim3(64), 0, st, N, dt, M_red, uk, K, (long)t.S * N,
                                             phi + (long)(step + 1) * K, rhs_red_K, Ku, rhs, part);
                        });
+}
+
+}  // extern "C"
+
+namespace {
+
+// doubles ahead of the groups in the work array of the batched trajectories: the step operator at the call-mean theta, its inverse
+// diagonal blocks, the coarse matrix and its inverse, the info word of the factorisation
+long red_euler_batch_shared_size(long S, int N) { return S * 7 * N * N + S * N * N + 2 * S * S + 2; }
+// a group without blocks of its own (reduced_batch_group_size carries a group-mean operator and its block inverse)
+long red_euler_batch_group_size(long S, int N) { return reduced_batch_group_size(S, N) - S * 7 * N * N - S * N * N; }
+
+// The driver of lrbms3_reduced_implicit_euler_batch(_src): a loop over the steps around red_batch_iterate.  K == 0: rhs [S][N] for
+// every column and step; K >= 1: rhs [K][S][N], phi_dev [nmu][nt+1][K] (device), step k takes row k + 1.
+int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nmu, const double* theta, double dt, int nt,
+                        const double* B_sys, const double* M_red, const double* rhs, int K, const double* phi_dev, double* work,
+                        double* U, double rtol, int max_iter, double* info, hipStream_t st) {
+  const T3& t = ctx->t;
+  const long S = t.S, per_q = S * 7 * N * N, rows = S * N;
+  const int ng = (nmu + 15) / 16;
+  if (info) info[0] = 0, info[1] = 0;
+  // ---- the preconditioner of the call, on the caller's stream ahead of the fork, shared by all groups: inverse diagonal blocks
+  // of M_red + dt sum_q mean(theta)_q B_q (zero-padded basis columns keep a zero diagonal: the identity there, they stay exactly 0)
+  // and the coarse level on the first local basis vectors of that operator.  A preconditioner installed with
+  // lrbms3_reduced_precond_use belongs to A and is neither read nor replaced.
+  double* Amu = work;
+  double* Dinv = Amu + per_q;
+  double* A0 = Dinv + S * N * N;
+  double* Id = A0 + S * S;
+  rocblas_int* pinfo = (rocblas_int*)(Id + S * S);
+  double* gwork = Id + S * S + 2;
+  QV mean{}, one{};
+  for (int m = 0; m < nmu; ++m)
+    for (int q = 0; q < Q; ++q) mean.v[q] += theta[m * Q + q] / nmu;
+  for (int q = 0; q < Q; ++q) mean.v[q] *= dt;
+  one.v[0] = 1.0;
+  if (!ctx->blas) {
+    rocblas_handle h = nullptr;
+    if (rocblas_create_handle(&h) != rocblas_status_success) return lrbms_fail(ctx, LRBMS_E_HIP, "rocblas_create_handle failed");
+    ctx->blas = h;
+  }
+  rocblas_handle h = (rocblas_handle)ctx->blas;
+  if (rocblas_set_stream(h, st) != rocblas_status_success) return lrbms_fail(ctx, LRBMS_E_HIP, "rocblas_set_stream failed");
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, mean, B_sys, Amu);
+  hipLaunchKernelGGL(k3p_red_add_mass, dim3((unsigned)((S * N * N + 255) / 256)), dim3(256), 0, st, S * N * N, N, M_red, Amu);
+  hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, Amu, Dinv);
+  LRBMS_HIP_CHECK(ctx, hipMemsetAsync(A0, 0, sizeof(double) * 2 * S * S, st));
+  hipLaunchKernelGGL(k3r_coarse_fill, dim3((unsigned)((S * 7 + 255) / 256)), dim3(256), 0, st, t, 1, N, one, Amu, A0, Id);
+  LRBMS_LAUNCH_CHECK(ctx);
+  if (rocsolver_dpotrf(h, rocblas_fill_lower, (rocblas_int)S, A0, (rocblas_int)S, pinfo) != rocblas_status_success)
+    return lrbms_fail(ctx, LRBMS_E_HIP, "rocsolver_dpotrf failed");
+  rocblas_int hinfo = 0;
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(&hinfo, pinfo, sizeof(rocblas_int), hipMemcpyDeviceToHost, st));
+  LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const double* A0inv = nullptr;       // not positive definite (a zeroed first basis vector): block-Jacobi alone
+  if (hinfo == 0) {
+    if (rocsolver_dpotrs(h, rocblas_fill_lower, (rocblas_int)S, (rocblas_int)S, A0, (rocblas_int)S, Id, (rocblas_int)S) !=
+        rocblas_status_success)
+      return lrbms_fail(ctx, LRBMS_E_HIP, "rocsolver_dpotrs failed");
+    A0inv = Id;
+  }
+  RbGroup g[4];
+  const long gsize = red_euler_batch_group_size(S, N);
+  for (int k = 0; k < ng; ++k) {
+    RbGroup& G = g[k];
+    G.m0 = 16 * k;
+    G.nm = nmu - G.m0 < 16 ? nmu - G.m0 : 16;
+    G.st = k == 0 ? st : ctx->aux[k - 1];
+    G.done = false;
+    G.rel = 0.0;
+    G.it = G.last_it = 0;
+    G.Amu = Amu;
+    G.Dinv = Dinv;
+    rb_group_vectors(G, gwork + k * gsize, S, N);
+    G.th = TB{};
+    for (int m = 0; m < G.nm; ++m)
+      for (int q = 0; q < Q; ++q) G.th.v[m][q] = dt * theta[(G.m0 + m) * Q + q];      // dt folded into the table
+  }
+  if (ng > 1) {
+    LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
+    for (int k = 1; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(g[k].st, ctx->ev_fork, 0));
+  }
+  for (int k = 0; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipMemsetAsync(g[k].scal, 0, sizeof(double) * 80, g[k].st));
+  const int check = A0inv ? 12 : 8;
+  const size_t lds_mv = sizeof(double) * (7 * N * 16 + 32 * 16), lds_mm = sizeof(double) * (7 * 32 * 16 + 4 * (N <= 16 ? 1 : 2) * 256 + 32 * 16);
+  const size_t lds_si = sizeof(double) * (2 * N * 16 + 32 * 16);
+  const bool mfma_mv = ctx->opt_solve_valu == 0;
+  const MassOp3<true> mo{M_red};
+  const CoarseB none{nullptr, nullptr, nullptr};
+  bool nan = false, capped = false;
+  long total_it = 0;
+  double worst = 0.0;
+  int rc = LRBMS_OK;
+  for (int step = 0; step < nt && rc == LRBMS_OK && !nan && !capped; ++step) {
+    const double* uk = U + (long)step * rows * nmu;
+    double* un = U + (long)(step + 1) * rows * nmu;
+    // ---- step start of every group, no look at the host: y = (M + dt A_m) u_k by the MASS matvec (first = 1, direction u_k
+    // gathered into the group's z, no coarse correction), then k3b_step_init
+    for (int k = 0; k < ng; ++k) {
+      RbGroup& G = g[k];
+      const long vec = rows * G.nm;
+      hipLaunchKernelGGL(k3b_gather, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, G.st, rows, G.nm,
+                         nmu, uk + G.m0, G.z);
+      if (mfma_mv && N <= 16)
+        hipLaunchKernelGGL((k3b_matvec_mfma<1, true>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, 1, G.th, B_sys, G.z, G.po, G.pn, G.Ap,
+                           G.prz, G.prz, G.ppap, none, mo);
+      else if (mfma_mv)
+        hipLaunchKernelGGL((k3b_matvec_mfma<2, true>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, 1, G.th, B_sys, G.z, G.po, G.pn, G.Ap,
+                           G.prz, G.prz, G.ppap, none, mo);
+      else
+        hipLaunchKernelGGL(k3b_matvec<true>, dim3(S), dim3(512), lds_mv, G.st, t, Q, N, G.nm, 1, G.th, B_sys, G.z, G.po, G.pn, G.Ap, G.prz,
+                           G.prz, G.ppap, none, mo);
+      hipLaunchKernelGGL(k3b_step_init, dim3(S), dim3(512), lds_si, G.st, N, G.nm, nmu, dt, M_red, uk + G.m0, K, rows, (long)(nt + 1) * K,
+                         K ? phi_dev + ((long)G.m0 * (nt + 1) + step + 1) * K : nullptr, rhs, G.Ap, Dinv, un + G.m0, G.r, G.z, G.po,
+                         G.prz, G.prr, G.ppap);
+      if (A0inv)
+        hipLaunchKernelGGL(k3b_coarse_apply, dim3((unsigned)((S + 15) / 16)), dim3(1024), 0, G.st, (int)S, N, G.nm, A0inv, G.r, G.y0, G.prc);
+      hipLaunchKernelGGL(k3b_reduce, dim3(1), dim3(256), 0, G.st, (int)S, G.nm, G.ppap, G.scal + 64);      // |f_m|^2: the step's reference
+      G.it = 0;
+      G.done = false;
+    }
+    LRBMS_LAUNCH_CHECK(ctx);
+    // the first block goes out with the start kernels, a little short of what the previous step took
+    int block = check;
+    for (int k = 0; k < ng; ++k) {
+      const int guess = (int)(0.8 * g[k].last_it);
+      if (guess > block) block = guess;
+    }
+    const RbOp op{Q, N, nmu, B_sys, M_red, A0inv, un};
+    rc = red_batch_iterate(ctx, op, g, ng, block, check, rtol, max_iter, nan);
+    if (rc != LRBMS_OK) break;
+    int it = 0;
+    for (int k = 0; k < ng; ++k) {
+      RbGroup& G = g[k];
+      G.last_it = G.it;
+      it = G.it > it ? G.it : it;
+      worst = G.rel > worst ? G.rel : worst;
+      if (G.rel > rtol) capped = true;
+    }
+    total_it += it;                    // the iterations of the slowest group, summed over the steps
+  }
+  if (rc != LRBMS_OK) {                // a HIP error between the fork and the join: drain the groups' streams before leaving
+    for (int k = 0; k < ng; ++k) (void)hipStreamSynchronize(g[k].st);
+    return rc;
+  }
+  for (int k = 1; k < ng; ++k) {
+    LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[k - 1], g[k].st));
+    LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0));
+  }
+  if (info) info[0] = (double)total_it, info[1] = worst;
+  if (nan) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": NaN residual");
+  if (capped) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": not converged");
+  return LRBMS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t lrbms3_reduced_implicit_euler_batch_work_size(lrbms3_ctx* ctx, int32_t N, int32_t nmu) {
+  if (!ctx || !ctx->has_mesh || N < 1 || nmu < 1) return -1;
+  const long S = ctx->t.S;
+  return red_euler_batch_shared_size(S, N) + (int64_t)((nmu + 15) / 16) * red_euler_batch_group_size(S, N);
+}
+
+int lrbms3_reduced_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t nmu, const double* theta, double dt, int32_t nt,
+                                        const double* B_sys, const double* M_red, const double* rhs_red, double* work, double* U,
+                                        double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (ctx->t.S_ext != ctx->t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 32 || nmu < 1 || nmu > 64 || !theta || !B_sys || !M_red || !rhs_red || !work || !U)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch: needs N <= 32 and nmu <= 64");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch: dt > 0 and nt >= 1 required");
+  return red_euler_batch_run(ctx, "reduced_implicit_euler_batch", Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red, 0, nullptr, work, U,
+                             rtol, max_iter, info, (hipStream_t)stream);
+}
+
+int lrbms3_reduced_implicit_euler_batch_src(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta, double dt,
+                                            int32_t nt, const double* B_sys, const double* M_red, const double* rhs_red_K,
+                                            const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
+                                            void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (ctx->t.S_ext != ctx->t.S)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_src: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 32 || nmu < 1 || nmu > 64 || !theta || !B_sys || !M_red || !rhs_red_K || !phi || !work || !U)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_src: needs N <= 32 and nmu <= 64");
+  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_src: need 1 <= K <= 64");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_src: dt > 0 and nt >= 1 required");
+  return red_euler_batch_run(ctx, "reduced_implicit_euler_batch_src", Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red_K, K, phi, work, U,
+                             rtol, max_iter, info, (hipStream_t)stream);
 }
 
 int64_t lrbms3_reduced_time_residual_work_size(lrbms3_ctx* ctx, int32_t N) {

@@ -151,6 +151,36 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
         self.last_solve_info = info
         return (u, info) if return_info else u
 
+    def solve_batch(self, mus, rtol=1e-12, max_iter=20000, return_info=False):
+        """Parameter sweep over the parabolic reduced model: one ``lrbms3_reduced_implicit_euler_batch(_src)`` call per 64
+        parameters -> [len(mus), nt + 1, S, N]; entry m is what ``solve(mus[m])`` returns (the estimator stays per trajectory).
+        info: (largest per-call iteration count, worst relative residual).  N > 32: one ``solve`` per parameter."""
+        import torch
+        d, nt, out = self.d, self.time_stepper.nt, []
+        info = (0, 0.0)
+        if self.N > 32:                       # the batched kernels take N <= 32
+            for mu in mus:
+                u, inf = self.solve(mu, rtol=rtol, max_iter=max_iter, return_info=True)
+                out.append(u[None])
+                info = (max(info[0], inf[0]), max(info[1], inf[1]))
+        else:
+            ctx = d.engine.ctx
+            for b0 in range(0, len(mus), 64):          # 64 per native call: four groups of 16 on four streams
+                chunk = mus[b0:b0 + 64]
+                th = np.stack([d.theta(mu) for mu in chunk])
+                if self.rhs_red_K is None:
+                    U, inf = ctx.reduced_implicit_euler_batch(d.Q, th, self.dt, nt, self.out['B_sys'], self.M_red, self.out['rhs_red'],
+                                                              rtol=rtol, max_iter=max_iter)
+                else:
+                    phi = np.stack([np.asarray(d.source_coefficients(mu), dtype=np.float64) for mu in chunk])     # [nmu, nt + 1, K]
+                    U, inf = ctx.reduced_implicit_euler_batch_src(d.Q, th, self.dt, nt, self.out['B_sys'], self.M_red, self.rhs_red_K,
+                                                                  phi, rtol=rtol, max_iter=max_iter)
+                out.append(U.permute(3, 0, 1, 2))
+                info = (max(info[0], inf[0]), max(info[1], inf[1]))
+        U = torch.cat(out, dim=0).contiguous()
+        self.last_solve_info = info
+        return (U, info) if return_info else U
+
     def estimate(self, u, mu, decompose=False):
         """The five parts of ``InstationaryDiscretization3D.estimate`` for reduced coefficients u [nt + 1, S, N]: the elliptic terms
         from the batched reduced estimate (one parameter column per time step), the nc row of the same call on the differences, the
