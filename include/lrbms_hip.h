@@ -275,7 +275,9 @@ void* lrbms_ctx_aux_stream(lrbms_ctx* ctx, int32_t i);
  *   LRBMS_OPT_F2_FORM          0 (default): the flux Grams G_bb, G_rdd [self, self] of the fused pass as symmetric Grams of the
  *                              Cholesky-scaled flux rows (k_f2g; Bbb must be SPD, see lrbms_assemble_products) wherever its
  *                              per-element factor table fits in LDS; 1: the R~^T B R~ form k_f2 for every shape (cross-check:
- *                              G_bb and G_rdd differ at rounding level, every other output is the same bits) */
+ *                              G_bb and G_rdd differ at rounding level, every other output is the same bits); 2: k_f2g with
+ *                              the producers that own one column per lane and half (what odd Q N runs in form 0 as well; the
+ *                              cross-check of the column-pair producers of form 0: every output is the same bits) */
 #define LRBMS_OPT_STREAMS 3
 #define LRBMS_OPT_F1_KSPLIT 4
 #define LRBMS_OPT_F1_FORM 5

@@ -246,7 +246,7 @@ class NativeContext(ContextBase):
     OPTIONS = {'oswald_zero_on_subdomain_boundary': 1, 'accumulate_coupling_across_q': 2, 'oswald_vertex_patch': 9, 'prep_lds': 10,
                # launch policy (no numerical convention): the library reads no environment variable
                'streams': 3, 'f1_ksplit': 4, 'f1_form': 5, 'coarse': 6, 'solve_valu': 7, 'estimate_valu': 8,
-               'f2_form': 11}
+               'f2_form': 11}      # f2_form: 0 Gram form (column-pair producers), 1 product form k_f2, 2 Gram form with one-column producers
     S = S_ext = None
     _keep = None
 

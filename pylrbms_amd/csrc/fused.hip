@@ -24,7 +24,7 @@
 //   k_vertex_avg     A(+B)  Oswald vertex averages Avg_self [S][nv][N], Avg_side [S][4][nvs][N]
 //   k_flux_side, k_vertex_side   B   R_side / Avg_side alone (phase 2 of a sharded pass)
 //   k_f1<NTX,7,Q>    A   X = V:  B_sys diag, E_red, M_red, G_aa, G_ab[:, self], rhs_red  (MFMA; grid.z = 2: K-split)
-//   k_f2g<NR>        A   X = C R~, sqrt|T| d: G_bb[self,self], G_rdd[self,self] as Grams X^T X, r_fd[self]  (MFMA, symmetric tiles;
+//   k_f2g<NR,PAIR>   A   X = C R~, sqrt|T| d: G_bb[self,self], G_rdd[self,self] as Grams X^T X, r_fd[self]  (MFMA, symmetric tiles;
 //                       k_f2<NR>: the R~^T B R~ form, LRBMS_OPT_F2_FORM 1)
 //   k_f3<NTX>        A   X = W_self: G_nc[self,self]                                     (MFMA, symmetric tiles)
 //   k_thin_nc        B   grid (4 sides, S): block-row `a` and block [self,a] of G_nc     (MFMA + VALU, latency-bound)
@@ -2439,8 +2439,8 @@ __global__ __launch_bounds__(512, 2) void k_f1v(Tmpl t, F1Args a, GrpTable gt) {
 // is Z V (two rows) instead of V.  A chunk of four elements is then 3 k-steps for the tiles of B_sys / E_red / M_red and 2 k-steps
 // for the others: 150 instead of 204 projection MFMAs per chunk.  What changes against k_f1v:
 //   * role A's stacked apply carries the two rows of Z_T (template table t.lgz) where it carried the three rows of K_T: Z V leaves
-//     the matrix pipe with the system rows, is stored once as the second X operand (Zs) and, times c^{qq'}, as the Y rows of the
-//     three G_aa groups;
+//     the matrix pipe with the system rows and is stored once as the second X operand (Zs); times c^{qq'} it is also the Y operand of
+//     the three G_aa groups, which their consumers form from Zs and the element's scalars (Cs) where they read it (F1wPlan::scaled);
 //   * role B multiplies W'^q_T (2 x 3 per component; k_prep_lds forms it from A_ab with the template table t.hab) with the three
 //     flux rows: four output rows, on the 4x4x4 MFMA (five instructions cover the 2 N columns of an element's flux rows);
 //   * the column tiles come in two kinds (3 or 2 K rows per element) and three classes (row tiles needed); which SIMD owns which
@@ -2453,6 +2453,13 @@ struct F1wPlan {
   // v1 block 1 of G_aa[0][0] / [1][1]; 3: v0 block 0 of those, v1 K2 tiles of class 3; 4 .. 6: K2 tiles of class 3
   static constexpr int cls(int l, int v) { return l == 0 ? 1 : l == 1 ? 2 : l == 2 ? (v == 0 ? 3 : 2) : l == 3 ? (v == 0 ? 1 : 3) : 3; }
   static constexpr int kr(int l, int v) { return l < 2 ? 3 : l == 2 ? (v == 0 ? 3 : 2) : 2; }      // K rows per element
+  // The G_aa tiles (10 .. 17: every SIMD owns two of them) have no columns in Ys: their B operand is c^{qq'}_T times a Z V row, which
+  // role A stores once (Zs); the consumer multiplies it with the element's scalar (Cs) where it reads it.  Ys holds the other
+  // NYT tiles side by side: 0 .. 9 (the kind-3 groups) where the plan has them, 18 .. 27 (the G_ab groups) GAA_TILES tiles lower.
+  static constexpr bool scaled(int l, int v) { return (l == 2 && v == 1) || l == 3 || (l == 4 && v == 0); }
+  static constexpr int GAA_TILES = 8, NYT = 4 * NL - GAA_TILES;
+  static constexpr int ytile_shift(int l) { return l >= 3 ? GAA_TILES : 0; }      // (of a tile that is not scaled)
+  static constexpr int LDY = NYT * 16 + 16;            // 336 = 16 (mod 32), as padded_ld
   static constexpr int first(int role) { return role == 0 ? 0 : LA; }
   static constexpr int count(int role) { return role == 0 ? LA : NL - LA; }
   static constexpr int slots_before(int role, int v, int jt) {
@@ -2470,17 +2477,19 @@ struct F1wPlan {
     return false;
   }
 };
+static_assert(F1wPlan::LDY % 32 == 16, "row stride of Ys");
 static_assert(F1wPlan::cls(0, 0) < 3 && F1wPlan::cls(0, 1) < 3 && F1wPlan::cls(1, 0) < 3 && F1wPlan::cls(1, 1) < 3, "class-3 tiles are role B's");
 template <int V> struct F1wV { static constexpr int value = V; };
+constexpr int F1W_CSE = 4;         // doubles per element of the scalar table Cs: c^{00}, c^{01}, c^{11}, (pad)
 
 template <int ROLE>
 __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const double* __restrict__ Wab, double* __restrict__ Xs,
-                                         double* __restrict__ Zs, double* __restrict__ Ys, double* __restrict__ red,
+                                         double* __restrict__ Zs, double* __restrict__ Ys, double* __restrict__ Cs, double* __restrict__ red,
                                          int* __restrict__ flag, const int* __restrict__ colmap, const Grp* grp) {
   using LV = F1wPlan;
-  constexpr int NTX = 3, QP = 2, NTYS = LV::NL;
+  constexpr int NTX = 3, QP = 2;
   constexpr int LDX = padded_ld(NTX);
-  constexpr int LDY = 4 * NTYS * 16 + 16;
+  constexpr int LDY = LV::LDY;
   constexpr int NT = LV::count(ROLE), LV0 = LV::first(ROLE);
   constexpr int NS = LV::max_slots(ROLE);
   static_assert(NS <= F1V_SLOTS, "K-split partial layout");
@@ -2517,12 +2526,28 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
       c[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(at[1], bv, c[1], 0, 0, 0);
     }
   };
+  // A scaled tile (LV::scaled; role B's) reads its B operand from Zs: lane (lk, li) holds K row kk + lk -- a Z V row of element
+  // (kk + lk) >> 1 -- of the basis column the column map gives for the lane's tile column, times that element's c^{qq'} of the group
+  // the column belongs to (pr = 0, 1, 2: (0,0), (0,1), (1,1); lane constants: the packed-tails tile 14 holds columns of two groups).
+  // fl(c * zv) is what role A stored into Ys before.  Dead columns (the column map drops them) take column 0 and pr = 0.
+  constexpr int NSC = ROLE == 1 ? 3 : 1;               // the scaled tiles are among the first three of role B's list
+  int zc[NSC], cso[NSC];
+  if constexpr (ROLE == 1) {
+#pragma unroll
+    for (int jt = 0; jt < NSC; ++jt) {
+      const int m = colmap[(4 * (LV0 + jt) + e) * 16 + li];
+      const bool gaa = m >= 0 && (m >> 8) >= QP + 2 && (m >> 8) < QP + 2 + NP;
+      zc[jt] = gaa ? (m & 255) : 0;
+      cso[jt] = (lk >> 1) * F1W_CSE + (gaa ? (m >> 8) - (QP + 2) : 0);
+    }
+  }
   // the projection of one chunk: 3 k-steps over the V rows for the tiles of kind 3, 2 k-steps over the Z rows for the tiles of kind 2
   auto mfma_phase = [&](int c, auto vtag) {
     constexpr int V = decltype(vtag)::value;
     const double* Xb = Xs + (c & 1) * 3 * EC * LDX;
     const double* Zb = Zs + (c & 1) * 2 * EC * LDX;
     const double* Yb = Ys + (c & 1) * 3 * EC * LDY;
+    const double* Cb = Cs + (c & 1) * EC * F1W_CSE;
     constexpr bool any3 = LV::kr(LV0, V) == 3 || LV::kr(LV0 + (NT > 1 ? 1 : 0), V) == 3;      // (kind-3 tiles are the first of a role's list)
     if constexpr (any3) {
 #pragma unroll
@@ -2535,7 +2560,7 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt) {
           if (LV::kr(LV0 + jt, V) == 3) {      // (compile time once the loop is unrolled)
-            const double bv = Yb[(kk + lk) * LDY + (4 * (LV0 + jt) + e) * 16 + li];
+            const double bv = Yb[(kk + lk) * LDY + (4 * (LV0 + jt) + e) * 16 + li];      // (tiles 0 .. 9: not shifted)
 #pragma unroll
             for (int i = 0; i < LV::cls(LV0 + jt, V); ++i) row_tile(acc[LV::slots_before(ROLE, V, jt) + i], i, av[i], at, bv);
           }
@@ -2550,12 +2575,21 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
         for (int i = 0; i < NTX; ++i) av[i] = Zb[(kk + lk) * LDX + i * 16 + li];
 #pragma unroll
         for (int h = 0; h < 2; ++h) at[h] = Zb[(kk + lk) * LDX + 32 + 4 * h + (li & 3)];
+        double bv[NT];                             // every fragment of the k-step is requested in front of its MFMAs
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt) {
           if (LV::kr(LV0 + jt, V) == 2) {
-            const double bv = Yb[(kk + lk) * LDY + (4 * (LV0 + jt) + e) * 16 + li];
+            if (jt < NSC && LV::scaled(LV0 + jt, V))
+              bv[jt] = Cb[(kk >> 1) * F1W_CSE + cso[jt % NSC]] * Zb[(kk + lk) * LDX + zc[jt % NSC]];
+            else
+              bv[jt] = Yb[(kk + lk) * LDY + (4 * (LV0 + jt) - LV::ytile_shift(LV0 + jt) + e) * 16 + li];
+          }
+        }
 #pragma unroll
-            for (int i = 0; i < LV::cls(LV0 + jt, V); ++i) row_tile(acc[LV::slots_before(ROLE, V, jt) + i], i, av[i], at, bv);
+        for (int jt = 0; jt < NT; ++jt) {
+          if (LV::kr(LV0 + jt, V) == 2) {
+#pragma unroll
+            for (int i = 0; i < LV::cls(LV0 + jt, V); ++i) row_tile(acc[LV::slots_before(ROLE, V, jt) + i], i, av[i], at, bv[jt]);
           }
         }
       }
@@ -2612,7 +2646,7 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
     const unsigned rs3 = 24u * (unsigned)N;
     // LDS offsets (doubles) of the apply's outputs (see k_f1v: lanes beyond N hold duplicates of a column < N and store the same
     // value to the same address).  Rows 0 .. 11 (registers 0 .. 2): every lane has a row; register 3: lanes kq < 2 hold a Z row
-    int xoff[NTX], zoff[NTX], yoff[3][NTX], koff[NP][NTX];
+    int xoff[NTX], zoff[NTX], yoff[3][NTX];
     const bool zrow = kq < 2;
 #pragma unroll
     for (int ct = 0; ct < NTX; ++ct) {
@@ -2624,8 +2658,6 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
         const int r = kq + 4 * rr;
         yoff[rr][ct] = (3 * e + r % 3) * LDY + pos(r / 3, col);
       }
-#pragma unroll
-      for (int pr = 0; pr < NP; ++pr) koff[pr][ct] = (2 * e + (zrow ? kq : 0)) * LDY + pos(QP + 2 + pr, col);
     }
     const cint_p nbc = (cint_p)t.nb_elem;
     struct Sc {
@@ -2682,6 +2714,7 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
       double* Xb = Xs + (c & 1) * 3 * EC * LDX;
       double* Zb = Zs + (c & 1) * 2 * EC * LDX;
       double* Yb = Ys + (c & 1) * 3 * EC * LDY;
+      double* Cb = Cs + (c & 1) * EC * F1W_CSE + e * F1W_CSE;
       if (e == 0) F1_STAMP(0, c, 0);
       touch_sc(sc_nxt);
       double cc[NP];
@@ -2706,14 +2739,11 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
       for (int rr = 0; rr < 3; ++rr)
 #pragma unroll
         for (int ct = 0; ct < NTX; ++ct) Yb[yoff[rr][ct]] = D[ct][rr];
-      if (zrow) {                                  // lane constant: one exec region for the Z rows and the c^{qq'} Z V stores
+      if (zrow) {                                  // lane constant
 #pragma unroll
         for (int ct = 0; ct < NTX; ++ct) Zb[zoff[ct]] = D[ct][RRZ];
-#pragma unroll
-        for (int pr = 0; pr < NP; ++pr)
-#pragma unroll
-          for (int ct = 0; ct < NTX; ++ct) Yb[koff[pr][ct]] = cc[pr] * D[ct][RRZ];
       }
+      if (lane < NP) Cb[lane] = lane == 0 ? cc[0] : lane == 1 ? cc[1] : cc[2];      // the consumers scale the Z V rows (mfma_phase)
 #pragma unroll
       for (int ct = 0; ct < NTX; ++ct) rhs_part[ct] += D[ct][RRZ];      // meaningful on the lanes kq == KQB
       if (e == 0) F1_STAMP(0, c, 2);
@@ -2788,7 +2818,7 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
 #pragma unroll
       for (int m = 0; m < NCI; ++m) {
         const int q2 = col[m] >= N ? 1 : 0;
-        yo[m] = (2 * e + (kq & 1)) * LDY + pos(QP + 2 + NP + (kq >> 1) * QP + q2, col[m] - q2 * N);
+        yo[m] = (2 * e + (kq & 1)) * LDY + pos(QP + 2 + NP + (kq >> 1) * QP + q2, col[m] - q2 * N) - 16 * LV::GAA_TILES;
       }
     }
     const unsigned rsr = 8u * (unsigned)QN;
@@ -2949,10 +2979,11 @@ __device__ __forceinline__ void f1w_body(const Tmpl& t, const F1Args& a, const d
 __global__ __launch_bounds__(512, 2) void k_f1w(Tmpl t, F1Args a, GrpTable gt, const double* __restrict__ Wab) {
   constexpr int NTX = 3, NTYS = F1wPlan::NL;
   constexpr int LDX = padded_ld(NTX);
-  constexpr int LDY = 4 * NTYS * 16 + 16;
+  constexpr int LDY = F1wPlan::LDY;
   __shared__ double Xs[2 * 3 * EC * LDX];
   __shared__ double Zs[2 * 2 * EC * LDX];
   __shared__ double Ys[2 * 3 * EC * LDY];
+  __shared__ double Cs[2 * EC * F1W_CSE];              // c^{qq'}_T of the chunk's elements, by chunk parity: [e][pr]
   __shared__ double red[EC * 64];
   __shared__ int colmap[4 * NTYS * 16];
   __shared__ Grp grp[F1_MAXG];
@@ -2973,9 +3004,9 @@ __global__ __launch_bounds__(512, 2) void k_f1w(Tmpl t, F1Args a, GrpTable gt, c
   }
   __syncthreads();
   if (uniform(tid >> 6) < EC)
-    f1w_body<0>(t, a, Wab, Xs, Zs, Ys, red, &flag, colmap, grp);
+    f1w_body<0>(t, a, Wab, Xs, Zs, Ys, Cs, red, &flag, colmap, grp);
   else
-    f1w_body<1>(t, a, Wab, Xs, Zs, Ys, red, &flag, colmap, grp);
+    f1w_body<1>(t, a, Wab, Xs, Zs, Ys, Cs, red, &flag, colmap, grp);
   if (gridDim.z == 1 && a.rhs_red != nullptr) {
     __syncthreads();
     if (tid < a.N) {
@@ -3314,12 +3345,20 @@ inline size_t f2g_dyn_lds_bytes(const Tmpl& t) { return sizeof(double) * (F2G_EL
 template <int NR>
 constexpr size_t f2g_static_lds_bytes() { return sizeof(double) * (2 * F2G_ROWS * padded_ld(NR) + EC * 128); }
 
-template <int NR>
+// a x + b y + c z and a x + b y as hipcc contracts them in the one-column producers of k_f2g (read off its gfx950 assembly)
+__device__ inline double f2g_dot3(double a, double x, double b, double y, double c, double z) { return __builtin_fma(c, z, __builtin_fma(a, x, b * y)); }
+__device__ inline double f2g_dot2(double a, double x, double b, double y) { return __builtin_fma(a, x, b * y); }
+
+// PAIR 1 (even QN, LRBMS_OPT_F2_FORM 0): a producer lane owns the adjacent columns 2 l, 2 l + 1 -- 3 loads of 16 bytes per element
+// from a wave-uniform base with a 32-bit byte offset (gload_s128, as role B of k_f1w) and 4 LDS stores of 16 bytes, in one exec
+// region; the per-column expressions are those of the one-column producers (PAIR 0: odd QN, LRBMS_OPT_F2_FORM 2), said with
+// explicit fma in the order hipcc contracts them there, so both forms give the same bits.
+template <int NR, int PAIR>
 __global__ __launch_bounds__(64 * (F2_NCW + EC)) __attribute__((amdgpu_waves_per_eu(NR <= 5 ? 2 * F2G_WG : 2))) void k_f2g(Tmpl t, F2Args a) {
   constexpr int LD = padded_ld(NR);
   extern __shared__ double dyn[];
-  __shared__ double Xg[2 * F2G_ROWS * LD];
-  __shared__ double red[EC * 128];
+  __shared__ __attribute__((aligned(16))) double Xg[2 * F2G_ROWS * LD];
+  __shared__ __attribute__((aligned(16))) double red[EC * 128];
   const int s = subdomain_of(t, blockIdx.x), tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const int wave = uniform(tid >> 6);
   const int nthreads = 64 * (F2_NCW + EC);
@@ -3362,8 +3401,67 @@ __global__ __launch_bounds__(64 * (F2_NCW + EC)) __attribute__((amdgpu_waves_per
   const int nchunks = t.nT / EC;
   const double* Rs = a.Rself + (long)s * t.nrt * QN;
 
-  if (wave < EC) {
-    // ================================================= producers
+  if (PAIR && wave < EC) {
+    // ================================================= producers, column pairs
+    // Prefetch set of one element: its 3 face rows of R~, 16 bytes per lane (3 asm loads; idle lanes re-read the last pair),
+    // completed by an explicit s_waitcnt vmcnt(3) (see gload_f64 and k_f2); the factors come from LDS.
+    d2 rv[3], nrv[3];
+    const int np = QN >> 1;                          // QN even, <= 128: at most 64 pairs
+    const bool own = lane < np;
+    const unsigned po = 16u * (unsigned)(own ? lane : np - 1), rsr = 8u * (unsigned)QN;   // (the launcher: n_rt QN 8 < 2^31)
+    auto load = [&](int T, d2 (&r)[3]) {
+      const unsigned r0 = (unsigned)rts[3 * T], r1 = (unsigned)rts[3 * T + 1], r2 = (unsigned)rts[3 * T + 2];
+      r[0] = gload_s128(Rs, r0 * rsr + po);
+      r[1] = gload_s128(Rs, r1 * rsr + po);
+      r[2] = gload_s128(Rs, r2 * rsr + po);
+    };
+    auto wait_set = [&](d2 (&r)[3]) { asm volatile("s_waitcnt vmcnt(3)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2])); };
+    auto wait_set_tie = [&](d2 (&r)[3]) { asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2])); };
+    load(wave, rv);
+    d2 rfd_part = {0.0, 0.0};                        // columns 2 lane, 2 lane + 1
+    auto step = [&](int c, d2 (&cr)[3], d2 (&nr)[3]) {
+      const int T = c * EC + wave, el = wave;
+      load(c + 1 < nchunks ? T + EC : T, nr);      // unconditional: the wait below counts on exactly 3 younger loads
+      wait_set(cr);
+      double* xb = Xg + (c & 1) * F2G_ROWS * LD + 2 * lane;
+      const double* ft = fac + F2G_EL * T;
+      const double u00 = ft[0], u01 = ft[1], u02 = ft[2], u11 = ft[3], u12 = ft[4], u22 = ft[5], sqa = ft[6];
+      const double c0f = coefs[3 * T], c1f = coefs[3 * T + 1], c2f = coefs[3 * T + 2];
+      const double bsum = bsums[T];
+#ifdef F2_NO_STAGE
+      if (own && cr[0][0] == 1.2345e300) {
+#else
+      if (own) {
+#endif
+        d2 x0, x1, x2, x3;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const double rv0 = cr[0][k], rv1 = cr[1][k], rv2 = cr[2][k];
+          x0[k] = f2g_dot3(u00, rv0, u01, rv1, u02, rv2);
+          x1[k] = f2g_dot2(u11, rv1, u12, rv2);
+          x2[k] = u22 * rv2;
+          const double d = f2g_dot3(c0f, rv0, c1f, rv1, c2f, rv2);     // as k_f2: r_fd stays bit-identical
+          x3[k] = sqa * d;
+          rfd_part[k] = __builtin_fma(bsum, d, rfd_part[k]);
+        }
+        *reinterpret_cast<d2*>(xb + (3 * el) * LD) = x0;
+        *reinterpret_cast<d2*>(xb + (3 * el + 1) * LD) = x1;
+        *reinterpret_cast<d2*>(xb + (3 * el + 2) * LD) = x2;
+        *reinterpret_cast<d2*>(xb + (3 * EC + el) * LD) = x3;
+      }
+      lds_barrier();                               // barrier c: buffer c & 1 complete (loads stay in flight)
+    };
+    for (int c = 0; c < nchunks; c += 2) {         // nT is a multiple of 8, so nchunks is even
+      step(c, rv, nrv);
+      step(c + 1, nrv, rv);
+    }
+    lds_barrier();                                 // final barrier
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last prefetch set is never consumed, but it has to stay
+    wait_set_tie(rv);                                  // live until its loads have landed (see k_f1)
+    wait_set_tie(nrv);
+    if (own) *reinterpret_cast<d2*>(red + wave * 128 + 2 * lane) = rfd_part;   // the other entries keep the zeros of the prologue
+  } else if (wave < EC) {
+    // ================================================= producers, one column per lane and half
     // Prefetch set of one element: its 3 face rows of R~ in two column halves (6 asm loads; idle lanes re-read the last
     // column), completed by an explicit s_waitcnt vmcnt(6) (see gload_f64 and k_f2); the factors come from LDS.
     double rv[2][3], nrv[2][3];
@@ -4622,8 +4720,9 @@ static bool f1w_usable(lrbms_ctx* ctx, int Q, int N) { return Q == 2 && N % 2 ==
 // Column layout of Y for k_f1w (Q = 2, three row tiles, even N in [34, 40]): the tiles of F1wPlan.  Symmetric groups of kind 3
 // (B_sys diagonal q = 0, 1, E_red, M_red; index si): block 0 -> tile si (level 0), block 1 -> tile 4 + si (level 1), the tails packed
 // into tiles 8, 9 (level 2, SIMDs 0, 1).  Symmetric groups of kind 2 (G_aa[0][0], G_aa[1][1]; index sj): block 0 -> tile 12 + sj
-// (level 3, SIMDs 0, 1), block 1 -> tile 10 + sj (level 2, SIMDs 2, 3), the tails packed into tile 14.  The unsymmetric groups
-// (G_aa[0][1], the four G_ab) contiguously from tile 15 on.  false if the shape is not the plan's.
+// (level 3, SIMDs 0, 1), block 1 -> tile 10 + sj (level 2, SIMDs 2, 3), the tails packed into tile 14.  G_aa[0][1] has tiles
+// 15 .. 17 to itself (so a tile reads either Ys or scaled Z V rows: F1wPlan::scaled), the four G_ab contiguously from tile 18 on.
+// false if the shape is not the plan's.
 static bool f1w_layout(std::vector<Grp>& groups, int N, int Q) {
   const int ntx = (N + 15) / 16, tail = N - 32;
   if (Q != 2 || ntx != 3 || N % 2 != 0 || tail < 2 || tail > 8 || groups.size() != 11) return false;
@@ -4642,11 +4741,12 @@ static bool f1w_layout(std::vector<Grp>& groups, int N, int Q) {
       g.cb[2] = 16 * 14 + s2 * tail;
       ++s2;
     } else {
-      for (int j = 0; j < 4; ++j) g.cb[j] = 16 * 15 + ui * N + 16 * j;
+      for (int j = 0; j < 4; ++j) g.cb[j] = g.kind == G_AA ? 16 * (15 + j) : 16 * 18 + (ui - 1) * N + 16 * j;
+      if (g.kind == G_AA && ui != 0) return false;      // (G_aa[0][1] is the first unsymmetric group)
       ++ui;
     }
   }
-  return s3 == 4 && s2 == 2 && ui == 5 && 16 * 15 + 5 * N <= 16 * 28;
+  return s3 == 4 && s2 == 2 && ui == 5 && 16 * 18 + 4 * N <= 16 * 28;
 }
 
 // MFMA work, in units of 2 048 flop (one v_mfma_f64_16x16x4_f64; a v_mfma_f64_4x4x4_4b_f64 is a quarter), the dense projection kernel
@@ -5161,18 +5261,26 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
   // ---- F2
   // LRBMS_OPT_F2_FORM 0: the Gram form k_f2g (every NR = ceil(QN / 16) the pass accepts); it keeps a factor table of
   // 64 bytes per element in LDS beside k_f2's tables, so a template whose table does not fit runs k_f2 instead (as does
-  // LRBMS_OPT_F2_FORM 1, the cross-check)
+  // LRBMS_OPT_F2_FORM 1, the cross-check); LRBMS_OPT_F2_FORM 2: k_f2g with one-column producers
   const int nr2 = (QN + 15) / 16;
   static const size_t f2g_static[8] = {f2g_static_lds_bytes<1>(), f2g_static_lds_bytes<2>(), f2g_static_lds_bytes<3>(), f2g_static_lds_bytes<4>(),
                                        f2g_static_lds_bytes<5>(), f2g_static_lds_bytes<6>(), f2g_static_lds_bytes<7>(), f2g_static_lds_bytes<8>()};
-  const bool f2_gram = ctx->opt_f2_form == 0 && f2g_dyn_lds_bytes(t) + f2g_static[nr2 - 1] <= 160 * 1024;
+  const bool f2_gram = (ctx->opt_f2_form == 0 || ctx->opt_f2_form == 2) && f2g_dyn_lds_bytes(t) + f2g_static[nr2 - 1] <= 160 * 1024;
+  // its producers own adjacent column pairs (16-byte loads at 32-bit byte offsets from the subdomain's R~) where QN is even;
+  // odd QN and LRBMS_OPT_F2_FORM 2 (the cross-check of the two producer forms) run the one-column producers
+  const bool f2_pair = ctx->opt_f2_form == 0 && QN % 2 == 0 && (reinterpret_cast<uintptr_t>(Rself) & 15) == 0 && 8L * t.nrt * QN < (1L << 31);
   if (do_a && f2_gram) {
     F2Args a{Rself, Bbb, b, ctx->nbr, G_bb, G_rdd, r_fd, Q, N, S, gstride};
     const size_t ldsf2 = f2g_dyn_lds_bytes(t);
+#define LRBMS_F2G_P(NRV, PV)                                                                                                \
+  do {                                                                                                                       \
+    LRBMS_HIP_CHECK(ctx, raise_max_lds(ctx->device, (const void*)k_f2g<NRV, PV>, (int)ldsf2));                              \
+    hipLaunchKernelGGL((k_f2g<NRV, PV>), dim3(Sg), dim3(64 * (F2_NCW + EC)), ldsf2, s_f23, t, a);                             \
+  } while (0)
 #define LRBMS_F2G(NRV)                                                                                                      \
   do {                                                                                                                       \
-    LRBMS_HIP_CHECK(ctx, raise_max_lds(ctx->device, (const void*)k_f2g<NRV>, (int)ldsf2));                                  \
-    hipLaunchKernelGGL(k_f2g<NRV>, dim3(Sg), dim3(64 * (F2_NCW + EC)), ldsf2, s_f23, t, a);                                   \
+    if (f2_pair) LRBMS_F2G_P(NRV, 1);                                                                                        \
+    else LRBMS_F2G_P(NRV, 0);                                                                                                \
   } while (0)
     KScope ks(ctx, "k_f2", s_f23);
     switch (nr2) {
@@ -5186,6 +5294,7 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
       default: LRBMS_F2G(8); break;
     }
 #undef LRBMS_F2G
+#undef LRBMS_F2G_P
     LRBMS_LAUNCH_CHECK(ctx);
   }
   if (do_a && !f2_gram) {
