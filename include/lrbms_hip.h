@@ -151,7 +151,11 @@ int lrbms_assemble_rhs(lrbms_ctx* ctx, const double* f_smp, const double* lhat, 
  *   Bbb    [S][n_T][3][3]                  df_bb element blocks [f][g]: symmetric positive definite (the kappa^-1-weighted RT0 mass
  *                                          of the element).  The fused pass relies on it (LRBMS_OPT_F2_FORM 0 factors each block by
  *                                          Cholesky from its upper triangle); a subdomain with a block that is not SPD gets a NaN
- *                                          G_bb[self, self] there, not finite wrong numbers */
+ *                                          G_bb[self, self] there, not finite wrong numbers.  A df_bb rule with ONE point gives
+ *                                          singular blocks (rank <= 2: three RT0 functions at one point of the plane): such a
+ *                                          quadrature needs LRBMS_OPT_F2_FORM 1, which does not factor Bbb and matches the oracle
+ *                                          (the Python Engine selects it; rules with positive weights at >= 3 points that are not
+ *                                          collinear give SPD blocks) */
 int lrbms_assemble_products(lrbms_ctx* ctx, int32_t Q, const double* theta_bar, const double* lam, const double* lam_df,
                             const double* lbar, const double* lhat, double* P_diag, double* ebar, double* caa, double* Aab,
                             double* Bbb, void* stream);

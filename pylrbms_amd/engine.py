@@ -86,7 +86,9 @@ class Engine:
     def __init__(self, grid, lambda_funcs, kappa, f, lambda_bar, lambda_hat, theta_bar, device_index=0, conventions=None,
                  quadrature=None):
         """``quadrature``: a ``QuadratureSpec`` (default: the reference's orders for these data functions,
-        ``QuadratureSpec.for_problem``; ``QuadratureSpec.uniform(5)`` is the round-1 convention)."""
+        ``QuadratureSpec.for_problem``; ``QuadratureSpec.uniform(5)`` is the round-1 convention).  With a one-point ``df_bb`` rule
+        (order 0 or 1) the element blocks ``Bbb`` are singular: the engine then selects ``f2_form`` 1, the form of the flux Grams that
+        does not factor them, and refuses a ``conventions['f2_form']`` that does."""
         self._init_args = (lambda_funcs, kappa, f, lambda_bar, lambda_hat, theta_bar, device_index, conventions, quadrature)
         self.conventions = dict(conventions or {})
         self.quadrature = quadrature if quadrature is not None else QuadratureSpec.for_problem(lambda_funcs, f, lambda_bar,
@@ -126,6 +128,13 @@ class Engine:
                                      dtype=np.int32).reshape(len(local), 4)
             self.ctx.set_diagonal_neighbours(self.nbr_diag)
         self.ctx.set_quadrature(self.quadrature)
+        if self.ctx.quad.df_bb.n == 1:
+            # one point: Bbb of an element is the outer product of the three RT0 functions at the centroid, rank <= 2 -- the Cholesky
+            # factors of LRBMS_OPT_F2_FORM 0 / 2 do not exist (NaN G_bb[self, self]); the product form 1 does not need them
+            if int(self.conventions.get('f2_form', 1)) != 1:
+                raise ValueError('f2_form {} factors the Bbb blocks by Cholesky, which a one-point df_bb rule (order {}) makes '
+                                 'singular: use f2_form 1 or a df_bb order >= 2'.format(self.conventions['f2_form'], self.quadrature.df_bb))
+            self.ctx.set_option('f2_form', 1)
         self.hdiam = grid.subdomain_diameter(0)
 
         # ---- coefficient sampling on the host at the points of the chosen rules, one H2D copy each

@@ -84,7 +84,10 @@ def edge_rule(order):
 
 
 class QuadratureSpec:
-    """Requested quadrature order per integrand (same fields and formulas as the oracle's spec; tests compare them)."""
+    """Requested quadrature order per integrand (same fields and formulas as the oracle's spec; tests compare them).
+
+    ``df_bb`` below 2 is a one-point rule: the RT0 element mass ``Bbb`` it gives is singular (rank <= 2).  ``Engine`` then runs the
+    fused pass with ``f2_form`` 1, which does not factor ``Bbb`` (the default form would return a NaN ``G_bb``)."""
 
     FIELDS = ('system_volume', 'system_inner_face', 'system_coupling_face', 'system_boundary_face', 'rhs', 'f2',
               'energy_volume', 'energy_face', 'elliptic_bar', 'flux_face', 'df_aa', 'df_ab', 'df_bb', 'ceps')

@@ -41,13 +41,15 @@ def frozen_problem(p, mu):
 class AffineSource:
     """The oracle discretization of a problem dict whose ``f`` is ``{'functions': [...], 'coefficients': [...]}``."""
 
-    def __init__(self, p):
+    def __init__(self, p, quad=None):
+        """``quad``: the oracle's ``QuadratureSpec`` (default: the orders the product picks for the problem)."""
         from pylrbms_amd.functions import SumFunction
         self.p = p
         self.funcs = list(p['f']['functions'])
         self.K = len(self.funcs)
         # the same quadrature orders as the product, which builds its engine on sum_j f_j
-        self.d = oracle_from_problem(dict(p, f=SumFunction(self.funcs, [1.0] * self.K)))
+        kw = {} if quad is None else {'quad': quad}
+        self.d = oracle_from_problem(dict(p, f=SumFunction(self.funcs, [1.0] * self.K)), **kw)
         self.b_K = np.stack([self.frozen(np.eye(self.K)[j]).b for j in range(self.K)])      # [K, ndof]
 
     def parse(self, mu):

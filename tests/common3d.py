@@ -46,23 +46,34 @@ PROBLEMS = {
 UNIT_DOMAIN = ([0.0, 0.0, 0.0], [1.0, 1.0, 1.0])
 
 
-def make_problem(name, domain=None, spec=None):
+def make_problem(name, domain=None, spec=None, data_degree=2):
     """The problem ``name`` of ``PROBLEMS`` -- or, with ``spec``, a tuple of the same layout under a name of the caller's -- on the
-    box ``domain`` = (lower_left, upper_right); default: the unit cube."""
+    box ``domain`` = (lower_left, upper_right); default: the unit cube.  ``data_degree``: the polynomial degree the quadrature
+    assumes for the data functions, kept in the dict for ``engine_of`` and ``oracle_of``."""
     P, kc, lams, thetas, kappa, N, mu = PROBLEMS[name] if spec is None else spec
     domain = UNIT_DOMAIN if domain is None else (list(domain[0]), list(domain[1]))
     from pylrbms_amd.grid3d import make_grid3d
     grid = make_grid3d(domain=domain, num_subdomains=P, cubes_per_subdomain_and_dim=kc, kappa=kappa)
     return dict(name=name, grid=grid, lambdas=lams, thetas=thetas, kappa=kappa, f=_f, lambda_bar=_lbar, lambda_hat=_lbar,
-                mu_bar=0.5, mu_hat=0.5, N=N, mu=mu, P=P, kc=kc, domain=domain)
+                mu_bar=0.5, mu_hat=0.5, N=N, mu=mu, P=P, kc=kc, domain=domain, data_degree=int(data_degree))
 
 
-def oracle_of(p, domain=None):
-    """The CPU oracle of a problem of ``make_problem``, on the problem's box unless ``domain`` names another."""
+def engine_of(p, data_degree=None, **kw):
+    """The (unassembled) ``Engine3D`` of a problem of ``make_problem`` at the problem's ``data_degree`` unless one is named."""
+    from pylrbms_amd.engine3d import Engine3D
+    deg = p.get('data_degree', 2) if data_degree is None else int(data_degree)
+    kw.setdefault('theta_bar', theta_of(p, p['mu_bar']))
+    return Engine3D(p['grid'], p['lambdas'], p['f'], p['lambda_bar'], p['lambda_hat'], data_degree=deg, **kw)
+
+
+def oracle_of(p, domain=None, data_degree=None):
+    """The CPU oracle of a problem of ``make_problem``, on the problem's box unless ``domain`` names another, at the problem's
+    ``data_degree`` unless one is named."""
     lo, hi = p.get('domain', UNIT_DOMAIN) if domain is None else domain
+    deg = p.get('data_degree', 2) if data_degree is None else int(data_degree)
     mesh = KuhnMesh3D(np.asarray(p['P']) * np.asarray(p['kc']), p['P'], lower_left=lo, upper_right=hi)
     return Discretization3D(mesh, p['lambdas'], p['thetas'], p['kappa'], p['f'], p['lambda_bar'], p['lambda_hat'], p['mu_bar'],
-                            p['mu_hat'])
+                            p['mu_hat'], data_degree=deg)
 
 
 def make_bases3d(S, n, N, seed=0):
