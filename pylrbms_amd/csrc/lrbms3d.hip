@@ -3681,6 +3681,7 @@ struct RbGroup {
   bool done;
   double rel;
   int it, last_it;
+  double look[32];                  // host: scal [3] (residuals) and [4] (|b|^2) as the last look at the group copied them
 };
 
 // the vectors, partials and scalars of a group from w on (5 S N 16 + 4 S 16 + 96 + 3 S 16 doubles)
@@ -3707,21 +3708,41 @@ struct RbOp {
   double* u;
 };
 
+// The panel matvec of one group: p_new = z + beta p_old (first: p_new = z), Ap = A p_new, in the matrix-core form with one or two
+// row tiles or in the VALU form (LRBMS3_OPT_SOLVE_VALU); MASS adds M_red on the self slot.
+template <bool MASS>
+void launch_matvec3(lrbms3_ctx* ctx, const RbOp& op, RbGroup& G, int first, const double* rz_cur, const double* rz_nxt, const CoarseB& cb) {
+  const T3& t = ctx->t;
+  const long S = t.S;
+  const int Q = op.Q, N = op.N;
+  const size_t lds_mv = sizeof(double) * (7 * N * 16 + 32 * 16);
+  const size_t lds_mm = sizeof(double) * (7 * 32 * 16 + 4 * (N <= 16 ? 1 : 2) * 256 + 32 * 16);
+  const bool mfma_mv = ctx->opt_solve_valu == 0;
+  MassOp3<MASS> mo;
+  if constexpr (MASS) mo.M = op.M_red;
+  if (mfma_mv && N <= 16)
+    hipLaunchKernelGGL((k3b_matvec_mfma<1, MASS>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, first, G.th, op.B_sys, G.z, G.po, G.pn,
+                       G.Ap, rz_cur, rz_nxt, G.ppap, cb, mo);
+  else if (mfma_mv)
+    hipLaunchKernelGGL((k3b_matvec_mfma<2, MASS>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, first, G.th, op.B_sys, G.z, G.po, G.pn,
+                       G.Ap, rz_cur, rz_nxt, G.ppap, cb, mo);
+  else
+    hipLaunchKernelGGL(k3b_matvec<MASS>, dim3(S), dim3(512), lds_mv, G.st, t, Q, N, G.nm, first, G.th, op.B_sys, G.z, G.po, G.pn, G.Ap,
+                       rz_cur, rz_nxt, G.ppap, cb, mo);
+}
+
 // The iteration loop of the batched reduced solvers from the state the start kernels left (G.it = 0, G.done = false): matvec /
 // update / coarse apply per group, launches interleaved iteration by iteration over the groups' streams, a look at the residuals
 // after first_block and then after every check iterations.  A group leaves at rel <= rtol, at max_iter (honoured exactly) or on a
 // NaN (nan set).  The residual norms sit in scal [3], their references in scal [4].
 int red_batch_iterate(lrbms3_ctx* ctx, const RbOp& op, RbGroup* g, int ng, int first_block, int check, double rtol, int max_iter,
                       bool& nan) {
-  const T3& t = ctx->t;
-  const long S = t.S;
-  const int Q = op.Q, N = op.N, nmu = op.nmu;
-  const double *B_sys = op.B_sys, *A0inv = op.A0inv;
+  const long S = ctx->t.S;
+  const int N = op.N, nmu = op.nmu;
+  const double* A0inv = op.A0inv;
   double* u = op.u;
-  const size_t lds_mv = sizeof(double) * (7 * N * 16 + 32 * 16), lds_up = sizeof(double) * (N * 16 + 32 * 16);
-  const size_t lds_mm = sizeof(double) * (7 * 32 * 16 + 4 * (N <= 16 ? 1 : 2) * 256 + 32 * 16);
-  const bool mfma_mv = ctx->opt_solve_valu == 0;      // LRBMS3_OPT_SOLVE_VALU: the VALU panel matvec
-  const MassOp3<true> mo{op.M_red};
+  const size_t lds_up = sizeof(double) * (N * 16 + 32 * 16);
+  const bool mfma_mv = ctx->opt_solve_valu == 0;
   bool all_done = false;
   int block = first_block;
   while (!all_done) {
@@ -3737,26 +3758,10 @@ int red_batch_iterate(lrbms3_ctx* ctx, const RbOp& op, RbGroup* g, int ng, int f
         const CoarseB cb{A0inv ? G.y0 : nullptr, rc_cur, rc_nxt};
         if (op.M_red) {
           KScope ks(ctx, mfma_mv ? "k3b_matvec_mfma<mass>" : "k3b_matvec<mass>", G.st);
-          if (mfma_mv && N <= 16)
-            hipLaunchKernelGGL((k3b_matvec_mfma<1, true>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys,
-                               G.z, G.po, G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb, mo);
-          else if (mfma_mv)
-            hipLaunchKernelGGL((k3b_matvec_mfma<2, true>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys,
-                               G.z, G.po, G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb, mo);
-          else
-            hipLaunchKernelGGL(k3b_matvec<true>, dim3(S), dim3(512), lds_mv, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
-                               G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb, mo);
+          launch_matvec3<true>(ctx, op, G, it == 0 ? 1 : 0, rz_cur, rz_nxt, cb);
         } else {
           KScope ks(ctx, mfma_mv ? "k3b_matvec_mfma" : "k3b_matvec", G.st);
-          if (mfma_mv && N <= 16)
-            hipLaunchKernelGGL(k3b_matvec_mfma<1>, dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
-                               G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb);
-          else if (mfma_mv)
-            hipLaunchKernelGGL(k3b_matvec_mfma<2>, dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
-                               G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb);
-          else
-            hipLaunchKernelGGL(k3b_matvec<false>, dim3(S), dim3(512), lds_mv, G.st, t, Q, N, G.nm, it == 0 ? 1 : 0, G.th, B_sys, G.z, G.po,
-                               G.pn, G.Ap, rz_cur, rz_nxt, G.ppap, cb);
+          launch_matvec3<false>(ctx, op, G, it == 0 ? 1 : 0, rz_cur, rz_nxt, cb);
         }
         hipLaunchKernelGGL(k3b_update, dim3(S), dim3(512), lds_up, G.st, N, G.nm, nmu, G.Dinv, G.pn, G.Ap, u + G.m0, G.r, G.z, (int)S,
                            rz_cur, A0inv ? rc_cur : nullptr, G.ppap, rz_nxt, G.prr);
@@ -3767,12 +3772,11 @@ int red_batch_iterate(lrbms3_ctx* ctx, const RbOp& op, RbGroup* g, int ng, int f
         ++G.it;
       }
     block = check;
-    double rr[4][32];
     for (int k = 0; k < ng; ++k) {
       RbGroup& G = g[k];
       if (G.done) continue;
       hipLaunchKernelGGL(k3b_reduce, dim3(1), dim3(256), 0, G.st, (int)S, G.nm, G.prr, G.scal + 48);
-      LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(rr[k], G.scal + 48, sizeof(double) * 32, hipMemcpyDeviceToHost, G.st));   // [3] residuals, [4] |b|^2
+      LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(G.look, G.scal + 48, sizeof(double) * 32, hipMemcpyDeviceToHost, G.st));   // [3] residuals, [4] |b|^2
     }
     LRBMS_LAUNCH_CHECK(ctx);
     all_done = true;
@@ -3782,7 +3786,7 @@ int red_batch_iterate(lrbms3_ctx* ctx, const RbOp& op, RbGroup* g, int ng, int f
       LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(G.st));
       G.rel = 0.0;
       for (int m = 0; m < G.nm; ++m) {
-        const double bbm = rr[k][16 + m], rm = bbm > 0.0 ? sqrt(rr[k][m] / bbm) : 0.0;
+        const double bbm = G.look[16 + m], rm = bbm > 0.0 ? sqrt(G.look[m] / bbm) : 0.0;
         if (!(rm == rm)) nan = true;
         G.rel = rm > G.rel ? rm : G.rel;
       }
@@ -3806,13 +3810,15 @@ int red_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nm
   // chip at little cost to each other.  Launches are interleaved iteration by iteration; residuals are looked at together.
   const int ng = (nmu + 15) / 16;
   const long gsize = reduced_batch_group_size(S, N);
-  RbGroup g[4];
+  RbGroup g[4];                       // (ahead of the fork: the groups' copies target it until the fork has left)
+  StreamFork fork(ctx);
+  if (int rc = fork.fork(st, ng)) return rc;
   const double* A0inv = ctx->user_pc_N == N ? ctx->user_pc : nullptr;
   for (int k = 0; k < ng; ++k) {
     RbGroup& G = g[k];
     G.m0 = 16 * k;
     G.nm = nmu - G.m0 < 16 ? nmu - G.m0 : 16;
-    G.st = k == 0 ? st : ctx->aux[k - 1];
+    G.st = fork.stream(k);
     G.done = false;
     G.rel = 0.0;
     G.it = G.last_it = 0;
@@ -3821,10 +3827,6 @@ int red_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nm
     G.Dinv = G.Amu + per_q;
     rb_group_vectors(G, G.Dinv + S * N * N, S, N);
     G.th = TB{};
-  }
-  if (ng > 1) {
-    LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
-    for (int k = 1; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(g[k].st, ctx->ev_fork, 0));
   }
   for (int k = 0; k < ng; ++k) {
     RbGroup& G = g[k];
@@ -3857,11 +3859,7 @@ int red_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nm
   bool nan = false;
   const RbOp op{Q, N, nmu, B_sys, nullptr, A0inv, u};
   if (int irc = red_batch_iterate(ctx, op, g, ng, check, check, rtol, max_iter, nan)) return irc;
-  if (ng > 1)
-    for (int k = 1; k < ng; ++k) {
-      LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[k - 1], g[k].st));
-      LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0));
-    }
+  if (int jrc = fork.join()) return jrc;
   int it = 0;
   double rel = 0.0;
   for (int k = 0; k < ng; ++k) {
@@ -4769,13 +4767,15 @@ int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, 
       return lrbms_fail(ctx, LRBMS_E_HIP, "rocsolver_dpotrs failed");
     A0inv = Id;
   }
-  RbGroup g[4];
+  RbGroup g[4];                        // (ahead of the fork: the groups' copies target it until the fork has left)
+  StreamFork fork(ctx);
+  if (int frc = fork.fork(st, ng)) return frc;
   const long gsize = red_euler_batch_group_size(S, N);
   for (int k = 0; k < ng; ++k) {
     RbGroup& G = g[k];
     G.m0 = 16 * k;
     G.nm = nmu - G.m0 < 16 ? nmu - G.m0 : 16;
-    G.st = k == 0 ? st : ctx->aux[k - 1];
+    G.st = fork.stream(k);
     G.done = false;
     G.rel = 0.0;
     G.it = G.last_it = 0;
@@ -4786,24 +4786,17 @@ int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, 
     for (int m = 0; m < G.nm; ++m)
       for (int q = 0; q < Q; ++q) G.th.v[m][q] = dt * theta[(G.m0 + m) * Q + q];      // dt folded into the table
   }
-  if (ng > 1) {
-    LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
-    for (int k = 1; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(g[k].st, ctx->ev_fork, 0));
-  }
   for (int k = 0; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipMemsetAsync(g[k].scal, 0, sizeof(double) * 80, g[k].st));
   const int check = A0inv ? 12 : 8;
-  const size_t lds_mv = sizeof(double) * (7 * N * 16 + 32 * 16), lds_mm = sizeof(double) * (7 * 32 * 16 + 4 * (N <= 16 ? 1 : 2) * 256 + 32 * 16);
   const size_t lds_si = sizeof(double) * (2 * N * 16 + 32 * 16);
-  const bool mfma_mv = ctx->opt_solve_valu == 0;
-  const MassOp3<true> mo{M_red};
   const CoarseB none{nullptr, nullptr, nullptr};
   bool nan = false, capped = false;
   long total_it = 0;
   double worst = 0.0;
-  int rc = LRBMS_OK;
-  for (int step = 0; step < nt && rc == LRBMS_OK && !nan && !capped; ++step) {
+  for (int step = 0; step < nt && !nan && !capped; ++step) {
     const double* uk = U + (long)step * rows * nmu;
     double* un = U + (long)(step + 1) * rows * nmu;
+    const RbOp op{Q, N, nmu, B_sys, M_red, A0inv, un};
     // ---- step start of every group, no look at the host: y = (M + dt A_m) u_k by the MASS matvec (first = 1, direction u_k
     // gathered into the group's z, no coarse correction), then k3b_step_init
     for (int k = 0; k < ng; ++k) {
@@ -4811,15 +4804,7 @@ int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, 
       const long vec = rows * G.nm;
       hipLaunchKernelGGL(k3b_gather, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, G.st, rows, G.nm,
                          nmu, uk + G.m0, G.z);
-      if (mfma_mv && N <= 16)
-        hipLaunchKernelGGL((k3b_matvec_mfma<1, true>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, 1, G.th, B_sys, G.z, G.po, G.pn, G.Ap,
-                           G.prz, G.prz, G.ppap, none, mo);
-      else if (mfma_mv)
-        hipLaunchKernelGGL((k3b_matvec_mfma<2, true>), dim3(S), dim3(256), lds_mm, G.st, t, Q, N, G.nm, 1, G.th, B_sys, G.z, G.po, G.pn, G.Ap,
-                           G.prz, G.prz, G.ppap, none, mo);
-      else
-        hipLaunchKernelGGL(k3b_matvec<true>, dim3(S), dim3(512), lds_mv, G.st, t, Q, N, G.nm, 1, G.th, B_sys, G.z, G.po, G.pn, G.Ap, G.prz,
-                           G.prz, G.ppap, none, mo);
+      launch_matvec3<true>(ctx, op, G, 1, G.prz, G.prz, none);
       hipLaunchKernelGGL(k3b_step_init, dim3(S), dim3(512), lds_si, G.st, N, G.nm, nmu, dt, M_red, uk + G.m0, K, rows, (long)(nt + 1) * K,
                          K ? phi_dev + ((long)G.m0 * (nt + 1) + step + 1) * K : nullptr, rhs, G.Ap, Dinv, un + G.m0, G.r, G.z, G.po,
                          G.prz, G.prr, G.ppap);
@@ -4836,9 +4821,7 @@ int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, 
       const int guess = (int)(0.8 * g[k].last_it);
       if (guess > block) block = guess;
     }
-    const RbOp op{Q, N, nmu, B_sys, M_red, A0inv, un};
-    rc = red_batch_iterate(ctx, op, g, ng, block, check, rtol, max_iter, nan);
-    if (rc != LRBMS_OK) break;
+    if (int rc = red_batch_iterate(ctx, op, g, ng, block, check, rtol, max_iter, nan)) return rc;
     int it = 0;
     for (int k = 0; k < ng; ++k) {
       RbGroup& G = g[k];
@@ -4849,14 +4832,7 @@ int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, 
     }
     total_it += it;                    // the iterations of the slowest group, summed over the steps
   }
-  if (rc != LRBMS_OK) {                // a HIP error between the fork and the join: drain the groups' streams before leaving
-    for (int k = 0; k < ng; ++k) (void)hipStreamSynchronize(g[k].st);
-    return rc;
-  }
-  for (int k = 1; k < ng; ++k) {
-    LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[k - 1], g[k].st));
-    LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0));
-  }
+  if (int jrc = fork.join()) return jrc;
   if (info) info[0] = (double)total_it, info[1] = worst;
   if (nan) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": NaN residual");
   if (capped) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": not converged");

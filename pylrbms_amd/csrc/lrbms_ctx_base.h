@@ -83,6 +83,48 @@ struct KScope {
   }
 };
 
+// RAII fork of ng <= 4 independent chains onto the caller's stream and the library's side streams (the batched reduced solvers,
+// 2D and 3D: one group of parameters per stream).  fork() makes the side streams wait for what the caller's stream holds, join()
+// makes the caller's stream wait for them.  Every EARLY return between the two (a failed HIP call) leaves through the destructor:
+// the group streams are drained -- their asynchronous copies target host memory of the frames that are being left -- and joined
+// into the caller's stream, which the fused pass and the next call share with them.
+struct StreamFork {
+  lrbms_ctx_base* ctx;
+  hipStream_t st = nullptr;
+  int ng = 0;
+  bool armed = false;
+  explicit StreamFork(lrbms_ctx_base* c) : ctx(c) {}
+  StreamFork(const StreamFork&) = delete;
+  StreamFork& operator=(const StreamFork&) = delete;
+  hipStream_t stream(int k) const { return k == 0 ? st : ctx->aux[k - 1]; }
+  int fork(hipStream_t s, int n) {
+    st = s;
+    ng = n;
+    armed = true;
+    if (ng > 1) {
+      LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
+      for (int k = 1; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(stream(k), ctx->ev_fork, 0));
+    }
+    return LRBMS_OK;
+  }
+  int join() {
+    for (int k = 1; k < ng; ++k) {
+      LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[k - 1], stream(k)));
+      LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0));
+    }
+    armed = false;
+    return LRBMS_OK;
+  }
+  ~StreamFork() {
+    if (!armed) return;
+    for (int k = 0; k < ng; ++k) (void)hipStreamSynchronize(stream(k));
+    for (int k = 1; k < ng; ++k) {
+      (void)hipEventRecord(ctx->ev_join[k - 1], stream(k));
+      (void)hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0);
+    }
+  }
+};
+
 // A ctx-owned device copy of count (at least one) elements of host; with host == nullptr the allocation is left uninitialised.
 template <typename T>
 int upload(lrbms_ctx_base* ctx, const T* host, long count, const T** dev) {

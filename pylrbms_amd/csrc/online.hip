@@ -2033,6 +2033,8 @@ __global__ __launch_bounds__(256) void k_bcg_init_src(long total, int nmu, int m
 // own [S][N][nm] array), r, z, p0, p1, y, two partial arrays, scalars
 // (sized for the widest group, 64 parameters)
 static long reduced_batch_group_size(long S, int N, int W) { return 6 * S * N * W + 2 * S * W + 4 * BMAX + 8 * BMAX; }
+// the group of reduced_batch_group_size and one more scalar array: |M u_k + dt b_m|^2 of the step
+static long pbe_group_size(long S, int N, int W) { return reduced_batch_group_size(S, N, W) + BMAX; }
 // parameters per group (= columns of the MFMA panel): calls of more than 16 parameters run panels of 32 -- every projected block
 // streamed by the panel matvec then serves 32 solves -- unless the VALU cross-check form is asked for (its kernels hold <= 16)
 static int reduced_batch_group_width(const lrbms_ctx* ctx, int nmu) {
@@ -2055,13 +2057,249 @@ __global__ __launch_bounds__(256) void k_bcg_scatter(long rows, int nm, int nmu,
 }
 }  // namespace
 
-// nmu <= 64 parameters per call in groups of <= 16, each group an independent CG on its own stream (the caller's and the
-// library's three side streams), launches interleaved iteration by iteration, residuals looked at together: a group's kernels
-// are S latency-bound workgroups, so the groups share the chip at little cost to each other (config 3: 6 100 mu-solves/s with
-// one group at a time, 8 700 with three in flight).  One preconditioner per call, read-only while the groups run: the prebuilt
-// one (lrbms_reduced_precond_use) or the inverse diagonal blocks + coarse level at the mean theta of the call.
-//
-// The group / iteration driver is shared with lrbms_reduced_solve_batch_src: K == 0 broadcasts rhs [S][N] to every column
+// =========================================================================================================
+// The group driver of the batched reduced solvers: lrbms_reduced_solve_batch(_src) and, with the MASS form of the matvec,
+// lrbms_reduced_implicit_euler_batch(_src).  nmu <= 64 parameters per call in groups of <= GW (BcgGroup), each group an
+// independent CG on its own stream (the caller's and the library's three side streams, StreamFork), launches interleaved
+// iteration by iteration, residuals looked at together (bcg_iterate): a group's kernels are S latency-bound workgroups, so the
+// groups share the chip at little cost to each other (config 3: 6 100 mu-solves/s with one group at a time, 8 700 with three in
+// flight).  One preconditioner per call, read-only while the groups run.  What a call can launch and with how much LDS is decided
+// once (BcgPlan); the two drivers below keep what differs: the preconditioner's source, the start kernels, the step loop, the
+// scatter and what goes into info.
+namespace {
+
+// One group of <= GW columns: its slice of the work array, its theta tables, its stream and state.
+struct BcgGroup {
+  int nm, m0, it, last_it;                              // last_it: the iterations of the previous time step
+  long total;                                           // (group 0) iterations of the slowest group, summed over the steps
+  ThetaBatch th;                                        // theta [m][8] of the group (panels of 16)
+  double thd[BMAX * 8];                                 // the same for the wide panels: copied to theta_dev
+  double *ug, *r, *z, *pin, *pout, *y, *partial, *partial2, *scal, *theta_dev, *ref2;
+  hipStream_t st;
+  bool done;
+  double rel;
+  double ref[BMAX];                                     // host: the squared reference norm of every column's stopping rule
+  double look[5 * BMAX];                                // host: rz, alpha, beta, rr | ref2 as the last look at the group copied them
+};
+
+// What the calls of one export launch: the form of the kernels, the k-steps of the panel matvec and the LDS of each kernel.
+struct BcgPlan {
+  int S, N, GW;
+  bool mass, use_mfma;                                  // use_mfma: the matrix-core forms (LRBMS_OPT_SOLVE_VALU forces the VALU forms)
+  int ksc_n;
+  size_t lds_mfma, lds_mv, lds_upd_mfma;
+};
+
+// What the iteration applies: sum_q th_qm B_q on the five slots, plus M_red on the self slot when it is given (the step operator
+// of the implicit Euler, dt folded into th); Dinv, A0inv: the preconditioner of the call (A0inv may be nullptr).
+struct BcgOp {
+  int Q;
+  const double *B_sys, *M_red, *Dinv, *A0inv;
+};
+
+#define LRBMS_PANEL_DISPATCH(X)                                                                                    \
+  do {                                                                                                             \
+    if (GW == 64) {                                                                                                \
+      if (ksc_n == 4) X(64, 4, 1); else if (ksc_n == 8) X(64, 8, 1); else if (ksc_n == 10) X(64, 10, 1); else if (ksc_n == 12) X(64, 12, 1); else X(64, 16, 1); \
+    } else {                                                                                                       \
+      if (ksc_n == 4) X(32, 4, 1); else if (ksc_n == 8) X(32, 8, 1); else if (ksc_n == 10) X(32, 10, 1); else if (ksc_n == 12) X(32, 12, 1); else X(32, 16, 1); \
+    }                                                                                                              \
+  } while (0)
+
+// the direction + matvec of one group and iteration: p_new = dir + beta p_old (first: p_new = dir), y = A p_new
+template <bool MASS>
+void bcg_matvec(lrbms_ctx* ctx, const BcgPlan& P, const BcgOp& op, BcgGroup& G, const double* dir, int first) {
+  const int S = P.S, N = P.N, Q = op.Q, GW = P.GW, ksc_n = P.ksc_n;
+  const long NM = (long)N * G.nm;
+  MassOp<MASS> mo;
+  if constexpr (MASS) mo.M = op.M_red;
+  if (P.use_mfma && GW > 16) {
+    KScope ks(ctx, MASS ? "k_bcg_matvec_panel<mass>" : "k_bcg_matvec_panel", G.st);      // (lrbms_kernel_timing: per-launch time)
+#define LRBMS_PANEL(NCV, KSV, CTV)                                                                                                  \
+  hipLaunchKernelGGL((k_bcg_matvec_panel<NCV, KSV, CTV, MASS>), dim3(S), dim3(64 * (NCV / 16 / CTV) * ((KSV + 3) / 4)), P.lds_mfma, G.st, S, ctx->nbr, \
+                     Q, N, G.nm, G.theta_dev, op.B_sys, dir, G.pin, G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo)
+    LRBMS_PANEL_DISPATCH(LRBMS_PANEL);
+#undef LRBMS_PANEL
+  } else if (P.use_mfma) {
+    hipLaunchKernelGGL((k_bcg_matvec_mfma<16, MASS>), dim3(S), dim3(256), P.lds_mfma, G.st, S, ctx->nbr, Q, N, G.nm, G.th, op.B_sys, dir, G.pin,
+                       G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo);
+  } else if (NM <= 768) {   // three outputs per thread: fewer registers, measurably faster for the usual batch of 16
+    hipLaunchKernelGGL((k_bcg_matvec<3, MASS>), dim3(S), dim3(256), P.lds_mv, G.st, S, ctx->nbr, Q, N, G.nm, G.th, op.B_sys, dir, G.pin,
+                       G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo);
+  } else {
+    hipLaunchKernelGGL((k_bcg_matvec<BCG_KMAX, MASS>), dim3(S), dim3(256), P.lds_mv, G.st, S, ctx->nbr, Q, N, G.nm, G.th, op.B_sys, dir, G.pin,
+                       G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo);
+  }
+}
+
+// more than the default 64 KiB of LDS for every matvec instantiation bcg_matvec<MASS> can launch under the plan
+template <bool MASS>
+int bcg_matvec_lds(lrbms_ctx* ctx, const BcgPlan& P) {
+  const int GW = P.GW, ksc_n = P.ksc_n;
+  if (P.use_mfma && P.lds_mfma > 64 * 1024) {
+    if (GW == 16) {
+      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec_mfma<16, MASS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_mfma));
+    } else {
+#define LRBMS_PANEL_ATTR(NCV, KSV, CTV) \
+  LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec_panel<NCV, KSV, CTV, MASS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_mfma))
+      LRBMS_PANEL_DISPATCH(LRBMS_PANEL_ATTR);
+#undef LRBMS_PANEL_ATTR
+    }
+  }
+  if (!P.use_mfma && P.lds_mv > 64 * 1024) {
+    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec<BCG_KMAX, MASS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_mv));
+    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec<3, MASS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_mv));
+  }
+  return LRBMS_OK;
+}
+#undef LRBMS_PANEL_DISPATCH
+
+// The plan of a call of groups of GW columns at basis size N (mass: the step operator M_red + dt A).  Refuses panels that do not
+// fit the LDS and raises the LDS limit of every kernel instantiation the call can launch.
+int bcg_plan(lrbms_ctx* ctx, const std::string& name, int N, int GW, bool mass, BcgPlan& P) {
+  const int kp = (N + 3) & ~3, ldb = N + ((4 - N % 8) + 8) % 8;
+  const size_t bs_lds = (size_t)(N + 1) * ldb > (size_t)N * 16 ? (size_t)(N + 1) * ldb : (size_t)N * 16;   // block, later the products
+  // panels of 16: the direction panels of the five slots in LDS (k_bcg_matvec_mfma); wider panels: in registers, two copies of
+  // the current block in LDS (k_bcg_matvec_panel), one theta row more in the mass form
+  const int ksc_n = N <= 16 ? 4 : N <= 32 ? 8 : N <= 40 ? 10 : N <= 48 ? 12 : 16;      // k-steps compiled into k_bcg_matvec_panel
+  const size_t lds_panel = sizeof(double) * (2 * ((size_t)(N + 1) * ldb + 16) + 2 * (size_t)4 * ksc_n * GW + (mass ? 6 : 5) * GW + 1);
+  P = BcgPlan{ctx->S, N, GW, mass, ctx->opt_solve_valu == 0, ksc_n,
+              GW == 16 ? sizeof(double) * ((size_t)5 * kp * 16 + bs_lds) : lds_panel,
+              sizeof(double) * (5 * (size_t)N * 16 + (size_t)N * N + 256), sizeof(double) * ((size_t)kp * GW + (size_t)2 * N * GW)};
+  if (P.use_mfma && P.lds_mfma > 160 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": panels exceed the LDS");
+  if (int rc = mass ? bcg_matvec_lds<true>(ctx, P) : bcg_matvec_lds<false>(ctx, P)) return rc;
+  if (P.use_mfma && P.lds_upd_mfma > 64 * 1024) {
+    if (GW == 64)
+      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_update_mfma<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_upd_mfma));
+    else
+      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_update_mfma<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_upd_mfma));
+  }
+  return LRBMS_OK;
+}
+
+// Group k of a call of nmu columns: its columns, its stream, its slice of gwork (reduced_batch_group_size doubles; pbe_group_size
+// in the mass form, ref2 behind theta_dev) and its theta tables scale * theta [m][q]; the mass form puts 1.0 at [m][Q] of the
+// wide panels' table, the coefficient of M_red.
+void bcg_group(BcgGroup& G, const BcgPlan& P, int k, int nmu, int Q, const double* theta, double scale, double* gwork, hipStream_t st) {
+  const long rows = (long)P.S * P.N;
+  const int GW = P.GW;
+  G.m0 = GW * k;
+  G.nm = nmu - G.m0 < GW ? nmu - G.m0 : GW;
+  G.st = st;
+  G.it = G.last_it = 0;
+  G.total = 0;
+  G.done = false;
+  G.rel = 0.0;
+  const long vec = rows * G.nm;
+  double* w = gwork + k * (P.mass ? pbe_group_size(P.S, P.N, GW) : reduced_batch_group_size(P.S, P.N, GW));
+  G.ug = w;                                             // (a single group iterates in the caller's array: the drivers point it there)
+  G.r = w + rows * GW;
+  G.z = G.r + vec;
+  G.pin = G.z + vec;
+  G.pout = G.pin + vec;
+  G.y = G.pout + vec;
+  G.partial = w + 6L * rows * GW;
+  G.partial2 = G.partial + (long)P.S * GW;
+  G.scal = G.partial2 + (long)P.S * GW;                 // rz, alpha, beta, rr (BMAX each)
+  G.theta_dev = G.scal + 4 * BMAX;                      // [BMAX][8]
+  G.ref2 = P.mass ? G.theta_dev + 8 * BMAX : nullptr;   // [BMAX]: |M u_k + dt b_m|^2 of the step
+  for (int m = 0; m < TBMAX; ++m)
+    for (int q = 0; q < 8; ++q) G.th.v[m * 8 + q] = (m < G.nm && q < Q) ? scale * theta[(G.m0 + m) * Q + q] : 0.0;
+  for (int m = 0; m < BMAX; ++m)
+    for (int q = 0; q < 8; ++q)
+      G.thd[m * 8 + q] = (m < G.nm && q < Q) ? scale * theta[(G.m0 + m) * Q + q] : (P.mass && m < G.nm && q == Q) ? 1.0 : 0.0;
+}
+
+// preconditioner + update of one group: z = M^-1 r (first: of the start residual), then rz, beta and the residual norms
+void bcg_update(const BcgPlan& P, const BcgOp& op, BcgGroup& G, int first) {
+  const int S = P.S, N = P.N, GW = P.GW;
+  const size_t lds_upd = sizeof(double) * 3 * (size_t)N * G.nm;
+  if (P.use_mfma && GW == 64)
+    hipLaunchKernelGGL(k_bcg_update_mfma<64>, dim3(S), dim3(1024), P.lds_upd_mfma, G.st, N, G.nm, op.Dinv, G.scal, first, G.ug, G.r,
+                       first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
+  else if (P.use_mfma && GW == 32)
+    hipLaunchKernelGGL(k_bcg_update_mfma<32>, dim3(S), dim3(512), P.lds_upd_mfma, G.st, N, G.nm, op.Dinv, G.scal, first, G.ug, G.r,
+                       first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
+  else if (P.use_mfma)
+    hipLaunchKernelGGL(k_bcg_update_mfma<16>, dim3(S), dim3(256), P.lds_upd_mfma, G.st, N, G.nm, op.Dinv, G.scal, first, G.ug, G.r,
+                       first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
+  else
+    hipLaunchKernelGGL(k_bcg_update, dim3(S), dim3(256), lds_upd, G.st, N, G.nm, op.Dinv, G.scal, first, G.ug, G.r,
+                       first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
+  if (op.A0inv)
+    hipLaunchKernelGGL(k_coarse_apply, dim3((S + 15) / 16, (G.nm + 15) / 16), dim3(1024), 0, G.st, S, N, G.nm, op.A0inv, G.r, G.z, G.partial);
+  hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, S, G.nm, G.partial, G.partial2, G.scal, first ? 0 : 2);
+}
+
+// The iteration loop of the batched reduced solvers from the state the start kernels left (G.it = 0; G.done set for a group that
+// has nothing to solve): matvec / reduce / update per group, launches interleaved iteration by iteration over the groups' streams,
+// a look at the residuals after first_block iterations and then after as many as the slowest group seems to need.  The residual
+// norms come back in scal [3]; their references are G.ref, which the caller filled (the stationary form: the start residuals) or
+// which come back with every look (the mass form: ref2, |M u_k + dt b_m|^2 of the step; a column with reference 0 counts as
+// converged).  A group leaves at rel <= rtol, at max_iter (honoured exactly) or on a NaN (nan set).
+int bcg_iterate(lrbms_ctx* ctx, const BcgPlan& P, const BcgOp& op, BcgGroup* g, int ng, int first_block, double rtol, int max_iter,
+                bool& nan) {
+  bool all_done = true;
+  for (int k = 0; k < ng; ++k) all_done &= g[k].done;
+  int block = first_block;                               // iterations until the next look at the residuals (see red_cg_run)
+  while (!all_done) {
+    for (int c = 0; c < block; ++c)
+      for (int k = 0; k < ng; ++k) {
+        BcgGroup& G = g[k];
+        if (G.done || G.it >= max_iter) continue;
+        const int first = G.it == 0 ? 1 : 0;
+        if (P.mass)
+          bcg_matvec<true>(ctx, P, op, G, G.z, first);
+        else
+          bcg_matvec<false>(ctx, P, op, G, G.z, first);
+        hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, P.S, G.nm, G.partial, (const double*)nullptr, G.scal, 1);
+        bcg_update(P, op, G, 0);
+        double* tmp = G.pin; G.pin = G.pout; G.pout = tmp;
+        ++G.it;
+      }
+    LRBMS_LAUNCH_CHECK(ctx);
+    for (int k = 0; k < ng; ++k)
+      if (!g[k].done) {                                  // (scal, theta_dev and ref2 are NOT adjacent: two copies)
+        LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(g[k].look, g[k].scal, sizeof(double) * 4 * BMAX, hipMemcpyDeviceToHost, g[k].st));
+        if (P.mass)
+          LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(g[k].look + 4 * BMAX, g[k].ref2, sizeof(double) * BMAX, hipMemcpyDeviceToHost, g[k].st));
+      }
+    all_done = true;
+    double need_max = 0.0;
+    for (int k = 0; k < ng; ++k) {
+      BcgGroup& G = g[k];
+      if (G.done) continue;
+      LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(G.st));
+      G.rel = 0.0;
+      for (int m = 0; m < G.nm; ++m) {
+        if (P.mass) G.ref[m] = G.look[4 * BMAX + m];
+        const double rm = G.ref[m] > 0.0 ? sqrt(G.look[3 * BMAX + m] / G.ref[m]) : 0.0;
+        if (!(rm == rm) || (P.mass && !(G.ref[m] == G.ref[m]))) nan = true;
+        G.rel = rm > G.rel ? rm : G.rel;
+      }
+      if (G.rel <= rtol || G.it >= max_iter || nan) {
+        G.done = true;
+        continue;
+      }
+      all_done = false;
+      // CG converges superlinearly, so the average rate so far overestimates what is left: aim a little short (a further
+      // look costs one host round trip, a wasted iteration three to four kernels)
+      double need = 10.0;
+      if (G.it > 0) {
+        const double rate = log(G.rel) / G.it;
+        if (rate < 0.0) need = 0.8 * (log(rtol) - log(G.rel)) / rate;
+      }
+      need_max = need > need_max ? need : need_max;
+    }
+    block = need_max < 2.0 ? 2 : need_max > 40.0 ? 40 : (int)need_max;
+  }
+  return LRBMS_OK;
+}
+
+}  // namespace
+
+// lrbms_reduced_solve_batch and lrbms_reduced_solve_batch_src: the prebuilt preconditioner (lrbms_reduced_precond_use) or the
+// inverse diagonal blocks + coarse level at the mean theta of the call.  K == 0 broadcasts rhs [S][N] to every column
 // (k_bcg_init); K >= 1 gives column m the right-hand side sum_j phi_dev[m][j] rhs[j] of rhs [K][S][N] (k_bcg_init_src).  The
 // start kernel is the only difference.  A column whose right-hand side is zero has r = z = p = 0, so rz, pAp and with them
 // alpha and beta stay 0 (k_bcg_reduce) and its relative residual counts as 0: it comes back as zeros beside the others.
@@ -2071,6 +2309,9 @@ static int reduced_solve_batch_drive(lrbms_ctx* ctx, int Q, int N, int nmu, cons
   const int S = ctx->S;
   const int GW = reduced_batch_group_width(ctx, nmu);
   const int ng = (nmu + GW - 1) / GW;
+  if (GW > 16 && Q > 4) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: more than 16 parameters per call need Q <= 4");
+  BcgPlan P;
+  if (int rc = bcg_plan(ctx, "reduced_solve_batch", N, GW, false, P)) return rc;
   const long per_q = (long)S * 5 * N * N;
   QVec mean;
   for (int q = 0; q < 8; ++q) mean.v[q] = 0.0;
@@ -2079,41 +2320,6 @@ static int reduced_solve_batch_drive(lrbms_ctx* ctx, int Q, int N, int nmu, cons
   double* Amu = work;                                   // blocks at the mean theta of the call (only the diagonal is inverted)
   double* Dinv = Amu + per_q;
   double* gwork = Dinv + (long)S * N * N;
-  const long gsize = reduced_batch_group_size(S, N, GW);
-  struct Group {
-    int nm, m0, it;
-    ThetaBatch th;
-    double thd[BMAX * 8];                               // theta [m][8] of the group, copied to the device for the wide panels
-    double *ug, *r, *z, *pin, *pout, *y, *partial, *partial2, *scal, *theta_dev;
-    hipStream_t st;
-    bool done;
-    double rel, rr0[BMAX];
-  } g[4];
-  for (int k = 0; k < ng; ++k) {
-    Group& G = g[k];
-    G.m0 = GW * k;
-    G.nm = nmu - G.m0 < GW ? nmu - G.m0 : GW;
-    G.st = k == 0 ? st : ctx->aux[k - 1];
-    G.it = 0;
-    G.done = false;
-    G.rel = 0.0;
-    const long vec = (long)S * N * G.nm;
-    double* w = gwork + k * gsize;
-    G.ug = ng == 1 ? u : w;                             // a single group solves straight into the caller's array
-    G.r = w + (long)S * N * GW;
-    G.z = G.r + vec;
-    G.pin = G.z + vec;
-    G.pout = G.pin + vec;
-    G.y = G.pout + vec;
-    G.partial = w + 6L * S * N * GW;
-    G.partial2 = G.partial + (long)S * GW;
-    G.scal = G.partial2 + (long)S * GW;                 // rz, alpha, beta, rr (BMAX each)
-    G.theta_dev = G.scal + 4 * BMAX;                    // [BMAX][8]
-    for (int m = 0; m < TBMAX; ++m)
-      for (int q = 0; q < 8; ++q) G.th.v[m * 8 + q] = (m < G.nm && q < Q) ? theta[(G.m0 + m) * Q + q] : 0.0;
-    for (int m = 0; m < BMAX; ++m)
-      for (int q = 0; q < 8; ++q) G.thd[m * 8 + q] = (m < G.nm && q < Q) ? theta[(G.m0 + m) * Q + q] : 0.0;
-  }
   // ---- the preconditioner of the call, on the caller's stream, before the groups fork
   const double* A0inv = nullptr;
   const double* pcD = nullptr;
@@ -2127,94 +2333,14 @@ static int reduced_solve_batch_drive(lrbms_ctx* ctx, int Q, int N, int nmu, cons
     LRBMS_LAUNCH_CHECK(ctx);
     if (int rc = coarse_setup(ctx, N, Amu, &A0inv, st)) return rc;
   }
-  // matrix-core form of the panel matvec and of the preconditioner (LRBMS_OPT_SOLVE_VALU forces the VALU form)
-  const int kp = (N + 3) & ~3, ldb = N + ((4 - N % 8) + 8) % 8;
-  const size_t bs_lds = (size_t)(N + 1) * ldb > (size_t)N * 16 ? (size_t)(N + 1) * ldb : (size_t)N * 16;   // block, later the products
-  // panels of 16: the direction panels of the five slots in LDS (k_bcg_matvec_mfma); wider panels: in registers, two copies of
-  // the current block in LDS (k_bcg_matvec_panel)
-  const int ksc_n = N <= 16 ? 4 : N <= 32 ? 8 : N <= 40 ? 10 : N <= 48 ? 12 : 16;      // k-steps compiled into k_bcg_matvec_panel
-  const size_t lds_panel = sizeof(double) * (2 * ((size_t)(N + 1) * ldb + 16) + 2 * (size_t)4 * ksc_n * GW + 5 * GW + 1);
-  if (GW > 16 && Q > 4) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: more than 16 parameters per call need Q <= 4");
-  const size_t lds_mfma = GW == 16 ? sizeof(double) * ((size_t)5 * kp * 16 + bs_lds) : lds_panel;
-  const bool use_mfma = ctx->opt_solve_valu == 0;
-  if (use_mfma && lds_mfma > 160 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_solve_batch: panels exceed the LDS");
-#define LRBMS_PANEL_DISPATCH(X)                                                                                    \
-  do {                                                                                                             \
-    if (GW == 64) {                                                                                                \
-      if (ksc_n == 4) X(64, 4, 1); else if (ksc_n == 8) X(64, 8, 1); else if (ksc_n == 10) X(64, 10, 1); else if (ksc_n == 12) X(64, 12, 1); else X(64, 16, 1); \
-    } else {                                                                                                       \
-      if (ksc_n == 4) X(32, 4, 1); else if (ksc_n == 8) X(32, 8, 1); else if (ksc_n == 10) X(32, 10, 1); else if (ksc_n == 12) X(32, 12, 1); else X(32, 16, 1); \
-    }                                                                                                              \
-  } while (0)
-  if (use_mfma && lds_mfma > 64 * 1024) {
-    if (GW == 16) {
-      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec_mfma<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mfma));
-    } else {
-#define LRBMS_PANEL_ATTR(NCV, KSV, CTV) \
-  LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec_panel<NCV, KSV, CTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mfma))
-      LRBMS_PANEL_DISPATCH(LRBMS_PANEL_ATTR);
-#undef LRBMS_PANEL_ATTR
-    }
-  }
-  const size_t lds_mv = sizeof(double) * (5 * (size_t)N * 16 + (size_t)N * N + 256);
-  if (!use_mfma && lds_mv > 64 * 1024)
-    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec<BCG_KMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mv));
-  const size_t lds_upd_mfma = sizeof(double) * ((size_t)kp * GW + (size_t)2 * N * GW);
-  if (use_mfma && lds_upd_mfma > 64 * 1024) {
-    if (GW == 64)
-      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_update_mfma<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_upd_mfma));
-    else
-      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_update_mfma<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_upd_mfma));
-  }
-  if (ng > 1) {
-    LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
-    for (int k = 1; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(g[k].st, ctx->ev_fork, 0));
-  }
-  auto join = [&]() -> int {                             // the side streams joined into the caller's
-    for (int k = 1; k < ng; ++k) {
-      LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[k - 1], g[k].st));
-      LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0));
-    }
-    return LRBMS_OK;
-  };
-  // every EARLY return below (a failed HIP call between the fork and the join) leaves through this guard: the group streams are
-  // drained -- their asynchronous copies target `host` in this stack frame -- and joined into the caller's stream, which the
-  // fused pass and the next call share with them
-  struct ExitGuard {
-    lrbms_ctx* ctx;
-    hipStream_t st;
-    hipStream_t gs[4];
-    int ng;
-    bool armed;
-    ~ExitGuard() {
-      if (!armed) return;
-      for (int k = 0; k < ng; ++k) (void)hipStreamSynchronize(gs[k]);
-      for (int k = 1; k < ng; ++k) {
-        (void)hipEventRecord(ctx->ev_join[k - 1], gs[k]);
-        (void)hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0);
-      }
-    }
-  } guard{ctx, st, {g[0].st, ng > 1 ? g[1].st : st, ng > 2 ? g[2].st : st, ng > 3 ? g[3].st : st}, ng, true};
-  auto update = [&](Group& G, int first) {
-    const size_t lds_upd = sizeof(double) * 3 * (size_t)N * G.nm;
-    if (use_mfma && GW == 64)
-      hipLaunchKernelGGL(k_bcg_update_mfma<64>, dim3(S), dim3(1024), lds_upd_mfma, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
-                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
-    else if (use_mfma && GW == 32)
-      hipLaunchKernelGGL(k_bcg_update_mfma<32>, dim3(S), dim3(512), lds_upd_mfma, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
-                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
-    else if (use_mfma)
-      hipLaunchKernelGGL(k_bcg_update_mfma<16>, dim3(S), dim3(256), lds_upd_mfma, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
-                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
-    else
-      hipLaunchKernelGGL(k_bcg_update, dim3(S), dim3(256), lds_upd, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
-                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
-    if (A0inv) hipLaunchKernelGGL(k_coarse_apply, dim3((S + 15) / 16, (G.nm + 15) / 16), dim3(1024), 0, G.st, S, N, G.nm, A0inv, G.r, G.z, G.partial);
-    hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, S, G.nm, G.partial, G.partial2, G.scal, first ? 0 : 2);
-  };
-  double host[4][4 * BMAX];
+  const BcgOp op{Q, B_sys, nullptr, Dinv, A0inv};
+  BcgGroup g[4];                                         // (ahead of the fork: the groups' copies target it until the fork has left)
+  StreamFork fork(ctx);
+  if (int rc = fork.fork(st, ng)) return rc;
   for (int k = 0; k < ng; ++k) {
-    Group& G = g[k];
+    BcgGroup& G = g[k];
+    bcg_group(G, P, k, nmu, Q, theta, 1.0, gwork, fork.stream(k));
+    if (ng == 1) G.ug = u;                               // a single group solves straight into the caller's array
     const long vec = (long)S * N * G.nm;
     if (GW > 16) LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(G.theta_dev, G.thd, sizeof(double) * 8 * BMAX, hipMemcpyHostToDevice, G.st));
     if (K == 0)
@@ -2223,83 +2349,21 @@ static int reduced_solve_batch_drive(lrbms_ctx* ctx, int Q, int N, int nmu, cons
     else
       hipLaunchKernelGGL(k_bcg_init_src, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, G.st, vec,
                          G.nm, G.m0, K, (long)S * N, phi_dev, rhs_red, G.ug, G.r);
-    update(G, 1);
-    LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host[k], G.scal, sizeof(double) * 4 * BMAX, hipMemcpyDeviceToHost, G.st));
+    bcg_update(P, op, G, 1);
+    LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(G.look, G.scal, sizeof(double) * 4 * BMAX, hipMemcpyDeviceToHost, G.st));
   }
   LRBMS_LAUNCH_CHECK(ctx);
-  bool all_done = true;
   for (int k = 0; k < ng; ++k) {
-    Group& G = g[k];
+    BcgGroup& G = g[k];
     LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(G.st));
-    bool all_zero = true;
+    G.done = true;                                       // zero right-hand side: x = 0 is the solution
     for (int m = 0; m < G.nm; ++m) {
-      G.rr0[m] = host[k][3 * BMAX + m];
-      all_zero &= G.rr0[m] == 0.0;
+      G.ref[m] = G.look[3 * BMAX + m];                   // the start residuals: the reference of the stopping rule
+      if (G.ref[m] != 0.0) G.done = false;
     }
-    G.done = all_zero;                                   // zero right-hand side: x = 0 is the solution
-    all_done &= G.done;
   }
-  int block = 10;                                        // iterations until the next look at the residuals (see red_cg_run)
-  int rc = LRBMS_OK;
-  while (!all_done) {
-    for (int c = 0; c < block; ++c)
-      for (int k = 0; k < ng; ++k) {
-        Group& G = g[k];
-        if (G.done || G.it >= max_iter) continue;
-        const int first = G.it == 0 ? 1 : 0;
-        const long NM = (long)N * G.nm;
-        if (use_mfma && GW > 16) {
-          KScope ks(ctx, "k_bcg_matvec_panel", G.st);      // (lrbms_kernel_timing: per-launch time, beside the <mass> form below)
-#define LRBMS_PANEL(NCV, KSV, CTV)                                                                                                  \
-  hipLaunchKernelGGL((k_bcg_matvec_panel<NCV, KSV, CTV>), dim3(S), dim3(64 * (NCV / 16 / CTV) * ((KSV + 3) / 4)), lds_mfma, G.st, S, ctx->nbr, Q, N, G.nm,   \
-                     G.theta_dev, B_sys, G.z, G.pin, G.scal + 2 * BMAX, first, G.pout, G.y, G.partial)
-          LRBMS_PANEL_DISPATCH(LRBMS_PANEL);
-#undef LRBMS_PANEL
-        }
-        else if (use_mfma)
-          hipLaunchKernelGGL(k_bcg_matvec_mfma<16>, dim3(S), dim3(256), lds_mfma, G.st, S, ctx->nbr, Q, N, G.nm, G.th, B_sys, G.z, G.pin,
-                             G.scal + 2 * BMAX, first, G.pout, G.y, G.partial);
-        else if (NM <= 768)   // three outputs per thread: fewer registers, measurably faster for the usual batch of 16
-          hipLaunchKernelGGL(k_bcg_matvec<3>, dim3(S), dim3(256), lds_mv, G.st, S, ctx->nbr, Q, N, G.nm, G.th, B_sys, G.z, G.pin,
-                             G.scal + 2 * BMAX, first, G.pout, G.y, G.partial);
-        else
-          hipLaunchKernelGGL(k_bcg_matvec<BCG_KMAX>, dim3(S), dim3(256), lds_mv, G.st, S, ctx->nbr, Q, N, G.nm, G.th, B_sys, G.z, G.pin,
-                             G.scal + 2 * BMAX, first, G.pout, G.y, G.partial);
-        hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, S, G.nm, G.partial, (const double*)nullptr, G.scal, 1);
-        update(G, 0);
-        double* tmp = G.pin; G.pin = G.pout; G.pout = tmp;
-        ++G.it;
-      }
-    LRBMS_LAUNCH_CHECK(ctx);
-    for (int k = 0; k < ng; ++k)
-      if (!g[k].done)
-        LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host[k], g[k].scal, sizeof(double) * 4 * BMAX, hipMemcpyDeviceToHost, g[k].st));
-    all_done = true;
-    double need_max = 0.0;
-    for (int k = 0; k < ng; ++k) {
-      Group& G = g[k];
-      if (G.done) continue;
-      LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(G.st));
-      G.rel = 0.0;
-      for (int m = 0; m < G.nm; ++m) {
-        const double rm = G.rr0[m] > 0.0 ? sqrt(host[k][3 * BMAX + m] / G.rr0[m]) : 0.0;
-        if (!(rm == rm)) rc = LRBMS_E_NOT_CONVERGED;
-        G.rel = rm > G.rel ? rm : G.rel;
-      }
-      if (G.rel <= rtol || G.it >= max_iter || rc != LRBMS_OK) {
-        G.done = true;
-        continue;
-      }
-      all_done = false;
-      // CG converges superlinearly, so the average rate so far overestimates what is left: aim a little short (a further
-      // look costs one host round trip, a wasted iteration three to four kernels)
-      const double rate = log(G.rel) / G.it;
-      double need = 10.0;
-      if (rate < 0.0) need = 0.8 * (log(rtol) - log(G.rel)) / rate;
-      need_max = need > need_max ? need : need_max;
-    }
-    block = need_max < 2.0 ? 2 : need_max > 40.0 ? 40 : (int)need_max;
-  }
+  bool nan = false;
+  if (int rc = bcg_iterate(ctx, P, op, g, ng, 10, rtol, max_iter, nan)) return rc;
   if (ng > 1)
     for (int k = 0; k < ng; ++k) {
       const long rows = (long)S * N;
@@ -2307,8 +2371,7 @@ static int reduced_solve_batch_drive(lrbms_ctx* ctx, int Q, int N, int nmu, cons
                          dim3(256), 0, g[k].st, rows, g[k].nm, nmu, g[k].ug, u + g[k].m0);
     }
   LRBMS_LAUNCH_CHECK(ctx);
-  if (int jrc = join()) return jrc;
-  guard.armed = false;
+  if (int rc = fork.join()) return rc;
   int it = 0;
   double rel = 0.0;
   for (int k = 0; k < ng; ++k) {
@@ -2316,7 +2379,7 @@ static int reduced_solve_batch_drive(lrbms_ctx* ctx, int Q, int N, int nmu, cons
     rel = g[k].rel > rel ? g[k].rel : rel;
   }
   if (info) { info[0] = it; info[1] = rel; }
-  if (rc != LRBMS_OK) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: NaN residual (system not SPD?)");
+  if (nan) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: NaN residual (system not SPD?)");
   if (rel > rtol) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "reduced_solve_batch: CG did not reach rtol");
   return LRBMS_OK;
 }
@@ -2350,11 +2413,11 @@ int launch_reduced_solve_batch_src(lrbms_ctx* ctx, int Q, int N, int K, int nmu,
 // per operand) per thread and step where every row is 16-byte aligned, a scalar loop otherwise
 // =========================================================================================================
 // Batched reduced implicit Euler: nmu <= 64 trajectories of (M_red + dt A(mu_m)) u_{k+1} = M_red u_k + dt b_m as ONE panel.
-// The groups, streams, fork / join and exit guard are those of reduced_solve_batch_drive; a loop over the time steps goes
-// around the iteration loop.  Per step and group: k_pbe_gather (x = u_k in the group's layout: the warm start), the MASS form
-// of the group's panel matvec with first = 1 and u_k as direction (y = (M + dt A_m) u_k), k_pbe_step_rhs (r = M u_k + dt b_m - y
-// and the partials of |M u_k + dt b_m|^2, the reference of the step's stopping rule), then the PCG of the stationary driver with
-// the MASS matvec.  The matvec reads Q (present slots) + 1 blocks per subdomain and iteration: M_red[s] is one more entry of the
+// Groups, plan, matvec / update launchers and iteration loop are those of the stationary solver (BcgGroup, BcgPlan, bcg_iterate
+// above); the driver below puts a loop over the time steps around bcg_iterate.  Per step and group: k_pbe_gather (x = u_k in the
+// group's layout: the warm start), the MASS form of the group's matvec with first = 1 and u_k as direction (y = (M + dt A_m) u_k),
+// k_pbe_step_rhs (r = M u_k + dt b_m - y and the partials of |M u_k + dt b_m|^2, the reference of the step's stopping rule), then
+// the shared PCG.  The matvec reads Q (present slots) + 1 blocks per subdomain and iteration: M_red[s] is one more entry of the
 // self slot's list, dt sits in the theta table.  One preconditioner per call: inverse diagonal blocks and coarse level of
 // M_red + dt sum_q mean(theta)_q B_q.  A preconditioner installed with lrbms_reduced_precond_use belongs to A and is not used.
 namespace {
@@ -2406,8 +2469,6 @@ __global__ __launch_bounds__(256) void k_pbe_step_rhs(int S, int N, int nm, int 
 
 }  // namespace
 
-// the group of reduced_batch_group_size and one more scalar array: |M u_k + dt b_m|^2 of the step
-static long pbe_group_size(long S, int N, int W) { return reduced_batch_group_size(S, N, W) + BMAX; }
 
 int64_t reduced_implicit_euler_batch_work_size(lrbms_ctx* ctx, int N, int nmu) {
   const long S = ctx->S;
@@ -2428,6 +2489,8 @@ static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, in
   const int S = ctx->S;
   const int GW = reduced_batch_group_width(ctx, nmu);
   const int ng = (nmu + GW - 1) / GW;
+  BcgPlan P;
+  if (int rc = bcg_plan(ctx, name, N, GW, true, P)) return rc;
   const long per_q = (long)S * 5 * N * N;
   const long rows = (long)S * N;
   QVec mean;                                             // dt * mean theta: the step operator the preconditioner is built for
@@ -2438,44 +2501,6 @@ static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, in
   double* Amu = work;
   double* Dinv = Amu + per_q;
   double* gwork = Dinv + (long)S * N * N;
-  const long gsize = pbe_group_size(S, N, GW);
-  struct Group {
-    int nm, m0, it, last_it;
-    long total;
-    ThetaBatch th;                                      // dt theta [m][q] (panels of 16)
-    double thd[BMAX * 8];                               // dt theta [m][q] and 1.0 at [m][Q]: the table of the wide panels
-    double *ug, *r, *z, *pin, *pout, *y, *partial, *partial2, *scal, *theta_dev, *ref2;
-    hipStream_t st;
-    bool done;
-    double rel;
-  } g[4];
-  for (int k = 0; k < ng; ++k) {
-    Group& G = g[k];
-    G.m0 = GW * k;
-    G.nm = nmu - G.m0 < GW ? nmu - G.m0 : GW;
-    G.st = k == 0 ? st : ctx->aux[k - 1];
-    G.it = G.last_it = 0;
-    G.total = 0;
-    G.done = false;
-    G.rel = 0.0;
-    const long vec = rows * G.nm;
-    double* w = gwork + k * gsize;
-    G.ug = w;                                           // (one group: set per step, it iterates in place in U[k + 1])
-    G.r = w + rows * GW;
-    G.z = G.r + vec;
-    G.pin = G.z + vec;
-    G.pout = G.pin + vec;
-    G.y = G.pout + vec;
-    G.partial = w + 6L * rows * GW;
-    G.partial2 = G.partial + (long)S * GW;
-    G.scal = G.partial2 + (long)S * GW;                 // rz, alpha, beta, rr (BMAX each)
-    G.theta_dev = G.scal + 4 * BMAX;                    // [BMAX][8]
-    G.ref2 = G.theta_dev + 8 * BMAX;                    // [BMAX]
-    for (int m = 0; m < TBMAX; ++m)
-      for (int q = 0; q < 8; ++q) G.th.v[m * 8 + q] = (m < G.nm && q < Q) ? dt * theta[(G.m0 + m) * Q + q] : 0.0;
-    for (int m = 0; m < BMAX; ++m)
-      for (int q = 0; q < 8; ++q) G.thd[m * 8 + q] = (m < G.nm && q < Q) ? dt * theta[(G.m0 + m) * Q + q] : (m < G.nm && q == Q) ? 1.0 : 0.0;
-  }
   // ---- the preconditioner of the call, on the caller's stream, before the groups fork
   const double* A0inv = nullptr;
   hipLaunchKernelGGL(k_assemble_mu_mass, dim3((unsigned)((per_q + 255) / 256 > 8192 ? 8192 : (per_q + 255) / 256)), dim3(256), 0, st,
@@ -2484,131 +2509,31 @@ static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, in
   if (int rc = launch_block_inverse(ctx, (int)S, N, Amu, Dinv, 5, 2, st)) return rc;
   LRBMS_LAUNCH_CHECK(ctx);
   if (int rc = coarse_setup(ctx, N, Amu, &A0inv, st)) return rc;
-  const int kp = (N + 3) & ~3, ldb = N + ((4 - N % 8) + 8) % 8;
-  const size_t bs_lds = (size_t)(N + 1) * ldb > (size_t)N * 16 ? (size_t)(N + 1) * ldb : (size_t)N * 16;
-  const int ksn = N <= 16 ? 4 : N <= 32 ? 8 : N <= 40 ? 10 : N <= 48 ? 12 : 16;        // the ksc_n ladder of reduced_solve_batch_drive
-  const size_t lds_panel = sizeof(double) * (2 * ((size_t)(N + 1) * ldb + 16) + 2 * (size_t)4 * ksn * GW + 6 * GW + 1);   // one theta row more
-  const size_t lds_mfma = GW == 16 ? sizeof(double) * ((size_t)5 * kp * 16 + bs_lds) : lds_panel;
-  const bool use_mfma = ctx->opt_solve_valu == 0;
-  if (use_mfma && lds_mfma > 160 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": panels exceed the LDS");
-#define LRBMS_PBE_DISPATCH(X)                                                                                      \
-  do {                                                                                                             \
-    if (GW == 64) {                                                                                                \
-      if (ksn == 4) X(64, 4); else if (ksn == 8) X(64, 8); else if (ksn == 10) X(64, 10); else if (ksn == 12) X(64, 12); else X(64, 16); \
-    } else {                                                                                                       \
-      if (ksn == 4) X(32, 4); else if (ksn == 8) X(32, 8); else if (ksn == 10) X(32, 10); else if (ksn == 12) X(32, 12); else X(32, 16); \
-    }                                                                                                              \
-  } while (0)
-  if (use_mfma && lds_mfma > 64 * 1024) {
-    if (GW == 16) {
-      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec_mfma<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mfma));
-    } else {
-#define LRBMS_PBE_ATTR(NCV, KSV) \
-  LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec_panel<NCV, KSV, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mfma))
-      LRBMS_PBE_DISPATCH(LRBMS_PBE_ATTR);
-#undef LRBMS_PBE_ATTR
-    }
-  }
-  const size_t lds_mv = sizeof(double) * (5 * (size_t)N * 16 + (size_t)N * N + 256);
-  if (!use_mfma && lds_mv > 64 * 1024) {
-    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec<BCG_KMAX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mv));
-    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_matvec<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mv));
-  }
-  const size_t lds_upd_mfma = sizeof(double) * ((size_t)kp * GW + (size_t)2 * N * GW);
-  if (use_mfma && lds_upd_mfma > 64 * 1024) {
-    if (GW == 64)
-      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_update_mfma<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_upd_mfma));
-    else
-      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_bcg_update_mfma<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_upd_mfma));
-  }
-  if (ng > 1) {
-    LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, st));
-    for (int k = 1; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(g[k].st, ctx->ev_fork, 0));
-  }
-  auto join = [&]() -> int {                             // the side streams joined into the caller's
-    for (int k = 1; k < ng; ++k) {
-      LRBMS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[k - 1], g[k].st));
-      LRBMS_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0));
-    }
-    return LRBMS_OK;
-  };
-  // every early return between the fork and the join leaves through this guard (see reduced_solve_batch_drive)
-  struct ExitGuard {
-    lrbms_ctx* ctx;
-    hipStream_t st;
-    hipStream_t gs[4];
-    int ng;
-    bool armed;
-    ~ExitGuard() {
-      if (!armed) return;
-      for (int k = 0; k < ng; ++k) (void)hipStreamSynchronize(gs[k]);
-      for (int k = 1; k < ng; ++k) {
-        (void)hipEventRecord(ctx->ev_join[k - 1], gs[k]);
-        (void)hipStreamWaitEvent(st, ctx->ev_join[k - 1], 0);
-      }
-    }
-  } guard{ctx, st, {g[0].st, ng > 1 ? g[1].st : st, ng > 2 ? g[2].st : st, ng > 3 ? g[3].st : st}, ng, true};
-  // the step operator applied to the direction z (+ beta p_old): the MASS form of the matvec reduced_solve_batch_drive would take
-  auto matvec = [&](Group& G, const double* zdir, int first) {
-    const long NM = (long)N * G.nm;
-    const MassOp<true> mo{M_red};
-    if (use_mfma && GW > 16) {
-      KScope ks(ctx, "k_bcg_matvec_panel<mass>", G.st);
-#define LRBMS_PBE_PANEL(NCV, KSV)                                                                                                    \
-  hipLaunchKernelGGL((k_bcg_matvec_panel<NCV, KSV, 1, true>), dim3(S), dim3(64 * (NCV / 16) * ((KSV + 3) / 4)), lds_mfma, G.st, S, ctx->nbr, Q, N, G.nm, \
-                     G.theta_dev, B_sys, zdir, G.pin, G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo)
-      LRBMS_PBE_DISPATCH(LRBMS_PBE_PANEL);
-#undef LRBMS_PBE_PANEL
-    } else if (use_mfma) {
-      hipLaunchKernelGGL((k_bcg_matvec_mfma<16, true>), dim3(S), dim3(256), lds_mfma, G.st, S, ctx->nbr, Q, N, G.nm, G.th, B_sys, zdir, G.pin,
-                         G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo);
-    } else if (NM <= 768) {
-      hipLaunchKernelGGL((k_bcg_matvec<3, true>), dim3(S), dim3(256), lds_mv, G.st, S, ctx->nbr, Q, N, G.nm, G.th, B_sys, zdir, G.pin,
-                         G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo);
-    } else {
-      hipLaunchKernelGGL((k_bcg_matvec<BCG_KMAX, true>), dim3(S), dim3(256), lds_mv, G.st, S, ctx->nbr, Q, N, G.nm, G.th, B_sys, zdir, G.pin,
-                         G.scal + 2 * BMAX, first, G.pout, G.y, G.partial, mo);
-    }
-  };
-  auto update = [&](Group& G, int first) {
-    const size_t lds_upd = sizeof(double) * 3 * (size_t)N * G.nm;
-    if (use_mfma && GW == 64)
-      hipLaunchKernelGGL(k_bcg_update_mfma<64>, dim3(S), dim3(1024), lds_upd_mfma, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
-                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
-    else if (use_mfma && GW == 32)
-      hipLaunchKernelGGL(k_bcg_update_mfma<32>, dim3(S), dim3(512), lds_upd_mfma, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
-                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
-    else if (use_mfma)
-      hipLaunchKernelGGL(k_bcg_update_mfma<16>, dim3(S), dim3(256), lds_upd_mfma, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
-                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
-    else
-      hipLaunchKernelGGL(k_bcg_update, dim3(S), dim3(256), lds_upd, G.st, N, G.nm, Dinv, G.scal, first, G.ug, G.r,
-                         first ? G.pin : G.pout, G.y, G.z, G.partial, G.partial2);
-    if (A0inv) hipLaunchKernelGGL(k_coarse_apply, dim3((S + 15) / 16, (G.nm + 15) / 16), dim3(1024), 0, G.st, S, N, G.nm, A0inv, G.r, G.z, G.partial);
-    hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, S, G.nm, G.partial, G.partial2, G.scal, first ? 0 : 2);
-  };
+  const BcgOp op{Q, B_sys, M_red, Dinv, A0inv};
+  BcgGroup g[4];                                         // (ahead of the fork: the groups' copies target it until the fork has left)
+  StreamFork fork(ctx);
+  if (int rc = fork.fork(st, ng)) return rc;
+  for (int k = 0; k < ng; ++k) bcg_group(g[k], P, k, nmu, Q, theta, dt, gwork, fork.stream(k));      // dt folded into the tables
   const size_t lds_rhs = sizeof(double) * 2 * (size_t)N * GW;
-  double host[4][5 * BMAX];                              // rz, alpha, beta, rr | ref2: scal, theta_dev and ref2 are NOT adjacent, two copies
-  int rc = LRBMS_OK;
+  bool nan = false, capped = false;
   double worst = 0.0;
-  bool capped = false;
-  for (int step = 0; step < nt && rc == LRBMS_OK && !capped; ++step) {
+  for (int step = 0; step < nt && !nan && !capped; ++step) {
     const double* uk = U + (long)step * rows * nmu;
     double* un = U + (long)(step + 1) * rows * nmu;
     // ---- step start: every group, no look at the host
     for (int k = 0; k < ng; ++k) {
-      Group& G = g[k];
+      BcgGroup& G = g[k];
       const long vec = rows * G.nm;
       const unsigned nb = (unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256);
-      if (ng == 1) G.ug = un;
+      if (ng == 1) G.ug = un;                            // a single group iterates in place in U[k + 1]
       if (step == 0 && GW > 16)
         LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(G.theta_dev, G.thd, sizeof(double) * 8 * BMAX, hipMemcpyHostToDevice, G.st));
       hipLaunchKernelGGL(k_pbe_gather, dim3(nb), dim3(256), 0, G.st, rows, G.nm, nmu, uk + G.m0, G.ug);
-      matvec(G, G.ug, 1);
+      bcg_matvec<true>(ctx, P, op, G, G.ug, 1);
       hipLaunchKernelGGL(k_pbe_step_rhs, dim3(S), dim3(256), lds_rhs, G.st, S, N, G.nm, G.m0, dt, M_red, G.ug, K,
                          K ? phi_dev + (long)(step + 1) * K : nullptr, (long)(nt + 1) * K, rhs, G.y, G.r, G.partial);
       hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, S, G.nm, G.partial, (const double*)nullptr, G.ref2, 0);
-      update(G, 1);
+      bcg_update(P, op, G, 1);
       G.it = 0;
       G.done = false;
     }
@@ -2620,54 +2545,10 @@ static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, in
       if (step > 0 && guess > block) block = guess;
     }
     if (step > 0 && block > 40) block = 40;
-    bool all_done = false;
-    while (!all_done) {
-      for (int c = 0; c < block; ++c)
-        for (int k = 0; k < ng; ++k) {
-          Group& G = g[k];
-          if (G.done || G.it >= max_iter) continue;
-          matvec(G, G.z, G.it == 0 ? 1 : 0);
-          hipLaunchKernelGGL(k_bcg_reduce, dim3((G.nm + 15) / 16), dim3(1024), 0, G.st, S, G.nm, G.partial, (const double*)nullptr, G.scal, 1);
-          update(G, 0);
-          double* tmp = G.pin; G.pin = G.pout; G.pout = tmp;
-          ++G.it;
-        }
-      LRBMS_LAUNCH_CHECK(ctx);
-      for (int k = 0; k < ng; ++k)
-        if (!g[k].done) {
-          LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host[k], g[k].scal, sizeof(double) * 4 * BMAX, hipMemcpyDeviceToHost, g[k].st));
-          LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host[k] + 4 * BMAX, g[k].ref2, sizeof(double) * BMAX, hipMemcpyDeviceToHost, g[k].st));
-        }
-      all_done = true;
-      double need_max = 0.0;
-      for (int k = 0; k < ng; ++k) {
-        Group& G = g[k];
-        if (G.done) continue;
-        LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(G.st));
-        G.rel = 0.0;
-        for (int m = 0; m < G.nm; ++m) {
-          const double ref2 = host[k][4 * BMAX + m];
-          const double rm = ref2 > 0.0 ? sqrt(host[k][3 * BMAX + m] / ref2) : 0.0;     // zero right-hand side: u_{k+1} = u_k
-          if (!(rm == rm) || !(ref2 == ref2)) rc = LRBMS_E_NOT_CONVERGED;
-          G.rel = rm > G.rel ? rm : G.rel;
-        }
-        if (G.rel <= rtol || G.it >= max_iter || rc != LRBMS_OK) {
-          G.done = true;
-          continue;
-        }
-        all_done = false;
-        double need = 10.0;
-        if (G.it > 0) {
-          const double rate = log(G.rel) / G.it;          // (relative to |rhs|, as in red_cg_run: aim a little short)
-          if (rate < 0.0) need = 0.8 * (log(rtol) - log(G.rel)) / rate;
-        }
-        need_max = need > need_max ? need : need_max;
-      }
-      block = need_max < 2.0 ? 2 : need_max > 40.0 ? 40 : (int)need_max;
-    }
+    if (int rc = bcg_iterate(ctx, P, op, g, ng, block, rtol, max_iter, nan)) return rc;
     int it = 0;
     for (int k = 0; k < ng; ++k) {
-      Group& G = g[k];
+      BcgGroup& G = g[k];
       G.last_it = G.it;
       it = G.it > it ? G.it : it;
       worst = G.rel > worst ? G.rel : worst;
@@ -2681,10 +2562,9 @@ static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, in
     g[0].total += it;                                    // the iterations of the slowest group, summed over the steps
     LRBMS_LAUNCH_CHECK(ctx);
   }
-  if (int jrc = join()) return jrc;
-  guard.armed = false;
+  if (int rc = fork.join()) return rc;
   if (info) { info[0] = (double)g[0].total; info[1] = worst; }
-  if (rc != LRBMS_OK) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual (system not SPD?)");
+  if (nan) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual (system not SPD?)");
   if (capped) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": CG did not reach rtol");
   return LRBMS_OK;
 }
