@@ -137,7 +137,13 @@ int lrbms_assemble_swipdg(lrbms_ctx* ctx, int32_t Q, const double* lam, double* 
 
 /* K5 + scalars: replaces make_l2_volume_vector_functional (block_swipdg.py:518-521), apply_l2_product,
  * min_diffusion_eigenvalue (:776-783).
- *   f_smp [S][n_T][f_stride], lhat [S][n_T][lhat_stride]  ->  b [S][n], f2 [S] = ||f||^2_{L2(Omega_ii)}, ceps [S] */
+ *   f_smp [S][n_T][f_stride], lhat [S][n_T][lhat_stride]  ->  b [S][n], f2 [S] = ||f||^2_{L2(Omega_ii)}, ceps [S]
+ * Lifetime: the context registers the address of `b` (lrbms_assembled_arrays), and with LRBMS_OPT_SIDE_TABLES 1, the default,
+ * this call and lrbms_assemble_products READ the b, ebar, Aab and Bbb the context assembled before (they build the side tables of
+ * the fused pass from them, on `stream`).  Registered arrays must therefore stay allocated until the register drops them
+ * (lrbms_assembled_arrays says when) or the next lrbms_mesh_upload.  Under LRBMS_OPT_SIDE_TABLES 0 the exports read nothing of an
+ * earlier call and the passes trust no registered address.  The call may be repeated with other `b` arrays (one load vector per source component): the tables the passes use stay with
+ * the b they were built from. */
 int lrbms_assemble_rhs(lrbms_ctx* ctx, const double* f_smp, const double* lhat, double* b, double* f2, double* ceps,
                        void* stream);
 
@@ -155,10 +161,21 @@ int lrbms_assemble_rhs(lrbms_ctx* ctx, const double* f_smp, const double* lhat, 
  *                                          singular blocks (rank <= 2: three RT0 functions at one point of the plane): such a
  *                                          quadrature needs LRBMS_OPT_F2_FORM 1, which does not factor Bbb and matches the oracle
  *                                          (the Python Engine selects it; rules with positive weights at >= 3 points that are not
- *                                          collinear give SPD blocks) */
+ *                                          collinear give SPD blocks)
+ * Lifetime: as for lrbms_assemble_rhs -- with LRBMS_OPT_SIDE_TABLES 1 this call reads the `b` an earlier lrbms_assemble_rhs of
+ * this context wrote, and later assembly calls read ebar, Aab and Bbb. */
 int lrbms_assemble_products(lrbms_ctx* ctx, int32_t Q, const double* theta_bar, const double* lam, const double* lam_df,
                             const double* lbar, const double* lhat, double* P_diag, double* ebar, double* caa, double* Aab,
                             double* Bbb, void* stream);
+
+/* The register behind LRBMS_OPT_SIDE_TABLES: the addresses of the arrays of one kind (0 Bbb, 1 Aab, 2 b, 3 ebar) the assembly
+ * exports of this context wrote and the context still remembers -- the last 32 load vectors b, the last 4 of the other kinds,
+ * and whatever its age the array the kept tables were built from; oldest first.  Writes up to `cap` addresses to `out` and returns
+ * the number registered (-1: bad argument).  An address is dropped when it is the oldest beyond those counts, and all are dropped
+ * by lrbms_mesh_upload.  A fused pass that is handed a REGISTERED address takes the array for the one the export wrote: while an
+ * address is registered its array must stay allocated, and the address must not come back as another array (a freed block the
+ * allocator hands out again).  The Python binding holds a reference to exactly the registered arrays. */
+int32_t lrbms_assembled_arrays(lrbms_ctx* ctx, int32_t kind, const double** out, int32_t cap);
 
 /* K8 (assembly half): coefficient rows of the RT0 diffusive-flux reconstruction
  * (RS2017_apply_diffusive_flux_reconstruction_in_neighborhood, block_swipdg.py:165-169).
@@ -281,7 +298,17 @@ void* lrbms_ctx_aux_stream(lrbms_ctx* ctx, int32_t i);
  *                              per-element factor table fits in LDS; 1: the R~^T B R~ form k_f2 for every shape (cross-check:
  *                              G_bb and G_rdd differ at rounding level, every other output is the same bits); 2: k_f2g with
  *                              the producers that own one column per lane and half (what odd Q N runs in form 0 as well; the
- *                              cross-check of the column-pair producers of form 0: every output is the same bits) */
+ *                              cross-check of the column-pair producers of form 0: every output is the same bits)
+ *   LRBMS_OPT_SIDE_TABLES      1 (default): the context keeps the basis-independent tables of the fused pass -- the side-face records
+ *                              and Ksc / M_ab tables of the thin side kernels, and W' of k_f1w -- from one pass to the next.  The assembly
+ *                              exports build them, and a pass reuses them only for the very arrays (b, ebar, Aab, Bbb) they were
+ *                              built from, as long as each is an array an assembly export of this context wrote (the register of
+ *                              lrbms_assembled_arrays) and has not been written by one since; for any other array they are
+ *                              rebuilt in that pass.  The exports read arrays of earlier assembly calls for this: see the lifetime
+ *                              note at lrbms_assemble_rhs.  0: rebuilt in every pass (the same bits), and the exports read
+ *                              nothing of an earlier call.  0 is the safe setting for a caller that modifies assembled arrays in place by other
+ *                              means than the assembly exports (the library cannot see such a write) or frees them between
+ *                              assembly calls */
 #define LRBMS_OPT_STREAMS 3
 #define LRBMS_OPT_F1_KSPLIT 4
 #define LRBMS_OPT_F1_FORM 5
@@ -290,6 +317,7 @@ void* lrbms_ctx_aux_stream(lrbms_ctx* ctx, int32_t i);
 #define LRBMS_OPT_ESTIMATE_VALU 8
 #define LRBMS_OPT_PREP_LDS 10
 #define LRBMS_OPT_F2_FORM 11
+#define LRBMS_OPT_SIDE_TABLES 12
 int lrbms_ctx_set_option(lrbms_ctx* ctx, int32_t option, int32_t value);
 
 /* LRBMS_OPT_OSWALD_VERTEX_PATCH on sharded grids: nbr_diag [S][4] (host) = index into the S_ext slabs of the diagonal neighbour

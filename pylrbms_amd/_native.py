@@ -85,6 +85,7 @@ SIGNATURES = {
     'lrbms_reduced_time_residual_work_size': (c_i64, [c_vp, c_i32]),
     'lrbms_reduced_time_residual': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'lrbms_assemble_source_gram': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    'lrbms_assembled_arrays': (c_i32, [c_vp, c_i32, ctypes.POINTER(c_vp), c_i32]),
     'lrbms_fom_implicit_euler_src': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                     c_dbl, c_i32, _P_DBL, c_vp]),
     'lrbms_reduced_implicit_euler_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -246,7 +247,8 @@ class NativeContext(ContextBase):
     OPTIONS = {'oswald_zero_on_subdomain_boundary': 1, 'accumulate_coupling_across_q': 2, 'oswald_vertex_patch': 9, 'prep_lds': 10,
                # launch policy (no numerical convention): the library reads no environment variable
                'streams': 3, 'f1_ksplit': 4, 'f1_form': 5, 'coarse': 6, 'solve_valu': 7, 'estimate_valu': 8,
-               'f2_form': 11}      # f2_form: 0 Gram form (column-pair producers), 1 product form k_f2, 2 Gram form with one-column producers
+               'f2_form': 11,      # f2_form: 0 Gram form (column-pair producers), 1 product form k_f2, 2 Gram form with one-column producers
+               'side_tables': 12}  # 1: basis-independent tables of the pass kept between passes; 0: rebuilt in every pass (arrays modified in place)
     S = S_ext = None
     _keep = None
 
@@ -277,6 +279,7 @@ class NativeContext(ContextBase):
         rc = self.lib.lrbms_mesh_upload(self.handle, ctypes.byref(d), S, S_ext, _i32p(nb))
         self._keep = (arrs, nb)
         self._check(rc, 'lrbms_mesh_upload')
+        self._pins = {}                 # (the upload has emptied the context's register of assembled arrays)
 
     # ------------------------------------------------------------------ assembly
     def set_quadrature(self, spec):
@@ -301,24 +304,52 @@ class NativeContext(ContextBase):
         self._check(rc, 'lrbms_assemble_swipdg')
         return A_diag, A_cpl
 
-    def assemble_rhs(self, f_smp, lhat):
+    def _out(self, out, shapes):
+        """The output tensors of an assembly export: fresh ones, or ``out`` (written in place) after a shape check."""
+        if out is None:
+            return tuple(self.empty(*shape) for shape in shapes)
+        assert len(out) == len(shapes)
+        for x, shape in zip(out, shapes):
+            self._ptr(x, shape, 'out')
+        return tuple(out)
+
+    def _pin_assembled(self, written):
+        """Hold a reference to the arrays an assembly export has just written (``written``: kind of ``lrbms_assembled_arrays`` ->
+        tensor) and let go of every array the context's register has dropped: pins and register hold the same addresses."""
+        pins = self.__dict__.setdefault('_pins', {})
+        for kind, x in written.items():
+            pins[(kind, x.data_ptr())] = x
+        cap = 64
+        buf = (c_vp * cap)()
+        live = set()
+        for kind in range(4):
+            n = self.lib.lrbms_assembled_arrays(self.handle, kind, buf, cap)
+            if n < 0 or n > cap:
+                raise NativeError('lrbms_assembled_arrays: {}'.format(n))
+            live.update((kind, int(buf[i] or 0)) for i in range(n))
+        for key in [k for k in pins if k not in live]:
+            del pins[key]
+
+    def assemble_rhs(self, f_smp, lhat, out=None):
+        """``out``: (b, f2, ceps) of an earlier call, re-assembled in place.  The context keeps tables derived from the
+        assembled arrays between fused passes (option ``side_tables``) and registers their addresses; the binding holds a
+        reference to exactly the registered arrays (``_pin_assembled``), so that a registered address cannot pass to another
+        tensor.  Arrays modified by other means than these calls need ``side_tables`` 0."""
         qd = self._quad()
-        b, f2, ceps = self.empty(self.S, self.n), self.empty(self.S), self.empty(self.S)
+        b, f2, ceps = self._out(out, [(self.S, self.n), (self.S,), (self.S,)])
         rc = self.lib.lrbms_assemble_rhs(self.handle, self._ptr(f_smp, (self.S, self.n_T, qd.f_stride), 'f_smp'),
                                          self._ptr(lhat, (self.S, self.n_T, qd.lhat_stride), 'lhat'), c_vp(b.data_ptr()),
                                          c_vp(f2.data_ptr()), c_vp(ceps.data_ptr()), self._stream())
         self._check(rc, 'lrbms_assemble_rhs')
+        self._pin_assembled({2: b})
         return b, f2, ceps
 
-    def assemble_products(self, theta_bar, lam, lam_df, lbar, lhat):
+    def assemble_products(self, theta_bar, lam, lam_df, lbar, lhat, out=None):
         Q, qd = lam.shape[0], self._quad()
         th = np.ascontiguousarray(theta_bar, dtype=np.float64)
         assert th.shape == (Q,)
-        P_diag = self.empty(self.S, self.n_T, 4, 9)
-        ebar = self.empty(self.S, self.n_T)
-        caa = self.empty(Q, Q, self.S, self.n_T)
-        Aab = self.empty(Q, self.S, self.n_T, 3, 3)
-        Bbb = self.empty(self.S, self.n_T, 3, 3)
+        P_diag, ebar, caa, Aab, Bbb = self._out(out, [(self.S, self.n_T, 4, 9), (self.S, self.n_T), (Q, Q, self.S, self.n_T),
+                                                      (Q, self.S, self.n_T, 3, 3), (self.S, self.n_T, 3, 3)])
         rc = self.lib.lrbms_assemble_products(
             self.handle, Q, _dblp(th), self._ptr(lam, (Q, self.S_ext, self.n_T, qd.lam_stride), 'lam'),
             self._ptr(lam_df, (Q, self.S, self.n_T, qd.lamdf_stride), 'lam_df'),
@@ -326,6 +357,7 @@ class NativeContext(ContextBase):
             c_vp(P_diag.data_ptr()), c_vp(ebar.data_ptr()), c_vp(caa.data_ptr()), c_vp(Aab.data_ptr()),
             c_vp(Bbb.data_ptr()), self._stream())
         self._check(rc, 'lrbms_assemble_products')
+        self._pin_assembled({0: Bbb, 1: Aab, 3: ebar})
         return P_diag, ebar, caa, Aab, Bbb
 
     def assemble_flux(self, lam):

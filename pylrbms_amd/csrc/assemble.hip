@@ -502,7 +502,8 @@ int launch_assemble_rhs(lrbms_ctx* ctx, const double* f_smp, const double* lhat,
   if (!ctx->qdev) return lrbms_fail(ctx, LRBMS_E_STATE, "quadrature not set (lrbms_set_quadrature)");
   hipLaunchKernelGGL(k_assemble_rhs, dim3(ctx->S), dim3(256), 0, st, ctx->t, ctx->qdev, f_smp, lhat, b, f2, ceps);
   LRBMS_LAUNCH_CHECK(ctx);
-  return LRBMS_OK;
+  note_assembled(ctx, lrbms_ctx::SRC_B, b);
+  return side_tables_after_assembly(ctx, true, st);
 }
 
 int launch_assemble_products(lrbms_ctx* ctx, int Q, const double* theta_bar, const double* lam, const double* lam_df,
@@ -515,7 +516,12 @@ int launch_assemble_products(lrbms_ctx* ctx, int Q, const double* theta_bar, con
   hipLaunchKernelGGL(k_assemble_products, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ctx->t, ctx->qdev, ctx->S,
                      ctx->S_ext, ctx->nbr, Q, tb, lam, lam_df, lbar, lhat, P_diag, ebar, caa, Aab, Bbb);
   LRBMS_LAUNCH_CHECK(ctx);
+  note_assembled(ctx, lrbms_ctx::SRC_BBB, Bbb);
+  note_assembled(ctx, lrbms_ctx::SRC_AAB, Aab);
+  note_assembled(ctx, lrbms_ctx::SRC_EBAR, ebar);
+  ctx->asm_Q = Q;
   // the rank-2 factors of the df_ab blocks (k_f1w), an assembled quantity: kept by the context, tagged with the Aab they belong to
+  // and the generation of that array (a pass handed the same array after it was written again by other means rebuilds them)
   const long need = (long)Q * ctx->S * ctx->t.nT * 6;
   if (ctx->wab_cap < need) {
     if (ctx->wab) LRBMS_HIP_CHECK(ctx, hipFree(ctx->wab));
@@ -528,7 +534,8 @@ int launch_assemble_products(lrbms_ctx* ctx, int Q, const double* theta_bar, con
   if (int rc = launch_wab(ctx, Q, Aab, ctx->wab, st)) return rc;
   ctx->wab_src = Aab;
   ctx->wab_Q = Q;
-  return LRBMS_OK;
+  ctx->wab_gen = asm_gen_of(ctx, lrbms_ctx::SRC_AAB, Aab);
+  return side_tables_after_assembly(ctx, false, st);
 }
 
 int launch_assemble_flux(lrbms_ctx* ctx, int Q, const double* lam, double* F, hipStream_t st) {

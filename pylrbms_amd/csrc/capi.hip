@@ -199,6 +199,7 @@ int lrbms_ctx_destroy(lrbms_ctx* ctx) {
   if (ctx->ksp_ticket) (void)hipFree(ctx->ksp_ticket);
   if (ctx->subset) (void)hipFree(ctx->subset);
   if (ctx->wab) (void)hipFree(ctx->wab);
+  if (ctx->stab) (void)hipFree(ctx->stab);
   if (ctx->src_phi) (void)hipFree(ctx->src_phi);
   lrbms_ctx_base_release(ctx);
   if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
@@ -238,6 +239,7 @@ int lrbms_ctx_set_option(lrbms_ctx* ctx, int32_t option, int32_t value) {
     case LRBMS_OPT_SOLVE_VALU: ctx->opt_solve_valu = value; break;
     case LRBMS_OPT_ESTIMATE_VALU: ctx->opt_estimate_valu = value; break;
     case LRBMS_OPT_PREP_LDS: ctx->opt_prep_lds = value; break;
+    case LRBMS_OPT_SIDE_TABLES: ctx->opt_side_tables = value; break;
     default: return lrbms_fail(ctx, LRBMS_E_INVALID, "set_option: unknown option");
   }
   return LRBMS_OK;
@@ -375,7 +377,7 @@ int lrbms_mesh_upload(lrbms_ctx* ctx, const lrbms_mesh_desc* d, int32_t S, int32
     ctx->diag_explicit = false;
   }
   ctx->subset_n = 0;
-  ctx->wab_src = nullptr;      // (factors of another mesh)
+  forget_assembled(ctx);       // (factors and side tables of another mesh or neighbour table)
   ctx->pass_ran = false;
   ctx->S = S;
   ctx->S_ext = S_ext;
@@ -440,6 +442,13 @@ int lrbms_assemble_products(lrbms_ctx* ctx, int32_t Q, const double* theta_bar, 
   LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, 1); CHECK_PTR(ctx, theta_bar); CHECK_PTR(ctx, lam); CHECK_PTR(ctx, lam_df); CHECK_PTR(ctx, lbar);
   CHECK_PTR(ctx, lhat); CHECK_PTR(ctx, P_diag); CHECK_PTR(ctx, ebar); CHECK_PTR(ctx, caa); CHECK_PTR(ctx, Aab); CHECK_PTR(ctx, Bbb);
   return launch_assemble_products(ctx, Q, theta_bar, lam, lam_df, lbar, lhat, P_diag, ebar, caa, Aab, Bbb, (hipStream_t)stream);
+}
+
+int32_t lrbms_assembled_arrays(lrbms_ctx* ctx, int32_t kind, const double** out, int32_t cap) {
+  if (!ctx || kind < 0 || kind >= lrbms_ctx::SRC_COUNT || cap < 0 || (cap > 0 && !out)) return -1;
+  const std::vector<lrbms_ctx::AsmRec>& known = ctx->asm_known[kind];
+  for (int32_t i = 0; i < cap && i < (int32_t)known.size(); ++i) out[i] = known[(size_t)i].p;
+  return (int32_t)known.size();
 }
 
 int lrbms_assemble_flux(lrbms_ctx* ctx, int32_t Q, const double* lam, double* F, void* stream) {

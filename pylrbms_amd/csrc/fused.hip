@@ -30,6 +30,9 @@
 //   k_thin_nc        B   grid (4 sides, S): block-row `a` and block [self,a] of G_nc     (MFMA + VALU, latency-bound)
 //   k_thin_rt        B   grid (4 sides, S): blocks [a,self], [a,a] of G_bb, G_rdd; G_ab[:, a], r_fd[a]  (write-bound)
 //   k_coupling       B   grid (4 sides, S): off-diagonal blocks of B_sys                 (MFMA, small)
+//   k_side_tables    -   grid (S, 4 sides): what k_thin_rt / k_thin_ncf need of Bbb, Aab, b, ebar, nbr and the template alone; NOT part
+//                       of a pass: launched by the assembly exports and kept by the context (in a pass only for arrays that are
+//                       not the context's, or under LRBMS_OPT_SIDE_TABLES 0)
 // Below 192 subdomains per rank the independent kernels are forked over the library's streams.  Every output element is
 // written exactly once (zeros included); all reductions have a fixed order (the 2-way K-split meets by atomic add, which
 // is order-independent for two contributions).
@@ -3850,11 +3853,55 @@ __host__ __device__ inline int fnc_ld(int nvs, int N, int vertex_patch = 0) { re
 constexpr int NCF_ROWS = 8;   // rows listed per side vertex in k_thin_ncf (4 in the 8-triangle pattern)
 
 struct ThinNcfArgs {
-  const double *V, *ebar, *AvgSelf, *AvgSide;
+  const double *V, *AvgSelf, *AvgSide;      // (ebar enters through ktab / mtab)
   const int* nbr;
   double* Fnc;
   int N, S;
+  const double *ktab = nullptr, *mtab = nullptr;   // side tables of the context (k_side_tables): Ksc [S][4][ntouch][9], M_ab rows [S][4][nvs][4 nvs]
 };
+
+// The basis-independent part of F_nc for (subdomain s, side): Ksc [ntouch][9] = ebar_T K_T of the touching elements (0 beyond the side's
+// count) and M_ab = P_a^T E P_b as the rows [nvs][4 nvs] thin_ncf_body copies (0 for vertices the side does not have).  Evaluated by
+// k_side_tables once per assembly, straight from the template tables, by ONE workgroup per (s, side); the sums run in the table order
+// of touch_rlist.
+__device__ inline void ncf_side_tables(const Tmpl& t, const double* __restrict__ ebar, int s, int side, int tid, int nthreads,
+                                       double* ksc, double* __restrict__ mab) {
+  const int nvs = nvs_of(t), ne = t.touch_count[side];
+  const int nside = (side == 0 || side == 3) ? t.nvx : t.nvy;
+  const double* ebs = ebar + (long)s * t.nT;
+  const int* telem = t.touch_elem + side * t.ntouch;
+  const int* side_mask = t.touch_mask + side * t.ntouch;
+  const int* ptab = t.touch_pos + side * t.ntouch * 12;
+  const int* rlist = t.touch_rlist + side * nvs * (NCF_ROWS + 1);
+  for (int i = tid; i < 9 * t.ntouch; i += nthreads) {
+    const int T = telem[i < 9 * ne ? i / 9 : 0];
+    ksc[i] = i < 9 * ne ? ebs[T] * t.stiff[9 * T + i % 9] : 0.0;
+  }
+  __syncthreads();      // M_ab sums the ROUNDED products, as the kernel did from its LDS copy of Ksc (every thread of the workgroup is here)
+  // one item per (side vertex, other side b, vertex of b)
+  for (int it = tid; it < nvs * 4 * nvs; it += nthreads) {
+    const int pos = it / (4 * nvs), rem = it - pos * 4 * nvs, sb = rem / nvs, pos2 = rem - sb * nvs;
+    double m = 0.0;
+    // two lattice vertices share an element only if they are lattice neighbours (every triangle of the template spans one lattice
+    // step): everything else is zero without a look at the tables
+    const int ax = side == 0 || side == 3 ? pos : (side == 1 ? 0 : t.nvx - 1), ay = side == 1 || side == 2 ? pos : (side == 0 ? 0 : t.nvy - 1);
+    const int bx = sb == 0 || sb == 3 ? pos2 : (sb == 1 ? 0 : t.nvx - 1), by = sb == 1 || sb == 2 ? pos2 : (sb == 0 ? 0 : t.nvy - 1);
+    const bool near = ax - bx <= 1 && bx - ax <= 1 && ay - by <= 1 && by - ay <= 1;
+    if (pos < nside && near) {
+      const int bit = 1 << sb;
+      const int* rl = rlist + pos * (NCF_ROWS + 1);
+      const int nr = rl[0] >= 0 ? rl[0] : 3 * ne;
+      for (int i = 0; i < nr; ++i) {
+        const int r = rl[0] >= 0 ? rl[1 + i] : i, p = r / 3, k = r - 3 * p;
+        if (!(side_mask[p] & bit) || ptab[r * 4 + side] != pos) continue;
+#pragma unroll
+        for (int k2 = 0; k2 < 3; ++k2)
+          if (ptab[(3 * p + k2) * 4 + sb] == pos2) m += ksc[9 * p + 3 * k + k2];
+      }
+    }
+    mab[it] = m;
+  }
+}
 
 __device__ __forceinline__ void thin_ncf_body(const Tmpl& t, const ThinNcfArgs& a, int side, int s) {
   extern __shared__ double lds[];
@@ -3875,21 +3922,23 @@ __device__ __forceinline__ void thin_ncf_body(const Tmpl& t, const ThinNcfArgs& 
   int* ptab = vtab + 3 * t.ntouch;                                // [ne][3][4]
   int* side_mask = ptab + 12 * t.ntouch;                          // [ne]
   int* rlist = side_mask + t.ntouch;                              // [nvs][NCF_ROWS + 1]: rows 3 p + k sitting on side vertex pos (count first)
-  const double* ebs = a.ebar + (long)s * t.nT;
-  for (int i = tid; i < ne; i += 256) {
-    ttab[i] = t.touch_elem[side * t.ntouch + i];
-    side_mask[i] = t.touch_mask[side * t.ntouch + i];
-  }
+  // Ksc = ebar_T K_T and the finished M_ab rows do not depend on the basis: both come from the context's side tables
+  // (ncf_side_tables, evaluated once per assembly), requested together with the touch tables
+  const double* kt = a.ktab + ((long)s * 4 + side) * 9 * t.ntouch;
+  const double* mt = a.mtab + ((long)s * 4 + side) * 4 * nvs * nvs;
+  constexpr int MT = 2;                             // M_ab items per thread held from here to the output phase (config 3: all of them)
+  double mv[MT];
+#pragma unroll
+  for (int u = 0; u < MT; ++u) mv[u] = mt[u * 256 + tid < 4 * nvs * nvs ? u * 256 + tid : 0];
+  (void)side_mask;                                  // (only the M_ab scan read it: the slot stays so that the LDS layout, and thin_ncf_lds_bytes, are the parent's)
+  for (int i = tid; i < ne; i += 256) ttab[i] = t.touch_elem[side * t.ntouch + i];
   // the rows that meet in a side vertex, in table order: t.touch_rlist (built at mesh upload; a vertex with more than NCF_ROWS rows has
   // count -1 and is scanned where it is used)
   static_assert(NCF_ROWS == 8, "layout of t.touch_rlist");
   for (int i = tid; i < nvs * (NCF_ROWS + 1); i += 256) rlist[i] = t.touch_rlist[side * nvs * (NCF_ROWS + 1) + i];
   for (int i = tid; i < 3 * ne; i += 256) vtab[i] = t.touch_vtx[side * t.ntouch * 3 + i];
   for (int i = tid; i < 12 * ne; i += 256) ptab[i] = t.touch_pos[side * t.ntouch * 12 + i];
-  for (int i = tid; i < 9 * ne; i += 256) {
-    const int T = t.touch_elem[side * t.ntouch + i / 9];
-    Ksc[i] = ebs[T] * t.stiff[9 * T + i % 9];
-  }
+  for (int i = tid; i < 9 * ne; i += 256) Ksc[i] = kt[i];
   THIN_STAMP(2, 1);
   __syncthreads();
   THIN_STAMP(2, 2);
@@ -3967,28 +4016,10 @@ __device__ __forceinline__ void thin_ncf_body(const Tmpl& t, const ThinNcfArgs& 
       Fs[(long)pos * LD + 2 * N + 4 * nvs + j] = carries ? Ac[((long)s * 4 + corner) * N + j] : 0.0;
     }
   }
-  // M_ab: one item per (side vertex, other side b, vertex of b)
-  for (int it = tid; it < nvs * 4 * nvs; it += 256) {
-    const int pos = it / (4 * nvs), rem = it - pos * 4 * nvs, sb = rem / nvs, pos2 = rem - sb * nvs;
-    double m = 0.0;
-    // two lattice vertices share an element only if they are lattice neighbours (every triangle of the template spans one lattice
-    // step): everything else is zero without a look at the tables
-    const int ax = side == 0 || side == 3 ? pos : (side == 1 ? 0 : t.nvx - 1), ay = side == 1 || side == 2 ? pos : (side == 0 ? 0 : t.nvy - 1);
-    const int bx = sb == 0 || sb == 3 ? pos2 : (sb == 1 ? 0 : t.nvx - 1), by = sb == 1 || sb == 2 ? pos2 : (sb == 0 ? 0 : t.nvy - 1);
-    const bool near = ax - bx <= 1 && bx - ax <= 1 && ay - by <= 1 && by - ay <= 1;
-    if (pos < nside && near) {
-      const int bit = 1 << sb;
-      const int* rl = rlist + pos * (NCF_ROWS + 1);
-      const int nr = rl[0] >= 0 ? rl[0] : 3 * ne;
-      for (int i = 0; i < nr; ++i) {
-        const int r = rl[0] >= 0 ? rl[1 + i] : i, p = r / 3, k = r - 3 * p;
-        if (!(side_mask[p] & bit) || ptab[r * 4 + side] != pos) continue;
-#pragma unroll
-        for (int k2 = 0; k2 < 3; ++k2)
-          if (ptab[(3 * p + k2) * 4 + sb] == pos2) m += Ksc[9 * p + 3 * k + k2];
-      }
-    }
-    Fs[(long)pos * LD + 2 * N + rem] = m;
+  // M_ab: the table rows [nvs][4 nvs] into columns [2 N, 2 N + 4 nvs) of the rows of F_nc
+  for (int it = tid, u = 0; it < nvs * 4 * nvs; it += 256, ++u) {
+    const int pos = it / (4 * nvs), rem = it - pos * 4 * nvs;
+    Fs[(long)pos * LD + 2 * N + rem] = u < MT ? (u == 0 ? mv[0] : mv[1]) : mt[it];
   }
   THIN_STAMP(2, 5);
 }
@@ -4015,11 +4046,60 @@ static size_t thin_ncf_lds_bytes(const Tmpl& t, int N) {
 // them by k_thin_expand.  Row layout of F_side [S][4][ncf][LD], LD = 4 QN + 4:
 //   [0, QN) Ra | [QN, 2QN) Yb | [2QN, 3QN) Dp | [3QN, 4QN) Xab (q, i) | sc0 sc1 sc2 0
 struct ThinRtArgs {
-  const double *V, *Rself, *Rside, *Bbb, *Aab, *b;
+  const double *V, *Rself, *Rside;      // (Bbb, Aab, b enter through rec)
   const int* nbr;
   double *Fside, *r_fd;
   int Q, N, S;
+  const double* rec = nullptr;   // side-face records [S][4][ncf][RTREC_LD] of the context's side tables (k_side_tables)
 };
+
+// Record of side face p of (subdomain s, side): everything thin_rt_body needs of that face that does not depend on the basis, resolved
+// once per assembly from the template row (t.sface_i / t.sface_d) and the subdomain's b, Bbb, Aab, nbr.  16-byte aligned, in doubles:
+//   [0, 4)  int T, fp, RT0 rows of faces 0..2, 3 pad       [4, 8)   fco: sign |e_g| / |T| (g = 0..2), |T|
+//   [8]     sc2 = (b_T . 1) c_p    [9, 12)  Bl: row f_p of B_T    [12, 16) the trailing entries of the F_side row: B_T[f_p][f_p], |T| c_p^2, sc2, 0
+//   [16, 16 + 3 Q)  Aq: column f_p of (A_ab^q)_T, q = 0 .. Q - 1 (Q <= 4)
+constexpr int RTREC_LD = 28;
+__device__ inline void rt_side_record(const Tmpl& t, const int* __restrict__ nbr, const double* __restrict__ Bbb, const double* __restrict__ Aab,
+                                      const double* __restrict__ b, int Q, int S, int s, int side, int p, double* __restrict__ rec) {
+  const int* nbr_s = nbr + s * 5;
+  const int4* ti4 = reinterpret_cast<const int4*>(t.sface_i + (side * t.ncf + p) * 12);
+  const int4 i0 = ti4[0], i1 = ti4[1], i2 = ti4[2];      // T fp rt0 rt1 | rt2 sg0 sg1 sg2 | bs0 bs1 bs2 -
+  const double* td = t.sface_d + (side * t.ncf + p) * 4;
+  const double len[3] = {td[0], td[1], td[2]}, area = td[3];
+  const int T = i0.x, fp = i0.y;
+  const int rt[3] = {i0.z, i0.w, i1.x}, sg[3] = {i1.y, i1.z, i1.w}, bs[3] = {i2.x, i2.y, i2.z};
+  const double* be = b + (long)s * t.n + 3 * T;
+  const double* B = Bbb + ((long)s * t.nT + T) * 9 + fp * 3;
+  const double b0 = be[0], b1 = be[1], b2 = be[2], B0 = B[0], B1 = B[1], B2 = B[2];
+  int* ri = reinterpret_cast<int*>(rec);
+  ri[0] = T;
+  ri[1] = fp;
+  double fco[4];
+#pragma unroll
+  for (int g = 0; g < 3; ++g) {
+    ri[2 + g] = rt[g];
+    const int sign = (bs[g] >= 0 && nbr_s[side_to_slot(bs[g] >= 0 ? bs[g] : 0)] < 0) ? 1 : sg[g];      // face_sign_at
+    fco[g] = sign * len[g] / area;
+  }
+  ri[5] = ri[6] = ri[7] = 0;
+  fco[3] = area;
+  const double cp = fp == 0 ? fco[0] : fp == 1 ? fco[1] : fco[2];
+  const double sc2 = (b0 + b1 + b2) * cp;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) rec[4 + g] = fco[g];
+  rec[8] = sc2;
+  rec[9] = B0;
+  rec[10] = B1;
+  rec[11] = B2;
+  rec[12] = fp == 0 ? B0 : fp == 1 ? B1 : B2;
+  rec[13] = area * cp * cp;
+  rec[14] = sc2;
+  rec[15] = 0.0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rec[16 + q * 3 + k] = q < Q ? Aab[(((long)q * S + s) * t.nT + T) * 9 + k * 3 + fp] : 0.0;
+}
 
 __host__ __device__ inline int fside_ld(int Q, int N) { return 4 * Q * N + 4; }
 
@@ -4030,7 +4110,7 @@ static size_t thin_rt_lds_bytes(const Tmpl& t, int Q, int N) {      // fco [ncf]
 __device__ __forceinline__ void thin_rt_body(const Tmpl& t, const ThinRtArgs& a, int side, int s) {
   extern __shared__ double lds[];
   const int slot = side_to_slot(side), tid = threadIdx.x;
-  const int Q = a.Q, N = a.N, QN = Q * N, C = 5 * QN, S = a.S, LD = fside_ld(Q, N);
+  const int Q = a.Q, N = a.N, QN = Q * N, C = 5 * QN, LD = fside_ld(Q, N);
   double* Fs = a.Fside + ((long)s * 4 + side) * t.ncf * LD;
   const int s2 = a.nbr[s * 5 + slot];
   const int np = s2 < 0 ? 0 : t.side_count[side];
@@ -4049,7 +4129,6 @@ __device__ __forceinline__ void thin_rt_body(const Tmpl& t, const ThinRtArgs& a,
   double* Aq = Bl + 3 * np;                           // [np][Q][3] column f_p of (A_ab^q)_T
   double* Rl = Aq + 3 * Q * np + ((np * (8 + 3 * Q)) & 1);   // [np][QN]   the neighbour's flux image on the side faces (Ra), 16-byte aligned
   int* fidx = reinterpret_cast<int*>(Rl + np * QN);   // [np][5]: T, fp, rt row of face 0..2
-  const int* nbr_s = a.nbr + s * 5;
   const double* Rs = a.Rself + (long)s * t.nrt * QN;
   const double* Rsd = a.Rside + ((long)s * 4 + side) * t.ncf * QN;
   // Ra (np QN contiguous doubles) is requested first and parked in LDS: the factor rows and r_fd both read it there
@@ -4058,50 +4137,39 @@ __device__ __forceinline__ void thin_rt_body(const Tmpl& t, const ThinRtArgs& a,
 #pragma unroll
   for (int u = 0; u < RT_IT; ++u) rr[u] = Rsd[u * 256 + tid < np * QN ? u * 256 + tid : 0];
   if (tid < np) {
-    // template data of the side face from ONE table row (t.sface_i / t.sface_d, built at mesh upload), then the subdomain's data
-    // of that element: two round trips (was a chain of five: side_elem -> nb_elem -> elem_rt / face_len / area -> b, B)
+    // the face's record of the context's side tables (rt_side_record, evaluated once per assembly), requested in the same batch as Ra:
+    // ONE round trip before the factor rows (was two: template row -> b, B, A_ab of that element)
     const int p = tid;
-    const int4* ti4 = reinterpret_cast<const int4*>(t.sface_i + (side * t.ncf + p) * 12);
-    const int4 i0 = ti4[0], i1 = ti4[1], i2 = ti4[2];      // T fp rt0 rt1 | rt2 sg0 sg1 sg2 | bs0 bs1 bs2 -
-    const double* td = t.sface_d + (side * t.ncf + p) * 4;
-    const double len[3] = {td[0], td[1], td[2]}, area = td[3];
-    const int T = i0.x, fp = i0.y;
-    const int rt[3] = {i0.z, i0.w, i1.x}, sg[3] = {i1.y, i1.z, i1.w}, bs[3] = {i2.x, i2.y, i2.z};
-    const double* be = a.b + (long)s * t.n + 3 * T;
-    const double* B = a.Bbb + ((long)s * t.nT + T) * 9 + fp * 3;
-    const double b0 = be[0], b1 = be[1], b2 = be[2], B0 = B[0], B1 = B[1], B2 = B[2];
-    double Aqv[4][3];
+    const d2* r2 = reinterpret_cast<const d2*>(a.rec + (((long)s * 4 + side) * t.ncf + p) * RTREC_LD);
+    const int4* ri4 = reinterpret_cast<const int4*>(r2);      // T fp rt0 rt1 | rt2 - - -
+    const int4 i0 = ri4[0], i1 = ri4[1];
+    d2 rc[8], ra[6];
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (q < Q) {
-        const double* A = a.Aab + (((long)q * S + s) * t.nT + T) * 9;
+    for (int k = 2; k < 8; ++k) rc[k] = r2[k];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) Aqv[q][k] = A[k * 3 + fp];
-      }
-    fidx[p * 5] = T;
-    fidx[p * 5 + 1] = fp;
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      fidx[p * 5 + 2 + g] = rt[g];
-      const int sign = (bs[g] >= 0 && nbr_s[side_to_slot(bs[g] >= 0 ? bs[g] : 0)] < 0) ? 1 : sg[g];      // face_sign_at
-      fco[p * 4 + g] = sign * len[g] / area;
-    }
-    fco[p * 4 + 3] = area;
-    const double cp = fco[p * 4 + fp];
-    sc2[p] = (b0 + b1 + b2) * cp;
+    for (int k = 0; k < 6; ++k)
+      if (2 * k < 3 * Q) ra[k] = r2[8 + k];
+    fidx[p * 5] = i0.x;            // T
+    fidx[p * 5 + 1] = i0.y;        // fp
+    fidx[p * 5 + 2] = i0.z;        // RT0 rows of the faces 0..2
+    fidx[p * 5 + 3] = i0.w;
+    fidx[p * 5 + 4] = i1.x;
+    fco[p * 4] = rc[2][0];
+    fco[p * 4 + 1] = rc[2][1];
+    fco[p * 4 + 2] = rc[3][0];
+    fco[p * 4 + 3] = rc[3][1];
+    sc2[p] = rc[4][0];
+    Bl[p * 3] = rc[4][1];
+    Bl[p * 3 + 1] = rc[5][0];
+    Bl[p * 3 + 2] = rc[5][1];
     double* row = Fs + (long)p * LD + 4 * QN;
-    row[0] = fp == 0 ? B0 : fp == 1 ? B1 : B2;
-    row[1] = area * cp * cp;
-    row[2] = sc2[p];
-    row[3] = 0.0;
-    Bl[p * 3] = B0;
-    Bl[p * 3 + 1] = B1;
-    Bl[p * 3 + 2] = B2;
+    row[0] = rc[6][0];
+    row[1] = rc[6][1];
+    row[2] = rc[7][0];
+    row[3] = rc[7][1];
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (q < Q)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) Aq[(p * Q + q) * 3 + k] = Aqv[q][k];
+    for (int k = 0; k < 12; ++k)
+      if (k < 3 * Q) Aq[p * Q * 3 + k] = ra[k >> 1][k & 1];
   }
 #pragma unroll
   for (int u = 0; u < RT_IT; ++u)
@@ -4467,6 +4535,7 @@ struct ThinNcArgs {
   const double *ebar, *AvgSelf, *AvgSide, *A_cpl;
   double *G_nc, *B_sys;
   double* Fnc;   // factored layout: the side factors of G_nc instead of its side blocks
+  const double *ktab, *mtab;   // ... and the side tables thin_ncf_body reads
 };
 template <int NTX>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NTX <= 3 ? 5 : 4, 8))) void k_thin(Tmpl t, ThinRtArgs a, ThinNcArgs c) {
@@ -4477,7 +4546,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NTX <= 3 ? 
   }
   if (threadIdx.x >= 256) return;
   if (blockIdx.z == 0) {
-    const ThinNcfArgs f{a.V, c.ebar, c.AvgSelf, c.AvgSide, a.nbr, c.Fnc, a.N, a.S};
+    const ThinNcfArgs f{a.V, c.AvgSelf, c.AvgSide, a.nbr, c.Fnc, a.N, a.S, c.ktab, c.mtab};
     thin_ncf_body(t, f, side, s);
     return;
   }
@@ -4715,6 +4784,93 @@ int launch_wab(lrbms_ctx* ctx, int Q, const double* Aab, double* Wab, hipStream_
   return LRBMS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Side tables: what the thin side kernels used to derive in EVERY pass from the assembled arrays, the neighbour table and the
+// template alone.  One context-owned allocation, per subdomain (config 3: 22 KB):
+//   rec  [S][4][ncf][RTREC_LD]    thin_rt_body: the side-face records (rt_side_record)
+//   ktab [S][4][ntouch][9]        thin_ncf_body: Ksc = ebar_T K_T of the touching elements
+//   mtab [S][4][nvs][4 nvs]       thin_ncf_body: the finished M_ab rows                              (ncf_side_tables)
+// k_side_tables: grid (S, 4), one workgroup per (subdomain, side); always over every subdomain, whatever subset a pass is restricted to.
+struct SideTabs {
+  double *rec, *ktab, *mtab;
+};
+static long side_tabs_size(const Tmpl& t, int S) {
+  const long nvs = t.nvx > t.nvy ? t.nvx : t.nvy;
+  return (long)S * (4L * t.ncf * RTREC_LD + 36L * t.ntouch + 16L * nvs * nvs);
+}
+static SideTabs side_tabs_of(const Tmpl& t, int S, double* base) {      // (every section an even number of doubles: 16-byte aligned)
+  SideTabs x;
+  x.rec = base;
+  x.ktab = x.rec + (long)S * 4 * t.ncf * RTREC_LD;
+  x.mtab = x.ktab + (long)S * 36 * t.ntouch;      // [S][4][nvs][4 nvs] to the end (side_tabs_size)
+  return x;
+}
+namespace {
+__global__ __launch_bounds__(256) void k_side_tables(Tmpl t, int S, int Q, const int* __restrict__ nbr, const double* __restrict__ Bbb,
+                                                     const double* __restrict__ Aab, const double* __restrict__ b,
+                                                     const double* __restrict__ ebar, SideTabs x) {
+  const int s = blockIdx.x, side = blockIdx.y, tid = threadIdx.x, nvs = nvs_of(t);
+  for (int p = tid; p < t.ncf; p += 256) {
+    double* rec = x.rec + (((long)s * 4 + side) * t.ncf + p) * RTREC_LD;
+    if (p < t.side_count[side]) rt_side_record(t, nbr, Bbb, Aab, b, Q, S, s, side, p, rec);
+    else
+      for (int i = 0; i < RTREC_LD; ++i) rec[i] = 0.0;
+  }
+  ncf_side_tables(t, ebar, s, side, tid, 256, x.ktab + ((long)s * 4 + side) * 9 * t.ntouch, x.mtab + ((long)s * 4 + side) * 4 * nvs * nvs);
+}
+}  // namespace
+
+// The context's side tables for these arrays: the kept ones if they were built from these very arrays at their current generation
+// (lrbms_dev.h), else built here, on `st`.
+static int side_tables_ensure(lrbms_ctx* ctx, int Q, const double* Bbb, const double* Aab, const double* b, const double* ebar,
+                              hipStream_t st, SideTabs* out) {
+  const Tmpl& t = ctx->t;
+  const long need = side_tabs_size(t, ctx->S);
+  if (ctx->stab_cap < need) {
+    if (ctx->stab) LRBMS_HIP_CHECK(ctx, hipFree(ctx->stab));
+    ctx->stab = nullptr;
+    ctx->stab_cap = 0;
+    LRBMS_HIP_CHECK(ctx, hipMalloc(&ctx->stab, sizeof(double) * (size_t)need));
+    ctx->stab_cap = need;
+    for (int k = 0; k < lrbms_ctx::SRC_COUNT; ++k) ctx->stab_ptr[k] = nullptr;
+  }
+  const SideTabs x = side_tabs_of(t, ctx->S, ctx->stab);
+  if (out) *out = x;
+  const double* src[lrbms_ctx::SRC_COUNT] = {Bbb, Aab, b, ebar};
+  bool kept = ctx->opt_side_tables != 0 && ctx->stab_Q == Q;
+  for (int k = 0; k < lrbms_ctx::SRC_COUNT; ++k) {
+    const long gen = asm_gen_of(ctx, k, src[k]);
+    kept = kept && gen >= 0 && ctx->stab_ptr[k] == src[k] && ctx->stab_gen[k] == gen;
+  }
+  if (kept) return LRBMS_OK;
+  {
+    KScope ks(ctx, "k_side_tables", st);
+    hipLaunchKernelGGL(k_side_tables, dim3(ctx->S, 4), dim3(256), 0, st, t, ctx->S, Q, ctx->nbr, Bbb, Aab, b, ebar, x);
+  }
+  LRBMS_LAUNCH_CHECK(ctx);
+  ctx->stab_Q = Q;
+  for (int k = 0; k < lrbms_ctx::SRC_COUNT; ++k) {
+    ctx->stab_ptr[k] = src[k];
+    ctx->stab_gen[k] = asm_gen_of(ctx, k, src[k]);      // (-1, an array foreign to the context: never kept)
+  }
+  return LRBMS_OK;
+}
+
+int side_tables_after_assembly(lrbms_ctx* ctx, bool from_rhs, hipStream_t st) {
+  for (int k = 0; k < lrbms_ctx::SRC_COUNT; ++k)
+    if (ctx->asm_ptr[k] == nullptr) return LRBMS_OK;      // (the other assembly export has not run yet)
+  if (ctx->opt_side_tables == 0 || ctx->asm_Q < 1 || ctx->asm_Q > 4) return LRBMS_OK;      // (the fused pass takes Q <= 4)
+  // A load vector assembled into ANOTHER array (one lrbms_assemble_rhs per source component) is not what the passes are handed:
+  // the kept tables stay with the b they were built from as long as that array is still one of the context's; a pass that is
+  // handed the new array builds its tables then.
+  const double* tb = ctx->stab_ptr[lrbms_ctx::SRC_B];
+  if (from_rhs && tb != nullptr && tb != ctx->asm_ptr[lrbms_ctx::SRC_B] && asm_gen_of(ctx, lrbms_ctx::SRC_B, tb) >= 0) return LRBMS_OK;
+  // (lrbms_assemble_products after such calls: again for the b of the kept tables, not for the last component's)
+  const double* b = tb != nullptr && asm_gen_of(ctx, lrbms_ctx::SRC_B, tb) >= 0 ? tb : ctx->asm_ptr[lrbms_ctx::SRC_B];
+  return side_tables_ensure(ctx, ctx->asm_Q, ctx->asm_ptr[lrbms_ctx::SRC_BBB], ctx->asm_ptr[lrbms_ctx::SRC_AAB], b,
+                            ctx->asm_ptr[lrbms_ctx::SRC_EBAR], st, nullptr);
+}
+
 static bool f1w_usable(lrbms_ctx* ctx, int Q, int N) { return Q == 2 && N % 2 == 0; }
 
 // Column layout of Y for k_f1w (Q = 2, three row tiles, even N in [34, 40]): the tiles of F1wPlan.  Symmetric groups of kind 3
@@ -4909,7 +5065,8 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
     for (int i = 0; i < 11; ++i) probe.push_back({i < 2 ? G_SYS : i == 2 ? G_ENERGY : i == 3 ? G_MASS : i < 7 ? G_AA : G_AB, i == 6 ? 1 : 0, i == 5 || i == 6 ? 1 : 0});
     f1w_ok = Q == 2 && f1w_layout(probe, N, Q);
     if (f1w_ok) {
-      if (ctx->wab != nullptr && ctx->wab_src == Aab && ctx->wab_Q == Q) {
+      if (ctx->opt_side_tables != 0 && ctx->wab != nullptr && ctx->wab_src == Aab && ctx->wab_Q == Q &&
+          ctx->wab_gen == asm_gen_of(ctx, lrbms_ctx::SRC_AAB, Aab)) {
         Wab = ctx->wab;
       } else {
         double* wloc = AvgSide + (long)S * 4 * nvs * N + (long)S * 4 * t.ncf * fside_ld(Q, N);
@@ -4918,6 +5075,10 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
       }
     }
   }
+  // the basis-independent tables of the thin side kernels: the context's, or rebuilt here, in front of the fork
+  SideTabs tabs{};
+  if (do_b)
+    if (int rc = side_tables_ensure(ctx, Q, Bbb, Aab, b, ebar, st, &tabs)) return rc;
   if (do_prep) {
     if (prep_from_lds) {
       KScope ks(ctx, "k_prep_lds", st);
@@ -5162,8 +5323,8 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
     if (int rc = side_prep(ctx->aux[0])) return rc;
   if (do_b && merge_thin) {
     const int ntx = (N + 15) / 16;
-    ThinRtArgs a{V, Rself, Rside, Bbb, Aab, b, ctx->nbr, Fside, r_fd, Q, N, S};
-    ThinNcArgs c{ebar, AvgSelf, AvgSide, A_cpl, G_nc, B_sys, Fnc};
+    ThinRtArgs a{V, Rself, Rside, ctx->nbr, Fside, r_fd, Q, N, S, tabs.rec};
+    ThinNcArgs c{ebar, AvgSelf, AvgSide, A_cpl, G_nc, B_sys, Fnc, tabs.ktab, tabs.mtab};
     size_t lds = factored ? thin_ncf_lds_bytes(t, N) : thin_nc_lds_bytes(t, ntx);
     lds = std::max(lds, thin_rt_lds_bytes(t, Q, N));
     lds = std::max(lds, coupling_lds_bytes(t, ntx, Q));
@@ -5180,7 +5341,7 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
     hipLaunchKernelGGL(k_thin3<NTX>, dim3(4, Sg, 3), dim3(256), lds, s_rt, t, a, f, A_cpl, B_sys);                            \
   } while (0)
     if (factored) {
-      const ThinNcfArgs f{V, ebar, AvgSelf, AvgSide, ctx->nbr, Fnc, N, S};
+      const ThinNcfArgs f{V, AvgSelf, AvgSide, ctx->nbr, Fnc, N, S, tabs.ktab, tabs.mtab};
       KScope ks(ctx, "k_thin3", s_rt);
       switch (ntx) {
         case 1: LRBMS_THIN3(1); break;
@@ -5216,7 +5377,7 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
     }
     const int ntx = (N + 15) / 16;
     if (factored) {
-      const ThinNcfArgs f{V, ebar, AvgSelf, AvgSide, ctx->nbr, Fnc, N, S};
+      const ThinNcfArgs f{V, AvgSelf, AvgSide, ctx->nbr, Fnc, N, S, tabs.ktab, tabs.mtab};
       const size_t ldsf = thin_ncf_lds_bytes(t, N);
       if (ldsf > 64 * 1024)
         LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_thin_ncf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf));
@@ -5243,7 +5404,7 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
 #undef LRBMS_THIN_NC
     }
     LRBMS_LAUNCH_CHECK(ctx);
-    ThinRtArgs a{V, Rself, Rside, Bbb, Aab, b, ctx->nbr, Fside, r_fd, Q, N, S};
+    ThinRtArgs a{V, Rself, Rside, ctx->nbr, Fside, r_fd, Q, N, S, tabs.rec};
     const size_t lds2 = thin_rt_lds_bytes(t, Q, N);
     {
       KScope ks(ctx, "k_thin_rt", s_rt);

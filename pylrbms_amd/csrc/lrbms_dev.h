@@ -78,6 +78,34 @@ struct lrbms_ctx : lrbms_ctx_base {
   long wab_cap = 0;
   const double* wab_src = nullptr;
   int wab_Q = 0;
+  long wab_gen = -1;                  // the generation of that Aab (asm_gen_of) the factors were formed at
+  // Assembled arrays the context keeps derived tables of (W' above, the side tables below).  Every array an assembly export writes
+  // is registered per kind with a generation that is new with every write (asm_known: the last asm_known_max(kind) arrays of a kind
+  // and, whatever its age, the array the kept side tables were built from; so an export into ANOTHER array -- one load vector per
+  // source component, say -- does not disown the arrays assembled before).  A registered address is a promise of the caller's: the
+  // array stays allocated while it is registered (include/lrbms_hip.h; lrbms_assembled_arrays lists the register).  A pass
+  // uses kept tables only while the arrays it is handed are the arrays the tables were built from, at the generation they were built
+  // at; an array that is not registered is foreign to the context (its content may change unseen) and its tables are rebuilt in every
+  // pass.  asm_ptr: the array the LAST export of a kind wrote (what the exports build tables for).  lrbms_mesh_upload forgets everything.
+  enum { SRC_BBB = 0, SRC_AAB, SRC_B, SRC_EBAR, SRC_COUNT };
+  static constexpr int asm_known_max(int kind) { return kind == SRC_B ? 32 : 4; }      // (load vectors come by the component)
+  struct AsmRec {
+    const double* p;
+    long gen;
+  };
+  std::vector<AsmRec> asm_known[SRC_COUNT];      // oldest first
+  long asm_counter = 0;
+  const double* asm_ptr[SRC_COUNT] = {nullptr, nullptr, nullptr, nullptr};
+  int asm_Q = 0;                      // Q of the last lrbms_assemble_products
+  // Side tables (fused.hip, k_side_tables): everything the thin side kernels derive from Bbb, Aab, b, ebar, nbr and the template
+  // alone -- basis-independent, so built once per assembly instead of once per pass: the side-face records of thin_rt_body and the
+  // Ksc / M_ab tables of thin_ncf_body.
+  double* stab = nullptr;
+  long stab_cap = 0;
+  const double* stab_ptr[SRC_COUNT] = {nullptr, nullptr, nullptr, nullptr};
+  long stab_gen[SRC_COUNT] = {0, 0, 0, 0};
+  int stab_Q = 0;
+  int opt_side_tables = 1;            // LRBMS_OPT_SIDE_TABLES
   bool pass_ran = false;              // a fused pass has run: conventions that change buffer shapes (the vertex patch: F_nc rows) are frozen
   bool diag_explicit = false;         // lrbms_set_diagonal_neighbours was called (needed with the vertex patch when S_ext > S)
   int* subset = nullptr;              // lrbms_fused_set_subset: device copy of the list (ctx-owned), subset_n == 0: no restriction
@@ -99,6 +127,39 @@ __host__ __device__ inline int slot_to_side(int slot) { return slot < 2 ? slot :
 
 int build_template_tables(lrbms_ctx* ctx);
 int launch_wab(lrbms_ctx* ctx, int Q, const double* Aab, double* Wab, hipStream_t st);   // fused.hip: W' = hab A_ab
+// an assembly export wrote the array `p` of kind lrbms_ctx::SRC_*: tables derived from an earlier content are stale
+inline void note_assembled(lrbms_ctx* ctx, int kind, const double* p) {
+  std::vector<lrbms_ctx::AsmRec>& known = ctx->asm_known[kind];
+  for (size_t i = 0; i < known.size(); ++i)
+    if (known[i].p == p) {
+      known.erase(known.begin() + (long)i);
+      break;
+    }
+  // the oldest goes -- but never the array the kept side tables were built from: the passes are handed that one
+  for (size_t i = 0; (int)known.size() >= lrbms_ctx::asm_known_max(kind) && i < known.size();) {
+    if (known[i].p == ctx->stab_ptr[kind]) ++i;
+    else known.erase(known.begin() + (long)i);
+  }
+  known.push_back({p, ++ctx->asm_counter});
+  ctx->asm_ptr[kind] = p;
+}
+// the generation of array `p` of that kind, or -1 if no assembly export of this context wrote it (or it was forgotten)
+inline long asm_gen_of(const lrbms_ctx* ctx, int kind, const double* p) {
+  for (const lrbms_ctx::AsmRec& r : ctx->asm_known[kind])
+    if (r.p == p) return r.gen;
+  return -1;
+}
+inline void forget_assembled(lrbms_ctx* ctx) {      // another mesh or neighbour table: nothing assembled before belongs to it
+  for (int k = 0; k < lrbms_ctx::SRC_COUNT; ++k) {
+    ctx->asm_known[k].clear();
+    ctx->asm_ptr[k] = nullptr;
+    ctx->stab_ptr[k] = nullptr;
+  }
+  ctx->wab_src = nullptr;
+}
+// fused.hip: called by the assembly exports -- builds the side tables of the arrays they wrote last, once all four kinds are known.
+// from_rhs: lrbms_assemble_rhs into an array the kept tables were not built from (another load vector) leaves those tables alone.
+int side_tables_after_assembly(lrbms_ctx* ctx, bool from_rhs, hipStream_t st);
 long f1_mfma_per_subdomain(lrbms_ctx* ctx, int Q, int N);   // fused.hip: executed MFMAs of the dense projection kernel
 // dense coarse level of the Krylov preconditioners (online.hip)
 int coarse_begin(lrbms_ctx* ctx, double** A0_out, hipStream_t st);

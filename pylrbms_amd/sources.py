@@ -90,6 +90,9 @@ def setup_sources(engine, funcs, coeffs):
     sp = eng.quadrature
     xf, cl, kl = volume_record_points(eng.grid, eng.local, (sp.rhs, sp.f2))
     f_smp_K = eng.ctx.from_numpy(np.ascontiguousarray(np.stack([sample_function(fn, xf, cl, kl) for fn in funcs])))
-    b_K = torch.stack([eng.ctx.assemble_rhs(f_smp_K[j].contiguous(), eng.lhat)[0] for j in range(len(funcs))]).contiguous()
+    c = eng.ctx
+    b_K, f2, ceps = c.empty(len(funcs), eng.S, eng.t.n), c.empty(eng.S), c.empty(eng.S)      # (f2, ceps of a component: not used)
+    for j in range(len(funcs)):
+        c.assemble_rhs(f_smp_K[j].contiguous(), eng.lhat, out=(b_K[j], f2, ceps))              # straight into its slab of b_K
     F2 = eng.ctx.assemble_source_gram(f_smp_K)
     return {'functions': funcs, 'coefficients': coeffs, 'K': len(funcs), 'f_smp_K': f_smp_K, 'b_K': b_K, 'F2': F2}

@@ -24,7 +24,7 @@ for d in sys.argv[3:]:
     for r in csv.DictReader(open(f)):
         m = re.search(r'(k_[a-z0-9_]+)', r['Kernel_Name'])
         k = m.group(1) if m else r['Kernel_Name'][:24]
-        k = {'k_f1u': 'k_f1', 'k_f1v': 'k_f1', 'k_f1w': 'k_f1'}.get(k, k)   # the forms of the projection kernel are the same step of the pass (bench.py: k_f1)
+        k = {'k_f1u': 'k_f1', 'k_f1v': 'k_f1', 'k_f1w': 'k_f1', 'k_f2g': 'k_f2'}.get(k, k)   # the forms of a kernel are the same step of the pass (bench.py: k_f1, k_f2)
         if r['Counter_Name'] in ('FETCH_SIZE', 'WRITE_SIZE'):
             tot[k][r['Counter_Name']] += float(r['Counter_Value'])
             calls[(k, r['Counter_Name'])] += 1
@@ -48,5 +48,5 @@ print('per pass (hot-path kernels): FETCH_SIZE {:.1f} MiB (x2 correction for wid
 with open(out_json, 'w') as fh:
     json.dump({'config': config, 'csrc_sha': source_sha(), 'per_kernel': per_kernel, 'per_pass_bytes': (2 * sf + sw) * 2 ** 20,
                'fetch_correction': 'FETCH_SIZE x 2 (gfx950, MI355X_MICROARCH.md HBM section); WRITE_SIZE as reported',
-               'source': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py'}, fh,
+               'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (a run each, no tracing) -- python3 bench.py'}, fh,
               indent=1)
