@@ -580,6 +580,43 @@ int lrbms_reduced_implicit_euler_batch_src(lrbms_ctx* ctx, int32_t Q, int32_t N,
                                            const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
                                            void* stream);
 
+/* -- batched parabolic estimates: the estimator of all trajectories of a batched solve in one call ----------
+ *   lrbms_reduced_parabolic_estimate_batch  ParabolicEstimator.estimate on the reduced model (elliptic_reconstruction = False),
+ *                                   term for term, for column m of the panel U [nt+1][S][N][nmu] (as
+ *                                   lrbms_reduced_implicit_euler_batch wrote it; read only) with theta[m] (theta [nmu][Q] host).
+ *                                   coef [nmu][2] host: sqrt(gamma(mu_m, mu_bar) / alpha(mu_m, mu_bar)) and
+ *                                   1 / sqrt(alpha(mu_m, mu_hat) alpha(mu_m, mu_bar)).  sqrt_local != 0: the local indicators
+ *                                   are replaced by sqrt(|.|) before the sums (EstimatorBase.sqrt_local).
+ *                                   Operators: the arguments of lrbms_reduced_estimate_batch_factored; F_side = F_nc = NULL
+ *                                   selects the dense layout of lrbms_reduced_estimate_batch (G_nc [S][5N][5N], ...).
+ *                                   K >= 1: a time-dependent source -- phi [nmu][nt+1][K] device, F2 [S][K][K],
+ *                                   r_fd_K [K][S][5QN]; the elliptic rows are then evaluated with f2 = 0 and r_fd = 0 (the
+ *                                   arguments f2 and r_fd are not read) and column (k, m) gets the source part of
+ *                                   lrbms_reduced_source_terms at theta[m], phi[m][k].  K = 0: phi = F2 = r_fd_K = NULL.
+ *                                   Outputs (device):
+ *                                     eta_loc       [3][nt+1][S][nmu]  nc, r, df per step, scaled by 2 sqrt(dt/3)
+ *                                     time_deriv_nc [nt][S][nmu]       sqrt(max(nc(U[k+1] - U[k]), 0) / dt), the difference
+ *                                                                      formed on the coefficients
+ *                                     time_residual [nt][nmu]          sqrt(dt/3 sum_s y^T M_red[s]^-1 y), y = A(theta_m)(U[k+1] - U[k])
+ *                                     eta           [nt+1][nmu]        the elliptic eta per step, scaled by 2 sqrt(dt/3)
+ *                                     est           [nmu]              |eta|_2 + |time_residual|_2 + |time_deriv_nc|_2
+ *                                   Everything runs on `stream`, no host synchronisation, no atomics: repeat calls give the same
+ *                                   bits.  M_red is inverted once per call (a zero diagonal entry of a zero-padded basis column
+ *                                   counts as 1).  A preconditioner installed with lrbms_reduced_precond_use is neither used
+ *                                   nor touched.
+ *                                   Limits (LRBMS_E_INVALID before any launch): 1 <= nmu <= 64, N <= 64, nt >= 1, dt > 0,
+ *                                   Q <= 8, Q <= 4 for more than 16 columns, S_ext == S, F_side and F_nc both or neither,
+ *                                   LRBMS_OPT_OSWALD_VERTEX_PATCH needs the factored layout.
+ *                                   work: lrbms_reduced_parabolic_estimate_batch_work_size(N, nmu, nt) doubles. */
+int64_t lrbms_reduced_parabolic_estimate_batch_work_size(lrbms_ctx* ctx, int32_t N, int32_t nmu, int32_t nt);
+int lrbms_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, int32_t nt, double dt,
+                                           const double* theta, const double* coef, int32_t sqrt_local, const double* U,
+                                           const double* B_sys, const double* M_red, const double* G_nc_self, const double* r_fd,
+                                           const double* G_rdd_self, const double* G_bb_self, const double* G_ab_self, const double* G_aa,
+                                           const double* F_side, const double* F_nc, const double* f2, const double* ceps, double hdiam,
+                                           const double* phi, const double* F2, const double* r_fd_K, double* work, double* eta_loc,
+                                           double* time_deriv_nc, double* time_residual, double* eta, double* est, void* stream);
+
 /* -- online enrichment (SURVEY.md section 8f "next" #1) ---------------------------------------------------- */
 /* Dirichlet correction blocks of the neighbourhood problems: on every coupling face of subdomain s, the boundary-form
  * diagonal block minus the inner-face block already contained in A_diag

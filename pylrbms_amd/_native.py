@@ -100,6 +100,9 @@ SIGNATURES = {
                                                           c_dbl, c_i32, _P_DBL, c_vp]),
     'lrbms_reduced_implicit_euler_batch_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp,
                                                               c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms_reduced_parabolic_estimate_batch_work_size': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
+    'lrbms_reduced_parabolic_estimate_batch': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_dbl, _P_DBL, _P_DBL, c_i32]
+                                               + [c_vp] * 13 + [c_dbl] + [c_vp] * 10),
     'lrbms_combine_sources': (ctypes.c_int, [c_vp, c_i32, c_i64, _P_DBL, c_vp, c_vp, c_vp]),
     'lrbms_assemble_dirichlet_correction': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms_local_correction_work_size': (c_i64, [c_vp, c_i32]),
@@ -858,6 +861,49 @@ class NativeContext(ContextBase):
                                                              c_vp(U.data_ptr()), float(rtol), int(max_iter), _dblp(info), self._stream())
         self._check(rc, 'lrbms_reduced_implicit_euler_batch_src')
         return U, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
+
+    def reduced_parabolic_estimate_batch(self, thetas, coef, dt, nt, U, B_sys, M_red, grams, f2, ceps, hdiam, sqrt_local=False,
+                                         phi=None, F2=None, r_fd_K=None, work=None):
+        """The parabolic estimate of the nmu <= 64 trajectories of the panel U [nt + 1, S, N, nmu] in one call
+        (``lrbms_reduced_parabolic_estimate_batch``): thetas [nmu, Q], coef [nmu, 2] (host), grams in either layout (6 tensors dense,
+        8 factored); with a time-dependent source phi [nmu, nt + 1, K], F2 [S, K, K], r_fd_K [K, S, 5 Q N].  Returns a dict of device
+        tensors: eta_loc [3, nt + 1, S, nmu], time_deriv_nc [nt, S, nmu], time_residual [nt, nmu], eta [nt + 1, nmu], est [nmu]."""
+        Q, S, N = B_sys.shape[0], self.S, B_sys.shape[3]
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu, nt = th.shape[0], int(nt)
+        assert th.shape == (nmu, Q)
+        cf = np.ascontiguousarray(coef, dtype=np.float64)
+        assert cf.shape == (nmu, 2), 'coef must be [nmu, 2]'
+        gptrs, factored = self._gram_ptrs(grams, Q, N)
+        if not factored:
+            gptrs = gptrs + [c_vp(None), c_vp(None)]
+        K = 0
+        src = [c_vp(None)] * 3
+        if phi is not None:
+            K = int(F2.shape[1])
+            ph = phi if hasattr(phi, 'data_ptr') else self.from_numpy(np.ascontiguousarray(np.asarray(phi, dtype=np.float64)))
+            assert tuple(ph.shape) == (nmu, max(nt, 0) + 1, K), 'phi must be [nmu, nt + 1, K]'
+            ph = ph.contiguous()
+            src = [self._ptr(ph, tuple(ph.shape), 'phi'), self._ptr(F2, (S, K, K), 'F2'),
+                   self._ptr(r_fd_K, (K, S, 5 * Q * N), 'r_fd_K')]
+        u_ptr = self._ptr(U, (max(nt, 0) + 1, S, N, nmu), 'U')
+        need = int(self.lib.lrbms_reduced_parabolic_estimate_batch_work_size(self.handle, N, max(nmu, 1), max(nt, 1)))
+        if need < 0:
+            raise NativeError('reduced_parabolic_estimate_batch: bad N / nmu / nt')
+        if work is None:
+            work = self.empty(need)
+        if work.numel() < need:
+            raise NativeError('reduced_parabolic_estimate_batch: work too small')
+        out = {'eta_loc': self.empty(3, max(nt, 0) + 1, S, nmu), 'time_deriv_nc': self.empty(max(nt, 0), S, nmu),
+               'time_residual': self.empty(max(nt, 0), nmu), 'eta': self.empty(max(nt, 0) + 1, nmu), 'est': self.empty(nmu)}
+        rc = self.lib.lrbms_reduced_parabolic_estimate_batch(
+            self.handle, Q, N, K, nmu, nt, float(dt), _dblp(th), _dblp(cf), int(bool(sqrt_local)), u_ptr,
+            self._ptr(B_sys, (Q, S, 5, N, N), 'B_sys'), self._ptr(M_red, (S, N, N), 'M_red'), *gptrs, self._ptr(f2, (S,), 'f2'),
+            self._ptr(ceps, (S,), 'ceps'), float(hdiam), *src, c_vp(work.data_ptr()), c_vp(out['eta_loc'].data_ptr()),
+            c_vp(out['time_deriv_nc'].data_ptr()), c_vp(out['time_residual'].data_ptr()), c_vp(out['eta'].data_ptr()),
+            c_vp(out['est'].data_ptr()), self._stream())
+        self._check(rc, 'lrbms_reduced_parabolic_estimate_batch')
+        return out
 
     def project_sources(self, Q, b_K, V, D, out=None):
         """b_K [K, S, n], V [S(_ext), n, N], D [S, n_T, 5 Q N] -> (rhs_red_K [K, S, N], r_fd_K [K, S, 5 Q N])."""

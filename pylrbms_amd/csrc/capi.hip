@@ -59,6 +59,14 @@ int launch_reduced_solve_batch_src(lrbms_ctx* ctx, int Q, int N, int K, int nmu,
                                    const double* B_sys, const double* rhs_red_K, double* work, double* u, double rtol, int max_iter,
                                    double* info, hipStream_t st);
 int launch_combine_sources(lrbms_ctx* ctx, int K, long M, const double* phi, const double* x_K, double* y, hipStream_t st);
+int64_t reduced_parabolic_estimate_batch_work_size(lrbms_ctx* ctx, int N, int nmu, int nt);
+int launch_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int Q, int N, int K, int nmu, int nt, double dt, const double* theta,
+                                            const double* coef, int sqrt_local, const double* U, const double* B_sys,
+                                            const double* M_red, const double* G_nc, const double* r_fd, const double* G_rdd,
+                                            const double* G_bb, const double* G_ab, const double* G_aa, const double* Fside,
+                                            const double* Fnc, const double* f2, const double* ceps, double hdiam, const double* phi,
+                                            const double* F2, const double* r_fd_K, double* work, double* eta_loc, double* time_deriv_nc,
+                                            double* time_residual, double* eta, double* est, hipStream_t st);
 void coarse_release(lrbms_ctx* ctx);   // online.hip
 int64_t reduced_precond_size(lrbms_ctx* ctx, int N);
 int launch_reduced_precond_build(lrbms_ctx* ctx, int Q, int N, const double* theta, const double* B_sys, double* work, double* pc,
@@ -787,6 +795,27 @@ int lrbms_reduced_implicit_euler_batch_src(lrbms_ctx* ctx, int32_t Q, int32_t N,
   CHECK_PTR(ctx, rhs_red_K); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
   return launch_reduced_implicit_euler_batch_src(ctx, Q, N, K, nmu, theta, dt, nt, B_sys, M_red, rhs_red_K, phi, work, U, rtol,
                                                  max_iter, info, (hipStream_t)stream);
+}
+
+int64_t lrbms_reduced_parabolic_estimate_batch_work_size(lrbms_ctx* ctx, int32_t N, int32_t nmu, int32_t nt) {
+  if (!ctx || !ctx->has_mesh || N < 1 || nmu < 1 || nt < 1) return -1;
+  return reduced_parabolic_estimate_batch_work_size(ctx, N, nmu, nt);
+}
+
+int lrbms_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, int32_t nt, double dt,
+                                           const double* theta, const double* coef, int32_t sqrt_local, const double* U,
+                                           const double* B_sys, const double* M_red, const double* G_nc_self, const double* r_fd,
+                                           const double* G_rdd_self, const double* G_bb_self, const double* G_ab_self, const double* G_aa,
+                                           const double* F_side, const double* F_nc, const double* f2, const double* ceps, double hdiam,
+                                           const double* phi, const double* F2, const double* r_fd_K, double* work, double* eta_loc,
+                                           double* time_deriv_nc, double* time_residual, double* eta, double* est, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, coef); CHECK_PTR(ctx, U); CHECK_PTR(ctx, B_sys);
+  CHECK_PTR(ctx, M_red); CHECK_PTR(ctx, G_nc_self); CHECK_PTR(ctx, r_fd); CHECK_PTR(ctx, G_rdd_self); CHECK_PTR(ctx, G_bb_self);
+  CHECK_PTR(ctx, G_ab_self); CHECK_PTR(ctx, G_aa); CHECK_PTR(ctx, f2); CHECK_PTR(ctx, ceps); CHECK_PTR(ctx, work); CHECK_PTR(ctx, eta_loc);
+  CHECK_PTR(ctx, time_deriv_nc); CHECK_PTR(ctx, time_residual); CHECK_PTR(ctx, eta); CHECK_PTR(ctx, est);
+  return launch_reduced_parabolic_estimate_batch(ctx, Q, N, K, nmu, nt, dt, theta, coef, sqrt_local, U, B_sys, M_red, G_nc_self, r_fd,
+                                                 G_rdd_self, G_bb_self, G_ab_self, G_aa, F_side, F_nc, f2, ceps, hdiam, phi, F2, r_fd_K, work,
+                                                 eta_loc, time_deriv_nc, time_residual, eta, est, (hipStream_t)stream);
 }
 
 int lrbms_combine_sources(lrbms_ctx* ctx, int32_t K, int64_t M, const double* phi, const double* x_K, double* y, void* stream) {

@@ -3089,3 +3089,402 @@ int launch_reduced_estimate_batch(lrbms_ctx* ctx, int Q, int N, int nmu, const d
   LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
+
+// =========================================================================================================
+// Batched parabolic estimates (lrbms_reduced_parabolic_estimate_batch): ParabolicEstimator.estimate (estimators.py:139-168, without
+// the elliptic reconstruction) for the nmu <= 64 trajectories of ONE panel U [nt+1][S][N][nmu] as lrbms_reduced_implicit_euler_batch
+// wrote it, column m at theta[m].  Everything runs on the caller's stream and nothing comes back to the host:
+//   * elliptic rows: the batched estimate (launch_reduced_estimate_batch, the launches of the existing export) on every slab U[k];
+//   * nc of the differences: k_reduced_nc_diff_mfma forms U[k+1] - U[k] while it fills its LDS panel and evaluates the
+//     nonconformity form alone (G_nc, or G_nc_self + F_nc with the vertex-patch corner terms);
+//   * time residual: k_pe_diff writes the direction panels dU[k] in the layout of the batched solver's groups, the stationary panel
+//     matvec of that solver (bcg_plan / bcg_matvec<false>, first = 1) forms y = sum_q theta_qm B_q dU, k_red_inv_norm2_panel the
+//     column dots y^T M_red[s]^-1 y against ONE block inverse of M_red per call;
+//   * time-dependent source: k_reduced_source_terms_cols, the per-column-theta form of k_reduced_source_terms;
+//   * k_pe_combine: the sums over the subdomains in a fixed order, the scalings and est.
+// Small host tables (theta, coef) travel as kernel arguments: no copy from caller-owned host memory outlives the call.
+namespace {
+
+struct PeTable { double v[256]; };
+
+__global__ __launch_bounds__(256) void k_pe_put(int n, PeTable t, double* __restrict__ dst) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = t.v[threadIdx.x];
+}
+
+// dU[k][row][m] = U[k+1][row][m0 + m] - U[k][row][m0 + m]: the nt direction panels [rows][nm] of one group of columns
+__global__ __launch_bounds__(256) void k_pe_diff(long rows, int nt, int nm, int m0, int nmu, const double* __restrict__ U,
+                                                 double* __restrict__ dU) {
+  const long total = (long)nt * rows * nm;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long kr = i / nm;                              // k rows + row
+    const long src = kr * nmu + m0 + (i - kr * nm);
+    dU[i] = U[src + rows * nmu] - U[src];
+  }
+}
+
+// out[k][s][m0 + m] = sqrt(max(nc_s(U[k+1] - U[k]), 0) / dt) for the nmu <= 16 columns from m0 on: the nonconformity form of
+// k_reduced_estimate_batch_mfma on the difference of two slabs of the panel, formed on the coefficients (grid: S x nt).
+// Fnc == nullptr: G_nc [S][5N][5N]; else G_nc = G_nc_self [S][N][N] and the side terms come from the factors F_nc.
+__global__ __launch_bounds__(64 * EST_NW) void k_reduced_nc_diff_mfma(int S, const int* __restrict__ nbr, int N, int nmu,
+                                                                      const double* __restrict__ U, long slab,
+                                                                      const double* __restrict__ G_nc, const double* __restrict__ Fnc,
+                                                                      int nvs, double inv_dt, double* __restrict__ out, int ldu, int m0,
+                                                                      int nvx_patch, const int* __restrict__ nbr_diag) {
+  extern __shared__ double lds[];
+  const int s = blockIdx.x, step = blockIdx.y, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4, wave = tid >> 6;
+  const double* u0 = U + (long)step * slab;
+  const double* u1 = u0 + slab;
+  const int W = 5 * N;
+  const bool factored = Fnc != nullptr;
+  const int Wp = (W + 3) & ~3, Zp = factored ? (4 * nvs + 3) & ~3 : 0;
+  double* uo = lds;                 // [Wp][16]  U[k+1] - U[k] of the own + neighbour bases (columns >= nmu and pad rows zero)
+  double* red = uo + Wp * 16;       // [EST_NW][16]
+  double* zn = red + EST_NW * 16;   // [Zp][16]  (factored layout) z_a = A_a du_a per side vertex
+  double* dcn = zn + Zp * 16;       // [4][16]   vertex patch: A_diag . du_diag per corner and column
+  for (int i = tid; i < Wp * 16; i += 64 * EST_NW) uo[i] = 0.0;
+  for (int i = tid; i < Zp * 16; i += 64 * EST_NW) zn[i] = 0.0;
+  if (nvx_patch > 0 && tid < 64) {
+    const int corner = tid >> 4, m = tid & 15, side = corner < 2 ? 0 : 3, pos = (corner & 1) ? nvx_patch - 1 : 0;
+    const int sd = nbr[s * 5 + (corner < 2 ? 0 : 4)] >= 0 ? nbr_diag[s * 4 + corner] : -1;
+    double d = 0.0;
+    if (sd >= 0 && m < nmu) {
+      const double* x = Fnc + ((long)s * 4 * nvs + side * nvs + pos) * (3 * N + 4 * nvs) + 2 * N + 4 * nvs;
+      for (int c = 0; c < N; ++c) {
+        const long g = ((long)sd * N + c) * ldu + m0 + m;
+        d += x[c] * (u1[g] - u0[g]);
+      }
+    }
+    dcn[tid] = d;
+  }
+  __syncthreads();
+  for (int i = tid; i < W * nmu; i += 64 * EST_NW) {
+    const int row = i / nmu, m = i - row * nmu, slot = row / N, j = row - slot * N;
+    const int s2 = nbr[s * 5 + slot];
+    if (s2 >= 0) {
+      const long g = ((long)s2 * N + j) * ldu + m0 + m;
+      uo[row * 16 + m] = u1[g] - u0[g];
+    }
+  }
+  __syncthreads();
+  double a_nc = 0.0;
+  const double* ui = uo + 2 * N * 16;
+  int unit = 0;
+  if (factored) {
+    const int LDn = 2 * N + 4 * nvs + (nvx_patch > 0 ? N : 0);
+    for (int side = wave; side < 4; side += EST_NW) {
+      const double* ua = uo + (side < 2 ? side : side + 1) * N * 16;
+      const double* Fn = Fnc + ((long)s * 4 + side) * nvs * LDn;
+      for (int tile = 0; tile * 16 < nvs; ++tile) {
+        const int rr0 = tile * 16 + li < nvs ? tile * 16 + li : nvs - 1;
+        const d4m Tz = tile_mfma(Fn + (long)rr0 * LDn, N, ua, 1.0);
+        const d4m Tc = tile_mfma(Fn + (long)rr0 * LDn + N, N, ui, 1.0);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const int row = tile * 16 + lk + 4 * rr;
+          if (row < nvs) {
+            double zz = Tz[rr];
+            if (nvx_patch > 0 && (side == 0 || side == 3) && (row == 0 || row == nvx_patch - 1))
+              zz += dcn[((side == 0 ? 0 : 2) + (row == 0 ? 0 : 1)) * 16 + li];
+            zn[(side * nvs + row) * 16 + li] = zz;
+            a_nc += 2.0 * zz * Tc[rr];
+          }
+        }
+      }
+    }
+    quad_mfma(G_nc + (long)s * N * N, N, N, N, ui, ui, 1.0, a_nc, unit, factored);
+    __syncthreads();                // the z panel of every side is complete
+    for (int side = wave - 4; side >= 0 && side < 4; side += EST_NW) {
+      const double* Fn = Fnc + ((long)s * 4 + side) * nvs * LDn + 2 * N;
+      for (int tile = 0; tile * 16 < nvs; ++tile) {
+        const int rr0 = tile * 16 + li < nvs ? tile * 16 + li : nvs - 1;
+        const d4m Tm = tile_mfma(Fn + (long)rr0 * LDn, 4 * nvs, zn, 1.0);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const int row = tile * 16 + lk + 4 * rr;
+          if (row < nvs) a_nc += zn[(side * nvs + row) * 16 + li] * Tm[rr];
+        }
+      }
+    }
+  } else {
+    quad_mfma(G_nc + (long)s * W * W, W, W, W, uo, uo, 1.0, a_nc, unit, factored);
+  }
+  for (int off = 32; off >= 16; off >>= 1) a_nc += __shfl_down(a_nc, off, 64);
+  if (lane < 16) red[wave * 16 + lane] = a_nc;
+  __syncthreads();
+  if (tid < nmu) {
+    double nc = 0.0;
+    for (int w = 0; w < EST_NW; ++w) nc += red[w * 16 + tid];
+    out[((long)step * S + s) * ldu + m0 + tid] = sqrt(fmax(nc * inv_dt, 0.0));
+  }
+}
+
+// k_reduced_source_terms with a theta and a source row of its own per column: column (k, m) of the panel U [nt+1][S][N][nmu] uses
+// theta [m][8] (device) and phi [m][k][:] (phi [nmu][nt+1][K]); out [nt+1][S][nmu].  Grid: S x (nt + 1), one wave per column.
+__global__ __launch_bounds__(256) void k_reduced_source_terms_cols(int S, const int* __restrict__ nbr, int Q, int N, int K, int nmu, int nt1,
+                                                                   const double* __restrict__ theta, const double* __restrict__ phi,
+                                                                   const double* __restrict__ F2, const double* __restrict__ r_fd_K,
+                                                                   const double* __restrict__ U, const double* __restrict__ ceps,
+                                                                   double hdiam, double* __restrict__ out) {
+  const int s = blockIdx.x, step = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int QN = Q * N, C = 5 * QN;
+  const double pi = 3.14159265358979323846;
+  const double scale = ((1.0 / (pi * pi)) / ceps[s]) * hdiam * hdiam;
+  const double* u = U + (long)step * S * N * nmu;
+  for (int l = wave; l < nmu; l += 4) {
+    const double* ph = phi + ((long)l * nt1 + step) * K;
+    const double* th = theta + l * 8;
+    double lin = 0.0;
+    for (int c = lane; c < C; c += 64) {
+      const int slot = c / QN, rem = c - slot * QN, q = rem / N, i = rem - q * N;
+      const int s2 = nbr[s * 5 + slot];
+      if (s2 < 0) continue;
+      const double w = th[q] * u[((long)s2 * N + i) * nmu + l];
+      double g = 0.0;
+      for (int j = 0; j < K; ++j) g += ph[j] * r_fd_K[((long)j * S + s) * C + c];
+      lin += g * w;
+    }
+    for (int off = 32; off > 0; off >>= 1) lin += __shfl_down(lin, off, 64);
+    if (lane == 0) {
+      const double* F = F2 + (long)s * K * K;
+      double quad = 0.0;
+      for (int j = 0; j < K; ++j)
+        for (int m = 0; m < K; ++m) quad += ph[j] * F[j * K + m] * ph[m];
+      out[((long)step * S + s) * nmu + l] = (quad - 2.0 * lin) * scale;
+    }
+  }
+}
+
+// out[k][s][m0 + m] = y_m^T Minv[s] y_m for the panels y [nt][S][N][nm] of one group of columns (grid: S x nt): z = Minv[s] y in
+// LDS, the products per entry, then the column sums over the rows in ascending order.
+__global__ __launch_bounds__(256) void k_red_inv_norm2_panel(int S, int N, int nm, int m0, int nmu, const double* __restrict__ Minv,
+                                                             const double* __restrict__ y, double* __restrict__ out) {
+  extern __shared__ double lds[];
+  const int s = blockIdx.x, step = blockIdx.y, tid = threadIdx.x, NM = N * nm;
+  double* yl = lds;                 // [N][nm]
+  double* pr = yl + NM;             // [N][nm]  z[r][m] y[r][m]
+  const double* ys = y + ((long)step * S + s) * NM;
+  for (int i = tid; i < NM; i += 256) yl[i] = ys[i];
+  __syncthreads();
+  const double* Ms = Minv + (long)s * N * N;
+  for (int i = tid; i < NM; i += 256) {
+    const int r = i / nm, m = i - r * nm;
+    double z = 0.0;
+    for (int c = 0; c < N; ++c) z += Ms[r * N + c] * yl[c * nm + m];
+    pr[i] = z * yl[i];
+  }
+  __syncthreads();
+  if (tid < nm) {
+    double sum = 0.0;
+    for (int r = 0; r < N; ++r) sum += pr[r * nm + tid];
+    out[((long)step * S + s) * nmu + m0 + tid] = sum;
+  }
+}
+
+struct PeCoef { double v[128]; };   // [m][2]: sqrt(gamma_bar / alpha_bar), 1 / sqrt(alpha_hat alpha_bar)
+
+// The host half of ParabolicEstimator.estimate for 16 columns per workgroup (thread = (s mod 16, column)): per step the sums over
+// the subdomains (16 strided partials, then their sum in ascending order), eta[k], time_residual[k] and est.
+//   raw [nt+1][3][S][nmu] (the batched estimate per slab), src [nt+1][S][nmu] or nullptr (added to the r row),
+//   trp [nt][S][nmu] (y^T M_red[s]^-1 y), tdn [nt][S][nmu] = time_deriv_nc (read only).
+__global__ __launch_bounds__(256) void k_pe_combine(int S, int nmu, int nt, double dt, int sqrt_local, PeCoef coef,
+                                                    const double* __restrict__ raw, const double* __restrict__ src,
+                                                    const double* __restrict__ trp, const double* __restrict__ tdn,
+                                                    double* __restrict__ eta_loc, double* __restrict__ time_residual,
+                                                    double* __restrict__ eta, double* __restrict__ est) {
+  __shared__ double red[4][16][16];
+  const int ml = threadIdx.x & 15, sl = threadIdx.x >> 4, m = blockIdx.x * 16 + ml;
+  const bool valid = m < nmu;
+  const double sc = 2.0 * sqrt(dt / 3.0);
+  const long SM = (long)S * nmu, row = (long)(nt + 1) * SM;
+  double eta2 = 0.0, tr2 = 0.0, nc2 = 0.0;
+  for (int k = 0; k <= nt; ++k) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    if (valid)
+      for (int s = sl; s < S; s += 16) {
+        const long o = (long)s * nmu + m;
+        double nc = raw[(long)(3 * k) * SM + o], r = raw[(long)(3 * k + 1) * SM + o], df = raw[(long)(3 * k + 2) * SM + o];
+        if (src) r += src[(long)k * SM + o];
+        if (sqrt_local) {
+          nc = sqrt(fabs(nc));
+          r = sqrt(fabs(r));
+          df = sqrt(fabs(df));
+        }
+        a0 += nc * nc;
+        a1 += (r + df) * (r + df);
+        eta_loc[(long)k * SM + o] = nc * sc;
+        eta_loc[row + (long)k * SM + o] = r * sc;
+        eta_loc[2 * row + (long)k * SM + o] = df * sc;
+        if (k < nt) {
+          a2 += trp[(long)k * SM + o];
+          const double v = tdn[(long)k * SM + o];
+          a3 += v * v;
+        }
+      }
+    red[0][sl][ml] = a0;
+    red[1][sl][ml] = a1;
+    red[2][sl][ml] = a2;
+    red[3][sl][ml] = a3;
+    __syncthreads();
+    if (sl == 0 && valid) {
+      double A0 = 0.0, A1 = 0.0, A2 = 0.0, A3 = 0.0;
+      for (int j = 0; j < 16; ++j) {
+        A0 += red[0][j][ml];
+        A1 += red[1][j][ml];
+        A2 += red[2][j][ml];
+        A3 += red[3][j][ml];
+      }
+      const double e = (coef.v[2 * m] * sqrt(A0) + coef.v[2 * m + 1] * sqrt(A1)) * sc;
+      eta[(long)k * nmu + m] = e;
+      eta2 += e * e;
+      if (k < nt) {
+        const double tr = sqrt(A2 * (dt / 3.0));
+        time_residual[(long)k * nmu + m] = tr;
+        tr2 += tr * tr;
+        nc2 += A3;
+      }
+    }
+    __syncthreads();
+  }
+  if (sl == 0 && valid) est[m] = sqrt(eta2) + sqrt(tr2) + sqrt(nc2);
+}
+
+// the layout of the work array (doubles)
+struct PeWork {
+  long minv, zero, raw, src, trp, du, y, pout, partial, scal, theta_dev, theta_cols, total;
+};
+
+PeWork pe_work(long S, int N, int nmu, int nt) {
+  PeWork w;
+  long o = 0;
+  w.minv = o;       o += S * N * N;
+  w.zero = o;       o += S + S * 5 * 8 * N;               // f2 = 0 and r_fd = 0 (Q <= 8) beside a time-dependent source
+  w.raw = o;        o += (long)(nt + 1) * 3 * S * nmu;
+  w.src = o;        o += (long)(nt + 1) * S * nmu;
+  w.trp = o;        o += (long)nt * S * nmu;
+  w.du = o;         o += (long)nt * S * N * nmu;
+  w.y = o;          o += (long)nt * S * N * nmu;
+  w.pout = o;       o += S * N * BMAX;
+  w.partial = o;    o += S * BMAX;
+  w.scal = o;       o += 4 * BMAX;
+  w.theta_dev = o;  o += 8 * BMAX;
+  w.theta_cols = o; o += 8 * BMAX;
+  w.total = o + 16;
+  return w;
+}
+
+}  // namespace
+
+int64_t reduced_parabolic_estimate_batch_work_size(lrbms_ctx* ctx, int N, int nmu, int nt) { return pe_work(ctx->S, N, nmu, nt).total; }
+
+int launch_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int Q, int N, int K, int nmu, int nt, double dt, const double* theta,
+                                            const double* coef, int sqrt_local, const double* U, const double* B_sys,
+                                            const double* M_red, const double* G_nc, const double* r_fd, const double* G_rdd,
+                                            const double* G_bb, const double* G_ab, const double* G_aa, const double* Fside,
+                                            const double* Fnc, const double* f2, const double* ceps, double hdiam, const double* phi,
+                                            const double* F2, const double* r_fd_K, double* work, double* eta_loc, double* time_deriv_nc,
+                                            double* time_residual, double* eta, double* est, hipStream_t st) {
+  const std::string name = "reduced_parabolic_estimate_batch";
+  // ---- every refusal, ahead of the first launch
+  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, name + " needs all subdomains on one rank (S_ext == S)");
+  if (nmu < 1 || nmu > 64 || N < 1 || N > 64 || nt < 1 || !(dt > 0.0))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": need 1 <= nmu <= 64, N <= 64, nt >= 1, dt > 0");
+  if (Q < 1 || Q > 8 || (nmu > 16 && Q > 4)) return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": need Q <= 8, Q <= 4 for more than 16 columns");
+  if (K < 0 || K > 64 || (K > 0 && (!phi || !F2 || !r_fd_K)))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": need 0 <= K <= 64, and phi, F2 and r_fd_K with K >= 1");
+  if ((Fside != nullptr) != (Fnc != nullptr)) return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": F_side and F_nc go together");
+  if (ctx->t.opt_oswald_vertex && Fnc == nullptr)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "LRBMS_OPT_OSWALD_VERTEX_PATCH: " + name + " needs the factored layout");
+  const int S = ctx->S;
+  const int nvs = ctx->t.nvx > ctx->t.nvy ? ctx->t.nvx : ctx->t.nvy;
+  {
+    const int nm = nmu < EB ? nmu : EB;                  // the LDS of the elliptic passes (launch_reduced_estimate_batch)
+    const size_t lds = sizeof(double) * ((size_t)(5 * N + 5 * Q * N) * nm + 8 * EB + 4 * 3 * EB);
+    const size_t ldm = sizeof(double) * ((size_t)(((5 * N + 3) & ~3) + (Fside ? ((Q * N + 3) & ~3) + ((4 * nvs + 3) & ~3) : (5 * Q * N + 3) & ~3)) * 16 +
+                                         EST_NW * 3 * 16 + 64);
+    if (lds > 160 * 1024 || ((Fside != nullptr || ctx->opt_estimate_valu == 0) && ldm > 160 * 1024))
+      return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": coefficient panels exceed the LDS");
+  }
+  const size_t lds_nc = sizeof(double) * ((size_t)(((5 * N + 3) & ~3) + EST_NW + (Fnc ? (4 * nvs + 3) & ~3 : 0)) * 16 + 64);
+  if (lds_nc > 160 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": coefficient panels exceed the LDS");
+  const int GW = reduced_batch_group_width(ctx, nmu);
+  const int ng = (nmu + GW - 1) / GW;
+  BcgPlan P;
+  if (int rc = bcg_plan(ctx, name, N, GW, false, P)) return rc;
+  if (lds_nc > 64 * 1024)
+    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_reduced_nc_diff_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nc));
+
+  const PeWork w = pe_work(S, N, nmu, nt);
+  const long rows = (long)S * N, SM = (long)S * nmu;
+  double* Minv = work + w.minv;
+  const double* f2_e = f2;
+  const double* r_fd_e = r_fd;
+  if (K > 0) {                                           // the source rows come from k_reduced_source_terms_cols
+    LRBMS_HIP_CHECK(ctx, hipMemsetAsync(work + w.zero, 0, sizeof(double) * ((size_t)S + (size_t)S * 5 * Q * N), st));
+    f2_e = work + w.zero;
+    r_fd_e = work + w.zero + S;
+  }
+  // ---- elliptic rows: the batched estimate on every slab
+  for (int k = 0; k <= nt; ++k)
+    if (int rc = launch_reduced_estimate_batch(ctx, Q, N, nmu, theta, U + (long)k * rows * nmu, G_nc, r_fd_e, G_rdd, G_bb, G_ab, G_aa, Fside,
+                                               Fnc, f2_e, ceps, hdiam, work + w.raw + (long)k * 3 * SM, st))
+      return rc;
+  // ---- nc of the differences
+  for (int m0 = 0; m0 < nmu; m0 += EB) {
+    const int nm = nmu - m0 < EB ? nmu - m0 : EB;
+    hipLaunchKernelGGL(k_reduced_nc_diff_mfma, dim3(S, nt), dim3(64 * EST_NW), lds_nc, st, S, ctx->nbr, N, nm, U, rows * nmu, G_nc, Fnc, nvs,
+                       1.0 / dt, time_deriv_nc, nmu, m0, ctx->t.opt_oswald_vertex ? ctx->t.nvx : 0, ctx->t.nbr_diag);
+  }
+  LRBMS_LAUNCH_CHECK(ctx);
+  // ---- time residual
+  if (int rc = launch_block_inverse(ctx, S, N, M_red, Minv, 1, 0, st)) return rc;
+  const BcgOp op{Q, B_sys, nullptr, nullptr, nullptr};
+  for (int k = 0; k < ng; ++k) {
+    BcgGroup G;
+    bcg_group(G, P, k, nmu, Q, theta, 1.0, work + w.pout, st);
+    G.ug = G.r = G.z = G.partial2 = G.ref2 = nullptr;    // (no iteration here: one matvec per step)
+    G.pout = work + w.pout;
+    G.partial = work + w.partial;
+    G.scal = work + w.scal;
+    G.theta_dev = work + w.theta_dev;
+    const long vec = rows * G.nm;
+    double* dUg = work + w.du + (long)nt * rows * G.m0;
+    double* yg = work + w.y + (long)nt * rows * G.m0;
+    G.pin = dUg;                                         // p_old of a first = 1 launch: loaded and dropped, never written
+    if (GW > 16)
+      for (int h = 0; h < 2; ++h) {
+        PeTable t;
+        for (int i = 0; i < 256; ++i) t.v[i] = G.thd[256 * h + i];
+        hipLaunchKernelGGL(k_pe_put, dim3(1), dim3(256), 0, st, 256, t, G.theta_dev + 256 * h);
+      }
+    const long total = (long)nt * vec;
+    hipLaunchKernelGGL(k_pe_diff, dim3((unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0, st, rows, nt,
+                       G.nm, G.m0, nmu, U, dUg);
+    for (int step = 0; step < nt; ++step) {
+      G.y = yg + (long)step * vec;
+      bcg_matvec<false>(ctx, P, op, G, dUg + (long)step * vec, 1);
+    }
+    hipLaunchKernelGGL(k_red_inv_norm2_panel, dim3(S, nt), dim3(256), sizeof(double) * 2 * N * G.nm, st, S, N, G.nm, G.m0, nmu, Minv, yg,
+                       work + w.trp);
+    LRBMS_LAUNCH_CHECK(ctx);
+  }
+  // ---- time-dependent source
+  if (K > 0) {
+    for (int h = 0; h < 2; ++h) {
+      PeTable t;
+      for (int i = 0; i < 256; ++i) {
+        const int m = (256 * h + i) / 8, q = i % 8;
+        t.v[i] = (m < nmu && q < Q) ? theta[m * Q + q] : 0.0;
+      }
+      hipLaunchKernelGGL(k_pe_put, dim3(1), dim3(256), 0, st, 256, t, work + w.theta_cols + 256 * h);
+    }
+    hipLaunchKernelGGL(k_reduced_source_terms_cols, dim3(S, nt + 1), dim3(256), 0, st, S, ctx->nbr, Q, N, K, nmu, nt + 1,
+                       work + w.theta_cols, phi, F2, r_fd_K, U, ceps, hdiam, work + w.src);
+  }
+  // ---- combine
+  PeCoef cf;
+  for (int i = 0; i < 128; ++i) cf.v[i] = i < 2 * nmu ? coef[i] : 0.0;
+  hipLaunchKernelGGL(k_pe_combine, dim3((nmu + 15) / 16), dim3(256), 0, st, S, nmu, nt, dt, sqrt_local, cf, work + w.raw,
+                     K > 0 ? work + w.src : (const double*)nullptr, work + w.trp, time_deriv_nc, eta_loc, time_residual, eta, est);
+  LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}

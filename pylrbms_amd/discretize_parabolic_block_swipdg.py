@@ -171,9 +171,10 @@ def _setup_sources(d, funcs, coeffs):
 
 
 def discretize(grid_and_problem_data, T, nt, solver_options=None, mpi_comm=None, device_index=None,
-               elliptic_reconstruction=False):
+               elliptic_reconstruction=False, conventions=None):
     """Reference :43-95.  Returns ``(d, d_data)``.  ``p['f']`` may be ``{'functions': [...], 'coefficients': [...]}`` with any
-    number of components and coefficients of ``mu`` and ``'_t'`` (module docstring)."""
+    number of components and coefficients of ``mu`` and ``'_t'`` (module docstring).  ``conventions``: the switches of the elliptic
+    ``discretize`` (e.g. ``{'oswald_vertex_patch': True}``), handed on to it."""
     src = _source_components(grid_and_problem_data)
     if src is not None:
         from pylrbms_amd.functions import SumFunction
@@ -185,7 +186,7 @@ def discretize(grid_and_problem_data, T, nt, solver_options=None, mpi_comm=None,
         # the elliptic discretization is built on sum_j f_j (its quadrature orders cover every component); its own b / f2
         # are not read on this path
         grid_and_problem_data = dict(grid_and_problem_data, f=SumFunction(src[0], [1.0] * len(src[0]), name='f_sum'))
-    d, d_data = discretize_ell(grid_and_problem_data, solver_options, mpi_comm, device_index=device_index)
+    d, d_data = discretize_ell(grid_and_problem_data, solver_options, mpi_comm, device_index=device_index, conventions=conventions)
     assert isinstance(d.parameter_space, CubicParameterSpace)              # :45
     d.__class__ = InstationaryDuneDiscretization
     d.T = float(T)

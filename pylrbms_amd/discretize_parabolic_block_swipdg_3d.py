@@ -204,6 +204,13 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
         tr2 = eng.ctx.reduced_time_residual(Q, theta, self.out['B_sys'], self.M_red, du).sum(dim=1).cpu().numpy()
         return _parabolic_estimate(d, mu, self.dt, eta_loc, tr2, tdnc2)
 
+    def estimate_batch(self, U, mus, decompose=False):
+        """The estimates of the trajectories U [len(mus), nt + 1, S, N] (as ``solve_batch`` returns them): the list of
+        ``estimate(U[m], mus[m])``.  A loop -- the native batch over trajectories is not built for the 3D path; the stationary
+        method this class inherits takes one solution per parameter, not a trajectory."""
+        assert len(U) == len(mus), 'estimate_batch: one trajectory per parameter'
+        return [self.estimate(U[m], mu, decompose=decompose) for m, mu in enumerate(mus)]
+
 
 class ParabolicLRBMSReductor3D(LRBMSReductor3D):
     """``ParabolicLRBMSReductor`` (2D: pylrbms_amd.reductor) for the 3D path.  ``extend_basis`` takes a trajectory [S, n, L]: its

@@ -317,6 +317,63 @@ class ReducedDiscretization:
         return self.estimator.estimate(U, self.parse_parameter(mu), self, decompose=decompose)
 
 
+    def estimate_batch(self, U, mus, decompose=False):
+        """``estimate`` for a parameter sweep: ``U`` holds one solution per parameter -- the array ``solve_batch(mus)`` returns
+        (``len(mus)`` vectors), a tensor ``[len(mus), S, N]`` or a list of single-vector arrays --, 64 parameters per
+        ``lrbms_reduced_estimate_batch`` call (plus ``lrbms_reduced_source_terms`` with an affine source).  Returns the list of what
+        ``estimate(U_m, mu_m, decompose=decompose)`` returns."""
+        torch = self._torch
+        eng = self.d.engine
+        mus = [self.parse_parameter(mu) for mu in mus]
+        if isinstance(U, (list, tuple)):
+            u_all = torch.cat([(u.tensor if hasattr(u, 'tensor') else u.reshape(eng.S, self.N, 1)) for u in U], dim=2)
+        elif hasattr(U, 'tensor'):
+            u_all = U.tensor                                               # [S, N, len(mus)]
+        else:
+            u_all = U.permute(1, 2, 0)                                     # [len(mus), S, N]
+        assert tuple(u_all.shape) == (eng.S, self.N, len(mus)), 'estimate_batch: one solution per parameter'
+        if eng.S_ext != eng.S:
+            return [self.estimate(ReducedVectorArray(u_all[:, :, m:m + 1].contiguous()), mu, decompose=decompose)
+                    for m, mu in enumerate(mus)]
+        est = self.estimator
+        affine = self._affine()
+        grams = list(self.grams)
+        f2 = eng.f2
+        if affine:
+            grams[1] = torch.zeros_like(grams[1])
+            f2 = eng.ctx.zeros(eng.S)
+        cols = []
+        for b0 in range(0, len(mus), 64):
+            chunk = mus[b0:b0 + 64]
+            u = u_all[:, :, b0:b0 + len(chunk)].contiguous()
+            thetas = np.array([self.d.theta(mu) for mu in chunk])
+            eta = eng.ctx.reduced_estimate_batch(thetas, u, tuple(grams), f2, eng.ceps, eng.hdiam)
+            if affine:                                                     # the source rows: theta enters, so one call per parameter
+                for m, mu in enumerate(chunk):
+                    eta[1, :, m:m + 1] += eng.ctx.reduced_source_terms(thetas[m], self.d.f_coefficients(mu)[None], self.d._affine_f['F2'],
+                                                                       self.r_fd_K, u[:, :, m:m + 1].contiguous(), eng.ceps, eng.hdiam)
+            cols.append(eta)
+        eta = torch.cat(cols, dim=2)                                       # [3, S, len(mus)]
+        if est.sqrt_local:
+            eta = eta.abs().sqrt()
+        sq = torch.stack([(eta[0] ** 2).sum(dim=0), ((eta[1] + eta[2]) ** 2).sum(dim=0)]).sqrt().cpu().numpy()      # ONE copy
+        loc = eta.cpu().numpy() if decompose else None
+        out = []
+        for m, mu in enumerate(mus):
+            alpha_bar = est.alpha(est.lambda_coeffs, mu, est.mu_bar)
+            gamma_bar = est.gamma(est.lambda_coeffs, mu, est.mu_bar)
+            alpha_hat = est.alpha(est.lambda_coeffs, mu, est.mu_hat)
+            e = (np.sqrt(gamma_bar) * float(sq[0, m]) + (1. / np.sqrt(alpha_hat)) * float(sq[1, m])) * 1. / np.sqrt(alpha_bar)
+            if not decompose:
+                out.append(e)
+                continue
+            nc, r, df = (np.ascontiguousarray(loc[i][:, m:m + 1]) for i in range(3))
+            ind = np.array([(2. / alpha_bar) * (gamma_bar * nc[ii] ** 2 + (1. / alpha_hat) * (r[ii] + df[ii]) ** 2)
+                            for ii in range(est.num_subdomains)])
+            out.append((e, (nc, r, df), ind))
+        return out
+
+
 class LRBMSReductor(LocalBasisSlab):
 
     def __init__(self, d, bases=None, products=None, order=None, num_cpus=1, solver_options=None):
@@ -558,7 +615,8 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
     def solve_batch(self, mus):
         """Parameter sweep over the parabolic reduced model: one ``lrbms_reduced_implicit_euler_batch(_src)`` call per 64
         parameters (every time step is one panel PCG for all of them); returns a list with, per parameter, the
-        ``ReducedVectorArray`` that ``solve(mu)`` returns, so ``estimate(U_m, mu_m)`` takes an entry as it is."""
+        ``ReducedVectorArray`` that ``solve(mu)`` returns, so ``estimate(U_m, mu_m)`` takes an entry as it is.  The entries of a
+        call are views of its panel ``[nt + 1, S, N, nmu]`` (column m): ``estimate_batch`` takes the panel back without a copy."""
         eng = self.d.engine
         if eng.S_ext != eng.S:
             raise NotImplementedError('solve_batch of the parabolic reduced model needs all subdomains on one rank '
@@ -576,8 +634,72 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
             else:
                 U, info = eng.ctx.reduced_implicit_euler_batch(thetas, dt, nt, self.B_sys, self.M_red, self.rhs_red)
             its, rel = its + info['iterations'], max(rel, info['relative_residual'])
-            out += [ReducedVectorArray(U[..., m].permute(1, 2, 0)) for m in range(len(chunk))]
+            out += [ReducedVectorArray.view_of(U[..., m].permute(1, 2, 0)) for m in range(len(chunk))]     # views of ONE panel
         self.last_solve_info = {'iterations': its, 'relative_residual': rel}
+        return out
+
+    def _panel_of(self, Us):
+        """The panel [nt + 1, S, N, len(Us)] of a chunk of trajectories: the entries' own storage when they are the column views
+        ``solve_batch`` built on one panel (no copy), otherwise stacked."""
+        torch = self._torch
+        nt1, S, N, nmu = self.time_stepper.nt + 1, self.d.engine.S, self.N, len(Us)
+        ts = [u.tensor if hasattr(u, 'tensor') else u for u in Us]
+        for t in ts:
+            assert tuple(t.shape) == (S, N, nt1), 'estimate_batch: every trajectory is [S, N, nt + 1]'
+        base = getattr(ts[0], '_base', None)
+        if (base is not None and tuple(base.shape) == (nt1, S, N, nmu) and base.is_contiguous()
+                and all(getattr(t, '_base', None) is base and t.stride() == (N * nmu, nmu, S * N * nmu)
+                        and t.data_ptr() == base.data_ptr() + m * base.element_size() for m, t in enumerate(ts))):
+            return base
+        return torch.stack([t.permute(2, 0, 1) for t in ts], dim=3).contiguous()
+
+    def estimate_batch(self, Us, mus):
+        """The parabolic estimates of a parameter sweep in one native call per 64 parameters (``lrbms_reduced_parabolic_estimate_batch``;
+        DESIGN.md 5.4.4).  ``Us``: the list ``solve_batch(mus)`` returned (its entries are views of one panel, which is used without
+        a copy) or a panel tensor ``[nt + 1, S, N, len(mus)]``.  Returns the list of what ``estimate(U_m, mu_m)`` returns:
+        ``(est, (local_eta_nc [S, nt + 1], local_eta_r, local_eta_df, time_residual [nt], time_deriv_nc [S, nt]))`` as NumPy
+        arrays; everything stays on the device until ONE copy per output at the end.  With ``estimator.elliptic_reconstruction`` the
+        per-trajectory loop runs instead."""
+        eng = self.d.engine
+        if eng.S_ext != eng.S:
+            raise NotImplementedError('estimate_batch of the parabolic reduced model needs all subdomains on one rank '
+                                      '(lrbms_reduced_parabolic_estimate_batch: S_ext == S); estimate(U, mu) works on a sharded '
+                                      'discretization')
+        mus = [self.parse_parameter(mu) for mu in mus]
+        est = self.estimator
+        nt = self.time_stepper.nt
+        dt = self.T / nt
+        panel = None
+        if not isinstance(Us, (list, tuple)):
+            panel = Us
+            assert tuple(panel.shape) == (nt + 1, eng.S, self.N, len(mus)), 'estimate_batch: the panel is [nt + 1, S, N, len(mus)]'
+        else:
+            assert len(Us) == len(mus), 'estimate_batch: one trajectory per parameter'
+        if getattr(est, 'elliptic_reconstruction', False) or self._affine():
+            if panel is not None:
+                Us = [ReducedVectorArray.view_of(panel[..., m].permute(1, 2, 0)) for m in range(len(mus))]
+            return [self.estimate(U, mu) for U, mu in zip(Us, mus)]
+        out = []
+        for b0 in range(0, len(mus), 64):
+            chunk = mus[b0:b0 + 64]
+            U = panel[..., b0:b0 + len(chunk)].contiguous() if panel is not None else self._panel_of(Us[b0:b0 + len(chunk)])
+            thetas = np.array([self.d.theta(mu) for mu in chunk])
+            coef = np.empty((len(chunk), 2))
+            for m, mu in enumerate(chunk):
+                alpha_bar = est.alpha(est.lambda_coeffs, mu, est.mu_bar)
+                gamma_bar = est.gamma(est.lambda_coeffs, mu, est.mu_bar)
+                alpha_hat = est.alpha(est.lambda_coeffs, mu, est.mu_hat)
+                coef[m] = np.sqrt(gamma_bar) / np.sqrt(alpha_bar), (1. / np.sqrt(alpha_hat)) / np.sqrt(alpha_bar)
+            src = {}
+            if self.rhs_red_K is not None:
+                src = dict(phi=self._torch.stack([self.d._phi_device(mu) for mu in chunk]).contiguous(), F2=self.d._src['F2'],
+                           r_fd_K=self.r_fd_K)
+            res = eng.ctx.reduced_parabolic_estimate_batch(thetas, coef, dt, nt, U, self.B_sys, self.M_red, self.grams, eng.f2, eng.ceps,
+                                                           eng.hdiam, sqrt_local=est.sqrt_local, **src)
+            loc, tdn, tr, e = (res[k].cpu().numpy() for k in ('eta_loc', 'time_deriv_nc', 'time_residual', 'est'))
+            for m in range(len(chunk)):
+                out.append((float(e[m]), tuple(np.ascontiguousarray(loc[i, :, :, m].T) for i in range(3))
+                            + (np.ascontiguousarray(tr[:, m]), np.ascontiguousarray(tdn[:, :, m].T))))
         return out
 
     def _local_estimates(self, U, mu):

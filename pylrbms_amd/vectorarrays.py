@@ -100,6 +100,15 @@ class ReducedVectorArray:
         assert tensor.dim() == 3
         self._t = tensor.contiguous()
 
+    @classmethod
+    def view_of(cls, tensor):
+        """The array on ``tensor`` [num_blocks, N, len] as it is, without the copy to a contiguous layout: a column of the panel of
+        a batched solve stays a view of the panel (``InstationaryReducedDiscretization.solve_batch`` / ``estimate_batch``)."""
+        assert tensor.dim() == 3
+        out = cls.__new__(cls)
+        out._t = tensor
+        return out
+
     def __len__(self):
         return int(self._t.shape[2])
 
