@@ -308,7 +308,10 @@ void* lrbms_ctx_aux_stream(lrbms_ctx* ctx, int32_t i);
  *                              note at lrbms_assemble_rhs.  0: rebuilt in every pass (the same bits), and the exports read
  *                              nothing of an earlier call.  0 is the safe setting for a caller that modifies assembled arrays in place by other
  *                              means than the assembly exports (the library cannot see such a write) or frees them between
- *                              assembly calls */
+ *                              assembly calls
+ *   LRBMS_OPT_THIN_MERGE       1 (default): in the factored layout the three thin side kernels share one launch (k_thin3); 0: they
+ *                              are launched one after the other (k_thin_ncf, k_thin_rt, k_coupling) unless the pass forks
+ *                              (LRBMS_OPT_STREAMS) -- the same bits; the cross-check of the merged kernel against its parts */
 #define LRBMS_OPT_STREAMS 3
 #define LRBMS_OPT_F1_KSPLIT 4
 #define LRBMS_OPT_F1_FORM 5
@@ -318,6 +321,7 @@ void* lrbms_ctx_aux_stream(lrbms_ctx* ctx, int32_t i);
 #define LRBMS_OPT_PREP_LDS 10
 #define LRBMS_OPT_F2_FORM 11
 #define LRBMS_OPT_SIDE_TABLES 12
+#define LRBMS_OPT_THIN_MERGE 13
 int lrbms_ctx_set_option(lrbms_ctx* ctx, int32_t option, int32_t value);
 
 /* LRBMS_OPT_OSWALD_VERTEX_PATCH on sharded grids: nbr_diag [S][4] (host) = index into the S_ext slabs of the diagonal neighbour

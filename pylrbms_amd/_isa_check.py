@@ -7,6 +7,9 @@ vector-memory instruction of its own (load, store, scratch spill) between issue 
 (iii) the kernels neither spill VGPRs nor use scratch.  This module checks exactly that on the gfx950 assembly hipcc
 emits for the product build (``hipcc -S --cuda-device-only``), runs on the CPU box (no GPU needed) from
 ``_build.build_native`` and from tests/test_capi_symbols.py.
+
+It also keeps the register count of the merged thin kernel below the line at which its fifth workgroup per CU is lost
+(``check_thin_registers``, from the kernel descriptors alone).
 """
 import re
 
@@ -203,11 +206,59 @@ def _inflight_register_hazards(lines, tags, region=None, max_states=400000, prol
     return sorted(bad)
 
 
+THIN_VGPR_LIMIT = 96      # 512 registers per SIMD lane, allocated in granules of 8: at most 96 for five waves per SIMD
+THIN_KERNELS = ('k_thin3<1>', 'k_thin3<2>', 'k_thin3<3>', 'k_thin_ncf')
+
+
+def _descriptors(text):
+    """{kernel symbol: {field: value}} of the ``.amdhsa_kernel`` blocks (the kernel descriptors) of an assembly text."""
+    out = {}
+    for m in re.finditer(r'^\s*\.amdhsa_kernel\s+(\S+)\s*\n(.*?)^\s*\.end_amdhsa_kernel', text, re.S | re.M):
+        out[m.group(1)] = {k: int(v) for k, v in re.findall(r'^\s*\.amdhsa_(\w+)\s+(\d+)\s*$', m.group(2), re.M)}
+    return out
+
+
+def check_thin_registers(text):
+    """k_thin3<1..3> and k_thin_ncf are 256-thread workgroups, one wave per SIMD, and their LDS admits five of them per CU: the
+    fifth is resident only while a wave takes at most 96 registers of the unified file -- ``next_free_vgpr`` of the kernel
+    descriptor, which counts the accumulation registers behind ``accum_offset`` as well (k_thin3 was at 104 + 8 and ran four) --
+    and no scratch.  Reads the descriptors' register and scratch fields only; raises IsaCheckError, returns a report."""
+    found, problems, report = {}, [], []
+    for name, d in _descriptors(text).items():
+        m = re.search(r'\dk_thin3ILi([123])E', name)
+        kernel = 'k_thin3<{}>'.format(m.group(1)) if m else ('k_thin_ncf' if re.search(r'\dk_thin_ncfE', name) else None)
+        if kernel is None:
+            continue
+        found[kernel] = d
+        regs, scratch = d.get('next_free_vgpr'), d.get('private_segment_fixed_size')
+        if regs is None or scratch is None:
+            problems.append('{}: descriptor without next_free_vgpr / private_segment_fixed_size'.format(kernel))
+            continue
+        if regs > THIN_VGPR_LIMIT:
+            problems.append('{}: next free VGPR {} > {} (accum_offset {}): four workgroups per CU instead of five'.format(
+                kernel, regs, THIN_VGPR_LIMIT, d.get('accum_offset')))
+        if scratch:
+            problems.append('{}: {} bytes of scratch per lane'.format(kernel, scratch))
+        report.append('{}: next free VGPR {}, accum_offset {}, scratch {}'.format(kernel, regs, d.get('accum_offset'), scratch))
+    for kernel in THIN_KERNELS:
+        if kernel not in found:
+            problems.append('no kernel descriptor of {} found'.format(kernel))
+    if problems:
+        raise IsaCheckError('thin-kernel register check failed:\n  ' + '\n  '.join(problems))
+    return sorted(report)
+
+
 def check_fused_isa(asm_path):
-    """Raises IsaCheckError when the emitted code breaks an assumption of the asm-managed prefetch; returns a report."""
+    """Raises IsaCheckError when the emitted code breaks an assumption of the asm-managed prefetch, or when a thin kernel has
+    outgrown its five workgroups per CU (check_thin_registers); returns a report."""
     fns = _functions(asm_path)
     meta = _metadata(asm_path)
     report, problems = [], []
+    with open(asm_path) as fh:
+        try:
+            report += check_thin_registers(fh.read())
+        except IsaCheckError as exc:
+            problems.append(str(exc))
     seen = 0
     for name, lines in fns.items():
         m = re.search(r'\dk_f(1u|1v|1|2g|2)I((?:Li\d+E)+)E', name) or re.search(r'\dk_f(1w)()E4Tmpl', name)      # (k_f1w is no template)

@@ -251,7 +251,8 @@ class NativeContext(ContextBase):
                # launch policy (no numerical convention): the library reads no environment variable
                'streams': 3, 'f1_ksplit': 4, 'f1_form': 5, 'coarse': 6, 'solve_valu': 7, 'estimate_valu': 8,
                'f2_form': 11,      # f2_form: 0 Gram form (column-pair producers), 1 product form k_f2, 2 Gram form with one-column producers
-               'side_tables': 12}  # 1: basis-independent tables of the pass kept between passes; 0: rebuilt in every pass (arrays modified in place)
+               'side_tables': 12,  # 1: basis-independent tables of the pass kept between passes; 0: rebuilt in every pass (arrays modified in place)
+               'thin_merge': 13}   # 1: k_thin3; 0: k_thin_ncf, k_thin_rt, k_coupling one after the other in the factored layout (cross-check)
     S = S_ext = None
     _keep = None
 

@@ -248,6 +248,7 @@ int lrbms_ctx_set_option(lrbms_ctx* ctx, int32_t option, int32_t value) {
     case LRBMS_OPT_ESTIMATE_VALU: ctx->opt_estimate_valu = value; break;
     case LRBMS_OPT_PREP_LDS: ctx->opt_prep_lds = value; break;
     case LRBMS_OPT_SIDE_TABLES: ctx->opt_side_tables = value; break;
+    case LRBMS_OPT_THIN_MERGE: ctx->opt_thin_merge = value; break;
     default: return lrbms_fail(ctx, LRBMS_E_INVALID, "set_option: unknown option");
   }
   return LRBMS_OK;

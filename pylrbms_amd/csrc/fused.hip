@@ -53,6 +53,10 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 template <int W> struct VecT { using T = double; };
 template <> struct VecT<2> { using T = d2; };
 template <int W> __device__ inline typename VecT<W>::T ldv(const double* p) { return *reinterpret_cast<const typename VecT<W>::T*>(p); }
+// (wave-uniform base + 32-bit byte offset per lane: one address register, no 64-bit VALU)
+template <int W> __device__ inline typename VecT<W>::T ldv_off(const double* base, unsigned byte_off) {
+  return *reinterpret_cast<const typename VecT<W>::T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
 template <int W> __device__ inline void stv(double* p, typename VecT<W>::T v) { *reinterpret_cast<typename VecT<W>::T*>(p) = v; }
 template <int W> __device__ inline typename VecT<W>::T zerov() { return typename VecT<W>::T(0.0); }
 using W1 = std::integral_constant<int, 1>;
@@ -3926,41 +3930,80 @@ __device__ __forceinline__ void thin_ncf_body(const Tmpl& t, const ThinNcfArgs& 
   // (ncf_side_tables, evaluated once per assembly), requested together with the touch tables
   const double* kt = a.ktab + ((long)s * 4 + side) * 9 * t.ntouch;
   const double* mt = a.mtab + ((long)s * 4 + side) * 4 * nvs * nvs;
-  constexpr int MT = 2;                             // M_ab items per thread held from here to the output phase (config 3: all of them)
+  // (register diet) the M_ab rows and the neighbour's vertex averages A_a are pure copies into F_nc: both are requested here, in the
+  // round trip of the touch tables, and stored right behind the first barrier -- nothing of them is live while stage_y holds its batch
+  constexpr int MT = 2;                             // M_ab items per thread copied this way (config 3: all of them)
   double mv[MT];
 #pragma unroll
   for (int u = 0; u < MT; ++u) mv[u] = mt[u * 256 + tid < 4 * nvs * nvs ? u * 256 + tid : 0];
-  (void)side_mask;                                  // (only the M_ab scan read it: the slot stays so that the LDS layout, and thin_ncf_lds_bytes, are the parent's)
-  for (int i = tid; i < ne; i += 256) ttab[i] = t.touch_elem[side * t.ntouch + i];
-  // the rows that meet in a side vertex, in table order: t.touch_rlist (built at mesh upload; a vertex with more than NCF_ROWS rows has
-  // count -1 and is scanned where it is used)
-  static_assert(NCF_ROWS == 8, "layout of t.touch_rlist");
-  for (int i = tid; i < nvs * (NCF_ROWS + 1); i += 256) rlist[i] = t.touch_rlist[side * nvs * (NCF_ROWS + 1) + i];
-  for (int i = tid; i < 3 * ne; i += 256) vtab[i] = t.touch_vtx[side * t.ntouch * 3 + i];
-  for (int i = tid; i < 12 * ne; i += 256) ptab[i] = t.touch_pos[side * t.ntouch * 12 + i];
-  for (int i = tid; i < 9 * ne; i += 256) Ksc[i] = kt[i];
-  THIN_STAMP(2, 1);
-  __syncthreads();
-  THIN_STAMP(2, 2);
-  const double* Vs = a.V + (long)s * t.n * N;
-  const double* As = a.AvgSelf + (long)s * t.nv * N;
-  // (round 3) every thread requests the rows of a batch of items before it uses the first one: one memory round trip per batch
-  // instead of one per item; the neighbour's vertex averages of the output sweep are requested here as well
   const int nside = (side == 0 || side == 3) ? t.nvx : t.nvy;
   const double* Aa = a.AvgSide + ((long)s * 4 + side) * nvs * N;
-  constexpr int OT = 2;                             // output items per thread held across the barrier (nvs N <= 512: checked below)
+  constexpr int OT = 2;                             // A_a items per thread copied this way (nvs N <= 512: all of them)
   double aav[OT];
 #pragma unroll
   for (int u = 0; u < OT; ++u) {
     const int it = u * 256 + tid, pos = it / N, j = it - pos * N;
     aav[u] = it < nvs * N && pos < nside ? Aa[(long)pos * N + j] : 0.0;
   }
+  (void)side_mask;                                  // (only the M_ab scan read it: the slot stays so that the LDS layout, and thin_ncf_lds_bytes, are the parent's)
+  // the rows that meet in a side vertex, in table order: t.touch_rlist (built at mesh upload; a vertex with more than NCF_ROWS rows has
+  // count -1 and is scanned where it is used)
+  static_assert(NCF_ROWS == 8, "layout of t.touch_rlist");
+  // The first trip of every table loop (config 3: everything but 32 entries of ptab, hence two trips of that one) is requested before
+  // any of it is written to LDS: one memory round trip for the tables instead of one per table (a load, its wait and its LDS write per
+  // loop).  Entries a thread does not have are read at index 0 and not written.
+  const int* g_tt = t.touch_elem + side * t.ntouch;
+  const int* g_rl = t.touch_rlist + side * nvs * (NCF_ROWS + 1);
+  const int* g_vt = t.touch_vtx + side * t.ntouch * 3;
+  const int* g_pt = t.touch_pos + side * t.ntouch * 12;
+  constexpr int PT = 2;
+  const int r_tt = g_tt[tid < ne ? tid : 0], r_rl = g_rl[tid < nvs * (NCF_ROWS + 1) ? tid : 0], r_vt = g_vt[tid < 3 * ne ? tid : 0];
+  int r_pt[PT];
+#pragma unroll
+  for (int u = 0; u < PT; ++u) r_pt[u] = g_pt[u * 256 + tid < 12 * ne ? u * 256 + tid : 0];
+  const double r_k = kt[tid < 9 * ne ? tid : 0];
+  // The empty asm reads every value requested so far, so the wait for all these loads stands here, once: behind it nothing is in
+  // flight that a thread may never use (the tables are read by every thread and written by few), and no later wait is extended to a
+  // store issued in between (the copies behind the barrier)
+  asm volatile("" ::"v"(aav[0]), "v"(aav[1]), "v"(mv[0]), "v"(mv[1]), "v"(r_tt), "v"(r_rl), "v"(r_vt), "v"(r_pt[0]), "v"(r_pt[1]), "v"(r_k));
+  static_assert(OT == 2 && MT == 2 && PT == 2, "operands of the asm above");
+  if (tid < ne) ttab[tid] = r_tt;
+  if (tid < nvs * (NCF_ROWS + 1)) rlist[tid] = r_rl;
+  if (tid < 3 * ne) vtab[tid] = r_vt;
+#pragma unroll
+  for (int u = 0; u < PT; ++u)
+    if (u * 256 + tid < 12 * ne) ptab[u * 256 + tid] = r_pt[u];
+  if (tid < 9 * ne) Ksc[tid] = r_k;
+  for (int i = 256 + tid; i < ne; i += 256) ttab[i] = g_tt[i];
+  for (int i = 256 + tid; i < nvs * (NCF_ROWS + 1); i += 256) rlist[i] = g_rl[i];
+  for (int i = 256 + tid; i < 3 * ne; i += 256) vtab[i] = g_vt[i];
+  for (int i = PT * 256 + tid; i < 12 * ne; i += 256) ptab[i] = g_pt[i];
+  for (int i = 256 + tid; i < 9 * ne; i += 256) Ksc[i] = kt[i];
+  THIN_STAMP(2, 1);
+  __syncthreads();
+  THIN_STAMP(2, 2);
+  // A_a into columns [0, N) and the M_ab table rows [nvs][4 nvs] into columns [2 N, 2 N + 4 nvs) of the rows of F_nc
+#pragma unroll
+  for (int u = 0; u < OT; ++u) {
+    const int it = u * 256 + tid, pos = it / N, j = it - pos * N;
+    if (it < nvs * N) Fs[(long)pos * LD + j] = aav[u];
+  }
+#pragma unroll
+  for (int u = 0; u < MT; ++u) {
+    const int it = u * 256 + tid, pos = it / (4 * nvs), rem = it - pos * 4 * nvs;
+    if (it < nvs * 4 * nvs) Fs[(long)pos * LD + 2 * N + rem] = mv[u];
+  }
+  const double* Vs = a.V + (long)s * t.n * N;
+  const double* As = a.AvgSelf + (long)s * t.nv * N;
+  // (round 3) every thread requests the rows of a batch of items before it uses the first one: one memory round trip per batch
+  // instead of one per item.  The rows are addressed as a wave-uniform base (the subdomain's slab) plus a 32-bit byte offset per
+  // lane (a slab is n N doubles, far below 4 GB): one address register per load instead of a 64-bit pair
   auto stage_y = [&](auto wtag) {
     constexpr int W = decltype(wtag)::value;
     using VT = typename VecT<W>::T;
     constexpr int IT = W == 2 ? 3 : 5;              // (config 3: all items of a thread in one batch)
     const int NW = N / W;
-    for (int base = 0; base < ne * NW; base += IT * 256) {
+    auto batch = [&](int base) {
       VT vv[IT][3], av[IT][3];
 #pragma unroll
       for (int u = 0; u < IT; ++u) {
@@ -3968,8 +4011,8 @@ __device__ __forceinline__ void thin_ncf_body(const Tmpl& t, const ThinNcfArgs& 
         const int p = itc / NW, j = (itc - p * NW) * W, T = ttab[p];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          vv[u][i] = ldv<W>(Vs + (long)(3 * T + i) * N + j);
-          av[u][i] = ldv<W>(As + (long)vtab[3 * p + i] * N + j);
+          vv[u][i] = ldv_off<W>(Vs, 8u * (unsigned)((3 * T + i) * N + j));
+          av[u][i] = ldv_off<W>(As, 8u * (unsigned)(vtab[3 * p + i] * N + j));
         }
       }
 #pragma unroll
@@ -3984,14 +4027,21 @@ __device__ __forceinline__ void thin_ncf_body(const Tmpl& t, const ThinNcfArgs& 
 #pragma unroll
         for (int k = 0; k < 3; ++k) stv<W>(Y + (3 * p + k) * N + j, K[k * 3] * ws[0] + K[k * 3 + 1] * ws[1] + K[k * 3 + 2] * ws[2]);
       }
-    }
+    };
+    // the first batch stands outside the loop: as the loop's first trip its loads waited for everything in flight at the loop's
+    // head (the copies above), because the head is also reached over the back edge with a batch of its own in flight
+    if (ne * NW > 0) batch(0);
+    for (int base = IT * 256; base < ne * NW; base += IT * 256) batch(base);
+    // W1 is laid out in front of W2, and W2 inherits whatever W1 may have left in flight: it would wait for that -- in fact for its own
+    // copy stores -- before its first load.  Every load of W1 has been used by here: say so (vmcnt 0; expcnt and lgkmcnt left alone)
+    if constexpr (W == 1) __builtin_amdgcn_s_waitcnt(0x0F70);
   };
   if (N & 1) stage_y(W1{});
   else stage_y(W2{});
   THIN_STAMP(2, 3);
   __syncthreads();
   THIN_STAMP(2, 4);
-  // A_a | C_a: one item per (side vertex, column); the rows that meet in a vertex are summed in table order
+  // C_a: one item per (side vertex, column); the rows that meet in a vertex are summed in table order
   for (int it = tid, u = 0; it < nvs * N; it += 256, ++u) {
     const int pos = it / N, j = it - pos * N;
     double c = 0.0;
@@ -4004,7 +4054,7 @@ __device__ __forceinline__ void thin_ncf_body(const Tmpl& t, const ThinNcfArgs& 
           if (ptab[r * 4 + side] == pos) c -= Y[r * N + j];
       }
     }
-    Fs[(long)pos * LD + j] = u < OT ? (u == 0 ? aav[0] : aav[1]) : (pos < nside ? Aa[(long)pos * N + j] : 0.0);
+    if (u >= OT) Fs[(long)pos * LD + j] = pos < nside ? Aa[(long)pos * N + j] : 0.0;      // (A_a beyond the copied items)
     Fs[(long)pos * LD + N + j] = c;
     if (t.opt_oswald_vertex) {
       // A_diag: the diagonal subdomain's share of the vertex average at a cross point, carried by the sides 0 (S) and 3 (N) at
@@ -4016,10 +4066,10 @@ __device__ __forceinline__ void thin_ncf_body(const Tmpl& t, const ThinNcfArgs& 
       Fs[(long)pos * LD + 2 * N + 4 * nvs + j] = carries ? Ac[((long)s * 4 + corner) * N + j] : 0.0;
     }
   }
-  // M_ab: the table rows [nvs][4 nvs] into columns [2 N, 2 N + 4 nvs) of the rows of F_nc
-  for (int it = tid, u = 0; it < nvs * 4 * nvs; it += 256, ++u) {
+  // M_ab beyond the copied items
+  for (int it = MT * 256 + tid; it < nvs * 4 * nvs; it += 256) {
     const int pos = it / (4 * nvs), rem = it - pos * 4 * nvs;
-    Fs[(long)pos * LD + 2 * N + rem] = u < MT ? (u == 0 ? mv[0] : mv[1]) : mt[it];
+    Fs[(long)pos * LD + 2 * N + rem] = mt[it];
   }
   THIN_STAMP(2, 5);
 }
@@ -4515,8 +4565,13 @@ __global__ __launch_bounds__(256) void k_coupling(Tmpl t, int S, const int* __re
 }
 
 // Factored layout: all three thin kernels are 256-thread workgroups -- one launch, grid (4, S, 3).
+// Five workgroups per CU (what the launch's LDS admits) need at most 96 registers per wave, accumulation registers included.  With
+// a register budget above 256 per wave hipcc gives coupling_body's f64 MFMAs accumulation registers of their own, 8 of them behind
+// the kernel's VGPR count rounded up to 4 (104 + 8 = 112: four workgroups).  waves_per_eu(2, 8) sets the budget to 256 and nothing
+// else: the accumulators become ordinary VGPRs inside the largest body's count (92), no body is squeezed and nothing spills.
+// _isa_check.check_thin_registers fails the build when the count of <1..3> passes 96.
 template <int NTX>
-__global__ __launch_bounds__(256) void k_thin3(Tmpl t, ThinRtArgs a, ThinNcfArgs f, const double* __restrict__ A_cpl,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_thin3(Tmpl t, ThinRtArgs a, ThinNcfArgs f, const double* __restrict__ A_cpl,
                                                double* __restrict__ B_sys) {
   // (an XCD-aware 1-D grid -- the twelve workgroups of a subdomain on one XCD, kinds interleaved -- was measured: no change)
   const int side = blockIdx.x, s = subdomain_of(t, blockIdx.y), z = blockIdx.z;
@@ -5047,7 +5102,8 @@ int launch_project_estimate_fused(lrbms_ctx* ctx, int Q, int N, const double* V,
   // (k_prep only there: at 1 024 subdomains it takes 182 us against 113 + 59 us for the two sweeps on their own)
   // factored layout: the three thin kernels are 256-thread workgroups and always share one launch (k_thin3: 141 us at
   // 1 024 subdomains against 65 + 49 + 41 us one after the other -- they are latency-bound and fill each other's gaps)
-  const bool merge_thin = forked || factored;
+  // (LRBMS_OPT_THIN_MERGE 0: the three kernels one after the other, the cross-check of k_thin3 against its parts)
+  const bool merge_thin = forked || (factored && ctx->opt_thin_merge != 0);
   // LRBMS_OPT_PREP_LDS: the preparation sweeps from one copy of the basis slab in LDS; with it G_nc[self, self] is folded into the same
   // kernel (k_f3 is not launched) whenever N <= 48 and the call covers both the preparation and the dense kernels
   const int ntx_p = (N + 15) / 16;

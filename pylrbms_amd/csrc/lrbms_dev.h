@@ -106,6 +106,7 @@ struct lrbms_ctx : lrbms_ctx_base {
   long stab_gen[SRC_COUNT] = {0, 0, 0, 0};
   int stab_Q = 0;
   int opt_side_tables = 1;            // LRBMS_OPT_SIDE_TABLES
+  int opt_thin_merge = 1;             // LRBMS_OPT_THIN_MERGE
   bool pass_ran = false;              // a fused pass has run: conventions that change buffer shapes (the vertex patch: F_nc rows) are frozen
   bool diag_explicit = false;         // lrbms_set_diagonal_neighbours was called (needed with the vertex patch when S_ext > S)
   int* subset = nullptr;              // lrbms_fused_set_subset: device copy of the list (ctx-owned), subset_n == 0: no restriction
