@@ -117,6 +117,17 @@ int lrbms3_assemble_energy_product(lrbms3_ctx* ctx, int32_t Q, const double* the
  * 2D: lrbms_blockell_apply. */
 int lrbms3_energy_product_apply(lrbms3_ctx* ctx, int32_t M, const double* P_diag, const double* X, double* Y, void* stream);
 
+/* Local POD basis extension, the batched method of snapshots per subdomain: lrbms_local_pod of include/lrbms_hip.h (algorithm,
+ * arguments, the work formula with this path's S and n, limits and refusals are the same, the kernels are shared) with the local
+ * energy product P_diag [S][n_T][5][100] applied as lrbms3_energy_product_apply does.  U [S][n][L] with 1 <= L <= 128,
+ * V [S(_ext)][n][Nw] with Nw <= 64, nloc / added / info [S] int32 on the device, sv [S][L].  n > 512: the reductions over n
+ * (V^T P R, R^T P R) run in min(8, ceil(n / 512)) pieces that are summed in their order.  rtol < 1e-7 is refused (the Gram
+ * matrix squares the singular values). */
+int64_t lrbms3_local_pod_work_size(lrbms3_ctx* ctx, int32_t L, int32_t Nw);
+int lrbms3_local_pod(lrbms3_ctx* ctx, int32_t L, int32_t Nw, int32_t modes, double rtol, double atol, const double* P_diag,
+                     const double* U, double* V, int32_t* nloc, double* sv, int32_t* added, int32_t* info, double* work,
+                     void* stream);
+
 /* Cf [Q][S_ext][n_T][4][10]: contribution of the element's own DoFs to the RT0 DoF of its face f (unsigned; the kernels
  * apply the orientation).  2D: lrbms_assemble_flux. */
 int lrbms3_assemble_flux(lrbms3_ctx* ctx, int32_t Q, const double* lam, double* Cf, void* stream);

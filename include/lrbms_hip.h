@@ -639,6 +639,48 @@ int lrbms_local_correction_solve(lrbms_ctx* ctx, int32_t Q, const double* theta,
                                  const double* A_diag, const double* A_cpl, const double* D_corr, const double* b,
                                  double* work, double* corr, double rtol, int32_t max_iter, double* info, void* stream);
 
+/* -- local POD basis extension: batched method of snapshots per subdomain ---------------- */
+/* Compresses L snapshots per subdomain into at most `modes` new basis vectors, every local subdomain independently:
+ *   norm0 = max_j |u_j|_P;  R = U deflated twice against V in the product P;  G = sym(R^T P R) = Z diag(lam) Z^T (cyclic
+ *   Jacobi, lam descending), sigma_j = sqrt(max(lam_j, 0));
+ *   k_s = min(#{j : sigma_j > max(atol, rtol norm0)}, modes, Nw - nloc[s]);  W = R Z_k Sigma_k^-1, deflated once more against V,
+ *   then W <- W (W^T P W)^{-1/2} (Loewdin: the energy order of the modes is kept);  V[s][:, nloc[s] .. nloc[s] + k_s) = W.
+ *     P_diag [S][n_T][4][9]   the local product, as lrbms_blockell_apply takes it
+ *     U      [S][n][L]        snapshots, 1 <= L <= 128 (not modified)
+ *     V      [S(_ext)][n][Nw] basis slab, Nw <= 64: nloc[s] P-orthonormal columns, zero columns behind them.  Only the k_s new
+ *                             columns of the S local subdomains are written; halo rows and all other columns keep their bits
+ *     nloc   [S] int32 device, in / out (+= added)
+ *     sv     [S][L]           sigma_j, descending (all L of them)
+ *     added  [S] int32        k_s
+ *     info   [S] int32        0, or bit 0: the Jacobi sweep cap was reached on G, bit 2: on W^T P W, bit 3: a retained eigenvalue
+ *                             of W^T P W was not positive
+ *     work   lrbms_local_pod_work_size(L, Nw) doubles (device) =
+ *            S (2 n L + n Kc + Nw L + 2 L^2 + Lp^2 + L + L Kc + 4 + (p > 1 ? p max(L, Nw) L : 0)),
+ *            Kc = min(L, Nw), Lp = L rounded up to even, p = 1 for n <= 512, else min(8, ceil(n / 512)) (the pieces the
+ *            reduction over n is split into).  Its content on entry is irrelevant.
+ *   The threshold is relative to the UNDEFLATED snapshots: what lies in the span of V adds nothing, a zero column has an exact
+ *   zero sigma.  Everything runs on `stream`: no host synchronisation, no atomics, fixed summation orders (repeat calls give
+ *   the same bits), no environment variables.
+ *   Refused with LRBMS_E_INVALID before any launch: L > 128, Nw > 64, modes < 1, a null work, and rtol < 1e-7 -- G squares the
+ *   singular values, so sigma_j below about 1e-7 sigma_1 (sqrt of the fp64 unit roundoff, with a margin) is rounding noise of
+ *   the Gram route; an SVD route would be needed there and is not part of this library. */
+int64_t lrbms_local_pod_work_size(lrbms_ctx* ctx, int32_t L, int32_t Nw);
+int lrbms_local_pod(lrbms_ctx* ctx, int32_t L, int32_t Nw, int32_t modes, double rtol, double atol, const double* P_diag,
+                    const double* U, double* V, int32_t* nloc, double* sv, int32_t* added, int32_t* info, double* work,
+                    void* stream);
+/* The two kernels of it that stand alone (cross-checks; any context, no mesh needed):
+ *   G[b] [L][L] = sym(X[b]^T Y[b]), X, Y [batch][K][L], L <= 128: the upper-triangle 16 x 16 tiles on the fp64 MFMA, mirrored
+ *   (G[i][j] = G[j][i] = x_i^T y_j for i <= j, exactly symmetric). */
+int lrbms_pod_gram(lrbms_ctx* ctx, int32_t batch, int32_t K, int32_t L, const double* X, const double* Y, double* G, void* stream);
+/*   Eigenpairs of sym(G[b]) [L][L], L <= 128, one workgroup per matrix (cyclic Jacobi, round-robin ordering, at most 40 sweeps):
+ *   lam [batch][L] descending (ties in index order).  mode 0: Z [batch][L][L] holds the eigenvector of lam[b][j] in ROW j;
+ *   mode 1: Z = sum over the kcount[b] (NULL: L) largest eigenpairs of z z^T / sqrt(lam), the Loewdin factor G^{-1/2}.
+ *   info [batch] int32: bit 0 not converged to off(G) <= eps |G|_F, bit 1 (mode 1) a retained eigenvalue was <= 0 (left out).
+ *   work: lrbms_pod_eigh_work_size(batch, L) = batch Lp^2 doubles. */
+int64_t lrbms_pod_eigh_work_size(lrbms_ctx* ctx, int32_t batch, int32_t L);
+int lrbms_pod_eigh(lrbms_ctx* ctx, int32_t batch, int32_t L, int32_t mode, const double* G, const int32_t* kcount, double* lam,
+                   double* Z, int32_t* info, double* work, void* stream);
+
 /* -- helpers used by the host shim and the parity tests ------------------------------------------------- */
 /* y [S][n][M] = blockELL(A [S][n_T][4][9]) x [S][n][M]   (diagonal blocks only, no coupling) */
 int lrbms_blockell_apply(lrbms_ctx* ctx, int32_t M, const double* A, const double* x, double* y, void* stream);

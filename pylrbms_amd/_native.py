@@ -112,6 +112,12 @@ SIGNATURES = {
     'lrbms_fom_apply': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'lrbms_gemm_tn': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp,
                                      c_i64, c_i32, c_vp, c_dbl, c_vp]),
+    # local POD basis extension
+    'lrbms_local_pod_work_size': (c_i64, [c_vp, c_i32, c_i32]),
+    'lrbms_local_pod': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_dbl, c_dbl] + [c_vp] * 9),
+    'lrbms_pod_gram': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'lrbms_pod_eigh_work_size': (c_i64, [c_vp, c_i32, c_i32]),
+    'lrbms_pod_eigh': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 7),
 }
 
 _lib = None
@@ -216,6 +222,36 @@ class ContextBase:
 
     def from_numpy(self, a):
         return self.torch.from_numpy(np.array(a, dtype=np.float64, order='C', copy=True)).to(self.device)
+
+    def _local_pod(self, P_ptr, U, V, nloc, modes, rtol, atol, work=None):
+        """``lrbms_local_pod`` / ``lrbms3_local_pod`` on the current stream.  ``U`` [S, n, L], ``V`` [S or S_ext, n, Nw] (its free
+        columns are filled in place; rows past S are a halo the call leaves alone), ``nloc`` int32 device tensor [S] (in / out),
+        ``work``: at least ``local_pod_work_size(L, Nw)`` doubles (default: allocated here).  Returns the device tensors ``sv`` [S, L] and
+        ``ai`` int32 [2, S] (row 0 ``added``, row 1 ``info``); nothing is copied to the host here."""
+        torch = self.torch
+        S, n = self.S, self.n
+        L, Nw = int(U.shape[2]), int(V.shape[2])
+        if V.shape[0] < S:
+            raise NativeError('V: expected at least {} subdomain rows, got {}'.format(S, V.shape[0]))
+        if nloc.dtype != torch.int32 or nloc.device != self.device or tuple(nloc.shape) != (S,) or not nloc.is_contiguous():
+            raise NativeError('nloc: expected a contiguous int32 tensor [{}] on {}'.format(S, self.device))
+        u_ptr, v_ptr = self._ptr(U, (S, n, L), 'U'), self._ptr(V, (V.shape[0], n, Nw), 'V')
+        size = self.local_pod_work_size(L, Nw)
+        if work is None:
+            work = self.empty(size) if size > 0 else None      # (a refused shape: the call below says why)
+        elif work.dtype != torch.float64 or work.device != self.device or not work.is_contiguous() or work.numel() < max(size, 1):
+            raise NativeError('work: expected a contiguous float64 tensor of at least {} elements on {}'.format(size, self.device))
+        sv = self.empty(S, L)
+        ai = torch.empty(2, S, dtype=torch.int32, device=self.device)
+        rc = self._fn('local_pod')(self.handle, L, Nw, int(modes), float(rtol), float(atol), P_ptr, u_ptr, v_ptr, c_vp(nloc.data_ptr()),
+                                   c_vp(sv.data_ptr()), c_vp(ai[0].data_ptr()), c_vp(ai[1].data_ptr()),
+                                   c_vp(work.data_ptr()) if work is not None else None, self._stream())
+        self._check(rc, self.PREFIX + 'local_pod')
+        return sv, ai
+
+    def local_pod_work_size(self, L, Nw):
+        """Doubles of ``work`` for ``local_pod`` (the formula of the C header), -1 for a shape the call refuses."""
+        return int(self._fn('local_pod_work_size')(self.handle, int(L), int(Nw)))
 
     def set_option(self, name, value):
         """Set one entry of ``OPTIONS``: a convention the reference tree leaves open or the launch policy of the library
@@ -1043,3 +1079,35 @@ class NativeContext(ContextBase):
                                     float(alpha), self._stream())
         self._check(rc, 'lrbms_gemm_tn')
         return G
+
+    # ------------------------------------------------------------------ local POD basis extension
+    def local_pod(self, P_diag, U, V, nloc, modes, rtol=1e-6, atol=0.0, work=None):
+        """``lrbms_local_pod``: at most ``modes`` POD modes of the snapshots ``U`` [S, n, L] per subdomain, in the block-ELL
+        product ``P_diag``, into the free columns of ``V``; see ``ContextBase._local_pod`` for the arguments and the result."""
+        return self._local_pod(self._ptr(P_diag, (self.S, self.n_T, 4, 9), 'P_diag'), U, V, nloc, modes, rtol, atol, work)
+
+    def pod_gram(self, X, Y):
+        """sym(X[b]^T Y[b]) for X, Y [B, K, L] (``lrbms_pod_gram``: upper-triangle MFMA tiles, mirrored)."""
+        B, K, L = X.shape
+        G = self.empty(B, L, L)
+        rc = self.lib.lrbms_pod_gram(self.handle, B, K, L, self._ptr(X, (B, K, L), 'X'), self._ptr(Y, (B, K, L), 'Y'),
+                                     c_vp(G.data_ptr()), self._stream())
+        self._check(rc, 'lrbms_pod_gram')
+        return G
+
+    def pod_eigh(self, G, mode=0, kcount=None):
+        """``lrbms_pod_eigh`` on G [B, L, L]: (lam [B, L] descending, Z [B, L, L], info int32 [B]).  mode 0: row j of Z[b] is the
+        eigenvector of lam[b, j]; mode 1: Z = G^{-1/2} over the ``kcount[b]`` (int32 device tensor; None: all) largest eigenpairs."""
+        torch = self.torch
+        B, L = int(G.shape[0]), int(G.shape[1])
+        lam, Z = self.empty(B, L), self.empty(B, L, L)
+        info = torch.empty(B, dtype=torch.int32, device=self.device)
+        size = int(self.lib.lrbms_pod_eigh_work_size(self.handle, B, L))
+        work = self.empty(size) if size > 0 else None
+        if kcount is not None:
+            assert kcount.dtype == torch.int32 and tuple(kcount.shape) == (B,) and kcount.device == self.device
+        rc = self.lib.lrbms_pod_eigh(self.handle, B, L, int(mode), self._ptr(G, (B, L, L), 'G'),
+                                     c_vp(kcount.data_ptr()) if kcount is not None else None, c_vp(lam.data_ptr()), c_vp(Z.data_ptr()),
+                                     c_vp(info.data_ptr()), c_vp(work.data_ptr()) if work is not None else None, self._stream())
+        self._check(rc, 'lrbms_pod_eigh')
+        return lam, Z, info

@@ -84,6 +84,9 @@ SIGNATURES3 = {
     'lrbms3_local_correction_work_size': (c_i64, [c_vp, c_i32]),
     'lrbms3_local_correction_solve': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_i32, _P_I32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32,
                                                      _P_DBL, c_vp]),
+    # local POD basis extension
+    'lrbms3_local_pod_work_size': (c_i64, [c_vp, c_i32, c_i32]),
+    'lrbms3_local_pod': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_dbl, c_dbl] + [c_vp] * 9),
 }
 
 _bound = None
@@ -215,6 +218,11 @@ class Native3DContext(_native.ContextBase):
                                                   self._ptr(X, (self.S, self.n, M), 'X'), c_vp(Y.data_ptr()), self._stream())
         self._check(rc, 'lrbms3_energy_product_apply')
         return Y
+
+    def local_pod(self, P_diag, U, V, nloc, modes, rtol=1e-6, atol=0.0, work=None):
+        """``lrbms3_local_pod``: at most ``modes`` POD modes of the snapshots ``U`` [S, n, L] per subdomain, in the local energy
+        product ``P_diag``, into the free columns of ``V``; arguments and result as ``ContextBase._local_pod``."""
+        return self._local_pod(self._ptr(P_diag, (self.S, self.n_T, 5, 100), 'P_diag'), U, V, nloc, modes, rtol, atol, work)
 
     # ------------------------------------------------------------------ pass
     OUT_NAMES = ('B_sys', 'rhs_red', 'G_nc', 'G_bb', 'G_rdd', 'G_ab', 'G_aa', 'r_fd', 'Rb', 'Yb', 'Dp', 'Xab', 'As', 'Cn')

@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include "lrbms_dev.h"
+#include "lrbms_pod.h"
 
 int64_t estimator_work_size(lrbms_ctx* ctx, int Q, int N);
 int64_t reduced_solve_work_size(lrbms_ctx* ctx, int N);
@@ -874,6 +875,48 @@ int lrbms_gemm_tn(lrbms_ctx* ctx, int32_t batch, int32_t K, int32_t Mx, int32_t 
   if (!ctx) return LRBMS_E_INVALID;
   CHECK_PTR(ctx, X); CHECK_PTR(ctx, Y); CHECK_PTR(ctx, G);
   return launch_gemm_tn(ctx, batch, K, Mx, My, X, sx, ldx, Y, sy, ldy, G, sg, ldg, rowscale, alpha, (hipStream_t)stream);
+}
+
+// -- local POD basis extension (pod.hip); the product is the block-ELL apply on P_diag
+namespace {
+struct Pod2D {
+  lrbms_ctx* ctx;
+  const double* P_diag;
+};
+int pod_product_2d(void* self, int M, const double* X, double* Y, hipStream_t st) {
+  const Pod2D* a = static_cast<const Pod2D*>(self);
+  return launch_blockell_apply(a->ctx, a->ctx->S, M, a->P_diag, (long)a->ctx->t.nT * 36, X, Y, st);
+}
+}  // namespace
+
+int64_t lrbms_local_pod_work_size(lrbms_ctx* ctx, int32_t L, int32_t Nw) {
+  if (!ctx || !ctx->has_mesh || L < 1 || L > POD_MAX_L || Nw < 1 || Nw > POD_MAX_NW) return -1;
+  return pod_work_size(ctx->S, ctx->t.n, L, Nw);
+}
+
+int lrbms_local_pod(lrbms_ctx* ctx, int32_t L, int32_t Nw, int32_t modes, double rtol, double atol, const double* P_diag,
+                    const double* U, double* V, int32_t* nloc, double* sv, int32_t* added, int32_t* info, double* work,
+                    void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_PTR(ctx, P_diag);
+  Pod2D self{ctx, P_diag};
+  return launch_local_pod(ctx, ctx->S, ctx->t.n, L, Nw, modes, rtol, atol, PodProduct{pod_product_2d, &self}, U, V, nloc, sv, added,
+                          info, work, (hipStream_t)stream);
+}
+
+int lrbms_pod_gram(lrbms_ctx* ctx, int32_t batch, int32_t K, int32_t L, const double* X, const double* Y, double* G, void* stream) {
+  if (!ctx) return LRBMS_E_INVALID;
+  return launch_pod_gram(ctx, batch, K, L, X, Y, G, (hipStream_t)stream);
+}
+
+int64_t lrbms_pod_eigh_work_size(lrbms_ctx* ctx, int32_t batch, int32_t L) {
+  if (!ctx || batch < 1 || L < 1 || L > POD_MAX_L) return -1;
+  return pod_eigh_work_size(batch, L);
+}
+
+int lrbms_pod_eigh(lrbms_ctx* ctx, int32_t batch, int32_t L, int32_t mode, const double* G, const int32_t* kcount, double* lam,
+                   double* Z, int32_t* info, double* work, void* stream) {
+  if (!ctx) return LRBMS_E_INVALID;
+  return launch_pod_eigh(ctx, batch, L, mode, G, kcount, lam, Z, info, work, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 
 #include "../../include/lrbms3d_hip.h"
 #include "lrbms_ctx_base.h"
+#include "lrbms_pod.h"
 
 namespace {
 
@@ -3261,6 +3262,33 @@ int lrbms3_energy_product_apply(lrbms3_ctx* ctx, int32_t M, const double* P_diag
                      (const double*)nullptr, X, Y);
   LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
+}
+
+// -- local POD basis extension (pod.hip); the product is the local energy product, applied as lrbms3_energy_product_apply does
+namespace {
+struct Pod3D {
+  lrbms3_ctx* ctx;
+  const double* P_diag;
+};
+int pod_product_3d(void* self, int M, const double* X, double* Y, hipStream_t st) {
+  const Pod3D* a = static_cast<const Pod3D*>(self);
+  return lrbms3_energy_product_apply(a->ctx, M, a->P_diag, X, Y, (void*)st);
+}
+}  // namespace
+
+int64_t lrbms3_local_pod_work_size(lrbms3_ctx* ctx, int32_t L, int32_t Nw) {
+  if (!ctx || !ctx->has_mesh || L < 1 || L > POD_MAX_L || Nw < 1 || Nw > POD_MAX_NW) return -1;
+  return pod_work_size(ctx->t.S, ctx->t.n, L, Nw);
+}
+
+int lrbms3_local_pod(lrbms3_ctx* ctx, int32_t L, int32_t Nw, int32_t modes, double rtol, double atol, const double* P_diag,
+                     const double* U, double* V, int32_t* nloc, double* sv, int32_t* added, int32_t* info, double* work,
+                     void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (!P_diag) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod: null pointer: P_diag");
+  Pod3D self{ctx, P_diag};
+  return launch_local_pod(ctx, ctx->t.S, ctx->t.n, L, Nw, modes, rtol, atol, PodProduct{pod_product_3d, &self}, U, V, nloc, sv, added,
+                          info, work, (hipStream_t)stream);
 }
 
 int lrbms3_assemble_flux(lrbms3_ctx* ctx, int32_t Q, const double* lam, double* Cf, void* stream) {

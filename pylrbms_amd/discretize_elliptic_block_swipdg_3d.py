@@ -389,6 +389,17 @@ class LRBMSReductor3D(LocalBasisSlab):
             return X
         return eng.ctx.energy_product_apply(eng.ops['P_diag'], X.contiguous())
 
+    def _pod_product(self):
+        if self.euclidean:
+            raise NotImplementedError("extend_basis(method='pod') works in the local energy product (products='euclidean' was asked for)")
+        return self.d.engine.ops['P_diag']
+
+    def _pod_max_width(self):
+        return max(min(self.POD_MAX_WIDTH, 64 // self.d.Q), self.basis_size())      # the limit of the pass, as reserve()
+
+    def _pod_mark_dirty(self, idx):
+        self._dirty = getattr(self, '_dirty', set()) | {int(i) for i in idx}
+
     def gram(self):
         """V^T P V per subdomain [S, N_max, N_max]: the identity on the filled columns after Gram-Schmidt (what the 2D pass returns
         as E_red)."""

@@ -13,7 +13,9 @@ enrichment of only the marked subdomains, reductor.py:75-78) has zero columns be
 columns project to exactly zero rows / columns of every reduced operator, the reduced solve puts 1 on those diagonal
 entries (``k_block_inverse``), so the padded unknowns stay 0 and every kernel keeps its uniform shape.
 A global ``extend_basis`` is all-or-nothing and raises ``ExtensionError`` if any block of the snapshot is numerically
-in the span of its basis.
+in the span of its basis.  ``extend_basis(U, method='pod', pod_modes=k)`` compresses instead: the leading POD modes of up to 128
+snapshots per subdomain in the same product, deflated against the local basis (``lrbms_local_pod``, one native call batched over
+the subdomains; ``LocalBasisSlab.extend_basis_pod``).
 
 Incremental re-projection (``reduce(touched=...)``): the reference re-reduces everything after a round of local enrichment
 (online_enrichment.py:49-58 after reductor.py:75-78).  The projected operators of a target subdomain depend on the bases of
@@ -114,15 +116,124 @@ class LocalBasisSlab:
                 raise ExtensionError('snapshot block is (numerically) in the span of its local basis')
             self._append_columns(v, ok)
 
-    def extend_basis(self, U):
+    def extend_basis(self, U, method='gram_schmidt', pod_modes=None):
         """Restrict a global snapshot to every subdomain and extend all local bases (the fork's ``extend_basis``;
-        online_adaptive_lrbms.py:117-121); all-or-nothing: ``ExtensionError`` if a block is in the span of its basis."""
+        online_adaptive_lrbms.py:117-121); all-or-nothing: ``ExtensionError`` if a block is in the span of its basis.
+        ``method='pod'`` (pyMOR's ``extend_basis(U, method='pod', pod_modes=k)``): ``extend_basis_pod(U, modes=pod_modes)``."""
+        if method == 'pod':
+            return self.extend_basis_pod(U, modes=pod_modes)
+        if method != 'gram_schmidt':
+            raise ValueError("extend_basis: method is 'gram_schmidt' or 'pod', not {!r}".format(method))
         self._gram_schmidt_extend(self._as_slab(U))
 
-    def _extend_basis_trajectory(self, U, max_vectors=None):
+    # ------------------------------------------------------------------ POD extension (DESIGN.md 5.6)
+    POD_MAX_COLUMNS = 128               # snapshots per native call (lrbms_local_pod: L <= 128)
+    POD_MAX_WIDTH = 64                  # slab width the native call takes (and the fused pass: N <= 64)
+    POD_MIN_RTOL = 1e-7                 # below it the Gram route resolves nothing (include/lrbms_hip.h)
+
+    def _pod_product(self):
+        """The local product in the form the context's ``local_pod`` takes."""
+        raise NotImplementedError
+
+    def _pod_width(self, width):
+        """The slab width that holds ``width`` vectors (a subclass rounds as its ``reserve`` does)."""
+        return width
+
+    def _pod_max_width(self):
+        """The widest slab a POD extension pads to (a subclass lowers it to what its pass takes)."""
+        return self.POD_MAX_WIDTH
+
+    def _pod_mark_dirty(self, idx):
+        """Record the local subdomains ``idx`` as changed since the last ``reduce()`` (``_dirty`` of the subclass)."""
+
+    def _pod_slab(self, U):
+        """``U`` as one slab [S, n, L]: a trajectory / block array, a ready-made slab, or a list of those, stacked along the
+        column axis in the order given."""
+        import torch
+        if isinstance(U, (list, tuple)):
+            if not U:
+                raise ValueError('extend_basis_pod: no snapshots')
+            return torch.cat([self._pod_slab(u) for u in U], dim=2).contiguous()
+        if isinstance(U, torch.Tensor) and U.dim() == 3:
+            return U.contiguous()
+        return self._as_slab(U).contiguous()
+
+    def extend_basis_pod(self, U, modes=None, rtol=1e-6, atol=0.0):
+        """POD extension of every local basis, the batched method of snapshots per subdomain (``lrbms_local_pod`` /
+        ``lrbms3_local_pod``): the snapshots are deflated against the local basis in the local product and at most ``modes`` of
+        their leading POD modes, those with a singular value above ``max(atol, rtol * max_j |u_j|)``, are appended,
+        product-orthonormal among themselves and to the basis.  Snapshots in the span of a basis add nothing there.
+
+        ``U``: a trajectory, a slab [S, n, L], or a list of those (stacked along the column axis).  More than 128 columns run as
+        consecutive calls of at most 128 columns, in order, each against the basis the previous one has grown, with ``modes`` as
+        the cap of every call: a HIERARCHICAL compression, not one global POD of all columns.  ``modes=None``: as many as pass
+        the threshold and fit.  The slab is padded to the width the call may need (at most 64; 3D: 64 // Q, the limit of the pass, as
+        ``reserve``) and cut back to what was filled.
+
+        Purely local: no communication, so it works on a sharded discretization as it is; halo rows of a slab that carries
+        them are not touched.  One device-to-host copy of the added counts per native call is the only synchronisation.
+        Returns ``(sv, added)`` as NumPy arrays: the singular values of the deflated snapshots [S, L], descending per call
+        (the calls side by side), and the number of vectors added per subdomain.  ``ExtensionError`` if nothing was added."""
+        import torch
+        eng = self.d.engine
+        S = eng.S
+        U = self._pod_slab(U)
+        if U.dim() != 3 or U.shape[0] != S or U.shape[1] != eng.t.n or U.shape[2] < 1:
+            raise ValueError('extend_basis_pod: snapshots [S = {}, n = {}, L >= 1] expected, got {}'.format(S, eng.t.n, tuple(U.shape)))
+        if modes is not None and int(modes) < 1:
+            raise ValueError('extend_basis_pod: modes must be >= 1')
+        if not rtol >= self.POD_MIN_RTOL:
+            raise ValueError('extend_basis_pod: rtol < 1e-7: the Gram matrix squares the singular values, below that they are noise')
+        if not atol >= 0.0:
+            raise ValueError('extend_basis_pod: atol must be >= 0')
+        P = self._pod_product()
+        if self._V is None:
+            self._V = eng.ctx.zeros(S, eng.t.n, 0)
+            self._nloc = np.zeros(S, dtype=np.int64)
+        width0 = self.basis_size()
+        svs, total = [], np.zeros(S, dtype=np.int64)
+        failed = None
+        for c0 in range(0, U.shape[2], self.POD_MAX_COLUMNS):
+            Uc = U[:, :, c0:c0 + self.POD_MAX_COLUMNS].contiguous()
+            k = Uc.shape[2] if modes is None else min(int(modes), Uc.shape[2])
+            need = self._pod_width(min(int(self._nloc[:S].max()) + k, self._pod_max_width()))
+            if need > self._V.shape[2]:
+                self._V = torch.nn.functional.pad(self._V, (0, need - self._V.shape[2])).contiguous()
+            nloc = torch.as_tensor(np.ascontiguousarray(self._nloc[:S], dtype=np.int32)).to(self._V.device)
+            sv, ai = eng.ctx.local_pod(P, Uc, self._V, nloc, k, rtol, atol)
+            added, info = ai.cpu().numpy().astype(np.int64)          # the one synchronisation
+            self._nloc[:S] += added
+            total += added
+            self._pod_mark_dirty(np.where(added > 0)[0])
+            svs.append(sv)
+            if info.any():
+                failed = np.where(info != 0)[0]
+                break
+        top = int(self._nloc.max())
+        keep = width0 if top <= width0 else self._pod_width(top)     # (nothing past the old width: the slab is as it was)
+        if self._V.shape[2] > keep:                                  # columns past every nloc[s] are zero
+            self._V = self._V[:, :, :keep].contiguous()
+        if failed is not None:
+            raise RuntimeError('extend_basis_pod: the eigen-solver reported info != 0 on local subdomains {}'.format(failed.tolist()))
+        if total.sum() == 0:
+            raise ExtensionError('no snapshot block extends its local basis')
+        return np.concatenate([sv.cpu().numpy() for sv in svs], axis=1), total
+
+    def _extend_basis_trajectory(self, U, max_vectors=None, method='gram_schmidt', pod_modes=None):
         """``extend_basis`` of the parabolic reductors: the vectors of a trajectory are Gram-Schmidt-ed into the local bases one
         after the other, a vector that is numerically in the span of a local basis is skipped for that subdomain (pyMOR
-        ``gram_schmidt`` semantics), at most until the slab is ``max_vectors`` wide; ``ExtensionError`` if nothing was added."""
+        ``gram_schmidt`` semantics), at most until the slab is ``max_vectors`` wide; ``ExtensionError`` if nothing was added.
+        ``method='pod'``: the leading ``pod_modes`` POD modes of the whole trajectory instead of its first vectors
+        (``extend_basis_pod``; with ``max_vectors`` no local basis grows past it)."""
+        if method == 'pod':
+            if max_vectors is not None:
+                room = int(max_vectors) - (0 if self._nloc is None else int(self._nloc[:self.d.engine.S].max()))
+                if room < 1:
+                    raise ExtensionError('no snapshot block extends its local basis')
+                pod_modes = room if pod_modes is None else min(int(pod_modes), room)
+            return self.extend_basis_pod(U, modes=pod_modes)
+        if method != 'gram_schmidt':
+            raise ValueError("extend_basis: method is 'gram_schmidt' or 'pod', not {!r}".format(method))
         U = self._as_slab(U)
         added = 0
         for k in range(U.shape[2]):
@@ -425,6 +536,16 @@ class LRBMSReductor(LocalBasisSlab):
 
     def _as_slab(self, U):
         return U.tensor
+
+    def _pod_product(self):
+        return self.d.engine.P_diag
+
+    def _pod_width(self, width):
+        return int(width) + (int(width) & 1)          # even, as reserve() pads: the lean kernels of the fused pass take even N
+
+    def _pod_mark_dirty(self, idx):
+        local = self.d.engine.local
+        self._dirty = getattr(self, '_dirty', set()) | {int(local[i]) for i in idx}
 
     def reserve(self, width):
         """Room for local bases of up to ``width`` vectors: pads the slab with zero columns (to an even width: the lean kernels
