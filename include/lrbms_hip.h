@@ -455,6 +455,26 @@ int64_t lrbms_fom_solve_work_size(lrbms_ctx* ctx);
 int lrbms_fom_solve(lrbms_ctx* ctx, int32_t Q, const double* theta, const double* A_diag, const double* A_cpl, const double* b,
                     double* work, double* x, double rtol, int32_t max_iter, double* info, void* stream);
 
+/* Batched snapshots: nmu <= 64 parameters in one call, solved in panels of at most 16 columns, one after the other on the
+ * caller's stream.  Column m solves (sum_q theta[m][q] A_q) x_m = sum_j phi[m][j] b_K[j] from x = 0 (K = 1, phi = 1,
+ * b_K = b: the plain source).  No combined operator per column: the panel kernels read the Q uncombined blocks once per
+ * iteration for all columns.  Preconditioner: per column the inverse 3x3 diagonal element blocks of A(theta_m); one coarse
+ * level per call on the subdomain indicator functions, built at the mean theta of the call's columns (coarse option and S range
+ * of lrbms_fom_solve; without it, or if it is not positive definite, the element blocks alone).
+ *   theta [nmu][Q] host; phi [nmu][K] DEVICE; b_K [K][S][n]; X [S][n][nmu] (parameter fastest: a BlockVectorArray of nmu
+ *   vectors); work: lrbms_fom_solve_batch_work_size doubles.  1 <= nmu <= 64, 1 <= K <= 64, 1 <= Q <= 8, S_ext == S.
+ *   A panel iterates until its worst column is at or below rtol relative to |b_m|; a column with a zero right-hand side has no
+ *   say and comes back as exact zeros.  max_iter caps one panel; after a miss the remaining panels still run and the call
+ *   returns LRBMS_E_NOT_CONVERGED with every iterate in place.  info (host, may be NULL): iterations of the slowest panel,
+ *   worst final ratio.  No atomics: repeat calls give the same bits.
+ *   lrbms_fom_solve_batch_panel_info: out [4][2] host = (iterations, final ratio) of every panel of the last call on this
+ *   context (zeros for panels it did not have). */
+int64_t lrbms_fom_solve_batch_work_size(lrbms_ctx* ctx, int32_t nmu);
+int lrbms_fom_solve_batch(lrbms_ctx* ctx, int32_t Q, int32_t nmu, const double* theta, const double* A_diag, const double* A_cpl,
+                          int32_t K, const double* phi, const double* b_K, double* work, double* X, double rtol, int32_t max_iter,
+                          double* info, void* stream);
+int lrbms_fom_solve_batch_panel_info(lrbms_ctx* ctx, double* out);
+
 /* -- parabolic LRBMS (SURVEY.md section 8f "next" #3) --------------------------------------------------------- */
 /* InstationaryDuneDiscretization._solve (discretize_parabolic_block_swipdg.py:28-40) with pyMOR's
  * ImplicitEulerTimeStepper(nt) (:87), mass = block L2 product (:49-59):

@@ -74,6 +74,10 @@ SIGNATURES = {
     'lrbms_reduced_precond_use': (ctypes.c_int, [c_vp, c_i32, c_vp]),
     'lrbms_fom_solve_work_size': (c_i64, [c_vp]),
     'lrbms_fom_solve': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms_fom_solve_batch_work_size': (c_i64, [c_vp, c_i32]),
+    'lrbms_fom_solve_batch': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32,
+                                             _P_DBL, c_vp]),
+    'lrbms_fom_solve_batch_panel_info': (ctypes.c_int, [c_vp, _P_DBL]),
     'lrbms_fom_implicit_euler': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL,
                                                 c_vp]),
     'lrbms_mass_inverse_norm2': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
@@ -697,6 +701,32 @@ class NativeContext(ContextBase):
                                       self._stream())
         self._check(rc, 'lrbms_fom_solve')
         return x, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
+
+    def fom_solve_batch(self, theta, A_diag, A_cpl, phi, b_K, rtol=1e-12, max_iter=100000):
+        """Column m: A(theta[m]) x_m = sum_j phi[m][j] b_K[j] for nmu <= 64 parameters in one call (panels of 16 columns, one
+        coarse level at the mean theta) -> (X [S, n, nmu], info).  theta [nmu, Q] host; phi [nmu, K] host or device; b_K [K, S, n]."""
+        Q, S = A_diag.shape[0], self.S
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, Q)
+        if not self.torch.is_tensor(phi):
+            phi = self.from_numpy(np.ascontiguousarray(phi, dtype=np.float64))
+        K = phi.shape[1]
+        size = int(self.lib.lrbms_fom_solve_batch_work_size(self.handle, nmu))
+        if size < 0:
+            raise NativeError('lrbms_fom_solve_batch: nmu = {} is not in 1..64'.format(nmu))
+        work = self.empty(size)
+        X = self.empty(S, self.n, nmu)
+        info = np.zeros(2)
+        rc = self.lib.lrbms_fom_solve_batch(self.handle, Q, nmu, _dblp(th), self._ptr(A_diag, (Q, S, self.n_T, 4, 9), 'A_diag'),
+                                            self._ptr(A_cpl, (Q, S, 4, self.ncf, 9), 'A_cpl'), K, self._ptr(phi, (nmu, K), 'phi'),
+                                            self._ptr(b_K, (K, S, self.n), 'b_K'), c_vp(work.data_ptr()), c_vp(X.data_ptr()),
+                                            float(rtol), int(max_iter), _dblp(info), self._stream())
+        panels = np.zeros(8)
+        self.lib.lrbms_fom_solve_batch_panel_info(self.handle, _dblp(panels))
+        self._check(rc, 'lrbms_fom_solve_batch')
+        return X, {'iterations': int(info[0]), 'relative_residual': float(info[1]),
+                   'panel_iterations': [int(v) for v in panels[0:2 * ((nmu + 15) // 16):2]]}
 
     # ------------------------------------------------------------------ parabolic path
     def fom_implicit_euler(self, theta, dt, nt, A_diag, A_cpl, b, U0=None, rtol=1e-12, max_iter=100000):

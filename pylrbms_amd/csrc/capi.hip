@@ -25,6 +25,10 @@ int launch_local_correction(lrbms_ctx* ctx, int Q, const double* theta, int nmar
 int64_t fom_solve_work_size(lrbms_ctx* ctx);
 int launch_fom_solve(lrbms_ctx* ctx, int Q, const double* theta, const double* A_diag, const double* A_cpl, const double* b,
                      double* work, double* x, double rtol, int max_iter, double* info, hipStream_t st);
+int64_t fom_solve_batch_work_size(lrbms_ctx* ctx, int nmu);
+int launch_fom_solve_batch(lrbms_ctx* ctx, int Q, int nmu, const double* theta, const double* A_diag, const double* A_cpl, int K,
+                           const double* phi, const double* bK, double* work, double* X, double rtol, int max_iter, double* info,
+                           hipStream_t st);
 int launch_fom_implicit_euler(lrbms_ctx* ctx, int Q, const double* theta, double dt, int nt, const double* A_diag, const double* A_cpl,
                               const double* b, double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st);
 int launch_mass_inverse_norm2(lrbms_ctx* ctx, int C, const double* Y, double* out, hipStream_t st);
@@ -683,6 +687,26 @@ int lrbms_fom_solve(lrbms_ctx* ctx, int32_t Q, const double* theta, const double
   LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, 1); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, A_diag); CHECK_PTR(ctx, A_cpl);
   CHECK_PTR(ctx, b); CHECK_PTR(ctx, work); CHECK_PTR(ctx, x);
   return launch_fom_solve(ctx, Q, theta, A_diag, A_cpl, b, work, x, rtol, max_iter, info, (hipStream_t)stream);
+}
+
+int64_t lrbms_fom_solve_batch_work_size(lrbms_ctx* ctx, int32_t nmu) {
+  if (!ctx || !ctx->has_mesh) return -1;
+  return fom_solve_batch_work_size(ctx, nmu);
+}
+
+int lrbms_fom_solve_batch(lrbms_ctx* ctx, int32_t Q, int32_t nmu, const double* theta, const double* A_diag, const double* A_cpl,
+                          int32_t K, const double* phi, const double* b_K, double* work, double* X, double rtol, int32_t max_iter,
+                          double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, 1); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, A_diag); CHECK_PTR(ctx, A_cpl);
+  CHECK_PTR(ctx, phi); CHECK_PTR(ctx, b_K); CHECK_PTR(ctx, work); CHECK_PTR(ctx, X);
+  return launch_fom_solve_batch(ctx, Q, nmu, theta, A_diag, A_cpl, K, phi, b_K, work, X, rtol, max_iter, info, (hipStream_t)stream);
+}
+
+int lrbms_fom_solve_batch_panel_info(lrbms_ctx* ctx, double* out) {
+  if (!ctx) return LRBMS_E_INVALID;
+  CHECK_PTR(ctx, out);
+  for (int i = 0; i < 8; ++i) out[i] = ctx->fomb_panels[i];
+  return LRBMS_OK;
 }
 
 int lrbms_fom_implicit_euler(lrbms_ctx* ctx, int32_t Q, const double* theta, double dt, int32_t nt, const double* A_diag,

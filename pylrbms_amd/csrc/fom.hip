@@ -12,6 +12,10 @@
 // order everywhere, so every workgroup gets the same bits; 4 launches per iteration: 31.8 us, 2 launches: see DESIGN.md).
 // The host looks at |r| where the observed convergence rate predicts the tolerance, at most 100 iterations apart.
 // The theta-weighted blocks are combined once per solve.
+//
+// Batched snapshots (lrbms_fom_solve_batch): up to 64 parameters per call in panels of 16 columns.
+// The panel kernels k_fomb_* further down read the Q uncombined blocks once per iteration for all 16 columns and weight
+// them per lane with the column's own theta; the kernels above are untouched by it.
 #include <type_traits>
 #include "lrbms_dev.h"
 
@@ -564,6 +568,467 @@ int launch_fom_solve(lrbms_ctx* ctx, int Q, const double* theta, const double* A
   if (int rc = fom_cg_run(ctx, c, x, -1.0, rtol, max_iter, &it, &rel, st)) return rc;
   if (info) { info[0] = it; info[1] = rel; }
   if (rel > rtol) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve: CG did not reach rtol");
+  return LRBMS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Batched snapshots (lrbms_fom_solve_batch): up to 64 parameters per call, solved in panels of 16 columns.  Column m solves
+// (sum_q theta[m][q] A_q) x_m = sum_j phi[m][j] b_K[j] from x = 0; the panel vectors r, z, p, y are [S n][16] (column
+// fastest: the 16 lanes of a column group read 128 contiguous bytes), x lives in the caller's X [S][n][nmu].
+// No combined operator per column: the kernels read the Q uncombined blocks once per iteration and weight them per lane
+// with the column's own theta (the panel's table travels as a kernel argument).  Per iteration
+//   k_fomb_matvec    lane = (column, block of the element's block row), one wave per element:  beta = rz' / rz,
+//                    p = z + c0 + beta p, y = A(theta_m) p, partial p.y per workgroup and column
+//   k_fomb_update    lane = (column, element of four):  alpha = rz / pAp, x += alpha p, r -= alpha y, z = D(theta_m)^-1 r
+//                    with the 3x3 diagonal block combined and inverted on the fly, partial r.z and r.r
+//   k_fomb_restrict + k_coarse_apply (coarse level only): r0 = R0 r per column, c0 = A0^-1 r0, coarse part of r.z
+//   k_fomb_scalars   rz per column = the update kernel's partials + the coarse parts (one workgroup per column)
+// Workgroups of 1024 threads loop over the elements, at most 256 of them: a kernel leaves <= 256 x 16 partials, which the
+// next kernel's workgroups re-sum themselves (p.y: 4 loads per thread).  The r.z sum also has S coarse parts per column
+// (16 S values); re-summing those in every workgroup of two kernels would cost more than the one small dependent launch of
+// k_fomb_scalars.  Every sum runs in a fixed order and nothing is accumulated with atomics: repeat calls give the same bits.
+// One coarse level per call, built at the mean theta of the call's columns with the kernels of lrbms_fom_solve.
+namespace {
+
+struct ThetaP { double v[16][8]; };                  // theta of the panel's columns (1 KB of kernel arguments)
+
+constexpr int FOMB_THREADS = 1024, FOMB_GRID_MAX = 256;
+
+// sum over the G rows of part [G][16] in column (threadIdx.x & 15), returned to every thread of a 1024-thread workgroup
+// (64 row groups, then one fixed-order tree: the same bits in every workgroup).  red: 1024 doubles.
+__device__ inline double fomb_colsum(const double* __restrict__ part, int G, double* red) {
+  const int tid = threadIdx.x, c = tid & 15, j = tid >> 4;
+  double acc = 0.0;
+  for (int base = 0; base < G; base += 256) {
+    double v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int row = base + j + 64 * k;
+      v[k] = row < G ? part[(long)row * 16 + c] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc += v[k];
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int off = 512; off >= 16; off >>= 1) {
+    if (tid < off) red[tid] += red[tid + off];
+    __syncthreads();
+  }
+  const double out = red[c];
+  __syncthreads();
+  return out;
+}
+
+// the per-wave sums v (lanes 0..15: one per column) of the 16 waves of a workgroup -> out[blockIdx.x][16]; red: 256 doubles
+__device__ inline void fomb_store_partial(double v, double* red, double* __restrict__ out) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (lane < 16) red[wave * 16 + lane] = v;
+  __syncthreads();
+  if (tid < 16) {
+    double acc = 0.0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) acc += red[w * 16 + tid];
+    out[(long)blockIdx.x * 16 + tid] = acc;
+  }
+  __syncthreads();
+}
+
+// r [S n][16] = sum_j phi[m0 + c][j] b_K[j] (fma from the first product: K = 1, phi = 1 gives the bits of b), columns
+// c >= P zero;  X[.][m0 + c] = 0
+__global__ __launch_bounds__(256) void k_fomb_rhs(long nv, int K, int P, int nmu, int m0, const double* __restrict__ phi,
+                                                  const double* __restrict__ bK, double* __restrict__ r, double* __restrict__ X) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv * 16; i += (long)gridDim.x * blockDim.x) {
+    const long g = i >> 4;
+    const int c = (int)(i & 15);
+    double acc = 0.0;
+    if (c < P) {
+      const double* ph = phi + (long)(m0 + c) * K;
+      acc = ph[0] * bK[g];
+      for (int j = 1; j < K; ++j) acc = __fma_rn(ph[j], bK[(long)j * nv + g], acc);
+      X[g * nmu + m0 + c] = 0.0;
+    }
+    r[i] = acc;
+  }
+}
+
+// One wave per element: lane = (column c = lane & 15, block b = lane >> 4 of the element's block row: its own 3x3 block and
+// the three face neighbours').  The 16 lanes of a block share the loads of the Q uncombined blocks and weight them with
+// their own theta; the three row sums meet by two butterflies across the blocks.  rz_new / rz_old [16]: r.z per column
+// (k_fomb_scalars).  partial [gridDim.x][16] = p . y over the workgroup's elements.
+__global__ __launch_bounds__(1024) void k_fomb_matvec(Tmpl t, int S, int Q, int P, ThetaP th, const int* __restrict__ nbr,
+                                                      const double* __restrict__ A_diag, const double* __restrict__ A_cpl,
+                                                      const double* __restrict__ z, const double* __restrict__ p_old,
+                                                      const double* __restrict__ rz_new, const double* __restrict__ rz_old, int first,
+                                                      const double* __restrict__ c0, double* __restrict__ p_new,
+                                                      double* __restrict__ y, double* __restrict__ partial) {
+  __shared__ double red[256];
+  const long ne = (long)S * t.nT, nd = ne * 36, nc = (long)S * 4 * t.ncf * 9;
+  const int lane = threadIdx.x & 63, c = lane & 15, b = lane >> 4, wave = threadIdx.x >> 6;
+  const bool on = c < P;
+  double thq[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) thq[q] = q < Q ? th.v[c][q] : 0.0;
+  double beta = 0.0;
+  if (!first) {
+    const double rn = rz_new[c], ro = rz_old[c];
+    beta = ro != 0.0 ? rn / ro : 0.0;
+  }
+  double dot = 0.0;
+  for (long idx = (long)blockIdx.x * 16 + wave; idx < ne; idx += (long)gridDim.x * 16) {
+    const int e = (int)(idx % t.nT), s = (int)(idx / t.nT);
+    int e2 = e, s2 = s;
+    const double* bp = A_diag + idx * 36 + b * 9;
+    long qs = nd;
+    if (b > 0) {
+      const int nb = t.nb_elem[e * 3 + b - 1];
+      if (nb >= 0) {
+        e2 = nb;
+      } else {
+        const int side = -1 - nb;
+        s2 = nbr[s * 5 + side_to_slot(side)];
+        e2 = t.nb_elem_out[e * 3 + b - 1];
+        bp = A_cpl + (((long)s * 4 + side) * t.ncf + t.elem_side_pos[e * 3 + b - 1]) * 9;
+        qs = nc;
+      }
+    }
+    double acc[3] = {0.0, 0.0, 0.0}, pv[3] = {0.0, 0.0, 0.0};
+    if (s2 >= 0 && on) {
+      double blk[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) blk[k] = 0.0;
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        if (q < Q) {
+#pragma unroll
+          for (int k = 0; k < 9; ++k) blk[k] += thq[q] * bp[q * qs + k];
+        }
+      const long g = ((long)s2 * t.nT + e2) * 3;
+      const double cz = c0 ? c0[(long)s2 * 16 + c] : 0.0;          // coarse part of the preconditioned residual (constant per subdomain)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double zv = z[(g + i) * 16 + c] + cz;
+        const double po = first ? 0.0 : p_old[(g + i) * 16 + c];
+        pv[i] = zv + beta * po;
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) acc[i] = blk[i * 3] * pv[0] + blk[i * 3 + 1] * pv[1] + blk[i * 3 + 2] * pv[2];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      acc[i] += __shfl_xor(acc[i], 16, 64);
+      acc[i] += __shfl_xor(acc[i], 32, 64);
+    }
+    if (b == 0 && on) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        p_new[(idx * 3 + i) * 16 + c] = pv[i];
+        y[(idx * 3 + i) * 16 + c] = acc[i];
+        dot += pv[i] * acc[i];
+      }
+    }
+  }
+  fomb_store_partial(dot, red, partial);
+}
+
+// lane = (column c = lane & 15, element lane >> 4 of the wave's four).  alpha = rz / pAp per column (rz [16] from
+// k_fomb_scalars, pAp re-summed from ppap [npap][16]); the diagonal 3x3 block of A(theta_c) is combined from the Q diagonal
+// blocks and inverted on the spot (the expressions of k_fom_combine).  first: only z and the partials of the start residual.
+// x is column m0 + c of X [S n][nmu].  prz_out / prr [gridDim.x][16].
+__global__ __launch_bounds__(1024) void k_fomb_update(long ne, int Q, int P, int nmu, int m0, ThetaP th, const double* __restrict__ A_diag,
+                                                      const double* __restrict__ rz_in, const double* __restrict__ ppap, int npap,
+                                                      int first, double* __restrict__ X, double* __restrict__ r,
+                                                      const double* __restrict__ p, const double* __restrict__ y,
+                                                      double* __restrict__ z, double* __restrict__ prz_out, double* __restrict__ prr) {
+  __shared__ double red[1024];
+  const long nd = ne * 36;
+  const int lane = threadIdx.x & 63, c = lane & 15, sub = lane >> 4, wave = threadIdx.x >> 6;
+  const bool on = c < P;
+  double thq[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) thq[q] = q < Q ? th.v[c][q] : 0.0;
+  double alpha = 0.0;
+  if (!first) {
+    const double pap = fomb_colsum(ppap, npap, red);
+    const double rz = rz_in[c];
+    alpha = pap != 0.0 ? rz / pap : 0.0;
+  }
+  double rz = 0.0, rr = 0.0;
+  for (long e0 = ((long)blockIdx.x * 16 + wave) * 4; e0 < ne; e0 += (long)gridDim.x * 64) {
+    const long idx = e0 + sub;
+    if (idx < ne && on) {
+      double a[9], rv[3], xv[3] = {0.0, 0.0, 0.0}, pv[3] = {0.0, 0.0, 0.0}, yv[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < 9; ++k) a[k] = 0.0;
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        if (q < Q) {
+#pragma unroll
+          for (int k = 0; k < 9; ++k) a[k] += thq[q] * A_diag[q * nd + idx * 36 + k];
+        }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const long g = (idx * 3 + i) * 16 + c;
+        rv[i] = r[g];
+        if (!first) {
+          xv[i] = X[(idx * 3 + i) * nmu + m0 + c];
+          pv[i] = p[g];
+          yv[i] = y[g];
+        }
+      }
+      const double d0 = a[4] * a[8] - a[5] * a[7], d1 = a[5] * a[6] - a[3] * a[8], d2 = a[3] * a[7] - a[4] * a[6];
+      const double id = 1.0 / (a[0] * d0 + a[1] * d1 + a[2] * d2);
+      double M[9];
+      M[0] = d0 * id;
+      M[1] = (a[2] * a[7] - a[1] * a[8]) * id;
+      M[2] = (a[1] * a[5] - a[2] * a[4]) * id;
+      M[3] = d1 * id;
+      M[4] = (a[0] * a[8] - a[2] * a[6]) * id;
+      M[5] = (a[2] * a[3] - a[0] * a[5]) * id;
+      M[6] = d2 * id;
+      M[7] = (a[1] * a[6] - a[0] * a[7]) * id;
+      M[8] = (a[0] * a[4] - a[1] * a[3]) * id;
+      if (!first) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          X[(idx * 3 + i) * nmu + m0 + c] = xv[i] + alpha * pv[i];
+          rv[i] -= alpha * yv[i];
+          r[(idx * 3 + i) * 16 + c] = rv[i];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double zi = M[i * 3] * rv[0] + M[i * 3 + 1] * rv[1] + M[i * 3 + 2] * rv[2];
+        z[(idx * 3 + i) * 16 + c] = zi;
+        rz += rv[i] * zi;
+        rr += rv[i] * rv[i];
+      }
+    }
+  }
+  rz += __shfl_xor(rz, 16, 64);
+  rz += __shfl_xor(rz, 32, 64);
+  rr += __shfl_xor(rr, 16, 64);
+  rr += __shfl_xor(rr, 32, 64);
+  fomb_store_partial(rz, red, prz_out);
+  fomb_store_partial(rr, red, prr);
+}
+
+// r0 [S][16] = sum of the residual over subdomain s per column (restriction to the coarse space); zeroes the coarse solution
+// c0 [S][16] and the coarse parts prz_c [16][S] of r.z, which k_coarse_apply accumulates into.  One workgroup per subdomain.
+__global__ __launch_bounds__(256) void k_fomb_restrict(int S, int n, const double* __restrict__ r, double* __restrict__ r0,
+                                                       double* __restrict__ c0, double* __restrict__ prz_c) {
+  __shared__ double red[256];
+  const int s = blockIdx.x, tid = threadIdx.x, c = tid & 15, j = tid >> 4;
+  double acc = 0.0;
+  for (int base = 0; base < n; base += 128) {
+    double v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int i = base + j + 16 * k;
+      v[k] = i < n ? r[((long)s * n + i) * 16 + c] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc += v[k];
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int off = 128; off >= 16; off >>= 1) {
+    if (tid < off) red[tid] += red[tid + off];
+    __syncthreads();
+  }
+  if (tid < 16) {
+    r0[(long)s * 16 + tid] = red[tid];
+    c0[(long)s * 16 + tid] = 0.0;
+    prz_c[(long)tid * S + s] = 0.0;
+  }
+}
+
+// rz [16]: column blockIdx.x = the npart partials prz [npart][16] of the update kernel + the ncoarse coarse parts prz_c [16][ncoarse]
+__global__ __launch_bounds__(256) void k_fomb_scalars(const double* __restrict__ prz, int npart, const double* __restrict__ prz_c,
+                                                      int ncoarse, double* __restrict__ rz) {
+  __shared__ double red[256];
+  const int c = blockIdx.x;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < npart; i += 256) acc += prz[(long)i * 16 + c];
+  for (int i = threadIdx.x; i < ncoarse; i += 256) acc += prz_c[(long)c * ncoarse + i];
+  const double sum = block_sum_256(acc, red);
+  if (threadIdx.x == 0) rz[c] = sum;
+}
+
+struct FomB {
+  double *Amu_d, *Amu_c, *Minv;     // scratch of the coarse setup: the combined operator at the mean theta
+  double *r, *z, *p[2], *y;         // [nv][16]
+  double *ppap, *prz, *prr;         // [gm][16], [gu][16], [gu][16]
+  double *r0, *c0, *prz_c, *rz[2];  // [S][16], [S][16], [16][S], [16] each
+  const double* A0inv = nullptr;
+  long ne, nv;
+  int gm, gu;                       // workgroups (= partial rows) of the matvec (16 elements per pass) / update kernel (64)
+  static long scratch(lrbms_ctx* ctx) {
+    const long S = ctx->S, ne = S * ctx->t.nT;
+    return ne * 36 + S * 4 * ctx->t.ncf * 9 + ne * 9;
+  }
+  static long total(lrbms_ctx* ctx) {
+    const long S = ctx->S, ne = S * ctx->t.nT;
+    return scratch(ctx) + 5 * ne * 3 * 16 + 3 * FOMB_GRID_MAX * 16 + 3 * S * 16 + 32 + 16;
+  }
+  void carve(lrbms_ctx* ctx, double* work) {
+    const Tmpl& t = ctx->t;
+    const long S = ctx->S;
+    ne = S * t.nT;
+    nv = ne * 3;
+    gm = (int)((ne + 15) / 16 < FOMB_GRID_MAX ? (ne + 15) / 16 : FOMB_GRID_MAX);
+    gu = (int)((ne + 63) / 64 < FOMB_GRID_MAX ? (ne + 63) / 64 : FOMB_GRID_MAX);
+    Amu_d = work;
+    Amu_c = Amu_d + ne * 36;
+    Minv = Amu_c + S * 4 * t.ncf * 9;
+    r = work + scratch(ctx);
+    z = r + nv * 16;
+    p[0] = z + nv * 16;
+    p[1] = p[0] + nv * 16;
+    y = p[1] + nv * 16;
+    ppap = y + nv * 16;
+    prz = ppap + FOMB_GRID_MAX * 16;
+    prr = prz + FOMB_GRID_MAX * 16;
+    r0 = prr + FOMB_GRID_MAX * 16;
+    c0 = r0 + S * 16;
+    prz_c = c0 + S * 16;
+    rz[0] = prz_c + S * 16;
+    rz[1] = rz[0] + 16;               // ends at total() - 16
+  }
+};
+
+// r.r per column from the update kernel's partials (host sum, fixed order)
+int fomb_host_rr(lrbms_ctx* ctx, const FomB& b, std::vector<double>& host, double* rr, hipStream_t st) {
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host.data(), b.prr, sizeof(double) * (size_t)b.gu * 16, hipMemcpyDeviceToHost, st));
+  LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  for (int c = 0; c < 16; ++c) {
+    double acc = 0.0;
+    for (int i = 0; i < b.gu; ++i) acc += host[(size_t)i * 16 + c];
+    rr[c] = acc;
+  }
+  return LRBMS_OK;
+}
+
+// z -> coarse part and r.z per column for the residual the update kernel has just written
+int fomb_precond_tail(lrbms_ctx* ctx, FomB& b, double* rz_out, hipStream_t st) {
+  const int S = ctx->S;
+  if (b.A0inv) {
+    hipLaunchKernelGGL(k_fomb_restrict, dim3(S), dim3(256), 0, st, S, ctx->t.n, b.r, b.r0, b.c0, b.prz_c);
+    LRBMS_LAUNCH_CHECK(ctx);
+    if (int rc = launch_coarse_apply(ctx, 1, 16, b.A0inv, b.r0, b.c0, b.prz_c, st)) return rc;
+  }
+  hipLaunchKernelGGL(k_fomb_scalars, dim3(16), dim3(256), 0, st, b.prz, b.gu, b.prz_c, b.A0inv ? S : 0, rz_out);
+  LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}
+
+// PCG on one panel of P <= 16 columns (columns m0 .. m0 + P - 1 of the call): iterates until the worst column with a
+// nonzero right-hand side is at or below rtol (relative to |b_m|); the host checks follow fom_cg_run.
+int fomb_panel_run(lrbms_ctx* ctx, FomB& b, int Q, int P, int nmu, int m0, const ThetaP& th, const double* A_diag, const double* A_cpl,
+                   double* X, double rtol, int max_iter, int* its, double* rel_out, hipStream_t st) {
+  const Tmpl& t = ctx->t;
+  const int S = ctx->S;
+  const double* c0 = b.A0inv ? b.c0 : nullptr;
+  std::vector<double> host((size_t)b.gu * 16);
+  hipLaunchKernelGGL(k_fomb_update, dim3(b.gu), dim3(FOMB_THREADS), 0, st, b.ne, Q, P, nmu, m0, th, A_diag, b.rz[0], b.ppap, b.gm, 1, X, b.r,
+                     b.p[0], b.y, b.z, b.prz, b.prr);
+  LRBMS_LAUNCH_CHECK(ctx);
+  if (int rc = fomb_precond_tail(ctx, b, b.rz[0], st)) return rc;
+  double ref2[16], rr[16];
+  if (int rc = fomb_host_rr(ctx, b, host, ref2, st)) return rc;
+  auto worst = [&](const double* cur) {
+    double w = 0.0;
+    for (int c = 0; c < P; ++c)
+      if (ref2[c] != 0.0) {
+        const double rel = sqrt(cur[c] / ref2[c]);
+        if (!(rel == rel)) return rel;                      // NaN
+        if (rel > w) w = rel;
+      }
+    return w;
+  };
+  *its = 0;
+  double rel = worst(ref2);                                  // 1, or 0 if every right-hand side of the panel is zero
+  *rel_out = 0.0;
+  if (rel == 0.0) return LRBMS_OK;
+  int it = 0, block = 10;
+  while (rel > rtol && it < max_iter) {
+    if (block > max_iter - it) block = max_iter - it;
+    for (int k = 0; k < block; ++k, ++it) {
+      const int c = it & 1, o = c ^ 1;
+      hipLaunchKernelGGL(k_fomb_matvec, dim3(b.gm), dim3(FOMB_THREADS), 0, st, t, S, Q, P, th, ctx->nbr, A_diag, A_cpl, b.z, b.p[o], b.rz[c],
+                         b.rz[o], it == 0 ? 1 : 0, c0, b.p[c], b.y, b.ppap);
+      hipLaunchKernelGGL(k_fomb_update, dim3(b.gu), dim3(FOMB_THREADS), 0, st, b.ne, Q, P, nmu, m0, th, A_diag, b.rz[c], b.ppap, b.gm, 0, X,
+                         b.r, b.p[c], b.y, b.z, b.prz, b.prr);
+      if (int rc = fomb_precond_tail(ctx, b, b.rz[o], st)) return rc;
+    }
+    LRBMS_LAUNCH_CHECK(ctx);
+    if (int rc = fomb_host_rr(ctx, b, host, rr, st)) return rc;
+    rel = worst(rr);
+    if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve_batch: NaN residual (operator not SPD?)");
+    const double rate = log(rel) / it;
+    block = 25;
+    if (rel > rtol && rate < 0.0) {                          // aim a little short: CG converges superlinearly
+      const double need = 0.8 * (log(rtol) - log(rel)) / rate;
+      block = need < 4.0 ? 4 : need > 100.0 ? 100 : (int)need;
+    }
+  }
+  *its = it;
+  *rel_out = rel;
+  return LRBMS_OK;
+}
+
+}  // namespace
+
+int64_t fom_solve_batch_work_size(lrbms_ctx* ctx, int nmu) {
+  if (nmu < 1 || nmu > 64) return -1;
+  return FomB::total(ctx);
+}
+
+int launch_fom_solve_batch(lrbms_ctx* ctx, int Q, int nmu, const double* theta, const double* A_diag, const double* A_cpl, int K,
+                           const double* phi, const double* bK, double* work, double* X, double rtol, int max_iter, double* info,
+                           hipStream_t st) {
+  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_solve_batch needs all subdomains on one rank");
+  if (Q < 1 || Q > 8 || nmu < 1 || nmu > 64 || K < 1 || K > 64 || max_iter < 1 || !(rtol > 0.0))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_solve_batch: bad Q / nmu / K / max_iter / rtol");
+  FomB b;
+  b.carve(ctx, work);
+  // one coarse level per call, at the mean theta of its columns (summed in column order)
+  double* A0 = nullptr;
+  if (int rc = coarse_begin(ctx, &A0, st)) return rc;
+  if (A0) {
+    QVecF tb;
+    for (int q = 0; q < 8; ++q) {
+      double acc = 0.0;
+      for (int m = 0; q < Q && m < nmu; ++m) acc += theta[(long)m * Q + q];
+      tb.v[q] = acc / nmu;
+    }
+    hipLaunchKernelGGL(k_fom_combine, dim3(4096), dim3(256), 0, st, ctx->t, ctx->S, Q, tb, 0.0, A_diag, A_cpl, b.Amu_d, b.Amu_c, b.Minv);
+    hipLaunchKernelGGL(k_fom_coarse_entries, dim3(ctx->S), dim3(256), 0, st, ctx->t, ctx->S, ctx->nbr, b.Amu_d, b.Amu_c, A0);
+    LRBMS_LAUNCH_CHECK(ctx);
+    if (int rc = coarse_finish(ctx, &b.A0inv, st)) return rc;
+  }
+  int its_max = 0;
+  double worst = 0.0;
+  bool missed = false;
+  for (int i = 0; i < 8; ++i) ctx->fomb_panels[i] = 0.0;
+  for (int m0 = 0; m0 < nmu; m0 += 16) {
+    const int P = nmu - m0 < 16 ? nmu - m0 : 16;
+    ThetaP th;
+    for (int c = 0; c < 16; ++c)
+      for (int q = 0; q < 8; ++q) th.v[c][q] = (c < P && q < Q) ? theta[(long)(m0 + c) * Q + q] : 0.0;
+    hipLaunchKernelGGL(k_fomb_rhs, dim3(2048), dim3(256), 0, st, b.nv, K, P, nmu, m0, phi, bK, b.r, X);
+    LRBMS_LAUNCH_CHECK(ctx);
+    int it = 0;
+    double rel = 0.0;
+    if (int rc = fomb_panel_run(ctx, b, Q, P, nmu, m0, th, A_diag, A_cpl, X, rtol, max_iter, &it, &rel, st)) return rc;
+    ctx->fomb_panels[m0 / 16 * 2] = it;
+    ctx->fomb_panels[m0 / 16 * 2 + 1] = rel;
+    if (it > its_max) its_max = it;
+    if (rel > worst) worst = rel;
+    if (rel > rtol) missed = true;
+  }
+  if (info) { info[0] = its_max; info[1] = worst; }
+  if (missed) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve_batch: CG did not reach rtol");
   return LRBMS_OK;
 }
 

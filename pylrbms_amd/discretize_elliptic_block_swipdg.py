@@ -239,6 +239,42 @@ class DuneDiscretization:
         x = x[torch.as_tensor(eng.local, device=x.device)]
         return BlockVectorArray(x.reshape(eng.S, eng.t.n, 1), self.solution_space)
 
+    def solve_batch(self, mus, inverse_options=None):
+        """Snapshots for a whole training set: one ``BlockVectorArray`` of ``len(mus)`` vectors ``[S, n, len(mus)]`` (the layout
+        ``extend_basis`` takes), 64 parameters per native ``lrbms_fom_solve_batch`` call (panels of 16 columns that share every
+        read of the operator blocks; one coarse level per call at the mean theta).  ``precision`` / ``max_iter`` as in ``solve``.
+        ``last_solve_info``: the largest iteration count of a panel and the worst final residual ratio.  On a sharded grid
+        it is the loop of ``solve``."""
+        import torch
+        eng = self.engine
+        mus = list(mus)
+        if not mus:
+            raise ValueError('solve_batch: no parameters')
+        if eng.S_ext != eng.S:
+            cols, its, rel = [], 0, 0.0
+            for mu in mus:
+                cols.append(self.solve(mu, inverse_options=inverse_options).tensor)
+                its = max(its, self.last_solve_info['iterations'])
+                rel = max(rel, self.last_solve_info['relative_residual'])
+            self.last_solve_info = {'iterations': its, 'relative_residual': rel}
+            return BlockVectorArray(torch.cat(cols, dim=2).contiguous(), self.solution_space)
+        opts = inverse_options or {}
+        rtol = float(opts.get('precision', 1e-12)) if isinstance(opts, dict) else 1e-12
+        rtol = min(rtol, 1e-10)
+        max_iter = int(opts.get('max_iter', 20000)) if isinstance(opts, dict) else 20000
+        max_iter = max(max_iter, 20000)
+        theta = np.stack([self.theta(mu) for mu in mus])
+        phi = np.stack([self.f_coefficients(mu) for mu in mus])
+        b_K = self._affine_f['b_K'] if self._affine_f is not None else eng.b.reshape(1, eng.S, eng.t.n)
+        cols, its, rel = [], 0, 0.0
+        for m0 in range(0, len(mus), 64):
+            X, info = eng.ctx.fom_solve_batch(theta[m0:m0 + 64], eng.A_diag, eng.A_cpl, phi[m0:m0 + 64], b_K, rtol=rtol,
+                                              max_iter=max_iter)
+            cols.append(X)
+            its, rel = max(its, info['iterations']), max(rel, info['relative_residual'])
+        self.last_solve_info = {'iterations': its, 'relative_residual': rel}
+        return BlockVectorArray(cols[0] if len(cols) == 1 else torch.cat(cols, dim=2).contiguous(), self.solution_space)
+
     def _owned_subdomains(self):
         """One list of global subdomain indices per rank (every rank computes the same lists)."""
         if getattr(self, '_owned', None) is None:
