@@ -259,6 +259,28 @@ int64_t lrbms3_fom_solve_work_size(lrbms3_ctx* ctx);
 int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const double* A_diag, const double* A_cpl, const double* b,
                      double* work, double* x, double rtol, int32_t max_iter, double* info, void* stream);
 
+/* Batched snapshots (2D: lrbms_fom_solve_batch): column m of X [S][n][nmu] (column fastest) solves
+ *     (sum_q theta[m][q] A_q) x_m = sum_j phi[m][j] b_K[j]        theta [nmu][Q] host, phi [nmu][K] device, b_K [K][S][n]
+ * from x = 0, 1 <= nmu <= 64 columns per call in panels of at most 16, one after the other on the caller's stream.  The panel
+ * kernels read the Q uncombined blocks of A_diag / A_cpl once per iteration for all columns of the panel (fp64 matrix cores) and
+ * weight them with the column's own theta; there is no combined operator per column.  ONE preconditioner per call, both levels
+ * (inverse 10 x 10 element blocks, coarse level of lrbms3_fom_coarse_space) built at the mean theta of the call's columns, summed
+ * in column order; the coarse inverse is private to the call, the one lrbms3_fom_precond_keep keeps is neither read nor replaced.
+ * x is updated in place in X; max_iter caps ONE panel and is honoured exactly (a call with max_iter = k leaves the k-th PCG iterate
+ * of every column).  info[0] = largest iteration count of a panel, info[1] = worst final |r| / |b_m| (host, may be NULL); the host
+ * reads r.r per column every 16 iterations.  LRBMS_E_NOT_CONVERGED after a miss (the remaining panels still run).  A column with a
+ * zero right-hand side stays exactly zero and has no say in convergence; all right-hand sides zero: LRBMS_OK, info = (0, 0).
+ * Fixed summation orders, no atomics: repeat calls give the same bits, equal columns give equal bits wherever they stand.
+ * LRBMS_E_INVALID before any launch (work and X untouched): Q outside [1, 8], nmu outside [1, 64], K outside [1, 64], rtol not
+ * > 0, max_iter < 1, a null pointer, S_ext != S.  work: lrbms3_fom_solve_batch_work_size doubles (< 0: no mesh, nmu outside
+ * [1, 64]).  lrbms3_fom_solve_batch_panel_info: out [4][2] = (iterations, final ratio) per panel of the last call, zeros for
+ * panels it did not have. */
+int64_t lrbms3_fom_solve_batch_work_size(lrbms3_ctx* ctx, int32_t nmu);
+int lrbms3_fom_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t nmu, const double* theta, const double* A_diag, const double* A_cpl,
+                           int32_t K, const double* phi, const double* b_K, double* work, double* X, double rtol, int32_t max_iter,
+                           double* info, void* stream);
+int lrbms3_fom_solve_batch_panel_info(lrbms3_ctx* ctx, double* out);
+
 /* y [S][n][M] = sum_q theta_q (A_diag_q x_s + sum_sides A_cpl_q x_neighbour), x [S_ext][n][M].  2D: lrbms_fom_apply. */
 int lrbms3_fom_apply(lrbms3_ctx* ctx, int32_t Q, int32_t M, const double* theta, const double* A_diag, const double* A_cpl,
                      const double* x, double* y, void* stream);

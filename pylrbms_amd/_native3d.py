@@ -51,6 +51,11 @@ SIGNATURES3 = {
     'lrbms3_reduced_precond_use': (ctypes.c_int, [c_vp, c_i32, c_vp]),
     'lrbms3_fom_solve_work_size': (c_i64, [c_vp]),
     'lrbms3_fom_solve': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    # batched snapshots
+    'lrbms3_fom_solve_batch_work_size': (c_i64, [c_vp, c_i32]),
+    'lrbms3_fom_solve_batch': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32,
+                                              _P_DBL, c_vp]),
+    'lrbms3_fom_solve_batch_panel_info': (ctypes.c_int, [c_vp, _P_DBL]),
     'lrbms3_fom_apply': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'lrbms3_mass_inverse_norm2': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms3_project_mass': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
@@ -362,6 +367,37 @@ class Native3DContext(_native.ContextBase):
                                        c_vp(work.data_ptr()), c_vp(x.data_ptr()), float(rtol), int(max_iter), info, self._stream())
         self._check(rc, 'lrbms3_fom_solve')
         return x, (int(info[0]), float(info[1]))
+
+    def fom_solve_batch(self, thetas, A_diag, A_cpl, phi, b_K, rtol=1e-10, max_iter=50000, work=None):
+        """Column m: A(thetas[m]) x_m = sum_j phi[m][j] b_K[j] for nmu <= 64 parameters in one call (``lrbms3_fom_solve_batch``:
+        panels of 16 columns on the matrix cores, one two-level preconditioner at the mean theta) -> (X [S, n, nmu], info).
+        thetas [nmu, Q] host; phi [nmu, K] host or device; b_K [K, S, n].  ``info``: ``iterations`` (largest panel count),
+        ``relative_residual`` (worst final |r| / |b_m|), ``panel_iterations``."""
+        Q, S = int(A_diag.shape[0]), self.S
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, Q)
+        K = int(b_K.shape[0])
+        ph = self._dev2(phi, (nmu, K), 'phi')
+        size = int(self.lib.lrbms3_fom_solve_batch_work_size(self.handle, nmu))
+        if size < 0:
+            raise NativeError('lrbms3_fom_solve_batch: nmu = {} is not in 1..64'.format(nmu))
+        if work is None:
+            work = self.empty(size)
+        elif work.numel() < size:
+            raise NativeError('work buffer too small')
+        X = self.empty(S, self.n, nmu)
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_fom_solve_batch(self.handle, Q, nmu, th.ctypes.data_as(_P_DBL),
+                                             self._ptr(A_diag, (Q, S, self.n_T, 5, 100), 'A_diag'),
+                                             self._ptr(A_cpl, (Q, S, 6, self.ncf, 100), 'A_cpl'), K, c_vp(ph.data_ptr()),
+                                             self._ptr(b_K, (K, S, self.n), 'b_K'), c_vp(work.data_ptr()), c_vp(X.data_ptr()),
+                                             float(rtol), int(max_iter), info, self._stream())
+        panels = (c_dbl * 8)()
+        self.lib.lrbms3_fom_solve_batch_panel_info(self.handle, panels)
+        self._check(rc, 'lrbms3_fom_solve_batch')
+        return X, {'iterations': int(info[0]), 'relative_residual': float(info[1]),
+                   'panel_iterations': [int(v) for v in list(panels)[0:2 * ((nmu + 15) // 16):2]]}
 
     def fom_apply(self, Q, theta, A_diag, A_cpl, x):
         M = x.shape[2]

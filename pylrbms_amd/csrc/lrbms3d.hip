@@ -54,6 +54,7 @@ struct lrbms3_ctx : lrbms_ctx_base {
   double* fom_pc = nullptr;       // [M][M] device (owned), valid for fom_pc_M = nc S unknowns of fom_pc_nc functions
   long fom_pc_M = 0;
   int fom_pc_nc = 0;
+  double fomb_panels[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // lrbms3_fom_solve_batch: (iterations, final ratio) of the up to four panels of the last call
   void* blas = nullptr;           // rocBLAS handle (dense coarse inverses), created on first use
   const double* user_pc = nullptr;   // coarse inverse the batched reduced solve uses (lrbms3_reduced_precond_use), caller-owned
   int user_pc_N = 0;
@@ -4188,9 +4189,476 @@ int fom_cg(lrbms3_ctx* ctx, hipStream_t st, FomWork& w, int nc, const double* A1
   return LRBMS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------- batched snapshots
+// lrbms3_fom_solve_batch: up to 64 parameters per call in panels of 16 columns.  Column m solves
+// (sum_q theta[m][q] A_q) x_m = sum_j phi[m][j] b_K[j] from x = 0; the panel vectors r, z, p, y are [S n][16] (column fastest: the
+// 16 lanes of a matrix-core operand row read 128 contiguous bytes), x lives in the caller's X [S][n][nmu].  There is no combined
+// operator per column: k3fb_matvec reads the Q uncombined blocks once per iteration for all 16 columns and folds the column's
+// theta into the direction operand.  ONE preconditioner per call, both levels at the mean theta of the call (k3_combine,
+// k3f_block_inverse, fom_coarse with a private inverse).  Per iteration
+//   k3fb_dir           p = z + R0^T y0 + beta p                          (beta = rz' / rz per column, 0 when rz = 0)
+//   k3fb_matvec        y = A(theta_m) p on the fp64 matrix cores, p.y per workgroup and column
+//   k3fb_scalars       pAp per column
+//   k3fb_update        alpha = rz / pAp (0 when pAp = 0), x += alpha p, r -= alpha y, z = Dinv r (matrix cores), per workgroup and
+//                      column r.z, r.r and the nc restriction sums phi_k . r
+//   k3fb_coarse_r0 + k3fb_coarse_apply   r0, y0 = A1inv r0, the coarse parts of r.z          (coarse level only)
+//   k3fb_scalars       rz per column
+// Every sum has a fixed order that depends on the mesh alone and no atomics are used: repeat calls give the same bits, and a
+// column's bits do not depend on its place in the panel (a lane owns one column: li = lane & 15).  Columns >= P of the panel
+// vectors are neither loaded nor stored.  scal [5][16]: rz (two alternating slots), pAp, rr, bb.
+//
+// Matrix-core tiles (v_mfma_f64_16x16x4): A operand lane l = M[row l & 15][k = (l >> 4) + 4 ks], B operand lane l =
+// V[k = (l >> 4) + 4 ks][column l & 15], result register r of lane l = (row (l >> 4) + 4 r, column l & 15).  The 10 x 10 blocks
+// are padded to 16 x 12 with zeros in the operand, never in memory.
+
+// The five blocks of element e's block row: where the q = 0 block lies, its stride over q, whether it is used transposed, and the
+// first entry of the direction it multiplies (nullptr: no block -- a physical boundary face).
+struct Fb3Row {
+  const double* src[5];
+  const double* pb[5];
+  long qs[5];
+  bool tr[5];
+};
+
+// y = A(theta_m) p for the 16 columns of a panel.  One wave per element at a time, four waves per workgroup, FOM_EPB elements per
+// workgroup, all workgroups of a subdomain on one XCD (xcd_block).  Per (element, q) the wave moves its five blocks from global
+// memory into the LDS with ONE 16-byte load per lane and block (50 lanes, 800 contiguous bytes) and reads the operand order of
+// the matrix cores from there; inside a subdomain the block towards the lower-index neighbour is that element's block read
+// transposed from the LDS (k3f_matvec's symmetric read: the second reader finds it in the XCD's L2).  The column's theta_q
+// multiplies the direction operand, every (block, q) adds three k-steps to the ONE accumulator tile of the element.
+__global__ __launch_bounds__(256) void k3fb_matvec(T3 t, int nbx, int Q, int P, TB th, const double* __restrict__ A_diag,
+                                                   const double* __restrict__ A_cpl, const double* __restrict__ p,
+                                                   double* __restrict__ y, double* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) double blk[4][5][104];
+  __shared__ double ths[128];
+  __shared__ double red[4][16];
+  int s, bx;
+  if (!xcd_block(nbx, t.S, bx, s)) return;
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (tid < 128) ths[tid] = th.v[tid >> 3][tid & 7];
+  __syncthreads();
+  const bool col = li < P;
+  const long qd = (long)t.S * t.nT * 500, qc = (long)t.S * 6 * t.ncf * 100;
+  const double* Ad = A_diag + (long)s * t.nT * 500;
+  const double* ps = p + (long)s * t.n * 16;
+  const int ii = li < 10 ? li : 9;
+  double py = 0.0;
+  const int e1 = (bx + 1) * FOM_EPB < t.nT ? (bx + 1) * FOM_EPB : t.nT;
+  for (int e = bx * FOM_EPB + wave; e < e1; e += 4) {
+    const int4 nb = *reinterpret_cast<const int4*>(t.nb_elem + e * 4);
+    const int nbv[4] = {nb.x, nb.y, nb.z, nb.w};
+    Fb3Row row;
+    row.src[0] = Ad + (long)e * 500;
+    row.pb[0] = ps + (long)e * 160;
+    row.qs[0] = qd;
+    row.tr[0] = false;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      const int ee = nbv[f];                          // wave-uniform
+      row.src[1 + f] = nullptr;
+      row.pb[1 + f] = ps;
+      row.qs[1 + f] = qd;
+      row.tr[1 + f] = false;
+      if (ee >= 0) {
+        if (ee < e) {                                 // the lower element's block towards e, used transposed
+          const int4 nb2 = *reinterpret_cast<const int4*>(t.nb_elem + ee * 4);
+          const int fb = nb2.x == e ? 0 : (nb2.y == e ? 1 : (nb2.z == e ? 2 : 3));
+          row.src[1 + f] = Ad + (long)ee * 500 + (1 + fb) * 100;
+          row.tr[1 + f] = true;
+        } else {
+          row.src[1 + f] = Ad + (long)e * 500 + (1 + f) * 100;
+        }
+        row.pb[1 + f] = ps + (long)ee * 160;
+      } else {
+        const int side = -(ee + 1), ss = t.nbr[s * 7 + side_slot(side)];
+        if (ss >= 0) {
+          row.src[1 + f] = A_cpl + (((long)s * 6 + side) * t.ncf + t.face_pos[e * 4 + f]) * 100;
+          row.qs[1 + f] = qc;
+          row.pb[1 + f] = p + ((long)ss * t.n + t.nb_out[e * 4 + f] * 10) * 16;
+        }
+      }
+    }
+    // direction operands: rows lk, lk + 4, lk + 8 of the block's ten, this lane's column
+    double pv[5][3];
+#pragma unroll
+    for (int b = 0; b < 5; ++b)
+#pragma unroll
+      for (int ks = 0; ks < 3; ++ks) {
+        const int k = lk + 4 * ks;
+        pv[b][ks] = (row.src[b] && col && k < 10) ? row.pb[b][k * 16 + li] : 0.0;
+      }
+    d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
+    for (int q = 0; q < Q; ++q) {
+      double2 a2[5];
+#pragma unroll
+      for (int b = 0; b < 5; ++b) {
+        a2[b] = make_double2(0.0, 0.0);
+        if (row.src[b] && lane < 50) a2[b] = *reinterpret_cast<const double2*>(row.src[b] + q * row.qs[b] + 2 * lane);
+      }
+      __builtin_amdgcn_wave_barrier();               // (the reads of the previous q come first: LDS operations of a wave run in order)
+#pragma unroll
+      for (int b = 0; b < 5; ++b)
+        if (row.src[b] && lane < 50) *reinterpret_cast<double2*>(&blk[wave][b][2 * lane]) = a2[b];
+      __builtin_amdgcn_wave_barrier();
+      const double tq = ths[li * 8 + q];
+#pragma unroll
+      for (int b = 0; b < 5; ++b) {
+        if (!row.src[b]) continue;                    // wave-uniform
+#pragma unroll
+        for (int ks = 0; ks < 3; ++ks) {
+          const int k = lk + 4 * ks, kk = k < 10 ? k : 9;
+          const double av = blk[wave][b][row.tr[b] ? kk * 10 + ii : ii * 10 + kk];
+          const double a = (li < 10 && k < 10) ? av : 0.0;
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, tq * pv[b][ks], acc, 0, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const int i = lk + 4 * r;
+      if (i < 10 && col) {
+        y[((long)s * t.n + e * 10 + i) * 16 + li] = acc[r];
+        py += acc[r] * pv[0][r];
+      }
+    }
+  }
+  py += __shfl_xor(py, 16);
+  py += __shfl_xor(py, 32);
+  if (lk == 0) red[wave][li] = py;
+  __syncthreads();
+  if (tid < 16) part[((long)s * nbx + bx) * 16 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// r [S n][16] = sum_j phi[m0 + c][j] b_K[j] (fma from the first product: K = 1, phi = 1 gives the bits of b), X[.][m0 + c] = 0
+__global__ __launch_bounds__(256) void k3fb_rhs(long nv, int K, int P, int nmu, int m0, const double* __restrict__ phi,
+                                                const double* __restrict__ bK, double* __restrict__ r, double* __restrict__ X) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x, g = i >> 4;
+  const int c = (int)(i & 15);
+  if (g >= nv || c >= P) return;
+  const double* ph = phi + (long)(m0 + c) * K;
+  double acc = ph[0] * bK[g];
+  for (int j = 1; j < K; ++j) acc = __fma_rn(ph[j], bK[(long)j * nv + g], acc);
+  r[i] = acc;
+  X[g * nmu + m0 + c] = 0.0;
+}
+
+// p = z + R0^T y0 + beta p per column (y0 [S nc][16]); the first direction does not read p.  Grid (16 n / 256, S): the subdomain
+// is a block index, no division per entry (measured: 281 us at config 5 either way, 2.7 TB/s on 8-byte lane accesses).
+__global__ __launch_bounds__(256) void k3fb_dir(int P, int first, int cur, const double* __restrict__ scal,
+                                                const double* __restrict__ z, double* __restrict__ p, int n, int nc,
+                                                const double* __restrict__ Phi, const double* __restrict__ y0) {
+  const int j = blockIdx.x * 256 + threadIdx.x, dof = j >> 4, c = j & 15, s = blockIdx.y;
+  if (dof >= n || c >= P) return;
+  const long i = ((long)s * n + dof) * 16 + c;
+  double zi = z[i];
+  for (int k = 0; k < nc; ++k) zi += Phi[dof * 4 + k] * y0[((long)s * nc + k) * 16 + c];
+  if (first) {
+    p[i] = zi;
+    return;
+  }
+  const double old = scal[(cur ^ 1) * 16 + c];
+  const double beta = old != 0.0 ? scal[cur * 16 + c] / old : 0.0;
+  p[i] = zi + beta * p[i];
+}
+
+// x += alpha p, r -= alpha y, z = Dinv r (init: r is the right-hand side k3fb_rhs wrote, x = 0 already; p and y are not read).
+// One wave per element at a time in the lane layout of the matrix-core tile: lane (column li, rows lk + 4 ks).  The packed
+// inverse block (56 doubles) goes through the LDS like the blocks of k3fb_matvec, z_e [10 x 16] is one 3 k-step tile.
+// prz, prr [S nbx][16], pr0 [S nbx][4][16].
+__global__ __launch_bounds__(256) void k3fb_update(T3 t, int P, int nmu, int m0, int init, int cur, const double* __restrict__ scal,
+                                                   const double* __restrict__ Dinv, const double* __restrict__ p,
+                                                   const double* __restrict__ y, double* __restrict__ X, double* __restrict__ r,
+                                                   double* __restrict__ z, double* __restrict__ prz, double* __restrict__ prr, int nc,
+                                                   const double* __restrict__ Phi, double* __restrict__ pr0) {
+  __shared__ __attribute__((aligned(16))) double dinv[4][56];
+  __shared__ double red[4][6][16];
+  const int s = blockIdx.y, bx = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool col = li < P;
+  double alpha = 0.0;
+  if (!init && col) {
+    const double pap = scal[32 + li];
+    alpha = pap != 0.0 ? scal[cur * 16 + li] / pap : 0.0;
+  }
+  double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // r.z, r.r, phi_k . r
+  const int e1 = (bx + 1) * FOM_EPB < t.nT ? (bx + 1) * FOM_EPB : t.nT;
+  for (int e = bx * FOM_EPB + wave; e < e1; e += 4) {
+    const double* D = Dinv + ((long)s * t.nT + e) * 56;
+    double2 d2 = make_double2(0.0, 0.0);
+    if (lane < 28) d2 = *reinterpret_cast<const double2*>(D + 2 * lane);
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 28) *reinterpret_cast<double2*>(&dinv[wave][2 * lane]) = d2;
+    __builtin_amdgcn_wave_barrier();
+    double rn[3];
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) {
+      const int i = lk + 4 * ks;
+      rn[ks] = 0.0;
+      if (i < 10 && col) {
+        const long g = (long)s * t.n + e * 10 + i, d = g * 16 + li;
+        if (init) {
+          rn[ks] = r[d];
+        } else {
+          X[g * nmu + m0 + li] += alpha * p[d];
+          rn[ks] = r[d] - alpha * y[d];
+          r[d] = rn[ks];
+        }
+      }
+    }
+    d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) {
+      const int k = lk + 4 * ks, kk = k < 10 ? k : 9, ii = li < 10 ? li : 9;
+      const int a = ii < kk ? ii : kk, b = ii < kk ? kk : ii;          // packed upper triangle: entry (a, b), a <= b
+      const double dv = dinv[wave][a * (21 - a) / 2 + b - a];
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64((li < 10 && k < 10) ? dv : 0.0, rn[ks], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) {
+      const int i = lk + 4 * ks;
+      if (i < 10 && col) {
+        z[((long)s * t.n + e * 10 + i) * 16 + li] = acc[ks];
+        sum[0] += rn[ks] * acc[ks];
+        sum[1] += rn[ks] * rn[ks];
+        for (int k = 0; k < nc; ++k) sum[2 + k] += rn[ks] * Phi[(e * 10 + i) * 4 + k];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double v = sum[j];
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    if (lk == 0) red[wave][j][li] = v;
+  }
+  __syncthreads();
+  if (tid < 96) {
+    const int j = tid >> 4, c = tid & 15;
+    const double v = (red[0][j][c] + red[1][j][c]) + (red[2][j][c] + red[3][j][c]);
+    const long blkid = (long)s * gridDim.x + bx;
+    if (j == 0) prz[blkid * 16 + c] = v;
+    else if (j == 1) prr[blkid * 16 + c] = v;
+    else if (j - 2 < nc) pr0[(blkid * 4 + (j - 2)) * 16 + c] = v;
+  }
+}
+
+// r0 [S nc][16] from the workgroups' restriction sums (fixed order)
+__global__ __launch_bounds__(256) void k3fb_coarse_r0(int S, int nbx, int nc, const double* __restrict__ pr0, double* __restrict__ r0) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)S * nc * 16) return;
+  const int c = (int)(idx & 15), m = (int)(idx >> 4), s = m / nc, k = m - s * nc;
+  double v = 0.0;
+  for (int bx = 0; bx < nbx; ++bx) v += pr0[(((long)s * nbx + bx) * 4 + k) * 16 + c];
+  r0[idx] = v;
+}
+
+// y0 = A1inv r0 for 16 columns, one wave per row (k3f_coarse_apply widened): lane (column li, every fourth entry of the row from
+// lk on); prc [M][16] = the row's part of r0 . y0
+__global__ __launch_bounds__(256) void k3fb_coarse_apply(int M, const double* __restrict__ A1inv, const double* __restrict__ r0,
+                                                         double* __restrict__ y0, double* __restrict__ prc) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
+  if (row >= M) return;
+  const double* a = A1inv + (long)row * M;
+  double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
+  int c = lk;
+  for (; c + 12 < M; c += 16) {
+    v0 += a[c] * r0[(long)c * 16 + li];
+    v1 += a[c + 4] * r0[(long)(c + 4) * 16 + li];
+    v2 += a[c + 8] * r0[(long)(c + 8) * 16 + li];
+    v3 += a[c + 12] * r0[(long)(c + 12) * 16 + li];
+  }
+  for (; c < M; c += 4) v0 += a[c] * r0[(long)c * 16 + li];
+  double v = (v0 + v1) + (v2 + v3);
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  if (lk == 0) {
+    y0[(long)row * 16 + li] = v;
+    prc[(long)row * 16 + li] = v * r0[(long)row * 16 + li];
+  }
+}
+
+// out [16]: column blockIdx.x = the sum over the rows of part [np][16] and of part2 [np2][16] (fixed order)
+__global__ __launch_bounds__(256) void k3fb_scalars(const double* __restrict__ part, long np, const double* __restrict__ part2, long np2,
+                                                    double* __restrict__ out) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x, c = blockIdx.x;
+  double a = 0.0, a2 = 0.0;
+#pragma unroll 4
+  for (long k = tid; k < np; k += 256) a += part[k * 16 + c];          // (unrolled: the loads of four rounds are in flight together)
+#pragma unroll 4
+  for (long k = tid; k < np2; k += 256) a2 += part2[k * 16 + c];
+  red[tid] = a + a2;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) out[c] = red[0];
+}
+
+// work of lrbms3_fom_solve_batch: the single solver's layout (the operator at the mean theta, the inverse blocks, the coarse
+// matrices) followed by the panel's own buffers
+struct FomBatch3 {
+  double *r, *z, *p, *y;               // [S n][16]
+  double *ppy, *prz, *prr, *pr0;       // [nblk][16] each, pr0 [nblk][4][16]
+  double *r0, *y0, *prc;               // [Mmax][16]
+  double* scal;                        // [5][16]
+  static long extra(const T3& t) {
+    const long S = t.S, nblk = S * ((t.nT + FOM_EPB - 1) / FOM_EPB), M = std::min<long>(4 * S, FOM_MAX_COARSE);
+    return 4 * S * t.n * 16 + 7 * nblk * 16 + 3 * M * 16 + 80;
+  }
+  void carve(const T3& t, const FomWork& w, double* at) {
+    const long tot = (long)t.S * t.n * 16;
+    r = at;
+    z = r + tot;
+    p = z + tot;
+    y = p + tot;
+    ppy = y + tot;
+    prz = ppy + w.nblk * 16;
+    prr = prz + w.nblk * 16;
+    pr0 = prr + w.nblk * 16;
+    r0 = pr0 + 4 * w.nblk * 16;
+    y0 = r0 + w.Mmax * 16;
+    prc = y0 + w.Mmax * 16;
+    scal = prc + w.Mmax * 16;
+  }
+};
+
+// PCG on the panel of P <= 16 columns m0 .. m0 + P - 1 of the call; the host reads r.r per column every 16 iterations (fom_cg)
+// and stops when the worst column with a nonzero right-hand side is at or below rtol relative to |b_m|.
+int fomb3_panel(lrbms3_ctx* ctx, hipStream_t st, const FomWork& w, const FomBatch3& b, int Q, int P, int nmu, int m0, const TB& th,
+                const double* A_diag, const double* A_cpl, int K, const double* phi, const double* b_K, int nc, const double* A1inv,
+                double* X, double rtol, int max_iter, int* its, double* rel_out) {
+  const T3& t = ctx->t;
+  const long S = t.S, total = S * t.n, nblk = w.nblk, M = (long)nc * S;
+  const int nbx = w.nbx;
+  const double* Phi = ctx->fom_phi;
+  const dim3 grid(nbx, S);
+  const unsigned gv = (unsigned)((total * 16 + 255) / 256);
+  auto tail = [&](double* rz) {                      // coarse step and r.z per column for the residual k3fb_update has just written
+    if (nc > 0) {
+      hipLaunchKernelGGL(k3fb_coarse_r0, dim3((unsigned)((M * 16 + 255) / 256)), dim3(256), 0, st, (int)S, nbx, nc, b.pr0, b.r0);
+      hipLaunchKernelGGL(k3fb_coarse_apply, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (int)M, A1inv, b.r0, b.y0, b.prc);
+    }
+    hipLaunchKernelGGL(k3fb_scalars, dim3(16), dim3(256), 0, st, b.prz, nblk, b.prc, nc > 0 ? M : 0L, rz);
+  };
+  hipLaunchKernelGGL(k3fb_rhs, dim3(gv), dim3(256), 0, st, total, K, P, nmu, m0, phi, b_K, b.r, X);
+  hipLaunchKernelGGL(k3fb_update, grid, dim3(256), 0, st, t, P, nmu, m0, 1, 0, b.scal, w.Dinv, b.p, b.y, X, b.r, b.z, b.prz, b.prr, nc,
+                     Phi, b.pr0);
+  tail(b.scal);
+  hipLaunchKernelGGL(k3fb_scalars, dim3(16), dim3(256), 0, st, b.prr, nblk, (const double*)nullptr, 0L, b.scal + 64);
+  LRBMS_LAUNCH_CHECK(ctx);
+  double bb[16], rr[16];
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(bb, b.scal + 64, sizeof(bb), hipMemcpyDeviceToHost, st));
+  LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  auto worst = [&](const double* cur) {
+    double wr = 0.0;
+    for (int c = 0; c < P; ++c)
+      if (bb[c] != 0.0) {
+        const double rel = sqrt(cur[c] / bb[c]);
+        if (!(rel == rel)) return rel;
+        if (rel > wr) wr = rel;
+      }
+    return wr;
+  };
+  *its = 0;
+  *rel_out = 0.0;
+  double rel = worst(bb);                            // 1, or 0 if every right-hand side of the panel is zero
+  if (rel == 0.0) return LRBMS_OK;
+  if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve_batch: NaN right-hand side");
+  int it = 0;
+  const int check = 16;
+  while (it < max_iter) {
+    for (int k = 0; k < check && it < max_iter; ++k, ++it) {
+      const int cur = it & 1;                        // slot of the current r.z (the update of this iteration writes the other one)
+      hipLaunchKernelGGL(k3fb_dir, dim3((unsigned)((t.n * 16 + 255) / 256), (unsigned)S), dim3(256), 0, st, P, it == 0 ? 1 : 0, cur, b.scal,
+                         b.z, b.p, t.n, nc, Phi, b.y0);
+      hipLaunchKernelGGL(k3fb_matvec, dim3(xcd_grid(nbx, (int)S)), dim3(256), 0, st, t, nbx, Q, P, th, A_diag, A_cpl, b.p, b.y, b.ppy);
+      hipLaunchKernelGGL(k3fb_scalars, dim3(16), dim3(256), 0, st, b.ppy, nblk, (const double*)nullptr, 0L, b.scal + 32);
+      hipLaunchKernelGGL(k3fb_update, grid, dim3(256), 0, st, t, P, nmu, m0, 0, cur, b.scal, w.Dinv, b.p, b.y, X, b.r, b.z, b.prz, b.prr,
+                         nc, Phi, b.pr0);
+      tail(b.scal + (cur ^ 1) * 16);
+    }
+    hipLaunchKernelGGL(k3fb_scalars, dim3(16), dim3(256), 0, st, b.prr, nblk, (const double*)nullptr, 0L, b.scal + 48);
+    LRBMS_LAUNCH_CHECK(ctx);
+    LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(rr, b.scal + 48, sizeof(rr), hipMemcpyDeviceToHost, st));
+    LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    rel = worst(rr);
+    if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve_batch: NaN residual");
+    if (rel <= rtol) break;
+  }
+  *its = it;
+  *rel_out = rel;
+  return LRBMS_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t lrbms3_fom_solve_batch_work_size(lrbms3_ctx* ctx, int32_t nmu) {
+  if (!ctx || !ctx->has_mesh || nmu < 1 || nmu > 64) return -1;
+  return lrbms3_fom_solve_work_size(ctx) + FomBatch3::extra(ctx->t);
+}
+
+int lrbms3_fom_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t nmu, const double* theta, const double* A_diag, const double* A_cpl,
+                           int32_t K, const double* phi, const double* b_K, double* work, double* X, double rtol, int32_t max_iter,
+                           double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_solve_batch: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || nmu < 1 || nmu > 64 || K < 1 || K > 64 || max_iter < 1 || !(rtol > 0.0))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_solve_batch: bad Q / nmu / K / max_iter / rtol");
+  if (!theta || !A_diag || !A_cpl || !phi || !b_K || !work || !X) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_solve_batch: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100;
+  FomWork w = fom_work(t, work);
+  FomBatch3 b;
+  b.carve(t, w, work + lrbms3_fom_solve_work_size(ctx));
+  // one preconditioner per call, both levels at the mean theta of its columns (summed in column order)
+  QV tb{};
+  for (int q = 0; q < Q; ++q) {
+    double acc = 0.0;
+    for (int m = 0; m < nmu; ++m) acc += theta[(long)m * Q + q];
+    tb.v[q] = acc / nmu;
+  }
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, nd, Q, tb, A_diag, w.Amu);
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((ncp + 255) / 256)), dim3(256), 0, st, ncp, Q, tb, A_cpl, w.Cmu);
+  hipLaunchKernelGGL(k3f_block_inverse, dim3((t.nT + 63) / 64, S), dim3(64), 0, st, t, w.Amu, w.Dinv);
+  int nc = 0;
+  const double* A1inv = nullptr;
+  if (int rc = fom_coarse(ctx, st, w, false, nc, A1inv)) return rc;
+  int its_max = 0;
+  double worst = 0.0;
+  bool missed = false;
+  for (int i = 0; i < 8; ++i) ctx->fomb_panels[i] = 0.0;
+  for (int m0 = 0; m0 < nmu; m0 += 16) {
+    const int P = nmu - m0 < 16 ? nmu - m0 : 16;
+    TB th;
+    for (int c = 0; c < 16; ++c)
+      for (int q = 0; q < 8; ++q) th.v[c][q] = (c < P && q < Q) ? theta[(long)(m0 + c) * Q + q] : 0.0;
+    int it = 0;
+    double rel = 0.0;
+    if (int rc = fomb3_panel(ctx, st, w, b, Q, P, nmu, m0, th, A_diag, A_cpl, K, phi, b_K, nc, A1inv, X, rtol, max_iter, &it, &rel))
+      return rc;
+    ctx->fomb_panels[m0 / 16 * 2] = it;
+    ctx->fomb_panels[m0 / 16 * 2 + 1] = rel;
+    if (it > its_max) its_max = it;
+    if (rel > worst) worst = rel;
+    if (rel > rtol) missed = true;
+  }
+  if (info) info[0] = its_max, info[1] = worst;
+  if (missed) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve_batch: CG did not reach rtol");
+  return LRBMS_OK;
+}
+
+int lrbms3_fom_solve_batch_panel_info(lrbms3_ctx* ctx, double* out) {
+  if (!ctx || !out) return LRBMS_E_INVALID;
+  for (int i = 0; i < 8; ++i) out[i] = ctx->fomb_panels[i];
+  return LRBMS_OK;
+}
 
 int lrbms3_fom_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, const double* A_diag, const double* A_cpl, const double* b,
                      double* work, double* x, double rtol, int32_t max_iter, double* info, void* stream) {
