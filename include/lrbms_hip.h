@@ -487,6 +487,28 @@ int lrbms_fom_implicit_euler(lrbms_ctx* ctx, int32_t Q, const double* theta, dou
                              const double* A_cpl, const double* b, double* work, double* U, double rtol, int32_t max_iter,
                              double* info, void* stream);
 
+/* Batched full-order trajectories: nmu <= 64 parameters in one call.  Column m runs
+ *   (M + dt A(theta_m)) u_{k+1} = M u_k + dt sum_j phi[m][k+1][j] b_K[j],  k = 0 .. nt-1  (K = 1, phi = 1, b_K = b: the plain source)
+ * in panels of at most 16 columns, panels outermost: a panel runs its whole trajectory, then the next one starts.  Every step
+ * is a warm-started CG (x = u_k) with the panel kernels of lrbms_fom_solve_batch on the step operator.  Preconditioner: per
+ * column the inverse 3x3 diagonal element blocks of M + dt A(theta_m); one coarse level per call, R0 (M + dt A(theta_bar)) R0^T
+ * at the mean theta of the call's columns (coarse option, S range and fallback of lrbms_fom_solve_batch).
+ *   theta [nmu][Q] host; phi [nmu][nt+1][K] DEVICE (row k: the time of step k); b_K [K][S][n]; U [nt+1][S][n][nmu] (parameter
+ *   fastest): slab 0 is input (the initial values per column), slabs 1..nt are written; work:
+ *   lrbms_fom_implicit_euler_batch_work_size doubles (-1 for nmu outside 1..64).  1 <= K <= 64, 1 <= Q <= 8, nt >= 1, S_ext == S.
+ *   A step of a panel iterates until its worst column is at or below rtol relative to |M u_k + dt sum_j phi b_j| of that column;
+ *   a column whose step right-hand side is exactly zero has no say and keeps u_{k+1} = u_k.  max_iter caps one step of one
+ *   panel; after a miss that panel stops at that step (its later slabs are not written), the other panels still run and the
+ *   call returns LRBMS_E_NOT_CONVERGED.  info (host, may be NULL): CG iterations summed over panels and steps, worst final
+ *   ratio.  No atomics: repeat calls give the same bits.
+ *   lrbms_fom_implicit_euler_batch_panel_info: out [4][2] host = (iterations summed over the steps, worst ratio) of every panel
+ *   of the last call on this context (zeros for panels it did not have). */
+int64_t lrbms_fom_implicit_euler_batch_work_size(lrbms_ctx* ctx, int32_t nmu);
+int lrbms_fom_implicit_euler_batch(lrbms_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta, double dt, int32_t nt,
+                                   const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                   double* U, double rtol, int32_t max_iter, double* info, void* stream);
+int lrbms_fom_implicit_euler_batch_panel_info(lrbms_ctx* ctx, double* out);
+
 /* d.l2_product.apply_inverse(Y).pairwise_dot(Y) per subdomain (time-stepping residual of ParabolicEstimator.estimate,
  * estimators.py:146-148; r_l2_i of discretize_parabolic_block_swipdg.py:72-74 applied to M^-1 Y):
  *   Y [S][n][L];  out [S][L] = y^T M_s^-1 y  (the P1 mass matrix is inverted element by element in closed form). */

@@ -80,6 +80,10 @@ SIGNATURES = {
     'lrbms_fom_solve_batch_panel_info': (ctypes.c_int, [c_vp, _P_DBL]),
     'lrbms_fom_implicit_euler': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL,
                                                 c_vp]),
+    'lrbms_fom_implicit_euler_batch_work_size': (c_i64, [c_vp, c_i32]),
+    'lrbms_fom_implicit_euler_batch': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                      c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms_fom_implicit_euler_batch_panel_info': (ctypes.c_int, [c_vp, _P_DBL]),
     'lrbms_mass_inverse_norm2': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms_div_apply': (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'lrbms_div_pairing': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp]),
@@ -746,6 +750,37 @@ class NativeContext(ContextBase):
                                                self._stream())
         self._check(rc, 'lrbms_fom_implicit_euler')
         return U, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
+
+    def fom_implicit_euler_batch(self, thetas, dt, nt, A_diag, A_cpl, b_K, phi, U0=None, rtol=1e-12, max_iter=100000):
+        """Column m: (M + dt A(thetas[m])) u_{k+1} = M u_k + dt sum_j phi[m, k + 1, j] b_K[j], nt steps, for nmu <= 64 parameters in
+        one call (panels of 16 columns, one coarse level at the mean theta) -> (U [nt + 1, S, n, nmu], info).  thetas [nmu, Q] host;
+        phi [nmu, nt + 1, K] host or device; b_K [K, S, n]; U0 [S, n] (every column) or [S, n, nmu] (default 0)."""
+        Q, S, K, nt = A_diag.shape[0], self.S, b_K.shape[0], int(nt)
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, Q)
+        if not self.torch.is_tensor(phi):
+            phi = self.from_numpy(np.ascontiguousarray(phi, dtype=np.float64))
+        phi = phi.contiguous()
+        size = int(self.lib.lrbms_fom_implicit_euler_batch_work_size(self.handle, nmu))
+        if size < 0:
+            raise NativeError('lrbms_fom_implicit_euler_batch: nmu = {} is not in 1..64'.format(nmu))
+        work = self.empty(size)
+        U = self.zeros(nt + 1, S, self.n, nmu)
+        if U0 is not None:
+            U[0] = U0.reshape(S, self.n, -1)                     # [S, n, 1] broadcasts over the columns
+        info = np.zeros(2)
+        rc = self.lib.lrbms_fom_implicit_euler_batch(self.handle, Q, K, nmu, _dblp(th), float(dt), nt,
+                                                     self._ptr(A_diag, (Q, S, self.n_T, 4, 9), 'A_diag'),
+                                                     self._ptr(A_cpl, (Q, S, 4, self.ncf, 9), 'A_cpl'),
+                                                     self._ptr(b_K, (K, S, self.n), 'b_K'), self._ptr(phi, (nmu, nt + 1, K), 'phi'),
+                                                     c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), _dblp(info),
+                                                     self._stream())
+        panels = np.zeros(8)
+        self.lib.lrbms_fom_implicit_euler_batch_panel_info(self.handle, _dblp(panels))
+        self._check(rc, 'lrbms_fom_implicit_euler_batch')
+        return U, {'iterations': int(info[0]), 'relative_residual': float(info[1]),
+                   'panel_iterations': [int(v) for v in panels[0:2 * ((nmu + 15) // 16):2]]}
 
     def mass_inverse_norm2(self, Y):
         """Y [S, n, L] -> [S, L]: y^T M^-1 y per subdomain and column."""

@@ -31,6 +31,10 @@ int launch_fom_solve_batch(lrbms_ctx* ctx, int Q, int nmu, const double* theta, 
                            hipStream_t st);
 int launch_fom_implicit_euler(lrbms_ctx* ctx, int Q, const double* theta, double dt, int nt, const double* A_diag, const double* A_cpl,
                               const double* b, double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st);
+int64_t fom_implicit_euler_batch_work_size(lrbms_ctx* ctx, int nmu);
+int launch_fom_implicit_euler_batch(lrbms_ctx* ctx, int Q, int K, int nmu, const double* theta, double dt, int nt, const double* A_diag,
+                                    const double* A_cpl, const double* bK, const double* phi, double* work, double* U, double rtol,
+                                    int max_iter, double* info, hipStream_t st);
 int launch_mass_inverse_norm2(lrbms_ctx* ctx, int C, const double* Y, double* out, hipStream_t st);
 int launch_div_apply(lrbms_ctx* ctx, int C, int mode, const double* Rt, double* out, hipStream_t st);
 int launch_div_pairing(lrbms_ctx* ctx, int Q, int L, const double* theta, const double* D, const double* G, double* out, hipStream_t st);
@@ -715,6 +719,27 @@ int lrbms_fom_implicit_euler(lrbms_ctx* ctx, int32_t Q, const double* theta, dou
   LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, 1); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, A_diag); CHECK_PTR(ctx, A_cpl);
   CHECK_PTR(ctx, b); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
   return launch_fom_implicit_euler(ctx, Q, theta, dt, nt, A_diag, A_cpl, b, work, U, rtol, max_iter, info, (hipStream_t)stream);
+}
+
+int64_t lrbms_fom_implicit_euler_batch_work_size(lrbms_ctx* ctx, int32_t nmu) {
+  if (!ctx || !ctx->has_mesh) return -1;
+  return fom_implicit_euler_batch_work_size(ctx, nmu);
+}
+
+int lrbms_fom_implicit_euler_batch(lrbms_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta, double dt, int32_t nt,
+                                   const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                   double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, 1); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, A_diag); CHECK_PTR(ctx, A_cpl);
+  CHECK_PTR(ctx, b_K); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
+  return launch_fom_implicit_euler_batch(ctx, Q, K, nmu, theta, dt, nt, A_diag, A_cpl, b_K, phi, work, U, rtol, max_iter, info,
+                                         (hipStream_t)stream);
+}
+
+int lrbms_fom_implicit_euler_batch_panel_info(lrbms_ctx* ctx, double* out) {
+  if (!ctx) return LRBMS_E_INVALID;
+  CHECK_PTR(ctx, out);
+  for (int i = 0; i < 8; ++i) out[i] = ctx->fombe_panels[i];
+  return LRBMS_OK;
 }
 
 int lrbms_mass_inverse_norm2(lrbms_ctx* ctx, int32_t L, const double* Y, double* out, void* stream) {

@@ -16,6 +16,10 @@
 // Batched snapshots (lrbms_fom_solve_batch): up to 64 parameters per call in panels of 16 columns.
 // The panel kernels k_fomb_* further down read the Q uncombined blocks once per iteration for all 16 columns and weight
 // them per lane with the column's own theta; the kernels above are untouched by it.
+//
+// Batched trajectories (lrbms_fom_implicit_euler_batch): the same panels on the step operator
+// M + dt A(theta_m) of the implicit Euler (the _mass instantiations of the two panel kernels), every step of a panel a
+// warm-started PCG relative to the step's full right-hand side.
 #include <type_traits>
 #include "lrbms_dev.h"
 
@@ -656,13 +660,15 @@ __global__ __launch_bounds__(256) void k_fomb_rhs(long nv, int K, int P, int nmu
 // the three face neighbours').  The 16 lanes of a block share the loads of the Q uncombined blocks and weight them with
 // their own theta; the three row sums meet by two butterflies across the blocks.  rz_new / rz_old [16]: r.z per column
 // (k_fomb_scalars).  partial [gridDim.x][16] = p . y over the workgroup's elements.
-__global__ __launch_bounds__(1024) void k_fomb_matvec(Tmpl t, int S, int Q, int P, ThetaP th, const int* __restrict__ nbr,
-                                                      const double* __restrict__ A_diag, const double* __restrict__ A_cpl,
-                                                      const double* __restrict__ z, const double* __restrict__ p_old,
-                                                      const double* __restrict__ rz_new, const double* __restrict__ rz_old, int first,
-                                                      const double* __restrict__ c0, double* __restrict__ p_new,
-                                                      double* __restrict__ y, double* __restrict__ partial) {
-  __shared__ double red[256];
+// MASS: the step operator of the implicit Euler, M + A(theta) with theta pre-multiplied by dt: the P1 mass |T|/12 (1 + delta_ij)
+// (the expression of k_fom_combine) joins the element's own 3x3 block on the b == 0 lanes.
+template <bool MASS>
+__device__ __forceinline__ void fomb_matvec_body(const Tmpl& t, int S, int Q, int P, const ThetaP& th, const int* __restrict__ nbr,
+                                                 const double* __restrict__ A_diag, const double* __restrict__ A_cpl,
+                                                 const double* __restrict__ z, const double* __restrict__ p_old,
+                                                 const double* __restrict__ rz_new, const double* __restrict__ rz_old, int first,
+                                                 const double* __restrict__ c0, double* __restrict__ p_new,
+                                                 double* __restrict__ y, double* __restrict__ partial, double* red) {
   const long ne = (long)S * t.nT, nd = ne * 36, nc = (long)S * 4 * t.ncf * 9;
   const int lane = threadIdx.x & 63, c = lane & 15, b = lane >> 4, wave = threadIdx.x >> 6;
   const bool on = c < P;
@@ -703,6 +709,11 @@ __global__ __launch_bounds__(1024) void k_fomb_matvec(Tmpl t, int S, int Q, int 
 #pragma unroll
           for (int k = 0; k < 9; ++k) blk[k] += thq[q] * bp[q * qs + k];
         }
+      if (MASS && b == 0) {
+        const double ma = t.area[e];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) blk[k] += ma / 12.0 * (k % 4 == 0 ? 2.0 : 1.0);
+      }
       const long g = ((long)s2 * t.nT + e2) * 3;
       const double cz = c0 ? c0[(long)s2 * 16 + c] : 0.0;          // coarse part of the preconditioned residual (constant per subdomain)
 #pragma unroll
@@ -731,16 +742,39 @@ __global__ __launch_bounds__(1024) void k_fomb_matvec(Tmpl t, int S, int Q, int 
   fomb_store_partial(dot, red, partial);
 }
 
+__global__ __launch_bounds__(1024) void k_fomb_matvec(Tmpl t, int S, int Q, int P, ThetaP th, const int* __restrict__ nbr,
+                                                      const double* __restrict__ A_diag, const double* __restrict__ A_cpl,
+                                                      const double* __restrict__ z, const double* __restrict__ p_old,
+                                                      const double* __restrict__ rz_new, const double* __restrict__ rz_old, int first,
+                                                      const double* __restrict__ c0, double* __restrict__ p_new,
+                                                      double* __restrict__ y, double* __restrict__ partial) {
+  __shared__ double red[256];
+  fomb_matvec_body<false>(t, S, Q, P, th, nbr, A_diag, A_cpl, z, p_old, rz_new, rz_old, first, c0, p_new, y, partial, red);
+}
+
+// the same on M + A(theta) (lrbms_fom_implicit_euler_batch)
+__global__ __launch_bounds__(1024) void k_fomb_matvec_mass(Tmpl t, int S, int Q, int P, ThetaP th, const int* __restrict__ nbr,
+                                                           const double* __restrict__ A_diag, const double* __restrict__ A_cpl,
+                                                           const double* __restrict__ z, const double* __restrict__ p_old,
+                                                           const double* __restrict__ rz_new, const double* __restrict__ rz_old,
+                                                           int first, const double* __restrict__ c0, double* __restrict__ p_new,
+                                                           double* __restrict__ y, double* __restrict__ partial) {
+  __shared__ double red[256];
+  fomb_matvec_body<true>(t, S, Q, P, th, nbr, A_diag, A_cpl, z, p_old, rz_new, rz_old, first, c0, p_new, y, partial, red);
+}
+
 // lane = (column c = lane & 15, element lane >> 4 of the wave's four).  alpha = rz / pAp per column (rz [16] from
 // k_fomb_scalars, pAp re-summed from ppap [npap][16]); the diagonal 3x3 block of A(theta_c) is combined from the Q diagonal
 // blocks and inverted on the spot (the expressions of k_fom_combine).  first: only z and the partials of the start residual.
 // x is column m0 + c of X [S n][nmu].  prz_out / prr [gridDim.x][16].
-__global__ __launch_bounds__(1024) void k_fomb_update(long ne, int Q, int P, int nmu, int m0, ThetaP th, const double* __restrict__ A_diag,
-                                                      const double* __restrict__ rz_in, const double* __restrict__ ppap, int npap,
-                                                      int first, double* __restrict__ X, double* __restrict__ r,
-                                                      const double* __restrict__ p, const double* __restrict__ y,
-                                                      double* __restrict__ z, double* __restrict__ prz_out, double* __restrict__ prr) {
-  __shared__ double red[1024];
+// MASS: the mass (area [nT]: the template's element areas) joins the diagonal block before the inverse.
+template <bool MASS>
+__device__ __forceinline__ void fomb_update_body(long ne, int Q, int P, int nmu, int m0, const ThetaP& th, const double* __restrict__ A_diag,
+                                                 const double* __restrict__ rz_in, const double* __restrict__ ppap, int npap,
+                                                 int first, double* __restrict__ X, double* __restrict__ r,
+                                                 const double* __restrict__ p, const double* __restrict__ y,
+                                                 double* __restrict__ z, double* __restrict__ prz_out, double* __restrict__ prr,
+                                                 const double* __restrict__ area, int nT, double* red) {
   const long nd = ne * 36;
   const int lane = threadIdx.x & 63, c = lane & 15, sub = lane >> 4, wave = threadIdx.x >> 6;
   const bool on = c < P;
@@ -766,6 +800,11 @@ __global__ __launch_bounds__(1024) void k_fomb_update(long ne, int Q, int P, int
 #pragma unroll
           for (int k = 0; k < 9; ++k) a[k] += thq[q] * A_diag[q * nd + idx * 36 + k];
         }
+      if (MASS) {
+        const double ma = area[(unsigned)idx % (unsigned)nT];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) a[k] += ma / 12.0 * (k % 4 == 0 ? 2.0 : 1.0);
+      }
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         const long g = (idx * 3 + i) * 16 + c;
@@ -811,6 +850,86 @@ __global__ __launch_bounds__(1024) void k_fomb_update(long ne, int Q, int P, int
   rr += __shfl_xor(rr, 32, 64);
   fomb_store_partial(rz, red, prz_out);
   fomb_store_partial(rr, red, prr);
+}
+
+__global__ __launch_bounds__(1024) void k_fomb_update(long ne, int Q, int P, int nmu, int m0, ThetaP th, const double* __restrict__ A_diag,
+                                                      const double* __restrict__ rz_in, const double* __restrict__ ppap, int npap,
+                                                      int first, double* __restrict__ X, double* __restrict__ r,
+                                                      const double* __restrict__ p, const double* __restrict__ y,
+                                                      double* __restrict__ z, double* __restrict__ prz_out, double* __restrict__ prr) {
+  __shared__ double red[1024];
+  fomb_update_body<false>(ne, Q, P, nmu, m0, th, A_diag, rz_in, ppap, npap, first, X, r, p, y, z, prz_out, prr, nullptr, 1, red);
+}
+
+// the same with the inverse diagonal blocks of M + A(theta) (lrbms_fom_implicit_euler_batch)
+__global__ __launch_bounds__(1024) void k_fomb_update_mass(long ne, int Q, int P, int nmu, int m0, ThetaP th,
+                                                           const double* __restrict__ A_diag, const double* __restrict__ rz_in,
+                                                           const double* __restrict__ ppap, int npap, int first, double* __restrict__ X,
+                                                           double* __restrict__ r, const double* __restrict__ p,
+                                                           const double* __restrict__ y, double* __restrict__ z,
+                                                           double* __restrict__ prz_out, double* __restrict__ prr,
+                                                           const double* __restrict__ area, int nT) {
+  __shared__ double red[1024];
+  fomb_update_body<true>(ne, Q, P, nmu, m0, th, A_diag, rz_in, ppap, npap, first, X, r, p, y, z, prz_out, prr, area, nT, red);
+}
+
+// Implicit Euler step of a panel (lrbms_fom_implicit_euler_batch), warm start x = u_k: the columns m0 .. m0 + P - 1 of the slab
+// Uk [S n][nmu] -> the panel vector uk [S n][16] (columns c >= P zero) and the same columns of the next slab X.
+__global__ __launch_bounds__(256) void k_fomb_load(long nv, int P, int nmu, int m0, const double* __restrict__ Uk, double* __restrict__ X,
+                                                   double* __restrict__ uk) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv * 16; i += (long)gridDim.x * blockDim.x) {
+    const long g = i >> 4;
+    const int c = (int)(i & 15);
+    double v = 0.0;
+    if (c < P) {
+      v = Uk[g * nmu + m0 + c];
+      X[g * nmu + m0 + c] = v;
+    }
+    uk[i] = v;
+  }
+}
+
+// r = M u_k + dt sum_j phi_c[j] b_j - y per column (y = (M + dt A(theta_c)) u_k from k_fomb_matvec_mass with first = 1), the
+// arithmetic of k_fom_step_residual_src; columns c >= P of r zero.  phi: the table [nmu][rows][K] offset to the step's row, so
+// column c reads phi + (m0 + c) rows K.  Lanes as in k_fomb_update; partial [gridDim.x][16] = |M u_k + dt sum_j phi b_j|^2.
+__global__ __launch_bounds__(1024) void k_fomb_step_residual(Tmpl t, long ne, double dt, int K, int P, int m0, long phi_stride,
+                                                             const double* __restrict__ phi, const double* __restrict__ bK,
+                                                             const double* __restrict__ uk, const double* __restrict__ y,
+                                                             double* __restrict__ r, double* __restrict__ partial) {
+  __shared__ double red[256];
+  const long nv = ne * 3;
+  const int lane = threadIdx.x & 63, c = lane & 15, sub = lane >> 4, wave = threadIdx.x >> 6;
+  const bool on = c < P;
+  const double* ph = phi + (long)(m0 + (on ? c : 0)) * phi_stride;
+  double acc = 0.0;
+  for (long e0 = ((long)blockIdx.x * 16 + wave) * 4; e0 < ne; e0 += (long)gridDim.x * 64) {
+    const long idx = e0 + sub;
+    if (idx >= ne) continue;
+    if (!on) {
+      for (int i = 0; i < 3; ++i) r[(idx * 3 + i) * 16 + c] = 0.0;
+      continue;
+    }
+    const double m = t.area[(unsigned)idx % (unsigned)t.nT] / 12.0;
+    const double u0 = uk[(idx * 3) * 16 + c], u1 = uk[(idx * 3 + 1) * 16 + c], u2 = uk[(idx * 3 + 2) * 16 + c];
+    const double sum = u0 + u1 + u2;
+    const double uv[3] = {u0, u1, u2};
+    double bk[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < K; ++j) {
+      const double pj = ph[j];
+      const double* bj = bK + (long)j * nv + idx * 3;
+      for (int i = 0; i < 3; ++i) bk[i] += pj * bj[i];
+    }
+    for (int i = 0; i < 3; ++i) {
+      // the spelled-out contraction of k_fom_step_residual_src
+      const double dtb = dt * bk[i];
+      const double rhs = __fma_rn(m, sum + uv[i], dtb);
+      r[(idx * 3 + i) * 16 + c] = rhs - y[(idx * 3 + i) * 16 + c];
+      acc += rhs * rhs;
+    }
+  }
+  acc += __shfl_xor(acc, 16, 64);
+  acc += __shfl_xor(acc, 32, 64);
+  fomb_store_partial(acc, red, partial);
 }
 
 // r0 [S][16] = sum of the residual over subdomain s per column (restriction to the coarse space); zeroes the coarse solution
@@ -897,9 +1016,9 @@ struct FomB {
   }
 };
 
-// r.r per column from the update kernel's partials (host sum, fixed order)
-int fomb_host_rr(lrbms_ctx* ctx, const FomB& b, std::vector<double>& host, double* rr, hipStream_t st) {
-  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host.data(), b.prr, sizeof(double) * (size_t)b.gu * 16, hipMemcpyDeviceToHost, st));
+// the sum per column of the partials part [b.gu][16] (r.r of the update kernel: b.prr), on the host in a fixed order
+int fomb_host_rr(lrbms_ctx* ctx, const FomB& b, const double* part, std::vector<double>& host, double* rr, hipStream_t st) {
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(host.data(), part, sizeof(double) * (size_t)b.gu * 16, hipMemcpyDeviceToHost, st));
   LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
   for (int c = 0; c < 16; ++c) {
     double acc = 0.0;
@@ -922,20 +1041,54 @@ int fomb_precond_tail(lrbms_ctx* ctx, FomB& b, double* rz_out, hipStream_t st) {
   return LRBMS_OK;
 }
 
-// PCG on one panel of P <= 16 columns (columns m0 .. m0 + P - 1 of the call): iterates until the worst column with a
-// nonzero right-hand side is at or below rtol (relative to |b_m|); the host checks follow fom_cg_run.
-int fomb_panel_run(lrbms_ctx* ctx, FomB& b, int Q, int P, int nmu, int m0, const ThetaP& th, const double* A_diag, const double* A_cpl,
-                   double* X, double rtol, int max_iter, int* its, double* rel_out, hipStream_t st) {
-  const Tmpl& t = ctx->t;
-  const int S = ctx->S;
+// The panel's operator: the elliptic one, or (mass) the step operator M + A(theta) with theta pre-multiplied by dt
+struct FombOp {
+  int Q, P, nmu, m0;
+  ThetaP th;
+  const double *A_diag, *A_cpl;
+  bool mass;
+};
+
+void fomb_launch_matvec(lrbms_ctx* ctx, FomB& b, const FombOp& op, const double* z, const double* p_old, const double* rz_new,
+                        const double* rz_old, int first, const double* c0, double* p_new, hipStream_t st) {
+  if (op.mass)
+    hipLaunchKernelGGL(k_fomb_matvec_mass, dim3(b.gm), dim3(FOMB_THREADS), 0, st, ctx->t, ctx->S, op.Q, op.P, op.th, ctx->nbr, op.A_diag,
+                       op.A_cpl, z, p_old, rz_new, rz_old, first, c0, p_new, b.y, b.ppap);
+  else
+    hipLaunchKernelGGL(k_fomb_matvec, dim3(b.gm), dim3(FOMB_THREADS), 0, st, ctx->t, ctx->S, op.Q, op.P, op.th, ctx->nbr, op.A_diag,
+                       op.A_cpl, z, p_old, rz_new, rz_old, first, c0, p_new, b.y, b.ppap);
+}
+
+void fomb_launch_update(lrbms_ctx* ctx, FomB& b, const FombOp& op, const double* rz_in, int first, double* X, const double* p,
+                        hipStream_t st) {
+  if (op.mass)
+    hipLaunchKernelGGL(k_fomb_update_mass, dim3(b.gu), dim3(FOMB_THREADS), 0, st, b.ne, op.Q, op.P, op.nmu, op.m0, op.th, op.A_diag, rz_in,
+                       b.ppap, b.gm, first, X, b.r, p, b.y, b.z, b.prz, b.prr, ctx->t.area, ctx->t.nT);
+  else
+    hipLaunchKernelGGL(k_fomb_update, dim3(b.gu), dim3(FOMB_THREADS), 0, st, b.ne, op.Q, op.P, op.nmu, op.m0, op.th, op.A_diag, rz_in, b.ppap,
+                       b.gm, first, X, b.r, p, b.y, b.z, b.prz, b.prr);
+}
+
+// PCG on one panel of P <= 16 columns (columns m0 .. m0 + P - 1 of the call), shared by lrbms_fom_solve_batch and the steps of
+// lrbms_fom_implicit_euler_batch: on entry X holds the start values and b.r the start residual.  Iterates until the worst
+// column with a nonzero reference is at or below rtol; the host checks follow fom_cg_run.  The reference per column is |r_0|
+// (ref_part == nullptr: the right-hand side, the start value being zero) or the sum of the partials ref_part [b.gu][16] (the
+// step's full right-hand side, left by k_fomb_step_residual); `what` names the caller in the error text.
+int fomb_panel_run(lrbms_ctx* ctx, FomB& b, const FombOp& op, double* X, const double* ref_part, double rtol, int max_iter, int* its,
+                   double* rel_out, const char* what, hipStream_t st) {
+  const int P = op.P;
   const double* c0 = b.A0inv ? b.c0 : nullptr;
   std::vector<double> host((size_t)b.gu * 16);
-  hipLaunchKernelGGL(k_fomb_update, dim3(b.gu), dim3(FOMB_THREADS), 0, st, b.ne, Q, P, nmu, m0, th, A_diag, b.rz[0], b.ppap, b.gm, 1, X, b.r,
-                     b.p[0], b.y, b.z, b.prz, b.prr);
+  fomb_launch_update(ctx, b, op, b.rz[0], 1, X, b.p[0], st);
   LRBMS_LAUNCH_CHECK(ctx);
   if (int rc = fomb_precond_tail(ctx, b, b.rz[0], st)) return rc;
   double ref2[16], rr[16];
-  if (int rc = fomb_host_rr(ctx, b, host, ref2, st)) return rc;
+  if (int rc = fomb_host_rr(ctx, b, b.prr, host, rr, st)) return rc;
+  if (ref_part) {
+    if (int rc = fomb_host_rr(ctx, b, ref_part, host, ref2, st)) return rc;
+  } else {
+    for (int c = 0; c < 16; ++c) ref2[c] = rr[c];
+  }
   auto worst = [&](const double* cur) {
     double w = 0.0;
     for (int c = 0; c < P; ++c)
@@ -947,7 +1100,7 @@ int fomb_panel_run(lrbms_ctx* ctx, FomB& b, int Q, int P, int nmu, int m0, const
     return w;
   };
   *its = 0;
-  double rel = worst(ref2);                                  // 1, or 0 if every right-hand side of the panel is zero
+  double rel = worst(rr);                  // 1 from a zero start value, or 0 if every right-hand side of the panel is zero
   *rel_out = 0.0;
   if (rel == 0.0) return LRBMS_OK;
   int it = 0, block = 10;
@@ -955,16 +1108,14 @@ int fomb_panel_run(lrbms_ctx* ctx, FomB& b, int Q, int P, int nmu, int m0, const
     if (block > max_iter - it) block = max_iter - it;
     for (int k = 0; k < block; ++k, ++it) {
       const int c = it & 1, o = c ^ 1;
-      hipLaunchKernelGGL(k_fomb_matvec, dim3(b.gm), dim3(FOMB_THREADS), 0, st, t, S, Q, P, th, ctx->nbr, A_diag, A_cpl, b.z, b.p[o], b.rz[c],
-                         b.rz[o], it == 0 ? 1 : 0, c0, b.p[c], b.y, b.ppap);
-      hipLaunchKernelGGL(k_fomb_update, dim3(b.gu), dim3(FOMB_THREADS), 0, st, b.ne, Q, P, nmu, m0, th, A_diag, b.rz[c], b.ppap, b.gm, 0, X,
-                         b.r, b.p[c], b.y, b.z, b.prz, b.prr);
+      fomb_launch_matvec(ctx, b, op, b.z, b.p[o], b.rz[c], b.rz[o], it == 0 ? 1 : 0, c0, b.p[c], st);
+      fomb_launch_update(ctx, b, op, b.rz[c], 0, X, b.p[c], st);
       if (int rc = fomb_precond_tail(ctx, b, b.rz[o], st)) return rc;
     }
     LRBMS_LAUNCH_CHECK(ctx);
-    if (int rc = fomb_host_rr(ctx, b, host, rr, st)) return rc;
+    if (int rc = fomb_host_rr(ctx, b, b.prr, host, rr, st)) return rc;
     rel = worst(rr);
-    if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve_batch: NaN residual (operator not SPD?)");
+    if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, what);
     const double rate = log(rel) / it;
     block = 25;
     if (rel > rtol && rate < 0.0) {                          // aim a little short: CG converges superlinearly
@@ -1020,7 +1171,9 @@ int launch_fom_solve_batch(lrbms_ctx* ctx, int Q, int nmu, const double* theta, 
     LRBMS_LAUNCH_CHECK(ctx);
     int it = 0;
     double rel = 0.0;
-    if (int rc = fomb_panel_run(ctx, b, Q, P, nmu, m0, th, A_diag, A_cpl, X, rtol, max_iter, &it, &rel, st)) return rc;
+    const FombOp op{Q, P, nmu, m0, th, A_diag, A_cpl, false};
+    if (int rc = fomb_panel_run(ctx, b, op, X, nullptr, rtol, max_iter, &it, &rel, "fom_solve_batch: NaN residual (operator not SPD?)", st))
+      return rc;
     ctx->fomb_panels[m0 / 16 * 2] = it;
     ctx->fomb_panels[m0 / 16 * 2 + 1] = rel;
     if (it > its_max) its_max = it;
@@ -1029,6 +1182,87 @@ int launch_fom_solve_batch(lrbms_ctx* ctx, int Q, int nmu, const double* theta, 
   }
   if (info) { info[0] = its_max; info[1] = worst; }
   if (missed) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve_batch: CG did not reach rtol");
+  return LRBMS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Batched full-order trajectories (lrbms_fom_implicit_euler_batch): column m runs the implicit Euler
+//   (M + dt A(theta_m)) u_{k+1} = M u_k + dt sum_j phi[m][k+1][j] b_K[j],   k = 0 .. nt-1,
+// on U [nt+1][S][n][nmu] (parameter fastest; slab 0 is input).  Panels of <= 16 columns, panels outermost: a panel runs its
+// whole trajectory with one theta table (pre-multiplied by dt), every step a warm-started PCG of the panel kernels on the step
+// operator (k_fomb_matvec_mass / k_fomb_update_mass), relative to the step's full right-hand side per column.  Per step
+//   k_fomb_load            u_k of the panel's columns -> b.z [S n][16] and the next slab (x = u_k)
+//   k_fomb_matvec_mass     first = 1, no coarse part: y = (M + dt A(theta_c)) u_k
+//   k_fomb_step_residual   r = M u_k + dt sum_j phi b_j - y, partials of |M u_k + dt sum_j phi b_j|^2 into b.ppap
+// then fomb_panel_run (its first update kernel overwrites b.z, which the two kernels before it have consumed: no extra work).
+// One coarse level per call, A0 = R0 (M + dt A(theta_bar)) R0^T at the call mean, for all panels and steps.
+int64_t fom_implicit_euler_batch_work_size(lrbms_ctx* ctx, int nmu) {
+  if (nmu < 1 || nmu > 64) return -1;
+  return FomB::total(ctx);
+}
+
+int launch_fom_implicit_euler_batch(lrbms_ctx* ctx, int Q, int K, int nmu, const double* theta, double dt, int nt, const double* A_diag,
+                                    const double* A_cpl, const double* bK, const double* phi, double* work, double* U, double rtol,
+                                    int max_iter, double* info, hipStream_t st) {
+  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch needs all subdomains on one rank");
+  if (Q < 1 || Q > 8 || nmu < 1 || nmu > 64 || K < 1 || K > 64 || nt < 1 || max_iter < 1 || !(rtol > 0.0) || !(dt > 0.0))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch: bad Q / nmu / K / nt / dt / max_iter / rtol");
+  FomB b;
+  b.carve(ctx, work);
+  // one coarse level per call, of the step operator at the mean theta of its columns (summed in column order)
+  double* A0 = nullptr;
+  if (int rc = coarse_begin(ctx, &A0, st)) return rc;
+  if (A0) {
+    QVecF tb;
+    for (int q = 0; q < 8; ++q) {
+      double acc = 0.0;
+      for (int m = 0; q < Q && m < nmu; ++m) acc += theta[(long)m * Q + q];
+      tb.v[q] = dt * (acc / nmu);
+    }
+    hipLaunchKernelGGL(k_fom_combine, dim3(4096), dim3(256), 0, st, ctx->t, ctx->S, Q, tb, 1.0, A_diag, A_cpl, b.Amu_d, b.Amu_c, b.Minv);
+    hipLaunchKernelGGL(k_fom_coarse_entries, dim3(ctx->S), dim3(256), 0, st, ctx->t, ctx->S, ctx->nbr, b.Amu_d, b.Amu_c, A0);
+    LRBMS_LAUNCH_CHECK(ctx);
+    if (int rc = coarse_finish(ctx, &b.A0inv, st)) return rc;
+  }
+  const long slab = b.nv * nmu;
+  long its_sum = 0;
+  double worst = 0.0;
+  bool missed = false;
+  for (int i = 0; i < 8; ++i) ctx->fombe_panels[i] = 0.0;
+  for (int m0 = 0; m0 < nmu; m0 += 16) {
+    FombOp op{Q, nmu - m0 < 16 ? nmu - m0 : 16, nmu, m0, {}, A_diag, A_cpl, true};
+    for (int c = 0; c < 16; ++c)
+      for (int q = 0; q < 8; ++q) op.th.v[c][q] = (c < op.P && q < Q) ? dt * theta[(long)(m0 + c) * Q + q] : 0.0;
+    long its_p = 0;
+    double worst_p = 0.0;
+    for (int step = 0; step < nt; ++step) {
+      const double* Uk = U + step * slab;
+      double* X = U + (step + 1) * slab;
+      hipLaunchKernelGGL(k_fomb_load, dim3(2048), dim3(256), 0, st, b.nv, op.P, nmu, m0, Uk, X, b.z);
+      fomb_launch_matvec(ctx, b, op, b.z, b.p[1], b.rz[0], b.rz[1], 1, nullptr, b.p[0], st);
+      hipLaunchKernelGGL(k_fomb_step_residual, dim3(b.gu), dim3(FOMB_THREADS), 0, st, ctx->t, b.ne, dt, K, op.P, m0, (long)(nt + 1) * K,
+                         phi + (long)(step + 1) * K, bK, b.z, b.y, b.r, b.ppap);
+      LRBMS_LAUNCH_CHECK(ctx);
+      int it = 0;
+      double rel = 0.0;
+      if (int rc = fomb_panel_run(ctx, b, op, X, b.ppap, rtol, max_iter, &it, &rel, "fom_implicit_euler_batch: NaN residual (operator not SPD?)",
+                                  st))
+        return rc;
+      its_p += it;
+      const bool nan = !(rel == rel);
+      if (nan || rel > worst_p) worst_p = rel;
+      if (nan || rel > rtol) {                               // this panel stops here; its later slabs are not written
+        missed = true;
+        break;
+      }
+    }
+    ctx->fombe_panels[m0 / 16 * 2] = (double)its_p;
+    ctx->fombe_panels[m0 / 16 * 2 + 1] = worst_p;
+    its_sum += its_p;
+    if (!(worst_p == worst_p) || worst_p > worst) worst = worst_p;
+  }
+  if (info) { info[0] = (double)its_sum; info[1] = worst; }
+  if (missed) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_implicit_euler_batch: CG did not reach rtol");
   return LRBMS_OK;
 }
 

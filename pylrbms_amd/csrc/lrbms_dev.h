@@ -116,6 +116,7 @@ struct lrbms_ctx : lrbms_ctx_base {
   int opt_streams = -1, opt_f1_ksplit = 0, opt_f1_legacy = 0, opt_coarse = 1, opt_solve_valu = 0, opt_estimate_valu = 0, opt_prep_lds = 1, opt_f2_form = 0;
   double* src_phi = nullptr;         // [64][64] source coefficients of lrbms_reduced_solve_batch_src, allocated on first use
   double fomb_panels[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // lrbms_fom_solve_batch: (iterations, final ratio) of the up to four panels of the last call
+  double fombe_panels[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lrbms_fom_implicit_euler_batch: (iterations over the steps, worst ratio) per panel of the last call
   const double* user_pc = nullptr;   // prebuilt preconditioner the reduced solves use (lrbms_reduced_precond_use), caller-owned
   int user_pc_N = 0;
 };

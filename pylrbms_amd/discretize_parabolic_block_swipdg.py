@@ -12,7 +12,9 @@ with ``nt`` steps (:87).  The reference's version does not run at HEAD (SURVEY.m
 ``solve(mu)`` is ONE native call for the whole trajectory (``lrbms_fom_implicit_euler``): the theta-weighted block
 operator plus the mass is combined once, every step is a warm-started CG on it.  On a sharded discretization the solves
 run on the gathered operator, and so does the time residual of the parabolic estimate (its elliptic-reconstruction
-variant needs all subdomains on one rank).
+variant needs all subdomains on one rank).  ``solve_batch(mus)`` runs the trajectories of a training set 64 parameters per
+native call (``lrbms_fom_implicit_euler_batch``); the elliptic batch stays reachable as
+``solve_stationary_batch``.
 
 Time-dependent affine sources (the reference's artificial-channels problem, python/scripts/parabolic.py):
 ``p['f'] = {'functions': [f_0 .. f_{K-1}], 'coefficients': [phi_0 .. phi_{K-1}]}`` with coefficients that may read ``mu`` and
@@ -100,11 +102,70 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         self.last_solve_info = info
         return BlockVectorArray(U.permute(1, 2, 0), self.solution_space)
 
+    def solve_batch(self, mus, inverse_options=None, as_snapshots=False):
+        """Trajectories for a whole training set, 64 parameters per native ``lrbms_fom_implicit_euler_batch`` call (panels of 16
+        columns that share every read of the operator blocks; one coarse level per call at the mean theta).  Returns a list with,
+        per parameter, the ``BlockVectorArray`` ``[S, n, nt + 1]`` that ``solve(mu)`` returns -- views of the call's panel
+        ``[nt + 1, S, n, nmu]``, as ``rd.solve_batch`` hands out its trajectories.  ``as_snapshots=True``: one ``BlockVectorArray`` of
+        ``len(mus) * nt`` vectors instead, the steps 1 .. nt of every parameter, parameter-major: the layout
+        ``extend_basis(..., method='pod')`` takes (at most 128 vectors).  ``precision`` / ``max_iter`` as in ``solve``.
+        ``last_solve_info``: the CG iterations summed over the calls and the worst final residual ratio.  On a sharded grid it is
+        the loop of ``solve``."""
+        import torch
+        eng = self.engine
+        mus = list(mus)
+        if not mus:
+            raise ValueError('solve_batch: no parameters')
+        nt = self.time_stepper.nt
+        if as_snapshots and len(mus) * nt > 128:
+            raise ValueError('solve_batch(as_snapshots=True): {} x {} vectors, the local POD takes at most 128'.format(len(mus), nt))
+        its, rel = 0, 0.0
+        if eng.S_ext != eng.S:
+            trajs = []
+            for mu in mus:
+                trajs.append(self.solve(mu, inverse_options=inverse_options))
+                its += self.last_solve_info['iterations']
+                rel = max(rel, self.last_solve_info['relative_residual'])
+        else:
+            rtol, max_iter = self._solve_options(inverse_options)
+            theta = np.stack([self.theta(mu) for mu in mus])
+            phi = np.stack([self.source_coefficients(mu) for mu in mus])                # [len(mus), nt + 1, K]
+            b_K = self._src['b_K'] if self._src is not None else eng.b.reshape(1, eng.S, eng.t.n)
+            U0 = self.initial_data.tensor[:, :, 0] if self.initial_data is not None else None
+            trajs = []
+            for m0 in range(0, len(mus), 64):
+                U, info = eng.ctx.fom_implicit_euler_batch(theta[m0:m0 + 64], self.T / nt, nt, eng.A_diag, eng.A_cpl, b_K,
+                                                           phi[m0:m0 + 64], U0=U0, rtol=rtol, max_iter=max_iter)
+                its, rel = its + info['iterations'], max(rel, info['relative_residual'])
+                trajs += [BlockVectorArray.view_of(U[:, :, :, m].permute(1, 2, 0), self.solution_space) for m in range(U.shape[3])]
+        self.last_solve_info = {'iterations': its, 'relative_residual': rel}
+        if not as_snapshots:
+            return trajs
+        return BlockVectorArray(torch.cat([u.tensor[:, :, 1:] for u in trajs], dim=2).contiguous(), self.solution_space)
+
     def solve_stationary(self, mu, inverse_options=None):
         """The elliptic solve of the underlying discretization (the limit ``t -> oo``)."""
         if self._src is not None:
             raise NotImplementedError('solve_stationary: the source depends on time (f = sum_j phi_j(t, mu) f_j)')
         return DuneDiscretization.solve(self, mu, inverse_options=inverse_options)
+
+    def solve_stationary_batch(self, mus, inverse_options=None):
+        """The elliptic ``solve_batch`` of the underlying discretization: one array of ``len(mus)`` stationary solutions."""
+        if self._src is not None:
+            raise NotImplementedError('solve_stationary_batch: the source depends on time (f = sum_j phi_j(t, mu) f_j)')
+        if self.engine.S_ext != self.engine.S:                       # (the elliptic loop would call this class's ``solve``)
+            import torch
+            mus = list(mus)
+            if not mus:
+                raise ValueError('solve_stationary_batch: no parameters')
+            cols, its, rel = [], 0, 0.0
+            for mu in mus:
+                cols.append(self.solve_stationary(mu, inverse_options=inverse_options).tensor)
+                its = max(its, self.last_solve_info['iterations'])
+                rel = max(rel, self.last_solve_info['relative_residual'])
+            self.last_solve_info = {'iterations': its, 'relative_residual': rel}
+            return BlockVectorArray(torch.cat(cols, dim=2).contiguous(), self.solution_space)
+        return DuneDiscretization.solve_batch(self, mus, inverse_options=inverse_options)
 
     def _source_rows(self, mu, L):
         """The phi rows of the columns of an array of ``L`` vectors: the trajectory's rows if ``L == nt + 1``; otherwise None

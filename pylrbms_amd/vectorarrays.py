@@ -38,6 +38,15 @@ class BlockVectorArray:
         self._t = tensor.contiguous()
         self.space = space
 
+    @classmethod
+    def view_of(cls, tensor, space):
+        """The array on ``tensor`` [num_blocks, block_dim, len] as it is, without the copy to a contiguous layout: a column of the
+        panel of a batched solve stays a view of the panel (``InstationaryDuneDiscretization.solve_batch``)."""
+        assert tensor.dim() == 3
+        out = cls.__new__(cls)
+        out._t, out.space = tensor, space
+        return out
+
     def __len__(self):
         return int(self._t.shape[2])
 
