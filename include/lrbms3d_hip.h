@@ -304,7 +304,8 @@ int lrbms3_project_mass(lrbms3_ctx* ctx, int32_t N, const double* V, double* M_r
  * lrbms3_fom_precond_keep holds for the elliptic solves is neither used nor replaced.
  *   theta [Q] host; U [nt+1][S][n]: U[0] = initial value (input), U[1..nt] written; work: lrbms3_fom_implicit_euler_work_size
  *   doubles; info (host, may be NULL): {total CG iterations, worst final residual relative to |M u_k + dt b|}.
- *   LRBMS_E_INVALID if dt <= 0 or nt < 1; LRBMS_E_NOT_CONVERGED if a step misses rtol within max_iter.
+ *   LRBMS_E_INVALID if dt <= 0 or nt < 1; LRBMS_E_NOT_CONVERGED if a step misses rtol within max_iter (U[k+1] then holds
+ *   that step's last iterate u_k + d, later slabs are untouched; the reduced counterpart does the same).
  * 2D: lrbms_fom_implicit_euler. */
 int64_t lrbms3_fom_implicit_euler_work_size(lrbms3_ctx* ctx);
 int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, double dt, int32_t nt, const double* A_diag,

@@ -5078,9 +5078,11 @@ int fom_euler_run(lrbms3_ctx* ctx, const char* name, int Q, const double* theta,
     iters += inf[0];
     worst = std::max(worst, inf[1]);
     if (info) info[0] = iters, info[1] = worst;
-    if (rc != LRBMS_OK) return rc;
+    if (rc != LRBMS_OK && rc != LRBMS_E_NOT_CONVERGED) return rc;
+    // (also behind a step that missed rtol: U[k + 1] holds the iterate u_k + d, as the batched exports leave it, not the bare correction)
     hipLaunchKernelGGL(k3p_axpy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, uk, un);
     LRBMS_LAUNCH_CHECK(ctx);
+    if (rc != LRBMS_OK) return rc;
   }
   return LRBMS_OK;
 }
@@ -5119,9 +5121,11 @@ int red_euler_run(lrbms3_ctx* ctx, const char* name, int Q, int N, const double*
     iters += inf[0];
     worst = std::max(worst, inf[1]);
     if (info) info[0] = iters, info[1] = worst;
-    if (rc != LRBMS_OK) return rc;
+    if (rc != LRBMS_OK && rc != LRBMS_E_NOT_CONVERGED) return rc;
+    // (also behind a step that missed rtol: U[k + 1] holds the iterate u_k + d, as the batched exports leave it, not the bare correction)
     hipLaunchKernelGGL(k3p_axpy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, uk, un);
     LRBMS_LAUNCH_CHECK(ctx);
+    if (rc != LRBMS_OK) return rc;
   }
   return LRBMS_OK;
 }
