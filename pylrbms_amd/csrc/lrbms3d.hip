@@ -1,4 +1,6 @@
-// 3D / P2 hot path (BASELINE.json config 5) for gfx950: C ABI of include/lrbms3d_hip.h.
+// 3D / P2 hot path (BASELINE.json config 5) for gfx950: C ABI of include/lrbms3d_hip.h.  Affine sources live in sources3d.hip and
+// online enrichment in enrich3d.hip, with lrbms3d_dev.h between the three files; enrich3d.hip calls launch_combine and
+// launch_fom_block_inverse of this file.
 //
 // Kuhn triangulation: every element is a translate of one of six reference tetrahedra, so every local integral is a
 // contraction of coefficient samples with a reference table (pylrbms_amd/grid3d.py builds the tables on the host, once):
@@ -8,83 +10,12 @@
 // staging, no VALU arithmetic in the loop), one wave per item, one workgroup per (subdomain, operator).  Images of a NEIGHBOUR's
 // basis live on the side faces / side nodes of the target subdomain only: they are returned as factors (Rb, Yb, Dp, Xab, As, Cn)
 // and the estimate kernel consumes the factors (header).
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include <rocsolver/rocsolver.h>
-
-#include "../../include/lrbms3d_hip.h"
-#include "lrbms_ctx_base.h"
+#include "lrbms3d_dev.h"
 #include "lrbms_pod.h"
 
-namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-struct T3 {
-  int S, S_ext, nT, n, nrt, ncf, nbf, nvs, nnodes, nb, nbel, nsel, nbd;
-  int nA, nB, nC, nFs, nFf, o_fs, o_ff, o_c, lam_stride, hat_stride, f_stride;
-  double volume, kmin;
-  const int *nbr, *phys;
-  const int *elem_type, *up_face, *order, *nb_elem, *nb_out, *face_pos, *tsign, *elem_rt, *rt_e0, *rt_f0, *rt_e1, *rt_f1;
-  const int *side_elem, *side_face, *side_elem_out, *side_face_out;
-  const int *dof_node, *node_ptr, *node_dofs, *node_mask, *node_count, *side_nodes, *sn_ptr, *sn_dofs;
-  const int *dof_bslot, *bn_ptr, *bn_slots, *bnodes, *bnode_sides, *bel_elem, *bel_bnode, *sel_elem, *sel_sf;
-  const double *divc, *TV, *TE, *TAA, *TFo, *TFn, *TFb, *TPo, *TPn, *TPb, *TC, *TCb, *TPH, *TM, *TB, *TAB, *WB, *WC;
-  const double* TSP;     // [6][nA + 8 nFs][100] diagonal block of the local energy product: TV | per face (TPo | TPb)
-  const double* TSD;     // [6][nA + 8 nFs][100] system diagonal block: TV | per face (TFo | TFb)  (built at mesh upload)
-  const double* zeros;   // [64] zeros: target of the loads of padding lanes
-};
-
-}  // namespace
-
-struct lrbms3_ctx : lrbms_ctx_base {
-  T3 t{};
-  std::vector<int32_t> nbr_host;
-  // coarse space of the full-order solver (lrbms3_fom_coarse_space): nc functions per subdomain, values at the local DoFs
-  int fom_nc = 0;
-  double* fom_phi = nullptr;      // [n][4] device, zero-padded columns
-  bool fom_keep = false;          // lrbms3_fom_precond_keep: the coarse inverse of a solve stays in the context for the next ones
-  double* fom_pc = nullptr;       // [M][M] device (owned), valid for fom_pc_M = nc S unknowns of fom_pc_nc functions
-  long fom_pc_M = 0;
-  int fom_pc_nc = 0;
-  double fomb_panels[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // lrbms3_fom_solve_batch: (iterations, final ratio) of the up to four panels of the last call
-  void* blas = nullptr;           // rocBLAS handle (dense coarse inverses), created on first use
-  const double* user_pc = nullptr;   // coarse inverse the batched reduced solve uses (lrbms3_reduced_precond_use), caller-owned
-  int user_pc_N = 0;
-  double* thbar = nullptr;         // [8] device: theta(mu_bar) of lrbms3_assemble_energy_product
-  double* tm_inv = nullptr;        // [6][100] device (owned): inverses of the element mass tables (parabolic path, first use)
-  const double* tm_inv_src = nullptr;   // the TM table they were taken from (a new mesh upload invalidates them)
-  double* pg_part = nullptr;       // K-split partial results of the k3_pg kernels (library-owned, grown on demand)
-  long pg_part_cap = 0;
-  // launch policy (lrbms3_ctx_set_option): the library reads no environment variable
-  int opt_ksplit = 0, opt_serial = 0, opt_waves = 0, opt_estimate_valu = 0, opt_solve_valu = 0, opt_fom_coarse = 1;
-  double* src_phi = nullptr;       // [64][64] device (owned): source coefficients of lrbms3_reduced_solve_batch_src, first use
-  int num_cus = 0;                 // compute units of the device (lrbms3_combine_sources sizes its grid by them), first use
-  bool side_padding = false;       // some side has fewer faces than ncf (unequal cubes per direction): padded factor rows exist
-  // restricted pass (lrbms3_pass_set_subset): device lists [S] each (one ctx-owned allocation, made at the first restriction)
-  bool sub_active = false;
-  int* sub_own = nullptr;          // changed local subdomains, ascending: phase 1 runs over them
-  int* sub_side = nullptr;         // local subdomains that are changed or have a changed face neighbour, ascending: phase 2
-  int sub_own_n = 0, sub_side_n = 0;
-};
+using namespace lrbms3;
 
 namespace {
-
-__device__ inline int side_slot(int side) { return side < 3 ? side : side + 1; }
-
-// RT0 orientation of (element, face) in subdomain s: +1 = outward from this element
-__device__ inline int sgn3(const T3& t, int s, int e, int f) {
-  const int nb = t.nb_elem[e * 4 + f];
-  if (nb < 0 && ((t.phys[s] >> (-(nb + 1))) & 1)) return 1;
-  return t.tsign[e * 4 + f];
-}
 
 // ------------------------------------------------------------------------------------------------- offline assembly
 __device__ inline double contract(const double* __restrict__ smp, const double* __restrict__ tab, int K, int C, int c) {
@@ -294,17 +225,6 @@ constexpr int FLUX_R = 1;     // rows per wave and step (4 rows with their loads
 #ifndef NODE_LOOP
 #define NODE_LOOP 4
 #endif
-
-// Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  The row blocks of one subdomain read overlapping basis
-// rows, so a 1D grid is decoded such that all blocks of a subdomain get ids that are equal modulo 8 (one XCD) and close in time:
-// chunks of 8 subdomains, inside a chunk the subdomain is the fast index.  Returns false for the padding of the last chunk.
-__device__ inline bool xcd_block(int nblk, int S, int& xblk, int& s) {
-  const int L = blockIdx.x, chunk = L / (8 * nblk), in = L - chunk * 8 * nblk;
-  s = chunk * 8 + (in & 7);
-  xblk = in >> 3;
-  return s < S;
-}
-inline unsigned xcd_grid(int nblk, int S) { return (unsigned)((S + 7) / 8 * 8 * nblk); }
 
 // The same decode for a pass restricted to a list of subdomains (lrbms3_pass_set_subset): the chunks of 8 are formed over the cnt
 // POSITIONS of the list and the subdomain is list[position]; every stride and every neighbour lookup keeps using the subdomain.
@@ -1448,8 +1368,6 @@ __global__ __launch_bounds__(256) void k3_zero_side_rows(T3 t, int Q, int N, con
 }
 
 // ------------------------------------------------------------------------------------------------- online: estimate
-struct QV { double v[8]; };
-
 __device__ inline double block_sum(double v, double* red) {   // fixed-order tree over 256 threads; red [256]
   const int tid = threadIdx.x;
   __syncthreads();
@@ -2740,7 +2658,6 @@ __global__ __launch_bounds__(256) void k3_fom_apply(T3 t, int Q, int M, QV th, c
 // A(mu) x = b on the never-assembled block operator: CG with the 10 x 10 element blocks as block-Jacobi preconditioner.  The
 // operator is combined once per solve (Amu = sum_q theta_q A_q); an iteration is three kernels + three one-block reductions,
 // all scalars stay on the device.  EPB elements (10 rows each) per workgroup.
-constexpr int FOM_EPB = 24;
 constexpr int FOM_MAX_COARSE = 8192;      // largest dense coarse problem of the full-order solver (2 x 0.5 GB of work, ~0.1 s to invert)
 
 // inverse of the diagonal 10 x 10 blocks (SPD): Gauss-Jordan, one thread per element, the block in LDS
@@ -3049,13 +2966,19 @@ __global__ __launch_bounds__(256) void k3f_coarse_apply(int M, const double* __r
 }
 
 
-QV make_theta(int Q, const double* theta) {
-  QV th{};
-  for (int q = 0; q < Q && q < 8; ++q) th.v[q] = theta[q];
-  return th;
+}  // namespace
+
+namespace lrbms3 {
+
+// the kernels of this file that enrich3d.hip launches: grid and block as at the launches below
+void launch_combine(hipStream_t st, long per_q, int Q, const QV& th, const double* B, double* Amu) {
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, th, B, Amu);
+}
+void launch_fom_block_inverse(hipStream_t st, const T3& t, const double* Amu, double* Dinv) {
+  hipLaunchKernelGGL(k3f_block_inverse, dim3((t.nT + 63) / 64, t.S), dim3(64), 0, st, t, Amu, Dinv);
 }
 
-}  // namespace
+}  // namespace lrbms3
 
 extern "C" {
 
@@ -5401,694 +5324,6 @@ int lrbms3_reduced_time_residual(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t 
   hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, make_theta(Q, theta), B_sys, Amu);
   hipLaunchKernelGGL(k3p_time_residual, dim3(S, L), dim3(64), sizeof(double) * (8 * N + 64), st, t, N, Amu, Minv, dU, out);
   LRBMS_LAUNCH_CHECK(ctx);
-  return LRBMS_OK;
-}
-
-}  // extern "C"
-
-// ================================================================================================= affine sources
-// f(mu) or f(t, mu) = sum_j phi_j f_j with K components: the Grams of the components, the projections of their
-// load vectors and element integrals, and the f terms of the residual indicator for columns with coefficients of their own.
-int launch_combine_sources_base(lrbms_ctx_base* ctx, int* num_cus, int K, long M, const double* phi, const double* x_K, double* y,
-                                hipStream_t st);      // online.hip: the 2D export's kernel, shape-agnostic
-
-namespace {
-
-// F2 [S][K][K]: one workgroup per (subdomain, pair j <= l), the expression and the fixed-order tree of k3_scalars' f2 with one factor
-// from each component -- K = 1 gives that f2 bit for bit.  comp = S n_T f_stride, the stride between two components' samples.
-__global__ __launch_bounds__(256) void k3_source_gram(T3 t, int K, long comp, const double* __restrict__ f_smp_K, double* __restrict__ F2) {
-  __shared__ double sa[256];
-  const int s = blockIdx.x, tid = threadIdx.x;
-  int j = 0, l = blockIdx.y;                 // pair index -> (j, l), row-wise over the upper triangle
-  while (l >= K - j) {
-    l -= K - j;
-    ++j;
-  }
-  l += j;
-  const double* fj = f_smp_K + (long)j * comp;
-  const double* fl = f_smp_K + (long)l * comp;
-  double acc = 0.0;
-  for (int e = tid; e < t.nT; e += 256) {
-    const double* rj = fj + ((long)s * t.nT + e) * t.f_stride;
-    const double* rl = fl + ((long)s * t.nT + e) * t.f_stride;
-    for (int k = 0; k < t.nB; ++k) acc += t.WB[k] * rj[k] * rl[k];
-  }
-  sa[tid] = acc;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) sa[tid] += sa[tid + w];
-    __syncthreads();
-  }
-  if (tid == 0) {
-    F2[((long)s * K + j) * K + l] = sa[0];
-    F2[((long)s * K + l) * K + j] = sa[0];
-  }
-}
-
-// Both projections of lrbms3_project_sources in one launch on the fp64 matrix cores, one workgroup of 8 waves per (subdomain, role):
-//   role 0   rhs_red_K [K][S][N]  = b_K[j][s]^T V_s                       rows = the n DoFs, row operand = the rows of V_s
-//   role 1   r_fd_K    [K][S][QN] = sum_e bdiv_K[j][s][e] div(R_self)_e    rows = the n_T elements, row operand = the divergence of the
-//            element's four RT0 rows of the flux image R_self [S][n_rt][QN], formed in the lane (orientation and |f| / |T| as k3_estimate)
-// A wave takes four rows per step: the A operand holds the K components' weights of these rows (lane: component l & 15, row l >> 4),
-// the B operand the row operand (lane: column l & 15, row l >> 4); V and R_self are read once, whatever K.  KT = 16-component tiles;
-// up to four 16-column tiles.  The waves' tiles are summed in a fixed order through the LDS.
-template <int KT>
-__global__ __launch_bounds__(512) void k3_project_sources(T3 t, int N, int QN, int K, const int* __restrict__ list,
-                                                          const double* __restrict__ b_K, const double* __restrict__ bdiv_K,
-                                                          const double* __restrict__ V,
-                                                          const double* __restrict__ Rs, double* __restrict__ rhs_K,
-                                                          double* __restrict__ rfd_K) {
-  __shared__ double red[8][256];
-  const int s = list ? list[blockIdx.x] : blockIdx.x, mode = blockIdx.y, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cols = mode ? QN : N, rows = mode ? t.nT : t.n, nct = (cols + 15) / 16;
-  const long xs = (long)t.S * rows;
-  const double* X = (mode ? bdiv_K : b_K) + (long)s * rows;
-  d4 acc[KT][4];
-#pragma unroll
-  for (int rt = 0; rt < KT; ++rt)
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = d4{0.0, 0.0, 0.0, 0.0};
-  for (int r0 = wave * 4; r0 < rows; r0 += 32) {
-    const int r = r0 + lk;
-    const bool rin = r < rows;
-    double a[KT], v[4];
-#pragma unroll
-    for (int rt = 0; rt < KT; ++rt) {
-      const int j = 16 * rt + li;
-      a[rt] = (rin && j < K) ? X[(long)j * xs + r] : 0.0;
-    }
-    if (mode == 0) {
-      const double* row = V + ((long)s * t.n + (rin ? r : 0)) * N;
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        const int c = 16 * ct + li;
-        v[ct] = (rin && c < cols) ? row[c] : 0.0;
-      }
-    } else {
-      const int e = rin ? r : 0, ty = t.elem_type[e];
-      double dd[4];
-      const double* rr[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        dd[f] = rin ? sgn3(t, s, e, f) * t.divc[ty * 4 + f] : 0.0;
-        rr[f] = Rs + ((long)s * t.nrt + t.elem_rt[e * 4 + f]) * QN;
-      }
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        const int c = 16 * ct + li;
-        double dv = 0.0;
-        if (c < cols) {
-#pragma unroll
-          for (int f = 0; f < 4; ++f) dv += dd[f] * rr[f][c];
-        }
-        v[ct] = dv;
-      }
-    }
-#pragma unroll
-    for (int rt = 0; rt < KT; ++rt)
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        if (ct < nct) acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rt], v[ct], acc[rt][ct], 0, 0, 0);
-  }
-  double* out = mode ? rfd_K : rhs_K;
-#pragma unroll
-  for (int rt = 0; rt < KT; ++rt)
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      if (ct >= nct) continue;               // (uniform over the workgroup)
-      __syncthreads();
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[wave][r * 64 + lane] = acc[rt][ct][r];
-      __syncthreads();
-      if (tid < 256) {
-        const int r = tid >> 6, l = tid & 63;
-        double sum = 0.0;
-        for (int w = 0; w < 8; ++w) sum += red[w][tid];
-        const int j = 16 * rt + (l >> 4) + 4 * r, c = 16 * ct + (l & 15);
-        if (j < K && c < cols) out[((long)j * t.S + s) * cols + c] = sum;
-      }
-    }
-}
-
-// Sum over the workers (tid >> 3) of the values of column tid & 7, fixed order; red [256].  The result is valid in every thread.
-__device__ inline double column_sum8(double v, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int w = 128; w >= 8; w >>= 1) {
-    if (tid < w) red[tid] += red[tid + w];
-    __syncthreads();
-  }
-  return red[tid & 7];
-}
-
-// The f terms of the residual indicator (lrbms3_reduced_source_terms) for eight columns per workgroup: threads = (worker tid >> 3,
-// column tid & 7) as in k3_estimate_batch, so the eight columns share every factor row.  ur, zf = Rb ur_a and the divergence of zf on
-// the side elements are those of k3_estimate; theta [L][Q] and phi [L][K] are per column.  out [S][L].
-__global__ __launch_bounds__(256) void k3_source_terms(T3 t, int Q, int N, int K, int L, const double* __restrict__ theta,
-                                                       const double* __restrict__ phi, const double* __restrict__ F2,
-                                                       const double* __restrict__ r_fd_K, const double* __restrict__ bdiv_K,
-                                                       const double* __restrict__ Rb, const double* __restrict__ u,
-                                                       const double* __restrict__ ceps, double hdiam, double* __restrict__ out) {
-  extern __shared__ double lds[];
-  const int s = blockIdx.x, tid = threadIdx.x, w = tid >> 3, m = tid & 7, QN = Q * N;
-  double* us = lds;                    // [7][N][8] coefficients on the neighbourhood (0 where no neighbour)
-  double* zf = us + 7 * N * 8;         // [nbf][8]  flux of the neighbours on the side faces
-  double* ths = zf + t.nbf * 8;        // [8][8]    theta_q of the columns
-  double* red = ths + 64;              // [256]
-  const int l0 = blockIdx.y * 8;
-  const int l = l0 + m < L ? l0 + m : L - 1;          // columns behind L repeat the last one and are not stored
-  for (int k = tid; k < 7 * N * 8; k += 256) {
-    const int slot = k / (N * 8), j = (k >> 3) % N, mm = k & 7;
-    const int ll = l0 + mm < L ? l0 + mm : L - 1;
-    const int s2 = t.nbr[s * 7 + slot];
-    us[k] = s2 >= 0 ? u[((long)s2 * N + j) * L + ll] : 0.0;
-  }
-  if (tid < 64) {
-    const int q = tid >> 3, ll = l0 + (tid & 7) < L ? l0 + (tid & 7) : L - 1;
-    ths[tid] = q < Q ? theta[(long)ll * Q + q] : 0.0;
-  }
-  __syncthreads();
-  for (int sf = w; sf < t.nbf; sf += 32) {
-    const double* ua = us + side_slot(sf / t.ncf) * N * 8 + m;
-    const double* r = Rb + ((long)s * t.nbf + sf) * QN;
-    double acc = 0.0;
-    for (int q = 0; q < Q; ++q) {
-      double aq = 0.0;
-      for (int j = 0; j < N; ++j) aq += r[q * N + j] * ua[j * 8];
-      acc += ths[q * 8 + m] * aq;
-    }
-    zf[sf * 8 + m] = acc;
-  }
-  __syncthreads();
-  const double* ph = phi + (long)l * K;
-  const double* u0 = us + 3 * N * 8 + m;
-  double p_fd = 0.0, p_ff = 0.0;
-  for (int r = w; r < QN; r += 32) {
-    double rp = 0.0;
-    for (int j = 0; j < K; ++j) rp += ph[j] * r_fd_K[((long)j * t.S + s) * QN + r];
-    p_fd += rp * (ths[(r / N) * 8 + m] * u0[(r % N) * 8]);
-  }
-  for (int k = w; k < t.nsel; k += 32) {
-    const int e = t.sel_elem[k], ty = t.elem_type[e];
-    double dv = 0.0;
-    for (int f = 0; f < 4; ++f) {
-      const int sf = t.sel_sf[k * 4 + f];
-      const double ze = sf >= 0 ? zf[sf * 8 + m] : 0.0;
-      dv += sgn3(t, s, e, f) * t.divc[ty * 4 + f] * ze;
-    }
-    double bp = 0.0;
-    for (int j = 0; j < K; ++j) bp += ph[j] * bdiv_K[((long)j * t.S + s) * t.nT + e];
-    p_fd += bp * dv;
-  }
-  for (int k = w; k < K * K; k += 32) p_ff += ph[k / K] * F2[(long)s * K * K + k] * ph[k % K];
-  const double fd = column_sum8(p_fd, red);
-  const double ff = column_sum8(p_ff, red);
-  if (w == 0 && l0 + m < L) {
-    const double pi = 3.14159265358979323846;
-    out[(long)s * L + l] = (ff - 2.0 * fd) * (1.0 / (pi * pi)) / ceps[s] * hdiam * hdiam;
-  }
-}
-
-}  // namespace
-
-extern "C" {
-
-int lrbms3_assemble_source_gram(lrbms3_ctx* ctx, int32_t K, const double* f_smp_K, double* F2, void* stream) {
-  LRBMS_REQUIRE_MESH(ctx);
-  const T3& t = ctx->t;
-  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_source_gram: needs all subdomains on this rank");
-  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_source_gram: K must be in [1, 64]");
-  if (!f_smp_K || !F2) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_source_gram: null argument");
-  hipLaunchKernelGGL(k3_source_gram, dim3(t.S, K * (K + 1) / 2), dim3(256), 0, (hipStream_t)stream, t, K, (long)t.S * t.nT * t.f_stride,
-                     f_smp_K, F2);
-  LRBMS_LAUNCH_CHECK(ctx);
-  return LRBMS_OK;
-}
-
-int lrbms3_project_sources(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, const double* b_K, const double* bdiv_K, const double* V,
-                           const double* R_self, double* rhs_red_K, double* r_fd_K, void* stream) {
-  LRBMS_REQUIRE_MESH(ctx);
-  const T3& t = ctx->t;
-  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: needs all subdomains on this rank");
-  if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: K must be in [1, 64]");
-  if (Q < 1 || Q > 8 || N < 1 || N > 64 || Q * N > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: needs N <= 64 and Q N <= 64");
-  if (!b_K || !bdiv_K || !V || !R_self || !rhs_red_K || !r_fd_K) return lrbms_fail(ctx, LRBMS_E_INVALID, "project_sources: null argument");
-  hipStream_t st = (hipStream_t)stream;
-  const int* list = ctx->sub_active ? ctx->sub_own : nullptr;      // lrbms3_pass_set_subset: the rows of the own list only
-  const int cnt = ctx->sub_active ? ctx->sub_own_n : t.S;
-  if (cnt <= 0) return LRBMS_OK;
-  const dim3 grid(cnt, 2);
-#define PSCASE(T)                                                                                                                  \
-  case T:                                                                                                                          \
-    hipLaunchKernelGGL(k3_project_sources<T>, grid, dim3(512), 0, st, t, N, Q * N, K, list, b_K, bdiv_K, V, R_self, rhs_red_K, r_fd_K); \
-    break
-  switch ((K + 15) / 16) {
-    PSCASE(1);
-    PSCASE(2);
-    PSCASE(3);
-    PSCASE(4);
-  }
-#undef PSCASE
-  LRBMS_LAUNCH_CHECK(ctx);
-  return LRBMS_OK;
-}
-
-int lrbms3_reduced_source_terms(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t L, const double* theta, const double* phi,
-                                const double* F2, const double* r_fd_K, const double* bdiv_K, const double* Rb, const double* u,
-                                const double* ceps, double hdiam, double* out, void* stream) {
-  LRBMS_REQUIRE_MESH(ctx);
-  const T3& t = ctx->t;
-  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: needs all subdomains on this rank");
-  if (Q < 1 || Q > 8 || N < 1 || N > 64 || K < 1 || K > 64 || L < 1 || (L + 7) / 8 > 65535)
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: bad N / L / K / Q");
-  if (!theta || !phi || !F2 || !r_fd_K || !bdiv_K || !Rb || !u || !ceps || !out)
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: null argument");
-  const size_t lds = sizeof(double) * (7 * (size_t)N * 8 + (size_t)t.nbf * 8 + 64 + 256);
-  if (lds > 64 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: the side faces of this template do not fit the LDS");
-  hipLaunchKernelGGL(k3_source_terms, dim3(t.S, (L + 7) / 8), dim3(256), lds, (hipStream_t)stream, t, Q, N, K, L, theta, phi, F2, r_fd_K,
-                     bdiv_K, Rb, u, ceps, hdiam, out);
-  LRBMS_LAUNCH_CHECK(ctx);
-  return LRBMS_OK;
-}
-
-int lrbms3_combine_sources(lrbms3_ctx* ctx, int32_t K, int64_t M, const double* phi, const double* x_K, double* y, void* stream) {
-  if (!ctx) return LRBMS_E_INVALID;
-  if (!phi || !x_K || !y) return lrbms_fail(ctx, LRBMS_E_INVALID, "combine_sources: null argument");
-  return launch_combine_sources_base(ctx, &ctx->num_cus, K, (long)M, phi, x_K, y, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------- online enrichment
-// Neighbourhood corrector problems (reference block_swipdg.py:227-316; 2D: csrc/enrich.hip): for a marked subdomain m the SWIPDG
-// problem on N(m) = m and its face neighbours with Dirichlet data on the outer boundary, right-hand side the L2 functional of f,
-// solution restricted to m.  In the block data: the operator restricted to the members of N(m), the coupling blocks towards
-// subdomains outside dropped and the correction block D_corr added to the own element's diagonal block on those faces.
-// A 3D neighbourhood does not fit a workgroup (7 x 3 840 unknowns at config 5), so this is a batched multi-kernel PCG in the
-// style of lrbms3_fom_solve with a problem dimension: vectors [nmark][7][n] (slot = the slot of nbr[m], absent slots never
-// touched), scalars per problem on the device, block-Jacobi from the uncorrected element blocks (SPD, one inverse per element
-// for all problems).  The matvec is organised by MEMBER subdomain: a workgroup owns (subdomain, element chunk), reads every
-// combined block once and applies it to the vectors of every problem that contains the subdomain.
-namespace {
-
-// per problem: [0], [1] r.z of the last two updates (alternating)  [2] p.Ap  [3] r.r  [4] b.b  [5] state: 0 running, 1 converged,
-// 2 broken down (p.Ap <= 0 or a NaN)  [6] iterations at the freeze.  A frozen problem is skipped by every kernel: its x stays.
-constexpr int LC_SCAL = 8;
-
-// D_corr[q][s][side][pos] = lambda_q at the face points of the own side element . (Dirichlet-face table - inner-face own/own table)
-__global__ __launch_bounds__(128) void k3l_dirichlet_correction(T3 t, const double* __restrict__ lam, double* __restrict__ D_corr) {
-  const int sf = blockIdx.x, s = blockIdx.y, q = blockIdx.z, c = threadIdx.x;
-  if (c >= 100) return;
-  const int side = sf / t.ncf, e = t.side_elem[sf], f = t.side_face[sf];
-  double acc = 0.0;
-  if (e >= 0 && !((t.phys[s] >> side) & 1) && t.nbr[s * 7 + side_slot(side)] >= 0) {
-    const double* w = lam + (((long)q * t.S_ext + s) * t.nT + e) * t.lam_stride + t.o_fs + f * t.nFs;
-    const long tab = ((long)(t.elem_type[e] * 4 + f) * t.nFs) * 100 + c;
-    for (int k = 0; k < t.nFs; ++k) acc += w[k] * (t.TFb[tab + (long)k * 100] - t.TFo[tab + (long)k * 100]);
-  }
-  D_corr[(((long)q * t.S + s) * t.nbf + sf) * 100 + c] = acc;
-}
-
-// p = z + beta p on the present slots of the running problems (the first direction does not read p)
-__global__ __launch_bounds__(256) void k3l_dir(T3 t, int first, int cur, const int* __restrict__ marked, const double* __restrict__ scal,
-                                               const double* __restrict__ z, double* __restrict__ p) {
-  const int slot = blockIdx.y, pm = blockIdx.z;
-  const double* sc = scal + (long)pm * LC_SCAL;
-  if (sc[5] != 0.0 || t.nbr[marked[pm] * 7 + slot] < 0) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= t.n) return;
-  const long d = ((long)pm * 7 + slot) * t.n + i;
-  p[d] = first ? z[d] : z[d] + (sc[cur] / sc[cur ^ 1]) * p[d];
-}
-
-// y = A_N(m) p for every running problem m that contains the subdomain of this workgroup; partial p.y per (problem, slot, chunk).
-// k3f_matvec (block loads of 16 bytes per lane, the symmetric read inside a subdomain, xcd_block) with the blocks of an element
-// held in registers over the loop of the <= 7 problems: nbr[s][j] = m marked <=> s sits in slot 6 - j of problem m.  A side
-// face with neighbour s' contributes the coupling block times x_m[s'] in problem m = s, times x_m[self] in problem m = s', and
-// Dmu times the own element's x in every other problem (s' lies outside that neighbourhood).
-__global__ __launch_bounds__(256) void k3l_matvec(T3 t, int nbx, int nmemb, const int* __restrict__ memb, const int* __restrict__ pidx,
-                                                  const double* __restrict__ scal, const double* __restrict__ Amu,
-                                                  const double* __restrict__ Cmu, const double* __restrict__ Dmu,
-                                                  const double* __restrict__ p, double* __restrict__ y, double* __restrict__ part) {
-  __shared__ double red[7][4];
-  int mi, bx;
-  if (!xcd_block(nbx, nmemb, bx, mi)) return;
-  const int s = memb[mi];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const bool act = lane < 50;
-  const int li = act ? lane : 49, row = li / 5, c2 = 2 * (li - row * 5);
-  int pmj[7];
-  bool any = false;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    const int m = t.nbr[s * 7 + j];
-    int pm = m >= 0 ? pidx[m] : -1;
-    if (pm >= 0 && scal[(long)pm * LC_SCAL + 5] != 0.0) pm = -1;
-    pmj[j] = pm;
-    any = any || pm >= 0;
-  }
-  if (!any) return;
-  const double* As = Amu + (long)s * t.nT * 500;
-  double py[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  const int e1 = (bx + 1) * FOM_EPB < t.nT ? (bx + 1) * FOM_EPB : t.nT;
-  for (int e = bx * FOM_EPB + wave; e < e1; e += 4) {
-    const int4 nb = *reinterpret_cast<const int4*>(t.nb_elem + e * 4);
-    const int nbv[4] = {nb.x, nb.y, nb.z, nb.w};
-    const double2 a0 = *reinterpret_cast<const double2*>(As + (long)e * 500 + li * 2);
-    double2 af[4], ad[4];
-    int kind[4], eo[4], sl[4];        // 0 nothing, 1 the lower element's block (transposed), 2 own block, 3 side face with a neighbour
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      const int ee = nbv[f];          // wave-uniform
-      af[f] = ad[f] = make_double2(0.0, 0.0);
-      kind[f] = 0, eo[f] = 0, sl[f] = 0;
-      if (ee >= 0 && ee < e) {
-        const int4 nb2 = *reinterpret_cast<const int4*>(t.nb_elem + ee * 4);
-        const int fb = nb2.x == e ? 0 : (nb2.y == e ? 1 : (nb2.z == e ? 2 : 3));
-        af[f] = *reinterpret_cast<const double2*>(As + (long)ee * 500 + (1 + fb) * 100 + li * 2);
-        kind[f] = 1, eo[f] = ee;
-      } else if (ee >= 0) {
-        af[f] = *reinterpret_cast<const double2*>(As + (long)e * 500 + (1 + f) * 100 + li * 2);
-        kind[f] = 2, eo[f] = ee;
-      } else {
-        const int side = -(ee + 1);
-        sl[f] = side_slot(side);
-        if (t.nbr[s * 7 + sl[f]] >= 0) {
-          const long off = (((long)s * 6 + side) * t.ncf + t.face_pos[e * 4 + f]) * 100 + li * 2;
-          af[f] = *reinterpret_cast<const double2*>(Cmu + off);
-          ad[f] = *reinterpret_cast<const double2*>(Dmu + off);
-          kind[f] = 3, eo[f] = t.nb_out[e * 4 + f];
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const int pm = pmj[j];          // wave-uniform
-      if (pm < 0) continue;
-      const double* P = p + (long)pm * 7 * t.n;
-      const double* ps = P + (long)(6 - j) * t.n;
-      double yr, yc0 = 0.0, yc1 = 0.0;                // row sums (valid in lanes 5 i), column sums (valid in lanes 0 .. 4)
-      {
-        const double2 pv = *reinterpret_cast<const double2*>(ps + e * 10 + c2);
-        yr = act ? a0.x * pv.x + a0.y * pv.y : 0.0;
-      }
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        if (kind[f] == 1) {
-          const double pr = ps[eo[f] * 10 + row];
-          yc0 += act ? af[f].x * pr : 0.0;
-          yc1 += act ? af[f].y * pr : 0.0;
-        } else if (kind[f] == 2) {
-          const double2 pv = *reinterpret_cast<const double2*>(ps + eo[f] * 10 + c2);
-          yr += act ? af[f].x * pv.x + af[f].y * pv.y : 0.0;
-        } else if (kind[f] == 3) {
-          const bool cpl = j == 3 || j == sl[f];      // the neighbour across this side belongs to the problem
-          const double* pn = j == 3 ? P + (long)sl[f] * t.n + eo[f] * 10 : (j == sl[f] ? P + 3L * t.n + eo[f] * 10 : ps + e * 10);
-          const double2 a = cpl ? af[f] : ad[f];
-          const double2 pv = *reinterpret_cast<const double2*>(pn + c2);
-          yr += act ? a.x * pv.x + a.y * pv.y : 0.0;
-        }
-      }
-      // row sums: lanes l .. l + 4 (fixed order), result in lanes 5 i;  column sums: lanes l, l + 5, ..., l + 45, result in lanes 0 .. 4
-      double r1 = yr + __shfl_down(yr, 1);
-      r1 = r1 + __shfl_down(r1, 2);
-      const double rs = r1 + __shfl_down(yr, 4);
-      double c0 = yc0 + __shfl_down(yc0, 5), c1 = yc1 + __shfl_down(yc1, 5);
-      c0 += __shfl_down(c0, 10); c1 += __shfl_down(c1, 10);
-      c0 += __shfl_down(c0, 20); c1 += __shfl_down(c1, 20);
-      c0 += __shfl_down(yc0 + __shfl_down(yc0, 5), 40); c1 += __shfl_down(yc1 + __shfl_down(yc1, 5), 40);
-      const int tl = lane < 10 ? lane : 0;
-      const double ya = __shfl(rs, 5 * tl), yb0 = __shfl(c0, tl >> 1), yb1 = __shfl(c1, tl >> 1);
-      if (lane < 10) {
-        const double v = ya + ((lane & 1) ? yb1 : yb0);
-        y[((long)pm * 7 + (6 - j)) * t.n + e * 10 + lane] = v;
-        py[j] += v * ps[e * 10 + lane];
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    double v = py[j];
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_down(v, o);          // lanes 0 .. 9 (others are zero)
-    if (lane == 0) red[j][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < 7; ++j)
-      if (pmj[j] >= 0) part[((long)pmj[j] * 7 + (6 - j)) * nbx + bx] = (red[j][0] + red[j][1]) + (red[j][2] + red[j][3]);
-  }
-}
-
-// k3f_update per (chunk, slot, problem): x += alpha p, r -= alpha y, z = Dinv r with the element inverses of the slot's subdomain;
-// partial r.z and r.r (init: x = 0, r = b of the member subdomain)
-__global__ __launch_bounds__(256) void k3l_update(T3 t, int init, int cur, const int* __restrict__ marked, const double* __restrict__ scal,
-                                                  const double* __restrict__ Dinv, const double* __restrict__ p, const double* __restrict__ y,
-                                                  const double* __restrict__ b, double* __restrict__ x, double* __restrict__ r,
-                                                  double* __restrict__ z, double* __restrict__ prz, double* __restrict__ prr) {
-  __shared__ double rs[256], red[256];
-  const int slot = blockIdx.y, pm = blockIdx.z, tid = threadIdx.x;
-  const double* sc = scal + (long)pm * LC_SCAL;
-  const int s = t.nbr[marked[pm] * 7 + slot];
-  if (s < 0 || (!init && sc[5] != 0.0)) return;
-  const int el = tid / 10, i = tid - el * 10, e = blockIdx.x * FOM_EPB + el;
-  const bool on = el < FOM_EPB && e < t.nT;
-  const long d = ((long)pm * 7 + slot) * t.n + e * 10 + i;
-  double ri = 0.0;
-  if (on) {
-    if (init) {
-      ri = b[(long)s * t.n + e * 10 + i];
-      x[d] = 0.0;
-    } else {
-      const double alpha = sc[cur] / sc[2];
-      x[d] += alpha * p[d];
-      ri = r[d] - alpha * y[d];
-    }
-    r[d] = ri;
-  }
-  rs[tid] = ri;
-  __syncthreads();
-  double zi = 0.0;
-  if (on) {
-    const double* D = Dinv + ((long)s * t.nT + e) * 56;          // packed upper triangle (k3f_block_inverse)
-#pragma unroll
-    for (int j = 0; j < 10; ++j) {
-      const int a = i < j ? i : j, bb = i < j ? j : i;
-      zi += D[a * (21 - a) / 2 + bb - a] * rs[el * 10 + j];
-    }
-    z[d] = zi;
-  }
-  const long blk = ((long)pm * 7 + slot) * gridDim.x + blockIdx.x;
-  red[tid] = ri * zi;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) red[tid] += red[tid + w];
-    __syncthreads();
-  }
-  if (tid == 0) prz[blk] = red[0];
-  __syncthreads();
-  red[tid] = ri * ri;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) red[tid] += red[tid + w];
-    __syncthreads();
-  }
-  if (tid == 0) prr[blk] = red[0];
-}
-
-// One workgroup per problem: the partials of its present slots and chunks summed in a fixed order (the same whatever else is in
-// the batch), then the problem's scalars and its state.
-//   mode 0 (after the init update):  pa -> r.z [0], pb -> r.r [3] and b.b [4];  b = 0: converged at 0 iterations (x = 0)
-//   mode 1 (after the matvec):       pa -> p.Ap [2];  p.Ap <= 0 (or NaN): broken down, x stays where it is
-//   mode 2 (after the update):       pa -> r.z [nxt], pb -> r.r [3];  sqrt(r.r / b.b) <= rtol: converged after it + 1 iterations
-__global__ __launch_bounds__(256) void k3l_reduce(T3 t, int mode, int nbx, int it, int nxt, double rtol, const int* __restrict__ marked,
-                                                  const double* __restrict__ pa, const double* __restrict__ pb, double* __restrict__ scal) {
-  __shared__ double ra[256], rb[256];
-  const int pm = blockIdx.x, tid = threadIdx.x;
-  double* sc = scal + (long)pm * LC_SCAL;
-  if (mode != 0 && sc[5] != 0.0) return;
-  const int m = marked[pm], cnt = 7 * nbx;
-  double a = 0.0, b = 0.0;
-  for (int k = tid; k < cnt; k += 256) {
-    if (t.nbr[m * 7 + k / nbx] < 0) continue;
-    a += pa[(long)pm * cnt + k];
-    if (pb) b += pb[(long)pm * cnt + k];
-  }
-  ra[tid] = a;
-  rb[tid] = b;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      ra[tid] += ra[tid + w];
-      rb[tid] += rb[tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid != 0) return;
-  a = ra[0], b = rb[0];
-  if (mode == 0) {
-    sc[0] = a, sc[3] = b, sc[4] = b;
-    sc[5] = b == 0.0 ? 1.0 : (b == b ? 0.0 : 2.0);
-    sc[6] = 0.0;
-  } else if (mode == 1) {
-    sc[2] = a;
-    if (!(a > 0.0)) sc[5] = 2.0, sc[6] = (double)it;
-  } else {
-    sc[nxt] = a, sc[3] = b;
-    if (!(b == b) || !(a == a)) sc[5] = 2.0, sc[6] = (double)(it + 1);
-    else if (sqrt(b / sc[4]) <= rtol) sc[5] = 1.0, sc[6] = (double)(it + 1);
-  }
-}
-
-// corr [nmark][n] = the self slot of x
-__global__ __launch_bounds__(256) void k3l_restrict(int n, const double* __restrict__ x, double* __restrict__ corr) {
-  const int i = blockIdx.x * 256 + threadIdx.x, pm = blockIdx.y;
-  if (i < n) corr[(long)pm * n + i] = x[((long)pm * 7 + 3) * n + i];
-}
-
-// work layout of lrbms3_local_correction_solve
-struct LcWork {
-  int nbx;
-  long nvec, npart;
-  double *Amu, *Cmu, *Dmu, *Dinv, *x, *r, *z, *p, *y, *ppy, *prz, *prr, *scal;
-  int *marked, *pidx, *memb;
-};
-
-long lc_work(const T3& t, long nmark, double* work, LcWork* w) {
-  const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100;
-  const int nbx = (t.nT + FOM_EPB - 1) / FOM_EPB;
-  const long nvec = nmark * 7 * t.n, npart = nmark * 7 * nbx;
-  if (w) {
-    LcWork& l = *w;
-    l.nbx = nbx, l.nvec = nvec, l.npart = npart;
-    l.Amu = work;                       // every vector below starts at an even offset: the matvec loads 16 bytes per lane
-    l.Cmu = l.Amu + nd;
-    l.Dmu = l.Cmu + ncp;
-    l.Dinv = l.Dmu + ncp;
-    l.x = l.Dinv + S * t.nT * 56;
-    l.r = l.x + nvec;
-    l.z = l.r + nvec;
-    l.p = l.z + nvec;
-    l.y = l.p + nvec;
-    l.ppy = l.y + nvec;
-    l.prz = l.ppy + npart;
-    l.prr = l.prz + npart;
-    l.scal = l.prr + npart;
-    l.marked = (int*)(l.scal + nmark * LC_SCAL);      // [nmark] | pidx [S] | memb [S]
-    l.pidx = l.marked + nmark;
-    l.memb = l.pidx + S;
-  }
-  return nd + 2 * ncp + S * t.nT * 56 + 5 * nvec + 3 * npart + nmark * LC_SCAL + (nmark + 2 * S + 1) / 2;
-}
-
-}  // namespace
-
-extern "C" {
-
-int lrbms3_assemble_dirichlet_correction(lrbms3_ctx* ctx, int32_t Q, const double* lam, double* D_corr, void* stream) {
-  LRBMS_REQUIRE_MESH(ctx);
-  if (Q < 1 || Q > 8 || !lam || !D_corr) return lrbms_fail(ctx, LRBMS_E_INVALID, "assemble_dirichlet_correction: bad argument");
-  const T3& t = ctx->t;
-  hipLaunchKernelGGL(k3l_dirichlet_correction, dim3(t.nbf, t.S, Q), dim3(128), 0, (hipStream_t)stream, t, lam, D_corr);
-  LRBMS_LAUNCH_CHECK(ctx);
-  return LRBMS_OK;
-}
-
-int64_t lrbms3_local_correction_work_size(lrbms3_ctx* ctx, int32_t nmark) {
-  if (!ctx || !ctx->has_mesh || nmark < 1) return -1;
-  return (int64_t)lc_work(ctx->t, nmark, nullptr, nullptr);
-}
-
-int lrbms3_local_correction_solve(lrbms3_ctx* ctx, int32_t Q, const double* theta, int32_t nmark, const int32_t* marked,
-                                  const double* A_diag, const double* A_cpl, const double* D_corr, const double* b, double* work,
-                                  double* corr, double rtol, int32_t max_iter, double* info, void* stream) {
-  LRBMS_REQUIRE_MESH(ctx);
-  const T3& t = ctx->t;
-  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_correction_solve: needs all subdomains on this rank");
-  if (Q < 1 || Q > 8 || nmark < 1 || nmark > 65535 || !theta || !marked || !A_diag || !A_cpl || !D_corr || !b || !work || !corr ||
-      !(rtol > 0.0) || max_iter < 1)
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "local_correction_solve: bad argument");
-  const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100;
-  // host tables: marked | problem index of a subdomain (-1: not marked) | the subdomains that belong to some problem, ascending
-  std::vector<int> tab((size_t)nmark + 2 * S, -1);
-  int* pidx = tab.data() + nmark;
-  int* memb = pidx + S;
-  for (int k = 0; k < nmark; ++k) {
-    const int m = marked[k];
-    if (m < 0 || m >= S) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_correction_solve: marked subdomain " + std::to_string(m) + " out of range");
-    if (pidx[m] >= 0) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_correction_solve: subdomain " + std::to_string(m) + " marked twice");
-    pidx[m] = k;
-    tab[k] = m;
-  }
-  int nmemb = 0;
-  for (int s = 0; s < S; ++s) {
-    bool in = false;
-    for (int j = 0; j < 7; ++j) in = in || (ctx->nbr_host[(size_t)s * 7 + j] >= 0 && pidx[ctx->nbr_host[(size_t)s * 7 + j]] >= 0);
-    if (in) memb[nmemb++] = s;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  LcWork w;
-  lc_work(t, nmark, work, &w);
-  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(w.marked, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, st));
-  LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  const QV th = make_theta(Q, theta);
-  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, nd, Q, th, A_diag, w.Amu);
-  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((ncp + 255) / 256)), dim3(256), 0, st, ncp, Q, th, A_cpl, w.Cmu);
-  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((ncp + 255) / 256)), dim3(256), 0, st, ncp, Q, th, D_corr, w.Dmu);
-  hipLaunchKernelGGL(k3f_block_inverse, dim3((t.nT + 63) / 64, S), dim3(64), 0, st, t, w.Amu, w.Dinv);
-  const int nbx = w.nbx;
-  const dim3 gupd(nbx, 7, nmark), gdir((t.n + 255) / 256, 7, nmark);
-  hipLaunchKernelGGL(k3l_update, gupd, dim3(256), 0, st, t, 1, 0, w.marked, w.scal, w.Dinv, w.p, w.y, b, w.x, w.r, w.z, w.prz, w.prr);
-  hipLaunchKernelGGL(k3l_reduce, dim3(nmark), dim3(256), 0, st, t, 0, nbx, 0, 0, rtol, w.marked, w.prz, w.prr, w.scal);
-  LRBMS_LAUNCH_CHECK(ctx);
-  std::vector<double> sc((size_t)nmark * LC_SCAL);
-  auto poll = [&](bool& all_done, bool& broken) -> int {
-    LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(sc.data(), w.scal, sizeof(double) * sc.size(), hipMemcpyDeviceToHost, st));
-    LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    all_done = true, broken = false;
-    for (int k = 0; k < nmark; ++k) {
-      all_done = all_done && sc[(size_t)k * LC_SCAL + 5] != 0.0;
-      broken = broken || sc[(size_t)k * LC_SCAL + 5] == 2.0;
-    }
-    return LRBMS_OK;
-  };
-  bool all_done = false, broken = false;
-  int rc = poll(all_done, broken);
-  if (rc != LRBMS_OK) return rc;
-  int it = 0;
-  const int check = 16;
-  while (!all_done && !broken && it < max_iter) {
-    for (int k = 0; k < check && it < max_iter; ++k, ++it) {
-      const int cur = it & 1;
-      hipLaunchKernelGGL(k3l_dir, gdir, dim3(256), 0, st, t, it == 0 ? 1 : 0, cur, w.marked, w.scal, w.z, w.p);
-      hipLaunchKernelGGL(k3l_matvec, dim3(xcd_grid(nbx, nmemb)), dim3(256), 0, st, t, nbx, nmemb, w.memb, w.pidx, w.scal, w.Amu, w.Cmu,
-                         w.Dmu, w.p, w.y, w.ppy);
-      hipLaunchKernelGGL(k3l_reduce, dim3(nmark), dim3(256), 0, st, t, 1, nbx, it, 0, rtol, w.marked, w.ppy, (const double*)nullptr, w.scal);
-      hipLaunchKernelGGL(k3l_update, gupd, dim3(256), 0, st, t, 0, cur, w.marked, w.scal, w.Dinv, w.p, w.y, b, w.x, w.r, w.z, w.prz, w.prr);
-      hipLaunchKernelGGL(k3l_reduce, dim3(nmark), dim3(256), 0, st, t, 2, nbx, it, cur ^ 1, rtol, w.marked, w.prz, w.prr, w.scal);
-    }
-    LRBMS_LAUNCH_CHECK(ctx);
-    if ((rc = poll(all_done, broken)) != LRBMS_OK) return rc;
-  }
-  hipLaunchKernelGGL(k3l_restrict, dim3((t.n + 255) / 256, nmark), dim3(256), 0, st, t.n, w.x, corr);
-  LRBMS_LAUNCH_CHECK(ctx);
-  int bad = -1, bad_state = 0;
-  for (int k = 0; k < nmark; ++k) {
-    const double* s8 = sc.data() + (size_t)k * LC_SCAL;
-    const int state = (int)s8[5];
-    if (info) {
-      info[2 * k] = state != 0 ? s8[6] : (double)it;
-      info[2 * k + 1] = s8[4] > 0.0 ? sqrt(s8[3] / s8[4]) : 0.0;
-    }
-    if (state != 1 && bad < 0) bad = k, bad_state = state;
-  }
-  if (bad >= 0)
-    return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED,
-                      "local_correction_solve: subdomain " + std::to_string(marked[bad]) +
-                          (bad_state == 2 ? ": p.Ap <= 0 (the neighbourhood operator is not positive definite)" : ": not converged"));
   return LRBMS_OK;
 }
 

@@ -1,4 +1,4 @@
-// Host-side plumbing shared by the 2D context (lrbms_ctx, lrbms_dev.h) and the 3D context (lrbms3_ctx, lrbms3d.hip): the error
+// Host-side plumbing shared by the 2D context (lrbms_ctx, lrbms_dev.h) and the 3D context (lrbms3_ctx, lrbms3d_dev.h): the error
 // string and the check macros, per-kernel event timing, template uploads and the library-owned side streams.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2617,7 +2617,7 @@ __global__ __launch_bounds__(256) void k_combine_sources(int K, long M, SrcPhi p
 }
 }  // namespace
 
-// The kernel is shape-agnostic: lrbms_combine_sources and lrbms3_combine_sources (lrbms3d.hip) both launch it through this entry,
+// The kernel is shape-agnostic: lrbms_combine_sources and lrbms3_combine_sources (sources3d.hip) both launch it through this entry,
 // each with its own context's error string and cached compute-unit count.
 int launch_combine_sources_base(lrbms_ctx_base* ctx, int* num_cus, int K, long M, const double* phi, const double* x_K, double* y,
                                 hipStream_t st) {

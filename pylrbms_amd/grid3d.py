@@ -1,5 +1,5 @@
 """3D domain-decomposition grid of BASELINE.json config 5 (8 x 8 x 8 subdomains, SWIPDG p = 2): host index layer and
-reference-element tables of the HIP kernels in csrc/lrbms3d.hip.
+reference-element tables of the HIP kernels of the 3D path (csrc/lrbms3d.hip and the other csrc/*3d.hip).
 
 The reference binds the 2D / P1 operators only (python/dune/pylrbms/discretize_elliptic_block_swipdg.py:22-23, ``x[0], x[1]``
 at :195); ``make_grid`` (python/dune/pylrbms/grid.py:18-30) is dimension independent in spirit (cube -> simplices ->

@@ -1,5 +1,7 @@
 """Shared helpers of the 3D / P2 parity tests (BASELINE.json config 5): problems, the CPU oracle for them, and the maps between
 the oracle's generic layouts (global sparse matrices, neighbourhood-compact dense operators) and the product's template layouts."""
+import os
+
 import numpy as np
 
 from oracle.lrbms3d import Discretization3D, Reductor3D
@@ -41,6 +43,21 @@ PROBLEMS = {
     # four subdomains: the kernel instantiations the benchmark times
     'cfg5_template': ([2, 1, 2], 4, [_one, _lam1], [lambda mu: 1.0, lambda mu: mu], np.eye(3), 30, 0.45),
 }
+
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'pylrbms_amd', 'csrc')
+
+
+def sources3d():
+    """The files of the 3D path in csrc/, found by name, in a fixed order: lrbms3d.hip, the other *3d.hip sorted, the shared
+    header last (a function's definition comes before its declaration)."""
+    others = sorted(f for f in os.listdir(CSRC) if f.endswith('3d.hip') and f != 'lrbms3d.hip')
+    return ['lrbms3d.hip'] + others + ['lrbms3d_dev.h']
+
+
+def source3d():
+    """The text of the 3D translation units of csrc/ as one string, for the tests that mirror host logic from the source."""
+    return ''.join(open(os.path.join(CSRC, f)).read() for f in sources3d())
 
 
 UNIT_DOMAIN = ([0.0, 0.0, 0.0], [1.0, 1.0, 1.0])

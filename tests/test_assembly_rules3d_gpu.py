@@ -1,5 +1,5 @@
 """The 3D / P2 offline assembly (k3_asm, k3_scalars, k3_assemble_flux, k3_source_gram and the Dirichlet-correction kernel of
-csrc/lrbms3d.hip) against the CPU oracle across the quadrature degree ``Engine3D(..., data_degree=)``: the degree decides the
+csrc/lrbms3d.hip, sources3d.hip, enrich3d.hip) against the CPU oracle across the quadrature degree ``Engine3D(..., data_degree=)``: the degree decides the
 reduction length of every k3_asm operator (single partial chunks of ASM_KC points up to 23 chunks with a tail,
 tests/test_quadrature_cases_host.py) and every offset of the sample records.  Data: tests/quadrature_cases.py (Q = 3 components
 that oscillate inside every element; the host tests assert that they tell the degrees apart).

@@ -2,7 +2,7 @@
 
 Online enrichment solves its corrector problems with a solver of its own on each path: in 2D ``k_hood_pcg`` (csrc/enrich.hip, one
 workgroup per marked subdomain), in 3D the batched multi-kernel PCG ``k3l_*`` behind ``lrbms3_local_correction_solve``
-(csrc/lrbms3d.hip).  Both are plain PCG from x_0 = 0 with a pure block-Jacobi preconditioner.  A converged corrector does not
+(csrc/enrich3d.hip).  Both are plain PCG from x_0 = 0 with a pure block-Jacobi preconditioner.  A converged corrector does not
 depend on that preconditioner, so this module does what tests/test_pcg_iterates_gpu.py does for the other solvers: the raw export
 is called with max_iter = k, it returns LRBMS_E_NOT_CONVERGED and leaves x_k (its part on the marked subdomain) and
 info = (k, |r_k| / |b|) behind, and tests/pcg_ref.py computes the same x_k in NumPy.

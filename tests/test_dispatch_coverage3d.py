@@ -4,19 +4,18 @@
 EVEN> for both forms where R and C are even and picks EVEN = true when N is even too.  The timing names of the 3D kernels do not
 carry the tile shape, so this mirror of the host's choice stands in for name assertions: a new instantiation, a dead one, or a
 dropped cell fails here instead of going untested on the GPU."""
-import os
 import re
 
+from common3d import source3d
 from test_dispatch_parity3d_gpu import CELLS
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'pylrbms_amd', 'csrc', 'lrbms3d.hip')
 SQUARE = ('AAA', 'SYS', 'NC', 'CPL', 'BB')
 KINDS = SQUARE + ('AB',)
 
 
 def listed_cases():
     """{kind: [(R, C), ...]} from the PGCASE lists of dispatch_pg."""
-    src = open(SRC).read()
+    src = source3d()
     body = re.search(r'int dispatch_pg\(.*?\n}\n', src, re.S).group(0)
     lists = dict(re.findall(r'if constexpr \(KIND (==|!=) G_AB\) \{([^}]*)\}', body))
     assert set(lists) == {'==', '!='}, 'dispatch_pg: expected one PGCASE list for AB and one for the other kinds'

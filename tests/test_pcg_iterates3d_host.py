@@ -9,7 +9,6 @@
   full-order blocks through ``common3d.oracle_assembled``, its mass matrix): every restated preconditioner is SPD, the reference
   PCG of every cell type converges to the direct solve, and every mutant of a cell misses the reference at k = MUTANT_K by more
   than MUTANT_FLOOR while the reference ratio there is still >= MIN_RATIO."""
-import os
 import re
 
 import numpy as np
@@ -22,13 +21,12 @@ import pcg_ref
 import test_pcg_iterates3d_gpu as cells
 from test_pcg_iterates_gpu import MIN_RATIO, MUTANT_FLOOR, TOL_X
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'pylrbms_amd', 'csrc', 'lrbms3d.hip')
 LDS_DEFAULT = 64 * 1024
 K2 = cells.MUTANT_K
 
 
 def _src():
-    return open(SRC).read()
+    return c3.source3d()
 
 
 # ------------------------------------------------------------------------------------------------ the dispatch mirror

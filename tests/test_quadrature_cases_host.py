@@ -7,7 +7,6 @@
   the case lists reach the sizes they claim (1 point, 16 points, 4 edge points, coupling > inner);
 * the 3D degrees give the reductions of k3_asm a length shorter than one staged chunk, an exact multiple of it and several
   chunks with a tail."""
-import os
 import re
 
 import numpy as np
@@ -118,9 +117,8 @@ def test_spec3d_layout(degree):
 
 # -------------------------------------------------------------------------------------------------------------- chunking
 def _asm_kc():
-    here = os.path.dirname(os.path.abspath(__file__))
-    with open(os.path.join(here, '..', 'pylrbms_amd', 'csrc', 'lrbms3d.hip')) as fh:
-        return int(re.search(r'constexpr int ASM_KC = (\d+);', fh.read()).group(1))
+    from common3d import source3d
+    return int(re.search(r'constexpr int ASM_KC = (\d+);', source3d()).group(1))
 
 
 def test_degrees_cover_the_chunk_forms_of_k3_asm():
