@@ -95,3 +95,125 @@ class ParabolicReduced3D:
         tdnc2 = np.array([self.rd.local_terms(self.split(v), mu)[0] for v in du]).T
         tr2 = np.array([np.linalg.solve(M, A @ v) @ (A @ v) for v in du])
         return combine(self.o, mu, self.dt, terms[:, 0].T, terms[:, 1].T, terms[:, 2].T, tr2, tdnc2)
+
+
+# ------------------------------------------------------------------------ the side kernels of the parabolic path, one by one
+# Plain restatements of lrbms3_project_mass, lrbms3_mass_inverse_norm2, lrbms3_reduced_time_residual and the reduced stepper for
+# tests/test_parabolic3d_dispatch_gpu.py.  Each takes one switch per property of the kernel it restates: with a switch thrown it
+# is a deliberately wrong ("mutant") reference, which tests/test_parabolic3d_dispatch_host.py shows to be more than 1e-6 away
+# from the right one at the cells of the GPU test -- so a kernel with that fault could not pass there.
+SELF = 3                                   # the self slot of the 7-slot layout
+WAVES = 8                                  # k3p_project_mass: waves per workgroup, one element per wave at a time
+CHUNK = 256                                # k3p_mass_inv_norm2: vectors per trip of its l0 loop = threads per workgroup
+
+
+def element_mass_blocks(o, s):
+    """The 10 x 10 element blocks [n_T, 10, 10] of the oracle's mass matrix on subdomain s (it is element-block-diagonal)."""
+    dofs = o.dofs_of(s)
+    Ms = o.M.tocsr()[dofs][:, dofs].toarray()
+    nT = o.n // 10
+    blk = Ms.reshape(nT, 10, nT, 10)
+    own = blk[np.arange(nT), :, np.arange(nT), :]
+    assert np.count_nonzero(Ms) == np.count_nonzero(own), 'the mass matrix couples elements'
+    return own
+
+
+def project_mass(o, V, elem_type=None, swap_types=None, drop_tail=False, drop_cross=False):
+    """lrbms3_project_mass: M_red [S, N, N] = sum_e V_e^T M_e V_e from the oracle's ``o.M``, accumulated in np.longdouble.
+    Mutants: ``swap_types`` = (a, b) with ``elem_type`` [n_T]: the elements of type a take the block of the first element of type
+    b; ``drop_tail``: the elements e >= 8 (n_T // 8) are left out (the partial last round of the 8 waves); ``drop_cross``: the
+    16 x 16 tiles off the diagonal (rt != ct) stay zero."""
+    V = np.asarray(V, dtype=np.float64)
+    S, n, N = V.shape
+    nT = n // 10
+    out = np.zeros((S, N, N), dtype=np.longdouble)
+    for s in range(S):
+        TM = element_mass_blocks(o, s).astype(np.longdouble)
+        if swap_types is not None:
+            a, b = swap_types
+            et = np.asarray(elem_type)
+            TM[et == a] = TM[np.flatnonzero(et == b)[0]]
+        Ve = V[s].reshape(nT, 10, N).astype(np.longdouble)
+        last = WAVES * (nT // WAVES) if drop_tail else nT
+        Z = np.einsum('eij,ejl->eil', TM[:last], Ve[:last])
+        out[s] = np.einsum('eik,eil->kl', Ve[:last], Z)
+    if drop_cross:
+        tile = np.arange(N) // 16
+        out[:, tile[:, None] != tile[None, :]] = 0.0
+    return out
+
+
+def chunk_of(L, l):
+    """(Lc, G) of column l in a call of k3p_mass_inv_norm2 with L vectors: its trip of the l0 loop holds Lc <= 256 vectors,
+    G = 256 // Lc threads share one vector, thread g takes the elements g, g + G, ..."""
+    l0 = CHUNK * (l // CHUNK)
+    Lc = min(L - l0, CHUNK)
+    return Lc, CHUNK // Lc
+
+
+def mass_inverse_norm2(o, Y, first_trip_only=False, drop_group_tail=False):
+    """lrbms3_mass_inverse_norm2: out [S, L] = y_s^T M_s^-1 y_s for the columns of Y [S, n, L], by a sparse LU of ``o.M``.
+    Mutants: ``first_trip_only``: the columns >= 256 stay zero (the l0 loop ends after one trip); ``drop_group_tail``: the
+    elements e >= G (n_T // G) of a column are left out (the partial last round of the column's G threads)."""
+    Y = np.asarray(Y, dtype=np.float64)
+    S, n, L = Y.shape
+    nT = n // 10
+    flat = Y.reshape(S * n, L)
+    X = spla.splu(o.M.tocsc()).solve(flat)
+    per_elem = (flat * X).reshape(S, nT, 10, L).sum(axis=2)              # [S, n_T, L]: M is element-block-diagonal
+    if drop_group_tail:
+        for l in range(L):
+            G = chunk_of(L, l)[1]
+            per_elem[:, G * (nT // G):, l] = 0.0
+    out = per_elem.sum(axis=1)
+    if first_trip_only:
+        out[:, CHUNK:] = 0.0
+    return out
+
+
+def reduced_operator_rows(B, nbr, theta, dU, drop_slot=None):
+    """y [L, S, N]: y_s = sum_slot sum_q theta_q B_q[s, slot] dU[nbr[s, slot]] over the present slots (mutant: without ``drop_slot``)."""
+    B, dU = np.asarray(B, dtype=np.float64), np.asarray(dU, dtype=np.float64)
+    nbr = np.asarray(nbr).reshape(-1, 7)
+    y = np.zeros_like(dU)
+    for s in range(dU.shape[1]):
+        for slot in range(7):
+            t = int(nbr[s, slot])
+            if t < 0 or slot == drop_slot:
+                continue
+            y[:, s] += dU[:, t] @ np.einsum('q,qij->ij', np.asarray(theta, dtype=np.float64), B[:, s, slot]).T
+    return y
+
+
+def reduced_time_residual(B, M_red, nbr, theta, dU, keep=None, drop_slot=None, diagonal_inverse=False):
+    """lrbms3_reduced_time_residual: out [L, S] = y_s^T M_red[s]^-1 y_s on the kept indices (``keep`` [S, N] bool: False on the
+    zero-padded unknowns of a ragged basis), dense NumPy per subdomain.  Mutants: ``drop_slot`` (one neighbour slot left out of
+    y), ``diagonal_inverse`` (the inverse of the diagonal of M_red in place of M_red^-1)."""
+    M_red = np.asarray(M_red, dtype=np.float64)
+    y = reduced_operator_rows(B, nbr, theta, dU, drop_slot)
+    L, S, N = y.shape
+    keep = np.ones((S, N), dtype=bool) if keep is None else np.asarray(keep, dtype=bool)
+    out = np.zeros((L, S))
+    for s in range(S):
+        ks = keep[s]
+        Ms = M_red[s][np.ix_(ks, ks)]
+        ys = y[:, s][:, ks]
+        out[:, s] = np.einsum('li,li->l', ys, ys / np.diag(Ms) if diagonal_inverse else np.linalg.solve(Ms, ys.T).T)
+    return out
+
+
+def reduced_stepping(A, M_red, rhs, dt, nt, keep=None, mass_in_rhs=True):
+    """lrbms3_reduced_implicit_euler from zero: (M + dt A) u_{k+1} = M u_k + dt rhs on the kept unknowns, dense; A [S N, S N] the
+    reduced operator at the parameter, M_red [S, N, N] -> u [nt + 1, S N] (zero on the unknowns not kept).
+    Mutant: ``mass_in_rhs`` False (every step starts from zero: the right-hand side without M u_k)."""
+    M_red = np.asarray(M_red, dtype=np.float64)
+    S, N = M_red.shape[:2]
+    M = np.zeros((S * N, S * N))
+    for s in range(S):
+        M[s * N:(s + 1) * N, s * N:(s + 1) * N] = M_red[s]
+    keep = np.ones(S * N, dtype=bool) if keep is None else np.asarray(keep, dtype=bool).reshape(S * N)
+    Ak, Mk, bk = np.asarray(A)[np.ix_(keep, keep)], M[np.ix_(keep, keep)], np.asarray(rhs).reshape(S * N)[keep]
+    u = np.zeros((nt + 1, S * N))
+    for k in range(nt):
+        u[k + 1, keep] = np.linalg.solve(Mk + dt * Ak, (Mk @ u[k, keep] if mass_in_rhs else 0.0) + dt * bk)
+    return u
