@@ -312,6 +312,36 @@ int lrbms3_fom_implicit_euler(lrbms3_ctx* ctx, int32_t Q, const double* theta, d
                               const double* A_cpl, const double* b, double* work, double* U, double rtol, int32_t max_iter,
                               double* info, void* stream);
 
+/* Batched full-order trajectories (2D: lrbms_fom_implicit_euler_batch): 1 <= nmu <= 64 parameters per call.
+ * Column m runs
+ *     (M + dt A(theta_m)) u_{k+1} = M u_k + dt sum_j phi[m][k+1][j] b_K[j],   k = 0 .. nt-1     (K = 1, phi = 1, b_K = b: the plain source)
+ * in panels of at most 16 columns, panels outermost: a panel runs its whole trajectory, then the next one starts; its theta table,
+ * pre-multiplied by dt, is one kernel argument for all steps.  Every step is a CG warm-started in place (x = slab k+1 preset to
+ * u_k) with the panel kernels of lrbms3_fom_solve_batch on the step operator (the element's TM joins its own block in the matvec).
+ * ONE preconditioner per call, both levels on M + dt A(theta_bar) at the mean theta of the call's columns (summed in column
+ * order): the inverse 10 x 10 element blocks and the coarse level of lrbms3_fom_coarse_space, private to the call -- the inverse
+ * that lrbms3_fom_precond_keep holds is neither read nor replaced, and the result does not depend on the call history.
+ *   theta [nmu][Q] host; phi [nmu][nt+1][K] DEVICE (row k: the time of step k; row 0 is not read); b_K [K][S][n];
+ *   U [nt+1][S][n][nmu] (parameter fastest): slab 0 is input (the initial values per column, read and never written), slabs
+ *   1..nt are written; nothing outside U and work is written.  work: lrbms3_fom_implicit_euler_batch_work_size doubles (-1 for nmu
+ *   outside [1, 64] or without a mesh).
+ * A step of a panel iterates until its worst column is at or below rtol relative to |M u_k + dt sum_j phi b_j| of that column (the
+ * full right-hand side, as lrbms3_fom_implicit_euler, not the start residual); the host reads r.r per column every 16 iterations.
+ * A column whose full right-hand side is exactly zero has no say and keeps u_{k+1} = u_k bit for bit.  max_iter caps ONE step of
+ * ONE panel and is honoured exactly (nt = 1, max_iter = k: U[1] - U[0] is the k-th PCG iterate of every column).  After a miss
+ * that panel stops at that step (its later slabs are not written), the other panels still run and the call returns
+ * LRBMS_E_NOT_CONVERGED.  info (host, may be NULL) = (CG iterations summed over panels and steps, worst final ratio).
+ * Fixed summation orders, no atomics: repeat calls give the same bits, equal columns give equal bits wherever they stand.
+ * LRBMS_E_INVALID before any launch (U[1..] and work untouched): S_ext != S, Q outside [1, 8], K outside [1, 64], nmu outside
+ * [1, 64], nt < 1, dt <= 0, rtol <= 0, max_iter < 1, a null pointer (info excepted).
+ * lrbms3_fom_implicit_euler_batch_panel_info: out [4][2] host = (iterations summed over the steps, worst ratio) per panel of the
+ * last call on this context, zeros for panels it did not have. */
+int64_t lrbms3_fom_implicit_euler_batch_work_size(lrbms3_ctx* ctx, int32_t nmu);
+int lrbms3_fom_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta, double dt, int32_t nt,
+                                    const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                    double* U, double rtol, int32_t max_iter, double* info, void* stream);
+int lrbms3_fom_implicit_euler_batch_panel_info(lrbms3_ctx* ctx, double* out);
+
 /* The reduced counterpart on the projected operators: (M_red + dt sum_q theta_q B_sys_q) u_{k+1} = M_red u_k + dt rhs_red.
  *   B_sys [Q][S][7][N][N], rhs_red [S][N] as the pass writes them, M_red [S][N][N] (lrbms3_project_mass); U [nt+1][S][N]
  *   (U[0] input); work: lrbms3_reduced_implicit_euler_work_size doubles; info as above.  The step operator and its inverse

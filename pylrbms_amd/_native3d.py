@@ -62,6 +62,11 @@ SIGNATURES3 = {
     'lrbms3_fom_implicit_euler_work_size': (c_i64, [c_vp]),
     'lrbms3_fom_implicit_euler': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32,
                                                  _P_DBL, c_vp]),
+    # batched full-order trajectories
+    'lrbms3_fom_implicit_euler_batch_work_size': (c_i64, [c_vp, c_i32]),
+    'lrbms3_fom_implicit_euler_batch': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                       c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms3_fom_implicit_euler_batch_panel_info': (ctypes.c_int, [c_vp, _P_DBL]),
     'lrbms3_reduced_implicit_euler_work_size': (c_i64, [c_vp, c_i32]),
     'lrbms3_reduced_implicit_euler': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
                                                      c_i32, _P_DBL, c_vp]),
@@ -457,6 +462,42 @@ class Native3DContext(_native.ContextBase):
                                                 float(rtol), int(max_iter), info, self._stream())
         self._check(rc, 'lrbms3_fom_implicit_euler')
         return U, (int(info[0]), float(info[1]))
+
+    def fom_implicit_euler_batch(self, thetas, dt, nt, A_diag, A_cpl, b_K, phi, U0=None, rtol=1e-10, max_iter=50000, work=None):
+        """Column m: (M + dt A(thetas[m])) u_{k+1} = M u_k + dt sum_j phi[m, k + 1, j] b_K[j], nt steps, for nmu <= 64 parameters in
+        one call (``lrbms3_fom_implicit_euler_batch``: panels of 16 columns on the matrix cores, one two-level preconditioner at the
+        mean theta) -> (U [nt + 1, S, n, nmu], info).  thetas [nmu, Q] host; phi [nmu, nt + 1, K] host or device; b_K [K, S, n];
+        U0 None (zeros), [S, n] (every column) or [S, n, nmu].  ``info``: ``iterations`` (summed over panels and steps),
+        ``relative_residual`` (worst final ratio), ``panel_iterations``."""
+        Q, S, K, nt = int(A_diag.shape[0]), self.S, int(b_K.shape[0]), int(nt)
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, Q)
+        ph = self._dev2(phi, (nmu, nt + 1, K), 'phi')
+        size = int(self.lib.lrbms3_fom_implicit_euler_batch_work_size(self.handle, nmu))
+        if size < 0:
+            raise NativeError('lrbms3_fom_implicit_euler_batch: nmu = {} is not in 1..64'.format(nmu))
+        if work is None:
+            work = self.empty(size)
+        elif work.numel() < size:
+            raise NativeError('work buffer too small')
+        U = self.empty(max(nt, 0) + 1, S, self.n, nmu)
+        if U0 is None:
+            U[0].zero_()
+        else:
+            U[0].copy_(U0.reshape(S, self.n, -1))                # [S, n, 1] broadcasts over the columns
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_fom_implicit_euler_batch(self.handle, Q, K, nmu, th.ctypes.data_as(_P_DBL), float(dt), nt,
+                                                      self._ptr(A_diag, (Q, S, self.n_T, 5, 100), 'A_diag'),
+                                                      self._ptr(A_cpl, (Q, S, 6, self.ncf, 100), 'A_cpl'),
+                                                      self._ptr(b_K, (K, S, self.n), 'b_K'), c_vp(ph.data_ptr()),
+                                                      c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), info,
+                                                      self._stream())
+        panels = (c_dbl * 8)()
+        self.lib.lrbms3_fom_implicit_euler_batch_panel_info(self.handle, panels)
+        self._check(rc, 'lrbms3_fom_implicit_euler_batch')
+        return U, {'iterations': int(info[0]), 'relative_residual': float(info[1]),
+                   'panel_iterations': [int(v) for v in list(panels)[0:2 * ((nmu + 15) // 16):2]]}
 
     def reduced_implicit_euler(self, Q, theta, dt, nt, B_sys, M_red, rhs_red, U0=None, rtol=1e-12, max_iter=20000, work=None):
         """(M_red + dt sum_q theta_q B_sys_q) u_{k+1} = M_red u_k + dt rhs_red -> U [nt + 1, S, N] (U[0] = U0, default zero),

@@ -4149,17 +4149,24 @@ struct Fb3Row {
 // the matrix cores from there; inside a subdomain the block towards the lower-index neighbour is that element's block read
 // transposed from the LDS (k3f_matvec's symmetric read: the second reader finds it in the XCD's L2).  The column's theta_q
 // multiplies the direction operand, every (block, q) adds three k-steps to the ONE accumulator tile of the element.
+// MASS: the step operator of the implicit Euler, M + A(theta) with theta pre-multiplied by dt (lrbms3_fom_implicit_euler_batch).
+// The element's mass block TM, unweighted, joins its own block: three more k-steps on the same accumulator tile whose direction
+// operand is the plain pv[0][ks].  The TM blocks of all six element types are staged in the LDS once per workgroup.
+template <bool MASS>
 __global__ __launch_bounds__(256) void k3fb_matvec(T3 t, int nbx, int Q, int P, TB th, const double* __restrict__ A_diag,
                                                    const double* __restrict__ A_cpl, const double* __restrict__ p,
                                                    double* __restrict__ y, double* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) double blk[4][5][104];
   __shared__ double ths[128];
   __shared__ double red[4][16];
+  __shared__ double tms[MASS ? 600 : 1];
   int s, bx;
   if (!xcd_block(nbx, t.S, bx, s)) return;
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (tid < 128) ths[tid] = th.v[tid >> 3][tid & 7];
+  if (MASS)
+    for (int i = tid; i < 600; i += 256) tms[i] = t.TM[i];
   __syncthreads();
   const bool col = li < P;
   const long qd = (long)t.S * t.nT * 500, qc = (long)t.S * 6 * t.ncf * 100;
@@ -4212,6 +4219,15 @@ __global__ __launch_bounds__(256) void k3fb_matvec(T3 t, int nbx, int Q, int P, 
         pv[b][ks] = (row.src[b] && col && k < 10) ? row.pb[b][k * 16 + li] : 0.0;
       }
     d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
+    if (MASS) {
+      const double* tm = tms + t.elem_type[e] * 100;          // wave-uniform; TM [i][j] as k3p_fom_add_mass adds it to the own block
+#pragma unroll
+      for (int ks = 0; ks < 3; ++ks) {
+        const int k = lk + 4 * ks, kk = k < 10 ? k : 9;
+        const double mv = tm[ii * 10 + kk];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64((li < 10 && k < 10) ? mv : 0.0, pv[0][ks], acc, 0, 0, 0);
+      }
+    }
     for (int q = 0; q < Q; ++q) {
       double2 a2[5];
 #pragma unroll
@@ -4449,17 +4465,35 @@ struct FomBatch3 {
   }
 };
 
-// PCG on the panel of P <= 16 columns m0 .. m0 + P - 1 of the call; the host reads r.r per column every 16 iterations (fom_cg)
-// and stops when the worst column with a nonzero right-hand side is at or below rtol relative to |b_m|.
-int fomb3_panel(lrbms3_ctx* ctx, hipStream_t st, const FomWork& w, const FomBatch3& b, int Q, int P, int nmu, int m0, const TB& th,
-                const double* A_diag, const double* A_cpl, int K, const double* phi, const double* b_K, int nc, const double* A1inv,
-                double* X, double rtol, int max_iter, int* its, double* rel_out) {
+// The panel's operator: the elliptic one, or (mass) the step operator M + A(theta) with theta pre-multiplied by dt
+struct Fb3Op {
+  int Q, P, nmu, m0;
+  TB th;
+  const double *A_diag, *A_cpl;
+  bool mass;
+};
+
+void fomb3_launch_matvec(lrbms3_ctx* ctx, hipStream_t st, const FomWork& w, const Fb3Op& op, const double* p, double* y, double* part) {
   const T3& t = ctx->t;
-  const long S = t.S, total = S * t.n, nblk = w.nblk, M = (long)nc * S;
-  const int nbx = w.nbx;
+  if (op.mass)
+    hipLaunchKernelGGL(k3fb_matvec<true>, dim3(xcd_grid(w.nbx, t.S)), dim3(256), 0, st, t, w.nbx, op.Q, op.P, op.th, op.A_diag, op.A_cpl, p, y,
+                       part);
+  else
+    hipLaunchKernelGGL(k3fb_matvec<false>, dim3(xcd_grid(w.nbx, t.S)), dim3(256), 0, st, t, w.nbx, op.Q, op.P, op.th, op.A_diag, op.A_cpl, p, y, part);
+}
+
+// PCG on the panel of P <= 16 columns m0 .. m0 + P - 1 of the call, shared by lrbms3_fom_solve_batch and the steps of
+// lrbms3_fom_implicit_euler_batch: on entry X holds the start values and b.r the start residual.  The host reads r.r per column
+// every 16 iterations (fom_cg) and stops when the worst column with a nonzero reference is at or below rtol.  The reference per
+// column is |r_0| (ref_part == nullptr: the right-hand side, the start value being zero) or the sum of the partials
+// ref_part [nblk][16] (the step's full right-hand side, left by k3fb_step_residual); `name` is the caller in the error texts.
+int fomb3_panel_run(lrbms3_ctx* ctx, hipStream_t st, const FomWork& w, const FomBatch3& b, const Fb3Op& op, int nc, const double* A1inv,
+                    double* X, const double* ref_part, double rtol, int max_iter, int* its, double* rel_out, const char* name) {
+  const T3& t = ctx->t;
+  const long S = t.S, nblk = w.nblk, M = (long)nc * S;
+  const int nbx = w.nbx, P = op.P, nmu = op.nmu, m0 = op.m0;
   const double* Phi = ctx->fom_phi;
   const dim3 grid(nbx, S);
-  const unsigned gv = (unsigned)((total * 16 + 255) / 256);
   auto tail = [&](double* rz) {                      // coarse step and r.z per column for the residual k3fb_update has just written
     if (nc > 0) {
       hipLaunchKernelGGL(k3fb_coarse_r0, dim3((unsigned)((M * 16 + 255) / 256)), dim3(256), 0, st, (int)S, nbx, nc, b.pr0, b.r0);
@@ -4467,14 +4501,15 @@ int fomb3_panel(lrbms3_ctx* ctx, hipStream_t st, const FomWork& w, const FomBatc
     }
     hipLaunchKernelGGL(k3fb_scalars, dim3(16), dim3(256), 0, st, b.prz, nblk, b.prc, nc > 0 ? M : 0L, rz);
   };
-  hipLaunchKernelGGL(k3fb_rhs, dim3(gv), dim3(256), 0, st, total, K, P, nmu, m0, phi, b_K, b.r, X);
   hipLaunchKernelGGL(k3fb_update, grid, dim3(256), 0, st, t, P, nmu, m0, 1, 0, b.scal, w.Dinv, b.p, b.y, X, b.r, b.z, b.prz, b.prr, nc,
                      Phi, b.pr0);
   tail(b.scal);
-  hipLaunchKernelGGL(k3fb_scalars, dim3(16), dim3(256), 0, st, b.prr, nblk, (const double*)nullptr, 0L, b.scal + 64);
+  hipLaunchKernelGGL(k3fb_scalars, dim3(16), dim3(256), 0, st, ref_part ? ref_part : b.prr, nblk, (const double*)nullptr, 0L, b.scal + 64);
+  if (ref_part) hipLaunchKernelGGL(k3fb_scalars, dim3(16), dim3(256), 0, st, b.prr, nblk, (const double*)nullptr, 0L, b.scal + 48);
   LRBMS_LAUNCH_CHECK(ctx);
   double bb[16], rr[16];
   LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(bb, b.scal + 64, sizeof(bb), hipMemcpyDeviceToHost, st));
+  if (ref_part) LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(rr, b.scal + 48, sizeof(rr), hipMemcpyDeviceToHost, st));
   LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
   auto worst = [&](const double* cur) {
     double wr = 0.0;
@@ -4488,9 +4523,9 @@ int fomb3_panel(lrbms3_ctx* ctx, hipStream_t st, const FomWork& w, const FomBatc
   };
   *its = 0;
   *rel_out = 0.0;
-  double rel = worst(bb);                            // 1, or 0 if every right-hand side of the panel is zero
+  double rel = worst(ref_part ? rr : bb);            // 1 from a zero start value; 0 if every reference or every start residual is zero
   if (rel == 0.0) return LRBMS_OK;
-  if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve_batch: NaN right-hand side");
+  if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN right-hand side");
   int it = 0;
   const int check = 16;
   while (it < max_iter) {
@@ -4498,7 +4533,7 @@ int fomb3_panel(lrbms3_ctx* ctx, hipStream_t st, const FomWork& w, const FomBatc
       const int cur = it & 1;                        // slot of the current r.z (the update of this iteration writes the other one)
       hipLaunchKernelGGL(k3fb_dir, dim3((unsigned)((t.n * 16 + 255) / 256), (unsigned)S), dim3(256), 0, st, P, it == 0 ? 1 : 0, cur, b.scal,
                          b.z, b.p, t.n, nc, Phi, b.y0);
-      hipLaunchKernelGGL(k3fb_matvec, dim3(xcd_grid(nbx, (int)S)), dim3(256), 0, st, t, nbx, Q, P, th, A_diag, A_cpl, b.p, b.y, b.ppy);
+      fomb3_launch_matvec(ctx, st, w, op, b.p, b.y, b.ppy);
       hipLaunchKernelGGL(k3fb_scalars, dim3(16), dim3(256), 0, st, b.ppy, nblk, (const double*)nullptr, 0L, b.scal + 32);
       hipLaunchKernelGGL(k3fb_update, grid, dim3(256), 0, st, t, P, nmu, m0, 0, cur, b.scal, w.Dinv, b.p, b.y, X, b.r, b.z, b.prz, b.prr,
                          nc, Phi, b.pr0);
@@ -4509,12 +4544,21 @@ int fomb3_panel(lrbms3_ctx* ctx, hipStream_t st, const FomWork& w, const FomBatc
     LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(rr, b.scal + 48, sizeof(rr), hipMemcpyDeviceToHost, st));
     LRBMS_HIP_CHECK(ctx, hipStreamSynchronize(st));
     rel = worst(rr);
-    if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_solve_batch: NaN residual");
+    if (!(rel == rel)) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, std::string(name) + ": NaN residual");
     if (rel <= rtol) break;
   }
   *its = it;
   *rel_out = rel;
   return LRBMS_OK;
+}
+
+// A panel of lrbms3_fom_solve_batch: the right-hand sides, x = 0, then the PCG relative to |b_m|
+int fomb3_panel(lrbms3_ctx* ctx, hipStream_t st, const FomWork& w, const FomBatch3& b, const Fb3Op& op, int K, const double* phi,
+                const double* b_K, int nc, const double* A1inv, double* X, double rtol, int max_iter, int* its, double* rel_out) {
+  const long total = (long)ctx->t.S * ctx->t.n;
+  hipLaunchKernelGGL(k3fb_rhs, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, st, total, K, op.P, op.nmu, op.m0, phi, b_K, b.r,
+                     X);
+  return fomb3_panel_run(ctx, st, w, b, op, nc, A1inv, X, nullptr, rtol, max_iter, its, rel_out, "fom_solve_batch");
 }
 
 }  // namespace
@@ -4559,13 +4603,12 @@ int lrbms3_fom_solve_batch(lrbms3_ctx* ctx, int32_t Q, int32_t nmu, const double
   for (int i = 0; i < 8; ++i) ctx->fomb_panels[i] = 0.0;
   for (int m0 = 0; m0 < nmu; m0 += 16) {
     const int P = nmu - m0 < 16 ? nmu - m0 : 16;
-    TB th;
+    Fb3Op op{Q, P, nmu, m0, {}, A_diag, A_cpl, false};
     for (int c = 0; c < 16; ++c)
-      for (int q = 0; q < 8; ++q) th.v[c][q] = (c < P && q < Q) ? theta[(long)(m0 + c) * Q + q] : 0.0;
+      for (int q = 0; q < 8; ++q) op.th.v[c][q] = (c < P && q < Q) ? theta[(long)(m0 + c) * Q + q] : 0.0;
     int it = 0;
     double rel = 0.0;
-    if (int rc = fomb3_panel(ctx, st, w, b, Q, P, nmu, m0, th, A_diag, A_cpl, K, phi, b_K, nc, A1inv, X, rtol, max_iter, &it, &rel))
-      return rc;
+    if (int rc = fomb3_panel(ctx, st, w, b, op, K, phi, b_K, nc, A1inv, X, rtol, max_iter, &it, &rel)) return rc;
     ctx->fomb_panels[m0 / 16 * 2] = it;
     ctx->fomb_panels[m0 / 16 * 2 + 1] = rel;
     if (it > its_max) its_max = it;
@@ -5089,6 +5132,165 @@ int lrbms3_fom_implicit_euler_src(lrbms3_ctx* ctx, int32_t Q, int32_t K, const d
                          hipLaunchKernelGGL(k3p_fom_rhs_src, dim3(nbx, t.S), dim3(256), 0, st, t, dt, uk, K, (long)t.S * t.n,
                                             phi + (long)(step + 1) * K, b_K, Ku, rhs, part);
                        });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------- batched trajectories
+// lrbms3_fom_implicit_euler_batch (2D: lrbms_fom_implicit_euler_batch): column m runs the implicit Euler
+//   (M + dt A(theta_m)) u_{k+1} = M u_k + dt sum_j phi[m][k+1][j] b_K[j],   k = 0 .. nt-1,
+// on U [nt+1][S][n][nmu] (parameter fastest; slab 0 is input).  Panels of <= 16 columns, panels outermost: a panel runs its whole
+// trajectory with one theta table (pre-multiplied by dt), every step a warm-started PCG of the panel kernels of
+// lrbms3_fom_solve_batch on the step operator (k3fb_matvec<true>), relative to the step's full right-hand side per column.  Per step
+//   k3fb_load            u_k of the panel's columns -> b.p [S n][16] and the next slab (x = u_k)
+//   k3fb_matvec<true>     y = (M + dt A(theta_c)) u_k
+//   k3fb_step_residual   r = M u_k + dt sum_j phi b_j - y, partials of |M u_k + dt sum_j phi b_j|^2
+// then fomb3_panel_run (its first direction overwrites b.p, which the two kernels before it have consumed).  ONE preconditioner
+// per call, both levels on M + dt A(theta_bar) at the call mean, for all panels and steps.
+namespace {
+
+// the columns m0 .. m0 + P - 1 of the slab Uk [S n][nmu] -> the panel vector uk [S n][16] and the same columns of the next slab X
+__global__ __launch_bounds__(256) void k3fb_load(long nv, int P, int nmu, int m0, const double* __restrict__ Uk, double* __restrict__ X,
+                                                 double* __restrict__ uk) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x, g = i >> 4;
+  const int c = (int)(i & 15);
+  if (g >= nv || c >= P) return;
+  const double v = Uk[g * nmu + m0 + c];
+  X[g * nmu + m0 + c] = v;
+  uk[i] = v;
+}
+
+// r = TM u_k + dt sum_j phi_c[j] b_j - y per column (y = (M + dt A(theta_c)) u_k from k3fb_matvec<true>), the arithmetic of
+// k3p_fom_rhs_src: the TM row sum in its order, the source sum as fma from the first product.  phi: the table [nmu][rows][K] offset
+// to the step's row, so column c reads phi + (m0 + c) phi_stride.  Workgroups and lanes as in k3fb_update: one wave per element at
+// a time, lane (column li, rows lk + 4 ks).  part [S nbx][16] = |TM u_k + dt sum_j phi b_j|^2 over the workgroup's elements.
+__global__ __launch_bounds__(256) void k3fb_step_residual(T3 t, double dt, int K, int P, int m0, long phi_stride,
+                                                          const double* __restrict__ phi, const double* __restrict__ b_K,
+                                                          const double* __restrict__ uk, const double* __restrict__ y,
+                                                          double* __restrict__ r, double* __restrict__ part) {
+  __shared__ double red[4][16];
+  const int s = blockIdx.y, bx = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool col = li < P;
+  const long SN = (long)t.S * t.n;
+  const double* ph = phi + (long)(m0 + (col ? li : 0)) * phi_stride;
+  double ff = 0.0;
+  const int e1 = (bx + 1) * FOM_EPB < t.nT ? (bx + 1) * FOM_EPB : t.nT;
+  for (int e = bx * FOM_EPB + wave; e < e1; e += 4) {
+    if (!col) continue;
+    const long g0 = (long)s * t.n + e * 10;
+    double ue[10];
+#pragma unroll
+    for (int j = 0; j < 10; ++j) ue[j] = uk[(g0 + j) * 16 + li];
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) {
+      const int i = lk + 4 * ks;
+      if (i >= 10) continue;
+      const long d = g0 + i;
+      const double* tm = t.TM + t.elem_type[e] * 100 + i * 10;
+      double acc = 0.0;
+#pragma unroll
+      for (int j = 0; j < 10; ++j) acc += tm[j] * ue[j];
+      double bs = ph[0] * b_K[d];
+      for (int j = 1; j < K; ++j) bs = __fma_rn(ph[j], b_K[(long)j * SN + d], bs);
+      const double f = acc + dt * bs;
+      r[d * 16 + li] = f - y[d * 16 + li];
+      ff += f * f;
+    }
+  }
+  ff += __shfl_xor(ff, 16);
+  ff += __shfl_xor(ff, 32);
+  if (lk == 0) red[wave][li] = ff;
+  __syncthreads();
+  if (tid < 16) part[((long)s * gridDim.x + bx) * 16 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t lrbms3_fom_implicit_euler_batch_work_size(lrbms3_ctx* ctx, int32_t nmu) {
+  const int64_t base = lrbms3_fom_solve_batch_work_size(ctx, nmu);
+  if (base < 0) return -1;
+  const T3& t = ctx->t;
+  return base + 16 * (int64_t)t.S * ((t.nT + FOM_EPB - 1) / FOM_EPB);          // + the partials of |M u_k + dt sum_j phi b_j|^2
+}
+
+int lrbms3_fom_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta, double dt, int32_t nt,
+                                    const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                    double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || nmu < 1 || nmu > 64 || K < 1 || K > 64 || nt < 1 || max_iter < 1 || !(rtol > 0.0) || !(dt > 0.0))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch: bad Q / nmu / K / nt / dt / max_iter / rtol");
+  if (!theta || !A_diag || !A_cpl || !b_K || !phi || !work || !U)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100, total = S * t.n;
+  FomWork w = fom_work(t, work);
+  FomBatch3 b;
+  b.carve(t, w, work + lrbms3_fom_solve_work_size(ctx));
+  double* pff = work + lrbms3_fom_solve_batch_work_size(ctx, nmu);
+  // one preconditioner per call, both levels on the step operator at the mean theta of its columns (summed in column order);
+  // never the elliptic solves' kept inverse
+  QV tb{};
+  for (int q = 0; q < Q; ++q) {
+    double acc = 0.0;
+    for (int m = 0; m < nmu; ++m) acc += theta[(long)m * Q + q];
+    tb.v[q] = dt * (acc / nmu);
+  }
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, nd, Q, tb, A_diag, w.Amu);
+  hipLaunchKernelGGL(k3_combine, dim3((unsigned)((ncp + 255) / 256)), dim3(256), 0, st, ncp, Q, tb, A_cpl, w.Cmu);
+  hipLaunchKernelGGL(k3p_fom_add_mass, dim3((unsigned)((S * t.nT * 100 + 255) / 256)), dim3(256), 0, st, t, S * t.nT * 100, w.Amu);
+  hipLaunchKernelGGL(k3f_block_inverse, dim3((t.nT + 63) / 64, S), dim3(64), 0, st, t, w.Amu, w.Dinv);
+  LRBMS_LAUNCH_CHECK(ctx);
+  int nc = 0;
+  const double* A1inv = nullptr;
+  if (int rc = fom_coarse(ctx, st, w, false, nc, A1inv)) return rc;
+  const long slab = total * nmu;
+  const unsigned gv = (unsigned)((total * 16 + 255) / 256);
+  double its_sum = 0.0, worst = 0.0;
+  bool missed = false;
+  for (int i = 0; i < 8; ++i) ctx->fombe_panels[i] = 0.0;
+  for (int m0 = 0; m0 < nmu; m0 += 16) {
+    const int P = nmu - m0 < 16 ? nmu - m0 : 16;
+    Fb3Op op{Q, P, nmu, m0, {}, A_diag, A_cpl, true};
+    for (int c = 0; c < 16; ++c)
+      for (int q = 0; q < 8; ++q) op.th.v[c][q] = (c < P && q < Q) ? dt * theta[(long)(m0 + c) * Q + q] : 0.0;
+    double its_p = 0.0, worst_p = 0.0;
+    for (int step = 0; step < nt; ++step) {
+      const double* Uk = U + step * slab;
+      double* X = U + (step + 1) * slab;
+      hipLaunchKernelGGL(k3fb_load, dim3(gv), dim3(256), 0, st, total, P, nmu, m0, Uk, X, b.p);
+      fomb3_launch_matvec(ctx, st, w, op, b.p, b.y, b.ppy);
+      hipLaunchKernelGGL(k3fb_step_residual, dim3(w.nbx, S), dim3(256), 0, st, t, dt, K, P, m0, (long)(nt + 1) * K,
+                         phi + (long)(step + 1) * K, b_K, b.p, b.y, b.r, pff);
+      int it = 0;
+      double rel = 0.0;
+      if (int rc = fomb3_panel_run(ctx, st, w, b, op, nc, A1inv, X, pff, rtol, max_iter, &it, &rel, "fom_implicit_euler_batch")) return rc;
+      its_p += it;
+      if (rel > worst_p) worst_p = rel;
+      if (rel > rtol) {                                      // this panel stops here; its later slabs are not written
+        missed = true;
+        break;
+      }
+    }
+    ctx->fombe_panels[m0 / 16 * 2] = its_p;
+    ctx->fombe_panels[m0 / 16 * 2 + 1] = worst_p;
+    its_sum += its_p;
+    if (worst_p > worst) worst = worst_p;
+  }
+  if (info) info[0] = its_sum, info[1] = worst;
+  if (missed) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_implicit_euler_batch: CG did not reach rtol");
+  return LRBMS_OK;
+}
+
+int lrbms3_fom_implicit_euler_batch_panel_info(lrbms3_ctx* ctx, double* out) {
+  if (!ctx || !out) return LRBMS_E_INVALID;
+  for (int i = 0; i < 8; ++i) out[i] = ctx->fombe_panels[i];
+  return LRBMS_OK;
 }
 
 int64_t lrbms3_reduced_implicit_euler_work_size(lrbms3_ctx* ctx, int32_t N) {

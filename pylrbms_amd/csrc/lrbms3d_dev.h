@@ -49,6 +49,7 @@ struct lrbms3_ctx : lrbms_ctx_base {
   long fom_pc_M = 0;
   int fom_pc_nc = 0;
   double fomb_panels[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // lrbms3_fom_solve_batch: (iterations, final ratio) of the up to four panels of the last call
+  double fombe_panels[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lrbms3_fom_implicit_euler_batch: (iterations over the steps, worst ratio) per panel of the last call
   void* blas = nullptr;           // rocBLAS handle (dense coarse inverses), created on first use
   const double* user_pc = nullptr;   // coarse inverse the batched reduced solve uses (lrbms3_reduced_precond_use), caller-owned
   int user_pc_N = 0;

@@ -182,7 +182,8 @@ class BlockDiscretization3D:
                 its, rel = max(its, info[0]), max(rel, info[1])
         else:
             theta = np.stack([self.theta(mu) for mu in mus])
-            phi = np.stack([self.source_coefficients(mu) for mu in mus])
+            # (the stationary coefficients [K] also on the parabolic subclass, whose table is [nt + 1, K]: ``solve_stationary_batch``)
+            phi = np.stack([BlockDiscretization3D.source_coefficients(self, mu) for mu in mus])
             b_K = self._src['b_K'] if self._src is not None else eng.ops['b'].reshape(1, eng.S, eng.t.n)
             for m0 in range(0, len(mus), 64):
                 X, info = eng.ctx.fom_solve_batch(theta[m0:m0 + 64], eng.ops['A_diag'], eng.ops['A_cpl'], phi[m0:m0 + 64], b_K,

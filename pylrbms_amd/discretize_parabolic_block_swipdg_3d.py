@@ -5,6 +5,7 @@
 
     d, data = discretize(grid_and_problem_data, T, nt)     # the elliptic 3D discretize + T, time_stepper, initial_data
     U = d.solve(mu)                                       # [S, n, nt + 1]: ONE native call (lrbms3_fom_implicit_euler)
+    Us = d.solve_batch(mus)                               # a training set, 64 trajectories per native call
     d.estimate(U, mu)                                     # est, (local_eta_nc, local_eta_r, local_eta_df, time_residual, time_deriv_nc)
     reductor = ParabolicLRBMSReductor3D(d)
     reductor.extend_basis(U[:, :, idx]);  rd = reductor.reduce()
@@ -80,6 +81,64 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
             from pylrbms_amd.sources3d import evaluate_stationary
             evaluate_stationary(self._src, mu)
         return BlockDiscretization3D.solve(self, mu, rtol=rtol, max_iter=max_iter, return_info=return_info)
+
+    def solve_batch(self, mus, rtol=1e-10, max_iter=50000, return_info=False, as_snapshots=False):
+        """Trajectories for a whole training set, 64 parameters per native ``lrbms3_fom_implicit_euler_batch`` call: panels of 16
+        columns share every read of the operator blocks, one two-level preconditioner per call on ``M + dt A`` at the mean theta of
+        its columns.  Returns a list with, per parameter, the tensor ``[S, n, nt + 1]`` that ``solve(mu)`` returns --
+        here a VIEW of the call's panel ``[nt + 1, S, n, nmu]`` (not contiguous; ``estimate`` makes its input contiguous, other
+        consumers call ``.contiguous()``).  ``as_snapshots=True``: one contiguous tensor ``[S, n, len(mus) * nt]`` instead, the steps
+        1 .. nt of every parameter, parameter-major: the slab ``extend_basis(..., method='pod')`` takes (at most 128 vectors).
+        ``last_solve_info`` / ``return_info``: (CG iterations summed over the calls, worst final residual ratio).  On a sharded grid
+        it is the loop of ``solve``."""
+        import torch
+        eng = self.engine
+        mus = list(mus)
+        if not mus:
+            raise ValueError('solve_batch: no parameters')
+        nt = self.time_stepper.nt
+        if as_snapshots and len(mus) * nt > 128:
+            raise ValueError('solve_batch(as_snapshots=True): {} x {} vectors, the local POD takes at most 128'.format(len(mus), nt))
+        trajs, its, rel = [], 0, 0.0
+        if eng.S_ext != eng.S:
+            for mu in mus:
+                U, info = self.solve(mu, rtol=rtol, max_iter=max_iter, return_info=True)
+                trajs.append(U)
+                its, rel = its + info[0], max(rel, info[1])
+        else:
+            theta = np.stack([self.theta(mu) for mu in mus])
+            phi = np.stack([np.asarray(self.source_coefficients(mu), dtype=np.float64) for mu in mus])     # [len(mus), nt + 1, K]
+            b_K = self._src['b_K'] if self._src is not None else eng.ops['b'].reshape(1, eng.S, eng.t.n)
+            for m0 in range(0, len(mus), 64):
+                U, info = eng.ctx.fom_implicit_euler_batch(theta[m0:m0 + 64], self.dt, nt, eng.ops['A_diag'], eng.ops['A_cpl'], b_K,
+                                                           phi[m0:m0 + 64], U0=self.initial_data, rtol=rtol, max_iter=max_iter)
+                its, rel = its + info['iterations'], max(rel, info['relative_residual'])
+                trajs += [U[:, :, :, m].permute(1, 2, 0) for m in range(U.shape[3])]
+        self.last_solve_info = (its, rel)
+        out = torch.cat([u[:, :, 1:] for u in trajs], dim=2).contiguous() if as_snapshots else trajs
+        return (out, self.last_solve_info) if return_info else out
+
+    def solve_stationary_batch(self, mus, rtol=1e-10, max_iter=50000, return_info=False):
+        """The elliptic ``solve_batch`` of the underlying discretization: one tensor [S, n, len(mus)] of stationary solutions.
+        NotImplementedError if a source coefficient depends on time, as ``solve_stationary``."""
+        mus = list(mus)
+        if self._src is not None:
+            from pylrbms_amd.sources3d import evaluate_stationary
+            for mu in mus:
+                evaluate_stationary(self._src, mu)
+        eng = self.engine
+        if eng.S_ext != eng.S:                       # (the elliptic loop would call this class's ``solve``)
+            import torch
+            if not mus:
+                raise ValueError('solve_stationary_batch: no parameters')
+            cols, its, rel = [], 0, 0.0
+            for mu in mus:
+                U, info = self.solve_stationary(mu, rtol=rtol, max_iter=max_iter, return_info=True)
+                cols.append(U[:, :, None])
+                its, rel = max(its, info[0]), max(rel, info[1])
+            U = torch.cat(cols, dim=2).contiguous()
+            return (U, (its, rel)) if return_info else U
+        return BlockDiscretization3D.solve_batch(self, mus, rtol=rtol, max_iter=max_iter, return_info=return_info)
 
     def _elliptic_terms(self, U, mu, rows=None):
         """Local nc / r / df [3, S, L] of every column of U [S, n, L]: chunks of <= 64 // Q columns become a basis of the pass
