@@ -100,6 +100,7 @@ def test_batch_columns_are_as_accurate_as_the_single_parameter_export(N, nmu):
         e_single = float(column_errors(U1.cpu().numpy()[..., None], ref[..., m:m + 1]).max())
         print('PARABOLIC-BATCH accuracy N={} nmu={} column {}: e_single {:.2e}, e_batch {:.2e}'.format(N, nmu, m, e_single,
                                                                                                        float(e_batch[m])))
+        assert e_single < TOL_TRAJ, (N, nmu, m, e_single)          # (a wrong single export would make the next line easier)
         assert e_batch[m] <= 10.0 * max(e_single, 1e-13), (N, nmu, m, e_single, float(e_batch[m]))
 
 
