@@ -663,6 +663,44 @@ int lrbms_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int32_t Q, int32_t N,
                                            const double* phi, const double* F2, const double* r_fd_K, double* work, double* eta_loc,
                                            double* time_deriv_nc, double* time_residual, double* eta, double* est, void* stream);
 
+/* -- time-dependent diffusion coefficients theta_q(t, mu) on the batched parabolic exports -----------------
+ * The three exports below are the batched exports above with a table theta_t [nmu][nt+1][Q] (host; row k: the coefficients at the
+ * time of step k, the shape of phi [nmu][nt+1][K]) in place of theta [nmu][Q].  The theta tables are launch arguments or small
+ * device tables, so a row per step rebuilds no operator.  Guarantees, limits, info and refusals are those of the twins: everything
+ * on `stream`, no atomics, repeat calls give the same bits, a refusal writes nothing.  One preconditioner per call, inverse
+ * diagonal blocks and coarse level at the mean of theta_t over the columns and the rows 1 .. nt.
+ *   lrbms_fom_implicit_euler_batch_tv       the step k -> k+1 of column m solves (M + dt A(theta_t[m][k+1])) u_{k+1} = M u_k + dt sum_j
+ *                                   phi[m][k+1][j] b_K[j]: the operator pyMOR's implicit Euler assembles at mu['_t'] = t_{k+1}.
+ *                                   work: lrbms_fom_implicit_euler_batch_work_size doubles; panel_info as for the twin.
+ *   lrbms_reduced_implicit_euler_batch_tv   the same on the reduced model.  K = 0: rhs_red_K is rhs_red [S][N] and phi is not read;
+ *                                   K >= 1: rhs_red_K [K][S][N], phi [nmu][nt+1][K] device.  The tables of all steps are uploaded
+ *                                   once per call into work: lrbms_reduced_implicit_euler_batch_tv_work_size(N, nmu, nt) doubles
+ *                                   (the twin's plus the tables).
+ *   lrbms_reduced_parabolic_estimate_batch_tv  the arguments of lrbms_reduced_parabolic_estimate_batch with theta_t and
+ *                                   coef [nmu][nt+1][2] (host; row k at theta_t[m][k]).  The elliptic rows (and the source part) of
+ *                                   U_k use row k, row 0 for U_0; the time residual of U_{k+1} - U_k uses row k + 1, the operator
+ *                                   that produced U_{k+1}; time_deriv_nc reads no theta; eta[k] is scaled with coef[m][k].  For a
+ *                                   table constant in time this is the twin term for term; otherwise it is an indicator with the
+ *                                   coefficient frozen per step, not a proven bound.
+ *                                   work: lrbms_reduced_parabolic_estimate_batch_tv_work_size(N, nmu, nt) doubles. */
+int lrbms_fom_implicit_euler_batch_tv(lrbms_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta_t, double dt, int32_t nt,
+                                      const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                      double* U, double rtol, int32_t max_iter, double* info, void* stream);
+int64_t lrbms_reduced_implicit_euler_batch_tv_work_size(lrbms_ctx* ctx, int32_t N, int32_t nmu, int32_t nt);
+int lrbms_reduced_implicit_euler_batch_tv(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta_t, double dt,
+                                          int32_t nt, const double* B_sys, const double* M_red, const double* rhs_red_K,
+                                          const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
+                                          void* stream);
+int64_t lrbms_reduced_parabolic_estimate_batch_tv_work_size(lrbms_ctx* ctx, int32_t N, int32_t nmu, int32_t nt);
+int lrbms_reduced_parabolic_estimate_batch_tv(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, int32_t nt, double dt,
+                                              const double* theta_t, const double* coef, int32_t sqrt_local, const double* U,
+                                              const double* B_sys, const double* M_red, const double* G_nc_self, const double* r_fd,
+                                              const double* G_rdd_self, const double* G_bb_self, const double* G_ab_self,
+                                              const double* G_aa, const double* F_side, const double* F_nc, const double* f2,
+                                              const double* ceps, double hdiam, const double* phi, const double* F2,
+                                              const double* r_fd_K, double* work, double* eta_loc, double* time_deriv_nc,
+                                              double* time_residual, double* eta, double* est, void* stream);
+
 /* -- online enrichment (SURVEY.md section 8f "next" #1) ---------------------------------------------------- */
 /* Dirichlet correction blocks of the neighbourhood problems: on every coupling face of subdomain s, the boundary-form
  * diagonal block minus the inner-face block already contained in A_diag

@@ -111,6 +111,15 @@ SIGNATURES = {
     'lrbms_reduced_parabolic_estimate_batch_work_size': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
     'lrbms_reduced_parabolic_estimate_batch': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_dbl, _P_DBL, _P_DBL, c_i32]
                                                + [c_vp] * 13 + [c_dbl] + [c_vp] * 10),
+    # time-dependent diffusion coefficients: theta_t [nmu][nt+1][Q]
+    'lrbms_fom_implicit_euler_batch_tv': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                         c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms_reduced_implicit_euler_batch_tv_work_size': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
+    'lrbms_reduced_implicit_euler_batch_tv': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp,
+                                                             c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms_reduced_parabolic_estimate_batch_tv_work_size': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
+    'lrbms_reduced_parabolic_estimate_batch_tv': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_dbl, _P_DBL, _P_DBL, c_i32]
+                                                  + [c_vp] * 13 + [c_dbl] + [c_vp] * 10),
     'lrbms_combine_sources': (ctypes.c_int, [c_vp, c_i32, c_i64, _P_DBL, c_vp, c_vp, c_vp]),
     'lrbms_assemble_dirichlet_correction': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms_local_correction_work_size': (c_i64, [c_vp, c_i32]),
@@ -1005,6 +1014,108 @@ class NativeContext(ContextBase):
             c_vp(out['time_deriv_nc'].data_ptr()), c_vp(out['time_residual'].data_ptr()), c_vp(out['eta'].data_ptr()),
             c_vp(out['est'].data_ptr()), self._stream())
         self._check(rc, 'lrbms_reduced_parabolic_estimate_batch')
+        return out
+
+    # ---- time-dependent diffusion coefficients: theta_t [nmu, nt + 1, Q] on the host
+    def _theta_t(self, theta_t, Q, nt):
+        th = np.ascontiguousarray(theta_t, dtype=np.float64)
+        assert th.ndim == 3 and th.shape[1:] == (max(int(nt), 0) + 1, Q), 'theta_t must be [nmu, nt + 1, Q]'
+        return th, th.shape[0]
+
+    def _phi_table(self, phi, nmu, nt, K):
+        ph = phi if hasattr(phi, 'data_ptr') else self.from_numpy(np.ascontiguousarray(np.asarray(phi, dtype=np.float64)))
+        assert tuple(ph.shape) == (nmu, max(int(nt), 0) + 1, K), 'phi must be [nmu, nt + 1, K]'
+        return ph.contiguous()
+
+    def fom_implicit_euler_batch_tv(self, theta_t, dt, nt, A_diag, A_cpl, b_K, phi, U0=None, rtol=1e-12, max_iter=100000):
+        """``fom_implicit_euler_batch`` with a coefficient row per step: the step k -> k + 1 of column m solves with
+        M + dt A(theta_t[m, k + 1]).  theta_t [nmu, nt + 1, Q] host."""
+        Q, S, K, nt = A_diag.shape[0], self.S, b_K.shape[0], int(nt)
+        th, nmu = self._theta_t(theta_t, Q, nt)
+        phi = self._phi_table(phi, nmu, nt, K)
+        size = int(self.lib.lrbms_fom_implicit_euler_batch_work_size(self.handle, nmu))
+        if size < 0:
+            raise NativeError('lrbms_fom_implicit_euler_batch_tv: nmu = {} is not in 1..64'.format(nmu))
+        work = self.empty(size)
+        U = self.zeros(nt + 1, S, self.n, nmu)
+        if U0 is not None:
+            U[0] = U0.reshape(S, self.n, -1)
+        info = np.zeros(2)
+        rc = self.lib.lrbms_fom_implicit_euler_batch_tv(self.handle, Q, K, nmu, _dblp(th), float(dt), nt,
+                                                        self._ptr(A_diag, (Q, S, self.n_T, 4, 9), 'A_diag'),
+                                                        self._ptr(A_cpl, (Q, S, 4, self.ncf, 9), 'A_cpl'),
+                                                        self._ptr(b_K, (K, S, self.n), 'b_K'), self._ptr(phi, (nmu, nt + 1, K), 'phi'),
+                                                        c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter),
+                                                        _dblp(info), self._stream())
+        panels = np.zeros(8)
+        self.lib.lrbms_fom_implicit_euler_batch_panel_info(self.handle, _dblp(panels))
+        self._check(rc, 'lrbms_fom_implicit_euler_batch_tv')
+        return U, {'iterations': int(info[0]), 'relative_residual': float(info[1]),
+                   'panel_iterations': [int(v) for v in panels[0:2 * ((nmu + 15) // 16):2]]}
+
+    def reduced_implicit_euler_batch_tv(self, theta_t, dt, nt, B_sys, M_red, rhs_red, phi=None, U0=None, rtol=1e-13, max_iter=20000,
+                                        work=None):
+        """``reduced_implicit_euler_batch`` (phi None, rhs_red [S, N]) / ``_src`` (rhs_red [K, S, N], phi [nmu, nt + 1, K]) with a
+        coefficient row per step: theta_t [nmu, nt + 1, Q] host, the step k -> k + 1 runs with row k + 1."""
+        Q, S, N = B_sys.shape[0], self.S, B_sys.shape[3]
+        th, nmu = self._theta_t(theta_t, Q, nt)
+        K = 0 if phi is None else int(rhs_red.shape[0])
+        ph = None if phi is None else self._phi_table(phi, nmu, nt, K)
+        need = int(self.lib.lrbms_reduced_implicit_euler_batch_tv_work_size(self.handle, N, nmu, max(int(nt), 1)))
+        if need < 0:
+            raise NativeError('reduced_implicit_euler_batch_tv: bad N / nmu')
+        if work is None:
+            work = self.empty(need)
+        if work.numel() < need:
+            raise NativeError('reduced_implicit_euler_batch_tv: work too small')
+        U = self.zeros(max(int(nt), 0) + 1, S, N, nmu)
+        if U0 is not None:
+            U[0] = U0.reshape(S, N, -1)
+        info = np.zeros(2)
+        rc = self.lib.lrbms_reduced_implicit_euler_batch_tv(
+            self.handle, Q, N, K, nmu, _dblp(th), float(dt), int(nt), self._ptr(B_sys, (Q, S, 5, N, N), 'B_sys'),
+            self._ptr(M_red, (S, N, N), 'M_red'), self._ptr(rhs_red, (K, S, N) if K else (S, N), 'rhs_red'),
+            c_vp(None) if ph is None else self._ptr(ph, tuple(ph.shape), 'phi'), c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol),
+            int(max_iter), _dblp(info), self._stream())
+        self._check(rc, 'lrbms_reduced_implicit_euler_batch_tv')
+        return U, {'iterations': int(info[0]), 'relative_residual': float(info[1])}
+
+    def reduced_parabolic_estimate_batch_tv(self, theta_t, coef, dt, nt, U, B_sys, M_red, grams, f2, ceps, hdiam, sqrt_local=False,
+                                            phi=None, F2=None, r_fd_K=None, work=None):
+        """``reduced_parabolic_estimate_batch`` with theta_t [nmu, nt + 1, Q] and coef [nmu, nt + 1, 2] (host): the elliptic rows of
+        U_k use row k, the time residual of U_{k+1} - U_k row k + 1.  Same outputs."""
+        Q, S, N = B_sys.shape[0], self.S, B_sys.shape[3]
+        nt = int(nt)
+        th, nmu = self._theta_t(theta_t, Q, nt)
+        cf = np.ascontiguousarray(coef, dtype=np.float64)
+        assert cf.shape == (nmu, max(nt, 0) + 1, 2), 'coef must be [nmu, nt + 1, 2]'
+        gptrs, factored = self._gram_ptrs(grams, Q, N)
+        if not factored:
+            gptrs = gptrs + [c_vp(None), c_vp(None)]
+        K = 0
+        src = [c_vp(None)] * 3
+        if phi is not None:
+            K = int(F2.shape[1])
+            ph = self._phi_table(phi, nmu, nt, K)
+            src = [self._ptr(ph, tuple(ph.shape), 'phi'), self._ptr(F2, (S, K, K), 'F2'),
+                   self._ptr(r_fd_K, (K, S, 5 * Q * N), 'r_fd_K')]
+        u_ptr = self._ptr(U, (max(nt, 0) + 1, S, N, nmu), 'U')
+        need = int(self.lib.lrbms_reduced_parabolic_estimate_batch_tv_work_size(self.handle, N, max(nmu, 1), max(nt, 1)))
+        if need < 0:
+            raise NativeError('reduced_parabolic_estimate_batch_tv: bad N / nmu / nt')
+        if work is None:
+            work = self.empty(need)
+        if work.numel() < need:
+            raise NativeError('reduced_parabolic_estimate_batch_tv: work too small')
+        out = {'eta_loc': self.empty(3, max(nt, 0) + 1, S, nmu), 'time_deriv_nc': self.empty(max(nt, 0), S, nmu),
+               'time_residual': self.empty(max(nt, 0), nmu), 'eta': self.empty(max(nt, 0) + 1, nmu), 'est': self.empty(nmu)}
+        rc = self.lib.lrbms_reduced_parabolic_estimate_batch_tv(
+            self.handle, Q, N, K, nmu, nt, float(dt), _dblp(th), _dblp(cf), int(bool(sqrt_local)), u_ptr,
+            self._ptr(B_sys, (Q, S, 5, N, N), 'B_sys'), self._ptr(M_red, (S, N, N), 'M_red'), *gptrs, self._ptr(f2, (S,), 'f2'),
+            self._ptr(ceps, (S,), 'ceps'), float(hdiam), *src, c_vp(work.data_ptr()), c_vp(out['eta_loc'].data_ptr()),
+            c_vp(out['time_deriv_nc'].data_ptr()), c_vp(out['time_residual'].data_ptr()), c_vp(out['eta'].data_ptr()),
+            c_vp(out['est'].data_ptr()), self._stream())
+        self._check(rc, 'lrbms_reduced_parabolic_estimate_batch_tv')
         return out
 
     def project_sources(self, Q, b_K, V, D, out=None):

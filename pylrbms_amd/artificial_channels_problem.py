@@ -36,7 +36,9 @@ def switched_vertical_connections(value):
     return [[[[x0, 3 / 8 + W], [x1, 5 / 8 - W]], value] for (x0, x1) in ((E, 1 / 4 - E), (3 / 4 + E, 1 - E))]
 
 
-def init_grid_and_problem(config, mu_bar=(1,), mu_hat=(1,), mpi_comm=None):
+def init_grid_and_problem(config, mu_bar=(1,), mu_hat=(1,), mpi_comm=None, switch_off_after=None):
+    """``switch_off_after=t*``: the switched connections carry ``switch`` for ``_t <= t*`` and ``mu_min`` afterwards -- they close
+    during the run (a diffusion coefficient of the time, parabolic path only).  None: open throughout."""
     lower_left, upper_right = [0, 0], [1, 1]
     mu_bar, mu_hat = tuple(mu_bar), tuple(mu_hat)
     mu_min = min((0.01,) + mu_bar + mu_hat)
@@ -57,6 +59,9 @@ def init_grid_and_problem(config, mu_bar=(1,), mu_hat=(1,), mpi_comm=None):
                            ExpressionParameterFunctional(str(mu_max), parameter_type),
                            ExpressionParameterFunctional(str(mu_max), parameter_type),
                            ProjectionParameterFunctional(component_name='switch', component_shape=(1,), coordinates=(0,))]
+    if switch_off_after is not None:
+        lambda_coefficients[3] = ExpressionParameterFunctional(
+            'switch if _t <= {!r} else {!r}'.format(float(switch_off_after), float(mu_min)), {'switch': (1,), '_t': ()})
     kappa = make_constant_function_2x2(grid, [[1., 0.], [0., 1.]], name='kappa')
     top_left = [b for b in fixed_vertical_connections(1) if b[0][0][0] < 0.5 and b[0][0][1] > 0.5]
     right = [b for b in fixed_vertical_connections(1) if b[0][0][0] > 0.5]

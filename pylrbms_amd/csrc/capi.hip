@@ -35,6 +35,21 @@ int64_t fom_implicit_euler_batch_work_size(lrbms_ctx* ctx, int nmu);
 int launch_fom_implicit_euler_batch(lrbms_ctx* ctx, int Q, int K, int nmu, const double* theta, double dt, int nt, const double* A_diag,
                                     const double* A_cpl, const double* bK, const double* phi, double* work, double* U, double rtol,
                                     int max_iter, double* info, hipStream_t st);
+int launch_fom_implicit_euler_batch_tv(lrbms_ctx* ctx, int Q, int K, int nmu, const double* theta_t, double dt, int nt,
+                                       const double* A_diag, const double* A_cpl, const double* bK, const double* phi, double* work,
+                                       double* U, double rtol, int max_iter, double* info, hipStream_t st);
+int64_t reduced_implicit_euler_batch_tv_work_size(lrbms_ctx* ctx, int N, int nmu, int nt);
+int launch_reduced_implicit_euler_batch_tv(lrbms_ctx* ctx, int Q, int N, int K, int nmu, const double* theta_t, double dt, int nt,
+                                           const double* B_sys, const double* M_red, const double* rhs, const double* phi, double* work,
+                                           double* U, double rtol, int max_iter, double* info, hipStream_t st);
+int64_t reduced_parabolic_estimate_batch_tv_work_size(lrbms_ctx* ctx, int N, int nmu, int nt);
+int launch_reduced_parabolic_estimate_batch_tv(lrbms_ctx* ctx, int Q, int N, int K, int nmu, int nt, double dt, const double* theta_t,
+                                               const double* coef, int sqrt_local, const double* U, const double* B_sys,
+                                               const double* M_red, const double* G_nc, const double* r_fd, const double* G_rdd,
+                                               const double* G_bb, const double* G_ab, const double* G_aa, const double* Fside,
+                                               const double* Fnc, const double* f2, const double* ceps, double hdiam, const double* phi,
+                                               const double* F2, const double* r_fd_K, double* work, double* eta_loc,
+                                               double* time_deriv_nc, double* time_residual, double* eta, double* est, hipStream_t st);
 int launch_mass_inverse_norm2(lrbms_ctx* ctx, int C, const double* Y, double* out, hipStream_t st);
 int launch_div_apply(lrbms_ctx* ctx, int C, int mode, const double* Rt, double* out, hipStream_t st);
 int launch_div_pairing(lrbms_ctx* ctx, int Q, int L, const double* theta, const double* D, const double* G, double* out, hipStream_t st);
@@ -867,6 +882,53 @@ int lrbms_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int32_t Q, int32_t N,
   return launch_reduced_parabolic_estimate_batch(ctx, Q, N, K, nmu, nt, dt, theta, coef, sqrt_local, U, B_sys, M_red, G_nc_self, r_fd,
                                                  G_rdd_self, G_bb_self, G_ab_self, G_aa, F_side, F_nc, f2, ceps, hdiam, phi, F2, r_fd_K, work,
                                                  eta_loc, time_deriv_nc, time_residual, eta, est, (hipStream_t)stream);
+}
+
+// -- time-dependent diffusion coefficients: theta_t [nmu][nt+1][Q] ---------------------------------------------
+int lrbms_fom_implicit_euler_batch_tv(lrbms_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta_t, double dt, int32_t nt,
+                                      const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                      double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, 1); CHECK_PTR(ctx, theta_t); CHECK_PTR(ctx, A_diag); CHECK_PTR(ctx, A_cpl);
+  CHECK_PTR(ctx, b_K); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
+  return launch_fom_implicit_euler_batch_tv(ctx, Q, K, nmu, theta_t, dt, nt, A_diag, A_cpl, b_K, phi, work, U, rtol, max_iter, info,
+                                            (hipStream_t)stream);
+}
+
+int64_t lrbms_reduced_implicit_euler_batch_tv_work_size(lrbms_ctx* ctx, int32_t N, int32_t nmu, int32_t nt) {
+  if (!ctx || !ctx->has_mesh || N < 1 || nmu < 1 || nt < 1) return -1;
+  return reduced_implicit_euler_batch_tv_work_size(ctx, N, nmu, nt);
+}
+
+int lrbms_reduced_implicit_euler_batch_tv(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta_t, double dt,
+                                          int32_t nt, const double* B_sys, const double* M_red, const double* rhs_red_K,
+                                          const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
+                                          void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, theta_t); CHECK_PTR(ctx, B_sys); CHECK_PTR(ctx, M_red);
+  CHECK_PTR(ctx, rhs_red_K); CHECK_PTR(ctx, work); CHECK_PTR(ctx, U);
+  return launch_reduced_implicit_euler_batch_tv(ctx, Q, N, K, nmu, theta_t, dt, nt, B_sys, M_red, rhs_red_K, phi, work, U, rtol,
+                                                max_iter, info, (hipStream_t)stream);
+}
+
+int64_t lrbms_reduced_parabolic_estimate_batch_tv_work_size(lrbms_ctx* ctx, int32_t N, int32_t nmu, int32_t nt) {
+  if (!ctx || !ctx->has_mesh || N < 1 || nmu < 1 || nt < 1) return -1;
+  return reduced_parabolic_estimate_batch_tv_work_size(ctx, N, nmu, nt);
+}
+
+int lrbms_reduced_parabolic_estimate_batch_tv(lrbms_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, int32_t nt, double dt,
+                                              const double* theta_t, const double* coef, int32_t sqrt_local, const double* U,
+                                              const double* B_sys, const double* M_red, const double* G_nc_self, const double* r_fd,
+                                              const double* G_rdd_self, const double* G_bb_self, const double* G_ab_self,
+                                              const double* G_aa, const double* F_side, const double* F_nc, const double* f2,
+                                              const double* ceps, double hdiam, const double* phi, const double* F2,
+                                              const double* r_fd_K, double* work, double* eta_loc, double* time_deriv_nc,
+                                              double* time_residual, double* eta, double* est, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_Q_N(ctx, Q, N); CHECK_PTR(ctx, theta_t); CHECK_PTR(ctx, coef); CHECK_PTR(ctx, U); CHECK_PTR(ctx, B_sys);
+  CHECK_PTR(ctx, M_red); CHECK_PTR(ctx, G_nc_self); CHECK_PTR(ctx, r_fd); CHECK_PTR(ctx, G_rdd_self); CHECK_PTR(ctx, G_bb_self);
+  CHECK_PTR(ctx, G_ab_self); CHECK_PTR(ctx, G_aa); CHECK_PTR(ctx, f2); CHECK_PTR(ctx, ceps); CHECK_PTR(ctx, work); CHECK_PTR(ctx, eta_loc);
+  CHECK_PTR(ctx, time_deriv_nc); CHECK_PTR(ctx, time_residual); CHECK_PTR(ctx, eta); CHECK_PTR(ctx, est);
+  return launch_reduced_parabolic_estimate_batch_tv(ctx, Q, N, K, nmu, nt, dt, theta_t, coef, sqrt_local, U, B_sys, M_red, G_nc_self,
+                                                    r_fd, G_rdd_self, G_bb_self, G_ab_self, G_aa, F_side, F_nc, f2, ceps, hdiam, phi, F2,
+                                                    r_fd_K, work, eta_loc, time_deriv_nc, time_residual, eta, est, (hipStream_t)stream);
 }
 
 int lrbms_combine_sources(lrbms_ctx* ctx, int32_t K, int64_t M, const double* phi, const double* x_K, double* y, void* stream) {

@@ -1201,12 +1201,19 @@ int64_t fom_implicit_euler_batch_work_size(lrbms_ctx* ctx, int nmu) {
   return FomB::total(ctx);
 }
 
-int launch_fom_implicit_euler_batch(lrbms_ctx* ctx, int Q, int K, int nmu, const double* theta, double dt, int nt, const double* A_diag,
-                                    const double* A_cpl, const double* bK, const double* phi, double* work, double* U, double rtol,
-                                    int max_iter, double* info, hipStream_t st) {
-  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch needs all subdomains on one rank");
+namespace {
+
+// The driver of lrbms_fom_implicit_euler_batch (tv == false: theta [nmu][Q], one table per panel) and of
+// lrbms_fom_implicit_euler_batch_tv (tv == true: theta [nmu][nt+1][Q], the step k -> k+1 fills the panel's table from row k + 1;
+// the coarse level sits at the mean over the columns and the rows 1 .. nt).  The launches are the same in both forms.
+int fom_euler_batch_drive(lrbms_ctx* ctx, const std::string& name, bool tv, int Q, int K, int nmu, const double* theta, double dt, int nt,
+                          const double* A_diag, const double* A_cpl, const double* bK, const double* phi, double* work, double* U,
+                          double rtol, int max_iter, double* info, hipStream_t st) {
+  if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, name + " needs all subdomains on one rank");
   if (Q < 1 || Q > 8 || nmu < 1 || nmu > 64 || K < 1 || K > 64 || nt < 1 || max_iter < 1 || !(rtol > 0.0) || !(dt > 0.0))
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch: bad Q / nmu / K / nt / dt / max_iter / rtol");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": bad Q / nmu / K / nt / dt / max_iter / rtol");
+  const long th_ld = tv ? (long)(nt + 1) * Q : Q;        // doubles per column of theta
+  const std::string nan_text = name + ": NaN residual (operator not SPD?)";
   FomB b;
   b.carve(ctx, work);
   // one coarse level per call, of the step operator at the mean theta of its columns (summed in column order)
@@ -1216,8 +1223,11 @@ int launch_fom_implicit_euler_batch(lrbms_ctx* ctx, int Q, int K, int nmu, const
     QVecF tb;
     for (int q = 0; q < 8; ++q) {
       double acc = 0.0;
-      for (int m = 0; q < Q && m < nmu; ++m) acc += theta[(long)m * Q + q];
-      tb.v[q] = dt * (acc / nmu);
+      for (int m = 0; q < Q && m < nmu; ++m) {
+        if (!tv) acc += theta[(long)m * Q + q];
+        for (int k = 1; tv && k <= nt; ++k) acc += theta[m * th_ld + (long)k * Q + q];
+      }
+      tb.v[q] = tv ? dt * (acc / ((double)nmu * nt)) : dt * (acc / nmu);
     }
     hipLaunchKernelGGL(k_fom_combine, dim3(4096), dim3(256), 0, st, ctx->t, ctx->S, Q, tb, 1.0, A_diag, A_cpl, b.Amu_d, b.Amu_c, b.Minv);
     hipLaunchKernelGGL(k_fom_coarse_entries, dim3(ctx->S), dim3(256), 0, st, ctx->t, ctx->S, ctx->nbr, b.Amu_d, b.Amu_c, A0);
@@ -1232,10 +1242,13 @@ int launch_fom_implicit_euler_batch(lrbms_ctx* ctx, int Q, int K, int nmu, const
   for (int m0 = 0; m0 < nmu; m0 += 16) {
     FombOp op{Q, nmu - m0 < 16 ? nmu - m0 : 16, nmu, m0, {}, A_diag, A_cpl, true};
     for (int c = 0; c < 16; ++c)
-      for (int q = 0; q < 8; ++q) op.th.v[c][q] = (c < op.P && q < Q) ? dt * theta[(long)(m0 + c) * Q + q] : 0.0;
+      for (int q = 0; q < 8; ++q) op.th.v[c][q] = (c < op.P && q < Q) ? dt * theta[(m0 + c) * th_ld + q] : 0.0;
     long its_p = 0;
     double worst_p = 0.0;
     for (int step = 0; step < nt; ++step) {
+      if (tv)                                                // the operator of this step: row step + 1
+        for (int c = 0; c < op.P; ++c)
+          for (int q = 0; q < Q; ++q) op.th.v[c][q] = dt * theta[(m0 + c) * th_ld + (long)(step + 1) * Q + q];
       const double* Uk = U + step * slab;
       double* X = U + (step + 1) * slab;
       hipLaunchKernelGGL(k_fomb_load, dim3(2048), dim3(256), 0, st, b.nv, op.P, nmu, m0, Uk, X, b.z);
@@ -1245,8 +1258,7 @@ int launch_fom_implicit_euler_batch(lrbms_ctx* ctx, int Q, int K, int nmu, const
       LRBMS_LAUNCH_CHECK(ctx);
       int it = 0;
       double rel = 0.0;
-      if (int rc = fomb_panel_run(ctx, b, op, X, b.ppap, rtol, max_iter, &it, &rel, "fom_implicit_euler_batch: NaN residual (operator not SPD?)",
-                                  st))
+      if (int rc = fomb_panel_run(ctx, b, op, X, b.ppap, rtol, max_iter, &it, &rel, nan_text.c_str(), st))
         return rc;
       its_p += it;
       const bool nan = !(rel == rel);
@@ -1262,8 +1274,25 @@ int launch_fom_implicit_euler_batch(lrbms_ctx* ctx, int Q, int K, int nmu, const
     if (!(worst_p == worst_p) || worst_p > worst) worst = worst_p;
   }
   if (info) { info[0] = (double)its_sum; info[1] = worst; }
-  if (missed) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_implicit_euler_batch: CG did not reach rtol");
+  if (missed) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": CG did not reach rtol");
   return LRBMS_OK;
+}
+
+}  // namespace
+
+int launch_fom_implicit_euler_batch(lrbms_ctx* ctx, int Q, int K, int nmu, const double* theta, double dt, int nt, const double* A_diag,
+                                    const double* A_cpl, const double* bK, const double* phi, double* work, double* U, double rtol,
+                                    int max_iter, double* info, hipStream_t st) {
+  return fom_euler_batch_drive(ctx, "fom_implicit_euler_batch", false, Q, K, nmu, theta, dt, nt, A_diag, A_cpl, bK, phi, work, U, rtol,
+                               max_iter, info, st);
+}
+
+// lrbms_fom_implicit_euler_batch_tv: theta_t [nmu][nt+1][Q] host, column m steps with (M + dt A(theta_t[m][k+1])) u_{k+1} = ...
+int launch_fom_implicit_euler_batch_tv(lrbms_ctx* ctx, int Q, int K, int nmu, const double* theta_t, double dt, int nt,
+                                       const double* A_diag, const double* A_cpl, const double* bK, const double* phi, double* work,
+                                       double* U, double rtol, int max_iter, double* info, hipStream_t st) {
+  return fom_euler_batch_drive(ctx, "fom_implicit_euler_batch_tv", true, Q, K, nmu, theta_t, dt, nt, A_diag, A_cpl, bK, phi, work, U,
+                               rtol, max_iter, info, st);
 }
 
 namespace {

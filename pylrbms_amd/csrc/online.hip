@@ -2177,6 +2177,16 @@ int bcg_plan(lrbms_ctx* ctx, const std::string& name, int N, int GW, bool mass, 
   return LRBMS_OK;
 }
 
+// The host theta tables of a group whose columns are set (m0, nm): scale * theta[column][q] with ld doubles between the columns
+// of theta (Q for theta [nmu][Q]; (nt + 1) Q for one row of a table [nmu][nt+1][Q], theta pointing at that row of column 0).
+void bcg_group_tables(BcgGroup& G, const BcgPlan& P, int Q, const double* theta, long ld, double scale) {
+  for (int m = 0; m < TBMAX; ++m)
+    for (int q = 0; q < 8; ++q) G.th.v[m * 8 + q] = (m < G.nm && q < Q) ? scale * theta[(G.m0 + m) * ld + q] : 0.0;
+  for (int m = 0; m < BMAX; ++m)
+    for (int q = 0; q < 8; ++q)
+      G.thd[m * 8 + q] = (m < G.nm && q < Q) ? scale * theta[(G.m0 + m) * ld + q] : (P.mass && m < G.nm && q == Q) ? 1.0 : 0.0;
+}
+
 // Group k of a call of nmu columns: its columns, its stream, its slice of gwork (reduced_batch_group_size doubles; pbe_group_size
 // in the mass form, ref2 behind theta_dev) and its theta tables scale * theta [m][q]; the mass form puts 1.0 at [m][Q] of the
 // wide panels' table, the coefficient of M_red.
@@ -2203,11 +2213,7 @@ void bcg_group(BcgGroup& G, const BcgPlan& P, int k, int nmu, int Q, const doubl
   G.scal = G.partial2 + (long)P.S * GW;                 // rz, alpha, beta, rr (BMAX each)
   G.theta_dev = G.scal + 4 * BMAX;                      // [BMAX][8]
   G.ref2 = P.mass ? G.theta_dev + 8 * BMAX : nullptr;   // [BMAX]: |M u_k + dt b_m|^2 of the step
-  for (int m = 0; m < TBMAX; ++m)
-    for (int q = 0; q < 8; ++q) G.th.v[m * 8 + q] = (m < G.nm && q < Q) ? scale * theta[(G.m0 + m) * Q + q] : 0.0;
-  for (int m = 0; m < BMAX; ++m)
-    for (int q = 0; q < 8; ++q)
-      G.thd[m * 8 + q] = (m < G.nm && q < Q) ? scale * theta[(G.m0 + m) * Q + q] : (P.mass && m < G.nm && q == Q) ? 1.0 : 0.0;
+  bcg_group_tables(G, P, Q, theta, Q, scale);
 }
 
 // preconditioner + update of one group: z = M^-1 r (first: of the start residual), then rz, beta and the residual norms
@@ -2477,8 +2483,16 @@ int64_t reduced_implicit_euler_batch_work_size(lrbms_ctx* ctx, int N, int nmu) {
   return S * 5 * N * N + S * N * N + (a > b ? a : b) + 16;
 }
 
-// K == 0: rhs [S][N] for every column and step; K >= 1: rhs [K][S][N], phi_dev [nmu][nt+1][K] (device), step k takes row k + 1
-static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, int N, int nmu, const double* theta, double dt, int nt,
+// the tables of the wide panels for every step of lrbms_reduced_implicit_euler_batch_tv, behind the work of the twin: [2][nt][BMAX][8]
+int64_t reduced_implicit_euler_batch_tv_work_size(lrbms_ctx* ctx, int N, int nmu, int nt) {
+  return reduced_implicit_euler_batch_work_size(ctx, N, nmu) + 2L * nt * 8 * BMAX;
+}
+
+// K == 0: rhs [S][N] for every column and step; K >= 1: rhs [K][S][N], phi_dev [nmu][nt+1][K] (device), step k takes row k + 1.
+// tv: theta is theta_t [nmu][nt+1][Q] and the step k -> k+1 runs with the groups' tables of row k + 1 (the operator pyMOR's implicit
+// Euler assembles at t_{k+1}); the preconditioner sits at the mean over the columns and the rows 1 .. nt.  The wide panels'
+// tables of all steps go to the device once, behind the twin's work, and a step moves the group's pointer.
+static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, bool tv, int Q, int N, int nmu, const double* theta, double dt, int nt,
                                      const double* B_sys, const double* M_red, const double* rhs, int K, const double* phi_dev,
                                      double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st) {
   if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + " needs all subdomains on one rank");
@@ -2493,10 +2507,14 @@ static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, in
   if (int rc = bcg_plan(ctx, name, N, GW, true, P)) return rc;
   const long per_q = (long)S * 5 * N * N;
   const long rows = (long)S * N;
+  const long th_ld = tv ? (long)(nt + 1) * Q : Q;        // doubles per column of theta
   QVec mean;                                             // dt * mean theta: the step operator the preconditioner is built for
   for (int q = 0; q < 8; ++q) mean.v[q] = 0.0;
   for (int m = 0; m < nmu; ++m)
-    for (int q = 0; q < Q; ++q) mean.v[q] += theta[m * Q + q] / nmu;
+    for (int q = 0; q < Q; ++q) {
+      if (!tv) mean.v[q] += theta[m * Q + q] / nmu;
+      for (int k = 1; tv && k <= nt; ++k) mean.v[q] += theta[m * th_ld + (long)k * Q + q] / ((double)nmu * nt);
+    }
   for (int q = 0; q < 8; ++q) mean.v[q] *= dt;
   double* Amu = work;
   double* Dinv = Amu + per_q;
@@ -2514,6 +2532,17 @@ static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, in
   StreamFork fork(ctx);
   if (int rc = fork.fork(st, ng)) return rc;
   for (int k = 0; k < ng; ++k) bcg_group(g[k], P, k, nmu, Q, theta, dt, gwork, fork.stream(k));      // dt folded into the tables
+  // tv, wide panels: the tables of every step, [group][step][BMAX][8], one copy per group ahead of its first step
+  std::vector<double> tv_host;
+  double* tv_dev = work + reduced_implicit_euler_batch_work_size(ctx, N, nmu);
+  if (tv && GW > 16) {
+    tv_host.resize((size_t)ng * nt * 8 * BMAX);
+    for (int k = 0; k < ng; ++k)
+      for (int step = 0; step < nt; ++step) {
+        bcg_group_tables(g[k], P, Q, theta + (long)(step + 1) * Q, th_ld, dt);
+        for (int i = 0; i < 8 * BMAX; ++i) tv_host[((size_t)k * nt + step) * 8 * BMAX + i] = g[k].thd[i];
+      }
+  }
   const size_t lds_rhs = sizeof(double) * 2 * (size_t)N * GW;
   bool nan = false, capped = false;
   double worst = 0.0;
@@ -2526,7 +2555,13 @@ static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, in
       const long vec = rows * G.nm;
       const unsigned nb = (unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256);
       if (ng == 1) G.ug = un;                            // a single group iterates in place in U[k + 1]
-      if (step == 0 && GW > 16)
+      if (tv) {                                          // the operator of this step: row step + 1
+        bcg_group_tables(G, P, Q, theta + (long)(step + 1) * Q, th_ld, dt);
+        G.theta_dev = tv_dev + ((long)k * nt + step) * 8 * BMAX;
+        if (step == 0 && GW > 16)
+          LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(G.theta_dev, tv_host.data() + (size_t)k * nt * 8 * BMAX, sizeof(double) * nt * 8 * BMAX,
+                                              hipMemcpyHostToDevice, G.st));
+      } else if (step == 0 && GW > 16)
         LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(G.theta_dev, G.thd, sizeof(double) * 8 * BMAX, hipMemcpyHostToDevice, G.st));
       hipLaunchKernelGGL(k_pbe_gather, dim3(nb), dim3(256), 0, G.st, rows, G.nm, nmu, uk + G.m0, G.ug);
       bcg_matvec<true>(ctx, P, op, G, G.ug, 1);
@@ -2572,7 +2607,7 @@ static int reduced_euler_batch_drive(lrbms_ctx* ctx, const char* name, int Q, in
 int launch_reduced_implicit_euler_batch(lrbms_ctx* ctx, int Q, int N, int nmu, const double* theta, double dt, int nt, const double* B_sys,
                                         const double* M_red, const double* rhs_red, double* work, double* U, double rtol, int max_iter,
                                         double* info, hipStream_t st) {
-  return reduced_euler_batch_drive(ctx, "reduced_implicit_euler_batch", Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red, 0, nullptr, work,
+  return reduced_euler_batch_drive(ctx, "reduced_implicit_euler_batch", false, Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red, 0, nullptr, work,
                                    U, rtol, max_iter, info, st);
 }
 
@@ -2580,8 +2615,17 @@ int launch_reduced_implicit_euler_batch_src(lrbms_ctx* ctx, int Q, int N, int K,
                                             const double* B_sys, const double* M_red, const double* rhs_red_K, const double* phi,
                                             double* work, double* U, double rtol, int max_iter, double* info, hipStream_t st) {
   if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_src: need 1 <= K <= 64");
-  return reduced_euler_batch_drive(ctx, "reduced_implicit_euler_batch_src", Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red_K, K, phi,
+  return reduced_euler_batch_drive(ctx, "reduced_implicit_euler_batch_src", false, Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red_K, K, phi,
                                    work, U, rtol, max_iter, info, st);
+}
+
+// lrbms_reduced_implicit_euler_batch_tv: theta_t [nmu][nt+1][Q] host; K == 0: rhs [S][N], K >= 1: rhs [K][S][N] and phi (device)
+int launch_reduced_implicit_euler_batch_tv(lrbms_ctx* ctx, int Q, int N, int K, int nmu, const double* theta_t, double dt, int nt,
+                                           const double* B_sys, const double* M_red, const double* rhs, const double* phi, double* work,
+                                           double* U, double rtol, int max_iter, double* info, hipStream_t st) {
+  if (K < 0 || K > 64 || (K > 0 && !phi)) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_tv: need 0 <= K <= 64, and phi with K >= 1");
+  return reduced_euler_batch_drive(ctx, "reduced_implicit_euler_batch_tv", true, Q, N, nmu, theta_t, dt, nt, B_sys, M_red, rhs, K, phi, work,
+                                   U, rtol, max_iter, info, st);
 }
 
 
@@ -3348,6 +3392,71 @@ __global__ __launch_bounds__(256) void k_pe_combine(int S, int nmu, int nt, doub
   if (sl == 0 && valid) est[m] = sqrt(eta2) + sqrt(tr2) + sqrt(nc2);
 }
 
+// k_pe_combine with the coefficients per (column, step): coef [nmu][nt+1][2] on the device (lrbms_reduced_parabolic_estimate_batch_tv;
+// eta[k] of column m is scaled with coef[m][k], everything else as above)
+__global__ __launch_bounds__(256) void k_pe_combine_tv(int S, int nmu, int nt, double dt, int sqrt_local, const double* __restrict__ coef,
+                                                       const double* __restrict__ raw, const double* __restrict__ src,
+                                                       const double* __restrict__ trp, const double* __restrict__ tdn,
+                                                       double* __restrict__ eta_loc, double* __restrict__ time_residual,
+                                                       double* __restrict__ eta, double* __restrict__ est) {
+  __shared__ double red[4][16][16];
+  const int ml = threadIdx.x & 15, sl = threadIdx.x >> 4, m = blockIdx.x * 16 + ml;
+  const bool valid = m < nmu;
+  const double sc = 2.0 * sqrt(dt / 3.0);
+  const long SM = (long)S * nmu, row = (long)(nt + 1) * SM;
+  double eta2 = 0.0, tr2 = 0.0, nc2 = 0.0;
+  for (int k = 0; k <= nt; ++k) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    if (valid)
+      for (int s = sl; s < S; s += 16) {
+        const long o = (long)s * nmu + m;
+        double nc = raw[(long)(3 * k) * SM + o], r = raw[(long)(3 * k + 1) * SM + o], df = raw[(long)(3 * k + 2) * SM + o];
+        if (src) r += src[(long)k * SM + o];
+        if (sqrt_local) {
+          nc = sqrt(fabs(nc));
+          r = sqrt(fabs(r));
+          df = sqrt(fabs(df));
+        }
+        a0 += nc * nc;
+        a1 += (r + df) * (r + df);
+        eta_loc[(long)k * SM + o] = nc * sc;
+        eta_loc[row + (long)k * SM + o] = r * sc;
+        eta_loc[2 * row + (long)k * SM + o] = df * sc;
+        if (k < nt) {
+          a2 += trp[(long)k * SM + o];
+          const double v = tdn[(long)k * SM + o];
+          a3 += v * v;
+        }
+      }
+    red[0][sl][ml] = a0;
+    red[1][sl][ml] = a1;
+    red[2][sl][ml] = a2;
+    red[3][sl][ml] = a3;
+    __syncthreads();
+    if (sl == 0 && valid) {
+      double A0 = 0.0, A1 = 0.0, A2 = 0.0, A3 = 0.0;
+      for (int j = 0; j < 16; ++j) {
+        A0 += red[0][j][ml];
+        A1 += red[1][j][ml];
+        A2 += red[2][j][ml];
+        A3 += red[3][j][ml];
+      }
+      const double* cf = coef + ((long)m * (nt + 1) + k) * 2;
+      const double e = (cf[0] * sqrt(A0) + cf[1] * sqrt(A1)) * sc;
+      eta[(long)k * nmu + m] = e;
+      eta2 += e * e;
+      if (k < nt) {
+        const double tr = sqrt(A2 * (dt / 3.0));
+        time_residual[(long)k * nmu + m] = tr;
+        tr2 += tr * tr;
+        nc2 += A3;
+      }
+    }
+    __syncthreads();
+  }
+  if (sl == 0 && valid) est[m] = sqrt(eta2) + sqrt(tr2) + sqrt(nc2);
+}
+
 // the layout of the work array (doubles)
 struct PeWork {
   long minv, zero, raw, src, trp, du, y, pout, partial, scal, theta_dev, theta_cols, total;
@@ -3376,14 +3485,22 @@ PeWork pe_work(long S, int N, int nmu, int nt) {
 
 int64_t reduced_parabolic_estimate_batch_work_size(lrbms_ctx* ctx, int N, int nmu, int nt) { return pe_work(ctx->S, N, nmu, nt).total; }
 
-int launch_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int Q, int N, int K, int nmu, int nt, double dt, const double* theta,
-                                            const double* coef, int sqrt_local, const double* U, const double* B_sys,
+// tables of lrbms_reduced_parabolic_estimate_batch_tv behind the work of the twin: coef [nmu][nt+1][2]
+int64_t reduced_parabolic_estimate_batch_tv_work_size(lrbms_ctx* ctx, int N, int nmu, int nt) {
+  return pe_work(ctx->S, N, nmu, nt).total + (((long)nmu * (nt + 1) * 2 + 15) & ~15L);
+}
+
+// The driver of lrbms_reduced_parabolic_estimate_batch (tv == false: theta [nmu][Q], coef [nmu][2]) and of its _tv twin (tv == true:
+// theta [nmu][nt+1][Q], coef [nmu][nt+1][2]): the elliptic rows and the source part of U_k use row k, the time residual of
+// U_{k+1} - U_k row k + 1 (the operator that produced U_{k+1}); time_deriv_nc reads no theta.  The per-step tables travel as kernel
+// arguments (k_pe_put into one slot, in stream order), coef of the _tv form into a table behind the twin's work.
+static int parabolic_estimate_batch_drive(lrbms_ctx* ctx, const std::string& name, bool tv, int Q, int N, int K, int nmu, int nt, double dt,
+                                          const double* theta, const double* coef, int sqrt_local, const double* U, const double* B_sys,
                                             const double* M_red, const double* G_nc, const double* r_fd, const double* G_rdd,
                                             const double* G_bb, const double* G_ab, const double* G_aa, const double* Fside,
                                             const double* Fnc, const double* f2, const double* ceps, double hdiam, const double* phi,
                                             const double* F2, const double* r_fd_K, double* work, double* eta_loc, double* time_deriv_nc,
                                             double* time_residual, double* eta, double* est, hipStream_t st) {
-  const std::string name = "reduced_parabolic_estimate_batch";
   // ---- every refusal, ahead of the first launch
   if (ctx->S_ext != ctx->S) return lrbms_fail(ctx, LRBMS_E_INVALID, name + " needs all subdomains on one rank (S_ext == S)");
   if (nmu < 1 || nmu > 64 || N < 1 || N > 64 || nt < 1 || !(dt > 0.0))
@@ -3424,10 +3541,15 @@ int launch_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int Q, int N, int K,
     r_fd_e = work + w.zero + S;
   }
   // ---- elliptic rows: the batched estimate on every slab
-  for (int k = 0; k <= nt; ++k)
-    if (int rc = launch_reduced_estimate_batch(ctx, Q, N, nmu, theta, U + (long)k * rows * nmu, G_nc, r_fd_e, G_rdd, G_bb, G_ab, G_aa, Fside,
+  const long th_ld = tv ? (long)(nt + 1) * Q : Q;        // doubles per column of theta
+  std::vector<double> th_row((size_t)nmu * Q);           // tv: row k of every column, contiguous
+  for (int k = 0; k <= nt; ++k) {
+    for (int m = 0; tv && m < nmu; ++m)
+      for (int q = 0; q < Q; ++q) th_row[(size_t)m * Q + q] = theta[m * th_ld + (long)k * Q + q];
+    if (int rc = launch_reduced_estimate_batch(ctx, Q, N, nmu, tv ? th_row.data() : theta, U + (long)k * rows * nmu, G_nc, r_fd_e, G_rdd, G_bb, G_ab, G_aa, Fside,
                                                Fnc, f2_e, ceps, hdiam, work + w.raw + (long)k * 3 * SM, st))
       return rc;
+  }
   // ---- nc of the differences
   for (int m0 = 0; m0 < nmu; m0 += EB) {
     const int nm = nmu - m0 < EB ? nmu - m0 : EB;
@@ -3450,16 +3572,22 @@ int launch_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int Q, int N, int K,
     double* dUg = work + w.du + (long)nt * rows * G.m0;
     double* yg = work + w.y + (long)nt * rows * G.m0;
     G.pin = dUg;                                         // p_old of a first = 1 launch: loaded and dropped, never written
-    if (GW > 16)
+    auto put_tables = [&]() {
       for (int h = 0; h < 2; ++h) {
         PeTable t;
         for (int i = 0; i < 256; ++i) t.v[i] = G.thd[256 * h + i];
         hipLaunchKernelGGL(k_pe_put, dim3(1), dim3(256), 0, st, 256, t, G.theta_dev + 256 * h);
       }
+    };
+    if (GW > 16 && !tv) put_tables();
     const long total = (long)nt * vec;
     hipLaunchKernelGGL(k_pe_diff, dim3((unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0, st, rows, nt,
                        G.nm, G.m0, nmu, U, dUg);
     for (int step = 0; step < nt; ++step) {
+      if (tv) {                                          // the operator that produced U[step + 1]: row step + 1
+        bcg_group_tables(G, P, Q, theta + (long)(step + 1) * Q, th_ld, 1.0);
+        if (GW > 16) put_tables();
+      }
       G.y = yg + (long)step * vec;
       bcg_matvec<false>(ctx, P, op, G, dUg + (long)step * vec, 1);
     }
@@ -3469,22 +3597,68 @@ int launch_reduced_parabolic_estimate_batch(lrbms_ctx* ctx, int Q, int N, int K,
   }
   // ---- time-dependent source
   if (K > 0) {
-    for (int h = 0; h < 2; ++h) {
-      PeTable t;
-      for (int i = 0; i < 256; ++i) {
-        const int m = (256 * h + i) / 8, q = i % 8;
-        t.v[i] = (m < nmu && q < Q) ? theta[m * Q + q] : 0.0;
+    auto put_cols = [&](const double* th) {              // theta [m][8] of every column, th: the row of column 0
+      for (int h = 0; h < 2; ++h) {
+        PeTable t;
+        for (int i = 0; i < 256; ++i) {
+          const int m = (256 * h + i) / 8, q = i % 8;
+          t.v[i] = (m < nmu && q < Q) ? th[m * th_ld + q] : 0.0;
+        }
+        hipLaunchKernelGGL(k_pe_put, dim3(1), dim3(256), 0, st, 256, t, work + w.theta_cols + 256 * h);
       }
-      hipLaunchKernelGGL(k_pe_put, dim3(1), dim3(256), 0, st, 256, t, work + w.theta_cols + 256 * h);
+    };
+    if (!tv) {
+      put_cols(theta);
+      hipLaunchKernelGGL(k_reduced_source_terms_cols, dim3(S, nt + 1), dim3(256), 0, st, S, ctx->nbr, Q, N, K, nmu, nt + 1,
+                         work + w.theta_cols, phi, F2, r_fd_K, U, ceps, hdiam, work + w.src);
+    } else {
+      for (int k = 0; k <= nt; ++k) {                    // one slab per launch, with the tables of row k
+        put_cols(theta + (long)k * Q);
+        hipLaunchKernelGGL(k_reduced_source_terms_cols, dim3(S, 1), dim3(256), 0, st, S, ctx->nbr, Q, N, K, nmu, nt + 1,
+                           work + w.theta_cols, phi + (long)k * K, F2, r_fd_K, U + (long)k * rows * nmu, ceps, hdiam,
+                           work + w.src + (long)k * SM);
+      }
     }
-    hipLaunchKernelGGL(k_reduced_source_terms_cols, dim3(S, nt + 1), dim3(256), 0, st, S, ctx->nbr, Q, N, K, nmu, nt + 1,
-                       work + w.theta_cols, phi, F2, r_fd_K, U, ceps, hdiam, work + w.src);
   }
   // ---- combine
-  PeCoef cf;
-  for (int i = 0; i < 128; ++i) cf.v[i] = i < 2 * nmu ? coef[i] : 0.0;
-  hipLaunchKernelGGL(k_pe_combine, dim3((nmu + 15) / 16), dim3(256), 0, st, S, nmu, nt, dt, sqrt_local, cf, work + w.raw,
-                     K > 0 ? work + w.src : (const double*)nullptr, work + w.trp, time_deriv_nc, eta_loc, time_residual, eta, est);
+  if (!tv) {
+    PeCoef cf;
+    for (int i = 0; i < 128; ++i) cf.v[i] = i < 2 * nmu ? coef[i] : 0.0;
+    hipLaunchKernelGGL(k_pe_combine, dim3((nmu + 15) / 16), dim3(256), 0, st, S, nmu, nt, dt, sqrt_local, cf, work + w.raw,
+                       K > 0 ? work + w.src : (const double*)nullptr, work + w.trp, time_deriv_nc, eta_loc, time_residual, eta, est);
+  } else {
+    double* coef_dev = work + w.total;
+    const long nc = (long)nmu * (nt + 1) * 2;
+    for (long c0 = 0; c0 < nc; c0 += 256) {
+      PeTable t;
+      const int n = nc - c0 < 256 ? (int)(nc - c0) : 256;
+      for (int i = 0; i < 256; ++i) t.v[i] = i < n ? coef[c0 + i] : 0.0;
+      hipLaunchKernelGGL(k_pe_put, dim3(1), dim3(256), 0, st, n, t, coef_dev + c0);
+    }
+    hipLaunchKernelGGL(k_pe_combine_tv, dim3((nmu + 15) / 16), dim3(256), 0, st, S, nmu, nt, dt, sqrt_local, coef_dev, work + w.raw,
+                       K > 0 ? work + w.src : (const double*)nullptr, work + w.trp, time_deriv_nc, eta_loc, time_residual, eta, est);
+  }
   LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
+
+#define LRBMS_PE_ARGS                                                                                                              \
+  Q, N, K, nmu, nt, dt, theta, coef, sqrt_local, U, B_sys, M_red, G_nc, r_fd, G_rdd, G_bb, G_ab, G_aa, Fside, Fnc, f2, ceps, hdiam, phi, F2, \
+      r_fd_K, work, eta_loc, time_deriv_nc, time_residual, eta, est, st
+#define LRBMS_PE_PARAMS                                                                                                            \
+  lrbms_ctx *ctx, int Q, int N, int K, int nmu, int nt, double dt, const double *theta, const double *coef, int sqrt_local,        \
+      const double *U, const double *B_sys, const double *M_red, const double *G_nc, const double *r_fd, const double *G_rdd,      \
+      const double *G_bb, const double *G_ab, const double *G_aa, const double *Fside, const double *Fnc, const double *f2,        \
+      const double *ceps, double hdiam, const double *phi, const double *F2, const double *r_fd_K, double *work, double *eta_loc,  \
+      double *time_deriv_nc, double *time_residual, double *eta, double *est, hipStream_t st
+
+int launch_reduced_parabolic_estimate_batch(LRBMS_PE_PARAMS) {
+  return parabolic_estimate_batch_drive(ctx, "reduced_parabolic_estimate_batch", false, LRBMS_PE_ARGS);
+}
+
+// theta = theta_t [nmu][nt+1][Q], coef [nmu][nt+1][2] (host)
+int launch_reduced_parabolic_estimate_batch_tv(LRBMS_PE_PARAMS) {
+  return parabolic_estimate_batch_drive(ctx, "reduced_parabolic_estimate_batch_tv", true, LRBMS_PE_ARGS);
+}
+#undef LRBMS_PE_ARGS
+#undef LRBMS_PE_PARAMS

@@ -21,7 +21,8 @@ from pylrbms_amd.engine import Engine, blockell_to_dense
 from pylrbms_amd.estimators import EllipticEstimator
 from pylrbms_amd.parallel import Communicator, HaloExchange, HaloPlan
 from pylrbms_amd.parameters import CubicParameterSpace, parse_parameter
-from pylrbms_amd.sources import check_coefficients, evaluate_coefficients, local_estimates, setup_sources, source_components
+from pylrbms_amd.sources import (check_coefficients, coefficient_parameter_type, evaluate_coefficients, local_estimates,
+                                 setup_sources, source_components)
 from pylrbms_amd.vectorarrays import BlockVectorArray, BlockVectorSpace, SubSpace
 
 
@@ -362,13 +363,18 @@ class DuneDiscretization:
         return out
 
 
-def discretize(grid_and_problem_data, solver_options=None, mpi_comm=None, device_index=None, conventions=None, quadrature=None):
-    """Reference block_swipdg.py:530-811.  Returns ``(d, data)`` with ``data`` keys as at :631-637."""
+def discretize(grid_and_problem_data, solver_options=None, mpi_comm=None, device_index=None, conventions=None, quadrature=None,
+               _time_dependent_lambda=False):
+    """Reference block_swipdg.py:530-811.  Returns ``(d, data)`` with ``data`` keys as at :631-637.  (``_time_dependent_lambda``: set
+    by the parabolic ``discretize``, which alone takes diffusion coefficients of the time ``'_t'``.)"""
     p = grid_and_problem_data
     grid = p['grid']
     lambda_, kappa = p['lambda'], p['kappa']
     if isinstance(lambda_, dict):
         lambda_funcs, lambda_coeffs = lambda_['functions'], lambda_['coefficients']
+        if not _time_dependent_lambda and any('_t' in coefficient_parameter_type(c) for c in lambda_coeffs):
+            raise NotImplementedError('a diffusion coefficient depends on the time (_t): time-dependent diffusion coefficients need the '
+                                      'parabolic discretize (discretize_parabolic_block_swipdg)')
     else:
         from pylrbms_amd.parameters import ConstantParameterFunctional
         lambda_funcs, lambda_coeffs = [lambda_], [ConstantParameterFunctional(1.)]

@@ -24,6 +24,13 @@ of step k accumulated as pyMOR's implicit Euler does, ``t += dt``); the load vec
 ``U_k`` with ``f(t_k, mu)`` (row k): ``lrbms_reduced_estimate_batch`` with f2 = 0, r_fd = 0 plus ``lrbms_project_sources`` /
 ``lrbms_reduced_source_terms``.  A single component with coefficient 1 takes the path above unchanged.
 Single rank only; the elliptic reconstruction is not available with such a source.
+
+Time-dependent diffusion coefficients: a ``lambda`` coefficient whose ``parameter_type`` names ``'_t'`` makes
+the discretization time-dependent (``'_t'`` does not join ``d.parameter_type``).  ``d.diffusion_coefficients(mu)`` is the table
+``theta_t [nt + 1][Q]`` at the times of ``source_coefficients``; the step k -> k + 1 solves with row k + 1, as pyMOR's implicit Euler
+assembles ``M + dt A(mu)`` at ``mu['_t'] = t_{k+1}``.  ``solve`` / ``solve_batch`` run ``lrbms_fom_implicit_euler_batch_tv`` (the batched
+kernels take theta per column as launch arguments: a row per step rebuilds no operator); the estimate freezes the coefficient per
+step.  Single rank, no elliptic reconstruction, no stationary solves; ``mu_bar`` / ``mu_hat`` without a ``'_t'`` sit at ``_t = 0``.
 """
 import numpy as np
 
@@ -31,7 +38,7 @@ from pylrbms_amd.discretize_elliptic_block_swipdg import DuneDiscretization, Ope
 from pylrbms_amd.discretize_elliptic_block_swipdg import discretize as discretize_ell
 from pylrbms_amd.estimators import ParabolicEstimator
 from pylrbms_amd.parameters import CubicParameterSpace
-from pylrbms_amd.sources import local_estimates, setup_sources, source_components
+from pylrbms_amd.sources import coefficient_parameter_type, local_estimates, setup_sources, source_components
 from pylrbms_amd.vectorarrays import BlockVectorArray
 
 
@@ -51,26 +58,61 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         return min(float(opts.get('precision', 1e-12)), 1e-10), max(int(opts.get('max_iter', 20000)), 20000)
 
     _src = None       # the time-dependent source (``_setup_sources``), None: one component with coefficient 1
+    _tv = False       # a lambda coefficient reads '_t': theta_q(t, mu), a coefficient row per step
 
-    def source_coefficients(self, mu):
-        """``phi [nt + 1][K]`` (fp64, host) of the time-dependent source at ``mu``: row 0 at t = 0, row k at the time of step k,
-        accumulated like pyMOR's ``implicit_euler`` (``t += dt``, then ``mu['_t'] = t``).  A plain number as
-        coefficient is a constant."""
-        if self._src is None:
-            return np.ones((self.time_stepper.nt + 1, 1))
+    def _time_rows(self, mu):
+        """``mu`` at the times of the ``nt + 1`` rows of the coefficient tables: row 0 at t = 0, row k at the time of step k,
+        accumulated like pyMOR's ``implicit_euler`` (``t += dt``, then ``mu['_t'] = t``).  The ONE loop behind
+        ``source_coefficients`` and ``diffusion_coefficients``: phi and theta cannot disagree on t_k."""
         from pylrbms_amd.parameters import Parameter
         mu = self.parse_parameter(mu)
         nt = self.time_stepper.nt
         dt = self.T / nt
-        coeffs = self._src['coefficients']
-        phi = np.empty((nt + 1, len(coeffs)))
+        rows = []
         t = 0.0
         for k in range(nt + 1):
             if k > 0:
                 t += dt
-            mu_t = Parameter(dict(mu, _t=np.array(t)))
-            phi[k] = [c.evaluate(mu_t) if hasattr(c, 'evaluate') else float(c) for c in coeffs]
-        return phi
+            rows.append(Parameter(dict(mu, _t=np.array(t))))
+        return rows
+
+    def source_coefficients(self, mu):
+        """``phi [nt + 1][K]`` (fp64, host) of the time-dependent source at ``mu``: row 0 at t = 0, row k at the time of step k
+        (``_time_rows``).  A plain number as coefficient is a constant."""
+        if self._src is None:
+            return np.ones((self.time_stepper.nt + 1, 1))
+        coeffs = self._src['coefficients']
+        return np.array([[c.evaluate(mu_t) if hasattr(c, 'evaluate') else float(c) for c in coeffs] for mu_t in self._time_rows(mu)])
+
+    def diffusion_coefficients(self, mu):
+        """``theta_t [nt + 1][Q]`` (fp64, host): row k holds theta_q(t_k, mu) at the times of ``source_coefficients``; on a
+        discretization without a time-dependent coefficient every row is ``theta(mu)``.  ValueError unless every entry is positive."""
+        if not self._tv:
+            return np.tile(self.theta(mu), (self.time_stepper.nt + 1, 1))
+        th = np.array([[c.evaluate(mu_t) for c in self.lambda_coeffs] for mu_t in self._time_rows(mu)])
+        bad = np.argwhere(~(th > 0))
+        if len(bad):
+            k, q = (int(v) for v in bad[0])
+            raise ValueError('diffusion coefficient q = {} at step k = {}: theta_q(t_k, mu) = {} is not positive'.format(q, k, th[k, q]))
+        return th
+
+    def theta(self, mu):
+        if self._tv and '_t' not in self.parse_parameter(mu):
+            raise NotImplementedError("theta(mu): the diffusion coefficients depend on time, mu needs a '_t' "
+                                      '(diffusion_coefficients(mu) is the table of all steps)')
+        return DuneDiscretization.theta(self, mu)
+
+    def _estimator_coefficients(self, mu):
+        """``coef [nt + 1][2]``: sqrt(gamma_bar / alpha_bar) and 1 / sqrt(alpha_hat alpha_bar) of the elliptic eta at every row of
+        ``_time_rows`` (the second argument of ``lrbms_reduced_parabolic_estimate_batch_tv``)."""
+        est = self.estimator
+        coef = np.empty((self.time_stepper.nt + 1, 2))
+        for k, mu_t in enumerate(self._time_rows(mu)):
+            alpha_bar = est.alpha(est.lambda_coeffs, mu_t, est.mu_bar)
+            gamma_bar = est.gamma(est.lambda_coeffs, mu_t, est.mu_bar)
+            alpha_hat = est.alpha(est.lambda_coeffs, mu_t, est.mu_hat)
+            coef[k] = np.sqrt(gamma_bar) / np.sqrt(alpha_bar), (1. / np.sqrt(alpha_hat)) / np.sqrt(alpha_bar)
+        return coef
 
     def _phi_device(self, mu):
         return self.engine.ctx.from_numpy(np.ascontiguousarray(self.source_coefficients(mu)))
@@ -82,6 +124,9 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         rtol, max_iter = self._solve_options(inverse_options)
         dt = self.T / self.time_stepper.nt
         U0 = self.initial_data.tensor[:, :, 0] if self.initial_data is not None else None
+        if self._tv:                                                       # one column of the batched export
+            U = self.solve_batch([mu], inverse_options=inverse_options)[0]
+            return BlockVectorArray(U.tensor.contiguous(), self.solution_space)
         if self._src is not None:
             U, info = eng.ctx.fom_implicit_euler_src(self.theta(mu), dt, self.time_stepper.nt, eng.A_diag, eng.A_cpl,
                                                      self._src['b_K'], self._phi_device(mu), U0=U0, rtol=rtol, max_iter=max_iter)
@@ -128,14 +173,19 @@ class InstationaryDuneDiscretization(DuneDiscretization):
                 rel = max(rel, self.last_solve_info['relative_residual'])
         else:
             rtol, max_iter = self._solve_options(inverse_options)
-            theta = np.stack([self.theta(mu) for mu in mus])
+            if self._tv:
+                theta = np.stack([self.diffusion_coefficients(mu) for mu in mus])   # [len(mus), nt + 1, Q]
+                native = eng.ctx.fom_implicit_euler_batch_tv
+            else:
+                theta = np.stack([self.theta(mu) for mu in mus])
+                native = eng.ctx.fom_implicit_euler_batch
             phi = np.stack([self.source_coefficients(mu) for mu in mus])                # [len(mus), nt + 1, K]
             b_K = self._src['b_K'] if self._src is not None else eng.b.reshape(1, eng.S, eng.t.n)
             U0 = self.initial_data.tensor[:, :, 0] if self.initial_data is not None else None
             trajs = []
             for m0 in range(0, len(mus), 64):
-                U, info = eng.ctx.fom_implicit_euler_batch(theta[m0:m0 + 64], self.T / nt, nt, eng.A_diag, eng.A_cpl, b_K,
-                                                           phi[m0:m0 + 64], U0=U0, rtol=rtol, max_iter=max_iter)
+                U, info = native(theta[m0:m0 + 64], self.T / nt, nt, eng.A_diag, eng.A_cpl, b_K, phi[m0:m0 + 64], U0=U0, rtol=rtol,
+                                 max_iter=max_iter)
                 its, rel = its + info['iterations'], max(rel, info['relative_residual'])
                 trajs += [BlockVectorArray.view_of(U[:, :, :, m].permute(1, 2, 0), self.solution_space) for m in range(U.shape[3])]
         self.last_solve_info = {'iterations': its, 'relative_residual': rel}
@@ -145,12 +195,16 @@ class InstationaryDuneDiscretization(DuneDiscretization):
 
     def solve_stationary(self, mu, inverse_options=None):
         """The elliptic solve of the underlying discretization (the limit ``t -> oo``)."""
+        if self._tv:
+            raise NotImplementedError('solve_stationary: the diffusion coefficients depend on time (theta_q(t, mu))')
         if self._src is not None:
             raise NotImplementedError('solve_stationary: the source depends on time (f = sum_j phi_j(t, mu) f_j)')
         return DuneDiscretization.solve(self, mu, inverse_options=inverse_options)
 
     def solve_stationary_batch(self, mus, inverse_options=None):
         """The elliptic ``solve_batch`` of the underlying discretization: one array of ``len(mus)`` stationary solutions."""
+        if self._tv:
+            raise NotImplementedError('solve_stationary_batch: the diffusion coefficients depend on time (theta_q(t, mu))')
         if self._src is not None:
             raise NotImplementedError('solve_stationary_batch: the source depends on time (f = sum_j phi_j(t, mu) f_j)')
         if self.engine.S_ext != self.engine.S:                       # (the elliptic loop would call this class's ``solve``)
@@ -197,6 +251,44 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         R = eng.ctx.fom_apply(self.theta(mu), eng.A_diag, eng.A_cpl, dU.tensor.contiguous())
         return eng.ctx.mass_inverse_norm2(R).sum(dim=0).cpu().numpy()
 
+    def estimate(self, U, mu=None, decompose=False):
+        if not self._tv:
+            return DuneDiscretization.estimate(self, U, mu, decompose=decompose)
+        return self._estimate_tv(U, mu)
+
+    def _estimate_tv(self, U, mu):
+        """The parabolic estimate of a full-order trajectory with the coefficient frozen per step (the verification path of
+        ``lrbms_reduced_parabolic_estimate_batch_tv``): the elliptic indicators of U_k at row k of
+        ``diffusion_coefficients`` / ``source_coefficients``, the time residual of U_{k+1} - U_k with A(theta_t[k + 1])
+        (``lrbms_fom_apply`` per step), the nonconformity of the differences as before (it reads no theta)."""
+        import torch
+        eng, est = self.engine, self.estimator
+        nt = self.time_stepper.nt
+        dt = self.T / nt
+        assert len(U) == nt + 1, 'estimate: a trajectory of nt + 1 vectors'
+        th, rows, coef = self.diffusion_coefficients(mu), self._time_rows(mu), self._estimator_coefficients(mu)
+        phi = self._phi_device(mu) if self._src is not None else None
+        cols = []
+        for k in range(nt + 1):
+            if self._src is not None:
+                cols.append(local_estimates(eng, U.tensor[:, :, k:k + 1].contiguous(), th[k], self._src, phi[k:k + 1]))
+            else:
+                cols.append(DuneDiscretization._local_estimates(self, U[k:k + 1], rows[k]))
+        nc, r, df = (torch.cat([c[i] for c in cols], dim=1) for i in range(3))       # [S, nt + 1]
+        if est.sqrt_local:
+            nc, r, df = (x.abs().sqrt() for x in (nc, r, df))
+        sc = 2 * np.sqrt(dt / 3)
+        eta = (coef[:, 0] * nc.norm(dim=0).cpu().numpy() + coef[:, 1] * (r + df).norm(dim=0).cpu().numpy()) * sc
+        dU = U[1:] - U[:-1]
+        tr = np.empty(nt)
+        for k in range(nt):
+            R = eng.ctx.fom_apply(th[k + 1], eng.A_diag, eng.A_cpl, dU.tensor[:, :, k:k + 1].contiguous())
+            tr[k] = float(eng.ctx.mass_inverse_norm2(R).sum())
+        time_residual = np.sqrt(tr * (dt / 3))
+        time_deriv_nc = np.sqrt(np.maximum(self._local_estimates(dU, rows[1])[0].cpu().numpy() * (1 / dt), 0.0))
+        est_value = np.linalg.norm(eta) + np.linalg.norm(time_residual) + np.sqrt(float(np.sum(time_deriv_nc ** 2)))
+        return est_value, tuple(x.cpu().numpy() * sc for x in (nc, r, df)) + (time_residual, time_deriv_nc)
+
     def _reconstruction_terms(self, U, mu):
         """``r_l2(BU_R, BU_R) - r_l2(F_R, F_R) - 2 r_ud(BUF_R, U_r)`` per subdomain and vector (estimators.py:65-68,
         :80-83) -> [S, len(U)]:  BU = A(mu) U (``lrbms_fom_apply``), the ``r_l2`` terms are ``M^-1`` norms
@@ -226,6 +318,19 @@ def _source_components(p):
     return source_components(p)
 
 
+def _lambda_reads_time(p):
+    """True if a coefficient of ``p['lambda']`` names ``'_t'`` in its ``parameter_type``."""
+    lam = p['lambda']
+    return isinstance(lam, dict) and any('_t' in coefficient_parameter_type(c) for c in lam['coefficients'])
+
+
+def _at_time_zero(mu, parameter_type):
+    """``mu`` as a ``Parameter`` with ``_t = 0`` unless it brings a ``'_t'`` of its own."""
+    from pylrbms_amd.parameters import Parameter, parse_parameter
+    mu = parse_parameter(mu, parameter_type)
+    return mu if '_t' in mu else Parameter(dict(mu, _t=np.array(0.0)))
+
+
 def _setup_sources(d, funcs, coeffs):
     """b_K, f_smp_K and F2 of the K source components (``pylrbms_amd.sources.setup_sources``), kept as ``d._src``."""
     d._src = setup_sources(d.engine, funcs, coeffs)
@@ -236,6 +341,18 @@ def discretize(grid_and_problem_data, T, nt, solver_options=None, mpi_comm=None,
     """Reference :43-95.  Returns ``(d, d_data)``.  ``p['f']`` may be ``{'functions': [...], 'coefficients': [...]}`` with any
     number of components and coefficients of ``mu`` and ``'_t'`` (module docstring).  ``conventions``: the switches of the elliptic
     ``discretize`` (e.g. ``{'oswald_vertex_patch': True}``), handed on to it."""
+    tv = _lambda_reads_time(grid_and_problem_data)
+    if tv:
+        grid = grid_and_problem_data['grid']
+        if len(grid.subdomains_on_rank) != grid.num_subdomains:
+            raise NotImplementedError('time-dependent diffusion coefficients (theta_q(t, mu)) need all subdomains on one rank')
+        if elliptic_reconstruction:
+            raise NotImplementedError('elliptic_reconstruction with time-dependent diffusion coefficients (theta_q(t, mu))')
+        # the reference parameters of alpha / gamma and of the energy product: without a '_t' of their own they sit at _t = 0
+        ptype = {k: v for k, v in grid_and_problem_data.get('parameter_type', {}).items() if k != '_t'}
+        grid_and_problem_data = dict(grid_and_problem_data, parameter_type=ptype,
+                                     mu_bar=_at_time_zero(grid_and_problem_data['mu_bar'], ptype),
+                                     mu_hat=_at_time_zero(grid_and_problem_data['mu_hat'], ptype))
     src = _source_components(grid_and_problem_data)
     if src is not None:
         from pylrbms_amd.functions import SumFunction
@@ -247,9 +364,11 @@ def discretize(grid_and_problem_data, T, nt, solver_options=None, mpi_comm=None,
         # the elliptic discretization is built on sum_j f_j (its quadrature orders cover every component); its own b / f2
         # are not read on this path
         grid_and_problem_data = dict(grid_and_problem_data, f=SumFunction(src[0], [1.0] * len(src[0]), name='f_sum'))
-    d, d_data = discretize_ell(grid_and_problem_data, solver_options, mpi_comm, device_index=device_index, conventions=conventions)
+    d, d_data = discretize_ell(grid_and_problem_data, solver_options, mpi_comm, device_index=device_index, conventions=conventions,
+                               _time_dependent_lambda=tv)
     assert isinstance(d.parameter_space, CubicParameterSpace)              # :45
     d.__class__ = InstationaryDuneDiscretization
+    d._tv = tv
     d.T = float(T)
     d.time_stepper = ImplicitEulerTimeStepper(nt=nt, solver_options='operator')   # :87
     d.initial_data = d.solution_space.zeros(1, d.engine.ctx)               # :82

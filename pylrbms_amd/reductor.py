@@ -714,9 +714,17 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
         self.T, self.time_stepper = self.d.T, self.d.time_stepper
         self.mass = self.M_red
 
+    def _tv(self):
+        """The diffusion coefficients depend on time (theta_q(t, mu)): the ``_tv`` exports, one column for ``solve`` /
+        ``estimate``."""
+        return bool(getattr(self.d, '_tv', False))
+
     def solve(self, mu, inverse_options=None):
         eng = self.d.engine
         dt = self.T / self.time_stepper.nt
+        if self._tv():
+            U = self.solve_batch([mu])[0]
+            return ReducedVectorArray(U.tensor.contiguous())
         if self.rhs_red_K is not None:                               # time-dependent source: sum_j phi[k+1][j] rhs_red_K[j]
             U, info = eng.ctx.reduced_implicit_euler_src(self.d.theta(mu), dt, self.time_stepper.nt, self.B_sys, self.M_red,
                                                          self.rhs_red_K, self.d._phi_device(mu))
@@ -748,6 +756,16 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
         out, its, rel = [], 0, 0.0
         for b0 in range(0, len(mus), 64):
             chunk = mus[b0:b0 + 64]
+            if self._tv():                                           # a theta row per step; phi beside it with a time-dependent source
+                theta_t = np.stack([self.d.diffusion_coefficients(mu) for mu in chunk])
+                if self.rhs_red_K is not None:
+                    phi = self._torch.stack([self.d._phi_device(mu) for mu in chunk]).contiguous()
+                    U, info = eng.ctx.reduced_implicit_euler_batch_tv(theta_t, dt, nt, self.B_sys, self.M_red, self.rhs_red_K, phi=phi)
+                else:
+                    U, info = eng.ctx.reduced_implicit_euler_batch_tv(theta_t, dt, nt, self.B_sys, self.M_red, self.rhs_red)
+                its, rel = its + info['iterations'], max(rel, info['relative_residual'])
+                out += [ReducedVectorArray.view_of(U[..., m].permute(1, 2, 0)) for m in range(len(chunk))]
+                continue
             thetas = np.array([self.d.theta(mu) for mu in chunk])
             if self.rhs_red_K is not None:                           # time-dependent source: a coefficient table per parameter
                 phi = self._torch.stack([self.d._phi_device(mu) for mu in chunk]).contiguous()
@@ -804,24 +822,35 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
         for b0 in range(0, len(mus), 64):
             chunk = mus[b0:b0 + 64]
             U = panel[..., b0:b0 + len(chunk)].contiguous() if panel is not None else self._panel_of(Us[b0:b0 + len(chunk)])
-            thetas = np.array([self.d.theta(mu) for mu in chunk])
-            coef = np.empty((len(chunk), 2))
-            for m, mu in enumerate(chunk):
-                alpha_bar = est.alpha(est.lambda_coeffs, mu, est.mu_bar)
-                gamma_bar = est.gamma(est.lambda_coeffs, mu, est.mu_bar)
-                alpha_hat = est.alpha(est.lambda_coeffs, mu, est.mu_hat)
-                coef[m] = np.sqrt(gamma_bar) / np.sqrt(alpha_bar), (1. / np.sqrt(alpha_hat)) / np.sqrt(alpha_bar)
+            if self._tv():
+                thetas = np.stack([self.d.diffusion_coefficients(mu) for mu in chunk])      # [len(chunk), nt + 1, Q]
+                coef = np.stack([self.d._estimator_coefficients(mu) for mu in chunk])       # [len(chunk), nt + 1, 2]
+                native = eng.ctx.reduced_parabolic_estimate_batch_tv
+            else:
+                thetas = np.array([self.d.theta(mu) for mu in chunk])
+                coef = np.empty((len(chunk), 2))
+                native = eng.ctx.reduced_parabolic_estimate_batch
+                for m, mu in enumerate(chunk):
+                    alpha_bar = est.alpha(est.lambda_coeffs, mu, est.mu_bar)
+                    gamma_bar = est.gamma(est.lambda_coeffs, mu, est.mu_bar)
+                    alpha_hat = est.alpha(est.lambda_coeffs, mu, est.mu_hat)
+                    coef[m] = np.sqrt(gamma_bar) / np.sqrt(alpha_bar), (1. / np.sqrt(alpha_hat)) / np.sqrt(alpha_bar)
             src = {}
             if self.rhs_red_K is not None:
                 src = dict(phi=self._torch.stack([self.d._phi_device(mu) for mu in chunk]).contiguous(), F2=self.d._src['F2'],
                            r_fd_K=self.r_fd_K)
-            res = eng.ctx.reduced_parabolic_estimate_batch(thetas, coef, dt, nt, U, self.B_sys, self.M_red, self.grams, eng.f2, eng.ceps,
-                                                           eng.hdiam, sqrt_local=est.sqrt_local, **src)
+            res = native(thetas, coef, dt, nt, U, self.B_sys, self.M_red, self.grams, eng.f2, eng.ceps, eng.hdiam,
+                         sqrt_local=est.sqrt_local, **src)
             loc, tdn, tr, e = (res[k].cpu().numpy() for k in ('eta_loc', 'time_deriv_nc', 'time_residual', 'est'))
             for m in range(len(chunk)):
                 out.append((float(e[m]), tuple(np.ascontiguousarray(loc[i, :, :, m].T) for i in range(3))
                             + (np.ascontiguousarray(tr[:, m]), np.ascontiguousarray(tdn[:, :, m].T))))
         return out
+
+    def estimate(self, U, mu=None, decompose=False):
+        if not self._tv():
+            return ReducedDiscretization.estimate(self, U, mu, decompose=decompose)
+        return self.estimate_batch([U], [mu])[0]                     # one column of lrbms_reduced_parabolic_estimate_batch_tv
 
     def _local_estimates(self, U, mu):
         """With a time-dependent source: the reduced counterpart of InstationaryDuneDiscretization._local_estimates -- the
