@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'liblrbms_hip.so')
 SOURCES = ['capi.hip', 'assemble.hip', 'apply.hip', 'gemm.hip', 'fused.hip', 'online.hip', 'enrich.hip', 'fom.hip', 'pod.hip',
-           'lrbms3d.hip', 'sources3d.hip', 'enrich3d.hip']
+           'lrbms3d.hip', 'online3d.hip', 'sources3d.hip', 'enrich3d.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
 

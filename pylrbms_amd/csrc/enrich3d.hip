@@ -1,6 +1,6 @@
 // 3D / P2 path: online enrichment -- the Dirichlet correction blocks and the batched neighbourhood corrector PCG k3l_* behind
 // lrbms3_assemble_dirichlet_correction and lrbms3_local_correction_solve.  No other file calls into this one; it combines its
-// operator with launch_combine and inverts the element blocks with launch_fom_block_inverse (both lrbms3d.hip).
+// operator with launch_combine and inverts the element blocks with launch_fom_block_inverse (online3d.hip, lrbms3d.hip).
 #include "lrbms3d_dev.h"
 
 using namespace lrbms3;

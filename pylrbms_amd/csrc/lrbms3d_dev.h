@@ -1,5 +1,6 @@
 // Internal definitions shared by the 3D / P2 translation units of liblrbms_hip.so (gfx950 only): the counterpart of
-// lrbms_dev.h for lrbms3d.hip, sources3d.hip and enrich3d.hip.  Everything that crosses a file sits in the namespace lrbms3
+// lrbms_dev.h for lrbms3d.hip (context, assembly, pass, estimator, full-order solvers), online3d.hip (reduced solvers),
+// sources3d.hip and enrich3d.hip.  Everything that crosses a file sits in the namespace lrbms3
 // (the 2D units keep internals of the same names); no kernel is defined here: a kernel that a second file needs is reached
 // through its home file's launch_* function.
 #pragma once
@@ -93,6 +94,8 @@ __device__ inline bool xcd_block(int nblk, int S, int& xblk, int& s) {
 inline unsigned xcd_grid(int nblk, int S) { return (unsigned)((S + 7) / 8 * 8 * nblk); }
 
 struct QV { double v[8]; };
+// theta table of <= 16 columns: a group of the batched reduced solvers (online3d.hip), a panel of the batched full-order ones (lrbms3d.hip)
+struct TB { double v[16][8]; };     // theta [nmu][Q]
 
 // elements (10 rows each) per workgroup of the full-order solver kernels and of the kernels that share their partial-sum layout
 constexpr int FOM_EPB = 24;
@@ -103,8 +106,18 @@ inline QV make_theta(int Q, const double* theta) {
   return th;
 }
 
-// ---- host functions that cross files: kernels of lrbms3d.hip that enrich3d.hip launches (the bodies are one hipLaunchKernelGGL each)
+// ---- host functions that cross files.  Kernels that a second file launches (the bodies are one hipLaunchKernelGGL each, grid,
+// block and LDS as at the launches of the home file):
+// online3d.hip, called by lrbms3d.hip (the full-order solvers) and enrich3d.hip
 void launch_combine(hipStream_t st, long per_q, int Q, const QV& th, const double* B, double* Amu);                  // k3_combine
+// online3d.hip, called by lrbms3d.hip (fom_euler_run)
+void launch_axpy(hipStream_t st, long total, const double* x, double* y);                                            // k3p_axpy
+// lrbms3d.hip, called by enrich3d.hip
 void launch_fom_block_inverse(hipStream_t st, const T3& t, const double* Amu, double* Dinv);                         // k3f_block_inverse
+// lrbms3d.hip, called by online3d.hip (red_cg, red_euler_run)
+void launch_reduce1(hipStream_t st, int S, const double* part, double* out);                                         // k3_reduce1
+// lrbms3d.hip (owner of ctx->blas), called there (fom_coarse) and by online3d.hip: A^-1 of a dense SPD matrix into Id (identity on entry) by
+// rocSOLVER potrf / potrs on the stream; hinfo != 0 (and LRBMS_OK) when A is not positive definite
+int dense_spd_inverse(lrbms3_ctx* ctx, hipStream_t st, long M, double* A, double* Id, rocblas_int* pinfo, rocblas_int& hinfo);
 
 }  // namespace lrbms3

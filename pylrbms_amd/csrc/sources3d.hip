@@ -1,6 +1,6 @@
 // 3D / P2 path: affine sources -- k3_source_gram, k3_project_sources, k3_source_terms and lrbms3_combine_sources, which launches
 // the shape-agnostic kernel of online.hip through launch_combine_sources_base.  No other file calls into this one.
-// (lrbms3_reduced_solve_batch_src and the _src forms of the implicit Euler live with their solvers in lrbms3d.hip.)
+// (lrbms3_reduced_solve_batch_src and the _src forms of the implicit Euler live with their solvers in online3d.hip and lrbms3d.hip.)
 #include "lrbms3d_dev.h"
 
 using namespace lrbms3;

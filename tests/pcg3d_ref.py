@@ -1,4 +1,4 @@
-"""NumPy restatement of the single and stationary 3D / P2 solvers (pylrbms_amd/csrc/lrbms3d.hip), iterate by iterate, on top of
+"""NumPy restatement of the single and stationary 3D / P2 solvers (pylrbms_amd/csrc/online3d.hip, lrbms3d.hip), iterate by iterate, on top of
 tests/pcg_ref.py, tests/fom_batch3d_ref.py and tests/parabolic_batch3d_ref.py.  Nothing here is new arithmetic: every function
 names the operator and the preconditioner of one export and hands them to ``pcg_ref.pcg_iterate``.
 

@@ -3,7 +3,7 @@
 A converged CG solution does not depend on the preconditioner, so the parity tests cannot see a wrong inverse block, a dropped
 coarse term, a coarse level built at the wrong parameter or a partial sum that skips entries.  The k-th iterate from x_0 = 0 can:
 lrbms3_reduced_solve, lrbms3_reduced_solve_batch(_src), lrbms3_fom_solve and the single implicit-Euler steppers honour
-``max_iter`` exactly (``red_cg``, ``red_batch_iterate``, ``fom_cg`` in pylrbms_amd/csrc/lrbms3d.hip): a call with max_iter = k
+``max_iter`` exactly (``red_cg``, ``red_batch_iterate``, ``fom_cg`` in pylrbms_amd/csrc/online3d.hip and lrbms3d.hip): a call with max_iter = k
 returns LRBMS_E_NOT_CONVERGED, leaves x_k in the caller's array and info = (k, |r_k| / |b|).  Every cell calls the raw export
 through ``ctx.lib`` with NaN-poisoned ``work`` and output for k in K_STEPS (``check_iterates`` of tests/test_pcg_iterates_gpu.py
 with its TOL_X = 1e-10 and TOL_RES = 1e-8, unchanged), closes with one converged call against a direct solve, and shows for every
@@ -11,7 +11,7 @@ mutant of tests/pcg3d_ref.py that the product's x_2 misses the mutant reference 
 
 The reference operators are the product's own B_sys / rhs_red / A_diag / A_cpl / M_red copied to the host (pinned to the oracle
 elsewhere): the cells test the solvers alone.  The cell lists are module constants; tests/test_pcg_iterates3d_host.py mirrors the
-host dispatch of lrbms3d.hip and proves on the CPU that they reach every branch and that every mutant is separable.
+host dispatch of online3d.hip / lrbms3d.hip and proves on the CPU that they reach every branch and that every mutant is separable.
 
 The Euler cells compare U[1] - U[0] with the correction's iterate.  They found that a step which missed rtol returned before u_k
 was added and left the bare correction in U[k + 1]; ``fom_euler_run`` and ``red_euler_run`` add u_k first now, as the batched

@@ -1,7 +1,7 @@
 """The restatements of tests/pcg3d_ref.py and the cells of tests/test_pcg_iterates3d_gpu.py, on the CPU.
 
-- A mirror of the host dispatch of pylrbms_amd/csrc/lrbms3d.hip, read from the source text: ``launch_matvec3`` (N <= 16 | N <= 32 |
-  VALU), ``red_batch_run`` (number of groups, installed or not), the ``nc`` ladder of ``fom_coarse``, both loops of
+- A mirror of the host dispatch of pylrbms_amd/csrc/online3d.hip and lrbms3d.hip, read from the source text: ``launch_matvec3``
+  (N <= 16 | N <= 32 | VALU), ``red_batch_run`` (number of groups, installed or not), the ``nc`` ladder of ``fom_coarse``, both loops of
   ``sum_partials`` and of ``k3_reduce1`` as functions of the partial count, and the dynamic LDS of ``k3_block_inverse`` either side
   of 65 536 bytes.  The cell lists of the GPU module must reach every branch; the ``nc S > 8192 -> none`` rung of ``fom_coarse``
   (8 193 subdomains) is checked here only.
@@ -193,11 +193,13 @@ def test_the_loops_honour_max_iter_and_the_euler_steps_finish_a_missed_step():
         assert 'while (it < max_iter) {' in body and 'k < check && it < max_iter; ++k, ++it' in body
         assert 'if (info) info[0] = it, info[1] = rel;' in body
     assert 'if (G.done || G.it >= max_iter) continue;' in _function(src, 'int red_batch_iterate(')
-    for head in ('int fom_euler_run(', 'int red_euler_run('):
+    # k3p_axpy lives beside red_euler_run (online3d.hip), which launches it directly; fom_euler_run reaches it through launch_axpy
+    for head, launch in (('int fom_euler_run(', 'launch_axpy('), ('int red_euler_run(', 'hipLaunchKernelGGL(k3p_axpy')):
         body = _function(src, head)
         miss = body.index('if (rc != LRBMS_OK && rc != LRBMS_E_NOT_CONVERGED) return rc;')
-        axpy = body.index('hipLaunchKernelGGL(k3p_axpy', miss)
+        axpy = body.index(launch, miss)
         assert body.index('if (rc != LRBMS_OK) return rc;', axpy) > axpy
+    assert 'hipLaunchKernelGGL(k3p_axpy' in _function(src, 'void launch_axpy(')
 
 
 def test_mirror_fails_on_a_changed_dispatch():
