@@ -12,13 +12,28 @@ from scipy.sparse.linalg import splu
 
 import pcg_ref
 from fom_euler_batch_ref import combine as combine_fom
-from parabolic_batch_ref import mass_operator, step_rhs
+from parabolic_batch_ref import mass_operator, step_blocks, step_rhs
 from parabolic_estimate_batch_ref import time_residual_panel
 
 
 def step_rows(theta_t):
     """The nt operator rows of the steps 0 .. nt - 1: rows 1 .. nt of the table (the right limit)."""
     return np.asarray(theta_t, dtype=np.float64)[1:]
+
+
+def step_mean(thetas_t, first=1, last=None):
+    """Where the drivers build the preconditioner (reduced) and the coarse level (full order) of a call: the mean of
+    thetas_t [nmu, nt + 1, Q] over the columns and the rows 1 .. nt -> [Q].  ``first`` / ``last`` (inclusive) select OTHER rows:
+    the wrong variants (row 1 only: last = 1; the rows 0 .. nt: first = 0) that the iterate tests must tell from the right one."""
+    thetas_t = np.asarray(thetas_t, dtype=np.float64)
+    last = thetas_t.shape[1] - 1 if last is None else last
+    return thetas_t[:, first:last + 1].mean(axis=(0, 1))
+
+
+def row_step_blocks(B, M_red, theta_row, dt):
+    """The step operator of one table row in the fixed-slot layout [S, 5, N, N]: M_red on the self slot + dt sum_q theta_row[q] B_q
+    (``parabolic_batch_ref.step_blocks`` at that row; the step k -> k + 1 of column m takes thetas_t[m, k + 1])."""
+    return step_blocks(B, M_red, np.asarray(theta_row, dtype=np.float64), dt)
 
 
 def dense_euler_tv(B, M_red, nbr, theta_t, dt, nt, rhs=None, rhs_K=None, phi=None, U0=None, keep=None, rows=None):
