@@ -444,6 +444,43 @@ int lrbms3_reduced_implicit_euler_batch_src(lrbms3_ctx* ctx, int32_t Q, int32_t 
                                             const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
                                             void* stream);
 
+/* -- batched parabolic estimates: the estimate of nmu <= 64 reduced trajectories in one call -------------------------
+ * The 3D counterpart of lrbms_reduced_parabolic_estimate_batch: for column m of the panel U [nt+1][S][N][nmu] (parameter fastest, as
+ * lrbms3_reduced_implicit_euler_batch returns it; read only) with theta[m], term for term what
+ * InstationaryReducedDiscretization3D.estimate computes for one trajectory:
+ *   eta_loc       [3][nt+1][S][nmu]  nc, r, df: the rows of lrbms3_reduced_estimate_batch on U[k], times 2 sqrt(dt / 3)
+ *   time_deriv_nc [nt][S][nmu]       sqrt(max(nc(U[k+1] - U[k]), 0) / dt)
+ *   time_residual [nt][nmu]          sqrt(dt / 3 sum_s y^T M_red[s]^-1 y),  y = (sum_q theta_qm B_sys_q (U[k+1] - U[k]))_s
+ *   eta           [nt+1][nmu]        2 sqrt(dt / 3) (coef[m][0] |nc[:, k]|_2 + coef[m][1] |(r + df)[:, k]|_2), norms of the raw rows over
+ *                                    the subdomains
+ *   est           [nmu]              |eta|_2 + |time_residual|_2 + |time_deriv_nc|_F
+ * theta [nmu][Q] and coef [nmu][2] = (sqrt(gamma_bar / alpha_bar), 1 / sqrt(alpha_hat alpha_bar)) are HOST arrays, read before the
+ * call returns (they travel as kernel arguments).  B_sys, M_red as for lrbms3_reduced_implicit_euler_batch; G_nc .. hdiam as for
+ * lrbms3_reduced_estimate_batch.  On zero-padded basis columns M_red counts as the identity (lrbms3_reduced_time_residual).
+ * Source f(t, mu) = sum_j phi_j f_j with K >= 1 components: phi [nmu][nt+1][K] (DEVICE; row k: the time of U[k]), F2 [S][K][K],
+ * r_fd_K [K][S][QN], bdiv_K [K][S][n_T] as for lrbms3_reduced_source_terms, and the caller passes zeroed f2 / r_fd / bdiv; the f terms
+ * of column m at step k are added to its r row.  K = 0: the four pointers are NULL and f2 / r_fd / bdiv are the discretization's.
+ * Per slab U[k] the call launches what lrbms3_reduced_estimate_batch launches (either form, LRBMS3_OPT_ESTIMATE_VALU); the nc form of
+ * the differences runs in a kernel of its own that reads As, G_nc, Cn and ebar only (row 0 of the full estimate where the 16-column
+ * form is not in use); the time residual uses the panel matvec of lrbms3_reduced_solve_batch (LRBMS3_OPT_SOLVE_VALU) on groups of
+ * <= 16 columns, no combined operator is written.  Everything runs on `stream`, without a host synchronisation and without atomics:
+ * fixed summation orders, repeat calls give the same bits, equal columns give equal bits wherever they stand.  Nothing but work
+ * and the five outputs is written; a preconditioner installed with lrbms3_reduced_precond_use is neither read nor replaced.
+ * Limits: 1 <= nmu <= 64, N <= 32, Q <= 8, Q N <= 64, nt >= 1, dt > 0, 0 <= K <= 64, S_ext == S; every violation, every null pointer
+ * (the K pointers: all set with K >= 1, all NULL with K = 0) and a template whose estimate does not fit the LDS is LRBMS_E_INVALID
+ * before any launch, outputs and work untouched.  work: lrbms3_reduced_parabolic_estimate_batch_work_size(N, nmu, nt) doubles (-1 for
+ * arguments outside the limits or without a mesh).  2D: lrbms_reduced_parabolic_estimate_batch. */
+int64_t lrbms3_reduced_parabolic_estimate_batch_work_size(lrbms3_ctx* ctx, int32_t N, int32_t nmu, int32_t nt);
+int lrbms3_reduced_parabolic_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, int32_t nt, double dt,
+                                            const double* theta, const double* coef, const double* U, const double* B_sys,
+                                            const double* M_red, const double* G_nc, const double* G_bb, const double* G_rdd,
+                                            const double* G_ab, const double* G_aa, const double* r_fd, const double* Rb, const double* Yb,
+                                            const double* Dp, const double* Xab, const double* As, const double* Cn, const double* ebar,
+                                            const double* Bbb, const double* bdiv, const double* f2, const double* ceps, double hdiam,
+                                            const double* phi, const double* F2, const double* r_fd_K, const double* bdiv_K, double* work,
+                                            double* eta_loc, double* time_deriv_nc, double* time_residual, double* eta, double* est,
+                                            void* stream);
+
 /* -- online enrichment ------------------------------------------------------------------------------------------------------ */
 /* Dirichlet correction blocks of the neighbourhood problems: on every coupling face of subdomain s, for the own side element,
  * the Dirichlet-face block (inside coefficient) minus the inner-face own / own block already contained in A_diag (mesh tables

@@ -89,6 +89,10 @@ SIGNATURES3 = {
                                                            c_dbl, c_i32, _P_DBL, c_vp]),
     'lrbms3_reduced_implicit_euler_batch_src': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp,
                                                                c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    # batched parabolic estimates
+    'lrbms3_reduced_parabolic_estimate_batch_work_size': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
+    'lrbms3_reduced_parabolic_estimate_batch': (ctypes.c_int, [c_vp] + [c_i32] * 5 + [c_dbl, _P_DBL, _P_DBL] + [c_vp] * 20 + [c_dbl] +
+                                                [c_vp] * 11),
     # online enrichment
     'lrbms3_assemble_dirichlet_correction': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms3_local_correction_work_size': (c_i64, [c_vp, c_i32]),
@@ -715,6 +719,47 @@ class Native3DContext(_native.ContextBase):
                                                               self._stream())
         self._check(rc, 'lrbms3_reduced_implicit_euler_batch_src')
         return U, (int(info[0]), float(info[1]))
+
+    # ------------------------------------------------------------------ batched parabolic estimates
+    def reduced_parabolic_estimate_batch(self, Q, thetas, coef, dt, nt, U, B_sys, M_red, out, ops, hdiam, phi=None, F2=None, r_fd_K=None,
+                                         bdiv_K=None, work=None):
+        """The parabolic estimate of the nmu <= 64 trajectories of the panel U [nt + 1, S, N, nmu] in one call
+        (``lrbms3_reduced_parabolic_estimate_batch``): thetas [nmu, Q], coef [nmu, 2] (host); ``out`` / ``ops`` as for
+        ``reduced_estimate_batch``; with a time-dependent source phi [nmu, nt + 1, K] (host or device), F2 [S, K, K], r_fd_K
+        [K, S, QN], bdiv_K [K, S, n_T] and ``out`` / ``ops`` with zeroed r_fd / f2 / bdiv.  Returns a dict of device tensors:
+        eta_loc [3, nt + 1, S, nmu], time_deriv_nc [nt, S, nmu], time_residual [nt, nmu], eta [nt + 1, nmu], est [nmu]."""
+        S, N, nt = self.S, int(B_sys.shape[-1]), int(nt)
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        nmu = th.shape[0]
+        cf = np.ascontiguousarray(coef, dtype=np.float64)
+        assert th.shape == (nmu, Q) and cf.shape == (nmu, 2), 'thetas must be [nmu, Q], coef [nmu, 2]'
+        shp = self.out_shapes(Q, N)
+        names = ('G_nc', 'G_bb', 'G_rdd', 'G_ab', 'G_aa', 'r_fd', 'Rb', 'Yb', 'Dp', 'Xab', 'As', 'Cn')
+        args = [self._ptr(U, (max(nt, 0) + 1, S, N, nmu), 'U'), self._ptr(B_sys, (Q, S, 7, N, N), 'B_sys'),
+                self._ptr(M_red, (S, N, N), 'M_red')] + [self._ptr(out[k], shp[k], k) for k in names]
+        args += [self._ptr(ops['ebar'], (S, self.n_T, 100), 'ebar'), self._ptr(ops['Bbb'], (S, self.n_T, 16), 'Bbb'),
+                 self._ptr(ops['bdiv'], (S, self.n_T), 'bdiv'), self._ptr(ops['f2'], (S,), 'f2'), self._ptr(ops['ceps'], (S,), 'ceps')]
+        K, src = 0, [c_vp(None)] * 4
+        if phi is not None:
+            K = int(F2.shape[1])
+            ph = self._dev2(phi, (nmu, max(nt, 0) + 1, K), 'phi')
+            src = [c_vp(ph.data_ptr()), self._ptr(F2, (S, K, K), 'F2'), self._ptr(r_fd_K, (K, S, Q * N), 'r_fd_K'),
+                   self._ptr(bdiv_K, (K, S, self.n_T), 'bdiv_K')]
+        need = int(self.lib.lrbms3_reduced_parabolic_estimate_batch_work_size(self.handle, N, nmu, nt))
+        if need < 0:
+            raise NativeError('reduced_parabolic_estimate_batch: bad N / nmu / nt')
+        if work is None:
+            work = self.empty(need)
+        if work.numel() < need:
+            raise NativeError('reduced_parabolic_estimate_batch: work too small')
+        res = {'eta_loc': self.empty(3, nt + 1, S, nmu), 'time_deriv_nc': self.empty(nt, S, nmu), 'time_residual': self.empty(nt, nmu),
+               'eta': self.empty(nt + 1, nmu), 'est': self.empty(nmu)}
+        rc = self.lib.lrbms3_reduced_parabolic_estimate_batch(
+            self.handle, Q, N, K, nmu, nt, float(dt), th.ctypes.data_as(_P_DBL), cf.ctypes.data_as(_P_DBL), *args, float(hdiam), *src,
+            c_vp(work.data_ptr()), *[c_vp(res[k].data_ptr()) for k in ('eta_loc', 'time_deriv_nc', 'time_residual', 'eta', 'est')],
+            self._stream())
+        self._check(rc, 'lrbms3_reduced_parabolic_estimate_batch')
+        return res
 
     # ------------------------------------------------------------------ online enrichment (DESIGN.md 9.11)
     def assemble_dirichlet_correction(self, lam):

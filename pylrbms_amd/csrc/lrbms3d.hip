@@ -1382,12 +1382,6 @@ __device__ inline double block_sum(double v, double* red) {   // fixed-order tre
   return red[0];
 }
 
-struct EA {
-  const double *u, *G_nc, *G_bb, *G_rdd, *G_ab, *G_aa, *r_fd, *Rb, *Yb, *Dp, *Xab, *As, *Cn, *ebar, *Bbb, *bdiv, *f2, *ceps;
-  double hdiam;
-  double* eta;
-};
-
 __global__ __launch_bounds__(256) void k3_estimate(T3 t, int Q, int N, QV th, EA a) {
   extern __shared__ double lds[];
   const int s = blockIdx.x, tid = threadIdx.x, QN = Q * N;
@@ -1938,6 +1932,95 @@ __global__ __launch_bounds__(64 * EST_NW) void k3_estimate_batch16(T3 t, int Q, 
   }
 }
 
+// ---- the nonconformity form ALONE for 16 columns per pass (the batched parabolic estimate evaluates it on the differences
+// U[k+1] - U[k]): nc = u^T G_nc u + 2 (Cn u) . z + sum_e ze^T E ze with z = sum_sides As u_a, the same panel layout, strips and
+// element tiles as k3_estimate_batch16; a.eta [S][nmu].  Of the estimator operators it reads As, G_nc, Cn and ebar only.
+// Without zf and the side elements nothing orders the terms but z, so the work is two flat item lists dealt round-robin to the 16
+// waves: A = the (side, strip) tiles of As and the strips of G_nc; B (behind z) = the strips of Cn and, starting at the wave where
+// those stop, the boundary elements in fours.  The tiles of the sides go to zs [6][nvs][16] (no two lanes meet, no barrier per side
+// as in the full kernel) and a node's z is the sum of its (<= 3) memberships in the order of bnode_sides.
+__global__ __launch_bounds__(64 * EST_NW) void k3_estimate_nc_batch16(T3 t, int N, int nmu, int m0, EA a) {
+  extern __shared__ double lds[];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int mb = nmu - m0 < EST16 ? nmu - m0 : EST16;
+  double* us = lds;                        // [7][N][16]    coefficients of the neighbourhood
+  double* zs = us + 7 * N * 16;            // [6][nvs][16]  As u_a per side node
+  double* z = zs + 6 * t.nvs * 16;         // [nb][16]      neighbours' node averages at the boundary nodes
+  double* red = z + t.nb * 16;             // [EST_NW][16]  parts of the waves
+  for (int i = tid; i < 7 * N * 16; i += 64 * EST_NW) {
+    const int mm = i & 15, row = i >> 4, s2 = t.nbr[s * 7 + row / N];
+    us[i] = (s2 >= 0 && mm < mb) ? a.u[((long)s2 * N + row % N) * nmu + m0 + mm] : 0.0;
+  }
+  __syncthreads();
+  const double* u0p = us + 3 * N * 16;     // own coefficients [N][16]
+  const int nst = (t.nvs + 15) / 16, ngs = (N + 15) / 16, ncs = (t.nb + 15) / 16;
+  double p_nc = 0.0;                       // per lane: its column, part of the rows
+  for (int it = wave; it < 6 * nst + ngs; it += EST_NW) {
+    if (it < 6 * nst) {
+      const int side = it / nst, row0 = 16 * (it - side * nst);
+      const d4 T = est_strip(a.As + ((long)s * 6 * t.nvs + side * t.nvs) * N, N, row0, t.nvs, N, us + side_slot(side) * N * 16, li, lk);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = row0 + lk + 4 * r;
+        if (row < t.nvs) zs[(side * t.nvs + row) * 16 + li] = T[r];
+      }
+    } else {
+      const int row0 = 16 * (it - 6 * nst);
+      p_nc += est_dot(est_strip(a.G_nc + (long)s * N * N, N, row0, N, N, u0p, li, lk), u0p, row0, N, li, lk);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < t.nb * 16; i += 64 * EST_NW) {
+    const int bn = i >> 4, mm = i & 15;
+    double acc = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      const int sp = t.bnode_sides[bn * 3 + k];
+      if (sp >= 0) acc += zs[sp * 16 + mm];
+    }
+    z[i] = acc;
+  }
+  __syncthreads();
+  for (int it = wave; it < ncs; it += EST_NW)
+    p_nc += 2.0 * est_dot(est_strip(a.Cn + (long)s * t.nb * N, N, 16 * it, t.nb, N, u0p, li, lk), z, 16 * it, t.nb, li, lk);
+  // boundary elements: ze^T E ze as in k3_estimate_batch16 (T = E ze a 10 x 16 tile, K = 10, four elements per wave in flight)
+  constexpr int EU = 4;
+  const int wel = (wave + EST_NW - ncs % EST_NW) % EST_NW;
+  for (int k0 = wel * EU; k0 < t.nbel; k0 += EST_NW * EU) {
+    double av[EU][3], bv[EU][3];
+#pragma unroll
+    for (int x = 0; x < EU; ++x) {
+      const int k = k0 + x < t.nbel ? k0 + x : t.nbel - 1;
+      const int e = t.bel_elem[k];
+      const double* E = a.ebar + ((long)s * t.nT + e) * 100 + (li < 10 ? li : 9) * 10;
+#pragma unroll
+      for (int u = 0; u < 3; ++u) {
+        const int c = 4 * u + lk, cc = c < 10 ? c : 9;
+        av[x][u] = E[cc];
+        const int bn = t.bel_bnode[k * 10 + cc];
+        bv[x][u] = (c < 10 && bn >= 0 && k0 + x < t.nbel) ? z[bn * 16 + li] : 0.0;      // also rows lk + 4 u of ze
+      }
+    }
+#pragma unroll
+    for (int x = 0; x < EU; ++x) {
+      d4 T = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int u = 0; u < 3; ++u) T = __builtin_amdgcn_mfma_f64_16x16x4f64(av[x][u], bv[x][u], T, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) p_nc += bv[x][r] * T[r];       // (rows >= 10 and missing nodes carry ze = 0)
+    }
+  }
+  p_nc += __shfl_xor(p_nc, 16);
+  p_nc += __shfl_xor(p_nc, 32);
+  if (lk == 0) red[wave * 16 + li] = p_nc;
+  __syncthreads();
+  if (tid < mb) {                          // totals per column, the waves in their order
+    double v = 0.0;
+    for (int ww = 0; ww < EST_NW; ++ww) v += red[ww * 16 + tid];
+    a.eta[(long)s * nmu + m0 + tid] = v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------- one-block sum of partials
 // (fom_cg, the Euler drivers and, through launch_reduce1, the reduced PCG of online3d.hip)
 __global__ __launch_bounds__(256) void k3_reduce1(int S, const double* __restrict__ part, double* __restrict__ out) {
@@ -2341,6 +2424,64 @@ int dense_spd_inverse(lrbms3_ctx* ctx, hipStream_t st, long M, double* A, double
   if (hinfo == 0 &&
       rocsolver_dpotrs(h, rocblas_fill_lower, (rocblas_int)M, (rocblas_int)M, A, (rocblas_int)M, Id, (rocblas_int)M) != rocblas_status_success)
     return lrbms_fail(ctx, LRBMS_E_HIP, "rocsolver_dpotrs failed");
+  return LRBMS_OK;
+}
+
+// ---- the batched estimate as a helper: the launch loop of lrbms3_reduced_estimate_batch, on the columns of one panel
+static size_t est16_lds(const T3& t, int Q, int N) {
+  return sizeof(double) * ((size_t)(7 * N + Q * N + t.nbf + t.nb) * EST16 + EST_NW * 6 * 16 + 4 * EST_NW * 16 + 3 * t.nvs + 1);
+}
+static size_t est8_lds(const T3& t, int Q, int N) { return sizeof(double) * ((size_t)(7 * N + Q * N + t.nbf + t.nb) * EST_MB + 256); }
+static size_t estnc16_lds(const T3& t, int N) { return sizeof(double) * ((size_t)(7 * N + 6 * t.nvs + t.nb) * EST16 + EST_NW * 16); }
+
+int estimate_batch_form(const lrbms3_ctx* ctx, int Q, int N) {
+  if (ctx->opt_estimate_valu == 0 && est16_lds(ctx->t, Q, N) <= 160 * 1024 - 2048) return 16;      // LRBMS3_OPT_ESTIMATE_VALU
+  return est8_lds(ctx->t, Q, N) <= 160 * 1024 ? 8 : 0;
+}
+
+int launch_reduced_estimate_batch(lrbms3_ctx* ctx, hipStream_t st, int Q, int N, int nmu, const double* theta, const EA& a) {
+  const T3& t = ctx->t;
+  const int form = estimate_batch_form(ctx, Q, N);
+  if (form == 16) {
+    const size_t lds16 = est16_lds(t, Q, N);
+    if (lds16 > 64 * 1024)
+      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k3_estimate_batch16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+    for (int m0 = 0; m0 < nmu; m0 += EST16) {
+      TB16 th{};
+      for (int m = 0; m < EST16 && m0 + m < nmu; ++m)
+        for (int q = 0; q < Q; ++q) th.v[m][q] = theta[(m0 + m) * Q + q];
+      KScope ks(ctx, "k3_estimate_batch16", st);
+      hipLaunchKernelGGL(k3_estimate_batch16, dim3(t.S), dim3(64 * EST_NW), lds16, st, t, Q, N, nmu, m0, th, a);
+    }
+    LRBMS_LAUNCH_CHECK(ctx);
+    return LRBMS_OK;
+  }
+  if (form == 0) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_estimate_batch: template too large for the LDS");
+  const size_t lds = est8_lds(t, Q, N);
+  if (lds > 64 * 1024)      // k_c = 4 at Q N = 64: 71 808 B
+    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k3_estimate_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  for (int m0 = 0; m0 < nmu; m0 += EST_MB) {
+    TB8 th{};
+    for (int m = 0; m < EST_MB && m0 + m < nmu; ++m)
+      for (int q = 0; q < Q; ++q) th.v[m][q] = theta[(m0 + m) * Q + q];
+    hipLaunchKernelGGL(k3_estimate_batch, dim3(t.S), dim3(256), lds, st, t, Q, N, nmu, m0, th, a);
+  }
+  LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}
+
+bool estimate_nc16_fits(const lrbms3_ctx* ctx, int N) { return estnc16_lds(ctx->t, N) <= 160 * 1024 - 2048; }
+
+int launch_estimate_nc_batch(lrbms3_ctx* ctx, hipStream_t st, int N, int nmu, const EA& a) {
+  const T3& t = ctx->t;
+  const size_t lds = estnc16_lds(t, N);
+  if (lds > 64 * 1024)
+    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k3_estimate_nc_batch16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  for (int m0 = 0; m0 < nmu; m0 += EST16) {
+    KScope ks(ctx, "k3_estimate_nc_batch16", st);
+    hipLaunchKernelGGL(k3_estimate_nc_batch16, dim3(t.S), dim3(64 * EST_NW), lds, st, t, N, nmu, m0, a);
+  }
+  LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
 
@@ -2853,34 +2994,8 @@ int lrbms3_reduced_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t
   LRBMS_REQUIRE_MESH(ctx);
   if (Q < 1 || Q > 8 || N < 1 || Q * N > 64 || nmu < 1 || !theta || !u || !eta_loc)
     return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_estimate_batch: bad argument");
-  const T3& t = ctx->t;
-  EA a{u, G_nc, G_bb, G_rdd, G_ab, G_aa, r_fd, Rb, Yb, Dp, Xab, As, Cn, ebar, Bbb, bdiv, f2, ceps, hdiam, eta_loc};
-  const bool est16_env = ctx->opt_estimate_valu == 0;      // LRBMS3_OPT_ESTIMATE_VALU
-  const size_t lds16 = sizeof(double) * ((size_t)(7 * N + Q * N + t.nbf + t.nb) * EST16 + EST_NW * 6 * 16 + 4 * EST_NW * 16 + 3 * t.nvs + 1);
-  if (est16_env && lds16 <= 160 * 1024 - 2048) {
-    if (lds16 > 64 * 1024)
-      LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k3_estimate_batch16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-    for (int m0 = 0; m0 < nmu; m0 += EST16) {
-      TB16 th{};
-      for (int m = 0; m < EST16 && m0 + m < nmu; ++m)
-        for (int q = 0; q < Q; ++q) th.v[m][q] = theta[(m0 + m) * Q + q];
-      hipLaunchKernelGGL(k3_estimate_batch16, dim3(t.S), dim3(64 * EST_NW), lds16, (hipStream_t)stream, t, Q, N, nmu, m0, th, a);
-    }
-    LRBMS_LAUNCH_CHECK(ctx);
-    return LRBMS_OK;
-  }
-  const size_t lds = sizeof(double) * ((size_t)(7 * N + Q * N + t.nbf + t.nb) * EST_MB + 256);
-  if (lds > 160 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_estimate_batch: template too large for the LDS");
-  if (lds > 64 * 1024)      // k_c = 4 at Q N = 64: 71 808 B
-    LRBMS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k3_estimate_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  for (int m0 = 0; m0 < nmu; m0 += EST_MB) {
-    TB8 th{};
-    for (int m = 0; m < EST_MB && m0 + m < nmu; ++m)
-      for (int q = 0; q < Q; ++q) th.v[m][q] = theta[(m0 + m) * Q + q];
-    hipLaunchKernelGGL(k3_estimate_batch, dim3(t.S), dim3(256), lds, (hipStream_t)stream, t, Q, N, nmu, m0, th, a);
-  }
-  LRBMS_LAUNCH_CHECK(ctx);
-  return LRBMS_OK;
+  const EA a{u, G_nc, G_bb, G_rdd, G_ab, G_aa, r_fd, Rb, Yb, Dp, Xab, As, Cn, ebar, Bbb, bdiv, f2, ceps, hdiam, eta_loc};
+  return launch_reduced_estimate_batch(ctx, (hipStream_t)stream, Q, N, nmu, theta, a);
 }
 
 int lrbms3_fom_coarse_space(lrbms3_ctx* ctx, int32_t nc, const double* Phi) {

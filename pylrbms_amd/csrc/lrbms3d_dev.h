@@ -100,6 +100,13 @@ struct TB { double v[16][8]; };     // theta [nmu][Q]
 // elements (10 rows each) per workgroup of the full-order solver kernels and of the kernels that share their partial-sum layout
 constexpr int FOM_EPB = 24;
 
+// arguments of the estimate kernels (lrbms3d.hip): the coefficients u, the factored estimator operators of the pass, eta the output
+struct EA {
+  const double *u, *G_nc, *G_bb, *G_rdd, *G_ab, *G_aa, *r_fd, *Rb, *Yb, *Dp, *Xab, *As, *Cn, *ebar, *Bbb, *bdiv, *f2, *ceps;
+  double hdiam;
+  double* eta;
+};
+
 inline QV make_theta(int Q, const double* theta) {
   QV th{};
   for (int q = 0; q < Q && q < 8; ++q) th.v[q] = theta[q];
@@ -119,5 +126,20 @@ void launch_reduce1(hipStream_t st, int S, const double* part, double* out);    
 // lrbms3d.hip (owner of ctx->blas), called there (fom_coarse) and by online3d.hip: A^-1 of a dense SPD matrix into Id (identity on entry) by
 // rocSOLVER potrf / potrs on the stream; hinfo != 0 (and LRBMS_OK) when A is not positive definite
 int dense_spd_inverse(lrbms3_ctx* ctx, hipStream_t st, long M, double* A, double* Id, rocblas_int* pinfo, rocblas_int& hinfo);
+// lrbms3d.hip, called there (lrbms3_reduced_estimate_batch) and by online3d.hip (the batched parabolic estimate): the launches of the
+// batched estimate for the nmu columns of the panel a.u [S][N][nmu] into a.eta [3][S][nmu] on st -- the 16-column matrix-core form
+// where its LDS fits and LRBMS3_OPT_ESTIMATE_VALU is 0, else the 8-column VALU form.  estimate_batch_form: 16 / 8 = the form the
+// helper will launch, 0 = neither fits the LDS (the helper would return LRBMS_E_INVALID): known before any launch.
+int estimate_batch_form(const lrbms3_ctx* ctx, int Q, int N);
+int launch_reduced_estimate_batch(lrbms3_ctx* ctx, hipStream_t st, int Q, int N, int nmu, const double* theta, const EA& a);      // k3_estimate_batch16 / k3_estimate_batch
+// lrbms3d.hip, called by online3d.hip: the nonconformity form alone, a.eta [S][nmu] (a.u, G_nc, As, Cn, ebar are read, nothing else);
+// estimate_nc16_fits: its LDS bound
+bool estimate_nc16_fits(const lrbms3_ctx* ctx, int N);
+int launch_estimate_nc_batch(lrbms3_ctx* ctx, hipStream_t st, int N, int nmu, const EA& a);                                         // k3_estimate_nc_batch16
+// sources3d.hip, called there (lrbms3_reduced_source_terms) and by online3d.hip: out [S][L]; source_terms_fits: its LDS bound
+bool source_terms_fits(const lrbms3_ctx* ctx, int N);
+void launch_source_terms(hipStream_t st, const T3& t, int Q, int N, int K, int L, const double* theta, const double* phi, const double* F2,
+                         const double* r_fd_K, const double* bdiv_K, const double* Rb, const double* u, const double* ceps, double hdiam,
+                         double* out);                                                                                              // k3_source_terms
 
 }  // namespace lrbms3

@@ -1,6 +1,8 @@
 // Reduced (online) solvers of the 3D / P2 path: the block-Jacobi PCG of lrbms3_reduced_solve, the batched solve in groups of
 // <= 16 parameters with its coarse level and the installable preconditioner, and the reduced side of the parabolic path
-// (implicit Euler single and batched, the time residual).  Cut out of lrbms3d.hip as text; the estimator stays there.
+// (implicit Euler single and batched, the time residual, the batched parabolic estimate).  Cut out of lrbms3d.hip as text; the
+// estimator kernels stay there and are reached through launch_reduced_estimate_batch / launch_estimate_nc_batch, the source terms
+// of sources3d.hip through launch_source_terms.
 // Home of k3_combine and k3p_axpy, which other files reach through launch_combine and launch_axpy; k3_reduce1 lives in
 // lrbms3d.hip with fom_cg (which launches it three times per iteration, red_cg once per residual check) and is reached
 // through launch_reduce1.  The dense coarse inverses go through dense_spd_inverse of lrbms3d.hip.
@@ -1450,6 +1452,247 @@ int lrbms3_reduced_time_residual(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t 
   hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, Amu, Minv);
   hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, make_theta(Q, theta), B_sys, Amu);
   hipLaunchKernelGGL(k3p_time_residual, dim3(S, L), dim3(64), sizeof(double) * (8 * N + 64), st, t, N, Amu, Minv, dU, out);
+  LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------- batched parabolic estimate
+// lrbms3_reduced_parabolic_estimate_batch: the parabolic estimate of the nmu <= 64 trajectories of one panel
+// U [nt+1][S][N][nmu].  The elliptic rows come from the batched estimate on every slab (launch_reduced_estimate_batch), the nc form of
+// the differences from k3_estimate_nc_batch16, the time residual from the panel matvec on gathered columns; the kernels below are the
+// glue: differences, the per-column tables of the source terms, M_red^-1 y . y per panel, and the combination into the five outputs.
+namespace {
+
+__global__ __launch_bounds__(256) void k3pe_diff(long total, const double* __restrict__ U, double* __restrict__ dU, long slab) {
+  for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < total; k += (long)gridDim.x * 256) dU[k] = U[k + slab] - U[k];
+}
+
+// theta of the group's columns into thd [nmu][Q], and its rows of phi [nmu][nt+1][K] into phid [nt+1][nmu][K] (the layout
+// k3_source_terms takes per step: one coefficient row per column)
+__global__ __launch_bounds__(256) void k3pe_tables(int Q, int K, int nmu, int nt, int m0, int nm, TB th, const double* __restrict__ phi,
+                                                   double* __restrict__ thd, double* __restrict__ phid) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < nm * Q; i += 256) thd[(long)m0 * Q + i] = th.v[i / Q][i % Q];
+  const long per = (long)(nt + 1) * K;
+  for (long i = tid; i < nm * per; i += 256) {
+    const long m = m0 + i / per, r = i % per, k = r / K, j = r % K;
+    phid[(k * nmu + m) * K + j] = phi[m * per + r];
+  }
+}
+
+// out[s ldo + m] = y^T Minv[s] y for the columns m < nm of the compact panel y [S][N][nm] (N <= 32): one workgroup per subdomain,
+// the panel in the LDS, thread = (row group tid >> 4, column tid & 15) -- the 16 lanes of a row group share the row of the inverse --
+// and the products y_i (Minv y)_i summed over the rows in ascending order
+__global__ __launch_bounds__(256) void k3pe_inv_norm2_panel(int N, int nm, int ldo, const double* __restrict__ Minv,
+                                                            const double* __restrict__ y, double* __restrict__ out) {
+  __shared__ double ys[32 * 16], pr[32 * 16];
+  const int s = blockIdx.x, tid = threadIdx.x, g = tid >> 4, m = tid & 15;
+  for (int k = tid; k < N * 16; k += 256) {
+    const int i = k >> 4, mm = k & 15;
+    ys[k] = mm < nm ? y[((long)s * N + i) * nm + mm] : 0.0;
+  }
+  __syncthreads();
+  for (int i = g; i < N; i += 16) {
+    const double* D = Minv + ((long)s * N + i) * N;
+    double z = 0.0;
+    for (int j = 0; j < N; ++j) z += D[j] * ys[j * 16 + m];
+    pr[i * 16 + m] = ys[i * 16 + m] * z;
+  }
+  __syncthreads();
+  if (tid < nm) {
+    double a = 0.0;
+    for (int i = 0; i < N; ++i) a += pr[i * 16 + tid];
+    out[(long)s * ldo + tid] = a;
+  }
+}
+
+struct PeCoef { double v[64][2]; };      // coef [nmu][2]: one kernel argument (1 KB)
+
+// The five outputs from the raw rows: one workgroup per 16 columns, thread = (part tid >> 4, column tid & 15).  Sums over the
+// subdomains: part g takes s = g, g + 16, ... in ascending order, the 16 parts are then added in their order.
+//   raw [nt+1][3][S][nmu] (nc, r, df of U[k]), src [nt+1][S][nmu] or nullptr (the f terms of the r row), ncd [nt][3][S][nmu] (row 0:
+//   nc of the differences), tr2 [nt][S][nmu] (y^T M_red^-1 y)
+__global__ __launch_bounds__(256) void k3pe_combine(int S, int nmu, int nt, double dt, PeCoef cf, const double* __restrict__ raw,
+                                                    const double* __restrict__ src, const double* __restrict__ ncd,
+                                                    const double* __restrict__ tr2, double* __restrict__ eta_loc,
+                                                    double* __restrict__ tdnc, double* __restrict__ tres, double* __restrict__ eta,
+                                                    double* __restrict__ est) {
+  __shared__ double buf[2][16 * 16];
+  const int tid = threadIdx.x, g = tid >> 4, mm = tid & 15, m = blockIdx.x * 16 + mm;
+  const bool on = m < nmu;
+  const double sc = 2.0 * sqrt(dt / 3.0);
+  const long SM = (long)S * nmu, row = (long)(nt + 1) * SM;
+  double e2 = 0.0, r2 = 0.0, d2 = 0.0;      // squares of eta, time_residual, time_deriv_nc (meaningful in part 0)
+  for (int k = 0; k <= nt; ++k) {
+    double a_nc = 0.0, a_rd = 0.0;
+    if (on)
+      for (int s = g; s < S; s += 16) {
+        const long o = (long)s * nmu + m;
+        const double nc = raw[(k * 3L + 0) * SM + o], df = raw[(k * 3L + 2) * SM + o];
+        double r = raw[(k * 3L + 1) * SM + o];
+        if (src) r += src[k * SM + o];
+        eta_loc[k * SM + o] = nc * sc;
+        eta_loc[row + k * SM + o] = r * sc;
+        eta_loc[2 * row + k * SM + o] = df * sc;
+        a_nc += nc * nc;
+        a_rd += (r + df) * (r + df);
+      }
+    __syncthreads();
+    buf[0][tid] = a_nc;
+    buf[1][tid] = a_rd;
+    __syncthreads();
+    if (g == 0 && on) {
+      double s_nc = 0.0, s_rd = 0.0;
+      for (int p = 0; p < 16; ++p) {
+        s_nc += buf[0][p * 16 + mm];
+        s_rd += buf[1][p * 16 + mm];
+      }
+      const double ek = sc * (cf.v[m][0] * sqrt(s_nc) + cf.v[m][1] * sqrt(s_rd));
+      eta[(long)k * nmu + m] = ek;
+      e2 += ek * ek;
+    }
+  }
+  for (int k = 0; k < nt; ++k) {
+    double a_tr = 0.0, a_td = 0.0;
+    if (on)
+      for (int s = g; s < S; s += 16) {
+        const long o = (long)s * nmu + m;
+        const double v = ncd[k * 3L * SM + o], q = (v > 0.0 ? v : 0.0) / dt;
+        tdnc[k * SM + o] = sqrt(q);
+        a_td += q;
+        a_tr += tr2[k * SM + o];
+      }
+    __syncthreads();
+    buf[0][tid] = a_tr;
+    buf[1][tid] = a_td;
+    __syncthreads();
+    if (g == 0 && on) {
+      double s_tr = 0.0, s_td = 0.0;
+      for (int p = 0; p < 16; ++p) {
+        s_tr += buf[0][p * 16 + mm];
+        s_td += buf[1][p * 16 + mm];
+      }
+      const double tk = sqrt(dt / 3.0 * s_tr);
+      tres[(long)k * nmu + m] = tk;
+      r2 += tk * tk;
+      d2 += s_td;
+    }
+  }
+  if (g == 0 && on) est[m] = sqrt(e2) + sqrt(r2) + sqrt(d2);
+}
+
+// doubles of work: raw, dU, ncd, tr2, src | thd [64][8], phid [nt+1][nmu][64] | Minv, the 7-slot copy of M_red the block inverse
+// reads | one group's panel vectors z, p, y [S][N][16] and partials [S][16]
+long pe_batch3_work_size(long S, long N, long nmu, long nt) {
+  return (nt + 1) * 3 * S * nmu + nt * S * N * nmu + nt * 3 * S * nmu + nt * S * nmu + (nt + 1) * S * nmu + 64 * 8 + (nt + 1) * nmu * 64 +
+         S * N * N + 7 * S * N * N + 3 * S * N * 16 + S * 16;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t lrbms3_reduced_parabolic_estimate_batch_work_size(lrbms3_ctx* ctx, int32_t N, int32_t nmu, int32_t nt) {
+  if (!ctx || !ctx->has_mesh || N < 1 || N > 32 || nmu < 1 || nmu > 64 || nt < 1) return -1;
+  return pe_batch3_work_size(ctx->t.S, N, nmu, nt);
+}
+
+int lrbms3_reduced_parabolic_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, int32_t nt, double dt,
+                                            const double* theta, const double* coef, const double* U, const double* B_sys,
+                                            const double* M_red, const double* G_nc, const double* G_bb, const double* G_rdd,
+                                            const double* G_ab, const double* G_aa, const double* r_fd, const double* Rb, const double* Yb,
+                                            const double* Dp, const double* Xab, const double* As, const double* Cn, const double* ebar,
+                                            const double* Bbb, const double* bdiv, const double* f2, const double* ceps, double hdiam,
+                                            const double* phi, const double* F2, const double* r_fd_K, const double* bdiv_K, double* work,
+                                            double* eta_loc, double* time_deriv_nc, double* time_residual, double* eta, double* est,
+                                            void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  const T3& t = ctx->t;
+  const char* name = "reduced_parabolic_estimate_batch";
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 32 || Q * N > 64 || nmu < 1 || nmu > 64 || K < 0 || K > 64)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": needs N <= 32, Q N <= 64, 1 <= nmu <= 64 and 0 <= K <= 64");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": dt > 0 and nt >= 1 required");
+  if (!theta || !coef || !U || !B_sys || !M_red || !G_nc || !G_bb || !G_rdd || !G_ab || !G_aa || !r_fd || !Rb || !Yb || !Dp || !Xab || !As ||
+      !Cn || !ebar || !Bbb || !bdiv || !f2 || !ceps || !work || !eta_loc || !time_deriv_nc || !time_residual || !eta || !est)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": null argument");
+  const int nsrc = (phi != nullptr) + (F2 != nullptr) + (r_fd_K != nullptr) + (bdiv_K != nullptr);
+  if (nsrc != (K > 0 ? 4 : 0))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": phi, F2, r_fd_K, bdiv_K are all set with K >= 1 and all null with K = 0");
+  if (estimate_batch_form(ctx, Q, N) == 0 || (K > 0 && !source_terms_fits(ctx, N)))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": template too large for the LDS");
+  hipStream_t st = (hipStream_t)stream;
+  const long S = t.S, SM = S * nmu, slab = S * N * nmu, NN = (long)N * N;
+  double* raw = work;
+  double* dU = raw + (nt + 1) * 3 * SM;
+  double* ncd = dU + nt * slab;
+  double* tr2 = ncd + nt * 3 * SM;
+  double* src = tr2 + nt * SM;
+  double* thd = src + (nt + 1) * SM;
+  double* phid = thd + 64 * 8;
+  double* Minv = phid + (long)(nt + 1) * nmu * 64;
+  double* Mslot = Minv + S * NN;
+  double* gw = Mslot + 7 * S * NN;
+  EA a{U, G_nc, G_bb, G_rdd, G_ab, G_aa, r_fd, Rb, Yb, Dp, Xab, As, Cn, ebar, Bbb, bdiv, f2, ceps, hdiam, raw};
+  // ---- 1. the elliptic rows of every slab
+  for (int k = 0; k <= nt; ++k) {
+    a.u = U + k * slab;
+    a.eta = raw + k * 3 * SM;
+    if (int rc = launch_reduced_estimate_batch(ctx, st, Q, N, nmu, theta, a)) return rc;
+  }
+  // ---- 2. the differences
+  {
+    const long total = nt * slab, blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k3pe_diff, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, st, total, U, dU, slab);
+  }
+  // ---- 3. their nc form: the nc-only matrix-core kernel, or row 0 of the full estimate where that form is not the one in use
+  const bool nc16 = estimate_batch_form(ctx, Q, N) == 16 && estimate_nc16_fits(ctx, N);
+  for (int k = 0; k < nt; ++k) {
+    a.u = dU + k * slab;
+    a.eta = ncd + k * 3 * SM;
+    if (int rc = nc16 ? launch_estimate_nc_batch(ctx, st, N, nmu, a) : launch_reduced_estimate_batch(ctx, st, Q, N, nmu, theta, a)) return rc;
+  }
+  // ---- 4. the time residual: M_red^-1 once (the block inverse reads the self slot of a 7-slot operator, with its identity rule on
+  // zero-padded basis columns), then per step and group y = sum_q theta_qm B_q dU by the panel matvec and y^T M_red^-1 y
+  LRBMS_HIP_CHECK(ctx, hipMemcpy2DAsync(Mslot + 3 * NN, sizeof(double) * 7 * NN, M_red, sizeof(double) * NN, sizeof(double) * NN, S,
+                                        hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(k3_block_inverse, dim3(S), dim3(256), sizeof(double) * N * (2 * N + 1), st, N, Mslot, Minv);
+  const CoarseB none{nullptr, nullptr, nullptr};
+  const long rows = S * N;
+  for (int m0 = 0; m0 < nmu; m0 += 16) {
+    RbGroup G{};
+    G.m0 = m0;
+    G.nm = nmu - m0 < 16 ? nmu - m0 : 16;
+    G.st = st;
+    G.z = gw;
+    G.po = gw;                         // (first = 1: not read)
+    G.pn = gw + rows * 16;
+    G.Ap = G.pn + rows * 16;
+    G.ppap = G.Ap + rows * 16;
+    G.th = TB{};
+    for (int m = 0; m < G.nm; ++m)
+      for (int q = 0; q < Q; ++q) G.th.v[m][q] = theta[(m0 + m) * Q + q];
+    if (K > 0) hipLaunchKernelGGL(k3pe_tables, dim3(1), dim3(256), 0, st, Q, K, nmu, nt, m0, G.nm, G.th, phi, thd, phid);
+    const RbOp op{Q, N, nmu, B_sys, nullptr, nullptr, nullptr};
+    const long vec = rows * G.nm;
+    for (int k = 0; k < nt; ++k) {
+      hipLaunchKernelGGL(k3b_gather, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, st, rows, G.nm, nmu,
+                         dU + k * slab + m0, G.z);
+      launch_matvec3<false>(ctx, op, G, 1, G.ppap, G.ppap, none);
+      hipLaunchKernelGGL(k3pe_inv_norm2_panel, dim3(S), dim3(256), 0, st, N, G.nm, nmu, Minv, G.Ap, tr2 + k * SM + m0);
+    }
+  }
+  // ---- 5. the f terms of the r rows (K >= 1: the caller's f2, r_fd and bdiv are zero)
+  if (K > 0)
+    for (int k = 0; k <= nt; ++k)
+      launch_source_terms(st, t, Q, N, K, nmu, thd, phid + (long)k * nmu * K, F2, r_fd_K, bdiv_K, Rb, U + k * slab, ceps, hdiam, src + k * SM);
+  // ---- 6. the five outputs
+  PeCoef cf{};
+  for (int m = 0; m < nmu; ++m) cf.v[m][0] = coef[m * 2], cf.v[m][1] = coef[m * 2 + 1];
+  hipLaunchKernelGGL(k3pe_combine, dim3((nmu + 15) / 16), dim3(256), 0, st, (int)S, nmu, nt, dt, cf, raw, K > 0 ? src : nullptr, ncd, tr2, eta_loc,
+                     time_deriv_nc, time_residual, eta, est);
   LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }

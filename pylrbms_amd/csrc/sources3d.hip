@@ -1,5 +1,6 @@
 // 3D / P2 path: affine sources -- k3_source_gram, k3_project_sources, k3_source_terms and lrbms3_combine_sources, which launches
-// the shape-agnostic kernel of online.hip through launch_combine_sources_base.  No other file calls into this one.
+// the shape-agnostic kernel of online.hip through launch_combine_sources_base.  online3d.hip (the batched parabolic estimate)
+// reaches k3_source_terms through launch_source_terms.
 // (lrbms3_reduced_solve_batch_src and the _src forms of the implicit Euler live with their solvers in online3d.hip and lrbms3d.hip.)
 #include "lrbms3d_dev.h"
 
@@ -213,6 +214,19 @@ __global__ __launch_bounds__(256) void k3_source_terms(T3 t, int Q, int N, int K
 
 }  // namespace
 
+namespace lrbms3 {
+
+static size_t source_terms_lds(const T3& t, int N) { return sizeof(double) * (7 * (size_t)N * 8 + (size_t)t.nbf * 8 + 64 + 256); }
+bool source_terms_fits(const lrbms3_ctx* ctx, int N) { return source_terms_lds(ctx->t, N) <= 64 * 1024; }
+void launch_source_terms(hipStream_t st, const T3& t, int Q, int N, int K, int L, const double* theta, const double* phi, const double* F2,
+                         const double* r_fd_K, const double* bdiv_K, const double* Rb, const double* u, const double* ceps, double hdiam,
+                         double* out) {
+  hipLaunchKernelGGL(k3_source_terms, dim3(t.S, (L + 7) / 8), dim3(256), source_terms_lds(t, N), st, t, Q, N, K, L, theta, phi, F2, r_fd_K,
+                     bdiv_K, Rb, u, ceps, hdiam, out);
+}
+
+}  // namespace lrbms3
+
 extern "C" {
 
 int lrbms3_assemble_source_gram(lrbms3_ctx* ctx, int32_t K, const double* f_smp_K, double* F2, void* stream) {
@@ -265,10 +279,8 @@ int lrbms3_reduced_source_terms(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K
     return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: bad N / L / K / Q");
   if (!theta || !phi || !F2 || !r_fd_K || !bdiv_K || !Rb || !u || !ceps || !out)
     return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: null argument");
-  const size_t lds = sizeof(double) * (7 * (size_t)N * 8 + (size_t)t.nbf * 8 + 64 + 256);
-  if (lds > 64 * 1024) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: the side faces of this template do not fit the LDS");
-  hipLaunchKernelGGL(k3_source_terms, dim3(t.S, (L + 7) / 8), dim3(256), lds, (hipStream_t)stream, t, Q, N, K, L, theta, phi, F2, r_fd_K,
-                     bdiv_K, Rb, u, ceps, hdiam, out);
+  if (!source_terms_fits(ctx, N)) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_source_terms: the side faces of this template do not fit the LDS");
+  launch_source_terms((hipStream_t)stream, t, Q, N, K, L, theta, phi, F2, r_fd_K, bdiv_K, Rb, u, ceps, hdiam, out);
   LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }

@@ -10,6 +10,7 @@
     reductor = ParabolicLRBMSReductor3D(d)
     reductor.extend_basis(U[:, :, idx]);  rd = reductor.reduce()
     u = rd.solve(mu);  rd.estimate(u, mu);  reductor.reconstruct(u)
+    us = rd.solve_batch(mus);  rd.estimate_batch(us, mus, native=True)     # sweeps: 64 parameters per native call
 
 The estimate restates ``OracleParabolic.estimate`` (oracle/parabolic.py): the elliptic terms of every vector of the trajectory,
 scaled by 2 sqrt(dt / 3); ``time_residual_k = sqrt(dt / 3 * sum_s y^T M_s^-1 y)`` with ``y = A(mu) (U_{k+1} - U_k)``;
@@ -263,12 +264,51 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
         tr2 = eng.ctx.reduced_time_residual(Q, theta, self.out['B_sys'], self.M_red, du).sum(dim=1).cpu().numpy()
         return _parabolic_estimate(d, mu, self.dt, eta_loc, tr2, tdnc2)
 
-    def estimate_batch(self, U, mus, decompose=False):
-        """The estimates of the trajectories U [len(mus), nt + 1, S, N] (as ``solve_batch`` returns them): the list of
-        ``estimate(U[m], mus[m])``.  A loop -- the native batch over trajectories is not built for the 3D path; the stationary
-        method this class inherits takes one solution per parameter, not a trajectory."""
+    def estimate_batch(self, U, mus, decompose=False, native=False):
+        """The estimates of the trajectories U [len(mus), nt + 1, S, N] (as ``solve_batch`` returns them): a list with, per
+        parameter, the tuple ``estimate(U[m], mus[m])`` returns.
+
+        ``native=False`` (the default) IS the loop of ``estimate``, bit for bit; nothing is routed to the batched export.
+        ``native=True``: one ``lrbms3_reduced_parabolic_estimate_batch`` call per 64 parameters -- the chunk is
+        permuted into the panel [nt + 1, S, N, nmu] once, the source coefficients come from ``d.source_coefficients``, one
+        device-to-host copy per output, NumPy parts as ``estimate`` returns them.  It agrees with the loop to round-off, not in
+        the bits: the time residual runs on the matrix-core panel matvec and the norms are summed on the device.  With N > 32
+        or Q N > 64 (the limits of the batched kernels) ``native=True`` runs the loop, as ``solve_batch`` does for N > 32."""
         assert len(U) == len(mus), 'estimate_batch: one trajectory per parameter'
-        return [self.estimate(U[m], mu, decompose=decompose) for m, mu in enumerate(mus)]
+        d = self.d
+        mus = list(mus)
+        if not native or self.N > 32 or d.Q * self.N > 64 or not mus:
+            return [self.estimate(U[m], mu, decompose=decompose) for m, mu in enumerate(mus)]
+        eng, nt = d.engine, self.time_stepper.nt
+        src = self.rhs_red_K is not None
+        if U.shape[1] != nt + 1:
+            if src:
+                raise ValueError('with a time-dependent source the estimate takes the whole trajectory [nt + 1, S, N]')
+            nt = int(U.shape[1]) - 1           # (a part of a trajectory: the estimate of its steps, as ``estimate`` does)
+            if nt < 1:
+                raise ValueError('estimate_batch: a trajectory has at least two vectors')
+        out, ops = self._zeroed() if src else (self.out, eng.ops)
+        res = []
+        for b0 in range(0, len(mus), 64):
+            chunk = mus[b0:b0 + 64]
+            th = np.stack([d.theta(mu) for mu in chunk])
+            coef = np.empty((len(chunk), 2))
+            for m, mu in enumerate(chunk):
+                a_bar, a_hat, g_bar = d.alpha(mu, d.mu_bar), d.alpha(mu, d.mu_hat), d.gamma(mu, d.mu_bar)
+                coef[m] = np.sqrt(g_bar / a_bar), 1.0 / np.sqrt(a_hat * a_bar)
+            panel = U[b0:b0 + 64].permute(1, 2, 3, 0).contiguous()
+            kw = {}
+            if src:
+                kw = dict(phi=np.stack([np.asarray(d.source_coefficients(mu), dtype=np.float64) for mu in chunk]), F2=d._src['F2'],
+                          r_fd_K=self.r_fd_K, bdiv_K=d._src['bdiv_K'])
+            r = eng.ctx.reduced_parabolic_estimate_batch(d.Q, th, coef, self.dt, nt, panel, self.out['B_sys'], self.M_red, out, ops,
+                                                         eng.hdiam, **kw)
+            h = {k: v.cpu().numpy() for k, v in r.items()}
+            for m in range(len(chunk)):
+                nc, rr, df = (np.ascontiguousarray(h['eta_loc'][i, :, :, m].T) for i in range(3))      # [S, nt + 1]
+                res.append((float(h['est'][m]), (nc, rr, df, np.ascontiguousarray(h['time_residual'][:, m]),
+                                                 np.ascontiguousarray(h['time_deriv_nc'][:, :, m].T))))
+        return res
 
 
 class ParabolicLRBMSReductor3D(LRBMSReductor3D):
