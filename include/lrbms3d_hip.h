@@ -481,6 +481,52 @@ int lrbms3_reduced_parabolic_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t 
                                             double* eta_loc, double* time_deriv_nc, double* time_residual, double* eta, double* est,
                                             void* stream);
 
+/* -- time-dependent diffusion coefficients theta_q(t, mu) on the three batched parabolic exports -------------------
+ * The 3D counterparts of the lrbms_*_tv exports.  Each is its twin above with theta_t [nmu][nt+1][Q] (HOST, the
+ * shape of phi; row k belongs to the time of step k, every entry positive) in place of theta [nmu][Q]; theta is never baked into an
+ * operator, so a row per step is one table refill per step and nothing is rebuilt.  Everything not named here is the twin's contract:
+ * limits, max_iter rules, info, refusals before any launch (outputs and work untouched), no atomics, fixed summation orders (repeat
+ * calls give the same bits, equal columns give equal bits wherever they stand), and a preconditioner installed with
+ * lrbms3_reduced_precond_use is neither read nor replaced.  The twins launch the same kernels with the same arguments as before
+ * (they go through the shared drivers with a row stride of zero).
+ *   lrbms3_fom_implicit_euler_batch_tv       column m steps with (M + dt A(theta_t[m][k+1])) u_{k+1} = M u_k + dt sum_j phi[m][k+1][j] b_K[j]:
+ *                                   the panel's table is filled with dt x row k+1 ahead of every step.  Row 0 is not read.  Work size
+ *                                   and lrbms3_fom_implicit_euler_batch_panel_info are the twin's.
+ *   lrbms3_reduced_implicit_euler_batch_tv   the same on the projected operators, one export for both right-hand sides: K = 0 takes
+ *                                   rhs_red_K = rhs_red [S][N] and phi = NULL, 1 <= K <= 64 takes rhs_red_K [K][S][N] and phi
+ *                                   [nmu][nt+1][K] (DEVICE); LRBMS_E_INVALID for a phi that does not go with K.  The groups' tables are
+ *                                   refilled from row k+1 per step.  Work size lrbms3_reduced_implicit_euler_batch_work_size(N, nmu).
+ *   lrbms3_reduced_parabolic_estimate_batch_tv  theta_t and coef [nmu][nt+1][2] (HOST, read before the call returns): the elliptic
+ *                                   rows and the source terms of U[k] use row k, as does coef in eta[k] (alpha, gamma of row k); the
+ *                                   time residual of U[k+1] - U[k] uses row k+1, the operator that produced U[k+1]; the nc form of
+ *                                   the differences reads no theta.  The coef table goes to work in stream order in kernel-argument
+ *                                   chunks of 256 doubles (no copy from pageable host memory, no host synchronisation); a table
+ *                                   that is constant in time gives the bits of the twin.
+ *                                   work: lrbms3_reduced_parabolic_estimate_batch_tv_work_size(N, nmu, nt) doubles (-1 outside the
+ *                                   twin's limits or without a mesh).
+ * The preconditioner of the two solvers: ONE per call, as in the twins, at the time mean of every column,
+ *     theta_bar_m[q] = (sum_{k=1..nt} theta_t[m][k][q]) / nt   (ascending k),
+ * then the twin's expression over the columns (reduced: sum_m theta_bar_m / nmu accumulated in column order; full order: the column sum
+ * divided by nmu), times dt.  With nt = 1 that is the twin's arithmetic on row 1: a _tv call with nt = 1 gives the bits of its twin at
+ * theta = row 1.  For d/dt A != 0 the estimate is an indicator, not a proven bound. */
+int lrbms3_fom_implicit_euler_batch_tv(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta_t, double dt, int32_t nt,
+                                       const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                       double* U, double rtol, int32_t max_iter, double* info, void* stream);
+int lrbms3_reduced_implicit_euler_batch_tv(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta_t, double dt,
+                                           int32_t nt, const double* B_sys, const double* M_red, const double* rhs_red_K,
+                                           const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
+                                           void* stream);
+int64_t lrbms3_reduced_parabolic_estimate_batch_tv_work_size(lrbms3_ctx* ctx, int32_t N, int32_t nmu, int32_t nt);
+int lrbms3_reduced_parabolic_estimate_batch_tv(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, int32_t nt, double dt,
+                                               const double* theta_t, const double* coef, const double* U, const double* B_sys,
+                                               const double* M_red, const double* G_nc, const double* G_bb, const double* G_rdd,
+                                               const double* G_ab, const double* G_aa, const double* r_fd, const double* Rb,
+                                               const double* Yb, const double* Dp, const double* Xab, const double* As, const double* Cn,
+                                               const double* ebar, const double* Bbb, const double* bdiv, const double* f2,
+                                               const double* ceps, double hdiam, const double* phi, const double* F2,
+                                               const double* r_fd_K, const double* bdiv_K, double* work, double* eta_loc,
+                                               double* time_deriv_nc, double* time_residual, double* eta, double* est, void* stream);
+
 /* -- online enrichment ------------------------------------------------------------------------------------------------------ */
 /* Dirichlet correction blocks of the neighbourhood problems: on every coupling face of subdomain s, for the own side element,
  * the Dirichlet-face block (inside coefficient) minus the inner-face own / own block already contained in A_diag (mesh tables

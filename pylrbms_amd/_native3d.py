@@ -93,6 +93,14 @@ SIGNATURES3 = {
     'lrbms3_reduced_parabolic_estimate_batch_work_size': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
     'lrbms3_reduced_parabolic_estimate_batch': (ctypes.c_int, [c_vp] + [c_i32] * 5 + [c_dbl, _P_DBL, _P_DBL] + [c_vp] * 20 + [c_dbl] +
                                                 [c_vp] * 11),
+    # time-dependent diffusion coefficients on the three batched parabolic exports
+    'lrbms3_fom_implicit_euler_batch_tv': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                          c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms3_reduced_implicit_euler_batch_tv': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_vp, c_vp, c_vp,
+                                                              c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
+    'lrbms3_reduced_parabolic_estimate_batch_tv_work_size': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
+    'lrbms3_reduced_parabolic_estimate_batch_tv': (ctypes.c_int, [c_vp] + [c_i32] * 5 + [c_dbl, _P_DBL, _P_DBL] + [c_vp] * 20 + [c_dbl] +
+                                                   [c_vp] * 11),
     # online enrichment
     'lrbms3_assemble_dirichlet_correction': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     'lrbms3_local_correction_work_size': (c_i64, [c_vp, c_i32]),
@@ -473,14 +481,24 @@ class Native3DContext(_native.ContextBase):
         mean theta) -> (U [nt + 1, S, n, nmu], info).  thetas [nmu, Q] host; phi [nmu, nt + 1, K] host or device; b_K [K, S, n];
         U0 None (zeros), [S, n] (every column) or [S, n, nmu].  ``info``: ``iterations`` (summed over panels and steps),
         ``relative_residual`` (worst final ratio), ``panel_iterations``."""
+        return self._fom_implicit_euler_batch('lrbms3_fom_implicit_euler_batch', thetas, dt, nt, A_diag, A_cpl, b_K, phi, U0, rtol,
+                                              max_iter, work)
+
+    def fom_implicit_euler_batch_tv(self, theta_t, dt, nt, A_diag, A_cpl, b_K, phi, U0=None, rtol=1e-10, max_iter=50000, work=None):
+        """``fom_implicit_euler_batch`` with a coefficient row per step (``lrbms3_fom_implicit_euler_batch_tv``):
+        theta_t [nmu, nt + 1, Q] host, the step k -> k + 1 of column m solves with theta_t[m, k + 1]."""
+        return self._fom_implicit_euler_batch('lrbms3_fom_implicit_euler_batch_tv', theta_t, dt, nt, A_diag, A_cpl, b_K, phi, U0, rtol,
+                                              max_iter, work)
+
+    def _fom_implicit_euler_batch(self, export, thetas, dt, nt, A_diag, A_cpl, b_K, phi, U0, rtol, max_iter, work):
         Q, S, K, nt = int(A_diag.shape[0]), self.S, int(b_K.shape[0]), int(nt)
         th = np.ascontiguousarray(thetas, dtype=np.float64)
         nmu = th.shape[0]
-        assert th.shape == (nmu, Q)
+        assert th.shape == ((nmu, nt + 1, Q) if export.endswith('_tv') else (nmu, Q))
         ph = self._dev2(phi, (nmu, nt + 1, K), 'phi')
         size = int(self.lib.lrbms3_fom_implicit_euler_batch_work_size(self.handle, nmu))
         if size < 0:
-            raise NativeError('lrbms3_fom_implicit_euler_batch: nmu = {} is not in 1..64'.format(nmu))
+            raise NativeError('{}: nmu = {} is not in 1..64'.format(export, nmu))
         if work is None:
             work = self.empty(size)
         elif work.numel() < size:
@@ -491,15 +509,14 @@ class Native3DContext(_native.ContextBase):
         else:
             U[0].copy_(U0.reshape(S, self.n, -1))                # [S, n, 1] broadcasts over the columns
         info = (c_dbl * 2)()
-        rc = self.lib.lrbms3_fom_implicit_euler_batch(self.handle, Q, K, nmu, th.ctypes.data_as(_P_DBL), float(dt), nt,
-                                                      self._ptr(A_diag, (Q, S, self.n_T, 5, 100), 'A_diag'),
-                                                      self._ptr(A_cpl, (Q, S, 6, self.ncf, 100), 'A_cpl'),
-                                                      self._ptr(b_K, (K, S, self.n), 'b_K'), c_vp(ph.data_ptr()),
-                                                      c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), info,
-                                                      self._stream())
+        rc = getattr(self.lib, export)(self.handle, Q, K, nmu, th.ctypes.data_as(_P_DBL), float(dt), nt,
+                                       self._ptr(A_diag, (Q, S, self.n_T, 5, 100), 'A_diag'),
+                                       self._ptr(A_cpl, (Q, S, 6, self.ncf, 100), 'A_cpl'), self._ptr(b_K, (K, S, self.n), 'b_K'),
+                                       c_vp(ph.data_ptr()), c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), info,
+                                       self._stream())
         panels = (c_dbl * 8)()
         self.lib.lrbms3_fom_implicit_euler_batch_panel_info(self.handle, panels)
-        self._check(rc, 'lrbms3_fom_implicit_euler_batch')
+        self._check(rc, export)
         return U, {'iterations': int(info[0]), 'relative_residual': float(info[1]),
                    'panel_iterations': [int(v) for v in list(panels)[0:2 * ((nmu + 15) // 16):2]]}
 
@@ -720,6 +737,29 @@ class Native3DContext(_native.ContextBase):
         self._check(rc, 'lrbms3_reduced_implicit_euler_batch_src')
         return U, (int(info[0]), float(info[1]))
 
+    def reduced_implicit_euler_batch_tv(self, Q, theta_t, dt, nt, B_sys, M_red, rhs_red, phi=None, U0=None, rtol=1e-12, max_iter=20000,
+                                        work=None):
+        """``reduced_implicit_euler_batch`` (phi None, rhs_red [S, N]) or ``reduced_implicit_euler_batch_src`` (phi [nmu, nt + 1, K],
+        rhs_red [K, S, N]) with a coefficient row per step (``lrbms3_reduced_implicit_euler_batch_tv``): theta_t
+        [nmu, nt + 1, Q] host, the step k -> k + 1 of column m solves with theta_t[m, k + 1]."""
+        S, nt = self.S, int(nt)
+        K = 0 if phi is None else int(rhs_red.shape[0])
+        N = int(rhs_red.shape[-1])
+        th = np.ascontiguousarray(theta_t, dtype=np.float64)
+        nmu = th.shape[0]
+        assert th.shape == (nmu, nt + 1, Q), 'theta_t must be [nmu, nt + 1, Q]'
+        ph = c_vp(None) if phi is None else c_vp(self._dev2(phi, (nmu, nt + 1, K), 'phi').data_ptr())
+        work, U = self._batch_trajectory_buffers('reduced_implicit_euler_batch_tv', N, nmu, nt, U0, work)
+        info = (c_dbl * 2)()
+        rc = self.lib.lrbms3_reduced_implicit_euler_batch_tv(self.handle, Q, N, K, nmu, th.ctypes.data_as(_P_DBL), float(dt), nt,
+                                                             self._ptr(B_sys, (Q, S, 7, N, N), 'B_sys'),
+                                                             self._ptr(M_red, (S, N, N), 'M_red'),
+                                                             self._ptr(rhs_red, (K, S, N) if K else (S, N), 'rhs_red'), ph,
+                                                             c_vp(work.data_ptr()), c_vp(U.data_ptr()), float(rtol), int(max_iter), info,
+                                                             self._stream())
+        self._check(rc, 'lrbms3_reduced_implicit_euler_batch_tv')
+        return U, (int(info[0]), float(info[1]))
+
     # ------------------------------------------------------------------ batched parabolic estimates (DESIGN.md 9.17)
     def reduced_parabolic_estimate_batch(self, Q, thetas, coef, dt, nt, U, B_sys, M_red, out, ops, hdiam, phi=None, F2=None, r_fd_K=None,
                                          bdiv_K=None, work=None):
@@ -728,11 +768,27 @@ class Native3DContext(_native.ContextBase):
         ``reduced_estimate_batch``; with a time-dependent source phi [nmu, nt + 1, K] (host or device), F2 [S, K, K], r_fd_K
         [K, S, QN], bdiv_K [K, S, n_T] and ``out`` / ``ops`` with zeroed r_fd / f2 / bdiv.  Returns a dict of device tensors:
         eta_loc [3, nt + 1, S, nmu], time_deriv_nc [nt, S, nmu], time_residual [nt, nmu], eta [nt + 1, nmu], est [nmu]."""
+        return self._reduced_parabolic_estimate_batch('lrbms3_reduced_parabolic_estimate_batch', Q, thetas, coef, dt, nt, U, B_sys, M_red, out,
+                                                      ops, hdiam, phi, F2, r_fd_K, bdiv_K, work)
+
+    def reduced_parabolic_estimate_batch_tv(self, Q, theta_t, coef, dt, nt, U, B_sys, M_red, out, ops, hdiam, phi=None, F2=None,
+                                            r_fd_K=None, bdiv_K=None, work=None):
+        """``reduced_parabolic_estimate_batch`` with a coefficient row per step (``lrbms3_reduced_parabolic_estimate_batch_tv``,
+        DESIGN.md 9.18): theta_t [nmu, nt + 1, Q], coef [nmu, nt + 1, 2] (host).  The elliptic rows of U[k], the source terms and
+        the scaling of eta[k] use row k, the time residual of U[k + 1] - U[k] row k + 1."""
+        return self._reduced_parabolic_estimate_batch('lrbms3_reduced_parabolic_estimate_batch_tv', Q, theta_t, coef, dt, nt, U, B_sys, M_red,
+                                                      out, ops, hdiam, phi, F2, r_fd_K, bdiv_K, work)
+
+    def _reduced_parabolic_estimate_batch(self, export, Q, thetas, coef, dt, nt, U, B_sys, M_red, out, ops, hdiam, phi, F2, r_fd_K, bdiv_K,
+                                          work):
         S, N, nt = self.S, int(B_sys.shape[-1]), int(nt)
         th = np.ascontiguousarray(thetas, dtype=np.float64)
         nmu = th.shape[0]
         cf = np.ascontiguousarray(coef, dtype=np.float64)
-        assert th.shape == (nmu, Q) and cf.shape == (nmu, 2), 'thetas must be [nmu, Q], coef [nmu, 2]'
+        if export.endswith('_tv'):
+            assert th.shape == (nmu, nt + 1, Q) and cf.shape == (nmu, nt + 1, 2), 'theta_t must be [nmu, nt + 1, Q], coef [nmu, nt + 1, 2]'
+        else:
+            assert th.shape == (nmu, Q) and cf.shape == (nmu, 2), 'thetas must be [nmu, Q], coef [nmu, 2]'
         shp = self.out_shapes(Q, N)
         names = ('G_nc', 'G_bb', 'G_rdd', 'G_ab', 'G_aa', 'r_fd', 'Rb', 'Yb', 'Dp', 'Xab', 'As', 'Cn')
         args = [self._ptr(U, (max(nt, 0) + 1, S, N, nmu), 'U'), self._ptr(B_sys, (Q, S, 7, N, N), 'B_sys'),
@@ -745,20 +801,20 @@ class Native3DContext(_native.ContextBase):
             ph = self._dev2(phi, (nmu, max(nt, 0) + 1, K), 'phi')
             src = [c_vp(ph.data_ptr()), self._ptr(F2, (S, K, K), 'F2'), self._ptr(r_fd_K, (K, S, Q * N), 'r_fd_K'),
                    self._ptr(bdiv_K, (K, S, self.n_T), 'bdiv_K')]
-        need = int(self.lib.lrbms3_reduced_parabolic_estimate_batch_work_size(self.handle, N, nmu, nt))
+        need = int(getattr(self.lib, export + '_work_size')(self.handle, N, nmu, nt))
         if need < 0:
-            raise NativeError('reduced_parabolic_estimate_batch: bad N / nmu / nt')
+            raise NativeError('{}: bad N / nmu / nt'.format(export[7:]))
         if work is None:
             work = self.empty(need)
         if work.numel() < need:
-            raise NativeError('reduced_parabolic_estimate_batch: work too small')
+            raise NativeError('{}: work too small'.format(export[7:]))
         res = {'eta_loc': self.empty(3, nt + 1, S, nmu), 'time_deriv_nc': self.empty(nt, S, nmu), 'time_residual': self.empty(nt, nmu),
                'eta': self.empty(nt + 1, nmu), 'est': self.empty(nmu)}
-        rc = self.lib.lrbms3_reduced_parabolic_estimate_batch(
+        rc = getattr(self.lib, export)(
             self.handle, Q, N, K, nmu, nt, float(dt), th.ctypes.data_as(_P_DBL), cf.ctypes.data_as(_P_DBL), *args, float(hdiam), *src,
             c_vp(work.data_ptr()), *[c_vp(res[k].data_ptr()) for k in ('eta_loc', 'time_deriv_nc', 'time_residual', 'eta', 'est')],
             self._stream())
-        self._check(rc, 'lrbms3_reduced_parabolic_estimate_batch')
+        self._check(rc, export)
         return res
 
     # ------------------------------------------------------------------ online enrichment

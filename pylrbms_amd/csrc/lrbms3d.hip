@@ -4135,16 +4135,23 @@ int64_t lrbms3_fom_implicit_euler_batch_work_size(lrbms3_ctx* ctx, int32_t nmu) 
   return base + 16 * (int64_t)t.S * ((t.nT + FOM_EPB - 1) / FOM_EPB);          // + the partials of |M u_k + dt sum_j phi b_j|^2
 }
 
-int lrbms3_fom_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta, double dt, int32_t nt,
-                                    const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
-                                    double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// The driver of lrbms3_fom_implicit_euler_batch (tv == false: theta [nmu][Q], one table per panel for all its steps) and of its
+// _tv twin (tv == true: theta_t [nmu][nt+1][Q], the panel's table is filled with dt x row k + 1 ahead of the step k -> k + 1;
+// DESIGN.md 9.18).  The preconditioner of the call sits at the mean over the columns of ThetaRows::bar.
+int fom3_euler_batch_drive(lrbms3_ctx* ctx, const std::string& name, bool tv, int Q, int K, int nmu, const double* theta, double dt,
+                           int nt, const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                           double* U, double rtol, int max_iter, double* info, void* stream) {
   LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch: needs all subdomains on this rank");
+  if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": needs all subdomains on this rank");
   if (Q < 1 || Q > 8 || nmu < 1 || nmu > 64 || K < 1 || K > 64 || nt < 1 || max_iter < 1 || !(rtol > 0.0) || !(dt > 0.0))
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch: bad Q / nmu / K / nt / dt / max_iter / rtol");
-  if (!theta || !A_diag || !A_cpl || !b_K || !phi || !work || !U)
-    return lrbms_fail(ctx, LRBMS_E_INVALID, "fom_implicit_euler_batch: null argument");
+    return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": bad Q / nmu / K / nt / dt / max_iter / rtol");
+  if (!theta || !A_diag || !A_cpl || !b_K || !phi || !work || !U) return lrbms_fail(ctx, LRBMS_E_INVALID, name + ": null argument");
+  const ThetaRows tr{theta, Q, tv ? nt + 1 : 0};
   hipStream_t st = (hipStream_t)stream;
   const long S = t.S, nd = S * t.nT * 500, ncp = S * 6 * t.ncf * 100, total = S * t.n;
   FomWork w = fom_work(t, work);
@@ -4156,7 +4163,7 @@ int lrbms3_fom_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32
   QV tb{};
   for (int q = 0; q < Q; ++q) {
     double acc = 0.0;
-    for (int m = 0; m < nmu; ++m) acc += theta[(long)m * Q + q];
+    for (int m = 0; m < nmu; ++m) acc += tr.bar(m, q);
     tb.v[q] = dt * (acc / nmu);
   }
   launch_combine(st, nd, Q, tb, A_diag, w.Amu);
@@ -4175,10 +4182,14 @@ int lrbms3_fom_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32
   for (int m0 = 0; m0 < nmu; m0 += 16) {
     const int P = nmu - m0 < 16 ? nmu - m0 : 16;
     Fb3Op op{Q, P, nmu, m0, {}, A_diag, A_cpl, true};
-    for (int c = 0; c < 16; ++c)
-      for (int q = 0; q < 8; ++q) op.th.v[c][q] = (c < P && q < Q) ? dt * theta[(long)(m0 + c) * Q + q] : 0.0;
+    auto fill = [&](int row) {
+      for (int c = 0; c < 16; ++c)
+        for (int q = 0; q < 8; ++q) op.th.v[c][q] = (c < P && q < Q) ? dt * tr.at(m0 + c, row, q) : 0.0;
+    };
+    if (!tv) fill(0);
     double its_p = 0.0, worst_p = 0.0;
     for (int step = 0; step < nt; ++step) {
+      if (tv) fill(step + 1);                                // the operator of the step k -> k + 1: row k + 1
       const double* Uk = U + step * slab;
       double* X = U + (step + 1) * slab;
       hipLaunchKernelGGL(k3fb_load, dim3(gv), dim3(256), 0, st, total, P, nmu, m0, Uk, X, b.p);
@@ -4187,7 +4198,7 @@ int lrbms3_fom_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32
                          phi + (long)(step + 1) * K, b_K, b.p, b.y, b.r, pff);
       int it = 0;
       double rel = 0.0;
-      if (int rc = fomb3_panel_run(ctx, st, w, b, op, nc, A1inv, X, pff, rtol, max_iter, &it, &rel, "fom_implicit_euler_batch")) return rc;
+      if (int rc = fomb3_panel_run(ctx, st, w, b, op, nc, A1inv, X, pff, rtol, max_iter, &it, &rel, name.c_str())) return rc;
       its_p += it;
       if (rel > worst_p) worst_p = rel;
       if (rel > rtol) {                                      // this panel stops here; its later slabs are not written
@@ -4201,8 +4212,26 @@ int lrbms3_fom_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32
     if (worst_p > worst) worst = worst_p;
   }
   if (info) info[0] = its_sum, info[1] = worst;
-  if (missed) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, "fom_implicit_euler_batch: CG did not reach rtol");
+  if (missed) return lrbms_fail(ctx, LRBMS_E_NOT_CONVERGED, name + ": CG did not reach rtol");
   return LRBMS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lrbms3_fom_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta, double dt, int32_t nt,
+                                    const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                    double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+  return fom3_euler_batch_drive(ctx, "fom_implicit_euler_batch", false, Q, K, nmu, theta, dt, nt, A_diag, A_cpl, b_K, phi, work, U, rtol,
+                                max_iter, info, stream);
+}
+
+int lrbms3_fom_implicit_euler_batch_tv(lrbms3_ctx* ctx, int32_t Q, int32_t K, int32_t nmu, const double* theta_t, double dt, int32_t nt,
+                                       const double* A_diag, const double* A_cpl, const double* b_K, const double* phi, double* work,
+                                       double* U, double rtol, int32_t max_iter, double* info, void* stream) {
+  return fom3_euler_batch_drive(ctx, "fom_implicit_euler_batch_tv", true, Q, K, nmu, theta_t, dt, nt, A_diag, A_cpl, b_K, phi, work, U,
+                                rtol, max_iter, info, stream);
 }
 
 int lrbms3_fom_implicit_euler_batch_panel_info(lrbms3_ctx* ctx, double* out) {

@@ -113,6 +113,22 @@ inline QV make_theta(int Q, const double* theta) {
   return th;
 }
 
+// Host tables of the batched parabolic drivers and their _tv twins: theta [nmu][Q] with rows == 0 (the twin: a row
+// stride of zero, every step reads the one row), theta_t [nmu][rows][Q] with rows == nt + 1 (row k: the time of step k).
+struct ThetaRows {
+  const double* theta;
+  int Q, rows;
+  double at(int m, int k, int q) const { return rows ? theta[((long)m * rows + k) * Q + q] : theta[(long)m * Q + q]; }
+  // what the call's preconditioner takes for column m: the entry itself, or the mean over the rows 1 .. nt summed in ascending
+  // order (nt == 1: row 1 exactly)
+  double bar(int m, int q) const {
+    if (!rows) return theta[(long)m * Q + q];
+    double acc = 0.0;
+    for (int k = 1; k < rows; ++k) acc += at(m, k, q);
+    return acc / (rows - 1);
+  }
+};
+
 // ---- host functions that cross files.  Kernels that a second file launches (the bodies are one hipLaunchKernelGGL each, grid,
 // block and LDS as at the launches of the home file):
 // online3d.hip, called by lrbms3d.hip (the full-order solvers) and enrich3d.hip

@@ -1286,8 +1286,10 @@ long red_euler_batch_shared_size(long S, int N) { return S * 7 * N * N + S * N *
 long red_euler_batch_group_size(long S, int N) { return reduced_batch_group_size(S, N) - S * 7 * N * N - S * N * N; }
 
 // The driver of lrbms3_reduced_implicit_euler_batch(_src): a loop over the steps around red_batch_iterate.  K == 0: rhs [S][N] for
-// every column and step; K >= 1: rhs [K][S][N], phi_dev [nmu][nt+1][K] (device), step k takes row k + 1.
-int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, int nmu, const double* theta, double dt, int nt,
+// every column and step; K >= 1: rhs [K][S][N], phi_dev [nmu][nt+1][K] (device), step k takes row k + 1.  tv == false: theta [nmu][Q],
+// the groups' tables are filled once; tv == true (lrbms3_reduced_implicit_euler_batch_tv): theta_t [nmu][nt+1][Q],
+// the tables are refilled with dt x row k + 1 ahead of the step k -> k + 1, the preconditioner sits at the time mean (ThetaRows::bar).
+int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, bool tv, int Q, int N, int nmu, const double* theta, double dt, int nt,
                         const double* B_sys, const double* M_red, const double* rhs, int K, const double* phi_dev, double* work,
                         double* U, double rtol, int max_iter, double* info, hipStream_t st) {
   const T3& t = ctx->t;
@@ -1304,9 +1306,10 @@ int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, 
   double* Id = A0 + S * S;
   rocblas_int* pinfo = (rocblas_int*)(Id + S * S);
   double* gwork = Id + S * S + 2;
+  const ThetaRows tr{theta, Q, tv ? nt + 1 : 0};
   QV mean{}, one{};
   for (int m = 0; m < nmu; ++m)
-    for (int q = 0; q < Q; ++q) mean.v[q] += theta[m * Q + q] / nmu;
+    for (int q = 0; q < Q; ++q) mean.v[q] += tr.bar(m, q) / nmu;
   for (int q = 0; q < Q; ++q) mean.v[q] *= dt;
   one.v[0] = 1.0;
   hipLaunchKernelGGL(k3_combine, dim3((unsigned)((per_q + 255) / 256)), dim3(256), 0, st, per_q, Q, mean, B_sys, Amu);
@@ -1336,7 +1339,7 @@ int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, 
     rb_group_vectors(G, gwork + k * gsize, S, N);
     G.th = TB{};
     for (int m = 0; m < G.nm; ++m)
-      for (int q = 0; q < Q; ++q) G.th.v[m][q] = dt * theta[(G.m0 + m) * Q + q];      // dt folded into the table
+      for (int q = 0; q < Q; ++q) G.th.v[m][q] = dt * tr.at(G.m0 + m, 0, q);          // dt folded into the table (tv: refilled per step)
   }
   for (int k = 0; k < ng; ++k) LRBMS_HIP_CHECK(ctx, hipMemsetAsync(g[k].scal, 0, sizeof(double) * 80, g[k].st));
   const int check = A0inv ? 12 : 8;
@@ -1354,6 +1357,8 @@ int red_euler_batch_run(lrbms3_ctx* ctx, const std::string& name, int Q, int N, 
     for (int k = 0; k < ng; ++k) {
       RbGroup& G = g[k];
       const long vec = rows * G.nm;
+      for (int m = 0; tv && m < G.nm; ++m)      // the operator of the step k -> k + 1: row k + 1
+        for (int q = 0; q < Q; ++q) G.th.v[m][q] = dt * tr.at(G.m0 + m, step + 1, q);
       hipLaunchKernelGGL(k3b_gather, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, G.st, rows, G.nm,
                          nmu, uk + G.m0, G.z);
       launch_matvec3<true>(ctx, op, G, 1, G.prz, G.prz, none);
@@ -1409,7 +1414,7 @@ int lrbms3_reduced_implicit_euler_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, i
   if (Q < 1 || Q > 8 || N < 1 || N > 32 || nmu < 1 || nmu > 64 || !theta || !B_sys || !M_red || !rhs_red || !work || !U)
     return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch: needs N <= 32 and nmu <= 64");
   if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch: dt > 0 and nt >= 1 required");
-  return red_euler_batch_run(ctx, "reduced_implicit_euler_batch", Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red, 0, nullptr, work, U,
+  return red_euler_batch_run(ctx, "reduced_implicit_euler_batch", false, Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red, 0, nullptr, work, U,
                              rtol, max_iter, info, (hipStream_t)stream);
 }
 
@@ -1424,8 +1429,25 @@ int lrbms3_reduced_implicit_euler_batch_src(lrbms3_ctx* ctx, int32_t Q, int32_t 
     return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_src: needs N <= 32 and nmu <= 64");
   if (K < 1 || K > 64) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_src: need 1 <= K <= 64");
   if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_src: dt > 0 and nt >= 1 required");
-  return red_euler_batch_run(ctx, "reduced_implicit_euler_batch_src", Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red_K, K, phi, work, U,
+  return red_euler_batch_run(ctx, "reduced_implicit_euler_batch_src", false, Q, N, nmu, theta, dt, nt, B_sys, M_red, rhs_red_K, K, phi, work, U,
                              rtol, max_iter, info, (hipStream_t)stream);
+}
+
+// theta_t [nmu][nt+1][Q] host; K == 0: rhs_red_K is rhs_red [S][N] and phi is null, K >= 1: rhs_red_K [K][S][N] and phi (device)
+int lrbms3_reduced_implicit_euler_batch_tv(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, const double* theta_t, double dt,
+                                           int32_t nt, const double* B_sys, const double* M_red, const double* rhs_red_K,
+                                           const double* phi, double* work, double* U, double rtol, int32_t max_iter, double* info,
+                                           void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (ctx->t.S_ext != ctx->t.S)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_tv: needs all subdomains on this rank");
+  if (Q < 1 || Q > 8 || N < 1 || N > 32 || nmu < 1 || nmu > 64 || !theta_t || !B_sys || !M_red || !rhs_red_K || !work || !U)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_tv: needs N <= 32 and nmu <= 64");
+  if (K < 0 || K > 64 || (K > 0) != (phi != nullptr))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_tv: need 0 <= K <= 64, phi with K >= 1 and null with K = 0");
+  if (!(dt > 0.0) || nt < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "reduced_implicit_euler_batch_tv: dt > 0 and nt >= 1 required");
+  return red_euler_batch_run(ctx, "reduced_implicit_euler_batch_tv", true, Q, N, nmu, theta_t, dt, nt, B_sys, M_red, rhs_red_K, K, phi, work,
+                             U, rtol, max_iter, info, (hipStream_t)stream);
 }
 
 int64_t lrbms3_reduced_time_residual_work_size(lrbms3_ctx* ctx, int32_t N) {
@@ -1482,6 +1504,26 @@ __global__ __launch_bounds__(256) void k3pe_tables(int Q, int K, int nmu, int nt
   }
 }
 
+// The per-step variant of k3pe_tables (lrbms3_reduced_parabolic_estimate_batch_tv): row k of the group's columns, theta from the
+// kernel argument into thd_t [nt+1][nmu][Q], phi [nmu][nt+1][K] into phid [nt+1][nmu][K]
+__global__ __launch_bounds__(256) void k3pe_tables_tv(int Q, int K, int nmu, int nt, int k, int m0, int nm, TB th,
+                                                      const double* __restrict__ phi, double* __restrict__ thd_t,
+                                                      double* __restrict__ phid) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < nm * Q; i += 256) thd_t[((long)k * nmu + m0) * Q + i] = th.v[i / Q][i % Q];
+  for (int i = tid; i < nm * K; i += 256) {
+    const long m = m0 + i / K, j = i % K;
+    phid[((long)k * nmu + m) * K + j] = phi[(m * (nt + 1) + k) * K + j];
+  }
+}
+
+// A chunk of a host table into the work array in stream order: the chunk is the kernel argument (2 KB), so no copy from pageable
+// host memory and no host synchronisation (2D: k_pe_put)
+struct PeChunk { double v[256]; };
+__global__ __launch_bounds__(256) void k3pe_put(int n, PeChunk c, double* __restrict__ dst) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = c.v[threadIdx.x];
+}
+
 // out[s ldo + m] = y^T Minv[s] y for the columns m < nm of the compact panel y [S][N][nm] (N <= 32): one workgroup per subdomain,
 // the panel in the LDS, thread = (row group tid >> 4, column tid & 15) -- the 16 lanes of a row group share the row of the inverse --
 // and the products y_i (Minv y)_i summed over the rows in ascending order
@@ -1509,16 +1551,27 @@ __global__ __launch_bounds__(256) void k3pe_inv_norm2_panel(int N, int nm, int l
 }
 
 struct PeCoef { double v[64][2]; };      // coef [nmu][2]: one kernel argument (1 KB)
+// the two coefficients of (column m, step k): from the kernel argument (k3pe_combine), from the table [nmu][nt+1][2] (k3pe_combine_tv)
+struct PeCoefArg {
+  const PeCoef& cf;
+  __device__ double get(int m, int, int i) const { return cf.v[m][i]; }
+};
+struct PeCoefTable {
+  const double* __restrict__ coef;
+  int nt;
+  __device__ double get(int m, int k, int i) const { return coef[((long)m * (nt + 1) + k) * 2 + i]; }
+};
 
 // The five outputs from the raw rows: one workgroup per 16 columns, thread = (part tid >> 4, column tid & 15).  Sums over the
 // subdomains: part g takes s = g, g + 16, ... in ascending order, the 16 parts are then added in their order.
 //   raw [nt+1][3][S][nmu] (nc, r, df of U[k]), src [nt+1][S][nmu] or nullptr (the f terms of the r row), ncd [nt][3][S][nmu] (row 0:
 //   nc of the differences), tr2 [nt][S][nmu] (y^T M_red^-1 y)
-__global__ __launch_bounds__(256) void k3pe_combine(int S, int nmu, int nt, double dt, PeCoef cf, const double* __restrict__ raw,
-                                                    const double* __restrict__ src, const double* __restrict__ ncd,
-                                                    const double* __restrict__ tr2, double* __restrict__ eta_loc,
-                                                    double* __restrict__ tdnc, double* __restrict__ tres, double* __restrict__ eta,
-                                                    double* __restrict__ est) {
+template <class CF>
+__device__ __forceinline__ void pe_combine_body(int S, int nmu, int nt, double dt, const CF& cf, const double* __restrict__ raw,
+                                                const double* __restrict__ src, const double* __restrict__ ncd,
+                                                const double* __restrict__ tr2, double* __restrict__ eta_loc,
+                                                double* __restrict__ tdnc, double* __restrict__ tres, double* __restrict__ eta,
+                                                double* __restrict__ est) {
   __shared__ double buf[2][16 * 16];
   const int tid = threadIdx.x, g = tid >> 4, mm = tid & 15, m = blockIdx.x * 16 + mm;
   const bool on = m < nmu;
@@ -1549,7 +1602,7 @@ __global__ __launch_bounds__(256) void k3pe_combine(int S, int nmu, int nt, doub
         s_nc += buf[0][p * 16 + mm];
         s_rd += buf[1][p * 16 + mm];
       }
-      const double ek = sc * (cf.v[m][0] * sqrt(s_nc) + cf.v[m][1] * sqrt(s_rd));
+      const double ek = sc * (cf.get(m, k, 0) * sqrt(s_nc) + cf.get(m, k, 1) * sqrt(s_rd));
       eta[(long)k * nmu + m] = ek;
       e2 += ek * ek;
     }
@@ -1583,12 +1636,32 @@ __global__ __launch_bounds__(256) void k3pe_combine(int S, int nmu, int nt, doub
   if (g == 0 && on) est[m] = sqrt(e2) + sqrt(r2) + sqrt(d2);
 }
 
+__global__ __launch_bounds__(256) void k3pe_combine(int S, int nmu, int nt, double dt, PeCoef cf, const double* __restrict__ raw,
+                                                    const double* __restrict__ src, const double* __restrict__ ncd,
+                                                    const double* __restrict__ tr2, double* __restrict__ eta_loc,
+                                                    double* __restrict__ tdnc, double* __restrict__ tres, double* __restrict__ eta,
+                                                    double* __restrict__ est) {
+  pe_combine_body(S, nmu, nt, dt, PeCoefArg{cf}, raw, src, ncd, tr2, eta_loc, tdnc, tres, eta, est);
+}
+
+// k3pe_combine with the coefficients per (column, step) from coef [nmu][nt+1][2] on the device: the same thread mapping and summation
+// order, so a table that is constant in time gives the bits of k3pe_combine
+__global__ __launch_bounds__(256) void k3pe_combine_tv(int S, int nmu, int nt, double dt, const double* __restrict__ coef,
+                                                       const double* __restrict__ raw, const double* __restrict__ src,
+                                                       const double* __restrict__ ncd, const double* __restrict__ tr2,
+                                                       double* __restrict__ eta_loc, double* __restrict__ tdnc,
+                                                       double* __restrict__ tres, double* __restrict__ eta, double* __restrict__ est) {
+  pe_combine_body(S, nmu, nt, dt, PeCoefTable{coef, nt}, raw, src, ncd, tr2, eta_loc, tdnc, tres, eta, est);
+}
+
 // doubles of work: raw, dU, ncd, tr2, src | thd [64][8], phid [nt+1][nmu][64] | Minv, the 7-slot copy of M_red the block inverse
 // reads | one group's panel vectors z, p, y [S][N][16] and partials [S][16]
 long pe_batch3_work_size(long S, long N, long nmu, long nt) {
   return (nt + 1) * 3 * S * nmu + nt * S * N * nmu + nt * 3 * S * nmu + nt * S * nmu + (nt + 1) * S * nmu + 64 * 8 + (nt + 1) * nmu * 64 +
          S * N * N + 7 * S * N * N + 3 * S * N * 16 + S * 16;
 }
+// behind the work of the twin, the tables of the _tv form: thd_t [nt+1][nmu][8], coef [nmu][nt+1][2]
+long pe_batch3_tv_extra(long nmu, long nt) { return (nt + 1) * nmu * 8 + ((nmu * (nt + 1) * 2 + 15) & ~15L); }
 
 }  // namespace
 
@@ -1599,18 +1672,34 @@ int64_t lrbms3_reduced_parabolic_estimate_batch_work_size(lrbms3_ctx* ctx, int32
   return pe_batch3_work_size(ctx->t.S, N, nmu, nt);
 }
 
-int lrbms3_reduced_parabolic_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, int32_t nt, double dt,
-                                            const double* theta, const double* coef, const double* U, const double* B_sys,
-                                            const double* M_red, const double* G_nc, const double* G_bb, const double* G_rdd,
-                                            const double* G_ab, const double* G_aa, const double* r_fd, const double* Rb, const double* Yb,
-                                            const double* Dp, const double* Xab, const double* As, const double* Cn, const double* ebar,
-                                            const double* Bbb, const double* bdiv, const double* f2, const double* ceps, double hdiam,
-                                            const double* phi, const double* F2, const double* r_fd_K, const double* bdiv_K, double* work,
-                                            double* eta_loc, double* time_deriv_nc, double* time_residual, double* eta, double* est,
-                                            void* stream) {
+int64_t lrbms3_reduced_parabolic_estimate_batch_tv_work_size(lrbms3_ctx* ctx, int32_t N, int32_t nmu, int32_t nt) {
+  const int64_t base = lrbms3_reduced_parabolic_estimate_batch_work_size(ctx, N, nmu, nt);
+  return base < 0 ? -1 : base + pe_batch3_tv_extra(nmu, nt);
+}
+
+}  // extern "C"
+
+namespace {
+
+#define LRBMS3_PE_PARAMS                                                                                                                \
+  lrbms3_ctx *ctx, int32_t Q, int32_t N, int32_t K, int32_t nmu, int32_t nt, double dt, const double *theta, const double *coef,        \
+      const double *U, const double *B_sys, const double *M_red, const double *G_nc, const double *G_bb, const double *G_rdd,           \
+      const double *G_ab, const double *G_aa, const double *r_fd, const double *Rb, const double *Yb, const double *Dp,                 \
+      const double *Xab, const double *As, const double *Cn, const double *ebar, const double *Bbb, const double *bdiv,                 \
+      const double *f2, const double *ceps, double hdiam, const double *phi, const double *F2, const double *r_fd_K,                    \
+      const double *bdiv_K, double *work, double *eta_loc, double *time_deriv_nc, double *time_residual, double *eta, double *est,      \
+      void *stream
+#define LRBMS3_PE_ARGS                                                                                                                  \
+  ctx, Q, N, K, nmu, nt, dt, theta, coef, U, B_sys, M_red, G_nc, G_bb, G_rdd, G_ab, G_aa, r_fd, Rb, Yb, Dp, Xab, As, Cn, ebar, Bbb, bdiv, \
+      f2, ceps, hdiam, phi, F2, r_fd_K, bdiv_K, work, eta_loc, time_deriv_nc, time_residual, eta, est, stream
+
+// The driver of lrbms3_reduced_parabolic_estimate_batch (tv == false: theta [nmu][Q], coef [nmu][2]) and of its _tv twin (tv == true:
+// theta_t [nmu][nt+1][Q], coef [nmu][nt+1][2]): the elliptic rows and the source terms of U[k] use row k, as does
+// coef in eta[k]; the time residual of U[k+1] - U[k] uses row k + 1 (the operator that produced U[k+1]); the nc form of the
+// differences reads no theta.
+int pe_batch3_drive(const char* name, bool tv, LRBMS3_PE_PARAMS) {
   LRBMS_REQUIRE_MESH(ctx);
   const T3& t = ctx->t;
-  const char* name = "reduced_parabolic_estimate_batch";
   if (t.S_ext != t.S) return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": needs all subdomains on this rank");
   if (Q < 1 || Q > 8 || N < 1 || N > 32 || Q * N > 64 || nmu < 1 || nmu > 64 || K < 0 || K > 64)
     return lrbms_fail(ctx, LRBMS_E_INVALID, std::string(name) + ": needs N <= 32, Q N <= 64, 1 <= nmu <= 64 and 0 <= K <= 64");
@@ -1635,12 +1724,22 @@ int lrbms3_reduced_parabolic_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t 
   double* Minv = phid + (long)(nt + 1) * nmu * 64;
   double* Mslot = Minv + S * NN;
   double* gw = Mslot + 7 * S * NN;
+  double* thd_t = work + pe_batch3_work_size(S, N, nmu, nt);      // tv only: theta rows [nt+1][nmu][Q], then coef [nmu][nt+1][2]
+  double* coef_t = thd_t + (long)(nt + 1) * nmu * 8;
+  const ThetaRows tr{theta, Q, tv ? nt + 1 : 0};
+  std::vector<double> th_row((size_t)nmu * Q);                    // tv: row k of every column, contiguous
+  auto row_of = [&](int k) {
+    if (!tv) return theta;
+    for (int m = 0; m < nmu; ++m)
+      for (int q = 0; q < Q; ++q) th_row[(size_t)m * Q + q] = tr.at(m, k, q);
+    return (const double*)th_row.data();
+  };
   EA a{U, G_nc, G_bb, G_rdd, G_ab, G_aa, r_fd, Rb, Yb, Dp, Xab, As, Cn, ebar, Bbb, bdiv, f2, ceps, hdiam, raw};
   // ---- 1. the elliptic rows of every slab
   for (int k = 0; k <= nt; ++k) {
     a.u = U + k * slab;
     a.eta = raw + k * 3 * SM;
-    if (int rc = launch_reduced_estimate_batch(ctx, st, Q, N, nmu, theta, a)) return rc;
+    if (int rc = launch_reduced_estimate_batch(ctx, st, Q, N, nmu, row_of(k), a)) return rc;
   }
   // ---- 2. the differences
   {
@@ -1649,10 +1748,11 @@ int lrbms3_reduced_parabolic_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t 
   }
   // ---- 3. their nc form: the nc-only matrix-core kernel, or row 0 of the full estimate where that form is not the one in use
   const bool nc16 = estimate_batch_form(ctx, Q, N) == 16 && estimate_nc16_fits(ctx, N);
+  const double* th_nc = row_of(0);                               // (row 0 of the full estimate reads no theta)
   for (int k = 0; k < nt; ++k) {
     a.u = dU + k * slab;
     a.eta = ncd + k * 3 * SM;
-    if (int rc = nc16 ? launch_estimate_nc_batch(ctx, st, N, nmu, a) : launch_reduced_estimate_batch(ctx, st, Q, N, nmu, theta, a)) return rc;
+    if (int rc = nc16 ? launch_estimate_nc_batch(ctx, st, N, nmu, a) : launch_reduced_estimate_batch(ctx, st, Q, N, nmu, th_nc, a)) return rc;
   }
   // ---- 4. the time residual: M_red^-1 once (the block inverse reads the self slot of a 7-slot operator, with its identity rule on
   // zero-padded basis columns), then per step and group y = sum_q theta_qm B_q dU by the panel matvec and y^T M_red^-1 y
@@ -1672,12 +1772,20 @@ int lrbms3_reduced_parabolic_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t 
     G.Ap = G.pn + rows * 16;
     G.ppap = G.Ap + rows * 16;
     G.th = TB{};
-    for (int m = 0; m < G.nm; ++m)
-      for (int q = 0; q < Q; ++q) G.th.v[m][q] = theta[(m0 + m) * Q + q];
-    if (K > 0) hipLaunchKernelGGL(k3pe_tables, dim3(1), dim3(256), 0, st, Q, K, nmu, nt, m0, G.nm, G.th, phi, thd, phid);
+    auto fill = [&](int row) {
+      for (int m = 0; m < G.nm; ++m)
+        for (int q = 0; q < Q; ++q) G.th.v[m][q] = tr.at(m0 + m, row, q);
+    };
+    fill(0);
+    if (K > 0 && !tv) hipLaunchKernelGGL(k3pe_tables, dim3(1), dim3(256), 0, st, Q, K, nmu, nt, m0, G.nm, G.th, phi, thd, phid);
+    if (K > 0 && tv) hipLaunchKernelGGL(k3pe_tables_tv, dim3(1), dim3(256), 0, st, Q, K, nmu, nt, 0, m0, G.nm, G.th, phi, thd_t, phid);
     const RbOp op{Q, N, nmu, B_sys, nullptr, nullptr, nullptr};
     const long vec = rows * G.nm;
     for (int k = 0; k < nt; ++k) {
+      if (tv) {                        // the operator that produced U[k + 1]: row k + 1, for the matvec and for the source terms of U[k + 1]
+        fill(k + 1);
+        if (K > 0) hipLaunchKernelGGL(k3pe_tables_tv, dim3(1), dim3(256), 0, st, Q, K, nmu, nt, k + 1, m0, G.nm, G.th, phi, thd_t, phid);
+      }
       hipLaunchKernelGGL(k3b_gather, dim3((unsigned)((vec + 255) / 256 > 4096 ? 4096 : (vec + 255) / 256)), dim3(256), 0, st, rows, G.nm, nmu,
                          dU + k * slab + m0, G.z);
       launch_matvec3<false>(ctx, op, G, 1, G.ppap, G.ppap, none);
@@ -1687,14 +1795,42 @@ int lrbms3_reduced_parabolic_estimate_batch(lrbms3_ctx* ctx, int32_t Q, int32_t 
   // ---- 5. the f terms of the r rows (K >= 1: the caller's f2, r_fd and bdiv are zero)
   if (K > 0)
     for (int k = 0; k <= nt; ++k)
-      launch_source_terms(st, t, Q, N, K, nmu, thd, phid + (long)k * nmu * K, F2, r_fd_K, bdiv_K, Rb, U + k * slab, ceps, hdiam, src + k * SM);
+      launch_source_terms(st, t, Q, N, K, nmu, tv ? thd_t + (long)k * nmu * Q : thd, phid + (long)k * nmu * K, F2, r_fd_K, bdiv_K, Rb,
+                          U + k * slab, ceps, hdiam, src + k * SM);
   // ---- 6. the five outputs
-  PeCoef cf{};
-  for (int m = 0; m < nmu; ++m) cf.v[m][0] = coef[m * 2], cf.v[m][1] = coef[m * 2 + 1];
-  hipLaunchKernelGGL(k3pe_combine, dim3((nmu + 15) / 16), dim3(256), 0, st, (int)S, nmu, nt, dt, cf, raw, K > 0 ? src : nullptr, ncd, tr2, eta_loc,
-                     time_deriv_nc, time_residual, eta, est);
+  if (!tv) {
+    PeCoef cf{};
+    for (int m = 0; m < nmu; ++m) cf.v[m][0] = coef[m * 2], cf.v[m][1] = coef[m * 2 + 1];
+    hipLaunchKernelGGL(k3pe_combine, dim3((nmu + 15) / 16), dim3(256), 0, st, (int)S, nmu, nt, dt, cf, raw, K > 0 ? src : nullptr, ncd, tr2,
+                       eta_loc, time_deriv_nc, time_residual, eta, est);
+  } else {                             // coef [nmu][nt+1][2] has no bound in nt: into the work array in chunks, in stream order
+    const long nc = (long)nmu * (nt + 1) * 2;
+    for (long c0 = 0; c0 < nc; c0 += 256) {
+      PeChunk c;
+      const int n = nc - c0 < 256 ? (int)(nc - c0) : 256;
+      for (int i = 0; i < 256; ++i) c.v[i] = i < n ? coef[c0 + i] : 0.0;
+      hipLaunchKernelGGL(k3pe_put, dim3(1), dim3(256), 0, st, n, c, coef_t + c0);
+    }
+    hipLaunchKernelGGL(k3pe_combine_tv, dim3((nmu + 15) / 16), dim3(256), 0, st, (int)S, nmu, nt, dt, coef_t, raw, K > 0 ? src : nullptr, ncd,
+                       tr2, eta_loc, time_deriv_nc, time_residual, eta, est);
+  }
   LRBMS_LAUNCH_CHECK(ctx);
   return LRBMS_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int lrbms3_reduced_parabolic_estimate_batch(LRBMS3_PE_PARAMS) {
+  return pe_batch3_drive("reduced_parabolic_estimate_batch", false, LRBMS3_PE_ARGS);
+}
+
+// theta = theta_t [nmu][nt+1][Q], coef [nmu][nt+1][2] (host); work: lrbms3_reduced_parabolic_estimate_batch_tv_work_size doubles
+int lrbms3_reduced_parabolic_estimate_batch_tv(LRBMS3_PE_PARAMS) {
+  return pe_batch3_drive("reduced_parabolic_estimate_batch_tv", true, LRBMS3_PE_ARGS);
+}
+#undef LRBMS3_PE_ARGS
+#undef LRBMS3_PE_PARAMS
 
 }  // extern "C"

@@ -35,6 +35,8 @@ _NEEDS_KEYWORD = 'online enrichment in 3D needs the corrector data: discretize(.
 class BlockDiscretization3D:
     _src = None                        # the affine source record (``sources3d.setup_sources3d``); None: one component, coefficient 1
     _time_dependent_source = False     # the parabolic subclass takes coefficients c(mu, t)
+    _tv = False                        # a diffusion coefficient reads the time: theta_q(t, mu), a row per step
+    _theta_arity = None                # 1 / 2 per diffusion coefficient (``sources3d.coefficient_arity``); None: all c(mu)
 
     def __init__(self, p, device_index=0, online_enrichment=False):
         self.grid = p['grid']
@@ -56,10 +58,15 @@ class BlockDiscretization3D:
                     raise NotImplementedError('a source coefficient c(mu, t) depends on time: this needs the parabolic discretize')
                 f = sources3d.sum_function(comp[0])          # the engine is built on sum_j f_j, as in 2D
         self.coefficients = list(lam['coefficients'])
+        from pylrbms_amd.sources3d import diffusion_arities
+        self._theta_arity = diffusion_arities(self.coefficients)      # c(mu) or c(mu, t), read before any device work
+        self._tv = 2 in self._theta_arity
+        if self._tv and not self._time_dependent_source:
+            raise NotImplementedError('a diffusion coefficient c(mu, t) depends on time: this needs the parabolic discretize')
         self.mu_bar, self.mu_hat = p['mu_bar'], p['mu_hat']
         self.engine = Engine3D(self.grid, lam['functions'], f, p['lambda_bar'], p['lambda_hat'],
                                data_degree=p.get('data_degree', 2), device_index=device_index,
-                               theta_bar=[float(c(self.mu_bar)) for c in self.coefficients]).assemble(self.online_enrichment)
+                               theta_bar=list(self._theta_at(self.mu_bar, 0.0))).assemble(self.online_enrichment)
         self.Q = self.engine.Q
         self.solution_space = BlockSpace3D(self.engine.S, self.engine.S * self.engine.t.n)
         self.parameter_range = p.get('parameter_range')
@@ -80,7 +87,18 @@ class BlockDiscretization3D:
         from pylrbms_amd.sources3d import evaluate_stationary
         return self.engine.ctx.combine_sources(evaluate_stationary(self._src, mu), self._src['b_K'])
 
+    def _coefficient(self, q, mu, t):
+        """Diffusion coefficient q at (mu, t): ``c(mu)``, or ``c(mu, t)`` where its signature takes the time."""
+        c = self.coefficients[q]
+        return c(mu, t) if self._theta_arity is not None and self._theta_arity[q] == 2 else c(mu)
+
+    def _theta_at(self, mu, t):
+        return np.array([float(self._coefficient(q, mu, t)) for q in range(len(self.coefficients))], dtype=np.float64)
+
     def theta(self, mu):
+        if self._tv:
+            raise NotImplementedError('the diffusion coefficients depend on time: no single row is "the" theta '
+                                      '(diffusion_coefficients(mu) is the table of all steps)')
         return np.array([float(c(mu)) for c in self.coefficients], dtype=np.float64)
 
     def parse_parameter(self, mu):
@@ -117,13 +135,14 @@ class BlockDiscretization3D:
             cols += [x[:, a] - centre[a] for a in range(3)]
         return eng.ctx.from_numpy(np.stack(cols, axis=1))
 
-    def alpha(self, mu, mu2):
+    def alpha(self, mu, mu2, t=0.0):
         """min_q theta_q(mu) / theta_q(mu2) as written in the reference: the loop returns in its first pass
-        (estimators.py:114-121), i.e. the first component only."""
-        return self.coefficients[0](mu) / self.coefficients[0](mu2)
+        (estimators.py:114-121), i.e. the first component only.  With coefficients of the time, ``mu`` is taken at ``t`` and the
+        reference parameter ``mu2`` (mu_bar / mu_hat) at t = 0."""
+        return self._coefficient(0, mu, t) / self._coefficient(0, mu2, 0.0)
 
-    def gamma(self, mu, mu2):
-        return max(c(mu) / c(mu2) for c in self.coefficients)
+    def gamma(self, mu, mu2, t=0.0):
+        return max(self._coefficient(q, mu, t) / self._coefficient(q, mu2, 0.0) for q in range(len(self.coefficients)))
 
     def combine(self, eta_loc, mu, decompose=False):
         """EstimatorBase._estimate_elliptic (estimators.py:99-112) from the local terms [3, S]."""

@@ -16,6 +16,13 @@ The estimate restates ``OracleParabolic.estimate`` (oracle/parabolic.py): the el
 scaled by 2 sqrt(dt / 3); ``time_residual_k = sqrt(dt / 3 * sum_s y^T M_s^-1 y)`` with ``y = A(mu) (U_{k+1} - U_k)``;
 ``time_deriv_nc = sqrt(max(nc(dU), 0) / dt)``; ``est = |eta| + |time_residual| + |time_deriv_nc|``.
 
+Diffusion coefficients of the time (2D: 5.4.6): a ``p['lambda']['coefficients']`` entry with the signature
+``c(mu, t)`` makes the discretization time-dependent (``d._tv``).  ``d.diffusion_coefficients(mu)`` is the table theta_t [nt + 1, Q]
+at the times of the source table; the step k -> k + 1 solves with row k + 1.  ``solve`` / ``solve_batch``, ``rd.solve`` /
+``rd.solve_batch`` and ``rd.estimate`` / ``rd.estimate_batch`` run the three ``lrbms3_*_tv`` exports (the single calls as one
+column: a single-trajectory export combines ``M + dt A`` once and has no row to change).  mu_bar / mu_hat sit at t = 0.  For
+d/dt A != 0 the estimate is an indicator, not a proven bound.
+
 Not built (``NotImplementedError``): the elliptic-reconstruction terms (the reference's branch is ``assert False``,
 estimators.py:64), sharded discretizations (``S_ext != S``) and ``enrich_local``."""
 import numpy as np
@@ -26,11 +33,16 @@ from pylrbms_amd.parameters import CubicParameterSpace
 from pylrbms_amd.reductor import LocalBasisSlab
 
 
-def _parabolic_estimate(d, mu, dt, eta_loc, time_residual2, time_deriv_nc2):
+def _parabolic_estimate(d, mu, dt, eta_loc, time_residual2, time_deriv_nc2, times=None):
     """ParabolicEstimator.estimate (estimators.py:141-168) from the local elliptic terms eta_loc [3, S, L] of the L vectors, the
-    summed time residuals y^T M^-1 y [L - 1] and the nc terms of the differences [S, L - 1] (all squared quantities)."""
+    summed time residuals y^T M^-1 y [L - 1] and the nc terms of the differences [S, L - 1] (all squared quantities).  ``times``
+    [L] (coefficients of the time): alpha and gamma of vector k are taken at t_k, mu_bar / mu_hat at t = 0."""
     nc, r, df = (np.asarray(x, dtype=np.float64) for x in eta_loc)
-    a_bar, a_hat, g_bar = d.alpha(mu, d.mu_bar), d.alpha(mu, d.mu_hat), d.gamma(mu, d.mu_bar)
+    if times is None:
+        a_bar, a_hat, g_bar = d.alpha(mu, d.mu_bar), d.alpha(mu, d.mu_hat), d.gamma(mu, d.mu_bar)
+    else:
+        a_bar, a_hat, g_bar = (np.array([fn(mu, ref, t) for t in times], dtype=np.float64)
+                               for fn, ref in ((d.alpha, d.mu_bar), (d.alpha, d.mu_hat), (d.gamma, d.mu_bar)))
     eta = (np.sqrt(g_bar) * np.linalg.norm(nc, axis=0) + (1.0 / np.sqrt(a_hat)) * np.linalg.norm(r + df, axis=0)) / np.sqrt(a_bar)
     time_residual = np.sqrt(np.asarray(time_residual2, dtype=np.float64) * (dt / 3))
     s = 2 * np.sqrt(dt / 3)
@@ -59,12 +71,46 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
         from pylrbms_amd.sources3d import evaluate_table
         return evaluate_table(self._src, mu, self.dt, nt)
 
+    def diffusion_coefficients(self, mu):
+        """The host table theta_t [nt + 1, Q] of the diffusion coefficients: row k at the time of row k of ``source_coefficients``
+        (``sources3d.table_times``).  The step k -> k + 1 solves with row k + 1; in the estimate the elliptic rows of U_k use row k
+        and the time residual of U_{k+1} - U_k row k + 1.  Every entry must be positive (ValueError naming q and k).  On a
+        time-independent discretization every row is ``theta(mu)``."""
+        from pylrbms_amd.sources3d import table_times
+        nt = self.time_stepper.nt
+        if not self._tv:
+            return np.tile(self.theta(mu), (nt + 1, 1))
+        tab = np.stack([self._theta_at(mu, t) for t in table_times(self.dt, nt).tolist()])
+        bad = np.argwhere(~(tab > 0.0))
+        if len(bad):
+            k, q = (int(v) for v in bad[0])
+            raise ValueError('diffusion coefficient q = {} is {!r} at step k = {} (t = {!r}), mu = {!r}: every theta_q(t, mu) must '
+                             'be positive'.format(q, float(tab[k, q]), k, k * self.dt, mu))
+        return tab
+
+    def _estimator_coefficients(self, mu):
+        """coef [nt + 1, 2] of ``lrbms3_reduced_parabolic_estimate_batch_tv``: (sqrt(gamma_bar / alpha_bar), 1 / sqrt(alpha_hat
+        alpha_bar)) with mu at t_k and mu_bar / mu_hat at t = 0."""
+        from pylrbms_amd.sources3d import table_times
+        out = np.empty((self.time_stepper.nt + 1, 2))
+        for k, t in enumerate(table_times(self.dt, self.time_stepper.nt).tolist()):
+            a_bar, a_hat, g_bar = self.alpha(mu, self.mu_bar, t), self.alpha(mu, self.mu_hat, t), self.gamma(mu, self.mu_bar, t)
+            out[k] = np.sqrt(g_bar / a_bar), 1.0 / np.sqrt(a_hat * a_bar)
+        return out
+
     def solve(self, mu, rtol=1e-10, max_iter=50000, return_info=False):
         """The trajectory as a device slab U [S, n, nt + 1] (U[:, :, 0] = the initial data): all nt implicit Euler steps in one
         native call, each a warm-started two-level CG on M + dt A(mu).  ``last_solve_info`` = (total CG iterations, worst relative
-        residual)."""
+        residual).  With diffusion coefficients of the time: one column of ``lrbms3_fom_implicit_euler_batch_tv``."""
         eng = self.engine
-        if self._src is None:
+        if self._tv:
+            b_K = self._src['b_K'] if self._src is not None else eng.ops['b'].reshape(1, eng.S, eng.t.n)
+            phi = np.asarray(self.source_coefficients(mu), dtype=np.float64)[None]
+            U, inf = eng.ctx.fom_implicit_euler_batch_tv(self.diffusion_coefficients(mu)[None], self.dt, self.time_stepper.nt,
+                                                         eng.ops['A_diag'], eng.ops['A_cpl'], b_K, phi, U0=self.initial_data, rtol=rtol,
+                                                         max_iter=max_iter)
+            U, info = U[:, :, :, 0], (inf['iterations'], inf['relative_residual'])
+        elif self._src is None:
             U, info = eng.ctx.fom_implicit_euler(self.Q, self.theta(mu), self.dt, self.time_stepper.nt, eng.ops['A_diag'],
                                                  eng.ops['A_cpl'], eng.ops['b'], U0=self.initial_data, rtol=rtol, max_iter=max_iter)
         else:
@@ -75,9 +121,15 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
         U = U.permute(1, 2, 0).contiguous()
         return (U, info) if return_info else U
 
+    def _no_stationary(self):
+        if self._tv:
+            raise NotImplementedError('the diffusion coefficients depend on time (a coefficient c(mu, t)): there is no stationary '
+                                      'operator, this needs the parabolic solve')
+
     def solve_stationary(self, mu, rtol=1e-10, max_iter=50000, return_info=False):
         """The elliptic solve of the underlying discretization (the limit t -> oo).  NotImplementedError if a source coefficient
         depends on time (before the engine is read)."""
+        self._no_stationary()
         if self._src is not None:
             from pylrbms_amd.sources3d import evaluate_stationary
             evaluate_stationary(self._src, mu)
@@ -107,12 +159,15 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
                 trajs.append(U)
                 its, rel = its + info[0], max(rel, info[1])
         else:
-            theta = np.stack([self.theta(mu) for mu in mus])
+            if self._tv:                                   # a theta row per step: [len(mus), nt + 1, Q]
+                theta, native = np.stack([self.diffusion_coefficients(mu) for mu in mus]), eng.ctx.fom_implicit_euler_batch_tv
+            else:
+                theta, native = np.stack([self.theta(mu) for mu in mus]), eng.ctx.fom_implicit_euler_batch
             phi = np.stack([np.asarray(self.source_coefficients(mu), dtype=np.float64) for mu in mus])     # [len(mus), nt + 1, K]
             b_K = self._src['b_K'] if self._src is not None else eng.ops['b'].reshape(1, eng.S, eng.t.n)
             for m0 in range(0, len(mus), 64):
-                U, info = eng.ctx.fom_implicit_euler_batch(theta[m0:m0 + 64], self.dt, nt, eng.ops['A_diag'], eng.ops['A_cpl'], b_K,
-                                                           phi[m0:m0 + 64], U0=self.initial_data, rtol=rtol, max_iter=max_iter)
+                U, info = native(theta[m0:m0 + 64], self.dt, nt, eng.ops['A_diag'], eng.ops['A_cpl'], b_K,
+                                 phi[m0:m0 + 64], U0=self.initial_data, rtol=rtol, max_iter=max_iter)
                 its, rel = its + info['iterations'], max(rel, info['relative_residual'])
                 trajs += [U[:, :, :, m].permute(1, 2, 0) for m in range(U.shape[3])]
         self.last_solve_info = (its, rel)
@@ -122,6 +177,7 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
     def solve_stationary_batch(self, mus, rtol=1e-10, max_iter=50000, return_info=False):
         """The elliptic ``solve_batch`` of the underlying discretization: one tensor [S, n, len(mus)] of stationary solutions.
         NotImplementedError if a source coefficient depends on time, as ``solve_stationary``."""
+        self._no_stationary()
         mus = list(mus)
         if self._src is not None:
             from pylrbms_amd.sources3d import evaluate_stationary
@@ -141,22 +197,23 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
             return (U, (its, rel)) if return_info else U
         return BlockDiscretization3D.solve_batch(self, mus, rtol=rtol, max_iter=max_iter, return_info=return_info)
 
-    def _elliptic_terms(self, U, mu, rows=None):
+    def _elliptic_terms(self, U, mu, rows=None, thetas=None):
         """Local nc / r / df [3, S, L] of every column of U [S, n, L]: chunks of <= 64 // Q columns become a basis of the pass
         (it takes Q N <= 64) and the batched estimate with identity coefficients evaluates each column's forms.  With an affine
         source the estimate runs without its f terms and ``rows`` [L, K] (the source coefficients of every column; None: no f terms,
-        the caller reads the nc row only) adds them through ``lrbms3_project_sources`` / ``lrbms3_reduced_source_terms``."""
+        the caller reads the nc row only) adds them through ``lrbms3_project_sources`` / ``lrbms3_reduced_source_terms``.
+        ``thetas`` [L, Q]: a diffusion coefficient row per column (None: ``theta(mu)`` for every column)."""
         import torch
         from pylrbms_amd import sources3d
         eng, src = self.engine, self._src
-        theta = self.theta(mu)
+        theta = self.theta(mu) if thetas is None else None
         step = max(1, 64 // self.Q)
         out = []
         for c0 in range(0, U.shape[2], step):
             V = U[:, :, c0:c0 + step].contiguous()
             L = V.shape[2]
             u = torch.eye(L, dtype=V.dtype, device=V.device).expand(eng.S_ext, L, L).contiguous()
-            th = np.tile(theta, (L, 1))
+            th = np.tile(theta, (L, 1)) if thetas is None else np.ascontiguousarray(thetas[c0:c0 + L], dtype=np.float64)
             if src is None:
                 buf = eng.project_and_estimate(V)
                 out.append(eng.ctx.reduced_estimate_batch(self.Q, th, u, buf, eng.ops, eng.hdiam))
@@ -173,10 +230,26 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
 
     def estimate(self, U, mu, decompose=False):
         """est, (local_eta_nc [S, nt+1], local_eta_r, local_eta_df, time_residual [nt], time_deriv_nc [S, nt]) of a trajectory
-        U [S, n, nt + 1] (``decompose`` is accepted for the API shape: the parts are always returned)."""
+        U [S, n, nt + 1] (``decompose`` is accepted for the API shape: the parts are always returned).  With diffusion
+        coefficients of the time this is the verification path of the ``_tv`` estimate: the same kernels per step, the elliptic
+        rows of U_k at row k of ``diffusion_coefficients``, A(row k + 1) (U_{k+1} - U_k) in the time residual, alpha and gamma per
+        row."""
         eng = self.engine
         U = (U if isinstance(U, eng.ctx.torch.Tensor) else eng.ctx.from_numpy(np.asarray(U))).contiguous()
         dU = (U[:, :, 1:] - U[:, :, :-1]).contiguous()
+        if self._tv:
+            import torch
+            from pylrbms_amd.sources3d import table_times
+            nt = self.time_stepper.nt
+            if U.shape[2] != nt + 1:
+                raise ValueError('with diffusion coefficients of the time the estimate takes the whole trajectory [S, n, nt + 1]')
+            th = self.diffusion_coefficients(mu)
+            eta_loc = self._elliptic_terms(U, mu, rows=self.source_coefficients(mu) if self._src is not None else None, thetas=th)
+            Y = torch.cat([eng.ctx.fom_apply(self.Q, th[k + 1], eng.ops['A_diag'], eng.ops['A_cpl'], dU[:, :, k:k + 1].contiguous())
+                           for k in range(nt)], dim=2).contiguous()
+            tr2 = eng.ctx.mass_inverse_norm2(Y).sum(dim=0).cpu().numpy()
+            tdnc2 = self._elliptic_terms(dU, mu, thetas=th[1:])[0]          # (the nc form reads no theta)
+            return _parabolic_estimate(self, mu, self.dt, eta_loc, tr2, tdnc2, times=table_times(self.dt, nt).tolist())
         if self._src is not None and U.shape[2] != self.time_stepper.nt + 1:
             raise ValueError('with a time-dependent source the estimate takes the whole trajectory [S, n, nt + 1]')
         eta_loc = self._elliptic_terms(U, mu, rows=self.source_coefficients(mu) if self._src is not None else None)
@@ -198,10 +271,35 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
     def dt(self):
         return self.T / self.time_stepper.nt
 
-    def solve(self, mu, rtol=1e-12, max_iter=20000, return_info=False):
-        """Reduced implicit Euler from zero: u [nt + 1, S, N] (one native call)."""
+    def _tv_limits(self, what, estimate=False):
+        """The ``_tv`` exports are batched kernels: a reduced model outside their limits is refused, never handed to a single export
+        that would silently use one coefficient row."""
+        if self.N > 32:
+            raise NotImplementedError('{} with diffusion coefficients of the time runs the batched kernels: N = {} > 32 is outside '
+                                      'their limit'.format(what, self.N))
+        if estimate and self.d.Q * self.N > 64:
+            raise NotImplementedError('{} with diffusion coefficients of the time runs the batched estimate: Q N = {} > 64 is outside '
+                                      'its limit'.format(what, self.d.Q * self.N))
+
+    def _solve_batch_tv(self, chunk, rtol, max_iter):
         d = self.d
+        theta_t = np.stack([d.diffusion_coefficients(mu) for mu in chunk])          # [nmu, nt + 1, Q]
         if self.rhs_red_K is None:
+            return d.engine.ctx.reduced_implicit_euler_batch_tv(d.Q, theta_t, self.dt, self.time_stepper.nt, self.out['B_sys'], self.M_red,
+                                                                self.out['rhs_red'], rtol=rtol, max_iter=max_iter)
+        phi = np.stack([np.asarray(d.source_coefficients(mu), dtype=np.float64) for mu in chunk])
+        return d.engine.ctx.reduced_implicit_euler_batch_tv(d.Q, theta_t, self.dt, self.time_stepper.nt, self.out['B_sys'], self.M_red,
+                                                            self.rhs_red_K, phi=phi, rtol=rtol, max_iter=max_iter)
+
+    def solve(self, mu, rtol=1e-12, max_iter=20000, return_info=False):
+        """Reduced implicit Euler from zero: u [nt + 1, S, N] (one native call; with diffusion coefficients of the time one column of
+        ``lrbms3_reduced_implicit_euler_batch_tv``)."""
+        d = self.d
+        if d._tv:
+            self._tv_limits('rd.solve')
+            U, info = self._solve_batch_tv([mu], rtol, max_iter)
+            u = U[:, :, :, 0].contiguous()
+        elif self.rhs_red_K is None:
             u, info = d.engine.ctx.reduced_implicit_euler(d.Q, d.theta(mu), self.dt, self.time_stepper.nt, self.out['B_sys'], self.M_red,
                                                           self.out['rhs_red'], rtol=rtol, max_iter=max_iter)
         else:
@@ -218,7 +316,13 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
         import torch
         d, nt, out = self.d, self.time_stepper.nt, []
         info = (0, 0.0)
-        if self.N > 32:                       # the batched kernels take N <= 32
+        if d._tv:
+            self._tv_limits('rd.solve_batch')
+            for b0 in range(0, len(mus), 64):
+                U, inf = self._solve_batch_tv(mus[b0:b0 + 64], rtol, max_iter)
+                out.append(U.permute(3, 0, 1, 2))
+                info = (max(info[0], inf[0]), max(info[1], inf[1]))
+        elif self.N > 32:                     # the batched kernels take N <= 32
             for mu in mus:
                 u, inf = self.solve(mu, rtol=rtol, max_iter=max_iter, return_info=True)
                 out.append(u[None])
@@ -244,8 +348,10 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
     def estimate(self, u, mu, decompose=False):
         """The five parts of ``InstationaryDiscretization3D.estimate`` for reduced coefficients u [nt + 1, S, N]: the elliptic terms
         from the batched reduced estimate (one parameter column per time step), the nc row of the same call on the differences, the
-        time residual with M_red^-1."""
+        time residual with M_red^-1.  With diffusion coefficients of the time: one column of the ``_tv`` export."""
         d = self.d
+        if d._tv:
+            return self.estimate_batch(u[None], [mu], decompose=decompose, native=True)[0]
         eng, Q, theta = d.engine, d.Q, d.theta(mu)
         u = u.contiguous()
         du = (u[1:] - u[:-1]).contiguous()
@@ -273,11 +379,21 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
         permuted into the panel [nt + 1, S, N, nmu] once, the source coefficients come from ``d.source_coefficients``, one
         device-to-host copy per output, NumPy parts as ``estimate`` returns them.  It agrees with the loop to round-off, not in
         the bits: the time residual runs on the matrix-core panel matvec and the norms are summed on the device.  With N > 32
-        or Q N > 64 (the limits of the batched kernels) ``native=True`` runs the loop, as ``solve_batch`` does for N > 32."""
+        or Q N > 64 (the limits of the batched kernels) ``native=True`` runs the loop, as ``solve_batch`` does for N > 32.
+
+        With diffusion coefficients of the time both values of ``native`` run ``lrbms3_reduced_parabolic_estimate_batch_tv`` on whole
+        trajectories; outside the limits of the batched kernels that is a NotImplementedError."""
         assert len(U) == len(mus), 'estimate_batch: one trajectory per parameter'
         d = self.d
         mus = list(mus)
-        if not native or self.N > 32 or d.Q * self.N > 64 or not mus:
+        tv = d._tv
+        if tv:
+            self._tv_limits('rd.estimate', estimate=True)
+            if not mus:
+                return []
+            if U.shape[1] != self.time_stepper.nt + 1:
+                raise ValueError('with diffusion coefficients of the time the estimate takes the whole trajectory [nt + 1, S, N]')
+        elif not native or self.N > 32 or d.Q * self.N > 64 or not mus:
             return [self.estimate(U[m], mu, decompose=decompose) for m, mu in enumerate(mus)]
         eng, nt = d.engine, self.time_stepper.nt
         src = self.rhs_red_K is not None
@@ -291,18 +407,23 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
         res = []
         for b0 in range(0, len(mus), 64):
             chunk = mus[b0:b0 + 64]
-            th = np.stack([d.theta(mu) for mu in chunk])
-            coef = np.empty((len(chunk), 2))
-            for m, mu in enumerate(chunk):
-                a_bar, a_hat, g_bar = d.alpha(mu, d.mu_bar), d.alpha(mu, d.mu_hat), d.gamma(mu, d.mu_bar)
-                coef[m] = np.sqrt(g_bar / a_bar), 1.0 / np.sqrt(a_hat * a_bar)
+            if tv:                                 # a row per step: theta_t [nmu, nt + 1, Q], coef [nmu, nt + 1, 2]
+                th = np.stack([d.diffusion_coefficients(mu) for mu in chunk])
+                coef = np.stack([d._estimator_coefficients(mu) for mu in chunk])
+                native_call = eng.ctx.reduced_parabolic_estimate_batch_tv
+            else:
+                th = np.stack([d.theta(mu) for mu in chunk])
+                coef = np.empty((len(chunk), 2))
+                for m, mu in enumerate(chunk):
+                    a_bar, a_hat, g_bar = d.alpha(mu, d.mu_bar), d.alpha(mu, d.mu_hat), d.gamma(mu, d.mu_bar)
+                    coef[m] = np.sqrt(g_bar / a_bar), 1.0 / np.sqrt(a_hat * a_bar)
+                native_call = eng.ctx.reduced_parabolic_estimate_batch
             panel = U[b0:b0 + 64].permute(1, 2, 3, 0).contiguous()
             kw = {}
             if src:
                 kw = dict(phi=np.stack([np.asarray(d.source_coefficients(mu), dtype=np.float64) for mu in chunk]), F2=d._src['F2'],
                           r_fd_K=self.r_fd_K, bdiv_K=d._src['bdiv_K'])
-            r = eng.ctx.reduced_parabolic_estimate_batch(d.Q, th, coef, self.dt, nt, panel, self.out['B_sys'], self.M_red, out, ops,
-                                                         eng.hdiam, **kw)
+            r = native_call(d.Q, th, coef, self.dt, nt, panel, self.out['B_sys'], self.M_red, out, ops, eng.hdiam, **kw)
             h = {k: v.cpu().numpy() for k, v in r.items()}
             for m in range(len(chunk)):
                 nc, rr, df = (np.ascontiguousarray(h['eta_loc'][i, :, :, m].T) for i in range(3))      # [S, nt + 1]

@@ -12,7 +12,10 @@ import numpy as np
 from pylrbms_amd.grid3d import make_grid3d
 
 
-def init_grid_and_problem(config, mu_bar=1.0, mu_hat=1.0, rank=0, world_size=1):
+def init_grid_and_problem(config, mu_bar=1.0, mu_hat=1.0, rank=0, world_size=1, switch_off_after=None):
+    """``switch_off_after=t*``: the channels carry ``mu`` for ``t <= t*`` and 0.1, the lower end of the parameter range, afterwards --
+    they close during the run (a diffusion coefficient c(mu, t) of the parabolic 3D path).  mu_bar / mu_hat and with
+    them lambda_bar / lambda_hat sit at t = 0 and do not change.  The default None is the time-independent problem."""
     P = tuple(config['num_subdomains'])
     kc = config.get('cubes_per_subdomain', 4)
     sigma = config.get('sigma', 0.5)
@@ -32,8 +35,12 @@ def init_grid_and_problem(config, mu_bar=1.0, mu_hat=1.0, rank=0, world_size=1):
     def f(x):
         return 0.75 * np.pi ** 2 * np.cos(0.5 * np.pi * x[..., 0]) * np.cos(0.5 * np.pi * x[..., 1]) * np.cos(0.5 * np.pi * x[..., 2])
 
+    channel = lambda mu: float(mu)                                                # noqa: E731
+    if switch_off_after is not None:
+        t_star = float(switch_off_after)
+        channel = lambda mu, t: float(mu) if t <= t_star else 0.1                 # noqa: E731
     return {'grid': grid,
-            'lambda': {'functions': [lambda_0, lambda_1], 'coefficients': [lambda mu: 1.0, lambda mu: float(mu)]},
+            'lambda': {'functions': [lambda_0, lambda_1], 'coefficients': [lambda mu: 1.0, channel]},
             'lambda_bar': lambda x: lambda_0(x) + mu_bar * lambda_1(x),
             'lambda_hat': lambda x: lambda_0(x) + mu_hat * lambda_1(x),
             'kappa': np.eye(3), 'f': f, 'data_degree': config.get('data_degree', 2),

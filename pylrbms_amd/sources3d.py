@@ -16,26 +16,28 @@ import numbers
 import numpy as np
 
 
-def coefficient_arity(c):
+def coefficient_arity(c, what='source coefficient'):
     """0 for a plain number, 1 for a callable ``c(mu)``, 2 for a callable ``c(mu, t)`` -- from the signature, never by trying a
     call.  Anything else is a TypeError, a callable whose signature cannot be read included.
 
     The rule: only positional parameters WITHOUT a default count.  A defaulted parameter is a bound constant, not an argument the
     path supplies -- the problem files write ``lambda mu, q=q: mu ** q`` to bind a loop variable -- so ``c(mu, t=0.0)`` is a
-    coefficient of mu alone and never receives the time; a coefficient that reads t declares it without a default."""
+    coefficient of mu alone and never receives the time; a coefficient that reads t declares it without a default.
+
+    ``what`` names the coefficient in the messages: the diffusion coefficients of the parabolic path go by the same rule."""
     if isinstance(c, numbers.Real) and not isinstance(c, bool):
         return 0
     if not callable(c):
-        raise TypeError('a source coefficient of the 3D path is a number or a callable, not {!r}'.format(type(c).__name__))
+        raise TypeError('a {} of the 3D path is a number or a callable, not {!r}'.format(what, type(c).__name__))
     kinds = (inspect.Parameter.POSITIONAL_ONLY, inspect.Parameter.POSITIONAL_OR_KEYWORD)
     try:
         sig = inspect.signature(c)
     except ValueError as exc:                      # some builtins and C callables carry no signature
-        raise TypeError('the signature of the source coefficient {!r} cannot be read ({}): wrap it in a function of (mu) or '
-                        '(mu, t)'.format(c, exc))
+        raise TypeError('the signature of the {} {!r} cannot be read ({}): wrap it in a function of (mu) or '
+                        '(mu, t)'.format(what, c, exc))
     pos = [q for q in sig.parameters.values() if q.kind in kinds and q.default is inspect.Parameter.empty]
     if len(pos) not in (1, 2):
-        raise TypeError('a source coefficient takes (mu) or (mu, t); this one takes {} positional arguments'.format(len(pos)))
+        raise TypeError('a {} takes (mu) or (mu, t); this one takes {} positional arguments'.format(what, len(pos)))
     return len(pos)
 
 
@@ -69,12 +71,25 @@ def evaluate_stationary(src, mu):
     return np.array([float(c) if a == 0 else float(c(mu)) for c, a in zip(src['coefficients'], src['arity'])], dtype=np.float64)
 
 
+def table_times(dt, nt):
+    """[nt + 1] fp64: t_k = k dt, the time of row k of every per-step table (the source's phi and the diffusion's theta_t): the one
+    place the times come from, so the two cannot disagree on t_k."""
+    return np.array([k * float(dt) for k in range(int(nt) + 1)], dtype=np.float64)
+
+
+def diffusion_arities(coeffs):
+    """The arities of the diffusion coefficients ``p['lambda']['coefficients']``: plain callables c(mu) or c(mu, t)."""
+    ar = [coefficient_arity(c, 'diffusion coefficient') for c in coeffs]
+    if 0 in ar:
+        raise TypeError('a diffusion coefficient of the 3D path is a callable c(mu) or c(mu, t), not a number')
+    return ar
+
+
 def evaluate_table(src, mu, dt, nt):
     """[nt + 1][K] fp64: row k holds the coefficients at t_k = k dt.  Step k -> k + 1 of implicit Euler uses row k + 1, the elliptic
     part of U_k in the estimate uses row k."""
     out = np.empty((int(nt) + 1, len(src['coefficients'])), dtype=np.float64)
-    for k in range(int(nt) + 1):
-        t = k * float(dt)
+    for k, t in enumerate(table_times(dt, nt).tolist()):
         out[k] = [float(c) if a == 0 else float(c(mu)) if a == 1 else float(c(mu, t)) for c, a in zip(src['coefficients'], src['arity'])]
     return out
 
