@@ -78,13 +78,15 @@ const char* lrbms3_last_error(lrbms3_ctx* ctx);
  *   LRBMS3_OPT_WAVES           0 (default): 4 / 8 waves per workgroup of the projection kernels; else that many
  *   LRBMS3_OPT_ESTIMATE_VALU   1: VALU form of the batched estimate (cross-check of the matrix-core form)
  *   LRBMS3_OPT_SOLVE_VALU      1: VALU form of the batched solver's panel matvec (cross-check)
- *   LRBMS3_OPT_FOM_COARSE      0: full-order solves without the coarse level whatever lrbms3_fom_coarse_space set */
+ *   LRBMS3_OPT_FOM_COARSE      0: full-order solves without the coarse level whatever lrbms3_fom_coarse_space set
+ *   LRBMS3_OPT_POD_ROTATE_VALU 1: the rotation of lrbms3_local_pod_stream_push through k_pod_xt and a copy back (cross-check) */
 #define LRBMS3_OPT_KSPLIT 1
 #define LRBMS3_OPT_SERIAL 2
 #define LRBMS3_OPT_WAVES 3
 #define LRBMS3_OPT_ESTIMATE_VALU 4
 #define LRBMS3_OPT_SOLVE_VALU 5
 #define LRBMS3_OPT_FOM_COARSE 6
+#define LRBMS3_OPT_POD_ROTATE_VALU 7
 int lrbms3_ctx_set_option(lrbms3_ctx* ctx, int32_t option, int32_t value);
 
 /* Template, tables, neighbour table nbr [S][7] (index into the S_ext ordering per slot, -1 = none, nbr[s][3] == s) and
@@ -127,6 +129,19 @@ int64_t lrbms3_local_pod_work_size(lrbms3_ctx* ctx, int32_t L, int32_t Nw);
 int lrbms3_local_pod(lrbms3_ctx* ctx, int32_t L, int32_t Nw, int32_t modes, double rtol, double atol, const double* P_diag,
                      const double* U, double* V, int32_t* nloc, double* sv, int32_t* added, int32_t* info, double* work,
                      void* stream);
+
+/* Streamed local POD over a training set of any size (incremental HAPOD): lrbms_local_pod_stream_* of include/lrbms_hip.h --
+ * algorithm, state and work layouts and their size formulas (state: S (2 n Lx + 3) doubles, Lx = keep + cmax; work: the formula
+ * stated there, with this path's S and n), limits, refusals and kernels are the same -- with the local energy product P_diag
+ * [S][n_T][5][100].  LRBMS3_OPT_POD_ROTATE_VALU 1 selects the k_pod_xt route of the rotation (cross-check). */
+int64_t lrbms3_local_pod_stream_state_size(lrbms3_ctx* ctx, int32_t keep, int32_t cmax);
+int64_t lrbms3_local_pod_stream_work_size(lrbms3_ctx* ctx, int32_t keep, int32_t cmax, int32_t Nw);
+int lrbms3_local_pod_stream_begin(lrbms3_ctx* ctx, int32_t keep, int32_t cmax, double* state, void* stream);
+int lrbms3_local_pod_stream_push(lrbms3_ctx* ctx, int32_t keep, int32_t cmax, int32_t C, int32_t Nw, const double* P_diag,
+                                 const double* U, const double* V, const int32_t* nloc, double* state, double* work, void* stream);
+int lrbms3_local_pod_stream_finish(lrbms3_ctx* ctx, int32_t keep, int32_t cmax, int32_t Nw, int32_t modes, double rtol, double atol,
+                                   const double* P_diag, double* V, int32_t* nloc, double* state, double* sv, int32_t* added,
+                                   int32_t* info, double* lost, double* work, void* stream);
 
 /* Cf [Q][S_ext][n_T][4][10]: contribution of the element's own DoFs to the RT0 DoF of its face f (unsigned; the kernels
  * apply the orientation).  2D: lrbms_assemble_flux. */

@@ -311,7 +311,9 @@ void* lrbms_ctx_aux_stream(lrbms_ctx* ctx, int32_t i);
  *                              assembly calls
  *   LRBMS_OPT_THIN_MERGE       1 (default): in the factored layout the three thin side kernels share one launch (k_thin3); 0: they
  *                              are launched one after the other (k_thin_ncf, k_thin_rt, k_coupling) unless the pass forks
- *                              (LRBMS_OPT_STREAMS) -- the same bits; the cross-check of the merged kernel against its parts */
+ *                              (LRBMS_OPT_STREAMS) -- the same bits; the cross-check of the merged kernel against its parts
+ *   LRBMS_OPT_POD_ROTATE_VALU  1: the rotation of lrbms_local_pod_stream_push through k_pod_xt and a copy back (cross-check of
+ *                              k_pod_stream_rotate) */
 #define LRBMS_OPT_STREAMS 3
 #define LRBMS_OPT_F1_KSPLIT 4
 #define LRBMS_OPT_F1_FORM 5
@@ -322,6 +324,7 @@ void* lrbms_ctx_aux_stream(lrbms_ctx* ctx, int32_t i);
 #define LRBMS_OPT_F2_FORM 11
 #define LRBMS_OPT_SIDE_TABLES 12
 #define LRBMS_OPT_THIN_MERGE 13
+#define LRBMS_OPT_POD_ROTATE_VALU 14
 int lrbms_ctx_set_option(lrbms_ctx* ctx, int32_t option, int32_t value);
 
 /* LRBMS_OPT_OSWALD_VERTEX_PATCH on sharded grids: nbr_diag [S][4] (host) = index into the S_ext slabs of the diagonal neighbour
@@ -748,6 +751,45 @@ int64_t lrbms_local_pod_work_size(lrbms_ctx* ctx, int32_t L, int32_t Nw);
 int lrbms_local_pod(lrbms_ctx* ctx, int32_t L, int32_t Nw, int32_t modes, double rtol, double atol, const double* P_diag,
                     const double* U, double* V, int32_t* nloc, double* sv, int32_t* added, int32_t* info, double* work,
                     void* stream);
+/* Streamed local POD over a training set of any size (incremental HAPOD, Himpe / Leibner / Rave 2018): chunks
+ * of at most cmax snapshots are pushed one after the other, per subdomain a panel of at most keep <= 64 scaled modes is carried
+ * from push to push, and finish appends at most `modes` of them to V as lrbms_local_pod does.  keep + cmax <= 128.
+ *   state per subdomain: X = [B | R] and PX = [PB | PR], both [n][Lx], Lx = keep + cmax (B: kb <= keep columns, zero behind), lost,
+ *   norm0sq, the OR of the eigen-solver flags.  Layout of `state`: X [S][n][Lx], PX [S][n][Lx], norm0sq [S], lost [S], then
+ *   int32 kb [S], flags [S].
+ *   begin:  state = 0.
+ *   push(U [S][n][C], 1 <= C <= cmax):  norm0sq = max(norm0sq, max_j u_j^T P u_j);  R = U deflated twice against V in P, PR = P R;
+ *           columns keep .. keep + C - 1 of X, PX = R, PR, zero up to Lx;  G = sym(X^T PX) = Z diag(lam) Z^T, lam descending;
+ *           kb = min(#{lam_j > (1e-7)^2 lam_1}, keep),  lost += sum_{j >= kb} max(lam_j, 0);
+ *           X[:, :keep] = X Z[:, :kb], PX[:, :keep] = PX Z[:, :kb] (zero columns behind kb): the columns carry their singular
+ *           values, nothing is divided and P is never applied to B.
+ *   finish: G = sym(B^T PB) = Z diag(lam) Z^T, sv = sqrt(max(lam, 0)) [S][keep] descending;
+ *           k_s = min(#{sigma_j > max(atol, rtol sqrt(norm0sq))}, modes, Nw - nloc[s]);  lost[s] = the pushes' + sum_{j >= k_s} max(lam_j, 0);
+ *           W = B Z_k Sigma_k^-1, then as lrbms_local_pod: deflated against V, Loewdin, written into columns nloc[s] .. of V,
+ *           nloc += k_s.  finish does not change `state`.
+ *   With R_all the pushed snapshots deflated against V and Pi the P-projection onto the new columns,
+ *   sum_j |(I - Pi) r_j|_P^2 <= lost[s] (up to rounding); while no push has more than keep eigenvalues above its floor the result
+ *   is the POD of all pushed columns, whatever the chunking.  V and nloc must not change between begin and finish.
+ *     info   [S] int32  the bits of lrbms_local_pod, bit 0 OR-ed over all pushes and finish
+ *     state  lrbms_local_pod_stream_state_size(keep, cmax) = S (2 n Lx + 3) doubles (device)
+ *     work   lrbms_local_pod_stream_work_size(keep, cmax, Nw) doubles (device) =
+ *            S (2 n M1 + 2 n keep + Nw M1 + 2 Lx^2 + Lxp^2 + Lx + Lx keep + 4 + (p > 1 ? p max(Lx, Nw) Lx : 0)),
+ *            M1 = max(cmax, keep), Lxp = Lx rounded up to even, p as for lrbms_local_pod.  Its content on entry is irrelevant;
+ *            behind a push it holds T = Z[:, :keep] [S][Lx][keep] at offset S (2 n M1 + 2 n keep + Nw M1 + 2 Lx^2 + Lxp^2 + Lx).
+ *   Everything runs on `stream`: no host synchronisation, no allocation, no atomics, no environment variable, fixed summation
+ *   orders (a repeated begin .. finish gives the same bits).  Only the k_s new columns of the S local subdomains of V are written.
+ *   The rotation X Z runs on the fp64 MFMA in place (k_pod_stream_rotate); LRBMS_OPT_POD_ROTATE_VALU 1 selects k_pod_xt into a
+ *   second buffer and a copy back (cross-check).
+ *   Refused with LRBMS_E_INVALID before any launch: keep outside [1, 64], cmax < 1, keep + cmax > 128, C outside [1, cmax],
+ *   Nw outside [1, 64], modes < 1, rtol < 1e-7, atol < 0, a null pointer.  The size functions return -1 for a refused shape. */
+int64_t lrbms_local_pod_stream_state_size(lrbms_ctx* ctx, int32_t keep, int32_t cmax);
+int64_t lrbms_local_pod_stream_work_size(lrbms_ctx* ctx, int32_t keep, int32_t cmax, int32_t Nw);
+int lrbms_local_pod_stream_begin(lrbms_ctx* ctx, int32_t keep, int32_t cmax, double* state, void* stream);
+int lrbms_local_pod_stream_push(lrbms_ctx* ctx, int32_t keep, int32_t cmax, int32_t C, int32_t Nw, const double* P_diag, const double* U,
+                                const double* V, const int32_t* nloc, double* state, double* work, void* stream);
+int lrbms_local_pod_stream_finish(lrbms_ctx* ctx, int32_t keep, int32_t cmax, int32_t Nw, int32_t modes, double rtol, double atol,
+                                  const double* P_diag, double* V, int32_t* nloc, double* state, double* sv, int32_t* added,
+                                  int32_t* info, double* lost, double* work, void* stream);
 /* The two kernels of it that stand alone (cross-checks; any context, no mesh needed):
  *   G[b] [L][L] = sym(X[b]^T Y[b]), X, Y [batch][K][L], L <= 128: the upper-triangle 16 x 16 tiles on the fp64 MFMA, mirrored
  *   (G[i][j] = G[j][i] = x_i^T y_j for i <= j, exactly symmetric). */

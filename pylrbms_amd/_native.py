@@ -132,6 +132,11 @@ SIGNATURES = {
     # local POD basis extension
     'lrbms_local_pod_work_size': (c_i64, [c_vp, c_i32, c_i32]),
     'lrbms_local_pod': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_dbl, c_dbl] + [c_vp] * 9),
+    'lrbms_local_pod_stream_state_size': (c_i64, [c_vp, c_i32, c_i32]),
+    'lrbms_local_pod_stream_work_size': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
+    'lrbms_local_pod_stream_begin': (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    'lrbms_local_pod_stream_push': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_vp] * 7),
+    'lrbms_local_pod_stream_finish': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_dbl, c_dbl] + [c_vp] * 10),
     'lrbms_pod_gram': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'lrbms_pod_eigh_work_size': (c_i64, [c_vp, c_i32, c_i32]),
     'lrbms_pod_eigh': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 7),
@@ -270,6 +275,16 @@ class ContextBase:
         """Doubles of ``work`` for ``local_pod`` (the formula of the C header), -1 for a shape the call refuses."""
         return int(self._fn('local_pod_work_size')(self.handle, int(L), int(Nw)))
 
+    def _pod_product_ptr(self, P_diag):
+        """The checked pointer of the local product in the layout of the subclass."""
+        raise NotImplementedError
+
+    def local_pod_stream(self, P_diag, V, nloc, keep=64, cmax=64):
+        """A streamed local POD (``lrbms_local_pod_stream_*`` / ``lrbms3_local_pod_stream_*``, incremental HAPOD) against the
+        basis slab ``V`` [S or S_ext, n, Nw] with ``nloc`` (int32 device tensor [S]): a ``LocalPodStream``, begun.  ``V`` and ``nloc``
+        must not change until its ``finish``."""
+        return LocalPodStream(self, P_diag, V, nloc, keep, cmax)
+
     def set_option(self, name, value):
         """Set one entry of ``OPTIONS``: a convention the reference tree leaves open or the launch policy of the library
         (LRBMS_OPT_* / LRBMS3_OPT_* of the C headers); the library reads no environment variable."""
@@ -293,6 +308,69 @@ class ContextBase:
         return [(nm[i], ms[i]) for i in range(count.value)]
 
 
+class LocalPodStream:
+    """One ``begin .. push .. finish`` of the streamed local POD on a context.  ``state`` and ``work`` are allocated once, here;
+    every call runs on the current stream and copies nothing to the host."""
+
+    def __init__(self, ctx, P_diag, V, nloc, keep=64, cmax=64):
+        torch = ctx.torch
+        self.ctx, self.keep, self.cmax = ctx, int(keep), int(cmax)
+        S, n = ctx.S, ctx.n
+        if V.dim() != 3 or V.shape[0] < S:
+            raise NativeError('V: expected [at least {} subdomain rows, n, Nw], got {}'.format(S, tuple(V.shape)))
+        if nloc.dtype != torch.int32 or nloc.device != ctx.device or tuple(nloc.shape) != (S,) or not nloc.is_contiguous():
+            raise NativeError('nloc: expected a contiguous int32 tensor [{}] on {}'.format(S, ctx.device))
+        self.Nw = int(V.shape[2])
+        self._P, self._P_ptr = P_diag, ctx._pod_product_ptr(P_diag)
+        self._V, self._v_ptr = V, ctx._ptr(V, (V.shape[0], n, self.Nw), 'V')
+        self._nloc = nloc
+        self.columns = self.nodes = 0
+        ssize = int(ctx._fn('local_pod_stream_state_size')(ctx.handle, self.keep, self.cmax))
+        wsize = int(ctx._fn('local_pod_stream_work_size')(ctx.handle, self.keep, self.cmax, self.Nw))
+        self.state = ctx.empty(ssize) if ssize > 0 else None        # (a refused shape: begin / push say why)
+        self.work = ctx.empty(wsize) if wsize > 0 else None
+        self.begin()
+
+    def _p(self, t):
+        return c_vp(t.data_ptr()) if t is not None else None
+
+    def begin(self):
+        """Reset the state: no carried modes, nothing lost."""
+        ctx = self.ctx
+        rc = ctx._fn('local_pod_stream_begin')(ctx.handle, self.keep, self.cmax, self._p(self.state), ctx._stream())
+        ctx._check(rc, ctx.PREFIX + 'local_pod_stream_begin')
+        self.columns = self.nodes = 0
+
+    def push(self, U):
+        """Push the snapshots ``U`` [S, n, C]; more than ``cmax`` columns go piece by piece (one ``.contiguous()`` per piece)."""
+        ctx = self.ctx
+        if U.dim() != 3 or U.shape[2] < 1:
+            raise NativeError('U: expected [S, n, C >= 1], got {}'.format(tuple(U.shape)))
+        for c0 in range(0, int(U.shape[2]), max(self.cmax, 1)):
+            Uc = U[:, :, c0:c0 + max(self.cmax, 1)].contiguous()
+            C = int(Uc.shape[2])
+            rc = ctx._fn('local_pod_stream_push')(ctx.handle, self.keep, self.cmax, C, self.Nw, self._P_ptr,
+                                                  ctx._ptr(Uc, (ctx.S, ctx.n, C), 'U'), self._v_ptr, self._p(self._nloc),
+                                                  self._p(self.state), self._p(self.work), ctx._stream())
+            ctx._check(rc, ctx.PREFIX + 'local_pod_stream_push')
+            self.columns += C
+            self.nodes += 1
+
+    def finish(self, modes, rtol=1e-6, atol=0.0):
+        """At most ``modes`` modes of everything pushed into the free columns of ``V`` (``nloc`` += added).  Returns the device
+        tensors ``sv`` [S, keep], ``ai`` int32 [2, S] (row 0 ``added``, row 1 ``info``) and ``lost`` [S]."""
+        ctx = self.ctx
+        torch = ctx.torch
+        sv = ctx.empty(ctx.S, max(self.keep, 1))
+        ai = torch.empty(2, ctx.S, dtype=torch.int32, device=ctx.device)
+        lost = ctx.empty(ctx.S)
+        rc = ctx._fn('local_pod_stream_finish')(ctx.handle, self.keep, self.cmax, self.Nw, int(modes), float(rtol), float(atol),
+                                                self._P_ptr, self._v_ptr, self._p(self._nloc), self._p(self.state), self._p(sv),
+                                                self._p(ai[0]), self._p(ai[1]), self._p(lost), self._p(self.work), ctx._stream())
+        ctx._check(rc, ctx.PREFIX + 'local_pod_stream_finish')
+        return sv, ai, lost
+
+
 class NativeContext(ContextBase):
     """One lrbms_ctx per (process, device).  Tensor arguments must be contiguous float64 CUDA tensors on that device;
     shapes are checked here, on the host, before any kernel may dereference them."""
@@ -305,7 +383,8 @@ class NativeContext(ContextBase):
                'streams': 3, 'f1_ksplit': 4, 'f1_form': 5, 'coarse': 6, 'solve_valu': 7, 'estimate_valu': 8,
                'f2_form': 11,      # f2_form: 0 Gram form (column-pair producers), 1 product form k_f2, 2 Gram form with one-column producers
                'side_tables': 12,  # 1: basis-independent tables of the pass kept between passes; 0: rebuilt in every pass (arrays modified in place)
-               'thin_merge': 13}   # 1: k_thin3; 0: k_thin_ncf, k_thin_rt, k_coupling one after the other in the factored layout (cross-check)
+               'thin_merge': 13,   # 1: k_thin3; 0: k_thin_ncf, k_thin_rt, k_coupling one after the other in the factored layout (cross-check)
+               'pod_rotate_valu': 14}   # 1: the rotation of local_pod_stream.push through k_pod_xt (cross-check of k_pod_stream_rotate)
     S = S_ext = None
     _keep = None
 
@@ -1261,6 +1340,9 @@ class NativeContext(ContextBase):
         """``lrbms_local_pod``: at most ``modes`` POD modes of the snapshots ``U`` [S, n, L] per subdomain, in the block-ELL
         product ``P_diag``, into the free columns of ``V``; see ``ContextBase._local_pod`` for the arguments and the result."""
         return self._local_pod(self._ptr(P_diag, (self.S, self.n_T, 4, 9), 'P_diag'), U, V, nloc, modes, rtol, atol, work)
+
+    def _pod_product_ptr(self, P_diag):
+        return self._ptr(P_diag, (self.S, self.n_T, 4, 9), 'P_diag')
 
     def pod_gram(self, X, Y):
         """sym(X[b]^T Y[b]) for X, Y [B, K, L] (``lrbms_pod_gram``: upper-triangle MFMA tiles, mirrored)."""

@@ -109,6 +109,11 @@ SIGNATURES3 = {
     # local POD basis extension
     'lrbms3_local_pod_work_size': (c_i64, [c_vp, c_i32, c_i32]),
     'lrbms3_local_pod': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_dbl, c_dbl] + [c_vp] * 9),
+    'lrbms3_local_pod_stream_state_size': (c_i64, [c_vp, c_i32, c_i32]),
+    'lrbms3_local_pod_stream_work_size': (c_i64, [c_vp, c_i32, c_i32, c_i32]),
+    'lrbms3_local_pod_stream_begin': (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    'lrbms3_local_pod_stream_push': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_vp] * 7),
+    'lrbms3_local_pod_stream_finish': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_dbl, c_dbl] + [c_vp] * 10),
 }
 
 _bound = None
@@ -132,7 +137,7 @@ class Native3DContext(_native.ContextBase):
     PREFIX = 'lrbms3_'
     TIMING_CAP = 4096
     _load = staticmethod(load_library)
-    OPTIONS = {'ksplit': 1, 'serial': 2, 'waves': 3, 'estimate_valu': 4, 'solve_valu': 5, 'fom_coarse': 6}
+    OPTIONS = {'ksplit': 1, 'serial': 2, 'waves': 3, 'estimate_valu': 4, 'solve_valu': 5, 'fom_coarse': 6, 'pod_rotate_valu': 7}
 
     # ------------------------------------------------------------------ mesh
     def mesh_upload(self, template, spec, tables, nbr, phys, S, S_ext):
@@ -245,6 +250,9 @@ class Native3DContext(_native.ContextBase):
         """``lrbms3_local_pod``: at most ``modes`` POD modes of the snapshots ``U`` [S, n, L] per subdomain, in the local energy
         product ``P_diag``, into the free columns of ``V``; arguments and result as ``ContextBase._local_pod``."""
         return self._local_pod(self._ptr(P_diag, (self.S, self.n_T, 5, 100), 'P_diag'), U, V, nloc, modes, rtol, atol, work)
+
+    def _pod_product_ptr(self, P_diag):
+        return self._ptr(P_diag, (self.S, self.n_T, 5, 100), 'P_diag')
 
     # ------------------------------------------------------------------ pass
     OUT_NAMES = ('B_sys', 'rhs_red', 'G_nc', 'G_bb', 'G_rdd', 'G_ab', 'G_aa', 'r_fd', 'Rb', 'Yb', 'Dp', 'Xab', 'As', 'Cn')

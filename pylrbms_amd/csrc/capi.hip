@@ -273,6 +273,7 @@ int lrbms_ctx_set_option(lrbms_ctx* ctx, int32_t option, int32_t value) {
     case LRBMS_OPT_PREP_LDS: ctx->opt_prep_lds = value; break;
     case LRBMS_OPT_SIDE_TABLES: ctx->opt_side_tables = value; break;
     case LRBMS_OPT_THIN_MERGE: ctx->opt_thin_merge = value; break;
+    case LRBMS_OPT_POD_ROTATE_VALU: ctx->opt_pod_rotate_valu = value; break;
     default: return lrbms_fail(ctx, LRBMS_E_INVALID, "set_option: unknown option");
   }
   return LRBMS_OK;
@@ -1012,6 +1013,40 @@ int lrbms_local_pod(lrbms_ctx* ctx, int32_t L, int32_t Nw, int32_t modes, double
   Pod2D self{ctx, P_diag};
   return launch_local_pod(ctx, ctx->S, ctx->t.n, L, Nw, modes, rtol, atol, PodProduct{pod_product_2d, &self}, U, V, nloc, sv, added,
                           info, work, (hipStream_t)stream);
+}
+
+int64_t lrbms_local_pod_stream_state_size(lrbms_ctx* ctx, int32_t keep, int32_t cmax) {
+  if (!ctx || !ctx->has_mesh || keep < 1 || keep > POD_MAX_NW || cmax < 1 || keep + cmax > POD_MAX_L) return -1;
+  return pod_stream_state_size(ctx->S, ctx->t.n, keep, cmax);
+}
+
+int64_t lrbms_local_pod_stream_work_size(lrbms_ctx* ctx, int32_t keep, int32_t cmax, int32_t Nw) {
+  if (lrbms_local_pod_stream_state_size(ctx, keep, cmax) < 0 || Nw < 1 || Nw > POD_MAX_NW) return -1;
+  return pod_stream_work_size(ctx->S, ctx->t.n, keep, cmax, Nw);
+}
+
+int lrbms_local_pod_stream_begin(lrbms_ctx* ctx, int32_t keep, int32_t cmax, double* state, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  return launch_pod_stream_begin(ctx, ctx->S, ctx->t.n, keep, cmax, state, (hipStream_t)stream);
+}
+
+int lrbms_local_pod_stream_push(lrbms_ctx* ctx, int32_t keep, int32_t cmax, int32_t C, int32_t Nw, const double* P_diag, const double* U,
+                                const double* V, const int32_t* nloc, double* state, double* work, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (!P_diag) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_push: null pointer: P_diag");
+  Pod2D self{ctx, P_diag};
+  return launch_pod_stream_push(ctx, ctx->S, ctx->t.n, keep, cmax, C, Nw, ctx->opt_pod_rotate_valu, PodProduct{pod_product_2d, &self}, U,
+                                V, nloc, state, work, (hipStream_t)stream);
+}
+
+int lrbms_local_pod_stream_finish(lrbms_ctx* ctx, int32_t keep, int32_t cmax, int32_t Nw, int32_t modes, double rtol, double atol,
+                                  const double* P_diag, double* V, int32_t* nloc, double* state, double* sv, int32_t* added,
+                                  int32_t* info, double* lost, double* work, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (!P_diag) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_finish: null pointer: P_diag");
+  Pod2D self{ctx, P_diag};
+  return launch_pod_stream_finish(ctx, ctx->S, ctx->t.n, keep, cmax, Nw, modes, rtol, atol, PodProduct{pod_product_2d, &self}, V, nloc,
+                                  state, sv, added, info, lost, work, (hipStream_t)stream);
 }
 
 int lrbms_pod_gram(lrbms_ctx* ctx, int32_t batch, int32_t K, int32_t L, const double* X, const double* Y, double* G, void* stream) {

@@ -2527,6 +2527,7 @@ int lrbms3_ctx_set_option(lrbms3_ctx* ctx, int32_t option, int32_t value) {
     case LRBMS3_OPT_ESTIMATE_VALU: ctx->opt_estimate_valu = value; break;
     case LRBMS3_OPT_SOLVE_VALU: ctx->opt_solve_valu = value; break;
     case LRBMS3_OPT_FOM_COARSE: ctx->opt_fom_coarse = value; break;
+    case LRBMS3_OPT_POD_ROTATE_VALU: ctx->opt_pod_rotate_valu = value; break;
     default: return lrbms_fail(ctx, LRBMS_E_INVALID, "set_option: unknown option");
   }
   return LRBMS_OK;
@@ -2720,6 +2721,40 @@ int lrbms3_local_pod(lrbms3_ctx* ctx, int32_t L, int32_t Nw, int32_t modes, doub
   Pod3D self{ctx, P_diag};
   return launch_local_pod(ctx, ctx->t.S, ctx->t.n, L, Nw, modes, rtol, atol, PodProduct{pod_product_3d, &self}, U, V, nloc, sv, added,
                           info, work, (hipStream_t)stream);
+}
+
+int64_t lrbms3_local_pod_stream_state_size(lrbms3_ctx* ctx, int32_t keep, int32_t cmax) {
+  if (!ctx || !ctx->has_mesh || keep < 1 || keep > POD_MAX_NW || cmax < 1 || keep + cmax > POD_MAX_L) return -1;
+  return pod_stream_state_size(ctx->t.S, ctx->t.n, keep, cmax);
+}
+
+int64_t lrbms3_local_pod_stream_work_size(lrbms3_ctx* ctx, int32_t keep, int32_t cmax, int32_t Nw) {
+  if (lrbms3_local_pod_stream_state_size(ctx, keep, cmax) < 0 || Nw < 1 || Nw > POD_MAX_NW) return -1;
+  return pod_stream_work_size(ctx->t.S, ctx->t.n, keep, cmax, Nw);
+}
+
+int lrbms3_local_pod_stream_begin(lrbms3_ctx* ctx, int32_t keep, int32_t cmax, double* state, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  return launch_pod_stream_begin(ctx, ctx->t.S, ctx->t.n, keep, cmax, state, (hipStream_t)stream);
+}
+
+int lrbms3_local_pod_stream_push(lrbms3_ctx* ctx, int32_t keep, int32_t cmax, int32_t C, int32_t Nw, const double* P_diag,
+                                 const double* U, const double* V, const int32_t* nloc, double* state, double* work, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (!P_diag) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_push: null pointer: P_diag");
+  Pod3D self{ctx, P_diag};
+  return launch_pod_stream_push(ctx, ctx->t.S, ctx->t.n, keep, cmax, C, Nw, ctx->opt_pod_rotate_valu, PodProduct{pod_product_3d, &self},
+                                U, V, nloc, state, work, (hipStream_t)stream);
+}
+
+int lrbms3_local_pod_stream_finish(lrbms3_ctx* ctx, int32_t keep, int32_t cmax, int32_t Nw, int32_t modes, double rtol, double atol,
+                                   const double* P_diag, double* V, int32_t* nloc, double* state, double* sv, int32_t* added,
+                                   int32_t* info, double* lost, double* work, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx);
+  if (!P_diag) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_finish: null pointer: P_diag");
+  Pod3D self{ctx, P_diag};
+  return launch_pod_stream_finish(ctx, ctx->t.S, ctx->t.n, keep, cmax, Nw, modes, rtol, atol, PodProduct{pod_product_3d, &self}, V, nloc,
+                                  state, sv, added, info, lost, work, (hipStream_t)stream);
 }
 
 int lrbms3_assemble_flux(lrbms3_ctx* ctx, int32_t Q, const double* lam, double* Cf, void* stream) {

@@ -28,6 +28,7 @@ struct lrbms_ctx_base {
   struct KTimer { const char* name; hipEvent_t e0, e1; bool used; };
   std::vector<KTimer> ktimers;
   int ktime_n = 0;
+  int opt_pod_rotate_valu = 0;    // LRBMS_OPT_POD_ROTATE_VALU / LRBMS3_OPT_POD_ROTATE_VALU
   std::string err;
 };
 

@@ -462,7 +462,324 @@ int xt(lrbms_ctx_base* ctx, int S, int n, int Kin, int J, const double* X, int l
   return LRBMS_OK;
 }
 
+// Steps 7 - 9 of the local POD, shared by launch_local_pod and the stream's finish: W [S][n][K] (ks[s] columns in use) is deflated
+// once more against V, re-orthonormalised (Loewdin) and written into the columns nloc[s] .. nloc[s] + ks[s] - 1 of V; nloc += ks,
+// info = ia | ib << 2.  PR [S][n][K], C [S][Nw][K], G, Zs [S][K][K], Zw (pod_eigh_work_size(S, K)), lam [S][K] are scratch.
+int pod_tail(lrbms_ctx_base* ctx, int S, int n, int Nw, int K, PodProduct P, double* V, int32_t* nloc, double* Wb, double* PR, double* C,
+             double* G, double* Zs, double* Zw, double* lam, const int32_t* ks, const int32_t* ia, int32_t* ib, double* part,
+             int32_t* info, hipStream_t st) {
+  int rc;
+  // 7: once more against V
+  if ((rc = P.apply(P.self, K, Wb, PR, st)) != LRBMS_OK) return rc;
+  if ((rc = xty(ctx, false, S, n, Nw, K, V, PR, C, part, st)) != LRBMS_OK) return rc;
+  if ((rc = xt(ctx, S, n, Nw, K, V, Nw, C, K, Wb, K, nullptr, nullptr, -1.0, 1, st)) != LRBMS_OK) return rc;
+  // 8: symmetric re-orthonormalisation
+  if ((rc = P.apply(P.self, K, Wb, PR, st)) != LRBMS_OK) return rc;
+  if ((rc = xty(ctx, true, S, n, K, K, Wb, PR, G, part, st)) != LRBMS_OK) return rc;
+  if ((rc = launch_pod_eigh(ctx, S, K, 1, G, ks, lam, Zs, ib, Zw, st)) != LRBMS_OK) return rc;
+  // 9: into the free columns of V
+  if ((rc = xt(ctx, S, n, K, K, Wb, K, Zs, K, V, Nw, nloc, ks, 1.0, 0, st)) != LRBMS_OK) return rc;
+  hipLaunchKernelGGL(k_pod_finish, dim3((S + 255) / 256), dim3(256), 0, st, S, (const int32_t*)ks, (const int32_t*)ia,
+                     (const int32_t*)ib, nloc, info);
+  LRBMS_LAUNCH_CHECK(ctx);
+  return LRBMS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Streamed local POD (incremental HAPOD).  Per subdomain the state carries the panels X = [B | R] and
+// PX = [PB | PR], both [n][Lx], Lx = keep + cmax: columns < kb hold the carried modes scaled by their singular values, the columns
+// from keep on the deflated chunk of the current push; everything else is zero.
+constexpr int RS_ROWS = 32;       // rows of a staged tile of the rotate kernel
+constexpr int RS_LDX = 130;       // its row length in LDS: 2 mod 32 doubles, the A operand's 16 rows x 4 k then hit every bank pair twice
+constexpr int RS_NK = POD_MAX_L / 4;      // k-steps of the MFMA at most
+
+// In place: X[s][:, :keep] = X[s] T[s], PX[s][:, :keep] = PX[s] T[s] with T [S][Lx][keep]; the columns j >= kb[s] get exact zeros.
+// A workgroup owns the rows [blockIdx.y rows_per_wg, ...) of subdomain blockIdx.x in both panels.  Wave w owns the 16 columns
+// 16 w .. 16 w + 15 of the result (keep <= 64: four waves) and keeps its slice of T, the B operand of every k-step, in registers
+// for the whole kernel; tile by tile, RS_ROWS whole rows are staged in LDS (row-major, the A operand of both row tiles), and the
+// tile's columns < keep are written only after the barrier behind its staging -- nobody else reads these rows.  33 KB of static
+// LDS: four workgroups per CU.  The sum over k runs in index order, four at a time.
+__global__ __launch_bounds__(256) void k_pod_stream_rotate(int n, int Lx, int keep, int rows_per_wg, double* X, double* PX,
+                                                           const double* __restrict__ T, const int32_t* __restrict__ kb) {
+  __shared__ double Xs[RS_ROWS * RS_LDX];
+  const int s = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, lk = lane >> 4;
+  const int K4 = (Lx + 3) & ~3, nk = K4 >> 2;
+  const int col = wave * 16 + li;
+  const bool active = wave * 16 < keep;      // wave-uniform
+  T += (long)s * Lx * keep;
+  double b[RS_NK];
+#pragma unroll
+  for (int q = 0; q < RS_NK; ++q) {
+    const int k = 4 * q + lk;
+    b[q] = (q < nk && k < Lx && col < keep) ? T[(long)k * keep + col] : 0.0;
+  }
+  int kbs = kb[s];
+  kbs = kbs < 0 ? 0 : (kbs > keep ? keep : kbs);
+  const int row_begin = blockIdx.y * rows_per_wg, row_end = min(n, row_begin + rows_per_wg);
+  const double* xa0 = Xs + li * RS_LDX + lk;
+  const double* xa1 = xa0 + 16 * RS_LDX;
+  for (int panel = 0; panel < 2; ++panel) {
+    double* A = (panel ? PX : X) + (long)s * n * Lx;
+    for (int r0 = row_begin; r0 < row_end; r0 += RS_ROWS) {
+      __syncthreads();      // the previous tile is consumed
+      for (int idx = tid; idx < RS_ROWS * K4; idx += 256) {
+        const int r = idx / K4, c = idx - r * K4;
+        Xs[r * RS_LDX + c] = (r0 + r < row_end && c < Lx) ? A[(long)(r0 + r) * Lx + c] : 0.0;
+      }
+      __syncthreads();      // every read of these rows is done: from here on they may be written
+      if (!active) continue;
+      d4 acc0 = (d4){0.0, 0.0, 0.0, 0.0}, acc1 = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int q = 0; q < RS_NK; ++q) {
+        if (q < nk) {      // uniform
+          acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(xa0[4 * q], b[q], acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(xa1[4 * q], b[q], acc1, 0, 0, 0);
+        }
+      }
+      if (col < keep) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = r0 + lk + 4 * r;
+          if (row < row_end) A[(long)row * Lx + col] = col < kbs ? acc0[r] : 0.0;
+          if (row + 16 < row_end) A[(long)(row + 16) * Lx + col] = col < kbs ? acc1[r] : 0.0;
+        }
+      }
+    }
+  }
+}
+
+// X[s][i][keep + j] = R[s][i][j], PX likewise from PR (R, PR [S][n][C]) for j < C, zero for C <= j < Lx - keep
+__global__ __launch_bounds__(256) void k_pod_stream_pack(int n, int C, int Lx, int keep, const double* __restrict__ R,
+                                                         const double* __restrict__ PR, double* __restrict__ X, double* __restrict__ PX) {
+  const int s = blockIdx.y, W = Lx - keep;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)n * W) return;
+  const int i = (int)(idx / W), j = (int)(idx - (long)i * W);
+  const long src = ((long)s * n + i) * C + j, dst = ((long)s * n + i) * Lx + keep + j;
+  X[dst] = j < C ? R[src] : 0.0;
+  PX[dst] = j < C ? PR[src] : 0.0;
+}
+
+// dst0[s][i][j] = src0[s][i][j], dst1 from src1, j < W: the leading columns between two row lengths
+__global__ __launch_bounds__(256) void k_pod_stream_copy(int n, int W, const double* __restrict__ src0, const double* __restrict__ src1,
+                                                         int lds_, double* __restrict__ dst0, double* __restrict__ dst1, int ldd) {
+  const int s = blockIdx.y;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)n * W) return;
+  const int i = (int)(idx / W), j = (int)(idx - (long)i * W);
+  const long a = ((long)s * n + i) * lds_ + j, b = ((long)s * n + i) * ldd + j;
+  dst0[b] = src0[a];
+  dst1[b] = src1[a];
+}
+
+// Node truncation of a push: kb = min(#{lam_j > (1e-7)^2 lam_1}, keep), lost += sum_{j >= kb} max(lam_j, 0) in index order,
+// norm0sq = max(norm0sq, that of the chunk), flags |= the eigen-solver's; T [Lx][keep]: column j = z_j for j < kb, 0 behind.
+__global__ __launch_bounds__(128) void k_pod_stream_select(int Lx, int keep, const double* __restrict__ lam, const double* __restrict__ Zs,
+                                                           const double* __restrict__ nrm, const int32_t* __restrict__ ia,
+                                                           double* __restrict__ norm0sq, double* __restrict__ lost,
+                                                           int32_t* __restrict__ kb, int32_t* __restrict__ flags, double* __restrict__ T) {
+  __shared__ int kk;
+  const int s = blockIdx.x, tid = threadIdx.x;
+  lam += (long)s * Lx;
+  Zs += (long)s * Lx * Lx;
+  T += (long)s * Lx * keep;
+  if (tid == 0) {
+    const double floor_ = POD_MIN_RTOL * POD_MIN_RTOL * lam[0];
+    int cnt = 0;
+    while (cnt < Lx && cnt < keep && lam[cnt] > 0.0 && lam[cnt] > floor_) ++cnt;      // descending; a NaN ends the count
+    double acc = 0.0;
+    for (int j = cnt; j < Lx; ++j) acc += lam[j] > 0.0 ? lam[j] : 0.0;
+    lost[s] += acc;
+    const double m = nrm[s];
+    if (m > norm0sq[s]) norm0sq[s] = m;
+    flags[s] |= ia[s];
+    kb[s] = cnt;
+    kk = cnt;
+  }
+  __syncthreads();
+  const int k = kk;
+  for (int idx = tid; idx < Lx * keep; idx += 128) {
+    const int i = idx / keep, j = idx - i * keep;
+    T[idx] = j < k ? Zs[(long)j * Lx + i] : 0.0;
+  }
+}
+
+// finish: lost_out = lost + sum_{ks <= j < keep} max(lam_j, 0), ia = flags of the pushes | that of the last eigen-solve
+__global__ void k_pod_stream_final(int S, int keep, const double* __restrict__ lam, const int32_t* __restrict__ ks,
+                                   const double* __restrict__ lost, const int32_t* __restrict__ flags, const int32_t* __restrict__ ia2,
+                                   double* __restrict__ lost_out, int32_t* __restrict__ ia) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  double acc = 0.0;
+  for (int j = ks[s] < 0 ? 0 : ks[s]; j < keep; ++j) {
+    const double l = lam[(long)s * keep + j];
+    acc += l > 0.0 ? l : 0.0;
+  }
+  lost_out[s] = lost[s] + acc;
+  ia[s] = (flags[s] | ia2[s]) & 1;
+}
+
+struct StreamBuffers {
+  // state
+  double *X, *PX, *norm0sq, *lost;
+  int32_t *kb, *flags;
+  // work
+  double *R, *PR, *X2, *X2b, *C, *G, *Zs, *Zw, *lam, *T, *nrm, *part;
+  int32_t *ks, *ia, *ib, *ia2;
+};
+
+StreamBuffers stream_buffers(int S, int n, int keep, int cmax, int Nw, double* state, double* work) {
+  const long Lx = keep + cmax, Lp = Lx + (Lx & 1), M1 = cmax > keep ? cmax : keep;
+  StreamBuffers b;
+  b.X = state;
+  b.PX = b.X + (long)S * n * Lx;
+  b.norm0sq = b.PX + (long)S * n * Lx;
+  b.lost = b.norm0sq + S;
+  b.kb = (int32_t*)(b.lost + S);
+  b.flags = b.kb + S;
+  b.R = work;
+  b.PR = b.R + (long)S * n * M1;
+  b.X2 = b.PR + (long)S * n * M1;
+  b.X2b = b.X2 + (long)S * n * keep;
+  b.C = b.X2b + (long)S * n * keep;
+  b.G = b.C + (long)S * Nw * M1;
+  b.Zs = b.G + (long)S * Lx * Lx;
+  b.Zw = b.Zs + (long)S * Lx * Lx;
+  b.lam = b.Zw + (long)S * Lp * Lp;
+  b.T = b.lam + (long)S * Lx;
+  b.nrm = b.T + (long)S * Lx * keep;
+  b.ks = (int32_t*)(b.nrm + S);      // 3 doubles = 6 int32 per subdomain, four in use
+  b.ia = b.ks + S;
+  b.ib = b.ia + S;
+  b.ia2 = b.ib + S;
+  b.part = b.nrm + 4L * S;
+  return b;
+}
+
+int stream_check(lrbms_ctx_base* ctx, int S, int n, int keep, int cmax) {
+  if (S < 1 || S > 65535 || n < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream: S in [1, 65535], n >= 1");
+  if (keep < 1 || keep > POD_MAX_NW) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream: keep must be in [1, 64]");
+  if (cmax < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream: cmax must be >= 1");
+  if (keep + cmax > POD_MAX_L) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream: keep + cmax must be <= 128");
+  return LRBMS_OK;
+}
+
 }  // namespace
+
+int64_t pod_stream_state_size(int S, int n, int keep, int cmax) {
+  const int64_t Lx = keep + cmax;
+  return (int64_t)S * (2 * (int64_t)n * Lx + 3);
+}
+
+int64_t pod_stream_work_size(int S, int n, int keep, int cmax, int Nw) {
+  const int64_t Lx = keep + cmax, Lp = Lx + (Lx & 1), M1 = cmax > keep ? cmax : keep, M = Lx > Nw ? Lx : Nw;
+  const int ns = pod_nsplit(n);
+  return (int64_t)S * (2 * (int64_t)n * M1 + 2 * (int64_t)n * keep + Nw * M1 + 2 * Lx * Lx + Lp * Lp + Lx + Lx * keep + 4 +
+                       (ns > 1 ? (int64_t)ns * M * Lx : 0));
+}
+
+int launch_pod_stream_begin(lrbms_ctx_base* ctx, int S, int n, int keep, int cmax, double* state, hipStream_t st) {
+  int rc;
+  if ((rc = stream_check(ctx, S, n, keep, cmax)) != LRBMS_OK) return rc;
+  if (!state) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_begin: null pointer");
+  LRBMS_HIP_CHECK(ctx, hipMemsetAsync(state, 0, sizeof(double) * (size_t)pod_stream_state_size(S, n, keep, cmax), st));
+  return LRBMS_OK;
+}
+
+int launch_pod_stream_push(lrbms_ctx_base* ctx, int S, int n, int keep, int cmax, int C, int Nw, int rotate_valu, PodProduct P,
+                           const double* U, const double* V, const int32_t* nloc, double* state, double* work, hipStream_t st) {
+  int rc;
+  if ((rc = stream_check(ctx, S, n, keep, cmax)) != LRBMS_OK) return rc;
+  if (C < 1 || C > cmax) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_push: the chunk width C must be in [1, cmax]");
+  if (Nw < 1 || Nw > POD_MAX_NW) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_push: the slab width Nw must be in [1, 64]");
+  if (!U || !V || !nloc || !state || !work) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_push: null pointer");
+  const int Lx = keep + cmax;
+  const StreamBuffers b = stream_buffers(S, n, keep, cmax, Nw, state, work);
+
+  // 1: the largest snapshot norm, of the undeflated chunk
+  if ((rc = P.apply(P.self, C, U, b.PR, st)) != LRBMS_OK) return rc;
+  hipLaunchKernelGGL(k_pod_norm0, dim3(S), dim3(256), 0, st, n, C, U, (const double*)b.PR, b.nrm);
+  LRBMS_LAUNCH_CHECK(ctx);
+  // 2: R = U, deflated twice against V
+  LRBMS_HIP_CHECK(ctx, hipMemcpyAsync(b.R, U, sizeof(double) * (size_t)S * n * C, hipMemcpyDeviceToDevice, st));
+  for (int pass = 0; pass < 2; ++pass) {
+    if ((rc = P.apply(P.self, C, b.R, b.PR, st)) != LRBMS_OK) return rc;
+    if ((rc = xty(ctx, false, S, n, Nw, C, V, b.PR, b.C, b.part, st)) != LRBMS_OK) return rc;
+    if ((rc = xt(ctx, S, n, Nw, C, V, Nw, b.C, C, b.R, C, nullptr, nullptr, -1.0, 1, st)) != LRBMS_OK) return rc;
+  }
+  if ((rc = P.apply(P.self, C, b.R, b.PR, st)) != LRBMS_OK) return rc;
+  // 3: X = [B | R], PX = [PB | PR], their Gram matrix and its eigenpairs
+  {
+    KScope ks(ctx, "k_pod_stream_pack", st);
+    hipLaunchKernelGGL(k_pod_stream_pack, dim3((unsigned)(((long)n * cmax + 255) / 256), S), dim3(256), 0, st, n, C, Lx, keep,
+                       (const double*)b.R, (const double*)b.PR, b.X, b.PX);
+    LRBMS_LAUNCH_CHECK(ctx);
+  }
+  if ((rc = xty(ctx, true, S, n, Lx, Lx, b.X, b.PX, b.G, b.part, st)) != LRBMS_OK) return rc;
+  if ((rc = launch_pod_eigh(ctx, S, Lx, 0, b.G, nullptr, b.lam, b.Zs, b.ia, b.Zw, st)) != LRBMS_OK) return rc;
+  // 4: the node's truncation
+  hipLaunchKernelGGL(k_pod_stream_select, dim3(S), dim3(128), 0, st, Lx, keep, (const double*)b.lam, (const double*)b.Zs,
+                     (const double*)b.nrm, (const int32_t*)b.ia, b.norm0sq, b.lost, b.kb, b.flags, b.T);
+  LRBMS_LAUNCH_CHECK(ctx);
+  // 5: B <- X T, PB <- PX T
+  if (!rotate_valu) {
+    const int tiles = (n + RS_ROWS - 1) / RS_ROWS;
+    int split = (2048 + S - 1) / S;                        // enough workgroups for the device, as few loads of T as that allows
+    split = split < tiles ? split : tiles;
+    const int rows_per_wg = ((tiles + split - 1) / split) * RS_ROWS;
+    KScope ks(ctx, "k_pod_stream_rotate", st);
+    hipLaunchKernelGGL(k_pod_stream_rotate, dim3(S, (n + rows_per_wg - 1) / rows_per_wg), dim3(256), 0, st, n, Lx, keep, rows_per_wg,
+                       b.X, b.PX, (const double*)b.T, (const int32_t*)b.kb);
+    LRBMS_LAUNCH_CHECK(ctx);
+  } else {      // the VALU route: two k_pod_xt launches into a second buffer and the copy back
+    if ((rc = xt(ctx, S, n, Lx, keep, b.X, Lx, b.T, keep, b.X2, keep, nullptr, nullptr, 1.0, 0, st)) != LRBMS_OK) return rc;
+    if ((rc = xt(ctx, S, n, Lx, keep, b.PX, Lx, b.T, keep, b.X2b, keep, nullptr, nullptr, 1.0, 0, st)) != LRBMS_OK) return rc;
+    KScope ks(ctx, "k_pod_stream_copy", st);
+    hipLaunchKernelGGL(k_pod_stream_copy, dim3((unsigned)(((long)n * keep + 255) / 256), S), dim3(256), 0, st, n, keep,
+                       (const double*)b.X2, (const double*)b.X2b, keep, b.X, b.PX, Lx);
+    LRBMS_LAUNCH_CHECK(ctx);
+  }
+  return LRBMS_OK;
+}
+
+int launch_pod_stream_finish(lrbms_ctx_base* ctx, int S, int n, int keep, int cmax, int Nw, int modes, double rtol, double atol,
+                             PodProduct P, double* V, int32_t* nloc, double* state, double* sv, int32_t* added, int32_t* info,
+                             double* lost, double* work, hipStream_t st) {
+  int rc;
+  if ((rc = stream_check(ctx, S, n, keep, cmax)) != LRBMS_OK) return rc;
+  if (Nw < 1 || Nw > POD_MAX_NW) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_finish: the slab width Nw must be in [1, 64]");
+  if (modes < 1) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_finish: modes must be >= 1");
+  if (!(rtol >= POD_MIN_RTOL))
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_finish: rtol < 1e-7: the Gram matrix squares the singular values, below 1e-7 relative they are rounding noise");
+  if (!(atol >= 0.0)) return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_finish: atol must be >= 0");
+  if (!V || !nloc || !state || !sv || !added || !info || !lost || !work)
+    return lrbms_fail(ctx, LRBMS_E_INVALID, "local_pod_stream_finish: null pointer");
+  const int Lx = keep + cmax;
+  int K = modes < keep ? modes : keep;
+  K = K < Nw ? K : Nw;
+  const StreamBuffers b = stream_buffers(S, n, keep, cmax, Nw, state, work);
+
+  // 1: B and PB side by side, their Gram matrix (diagonal up to rounding: the last push left B = X Z_k) and its eigenpairs
+  {
+    KScope ks(ctx, "k_pod_stream_copy", st);
+    hipLaunchKernelGGL(k_pod_stream_copy, dim3((unsigned)(((long)n * keep + 255) / 256), S), dim3(256), 0, st, n, keep,
+                       (const double*)b.X, (const double*)b.PX, Lx, b.R, b.PR, keep);
+    LRBMS_LAUNCH_CHECK(ctx);
+  }
+  if ((rc = xty(ctx, true, S, n, keep, keep, b.R, b.PR, b.G, b.part, st)) != LRBMS_OK) return rc;
+  if ((rc = launch_pod_eigh(ctx, S, keep, 0, b.G, nullptr, b.lam, b.Zs, b.ia2, b.Zw, st)) != LRBMS_OK) return rc;
+  // 2, 3: selection, the energy it leaves behind
+  hipLaunchKernelGGL(k_pod_select, dim3(S), dim3(128), 0, st, keep, Nw, modes, K, rtol, atol, (const double*)b.lam, (const double*)b.Zs,
+                     (const double*)b.norm0sq, (const int32_t*)nloc, sv, b.ks, added, b.T);
+  LRBMS_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(k_pod_stream_final, dim3((S + 255) / 256), dim3(256), 0, st, S, keep, (const double*)b.lam, (const int32_t*)b.ks,
+                     (const double*)b.lost, (const int32_t*)b.flags, (const int32_t*)b.ia2, lost, b.ia);
+  LRBMS_LAUNCH_CHECK(ctx);
+  // 4: W = B Z_k Sigma_k^-1 and the tail of the local POD
+  if ((rc = xt(ctx, S, n, keep, K, b.R, keep, b.T, K, b.X2, K, nullptr, nullptr, 1.0, 0, st)) != LRBMS_OK) return rc;
+  return pod_tail(ctx, S, n, Nw, K, P, V, nloc, b.X2, b.X2b, b.C, b.G, b.Zs, b.Zw, b.lam, b.ks, b.ia, b.ib, b.part, info, st);
+}
 
 int64_t pod_eigh_work_size(int batch, int L) {
   const int64_t Lp = L + (L & 1);
@@ -555,18 +872,5 @@ int launch_local_pod(lrbms_ctx_base* ctx, int S, int n, int L, int Nw, int modes
                      (const double*)norm0, (const int32_t*)nloc, sv, ks, added, T);
   LRBMS_LAUNCH_CHECK(ctx);
   if ((rc = xt(ctx, S, n, L, K, R, L, T, K, Wb, K, nullptr, nullptr, 1.0, 0, st)) != LRBMS_OK) return rc;
-  // 7: once more against V
-  if ((rc = P.apply(P.self, K, Wb, PR, st)) != LRBMS_OK) return rc;
-  if ((rc = xty(ctx, false, S, n, Nw, K, V, PR, C, part, st)) != LRBMS_OK) return rc;
-  if ((rc = xt(ctx, S, n, Nw, K, V, Nw, C, K, Wb, K, nullptr, nullptr, -1.0, 1, st)) != LRBMS_OK) return rc;
-  // 8: symmetric re-orthonormalisation
-  if ((rc = P.apply(P.self, K, Wb, PR, st)) != LRBMS_OK) return rc;
-  if ((rc = xty(ctx, true, S, n, K, K, Wb, PR, G, part, st)) != LRBMS_OK) return rc;
-  if ((rc = launch_pod_eigh(ctx, S, K, 1, G, ks, lam, Zs, ib, Zw, st)) != LRBMS_OK) return rc;
-  // 9: into the free columns of V
-  if ((rc = xt(ctx, S, n, K, K, Wb, K, Zs, K, V, Nw, nloc, ks, 1.0, 0, st)) != LRBMS_OK) return rc;
-  hipLaunchKernelGGL(k_pod_finish, dim3((S + 255) / 256), dim3(256), 0, st, S, (const int32_t*)ks, (const int32_t*)ia,
-                     (const int32_t*)ib, nloc, info);
-  LRBMS_LAUNCH_CHECK(ctx);
-  return LRBMS_OK;
+  return pod_tail(ctx, S, n, Nw, K, P, V, nloc, Wb, PR, C, G, Zs, Zw, lam, ks, ia, ib, part, info, st);
 }

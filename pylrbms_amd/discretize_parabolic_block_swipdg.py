@@ -153,7 +153,10 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         per parameter, the ``BlockVectorArray`` ``[S, n, nt + 1]`` that ``solve(mu)`` returns -- views of the call's panel
         ``[nt + 1, S, n, nmu]``, as ``rd.solve_batch`` hands out its trajectories.  ``as_snapshots=True``: one ``BlockVectorArray`` of
         ``len(mus) * nt`` vectors instead, the steps 1 .. nt of every parameter, parameter-major: the layout
-        ``extend_basis(..., method='pod')`` takes (at most 128 vectors).  ``precision`` / ``max_iter`` as in ``solve``.
+        ``extend_basis(..., method='pod')`` takes (at most 128 vectors).  ``as_snapshots='slabs'``: the list of the step slabs
+        ``U[k]``, k = 1 .. nt, of every native call instead -- contiguous views ``[S, n, nmu_call]`` of the panels, no copy and no limit:
+        what ``extend_basis(..., method='hapod')`` takes (sharded: the views ``[S, n, nt]`` of the trajectories).
+        ``precision`` / ``max_iter`` as in ``solve``.
         ``last_solve_info``: the CG iterations summed over the calls and the worst final residual ratio.  On a sharded grid it is
         the loop of ``solve``."""
         import torch
@@ -162,9 +165,11 @@ class InstationaryDuneDiscretization(DuneDiscretization):
         if not mus:
             raise ValueError('solve_batch: no parameters')
         nt = self.time_stepper.nt
-        if as_snapshots and len(mus) * nt > 128:
+        slabs = isinstance(as_snapshots, str) and as_snapshots == 'slabs'
+        if as_snapshots and not slabs and len(mus) * nt > 128:
             raise ValueError('solve_batch(as_snapshots=True): {} x {} vectors, the local POD takes at most 128'.format(len(mus), nt))
         its, rel = 0, 0.0
+        panels = []
         if eng.S_ext != eng.S:
             trajs = []
             for mu in mus:
@@ -188,7 +193,12 @@ class InstationaryDuneDiscretization(DuneDiscretization):
                                  max_iter=max_iter)
                 its, rel = its + info['iterations'], max(rel, info['relative_residual'])
                 trajs += [BlockVectorArray.view_of(U[:, :, :, m].permute(1, 2, 0), self.solution_space) for m in range(U.shape[3])]
+                panels.append(U)
         self.last_solve_info = {'iterations': its, 'relative_residual': rel}
+        if slabs:
+            if eng.S_ext != eng.S:
+                return [u.tensor[:, :, 1:] for u in trajs]
+            return [U[k] for U in panels for k in range(1, nt + 1)]
         if not as_snapshots:
             return trajs
         return BlockVectorArray(torch.cat([u.tensor[:, :, 1:] for u in trajs], dim=2).contiguous(), self.solution_space)

@@ -142,6 +142,9 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
         here a VIEW of the call's panel ``[nt + 1, S, n, nmu]`` (not contiguous; ``estimate`` makes its input contiguous, other
         consumers call ``.contiguous()``).  ``as_snapshots=True``: one contiguous tensor ``[S, n, len(mus) * nt]`` instead, the steps
         1 .. nt of every parameter, parameter-major: the slab ``extend_basis(..., method='pod')`` takes (at most 128 vectors).
+        ``as_snapshots='slabs'``: the list of the step slabs ``U[k]``, k = 1 .. nt, of every native call -- contiguous views
+        ``[S, n, nmu_call]`` of the panels, no copy and no limit: what ``extend_basis(..., method='hapod')`` takes (sharded: the views
+        ``[S, n, nt]`` of the trajectories).
         ``last_solve_info`` / ``return_info``: (CG iterations summed over the calls, worst final residual ratio).  On a sharded grid
         it is the loop of ``solve``."""
         import torch
@@ -150,9 +153,10 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
         if not mus:
             raise ValueError('solve_batch: no parameters')
         nt = self.time_stepper.nt
-        if as_snapshots and len(mus) * nt > 128:
+        slabs = isinstance(as_snapshots, str) and as_snapshots == 'slabs'
+        if as_snapshots and not slabs and len(mus) * nt > 128:
             raise ValueError('solve_batch(as_snapshots=True): {} x {} vectors, the local POD takes at most 128'.format(len(mus), nt))
-        trajs, its, rel = [], 0, 0.0
+        trajs, panels, its, rel = [], [], 0, 0.0
         if eng.S_ext != eng.S:
             for mu in mus:
                 U, info = self.solve(mu, rtol=rtol, max_iter=max_iter, return_info=True)
@@ -170,8 +174,12 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
                                  phi[m0:m0 + 64], U0=self.initial_data, rtol=rtol, max_iter=max_iter)
                 its, rel = its + info['iterations'], max(rel, info['relative_residual'])
                 trajs += [U[:, :, :, m].permute(1, 2, 0) for m in range(U.shape[3])]
+                panels.append(U)
         self.last_solve_info = (its, rel)
-        out = torch.cat([u[:, :, 1:] for u in trajs], dim=2).contiguous() if as_snapshots else trajs
+        if slabs:
+            out = [U[k] for U in panels for k in range(1, nt + 1)] if eng.S_ext == eng.S else [u[:, :, 1:] for u in trajs]
+        else:
+            out = torch.cat([u[:, :, 1:] for u in trajs], dim=2).contiguous() if as_snapshots else trajs
         return (out, self.last_solve_info) if return_info else out
 
     def solve_stationary_batch(self, mus, rtol=1e-10, max_iter=50000, return_info=False):

@@ -15,7 +15,9 @@ entries (``k_block_inverse``), so the padded unknowns stay 0 and every kernel ke
 A global ``extend_basis`` is all-or-nothing and raises ``ExtensionError`` if any block of the snapshot is numerically
 in the span of its basis.  ``extend_basis(U, method='pod', pod_modes=k)`` compresses instead: the leading POD modes of up to 128
 snapshots per subdomain in the same product, deflated against the local basis (``lrbms_local_pod``, one native call batched over
-the subdomains; ``LocalBasisSlab.extend_basis_pod``).
+the subdomains; ``LocalBasisSlab.extend_basis_pod``).  ``method='hapod'`` takes a training set of any size, e.g. the
+list ``d.solve_batch(mus, as_snapshots='slabs')``: the items are pushed one after the other through ``lrbms_local_pod_stream_*``
+(incremental HAPOD per subdomain) and ``pod_modes`` counts modes of the whole set (``extend_basis_hapod``).
 
 Incremental re-projection (``reduce(touched=...)``): the reference re-reduces everything after a round of local enrichment
 (online_enrichment.py:49-58 after reductor.py:75-78).  The projected operators of a target subdomain depend on the bases of
@@ -119,11 +121,14 @@ class LocalBasisSlab:
     def extend_basis(self, U, method='gram_schmidt', pod_modes=None):
         """Restrict a global snapshot to every subdomain and extend all local bases (the fork's ``extend_basis``;
         online_adaptive_lrbms.py:117-121); all-or-nothing: ``ExtensionError`` if a block is in the span of its basis.
-        ``method='pod'`` (pyMOR's ``extend_basis(U, method='pod', pod_modes=k)``): ``extend_basis_pod(U, modes=pod_modes)``."""
+        ``method='pod'`` (pyMOR's ``extend_basis(U, method='pod', pod_modes=k)``): ``extend_basis_pod(U, modes=pod_modes)``;
+        ``method='hapod'``: ``extend_basis_hapod(U, modes=pod_modes)``, the streamed POD of a training set of any size."""
         if method == 'pod':
             return self.extend_basis_pod(U, modes=pod_modes)
+        if method == 'hapod':
+            return self.extend_basis_hapod(U, modes=pod_modes)
         if method != 'gram_schmidt':
-            raise ValueError("extend_basis: method is 'gram_schmidt' or 'pod', not {!r}".format(method))
+            raise ValueError("extend_basis: method is 'gram_schmidt', 'pod' or 'hapod', not {!r}".format(method))
         self._gram_schmidt_extend(self._as_slab(U))
 
     # ------------------------------------------------------------------ POD extension (DESIGN.md 5.6)
@@ -219,21 +224,113 @@ class LocalBasisSlab:
             raise ExtensionError('no snapshot block extends its local basis')
         return np.concatenate([sv.cpu().numpy() for sv in svs], axis=1), total
 
+    # ------------------------------------------------------------------ streamed POD extension (HAPOD)
+    last_pod_info = None                # {'columns', 'nodes', 'lost'} of the last extend_basis_hapod
+
+    def _hapod_items(self, U):
+        """The slabs [S, n, C] of ``U`` in the order given: a trajectory / block array, a ready-made slab, or a list / iterator of
+        those.  Nothing is stacked."""
+        import collections.abc
+        import torch
+        if isinstance(U, torch.Tensor) and U.dim() == 3:
+            yield U
+        elif isinstance(U, (list, tuple, collections.abc.Iterator)):
+            for u in U:
+                yield from self._hapod_items(u)
+        else:
+            yield self._as_slab(U)
+
+    def extend_basis_hapod(self, U, modes=None, rtol=1e-6, atol=0.0, keep=64):
+        """POD extension of every local basis by a training set of ANY size (``lrbms_local_pod_stream_*``, the incremental
+        hierarchical approximate POD of Himpe, Leibner and Rave 2018, per subdomain): the items of ``U`` -- a trajectory, a block
+        array or a slab [S, n, C], or a list or iterator of those, e.g. ``d.solve_batch(mus, as_snapshots='slabs')`` -- are pushed
+        one after the other in the order given, in pieces of at most ``128 - keep`` columns, and never concatenated; per subdomain
+        at most ``keep`` scaled modes are carried from piece to piece.  At the end at most ``modes`` modes of the WHOLE set, those
+        above ``max(atol, rtol * max_j |u_j|)``, are appended as ``extend_basis_pod`` appends them (``modes=None``: as many as pass
+        and fit).  While no piece has more than ``keep`` directions above the Gram route's noise floor the result is the POD of all
+        columns whatever the chunking; in any case the squared projection error of the deflated set is at most
+        ``last_pod_info['lost']`` per subdomain.
+
+        Slab padding and cut-back, reserved columns, ``_dirty``, ``ExtensionError`` and the ``RuntimeError`` on ``info`` are those of
+        ``extend_basis_pod``.  Purely local (works on a sharded discretization as it is).  One device-to-host copy at the end is
+        the only synchronisation, however many columns were pushed.  Returns ``(sv, added)`` as NumPy arrays: the singular values
+        of the carried panel [S, keep], descending, and the number of vectors added per subdomain; ``last_pod_info`` =
+        ``{'columns', 'nodes', 'lost'}`` (columns pushed, native pushes, ``lost`` [S])."""
+        import torch
+        eng = self.d.engine
+        S = eng.S
+        keep = int(keep)
+        if not 1 <= keep <= self.POD_MAX_WIDTH:
+            raise ValueError('extend_basis_hapod: keep must be in [1, 64]')
+        if modes is not None and int(modes) < 1:
+            raise ValueError('extend_basis_hapod: modes must be >= 1')
+        if not rtol >= self.POD_MIN_RTOL:
+            raise ValueError('extend_basis_hapod: rtol < 1e-7: the Gram matrix squares the singular values, below that they are noise')
+        if not atol >= 0.0:
+            raise ValueError('extend_basis_hapod: atol must be >= 0')
+        P = self._pod_product()
+        items = self._hapod_items(U)
+        first = next(items, None)
+        if first is None:
+            raise ValueError('extend_basis_hapod: no snapshots')
+        if self._V is None:
+            self._V = eng.ctx.zeros(S, eng.t.n, 0)
+            self._nloc = np.zeros(S, dtype=np.int64)
+        width0 = self.basis_size()
+        k = keep if modes is None else min(int(modes), keep)
+        need = self._pod_width(min(int(self._nloc[:S].max()) + k, self._pod_max_width()))
+        if need > self._V.shape[2]:
+            self._V = torch.nn.functional.pad(self._V, (0, need - self._V.shape[2])).contiguous()
+
+        def cut_back():
+            top = int(self._nloc.max())
+            width = width0 if top <= width0 else self._pod_width(top)   # (nothing past the old width: the slab is as it was)
+            if self._V.shape[2] > width:                                # columns past every nloc[s] are zero
+                self._V = self._V[:, :, :width].contiguous()
+
+        try:
+            nloc = torch.as_tensor(np.ascontiguousarray(self._nloc[:S], dtype=np.int32)).to(self._V.device)
+            stream = eng.ctx.local_pod_stream(P, self._V, nloc, keep=keep, cmax=self.POD_MAX_COLUMNS - keep)
+            item = first
+            while item is not None:
+                if item.dim() != 3 or item.shape[0] != S or item.shape[1] != eng.t.n or item.shape[2] < 1:
+                    raise ValueError('extend_basis_hapod: snapshots [S = {}, n = {}, C >= 1] expected, got {}'.format(
+                        S, eng.t.n, tuple(item.shape)))
+                stream.push(item)
+                item = next(items, None)
+            sv, ai, lost = stream.finish(k, rtol, atol)
+            host = torch.cat([ai.to(sv.dtype).t(), lost[:, None], sv], dim=1).cpu().numpy()      # the one synchronisation
+            added, info = host[:, 0].astype(np.int64), host[:, 1].astype(np.int64)
+            self._nloc[:S] += added
+            self._pod_mark_dirty(np.where(added > 0)[0])
+            self.last_pod_info = {'columns': int(stream.columns), 'nodes': int(stream.nodes), 'lost': host[:, 2].copy()}
+        finally:
+            cut_back()
+        if info.any():
+            raise RuntimeError('extend_basis_hapod: the eigen-solver reported info != 0 on local subdomains {}'.format(
+                np.where(info != 0)[0].tolist()))
+        if added.sum() == 0:
+            raise ExtensionError('no snapshot block extends its local basis')
+        return host[:, 3:].copy(), added
+
     def _extend_basis_trajectory(self, U, max_vectors=None, method='gram_schmidt', pod_modes=None):
         """``extend_basis`` of the parabolic reductors: the vectors of a trajectory are Gram-Schmidt-ed into the local bases one
         after the other, a vector that is numerically in the span of a local basis is skipped for that subdomain (pyMOR
         ``gram_schmidt`` semantics), at most until the slab is ``max_vectors`` wide; ``ExtensionError`` if nothing was added.
         ``method='pod'``: the leading ``pod_modes`` POD modes of the whole trajectory instead of its first vectors
-        (``extend_basis_pod``; with ``max_vectors`` no local basis grows past it)."""
-        if method == 'pod':
+        (``extend_basis_pod``; with ``max_vectors`` no local basis grows past it); ``method='hapod'``: the same through
+        ``extend_basis_hapod``, for any number of snapshots (``U`` may be the list of ``solve_batch(mus, as_snapshots='slabs')``)."""
+        if method in ('pod', 'hapod'):
             if max_vectors is not None:
                 room = int(max_vectors) - (0 if self._nloc is None else int(self._nloc[:self.d.engine.S].max()))
                 if room < 1:
                     raise ExtensionError('no snapshot block extends its local basis')
                 pod_modes = room if pod_modes is None else min(int(pod_modes), room)
+            if method == 'hapod':
+                return self.extend_basis_hapod(U, modes=pod_modes)
             return self.extend_basis_pod(U, modes=pod_modes)
         if method != 'gram_schmidt':
-            raise ValueError("extend_basis: method is 'gram_schmidt' or 'pod', not {!r}".format(method))
+            raise ValueError("extend_basis: method is 'gram_schmidt', 'pod' or 'hapod', not {!r}".format(method))
         U = self._as_slab(U)
         added = 0
         for k in range(U.shape[2]):
