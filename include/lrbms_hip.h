@@ -722,6 +722,26 @@ int lrbms_local_correction_solve(lrbms_ctx* ctx, int32_t Q, const double* theta,
                                  const double* A_diag, const double* A_cpl, const double* D_corr, const double* b,
                                  double* work, double* corr, double rtol, int32_t max_iter, double* info, void* stream);
 
+/* The parabolic counterpart: the corrector TRAJECTORIES of nmark marked subdomains, implicit Euler with zero
+ * initial value on the same neighbourhood problems,
+ *   (M_N + dt A_N(theta)) x_{k+1} = M_N x_k + dt sum_j phi[k+1][j] b_j|_N,   k = 0 .. nt-1,   x_0 = 0,
+ * M_N the P1 element mass of lrbms_fom_implicit_euler; x_k restricted to the marked subdomain is kept.
+ *   theta [Q] host, marked [nmark] host, b_K [K][S][n], phi [nt + 1][K] device (row k = time of step k; row 0 is not read),
+ *   work (device, lrbms_local_correction_euler_work_size doubles), corr [nmark][n][nt] out, step fastest: column k - 1 = x_k.
+ * One workgroup per marked subdomain runs all nt steps; a step is a block-Jacobi PCG warm-started at x_k that stops at
+ * |r| <= rtol |rhs| or after max_iter iterations; a step whose right-hand side is exactly zero keeps x_{k+1} = x_k.  Fixed-order
+ * reductions: repeat calls give the same bits.
+ *   info (host, may be NULL) [nmark][2] = iterations summed over the steps, worst final ratio |r| / |rhs| of a step (-1: pAp <= 0,
+ *   the trajectory ended there and its later columns repeat the last state).
+ * LRBMS_E_INVALID (before any launch): nmark < 1, Q outside 1..8, K outside 1..64, nt < 1, dt <= 0, a marked index out of range, a
+ * neighbourhood that is not assembled on this rank, a neighbourhood that does not fit in LDS.  LRBMS_E_NOT_CONVERGED if any step of
+ * any neighbourhood is above rtol after max_iter.  Needs S_ext == S. */
+int64_t lrbms_local_correction_euler_work_size(lrbms_ctx* ctx, int32_t nmark);
+int lrbms_local_correction_euler(lrbms_ctx* ctx, int32_t Q, int32_t K, const double* theta, double dt, int32_t nt, int32_t nmark,
+                                 const int32_t* marked, const double* A_diag, const double* A_cpl, const double* D_corr,
+                                 const double* b_K, const double* phi, double* work, double* corr, double rtol, int32_t max_iter,
+                                 double* info, void* stream);
+
 /* -- local POD basis extension: batched method of snapshots per subdomain ---------------- */
 /* Compresses L snapshots per subdomain into at most `modes` new basis vectors, every local subdomain independently:
  *   norm0 = max_j |u_j|_P;  R = U deflated twice against V in the product P;  G = sym(R^T P R) = Z diag(lam) Z^T (cyclic

@@ -125,6 +125,9 @@ SIGNATURES = {
     'lrbms_local_correction_work_size': (c_i64, [c_vp, c_i32]),
     'lrbms_local_correction_solve': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_i32, _P_I32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
                                                     c_i32, _P_DBL, c_vp]),
+    'lrbms_local_correction_euler_work_size': (c_i64, [c_vp, c_i32]),
+    'lrbms_local_correction_euler': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_i32, _P_I32, c_vp, c_vp, c_vp, c_vp,
+                                                    c_vp, c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
     'lrbms_blockell_apply': (ctypes.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'lrbms_fom_apply': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'lrbms_gemm_tn': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp,
@@ -1299,6 +1302,30 @@ class NativeContext(ContextBase):
             self._ptr(b, (S, self.n), 'b'), c_vp(work.data_ptr()), c_vp(corr.data_ptr()), float(rtol), int(max_iter),
             _dblp(info), self._stream())
         self._check(rc, 'lrbms_local_correction_solve')
+        return corr, info
+
+    def local_correction_euler(self, theta, dt, nt, marked, A_diag, A_cpl, D_corr, b_K, phi, rtol=1e-10, max_iter=20000):
+        """The corrector trajectories of the parabolic enrichment (``lrbms_local_correction_euler``): b_K [K, S, n], phi
+        [nt + 1, K] (device) -> (corr [nmark, n, nt], step fastest: column k - 1 = x_k; info [nmark, 2] = iterations summed over the
+        steps, worst final residual ratio of a step)."""
+        Q, S, K = A_diag.shape[0], self.S, b_K.shape[0]
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        assert th.shape == (Q,)
+        mk = np.ascontiguousarray(marked, dtype=np.int32)
+        nmark, nt = int(mk.shape[0]), int(nt)
+        if phi.dim() != 2 or phi.shape[1] != K or phi.shape[0] < nt + 1:
+            raise NativeError('phi: expected [nt + 1 = {}, K = {}], got {}'.format(nt + 1, K, tuple(phi.shape)))
+        # (sizes the library refuses still reach it: the refusal is the library's)
+        work = self.empty(max(int(self.lib.lrbms_local_correction_euler_work_size(self.handle, nmark)), 1))
+        corr = self.empty(max(nmark, 1), self.n, max(nt, 1))
+        info = np.zeros((max(nmark, 1), 2))
+        rc = self.lib.lrbms_local_correction_euler(
+            self.handle, Q, K, _dblp(th), float(dt), nt, nmark, mk.ctypes.data_as(_P_I32),
+            self._ptr(A_diag, (Q, S, self.n_T, 4, 9), 'A_diag'), self._ptr(A_cpl, (Q, S, 4, self.ncf, 9), 'A_cpl'),
+            self._ptr(D_corr, (Q, S, 4, self.ncf, 9), 'D_corr'), self._ptr(b_K, (K, S, self.n), 'b_K'),
+            self._ptr(phi, tuple(phi.shape), 'phi'), c_vp(work.data_ptr()), c_vp(corr.data_ptr()), float(rtol), int(max_iter),
+            _dblp(info), self._stream())
+        self._check(rc, 'lrbms_local_correction_euler')
         return corr, info
 
     # ------------------------------------------------------------------ helpers

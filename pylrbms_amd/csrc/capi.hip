@@ -22,6 +22,11 @@ int64_t local_correction_work_size(lrbms_ctx* ctx, int nmark);
 int launch_local_correction(lrbms_ctx* ctx, int Q, const double* theta, int nmark, const int32_t* marked, const double* A_diag,
                             const double* A_cpl, const double* D_corr, const double* b, double* work, double* corr, double rtol,
                             int max_iter, double* info, hipStream_t st);
+int64_t local_correction_euler_work_size(lrbms_ctx* ctx, int nmark);
+int launch_local_correction_euler(lrbms_ctx* ctx, int Q, int K, const double* theta, double dt, int nt, int nmark,
+                                  const int32_t* marked, const double* A_diag, const double* A_cpl, const double* D_corr,
+                                  const double* bK, const double* phi, double* work, double* corr, double rtol, int max_iter,
+                                  double* info, hipStream_t st);
 int64_t fom_solve_work_size(lrbms_ctx* ctx);
 int launch_fom_solve(lrbms_ctx* ctx, int Q, const double* theta, const double* A_diag, const double* A_cpl, const double* b,
                      double* work, double* x, double rtol, int max_iter, double* info, hipStream_t st);
@@ -967,6 +972,21 @@ int lrbms_local_correction_solve(lrbms_ctx* ctx, int32_t Q, const double* theta,
   CHECK_PTR(ctx, A_cpl); CHECK_PTR(ctx, D_corr); CHECK_PTR(ctx, b); CHECK_PTR(ctx, work); CHECK_PTR(ctx, corr);
   return launch_local_correction(ctx, Q, theta, nmark, marked, A_diag, A_cpl, D_corr, b, work, corr, rtol, max_iter, info,
                                  (hipStream_t)stream);
+}
+
+int64_t lrbms_local_correction_euler_work_size(lrbms_ctx* ctx, int32_t nmark) {
+  if (!ctx || !ctx->has_mesh || nmark < 1) return -1;
+  return local_correction_euler_work_size(ctx, nmark);
+}
+
+int lrbms_local_correction_euler(lrbms_ctx* ctx, int32_t Q, int32_t K, const double* theta, double dt, int32_t nt, int32_t nmark,
+                                 const int32_t* marked, const double* A_diag, const double* A_cpl, const double* D_corr,
+                                 const double* b_K, const double* phi, double* work, double* corr, double rtol, int32_t max_iter,
+                                 double* info, void* stream) {
+  LRBMS_REQUIRE_MESH(ctx); CHECK_PTR(ctx, theta); CHECK_PTR(ctx, marked); CHECK_PTR(ctx, A_diag); CHECK_PTR(ctx, A_cpl);
+  CHECK_PTR(ctx, D_corr); CHECK_PTR(ctx, b_K); CHECK_PTR(ctx, phi); CHECK_PTR(ctx, work); CHECK_PTR(ctx, corr);
+  return launch_local_correction_euler(ctx, Q, K, theta, dt, nt, nmark, marked, A_diag, A_cpl, D_corr, b_K, phi, work, corr, rtol,
+                                       max_iter, info, (hipStream_t)stream);
 }
 
 int lrbms_blockell_apply(lrbms_ctx* ctx, int32_t M, const double* A, const double* x, double* y, void* stream) {

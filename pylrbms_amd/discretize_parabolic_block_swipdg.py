@@ -231,6 +231,42 @@ class InstationaryDuneDiscretization(DuneDiscretization):
             return BlockVectorArray(torch.cat(cols, dim=2).contiguous(), self.solution_space)
         return DuneDiscretization.solve_batch(self, mus, inverse_options=inverse_options)
 
+    def _refuse_local_corrections(self, what):
+        """What the parabolic enrichment does not cover, refused before anything runs."""
+        import torch
+        eng = self.engine
+        if self._tv:
+            raise NotImplementedError(what + ': the diffusion coefficients depend on time (theta_q(t, mu)); the corrector kernel '
+                                      'builds its step operator M + dt A(theta) once and would have to rebuild it in every step')
+        if eng.S_ext != eng.S:
+            raise NotImplementedError(what + ': a sharded discretization (S_ext != S); the neighbourhood problems need the operator '
+                                      'blocks and load vectors of the halo subdomains on this rank')
+        if getattr(self.estimator, 'elliptic_reconstruction', False):
+            raise NotImplementedError(what + ': elliptic_reconstruction=True; the indicators that mark subdomains do not carry the '
+                                      'reconstruction terms')
+        if self.initial_data is not None and bool(torch.count_nonzero(self.initial_data.tensor)):
+            raise NotImplementedError(what + ': non-zero initial data; the corrector trajectories start at x_0 = 0')
+
+    def solve_for_local_correction_trajectories(self, subdomains, mu=None, inverse_options=None):
+        """The parabolic counterpart of ``solve_for_local_corrections``: on the neighbourhood of every subdomain of ``subdomains``
+        (all-Dirichlet outer boundary) the implicit Euler trajectory with zero initial value, the source of ``solve(mu)`` and the
+        ``nt`` steps of the time stepper, restricted to the subdomain -- all of them in ONE launch
+        (``lrbms_local_correction_euler``: one workgroup per neighbourhood runs every step).  Returns the device tensor
+        ``[len(subdomains), n, nt]`` (column k - 1 = step k); ``last_local_correction_info`` [len(subdomains), 2] = the PCG iterations
+        summed over the steps and the worst final residual ratio of a step.  ``NotImplementedError`` for time-dependent diffusion
+        coefficients, non-zero initial data, a sharded discretization and ``elliptic_reconstruction=True``."""
+        self._refuse_local_corrections('solve_for_local_correction_trajectories')
+        eng = self.engine
+        rtol, max_iter = self._solve_options(inverse_options)
+        mu = self.parse_parameter(mu)
+        nt = self.time_stepper.nt
+        marked = [eng.local.index(int(ii)) for ii in subdomains]
+        b_K = self._src['b_K'] if self._src is not None else None
+        corr, info = eng.local_corrections_euler(self.theta(mu), self.T / nt, nt, marked, self._phi_device(mu), b_K=b_K, rtol=rtol,
+                                                 max_iter=max_iter)
+        self.last_local_correction_info = info
+        return corr
+
     def _source_rows(self, mu, L):
         """The phi rows of the columns of an array of ``L`` vectors: the trajectory's rows if ``L == nt + 1``; otherwise None
         (no source: the time-derivative term reads only the nonconformity of U_{k+1} - U_k, which does not involve f)."""

@@ -448,11 +448,14 @@ class ParabolicLRBMSReductor3D(LRBMSReductor3D):
 
     extend_basis = LocalBasisSlab._extend_basis_trajectory
 
-    def enrich_local(self, subdomain, U, mu=None):
-        raise NotImplementedError('online enrichment is not built for the parabolic 3D path')
+    _NO_ENRICHMENT = ('online enrichment is not built for the parabolic 3D path: the 3D corrector solver (lrbms3_local_correction_solve, '
+                      'batched in global memory) has no time-stepping form; the 2D path has one (lrbms_local_correction_euler)')
 
-    def enrich_local_batch(self, subdomains, U, mu=None):
-        raise NotImplementedError('online enrichment is not built for the parabolic 3D path')
+    def enrich_local(self, subdomain, U, mu=None, **kwargs):
+        raise NotImplementedError(ParabolicLRBMSReductor3D._NO_ENRICHMENT)
+
+    def enrich_local_batch(self, subdomains, U, mu=None, **kwargs):
+        raise NotImplementedError(ParabolicLRBMSReductor3D._NO_ENRICHMENT)
 
     def reduce(self):
         rd = super().reduce()

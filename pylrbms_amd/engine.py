@@ -346,6 +346,22 @@ class Engine:
         return self.ctx.local_correction_solve(theta, marked, self.A_diag, self.A_cpl, self.D_corr, self.b if b is None else b,
                                                rtol=rtol, max_iter=max_iter)
 
+    def local_corrections_euler(self, theta, dt, nt, marked, phi, b_K=None, rtol=1e-10, max_iter=20000):
+        """The neighbourhood corrector TRAJECTORIES of the parabolic enrichment for the subdomains ``marked`` (local indices), implicit
+        Euler with zero initial value (``lrbms_local_correction_euler``): ``phi`` [nt + 1, K] on the device,
+        ``b_K`` [K, S, n] (default: the engine's load vector as one component) -> (corr [len(marked), n, nt], info)."""
+        if not self.assembled:
+            raise NativeError('assemble() must run before local_corrections_euler()')
+        if self.S_ext != self.S:
+            raise NotImplementedError('corrector trajectories on a sharded discretization (S_ext != S): the neighbourhood of a local '
+                                      'subdomain reaches into the halo, whose operator blocks and load vectors this rank does not hold')
+        if getattr(self, 'D_corr', None) is None:
+            self.D_corr = self.ctx.assemble_dirichlet_correction(self.lam)
+        if b_K is None:
+            b_K = self.b.reshape(1, self.S, self.t.n)
+        return self.ctx.local_correction_euler(theta, dt, nt, marked, self.A_diag, self.A_cpl, self.D_corr, b_K, phi, rtol=rtol,
+                                               max_iter=max_iter)
+
 
 # ---------------------------------------------------------------------- layout converters (host, for API / tests)
 def expand_factored_grams(grams, ncf=None):

@@ -31,7 +31,7 @@ def doerfler_marking(indicators, theta):
 class AdaptiveEnrichment:
 
     def __init__(self, grid_and_problem_data, discretization, block_space, reductor, rd, target_error,
-                 marking_doerfler_theta, marking_max_age):
+                 marking_doerfler_theta, marking_max_age, pod_modes=None):
         self.grid_and_problem_data = grid_and_problem_data
         self.discretization = discretization
         self.block_space = block_space
@@ -40,6 +40,9 @@ class AdaptiveEnrichment:
         self.target_error = target_error
         self.marking_doerfler_theta = marking_doerfler_theta
         self.marking_max_age = marking_max_age
+        # parabolic reductor: the corrector of a marked subdomain is a trajectory, compressed to at most ``pod_modes`` new vectors per
+        # round (ParabolicLRBMSReductor.enrich_local_batch; None: its default, 1).  The stationary reductor adds one vector and takes none.
+        self.pod_modes = None if pod_modes is None else int(pod_modes)
         self._incremental = 'touched' in inspect.signature(reductor.reduce).parameters
 
     def _global_indicators(self, indicators):
@@ -70,11 +73,12 @@ class AdaptiveEnrichment:
             if need > self.reductor.basis_size():
                 self.reductor.reserve(min(need, MAX_BASIS_SIZE))
             self._reserve = 0
+        extra = {} if self.pod_modes is None else {'pod_modes': self.pod_modes}
         if hasattr(self.reductor, 'enrich_local_batch'):
-            self.reductor.enrich_local_batch(mine, U, mu)
+            self.reductor.enrich_local_batch(mine, U, mu, **extra)
         else:
             for ii in mine:
-                self.reductor.enrich_local(ii, U, mu)
+                self.reductor.enrich_local(ii, U, mu, **extra)
         # re-projection (online_enrichment.py:52 calls reductor.reduce()): only the marked subdomains' bases changed, so only they
         # and their neighbours are projected again -- into the arrays of self.rd -- unless the basis slab had to grow
         if self._incremental:
@@ -90,9 +94,10 @@ class AdaptiveEnrichment:
 
     def solve(self, mu, enrichment_steps=np.inf, callback=None):
         mu = self.discretization.parse_parameter(mu)
-        # room for the vectors this loop can add (one per subdomain and round), reserved in front of the FIRST enrichment: the slab
-        # then keeps its width and every later round re-projects marked + neighbours only (zero columns change no result)
-        self._reserve = int(min(enrichment_steps, 16)) if np.isfinite(enrichment_steps) else 8
+        # room for the vectors this loop can add (one per subdomain and round; ``pod_modes`` with the parabolic reductor), reserved in
+        # front of the FIRST enrichment: the slab then keeps its width and every later round re-projects marked + neighbours only
+        # (zero columns change no result)
+        self._reserve = (int(min(enrichment_steps, 16)) if np.isfinite(enrichment_steps) else 8) * (self.pod_modes or 1)
         enrichment_step = 1
         age_count = np.ones(self.block_space.num_blocks)
         local_problem_solves = 0

@@ -163,6 +163,30 @@ class LocalBasisSlab:
             return U.contiguous()
         return self._as_slab(U).contiguous()
 
+    def _pod_call(self, Uc, k, rtol, atol):
+        """One ``local_pod`` call on the chunk ``Uc`` [S, n, L <= 128] with at most ``k`` new vectors per subdomain: pads the slab to
+        the width the call may need, runs it, adds the counts to ``_nloc`` and marks the grown subdomains dirty.  Returns
+        ``(sv, added, info)``; the device-to-host copy of the counts is the one synchronisation."""
+        import torch
+        eng = self.d.engine
+        S = eng.S
+        need = self._pod_width(min(int(self._nloc[:S].max()) + k, self._pod_max_width()))
+        if need > self._V.shape[2]:
+            self._V = torch.nn.functional.pad(self._V, (0, need - self._V.shape[2])).contiguous()
+        nloc = torch.as_tensor(np.ascontiguousarray(self._nloc[:S], dtype=np.int32)).to(self._V.device)
+        sv, ai = eng.ctx.local_pod(self._pod_product(), Uc, self._V, nloc, k, rtol, atol)
+        added, info = ai.cpu().numpy().astype(np.int64)
+        self._nloc[:S] += added
+        self._pod_mark_dirty(np.where(added > 0)[0])
+        return sv, added, info
+
+    def _pod_cut_back(self, width0):
+        """Cut the slab back to what was filled, but never below ``width0``, its width before the POD calls."""
+        top = int(self._nloc.max())
+        keep = width0 if top <= width0 else self._pod_width(top)     # (nothing past the old width: the slab is as it was)
+        if self._V.shape[2] > keep:                                  # columns past every nloc[s] are zero
+            self._V = self._V[:, :, :keep].contiguous()
+
     def extend_basis_pod(self, U, modes=None, rtol=1e-6, atol=0.0):
         """POD extension of every local basis, the batched method of snapshots per subdomain (``lrbms_local_pod`` /
         ``lrbms3_local_pod``): the snapshots are deflated against the local basis in the local product and at most ``modes`` of
@@ -179,7 +203,6 @@ class LocalBasisSlab:
         them are not touched.  One device-to-host copy of the added counts per native call is the only synchronisation.
         Returns ``(sv, added)`` as NumPy arrays: the singular values of the deflated snapshots [S, L], descending per call
         (the calls side by side), and the number of vectors added per subdomain.  ``ExtensionError`` if nothing was added."""
-        import torch
         eng = self.d.engine
         S = eng.S
         U = self._pod_slab(U)
@@ -191,7 +214,7 @@ class LocalBasisSlab:
             raise ValueError('extend_basis_pod: rtol < 1e-7: the Gram matrix squares the singular values, below that they are noise')
         if not atol >= 0.0:
             raise ValueError('extend_basis_pod: atol must be >= 0')
-        P = self._pod_product()
+        self._pod_product()                                          # (a reductor without such a product refuses here)
         if self._V is None:
             self._V = eng.ctx.zeros(S, eng.t.n, 0)
             self._nloc = np.zeros(S, dtype=np.int64)
@@ -201,23 +224,13 @@ class LocalBasisSlab:
         for c0 in range(0, U.shape[2], self.POD_MAX_COLUMNS):
             Uc = U[:, :, c0:c0 + self.POD_MAX_COLUMNS].contiguous()
             k = Uc.shape[2] if modes is None else min(int(modes), Uc.shape[2])
-            need = self._pod_width(min(int(self._nloc[:S].max()) + k, self._pod_max_width()))
-            if need > self._V.shape[2]:
-                self._V = torch.nn.functional.pad(self._V, (0, need - self._V.shape[2])).contiguous()
-            nloc = torch.as_tensor(np.ascontiguousarray(self._nloc[:S], dtype=np.int32)).to(self._V.device)
-            sv, ai = eng.ctx.local_pod(P, Uc, self._V, nloc, k, rtol, atol)
-            added, info = ai.cpu().numpy().astype(np.int64)          # the one synchronisation
-            self._nloc[:S] += added
+            sv, added, info = self._pod_call(Uc, k, rtol, atol)
             total += added
-            self._pod_mark_dirty(np.where(added > 0)[0])
             svs.append(sv)
             if info.any():
                 failed = np.where(info != 0)[0]
                 break
-        top = int(self._nloc.max())
-        keep = width0 if top <= width0 else self._pod_width(top)     # (nothing past the old width: the slab is as it was)
-        if self._V.shape[2] > keep:                                  # columns past every nloc[s] are zero
-            self._V = self._V[:, :, :keep].contiguous()
+        self._pod_cut_back(width0)
         if failed is not None:
             raise RuntimeError('extend_basis_pod: the eigen-solver reported info != 0 on local subdomains {}'.format(failed.tolist()))
         if total.sum() == 0:
@@ -945,9 +958,32 @@ class InstationaryReducedDiscretization(ReducedDiscretization):
         return out
 
     def estimate(self, U, mu=None, decompose=False):
-        if not self._tv():
-            return ReducedDiscretization.estimate(self, U, mu, decompose=decompose)
-        return self.estimate_batch([U], [mu])[0]                     # one column of lrbms_reduced_parabolic_estimate_batch_tv
+        """``(est, (local_eta_nc, local_eta_r, local_eta_df, time_residual, time_deriv_nc))``; with ``decompose=True`` a third entry
+        ``indicators [S]``, what ``AdaptiveEnrichment`` marks subdomains with (``local_indicators``)."""
+        if self._tv():
+            if decompose:
+                raise NotImplementedError('estimate(decompose=True): the diffusion coefficients depend on time (theta_q(t, mu)); '
+                                          'alpha / gamma of the local indicators would change from step to step')
+            return self.estimate_batch([U], [mu])[0]                 # one column of lrbms_reduced_parabolic_estimate_batch_tv
+        est, parts = ReducedDiscretization.estimate(self, U, mu, decompose=False)
+        if not decompose:
+            return est, parts
+        return est, parts, self.local_indicators(parts, mu)
+
+    def local_indicators(self, parts, mu):
+        """Per-subdomain indicators [S] of a parabolic estimate, from its ``parts``: per step the expression of the stationary
+        ``estimate(decompose=True)`` (estimators.py:105-109: ``2 / alpha_bar (gamma_bar nc^2 + (r + df)^2 / alpha_hat)``, the same
+        alpha / gamma and convention switches) on that step's ``(nc, r, df)`` columns, summed over the steps, plus
+        ``sum_k time_deriv_nc[s, k]^2``.  The time-stepping residual is a global ``M^-1`` norm and has no local share, so the
+        indicators do not sum to the estimate: a marking heuristic, not a bound."""
+        est = self.estimator
+        mu = self.parse_parameter(mu)
+        nc, r, df, _, time_deriv_nc = parts
+        alpha_bar = est.alpha(est.lambda_coeffs, mu, est.mu_bar)
+        gamma_bar = est.gamma(est.lambda_coeffs, mu, est.mu_bar)
+        alpha_hat = est.alpha(est.lambda_coeffs, mu, est.mu_hat)
+        elliptic = (2. / alpha_bar) * (gamma_bar * nc ** 2 + (1. / alpha_hat) * (r + df) ** 2)        # [S, nt + 1]
+        return elliptic.sum(axis=1) + (time_deriv_nc ** 2).sum(axis=1)
 
     def _local_estimates(self, U, mu):
         """With a time-dependent source: the reduced counterpart of InstationaryDuneDiscretization._local_estimates -- the
@@ -1022,6 +1058,65 @@ class ParabolicLRBMSReductor(LRBMSReductor):
     was added anywhere; ``reduce()`` returns the instationary reduced model."""
 
     extend_basis = LocalBasisSlab._extend_basis_trajectory
+
+    def enrich_local(self, subdomain, U, mu=None, pod_modes=1, rtol=1e-6):
+        """``enrich_local_batch`` for the one subdomain; ``ExtensionError`` if its basis did not grow."""
+        if not self.enrich_local_batch([subdomain], U, mu, pod_modes=pod_modes, rtol=rtol):
+            raise ExtensionError('the local corrector trajectory is (numerically) in the span of the local basis')
+
+    def enrich_local_batch(self, subdomains, U, mu=None, pod_modes=1, rtol=1e-6):
+        """Online enrichment of the parabolic reduced model.  The stationary reductor adds the ONE
+        elliptic corrector of a marked subdomain; here the corrector is a trajectory: implicit Euler on the neighbourhood of every
+        marked subdomain with the time stepping, source and parameter of ``solve(mu)``
+        (``d.solve_for_local_correction_trajectories``, all marked subdomains and all steps in one launch), compressed by the local
+        POD against the current basis in the local energy product (``lrbms_local_pod``): at most ``pod_modes`` new vectors per marked
+        subdomain, those with a singular value above ``rtol`` times the largest snapshot norm.
+
+        The trajectories are scattered into a zero slab [S, n, nt]: a zero column has an exact zero singular value, so an unmarked
+        subdomain gains nothing and its slab keeps its bits.  ``nt > 128`` runs in consecutive chunks of 128 columns as
+        ``extend_basis_pod`` does, each against the basis the previous one has grown; a later chunk sees only the subdomains
+        that have room left under ``pod_modes``.  ``U`` (the current reduced solution) is accepted and unused, as in the stationary
+        reductor.  Returns the subdomains whose basis grew (they are marked dirty for ``reduce(touched=)``); adding nothing is
+        not an error here."""
+        import torch
+        subdomains = [int(ii) for ii in subdomains]
+        if not subdomains:
+            return []
+        if int(pod_modes) < 1:
+            raise ValueError('enrich_local_batch: pod_modes must be >= 1')
+        if not rtol >= self.POD_MIN_RTOL:
+            raise ValueError('enrich_local_batch: rtol < 1e-7: the Gram matrix squares the singular values, below that they are noise')
+        eng = self.d.engine
+        corr = self.d.solve_for_local_correction_trajectories(subdomains, mu, inverse_options=self.solver_options)   # [nmark, n, nt]
+        rows_host = np.array([eng.local.index(ii) for ii in subdomains], dtype=np.int64)
+        rows = torch.as_tensor(rows_host, device=corr.device)
+        slab = eng.ctx.zeros(eng.S, eng.t.n, corr.shape[2])
+        slab[rows] = corr
+        if self._V is None:
+            self._V = eng.ctx.zeros(eng.S, eng.t.n, 0)
+            self._nloc = np.zeros(eng.S, dtype=np.int64)
+        width0 = self.basis_size()
+        gained = np.zeros(eng.S, dtype=np.int64)
+        room = np.zeros(eng.S, dtype=np.int64)
+        room[rows_host] = int(pod_modes)
+        failed = None
+        for c0 in range(0, slab.shape[2], self.POD_MAX_COLUMNS):
+            room_c = room.copy()                                                      # the room at the start of this chunk
+            for k in sorted(set(int(v) for v in room_c[room_c > 0]), reverse=True):   # (the first chunk: one call, k = pod_modes)
+                Uc = slab[:, :, c0:c0 + self.POD_MAX_COLUMNS].clone()
+                Uc[torch.as_tensor(np.where(room_c != k)[0], device=Uc.device)] = 0.0
+                _, added, info = self._pod_call(Uc, min(k, Uc.shape[2]), rtol, 0.0)
+                gained += added
+                room -= added
+                if info.any():
+                    failed = np.where(info != 0)[0]
+                    break
+            if failed is not None:
+                break
+        self._pod_cut_back(width0)
+        if failed is not None:
+            raise RuntimeError('enrich_local_batch: the eigen-solver reported info != 0 on local subdomains {}'.format(failed.tolist()))
+        return [ii for ii, i in zip(subdomains, rows_host) if gained[i] > 0]
 
     def _reduce(self, touched=None):
         rd = super()._reduce(touched=touched)
