@@ -1286,21 +1286,26 @@ class NativeContext(ContextBase):
         self._check(rc, 'lrbms_assemble_dirichlet_correction')
         return D
 
-    def local_correction_solve(self, theta, marked, A_diag, A_cpl, D_corr, b, rtol=1e-12, max_iter=20000):
-        """marked: subdomain indices -> (corr [nmark, n], info [nmark, 2] = iterations, relative residual)."""
+    def _hood_args(self, theta, marked, A_diag, A_cpl, D_corr):
+        """What both corrector exports marshal alike: theta [Q] and marked [nmark] as host arrays, the three operator pointers after
+        their shape checks, work and the host array info.  (Sizes the library refuses still reach it: the refusal is the library's.)"""
         Q, S = A_diag.shape[0], self.S
         th = np.ascontiguousarray(theta, dtype=np.float64)
         assert th.shape == (Q,)
         mk = np.ascontiguousarray(marked, dtype=np.int32)
         nmark = int(mk.shape[0])
-        work = self.empty(int(self.lib.lrbms_local_correction_work_size(self.handle, nmark)))
-        corr = self.empty(nmark, self.n)
-        info = np.zeros((nmark, 2))
+        ops = (self._ptr(A_diag, (Q, S, self.n_T, 4, 9), 'A_diag'), self._ptr(A_cpl, (Q, S, 4, self.ncf, 9), 'A_cpl'),
+               self._ptr(D_corr, (Q, S, 4, self.ncf, 9), 'D_corr'))
+        work = self.empty(max(int(self.lib.lrbms_local_correction_work_size(self.handle, nmark)), 1))
+        return th, mk, ops, work, np.zeros((max(nmark, 1), 2))
+
+    def local_correction_solve(self, theta, marked, A_diag, A_cpl, D_corr, b, rtol=1e-12, max_iter=20000):
+        """marked: subdomain indices -> (corr [nmark, n], info [nmark, 2] = iterations, relative residual)."""
+        th, mk, ops, work, info = self._hood_args(theta, marked, A_diag, A_cpl, D_corr)
+        corr = self.empty(len(mk), self.n)
         rc = self.lib.lrbms_local_correction_solve(
-            self.handle, Q, _dblp(th), nmark, mk.ctypes.data_as(_P_I32), self._ptr(A_diag, (Q, S, self.n_T, 4, 9), 'A_diag'),
-            self._ptr(A_cpl, (Q, S, 4, self.ncf, 9), 'A_cpl'), self._ptr(D_corr, (Q, S, 4, self.ncf, 9), 'D_corr'),
-            self._ptr(b, (S, self.n), 'b'), c_vp(work.data_ptr()), c_vp(corr.data_ptr()), float(rtol), int(max_iter),
-            _dblp(info), self._stream())
+            self.handle, len(th), _dblp(th), len(mk), mk.ctypes.data_as(_P_I32), *ops, self._ptr(b, (self.S, self.n), 'b'),
+            c_vp(work.data_ptr()), c_vp(corr.data_ptr()), float(rtol), int(max_iter), _dblp(info), self._stream())
         self._check(rc, 'lrbms_local_correction_solve')
         return corr, info
 
@@ -1308,23 +1313,15 @@ class NativeContext(ContextBase):
         """The corrector trajectories of the parabolic enrichment (``lrbms_local_correction_euler``): b_K [K, S, n], phi
         [nt + 1, K] (device) -> (corr [nmark, n, nt], step fastest: column k - 1 = x_k; info [nmark, 2] = iterations summed over the
         steps, worst final residual ratio of a step)."""
-        Q, S, K = A_diag.shape[0], self.S, b_K.shape[0]
-        th = np.ascontiguousarray(theta, dtype=np.float64)
-        assert th.shape == (Q,)
-        mk = np.ascontiguousarray(marked, dtype=np.int32)
-        nmark, nt = int(mk.shape[0]), int(nt)
+        K, nt = b_K.shape[0], int(nt)
         if phi.dim() != 2 or phi.shape[1] != K or phi.shape[0] < nt + 1:
             raise NativeError('phi: expected [nt + 1 = {}, K = {}], got {}'.format(nt + 1, K, tuple(phi.shape)))
-        # (sizes the library refuses still reach it: the refusal is the library's)
-        work = self.empty(max(int(self.lib.lrbms_local_correction_euler_work_size(self.handle, nmark)), 1))
-        corr = self.empty(max(nmark, 1), self.n, max(nt, 1))
-        info = np.zeros((max(nmark, 1), 2))
+        th, mk, ops, work, info = self._hood_args(theta, marked, A_diag, A_cpl, D_corr)
+        corr = self.empty(max(len(mk), 1), self.n, max(nt, 1))
         rc = self.lib.lrbms_local_correction_euler(
-            self.handle, Q, K, _dblp(th), float(dt), nt, nmark, mk.ctypes.data_as(_P_I32),
-            self._ptr(A_diag, (Q, S, self.n_T, 4, 9), 'A_diag'), self._ptr(A_cpl, (Q, S, 4, self.ncf, 9), 'A_cpl'),
-            self._ptr(D_corr, (Q, S, 4, self.ncf, 9), 'D_corr'), self._ptr(b_K, (K, S, self.n), 'b_K'),
-            self._ptr(phi, tuple(phi.shape), 'phi'), c_vp(work.data_ptr()), c_vp(corr.data_ptr()), float(rtol), int(max_iter),
-            _dblp(info), self._stream())
+            self.handle, len(th), K, _dblp(th), float(dt), nt, len(mk), mk.ctypes.data_as(_P_I32), *ops,
+            self._ptr(b_K, (K, self.S, self.n), 'b_K'), self._ptr(phi, tuple(phi.shape), 'phi'), c_vp(work.data_ptr()),
+            c_vp(corr.data_ptr()), float(rtol), int(max_iter), _dblp(info), self._stream())
         self._check(rc, 'lrbms_local_correction_euler')
         return corr, info
 

@@ -1,6 +1,6 @@
 """The cells of tests/test_corrector_iterates_gpu.py and the corrector pieces of tests/pcg_ref.py, on the CPU.
 
-- A mirror of ``launch_local_correction`` (csrc/enrich.hip): the nel ladder, the LDS byte count of ``launch_hood`` and the 160 KB
+- A mirror of ``launch_local_correction`` (csrc/enrich.hip; the internal one both exports go through): the nel ladder, the LDS byte count of ``launch_hood`` and the 160 KB
   refusal, read from the source.  The 2D cells must reach all five instantiations of ``k_hood_pcg``, both ends of the range of
   every instantiation above <1,640>, at least two shapes above 64 KB of LDS, the largest accepted template and a refused one.
 - ``pcg_ref.hood_operator_2d`` on the oracle's blocks in the product's layouts equals the oracle's own neighbourhood system
@@ -72,6 +72,26 @@ def test_the_mirror_reads_the_ladder_of_the_source():
     for bound, ept, bt in lad:
         assert ept * bt >= bound                             # every element of the largest template of a form has a thread
     assert lds_bytes(128, 640) == 8 * (5 * 384 + 30) and not refused(1352) and refused(1360)
+
+
+def test_both_exports_reach_their_kernels_through_the_one_ladder():
+    """The ladder is in the source once, in the internal ``launch_local_correction`` that ``ladder()`` reads; every kernel launch lies
+    behind it, and each export calls that function exactly once."""
+    src = _src()
+    rungs = re.findall(r'if \(nel <= \d+\)\s*(\w+)<\d+, \d+>', src)
+    assert rungs == ['launch_hood'] * len(ladder()) and len(rungs) == 5          # no rung outside the function ladder() reads
+    assert len(re.findall(r'\blaunch_hood<', src)) == len(rungs)                 # and no instantiation beside the rungs
+    launcher = re.search(r'void launch_hood\(.*?\n}\n', src, re.S).group(0)
+    outside = src.replace(launcher, '')
+    for kernel in ('k_hood_pcg', 'k_hood_euler'):
+        assert len(re.findall(r'hipLaunchKernelGGL\(\(%s<EPT, BT>\)' % kernel, launcher)) == 1
+        assert 'hipLaunchKernelGGL((%s' % kernel not in outside and '%s<<<' % kernel not in src
+    assert src.count('const size_t lds =') == 1
+    bodies = re.findall(r'\nint launch_local_correction(?:_euler)?\(.*?\n}\n', src, re.S)
+    assert len(bodies) == 3 and 'launch_hood<' in bodies[0]                      # the shared function, then the two exports
+    for body in bodies[1:]:
+        calls = re.findall(r'\blaunch_local_correction\(', body[body.index('{'):])
+        assert len(calls) == 1 and 'launch_hood' not in body and 'hipLaunchKernelGGL' not in body and 'nel' not in body
 
 
 def test_2d_cells_reach_every_launch_form_on_both_sides():
