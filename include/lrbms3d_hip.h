@@ -566,6 +566,29 @@ int lrbms3_local_correction_solve(lrbms3_ctx* ctx, int32_t Q, const double* thet
                                   const double* A_diag, const double* A_cpl, const double* D_corr, const double* b, double* work,
                                   double* corr, double rtol, int32_t max_iter, double* info, void* stream);
 
+/* The parabolic counterpart (2D: lrbms_local_correction_euler): the corrector TRAJECTORIES of nmark marked
+ * subdomains, implicit Euler with zero initial value on the same neighbourhood problems,
+ *   (M_N + dt A_N(theta)) x_{k+1} = M_N x_k + dt sum_j phi[k+1][j] b_j|_N,   k = 0 .. nt-1,   x_0 = 0,
+ * M_N the element mass of lrbms3_fom_implicit_euler; x_k restricted to the marked subdomain is kept.
+ *   theta [Q] host, marked [nmark] host, b_K [K][S][n], phi [nt + 1][K] device (row k = time of step k; row 0 is not read; K = 1,
+ *   phi = 1: the plain load), work: lrbms3_local_correction_euler_work_size(nmark, nt) doubles, its content on entry does not
+ *   matter; corr [nmark][n][nt] out, step fastest: column k - 1 = x_k.
+ * The step operator, its element inverses and the host tables are built once per call; a step is the batched PCG of
+ * lrbms3_local_correction_solve on it, warm-started at x_k, that stops per problem at |r| <= rtol |M x_k + dt sum_j phi b_j| or after
+ * max_iter iterations of the step.  A step whose right-hand side is exactly zero, or whose first residual is within rtol, keeps
+ * x_{k+1} = x_k at 0 iterations.  Fixed-order reductions and per-problem freezing: a trajectory and its info row do not depend on
+ * what else is in the batch, on the order of marked, or on the content of work.
+ *   info (host, may be NULL) [nmark][2] = iterations summed over the steps, worst final ratio of a step.
+ * LRBMS_E_INVALID (before any launch): the refusals of lrbms3_local_correction_solve, K outside 1..64, nt < 1, dt <= 0, b_K or phi
+ * NULL.  LRBMS_E_NOT_CONVERGED (message naming the first such subdomain and its step) if a step of a problem is above rtol after
+ * max_iter or hit p.Ap <= 0: that trajectory ends there, the column of the step holds the iterate as it stands and the later
+ * columns repeat it; the other problems run on, corr and info are filled. */
+int64_t lrbms3_local_correction_euler_work_size(lrbms3_ctx* ctx, int32_t nmark, int32_t nt);
+int lrbms3_local_correction_euler(lrbms3_ctx* ctx, int32_t Q, int32_t K, const double* theta, double dt, int32_t nt, int32_t nmark,
+                                  const int32_t* marked, const double* A_diag, const double* A_cpl, const double* D_corr,
+                                  const double* b_K, const double* phi, double* work, double* corr, double rtol, int32_t max_iter,
+                                  double* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

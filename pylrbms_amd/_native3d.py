@@ -106,6 +106,10 @@ SIGNATURES3 = {
     'lrbms3_local_correction_work_size': (c_i64, [c_vp, c_i32]),
     'lrbms3_local_correction_solve': (ctypes.c_int, [c_vp, c_i32, _P_DBL, c_i32, _P_I32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_i32,
                                                      _P_DBL, c_vp]),
+    # corrector trajectories
+    'lrbms3_local_correction_euler_work_size': (c_i64, [c_vp, c_i32, c_i32]),
+    'lrbms3_local_correction_euler': (ctypes.c_int, [c_vp, c_i32, c_i32, _P_DBL, c_dbl, c_i32, c_i32, _P_I32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                     c_vp, c_vp, c_dbl, c_i32, _P_DBL, c_vp]),
     # local POD basis extension
     'lrbms3_local_pod_work_size': (c_i64, [c_vp, c_i32, c_i32]),
     'lrbms3_local_pod': (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_dbl, c_dbl] + [c_vp] * 9),
@@ -858,4 +862,34 @@ class Native3DContext(_native.ContextBase):
                                                     self._ptr(b, (self.S, self.n), 'b'), c_vp(work.data_ptr()), c_vp(corr.data_ptr()),
                                                     float(rtol), int(max_iter), info.ctypes.data_as(_P_DBL), self._stream())
         self._check(rc, 'lrbms3_local_correction_solve')
+        return corr, info
+
+    def local_correction_euler_work_size(self, nmark, nt):
+        return int(self.lib.lrbms3_local_correction_euler_work_size(self.handle, int(nmark), int(nt)))
+
+    def local_correction_euler(self, Q, theta, dt, nt, marked, A_diag, A_cpl, D_corr, b_K, phi, rtol=1e-10, max_iter=20000, work=None):
+        """The corrector trajectories of the parabolic enrichment (``lrbms3_local_correction_euler``): b_K [K, S, n],
+        phi [nt + 1, K] (host or device) -> corr [nmark, n, nt] (step fastest: column k - 1 = x_k), info [nmark, 2] (host:
+        iterations summed over the steps, worst final residual ratio of a step)."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        mk = np.ascontiguousarray(marked, dtype=np.int32).reshape(-1)
+        nmark, nt, K = int(mk.size), int(nt), int(b_K.shape[0])
+        assert th.shape == (Q,) and nmark >= 1 and nt >= 1
+        ph = self._dev2(phi, (nt + 1, K), 'phi')
+        need = self.local_correction_euler_work_size(nmark, nt)
+        if work is None:
+            work = self.empty(need)
+        elif work.numel() < need:
+            raise NativeError('work buffer too small')
+        corr = self.empty(nmark, self.n, nt)
+        info = np.zeros((nmark, 2))
+        rc = self.lib.lrbms3_local_correction_euler(self.handle, Q, K, th.ctypes.data_as(_P_DBL), float(dt), nt, nmark,
+                                                    mk.ctypes.data_as(_P_I32),
+                                                    self._ptr(A_diag, (Q, self.S, self.n_T, 5, 100), 'A_diag'),
+                                                    self._ptr(A_cpl, (Q, self.S, 6, self.ncf, 100), 'A_cpl'),
+                                                    self._ptr(D_corr, (Q, self.S, 6, self.ncf, 100), 'D_corr'),
+                                                    self._ptr(b_K, (K, self.S, self.n), 'b_K'), c_vp(ph.data_ptr()),
+                                                    c_vp(work.data_ptr()), c_vp(corr.data_ptr()), float(rtol), int(max_iter),
+                                                    info.ctypes.data_as(_P_DBL), self._stream())
+        self._check(rc, 'lrbms3_local_correction_euler')
         return corr, info

@@ -1,8 +1,8 @@
 // 3D / P2 hot path (BASELINE.json config 5) for gfx950: C ABI of include/lrbms3d_hip.h.  This file holds the context and the
 // mesh upload, the offline assembly, the pass, the estimator and the full-order solvers with their parabolic side.  The reduced
 // solvers live in online3d.hip, affine sources in sources3d.hip and online enrichment in enrich3d.hip, with lrbms3d_dev.h between
-// the four files.  Other files call launch_fom_block_inverse and launch_reduce1 of this file, and dense_spd_inverse: this file
-// owns the rocBLAS handle of the context.
+// the four files.  Other files call launch_fom_block_inverse, launch_fom_add_mass and launch_reduce1 of this file, and
+// dense_spd_inverse: this file owns the rocBLAS handle of the context.
 //
 // Kuhn triangulation: every element is a translate of one of six reference tetrahedra, so every local integral is a
 // contraction of coefficient samples with a reference table (pylrbms_amd/grid3d.py builds the tables on the host, once):
@@ -3958,6 +3958,15 @@ int ensure_tm_inverse(lrbms3_ctx* ctx, hipStream_t st) {
 }
 
 }  // namespace
+
+namespace lrbms3 {
+
+void launch_fom_add_mass(hipStream_t st, const T3& t, double* Amu) {
+  const long total = (long)t.S * t.nT * 100;
+  hipLaunchKernelGGL(k3p_fom_add_mass, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, t, total, Amu);
+}
+
+}  // namespace lrbms3
 
 extern "C" {
 

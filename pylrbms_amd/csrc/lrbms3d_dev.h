@@ -137,6 +137,8 @@ void launch_combine(hipStream_t st, long per_q, int Q, const QV& th, const doubl
 void launch_axpy(hipStream_t st, long total, const double* x, double* y);                                            // k3p_axpy
 // lrbms3d.hip, called by enrich3d.hip
 void launch_fom_block_inverse(hipStream_t st, const T3& t, const double* Amu, double* Dinv);                         // k3f_block_inverse
+// lrbms3d.hip, called by enrich3d.hip (the corrector trajectories): slot 0 of Amu [S][n_T][5][100] += the element mass
+void launch_fom_add_mass(hipStream_t st, const T3& t, double* Amu);                                                  // k3p_fom_add_mass
 // lrbms3d.hip, called by online3d.hip (red_cg, red_euler_run)
 void launch_reduce1(hipStream_t st, int S, const double* part, double* out);                                         // k3_reduce1
 // lrbms3d.hip (owner of ctx->blas), called there (fom_coarse) and by online3d.hip: A^-1 of a dense SPD matrix into Id (identity on entry) by

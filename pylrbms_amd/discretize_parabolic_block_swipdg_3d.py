@@ -12,6 +12,13 @@
     u = rd.solve(mu);  rd.estimate(u, mu);  reductor.reconstruct(u)
     us = rd.solve_batch(mus);  rd.estimate_batch(us, mus, native=True)     # sweeps: 64 parameters per native call
 
+Online enrichment (2D: 5.3.1) is opt-in, as on the elliptic 3D path: ``discretize(..., online_enrichment=True)``
+also assembles the corrector data.  Then
+
+    d.solve_for_local_correction_trajectories(subdomains, mu)     # [nmark, n, nt]: ONE native call (lrbms3_local_correction_euler)
+    reductor.enrich_local_batch(marked, u, mu, pod_modes=2);  rd = reductor.reduce(touched=marked)
+    est, parts, indicators = rd.estimate(u, mu, decompose=True)   # what AdaptiveEnrichment(..., pod_modes=) marks with
+
 The estimate restates ``OracleParabolic.estimate`` (oracle/parabolic.py): the elliptic terms of every vector of the trajectory,
 scaled by 2 sqrt(dt / 3); ``time_residual_k = sqrt(dt / 3 * sum_s y^T M_s^-1 y)`` with ``y = A(mu) (U_{k+1} - U_k)``;
 ``time_deriv_nc = sqrt(max(nc(dU), 0) / dt)``; ``est = |eta| + |time_residual| + |time_deriv_nc|``.
@@ -24,13 +31,17 @@ column: a single-trajectory export combines ``M + dt A`` once and has no row to 
 d/dt A != 0 the estimate is an indicator, not a proven bound.
 
 Not built (``NotImplementedError``): the elliptic-reconstruction terms (the reference's branch is ``assert False``,
-estimators.py:64), sharded discretizations (``S_ext != S``) and ``enrich_local``."""
+estimators.py:64) and sharded discretizations (``S_ext != S``); enrichment without the keyword, with diffusion coefficients of the
+time (the step operator of the corrector solver is built once per call) or with non-zero initial data."""
 import numpy as np
 
 from pylrbms_amd.discretize_elliptic_block_swipdg_3d import BlockDiscretization3D, LRBMSReductor3D, ReducedDiscretization3D
 from pylrbms_amd.discretize_parabolic_block_swipdg import ImplicitEulerTimeStepper
 from pylrbms_amd.parameters import CubicParameterSpace
-from pylrbms_amd.reductor import LocalBasisSlab
+from pylrbms_amd.reductor import ExtensionError, LocalBasisSlab
+
+_NEEDS_KEYWORD = ('online enrichment on the parabolic 3D path needs the corrector data: '
+                  'discretize(grid_and_problem_data, T, nt, online_enrichment=True)')
 
 
 def _parabolic_estimate(d, mu, dt, eta_loc, time_residual2, time_deriv_nc2, times=None):
@@ -120,6 +131,31 @@ class InstationaryDiscretization3D(BlockDiscretization3D):
         self.last_solve_info = info
         U = U.permute(1, 2, 0).contiguous()
         return (U, info) if return_info else U
+
+    def solve_for_local_correction_trajectories(self, subdomains, mu, rtol=1e-12, max_iter=20000, return_info=False):
+        """The parabolic counterpart of ``solve_for_local_corrections``: on the neighbourhood of every subdomain of ``subdomains``
+        (all-Dirichlet outer boundary) the implicit Euler trajectory with zero initial value, the source of ``solve(mu)`` and the
+        ``nt`` steps of the time stepper, restricted to the subdomain -- all of them in ONE native call
+        (``lrbms3_local_correction_euler``).  Returns the device tensor ``[len(subdomains), n, nt]`` (column k - 1 =
+        step k); ``info`` / ``last_local_correction_info`` [len(subdomains), 2] = the PCG iterations summed over the steps and the
+        worst final residual ratio of a step.  ``NotImplementedError`` (before any device work) without
+        ``discretize(..., online_enrichment=True)``, for diffusion coefficients of the time and for non-zero initial data."""
+        if not self.online_enrichment:
+            raise NotImplementedError(_NEEDS_KEYWORD)
+        if self._tv:
+            raise NotImplementedError('solve_for_local_correction_trajectories: the diffusion coefficients depend on time (a coefficient '
+                                      'c(mu, t)); the corrector solver builds its step operator M + dt A(theta) once per call and '
+                                      'would have to rebuild it in every step')
+        if self.initial_data is not None and bool((self.initial_data != 0).any()):
+            raise NotImplementedError('solve_for_local_correction_trajectories: non-zero initial data; the corrector trajectories '
+                                      'start at x_0 = 0')
+        eng, nt = self.engine, self.time_stepper.nt
+        marked = [eng.local.index(int(ii)) for ii in subdomains]
+        b_K = self._src['b_K'] if self._src is not None else eng.ops['b'].reshape(1, eng.S, eng.t.n)
+        corr, info = eng.local_corrections_euler(self.theta(mu), self.dt, nt, marked, b_K=b_K, phi=self.source_coefficients(mu),
+                                                 rtol=rtol, max_iter=max_iter)
+        self.last_local_correction_info = info
+        return (corr, info) if return_info else corr
 
     def _no_stationary(self):
         if self._tv:
@@ -353,10 +389,28 @@ class InstationaryReducedDiscretization3D(ReducedDiscretization3D):
         self.last_solve_info = info
         return (U, info) if return_info else U
 
+    def local_indicators(self, parts, mu):
+        """Per-subdomain indicators [S] of a parabolic estimate, from its ``parts`` (2D: ``InstationaryReducedDiscretization
+        .local_indicators``): per step ``2 / alpha_bar (gamma_bar nc^2 + (r + df)^2 / alpha_hat)`` on that step's columns, summed
+        over the steps, plus ``sum_k time_deriv_nc[s, k]^2``.  The time-stepping residual is a global ``M^-1`` norm and has no local
+        share: a marking heuristic, not a bound."""
+        d = self.d
+        nc, r, df, _, time_deriv_nc = parts
+        a_bar, a_hat, g_bar = d.alpha(mu, d.mu_bar), d.alpha(mu, d.mu_hat), d.gamma(mu, d.mu_bar)
+        elliptic = (2. / a_bar) * (g_bar * nc ** 2 + (1. / a_hat) * (r + df) ** 2)        # [S, nt + 1]
+        return elliptic.sum(axis=1) + (time_deriv_nc ** 2).sum(axis=1)
+
     def estimate(self, u, mu, decompose=False):
         """The five parts of ``InstationaryDiscretization3D.estimate`` for reduced coefficients u [nt + 1, S, N]: the elliptic terms
         from the batched reduced estimate (one parameter column per time step), the nc row of the same call on the differences, the
-        time residual with M_red^-1.  With diffusion coefficients of the time: one column of the ``_tv`` export."""
+        time residual with M_red^-1.  With diffusion coefficients of the time: one column of the ``_tv`` export.
+        ``decompose=True``: a third entry ``indicators [S]`` (``local_indicators``), what ``AdaptiveEnrichment`` marks with."""
+        if decompose:
+            if self.d._tv:
+                raise NotImplementedError('estimate(decompose=True): the diffusion coefficients depend on time (a coefficient c(mu, t)); '
+                                          'alpha / gamma of the local indicators would change from step to step')
+            est, parts = self.estimate(u, mu)
+            return est, parts, self.local_indicators(parts, mu)
         d = self.d
         if d._tv:
             return self.estimate_batch(u[None], [mu], decompose=decompose, native=True)[0]
@@ -444,21 +498,62 @@ class ParabolicLRBMSReductor3D(LRBMSReductor3D):
     """``ParabolicLRBMSReductor`` (2D: pylrbms_amd.reductor) for the 3D path.  ``extend_basis`` takes a trajectory [S, n, L]: its
     vectors are Gram-Schmidt-ed into the local bases one after the other, a vector that is numerically in the span of a local basis
     is skipped for that subdomain, ``ExtensionError`` if nothing was added anywhere; ``reduce()`` returns the instationary reduced
-    model; ``reconstruct(u)`` maps u [nt + 1, S, N] to [S, n, nt + 1]."""
+    model; ``reconstruct(u)`` maps u [nt + 1, S, N] to [S, n, nt + 1].
+
+    Online enrichment is opt-in.  On a discretization made with ``online_enrichment=True`` the constructor returns
+    an ``EnrichingParabolicLRBMSReductor3D``, whose ``reduce(touched=None)`` has the incremental form ``AdaptiveEnrichment`` probes
+    the signature for; this class keeps ``reduce()``, the whole re-reduction, and its ``enrich_local(_batch)`` name the keyword."""
 
     extend_basis = LocalBasisSlab._extend_basis_trajectory
 
-    _NO_ENRICHMENT = ('online enrichment is not built for the parabolic 3D path: the 3D corrector solver (lrbms3_local_correction_solve, '
-                      'batched in global memory) has no time-stepping form; the 2D path has one (lrbms_local_correction_euler)')
+    def __new__(cls, d=None, *args, **kwargs):
+        if cls is ParabolicLRBMSReductor3D and getattr(d, 'online_enrichment', False):
+            cls = EnrichingParabolicLRBMSReductor3D                  # (a subclass: __init__ runs on it with the same arguments)
+        return super().__new__(cls)
 
-    def enrich_local(self, subdomain, U, mu=None, **kwargs):
-        raise NotImplementedError(ParabolicLRBMSReductor3D._NO_ENRICHMENT)
+    def enrich_local(self, subdomain, U, mu=None, pod_modes=1, rtol=1e-6):
+        """``enrich_local_batch`` for the one subdomain; ``ExtensionError`` if its basis did not grow."""
+        d = getattr(self, 'd', None)
+        if d is None or not d.online_enrichment:
+            raise NotImplementedError(_NEEDS_KEYWORD)
+        if not self.enrich_local_batch([subdomain], U, mu, pod_modes=pod_modes, rtol=rtol):
+            raise ExtensionError('the local corrector trajectory is (numerically) in the span of the local basis')
 
-    def enrich_local_batch(self, subdomains, U, mu=None, **kwargs):
-        raise NotImplementedError(ParabolicLRBMSReductor3D._NO_ENRICHMENT)
+    def enrich_local_batch(self, subdomains, U, mu=None, pod_modes=1, rtol=1e-6):
+        """Online enrichment of the parabolic reduced model (the semantics of the 2D reductor, 5.3.1): the corrector
+        trajectories of the marked subdomains (``d.solve_for_local_correction_trajectories``, one native call) are scattered into a
+        zero slab [S, n, nt] and compressed by ``lrbms3_local_pod`` against the current bases in the local energy product: at most
+        ``pod_modes`` new vectors per marked subdomain, those with a singular value above ``rtol`` times the largest snapshot norm;
+        an unmarked subdomain keeps its bits.  The slab grows only when its free columns do not suffice, and then to an even width
+        as ``reserve`` pads (the wide-load form of the pass takes even N; at most 64 // Q); a call that gains nothing leaves the
+        width as it was, so the next ``reduce(touched=)`` stays incremental.  ``U`` is accepted and unused.  Returns the subdomains
+        whose basis grew (they are marked dirty for ``reduce(touched=)``); adding nothing is not an error here."""
+        d = getattr(self, 'd', None)
+        if d is None or not d.online_enrichment:
+            raise NotImplementedError(_NEEDS_KEYWORD)
+        subdomains = [int(ii) for ii in subdomains]
+        if not subdomains:
+            return []
+        if int(pod_modes) < 1:
+            raise ValueError('enrich_local_batch: pod_modes must be >= 1')
+        if not rtol >= self.POD_MIN_RTOL:
+            raise ValueError('enrich_local_batch: rtol < 1e-7: the Gram matrix squares the singular values, below that they are noise')
+        self._pod_product()                                          # (a reductor without such a product refuses here)
+        eng = d.engine
+        corr = d.solve_for_local_correction_trajectories(subdomains, mu)           # [nmark, n, nt]
+        rows_host = np.array([eng.local.index(ii) for ii in subdomains], dtype=np.int64)
+        width0 = self.basis_size()
+        gained = self._extend_marked_pod(rows_host, corr, pod_modes, rtol)
+        if self.basis_size() != width0:
+            self.reserve(self.basis_size())                          # the slab grew: to an even width
+        return [ii for ii, i in zip(subdomains, rows_host) if gained[i] > 0]
 
     def reduce(self):
-        rd = super().reduce()
+        rd = LRBMSReductor3D.reduce(self)
+        return self._with_mass(rd)
+
+    def _with_mass(self, rd):
+        """The instationary model of the elliptic one: the mass is projected for the whole slab (one workgroup per subdomain)."""
         M_red = self.d.engine.ctx.project_mass(self._V.contiguous())
         return InstationaryReducedDiscretization3D(self, rd.out, M_red, rd.rhs_red_K, rd.r_fd_K)
 
@@ -466,16 +561,27 @@ class ParabolicLRBMSReductor3D(LRBMSReductor3D):
         return self._torch.einsum('snj,ksj->snk', self._V, u).contiguous()
 
 
-def discretize(grid_and_problem_data, T, nt, device_index=0, elliptic_reconstruction=False):
+class EnrichingParabolicLRBMSReductor3D(ParabolicLRBMSReductor3D):
+    """The parabolic 3D reductor of a discretization made with ``online_enrichment=True`` (what ``ParabolicLRBMSReductor3D(d)`` returns
+    there): ``reduce`` takes ``touched``."""
+
+    def reduce(self, touched=None):
+        """``touched``: as ``LRBMSReductor3D.reduce`` -- only the changed subdomains and their neighbours are projected again, into
+        the arrays of the previous model; the mass is projected for the whole slab either way."""
+        return self._with_mass(LRBMSReductor3D.reduce(self, touched=touched))
+
+
+def discretize(grid_and_problem_data, T, nt, device_index=0, elliptic_reconstruction=False, online_enrichment=False):
     """``(d, data)`` of the parabolic 3D path: the elliptic 3D ``discretize`` plus ``T``, implicit Euler with ``nt`` steps, zero
-    initial data and the parameter space."""
+    initial data and the parameter space.  ``online_enrichment=True`` also assembles the corrector data (``D_corr``, as the
+    elliptic 3D ``discretize``) that ``solve_for_local_correction_trajectories`` and ``enrich_local(_batch)`` need."""
     if elliptic_reconstruction:
         raise NotImplementedError('elliptic_reconstruction: the reference never evaluates it (estimators.py:64 is assert False); '
                                   'the 3D parabolic path does not build it')
     grid = grid_and_problem_data['grid']
     if getattr(grid, 'world_size', 1) > 1:
         raise NotImplementedError('the 3D parabolic path needs all subdomains on one rank (sharded discretization: S_ext != S)')
-    d = InstationaryDiscretization3D(grid_and_problem_data, device_index=device_index)
+    d = InstationaryDiscretization3D(grid_and_problem_data, device_index=device_index, online_enrichment=online_enrichment)
     eng = d.engine
     if eng.S_ext != eng.S:
         raise NotImplementedError('the 3D parabolic path needs all subdomains on one rank (sharded discretization: S_ext != S)')

@@ -142,6 +142,19 @@ class Engine3D:
         return self.ctx.local_correction_solve(self.Q, theta, marked, self.ops['A_diag'], self.ops['A_cpl'], self.ops['D_corr'],
                                                self.ops['b'] if b is None else b, rtol=rtol, max_iter=max_iter)
 
+    def local_corrections_euler(self, theta, dt, nt, marked, b_K=None, phi=None, rtol=1e-10, max_iter=20000):
+        """The neighbourhood corrector TRAJECTORIES of the parabolic enrichment for the local subdomains ``marked``, implicit Euler
+        with zero initial value (``lrbms3_local_correction_euler``): ``b_K`` [K, S, n] (default: the assembled load
+        vector as one component), ``phi`` [nt + 1, K] host or device (default: ones) -> (corr [nmark, n, nt], info [nmark, 2])."""
+        if self.ops is None or 'D_corr' not in self.ops:
+            raise NativeError('assemble(online_enrichment=True) must run before local_corrections_euler()')
+        if b_K is None:
+            b_K = self.ops['b'].reshape(1, self.S, self.t.n)
+        if phi is None:
+            phi = np.ones((int(nt) + 1, int(b_K.shape[0])))
+        return self.ctx.local_correction_euler(self.Q, theta, dt, nt, marked, self.ops['A_diag'], self.ops['A_cpl'], self.ops['D_corr'],
+                                               b_K, phi, rtol=rtol, max_iter=max_iter)
+
     def interpolate(self, fn):
         """P2 nodal interpolant as a block DG vector [S, n] (host)."""
         x = self.t.node_coordinates()

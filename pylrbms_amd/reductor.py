@@ -187,6 +187,43 @@ class LocalBasisSlab:
         if self._V.shape[2] > keep:                                  # columns past every nloc[s] are zero
             self._V = self._V[:, :, :keep].contiguous()
 
+    def _extend_marked_pod(self, rows_host, corr, pod_modes, rtol):
+        """The POD step of the parabolic reductors' ``enrich_local_batch`` (2D and 3D): the corrector trajectories ``corr``
+        [len(rows_host), n, nt] of the local subdomains ``rows_host`` are scattered into a zero slab [S, n, nt] and compressed by
+        the local POD against the current bases, at most ``pod_modes`` new vectors per marked subdomain; chunks of 128 columns, each
+        against the basis the previous one has grown, a later chunk with only the subdomains that have room left.  Returns the
+        number of vectors gained per local subdomain [S]."""
+        import torch
+        eng = self.d.engine
+        rows = torch.as_tensor(rows_host, device=corr.device)
+        slab = eng.ctx.zeros(eng.S, eng.t.n, corr.shape[2])
+        slab[rows] = corr
+        if self._V is None:
+            self._V = eng.ctx.zeros(eng.S, eng.t.n, 0)
+            self._nloc = np.zeros(eng.S, dtype=np.int64)
+        width0 = self.basis_size()
+        gained = np.zeros(eng.S, dtype=np.int64)
+        room = np.zeros(eng.S, dtype=np.int64)
+        room[rows_host] = int(pod_modes)
+        failed = None
+        for c0 in range(0, slab.shape[2], self.POD_MAX_COLUMNS):
+            room_c = room.copy()                                                      # the room at the start of this chunk
+            for k in sorted(set(int(v) for v in room_c[room_c > 0]), reverse=True):   # (the first chunk: one call, k = pod_modes)
+                Uc = slab[:, :, c0:c0 + self.POD_MAX_COLUMNS].clone()
+                Uc[torch.as_tensor(np.where(room_c != k)[0], device=Uc.device)] = 0.0
+                _, added, info = self._pod_call(Uc, min(k, Uc.shape[2]), rtol, 0.0)
+                gained += added
+                room -= added
+                if info.any():
+                    failed = np.where(info != 0)[0]
+                    break
+            if failed is not None:
+                break
+        self._pod_cut_back(width0)
+        if failed is not None:
+            raise RuntimeError('enrich_local_batch: the eigen-solver reported info != 0 on local subdomains {}'.format(failed.tolist()))
+        return gained
+
     def extend_basis_pod(self, U, modes=None, rtol=1e-6, atol=0.0):
         """POD extension of every local basis, the batched method of snapshots per subdomain (``lrbms_local_pod`` /
         ``lrbms3_local_pod``): the snapshots are deflated against the local basis in the local product and at most ``modes`` of
@@ -1078,7 +1115,6 @@ class ParabolicLRBMSReductor(LRBMSReductor):
         that have room left under ``pod_modes``.  ``U`` (the current reduced solution) is accepted and unused, as in the stationary
         reductor.  Returns the subdomains whose basis grew (they are marked dirty for ``reduce(touched=)``); adding nothing is
         not an error here."""
-        import torch
         subdomains = [int(ii) for ii in subdomains]
         if not subdomains:
             return []
@@ -1089,33 +1125,7 @@ class ParabolicLRBMSReductor(LRBMSReductor):
         eng = self.d.engine
         corr = self.d.solve_for_local_correction_trajectories(subdomains, mu, inverse_options=self.solver_options)   # [nmark, n, nt]
         rows_host = np.array([eng.local.index(ii) for ii in subdomains], dtype=np.int64)
-        rows = torch.as_tensor(rows_host, device=corr.device)
-        slab = eng.ctx.zeros(eng.S, eng.t.n, corr.shape[2])
-        slab[rows] = corr
-        if self._V is None:
-            self._V = eng.ctx.zeros(eng.S, eng.t.n, 0)
-            self._nloc = np.zeros(eng.S, dtype=np.int64)
-        width0 = self.basis_size()
-        gained = np.zeros(eng.S, dtype=np.int64)
-        room = np.zeros(eng.S, dtype=np.int64)
-        room[rows_host] = int(pod_modes)
-        failed = None
-        for c0 in range(0, slab.shape[2], self.POD_MAX_COLUMNS):
-            room_c = room.copy()                                                      # the room at the start of this chunk
-            for k in sorted(set(int(v) for v in room_c[room_c > 0]), reverse=True):   # (the first chunk: one call, k = pod_modes)
-                Uc = slab[:, :, c0:c0 + self.POD_MAX_COLUMNS].clone()
-                Uc[torch.as_tensor(np.where(room_c != k)[0], device=Uc.device)] = 0.0
-                _, added, info = self._pod_call(Uc, min(k, Uc.shape[2]), rtol, 0.0)
-                gained += added
-                room -= added
-                if info.any():
-                    failed = np.where(info != 0)[0]
-                    break
-            if failed is not None:
-                break
-        self._pod_cut_back(width0)
-        if failed is not None:
-            raise RuntimeError('enrich_local_batch: the eigen-solver reported info != 0 on local subdomains {}'.format(failed.tolist()))
+        gained = self._extend_marked_pod(rows_host, corr, pod_modes, rtol)
         return [ii for ii, i in zip(subdomains, rows_host) if gained[i] > 0]
 
     def _reduce(self, touched=None):
